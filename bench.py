@@ -2,15 +2,18 @@
 """Benchmark of the WaveNet hot path on MI355X (BASELINE.json metric: audio samples/sec, train
 fwd+bwd and AR-generate, 4x10-layer dilated stack).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one training step of config 2 (4 blocks x 10 dilations, 32 residual / 256 skip channels,
 fp32, 8 clips x 16,384 samples per GPU, loss over the last 12,290 columns as train_audio/train.py
 does): forward, cross-entropy, backward, [RCCL all-reduce], clip + Adam.  Inputs (tokens, targets)
-are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  Besides `value` (train
-samples/s over all GPUs) the line carries the stack-forward rate, the AR-decode rate (config 4,
-N=1 only), `roofline` for the dominant kernel and `cpu_baseline` (the oracle's literal
-"Chainer-equivalent" restatement timed on this box's host cores, N=1 only).
+are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up,
+warms up, times K steps and prints `value` (train samples/s over all GPUs) and `ms_per_step`.
+--dump-outputs DIR writes what the last timed step computed (loss, updated weights, gradients) as
+DIR/<name>.npy.  --full adds the side measurements and checks: the same step in every arithmetic
+mode, the golden-loss check, the per-entry-point profile, the stack-forward rate, `roofline` for the
+dominant kernel, the AR-decode rate (config 4), config 5 and `cpu_baseline` (the oracle's literal
+"Chainer-equivalent" restatement timed on the host's cores); all but the profile at N=1 only.
 """
 import argparse
 import json
@@ -124,6 +127,18 @@ def train_step(net, x, tgt, iw):
     loss = net.head_cross_entropy(s, tgt)
     net.backprop(loss)
     return loss
+
+
+def dump_outputs(d, net, loss):
+    """What the last timed step hands its caller, as float32 .npy files in `d`: loss.npy (the step's loss), weights.npy and
+    grads.npy (every parameter after the optimiser step and its gradient of this step, concatenated in state_dict order
+    without the arenas' alignment padding)."""
+    os.makedirs(d, exist_ok=True)
+    spans = [(o, n) for _, _, o, n, _ in net._spans]
+    np.save(os.path.join(d, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    for name, arena in (("weights", net._arena), ("grads", net._grad_arena)):
+        a = arena.detach()
+        np.save(os.path.join(d, name + ".npy"), torch.cat([a[o:o + n] for o, n in spans]).cpu().numpy())
 
 
 def wide_channel_step(rank, world, steps=10, warmup=3):
@@ -266,6 +281,10 @@ def main():
     ap.add_argument("--no-wide", action="store_true", help="skip the config-5 (128/512 channels, bf16 operands) side measurement")
     ap.add_argument("--no-graph", action="store_true", help="time op-by-op launches instead of hipGraph replays")
     ap.add_argument("--wide-only", action="store_true", help="only the config-5 side measurement (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements and checks (the --no-* options trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss, updated weights and gradients as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -345,11 +364,12 @@ def main():
     spinup = max(0, 60 - args.warmup)
     # The FIRST step (seed-1234 weights, this batch) against the oracle's loss for exactly that step, committed as
     # tests/golden/cfg2_bench_step.npz (tests/golden/make_golden.py::cfg2_bench_step; N = 1 only: the fixture is rank 0's batch
-    # of a world of one).  Like golden_tokens_match for the decode: the bench checks the thing it times, before it times it.
+    # of a world of one).  Like golden_tokens_match for the decode: the bench checks the thing it times, before it times it
+    # (--full only).
     first_loss = float(step_fn().detach())
     golden = None
     gfile = os.path.join(ROOT, "tests", "golden", "cfg2_bench_step.npz")
-    if world == 1 and os.path.exists(gfile):
+    if args.full and world == 1 and os.path.exists(gfile):
         gz = np.load(gfile)
         if [int(x.sum().item()), int(tgt.sum().item())] == gz["tokens_checksum"].tolist():
             golden = float(gz["loss"])
@@ -381,32 +401,8 @@ def main():
         tt = torch.tensor([dt, wall_dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt, wall_dt = float(tt[0].item()), float(tt[1].item())
-    # ---- the same K steps launched op by op under the in-library HIP-event profiler: per-entry-point kernel time
-    # (events on the launch stream around every C-ABI call; a replayed graph has no host code to record them)
-    with _lib.profile() as prof:
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            train_step(net, x, tgt, iw)
-        torch.cuda.synchronize()
-        eager_dt = (time.perf_counter() - t0) / args.steps
-    per_step = {k: v[1] / args.steps for k, v in prof.result().items()}  # ms of each entry point per step
-    # the step plan of the timed graph (wn_plan_*: the weight-only preparation of the step in two launches)
-    step_plan = None
-    if graph is not None and getattr(graph, "_use_plan", False):
-        try:
-            net.plan_use(graph._plan)
-            step_plan = net.plan_stats()
-        except Exception as e:
-            step_plan = {"error": "%s: %s" % (type(e).__name__, e)}
-        finally:
-            net.plan_off()
-    # what ONE replayed step launches: the node counts of the same step captured once more with the hipGraph_t kept
-    graph_nodes = None
-    if graph is not None:
-        try:
-            graph_nodes = TrainStepGraph(net, x, tgt, keep_graph=True).node_counts()
-        except Exception as e:
-            graph_nodes = {"error": "%s: %s" % (type(e).__name__, e)}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net, loss)
     samples = world * B_PER_GPU * T
     value = samples / dt
 
@@ -419,7 +415,6 @@ def main():
                   "ms_per_step_wall_mean = wall clock over the K steps between barrier + synchronize brackets / K",
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": DTYPE_TEXT[_lib.get_gemm_precision()], "data": "synthetic",
-        "arith": arith_record(_lib.get_gemm_precision()),
         "gemm_mode": GEMM_MODE_TEXT[_lib.get_gemm_precision()],
         "dtype_note": "dtype names STORAGE and ACCUMULATION (fp32 tensors in HBM, fp32 MFMA accumulators); what the matrix "
                       "cores multiply is in gemm_mode; exact_fp32_ms_per_step is the same step with every contraction on "
@@ -428,19 +423,51 @@ def main():
                                "16 kHz, %d clips x 16384 samples per GPU, loss over last 12290 columns, "
                                "fwd + bwd + clip + Adam%s" % (B_PER_GPU, " + RCCL all-reduce" if world > 1 or force_dist else ""),
                    "global_batch": world * B_PER_GPU, "seq_len": T, "parallelism": "dp%d" % world},
-        "loss": float(loss.detach()),
-        "first_step_loss": first_loss, "golden_loss": golden,
-        "golden_loss_match": (abs(first_loss - golden) <= 1e-4) if golden is not None else None,
-        "golden_loss_source": "tests/golden/cfg2_bench_step.npz: the oracle's loss for this batch and the seed-1234 weights "
-                              "(bar 1e-4); `loss` is the loss after the %d optimiser steps of this run" % (spinup + args.warmup + args.steps),
+        "loss": float(loss.detach()), "first_step_loss": first_loss,
         "launch": ("hipGraph replay, one graph launch per step" + (" (fwd+bwd graph, RCCL all-reduce, optimiser graph)"
                    if world > 1 or force_dist else "")) if graph is not None else "op-by-op launches from Python",
-        "eager_ms_per_step": eager_dt * 1e3, "graph_nodes_per_step": graph_nodes,
-        "step_plan": step_plan,
-        "entry_point_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step.items(), key=lambda kv: -kv[1])},
     }
 
-    if rank == 0 and world == 1 and not force_dist and not args.no_exact_fp32:
+    if args.full:
+        # ---- the same K steps launched op by op under the in-library HIP-event profiler: per-entry-point kernel time
+        # (events on the launch stream around every C-ABI call; a replayed graph has no host code to record them)
+        with _lib.profile() as prof:
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                train_step(net, x, tgt, iw)
+            torch.cuda.synchronize()
+            eager_dt = (time.perf_counter() - t0) / args.steps
+        per_step = {k: v[1] / args.steps for k, v in prof.result().items()}  # ms of each entry point per step
+        # the step plan of the timed graph (wn_plan_*: the weight-only preparation of the step in two launches)
+        step_plan = None
+        if graph is not None and getattr(graph, "_use_plan", False):
+            try:
+                net.plan_use(graph._plan)
+                step_plan = net.plan_stats()
+            except Exception as e:
+                step_plan = {"error": "%s: %s" % (type(e).__name__, e)}
+            finally:
+                net.plan_off()
+        # what ONE replayed step launches: the node counts of the same step captured once more with the hipGraph_t kept
+        graph_nodes = None
+        if graph is not None:
+            try:
+                graph_nodes = TrainStepGraph(net, x, tgt, keep_graph=True).node_counts()
+            except Exception as e:
+                graph_nodes = {"error": "%s: %s" % (type(e).__name__, e)}
+        out.update({
+            "arith": arith_record(_lib.get_gemm_precision()),
+            "golden_loss": golden,
+            "golden_loss_match": (abs(first_loss - golden) <= 1e-4) if golden is not None else None,
+            "golden_loss_source": "tests/golden/cfg2_bench_step.npz: the oracle's loss for this batch and the seed-1234 weights "
+                                  "(bar 1e-4); `loss` is the loss after the %d optimiser steps of this run"
+                                  % (spinup + args.warmup + args.steps),
+            "eager_ms_per_step": eager_dt * 1e3, "graph_nodes_per_step": graph_nodes,
+            "step_plan": step_plan,
+            "entry_point_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step.items(), key=lambda kv: -kv[1])},
+        })
+
+    if args.full and rank == 0 and world == 1 and not force_dist and not args.no_exact_fp32:
         # ---- the SAME captured step in every shipped arithmetic mode: 10 graph replays each after 3 warm-up replays.
         # fp32 = the reference's own arithmetic (exact fp32 products); bf16x3 = fp32-accurate split products on the skip path
         # and the head, exact fp32 MFMA in the layer kernels; fp16x2 = the default (see `arith`).
@@ -473,7 +500,7 @@ def main():
                               "exact_fp32_samples_per_s": out["samples_per_s_by_mode"].get("fp32"),
                               "exact_fp32_ms_per_step": by_mode.get("fp32"),
                               "golden_loss_match": out.get("golden_loss_match")})
-    if rank == 0 and world == 1 and not force_dist:
+    if args.full and rank == 0 and world == 1 and not force_dist:
         # ---- fused residual-stack forward (the north star's roofline target) -------------------
         with torch.no_grad():
             c = net.forward_causal_block(x)

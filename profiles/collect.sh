@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence for bench.py on the GPU box (run from the repo root through gpurun):
 #   bash profiles/collect.sh <tag>          e.g. r2
-# 1. kernel trace + stats of the default bench command (graph-replayed timed region + op-by-op profiled pass)
+# 1. kernel trace + stats of the --full bench command (graph-replayed timed region + op-by-op profiled pass)
 # 2./3. PMC FETCH_SIZE and WRITE_SIZE in their own passes (--kernel-trace only, as the pool requires), op-by-op launches,
 #       config 2 (the headline) and config 5 (--wide-only) in the same passes
 # 4. PMC matrix-core pass: SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE, SQ_INSTS_VALU_MFMA_MOPS_{BF16,F16,F32}
@@ -13,9 +13,9 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-PMCARGS="--no-cpu-baseline --no-decode --no-graph --no-wide --steps 3 --warmup 1"
-WIDEARGS="--wide-only --steps 2 --warmup 1"
-timeout 480 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
+PMCARGS="--full --no-cpu-baseline --no-decode --no-graph --no-wide --steps 3 --warmup 1"
+WIDEARGS="--full --wide-only --steps 2 --warmup 1"
+timeout 480 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 for C in fetch:FETCH_SIZE write:WRITE_SIZE; do
   D=${C%%:*}; P=${C##*:}
   timeout 420 rocprofv3 --kernel-trace --pmc $P --output-format csv -d $OUT/$D -o bench -- python3 $ROOT/bench.py $PMCARGS > /dev/null 2> $OUT/$D.log

@@ -153,6 +153,35 @@ def cfg2_bench_step(probes=384):
     print("cfg2 bench step: loss %.9f" % loss)
 
 
+def cfg2_bench_step_f64(full_probes=16):
+    """The step of ``cfg2_bench_step`` through the oracle in float64, at that fixture's probes: the loss, the logits and the
+    skip sum in every channel at the first ``full_probes`` probes and their channel sums at all of them, the ReLU count and
+    every gradient tensor's L2 norm.  fp32 results move by a few 1e-6 with the summation order of the CPU's convolution
+    kernels (another CPU model, another order); float64 ones stay within ~1e-12, so this is what pins the oracle on any
+    machine (one float64 step: 15 s, 9.2 GB with 8 threads)."""
+    from wavenet_amd import data
+    z = np.load(os.path.join(OUT, "cfg2_bench_step.npz"))
+    p = R.make_params(**CFG2)
+    w = R.init_weights(p, 1234)
+    iw = R.input_width(p)
+    B, T = 8, 16384
+    tok = data.mulaw_encode(data.synthetic_waveform(B, T + 1, 16000, b0=0, Btot=B))
+    idx, tgt = tok[:, :T].astype(np.int32), tok[:, iw + 1:T + 1].astype(np.int32)
+    keep = {}
+    loss, logits, g = R.train_step_grads(p, w, idx, tgt, dtype=torch.float64, keep=keep)
+    pb, pt = z["probe_b"], z["probe_t"]
+    names = sorted(g)
+    assert names == [str(k) for k in z["grad_names"]]
+    np.savez_compressed(
+        os.path.join(OUT, "cfg2_bench_step_f64.npz"), loss=np.array(loss, np.float64),
+        logits_probes=logits[pb[:full_probes], :, 0, pt[:full_probes]],
+        skip_probes=keep["skip"][pb[:full_probes], :, 0, pt[:full_probes]],
+        logits_probe_sums=logits[pb, :, 0, pt].sum(axis=1), skip_probe_sums=keep["skip"][pb, :, 0, pt].sum(axis=1),
+        relu_live=np.array(int((keep["skip"] > 0).sum())), grad_names=np.array(names),
+        grad_l2=np.array([float(np.sqrt((g[k] ** 2).sum())) for k in names]))
+    print("cfg2 bench step, float64: loss %.15f" % loss)
+
+
 def mulaw_table():
     q = D.mulaw_quantize_pcm16(np.arange(-32768, 32768))
     np.savez_compressed(os.path.join(OUT, "mulaw_pcm16.npz"), table=q.astype(np.uint8))
@@ -160,7 +189,8 @@ def mulaw_table():
 
 if __name__ == "__main__":
     only = sys.argv[1:]
-    for fn in (kat1, cfg1_forward, cfg1_train_step, fastgen_trace, mulaw_table, cfg4_decode_trace, cfg2_bench_step):
+    for fn in (kat1, cfg1_forward, cfg1_train_step, fastgen_trace, mulaw_table, cfg4_decode_trace, cfg2_bench_step,
+               cfg2_bench_step_f64):
         if not only or fn.__name__ in only:
             fn()
     for f in sorted(os.listdir(OUT)):

@@ -253,7 +253,7 @@ def test_bench_two_ranks_on_one_gpu_runs_the_n_gt_1_branch():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-decode", "--no-wide"], env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-decode", "--no-wide"], env=env, capture_output=True, text=True,
                        timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -265,6 +265,40 @@ def test_bench_two_ranks_on_one_gpu_runs_the_n_gt_1_branch():
         assert "fwd+bwd graph" in rk["launch"], rk
     assert np.isfinite(out["loss"]) and out["value"] > 0
     assert out["config"]["global_batch"] == 16 and out["scaling"] == "weak"
+
+
+def test_bench_plain_run_dumps_its_last_step_and_repeats_bit_for_bit(tmp_path):
+    """A plain `python bench.py --dump-outputs DIR` times exactly --steps steps, prints the headline without the --full
+    records, and writes what its last timed step computed: loss.npy is the line's `loss`, weights.npy / grads.npy hold every
+    parameter after the optimiser step and its gradient (float32, state_dict order).  A second run with the same arguments
+    writes the same files bit for bit (same batch, same seed, a reproducible step), so two builds compare output for output."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n_params = FasterWaveNet(Params(R.make_params(**CFG2))).num_parameters
+    runs = []
+    for rep in range(2):
+        d = tmp_path / ("run%d" % rep)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+        for k in ("ms_per_step_by_mode", "roofline", "ar_generate", "cpu_baseline", "entry_point_ms_per_step"):
+            assert k not in out, k
+        files = {f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert sorted(files) == ["grads.npy", "loss.npy", "weights.npy"]
+        assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["loss.npy"].shape == (1,) and float(files["loss.npy"][0]) == out["loss"]
+        assert files["weights.npy"].shape == files["grads.npy"].shape == (n_params,)
+        assert np.isfinite(files["weights.npy"]).all() and np.isfinite(files["grads.npy"]).all()
+        assert np.abs(files["grads.npy"]).max() > 0
+        runs.append(files)
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
 
 
 @pytest.mark.parametrize("prec", ["fp16x2", "bf16x3", "fp32"])
@@ -365,7 +399,7 @@ def test_bench_eight_ranks_rehearsed_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-decode", "--no-wide"], env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu-baseline", "--no-decode", "--no-wide"], env=env, capture_output=True, text=True,
                        timeout=1500, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
