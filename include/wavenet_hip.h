@@ -75,10 +75,9 @@ const char* wn_last_error(void);
  * ws / ws_bytes: device scratch, at least wn_exec_workspace_bytes() for the model and batch; its contents are dead when the
  * call's kernels have run, so ONE buffer per stream serves every call on that stream (never one buffer for two streams).
  * flags (ABI 3; the library reads NO environment variable and keeps no switch of its own -- what used to be
- * WAVENET_HIP_FORCE_GENERIC / _NO_FUSED_WIDE / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here):
+ * WAVENET_HIP_FORCE_GENERIC / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here; bits 2 and 32 are unassigned):
  *   WN_EXEC_FORCE_GENERIC   every kernel of the call from the any-shape correctness path (generic_kernels.hip), fp32
- *   WN_EXEC_NO_FUSED_WIDE   the 128/128-channel bf16-operand layer forward as two launches instead of one (diagnostic)
- *   WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM, WN_EXEC_NO_MULTI_LAYER_BWD, WN_EXEC_BF16_MULTI_LAYER_BWD   see the defines
+ *   WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM, WN_EXEC_NO_MULTI_LAYER_BWD   see the defines
  * fwd_t1_min_blocks: launch size (workgroups of four 32-column tiles) from which the fused 32-channel layer forward takes its
  * one-tile-per-wave form; 0 = the library's default (512: every CU gets two to four workgroups), n > 0 = n (1 = always:
  * parity tests of that kernel at small sizes), < 0 = never.
@@ -87,7 +86,6 @@ const char* wn_last_error(void);
  * otherwise. */
 enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 3 };
 #define WN_EXEC_FORCE_GENERIC 1u
-#define WN_EXEC_NO_FUSED_WIDE 2u
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
 #define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
@@ -98,15 +96,6 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                           (V, U) rotate through three buffer pairs, the deal of tiles to waves rotates from
                                           layer to layer.  Results agree with the per-layer launches to fp32 summation order
                                           (which wave sums which tiles; ~1e-7) and are bit-reproducible from run to run */
-#define WN_EXEC_BF16_MULTI_LAYER_BWD 32u /* bf16 storage (wn16_stack_bwd): layers L-2 .. 1 of the layer backward in ONE launch
-                                            (k16_bwd_multi: the same dataflow words, k16_gate_bwd / k16_dx tile code unchanged)
-                                            instead of two launches per layer.  Same results, bit for bit.  OPT-IN: measured
-                                            equal to the per-layer launches within 1 %, and it needs every
-                                            workgroup resident -- the library falls back by itself when the static occupancy
-                                            query says they would not be.  CUs held by OTHER work at launch time are not
-                                            covered by that query: a dataflow wait that then gives up (2^18 polls) poisons
-                                            the layer's dWp with a NaN, so the gradient norm is not finite and wn_adam_step
-                                            skips the step (WaveNet.last_update_applied() == False) -- never a silent update */
 typedef struct WnExec {
     int precision;
     unsigned flags;
@@ -412,8 +401,7 @@ int wn16_stack_fwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
                    uint16_t* skip, int B, int T, int t_off, int compat_zero_prefix, void* stream);
 size_t wn16_stack_bwd_workspace_bytes(const WnStackDesc* d, int B, int T, int t_off);
 /* A15: dout must be NULL (train_audio/train.py:72 discards the stack's residual output), dskip (B,T-t_off,Cs),
- * dx (B,T,128) or NULL; fp32 gradients accumulated.  flags (ABI 4): WN_EXEC_* bits; WN_EXEC_BF16_MULTI_LAYER_BWD selects the
- * one-launch form of the layer backward (see the define). */
+ * dx (B,T,128) or NULL; fp32 gradients accumulated.  flags: unused (kept for the ABI), pass 0. */
 int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x, const uint16_t* xs, const uint16_t* z,
                    const uint16_t* dout, const uint16_t* dskip, uint16_t* dx, float* const* dWf, float* const* dWg,
                    float* const* dWp, float* const* dWs, void* ws, size_t ws_bytes, int B, int T, int t_off,

@@ -208,29 +208,24 @@ def stream_ptr() -> Optional[int]:
 
 
 GEMM_PRECISIONS = ("fp32", "bf16x3", "bf16", "fp16x2")
-WN_EXEC_FORCE_GENERIC, WN_EXEC_NO_FUSED_WIDE, WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM = 1, 2, 4, 8
+WN_EXEC_FORCE_GENERIC, WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM = 1, 4, 8
 WN_EXEC_NO_MULTI_LAYER_BWD = 16
-WN_EXEC_BF16_MULTI_LAYER_BWD = 32     # bf16 storage: the layer backward of layers L-2 .. 1 in one launch (opt-in; no faster, bit-identical)
 WN_DECODER_ONE_WORKGROUP = 64          # WnDecoderDesc.flags: wn_decoder_run on one workgroup instead of nine (other summation order: ~1e-7)
 
 
 def default_exec_flags() -> int:
     """WnExec.flags for models that do not set ``net.exec_flags`` themselves.  The library reads no environment variable
-    (ABI 3); these two diagnostic switches are host policy, read here, and travel with every call:
-    WAVENET_HIP_FORCE_GENERIC=1 (any-shape correctness kernels everywhere), WAVENET_HIP_NO_FUSED_WIDE=1."""
+    (ABI 3); these switches are host policy, read here, and travel with every call, e.g.
+    WAVENET_HIP_FORCE_GENERIC=1 (any-shape correctness kernels everywhere)."""
     f = 0
     if os.environ.get("WAVENET_HIP_FORCE_GENERIC") == "1":
         f |= WN_EXEC_FORCE_GENERIC
-    if os.environ.get("WAVENET_HIP_NO_FUSED_WIDE"):
-        f |= WN_EXEC_NO_FUSED_WIDE
     if os.environ.get("WAVENET_HIP_NO_FWD_GROUPS") == "1":
         f |= WN_EXEC_NO_FWD_GROUPS
     if os.environ.get("WAVENET_HIP_NO_PIPELINED_GEMM") == "1":
         f |= WN_EXEC_NO_PIPELINED_GEMM
     if os.environ.get("WAVENET_HIP_NO_MULTI_LAYER_BWD") == "1":
         f |= WN_EXEC_NO_MULTI_LAYER_BWD
-    if os.environ.get("WAVENET_HIP_BF16_MULTI_LAYER_BWD") == "1":
-        f |= WN_EXEC_BF16_MULTI_LAYER_BWD
     if os.environ.get("WAVENET_HIP_DECODER_ONE_WORKGROUP") == "1":
         f |= WN_DECODER_ONE_WORKGROUP
     return f

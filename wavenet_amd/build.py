@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libwavenet_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"] + \
-    os.environ.get("WAVENET_HIP_EXTRA_FLAGS", "").split()        # e.g. -DWN16_STAMPS for the in-kernel timestamps
+    os.environ.get("WAVENET_HIP_EXTRA_FLAGS", "").split()
 
 
 def _newest_header() -> float:

@@ -227,9 +227,6 @@ __device__ __forceinline__ void old_layer(const FastLds& S, const OldW& w, int l
 // zx != NULL (three-workgroup form): z also goes to the skip workgroup, every lane's value in ONE 8-byte store together with
 // the step's sequence number (flag-in-data: the reader spins on the entry itself, so no ordering between a data store and
 // a flag store is needed and the chain never waits for a store).
-#ifndef XSLEEP
-#define XSLEEP 1
-#endif
 typedef unsigned long long u64;
 __device__ __forceinline__ void xput(u64* p, float v, unsigned seq) {
     __hip_atomic_store(p, ((u64)seq << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -244,7 +241,7 @@ __device__ __forceinline__ float xget(const u64* p, unsigned seq, u64* err, bool
     u64 w = 0;
     if (dead) return 0.f;
     while ((unsigned)((w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) != seq) {
-        __builtin_amdgcn_s_sleep(XSLEEP);
+        __builtin_amdgcn_s_sleep(1);
         ++spins;
         // after a while also look at the error entry: when another workgroup has given up, this entry may never come
         if (spins > (1 << 21) || ((spins & 0xfff) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
@@ -322,12 +319,6 @@ __device__ __forceinline__ void skip_layer(const FastLds& S, const SkipW& w, int
     }
 }
 
-#ifdef WN_DECODE_STAMPS
-#define STAMP(k) do { if (tid == 0) stamps[k] = clock64(); } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
 static constexpr int kUnroll = 10;      // layers per trip of the layer loop (one block of the 4 x 10 stack)
 
 // The chain wave's walk over the layers of one step.  Layer l's weights were requested a whole layer ago (an L2 hit lands in
@@ -383,15 +374,11 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
     __syncthreads();
     FastLds S{xold, xcur, zall, aold, ready, ready + 1};
     const unsigned t4 = 4u * (tid & 127);
-#ifdef WN_DECODE_STAMPS
-    long long stamps[8];
-#endif
 
     for (int it = 0; it < nsteps; ++it) {
         const unsigned n = (unsigned)(n0 + it);
         const int token = s_tok[0], tprev = s_tok[1];
         const double u_draw = do_sample ? uniforms[it] : 0.0;      // fetched here, used after the network
-        STAMP(0);
         // every layer's x[n-d] was written at least one step ago: fetch them all now, off the layer chain
         for (int i = tid; i < nlayers * 32; i += kFT) {
             const int l = i >> 5;
@@ -407,7 +394,6 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             const ChainOff co = chain_offsets(lane);
             load_chain(w[0], P, 0, co);
             __syncthreads();
-            STAMP(1);
             const float xc0 = xcur[lane & 31];
             wait_count(S.ready_old, 1);
             const float a0 = aold[lane];
@@ -452,7 +438,6 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             hvec[2 * (tid - 128)] = act_apply(skip0, head_act);
             hvec[2 * (tid - 128) + 1] = act_apply(skip1, head_act);
         }
-        STAMP(2);
         // ---- head on the newest column: thread q owns logit q; its 256 weights stream in from L2 -------
         float v;
         {
@@ -503,11 +488,8 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             v = e * (1.f / s);
         }
         lg[tid] = v;
-#ifndef WN_DECODE_STAMPS
         if (prob_out) prob_out[(long long)it * prob_stride + tid] = v;
-#endif
         lds_barrier();
-        STAMP(3);
         if (do_sample) {
             // numpy: cdf = cumsum(float64(p)); cdf /= cdf[-1]; first index with cdf > u.  The running sum is a
             // 256-long dependent chain (9.5 k cycles); a parallel scan associates differently, so its cdf may differ
@@ -561,11 +543,6 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             s_tok[1] = token;
         }
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
-#ifdef WN_DECODE_STAMPS
-        STAMP(4);
-        if (tid == 0 && prob_out)
-            for (int k = 0; k < 4; ++k) prob_out[(long long)it * prob_stride + k] = (float)(stamps[k + 1] - stamps[k]);
-#endif
     }
     if (tid == 0) tok_ring[0] = s_tok[1];          // the token before the next one to be consumed
 }
@@ -681,9 +658,6 @@ __device__ __forceinline__ void decode_fast3_body(
         const unsigned seq = (unsigned)(it + 1);
         const int token = s_tok[0], tprev = s_tok[1];
         const double u_draw = do_sample ? uniforms[it] : 0.0;
-#ifdef WN_DEC3_STAMPS
-        long long st0 = clock64();
-#endif
         if (it == 0) {                                    // later steps: fetched during the previous step's wait (below)
             for (int i = tid; i < nlayers * 32; i += kFT) {
                 const int l = i >> 5;
@@ -731,9 +705,6 @@ __device__ __forceinline__ void decode_fast3_body(
             __syncthreads();
         }
         lds_barrier();                                    // the chain has written every x_cur
-#ifdef WN_DEC3_STAMPS
-        long long st1 = clock64();
-#endif
         for (int i = tid; i < nlayers * 32; i += kFT) {   // this step's x_cur of every layer becomes the newest ring column
             const int l = i >> 5;
             const unsigned dm = (unsigned)dmask[l];
@@ -771,9 +742,6 @@ __device__ __forceinline__ void decode_fast3_body(
 #pragma unroll
             for (int k = 0; k < kD10Skip; ++k) v += __uint_as_float((unsigned)wd[k]);
         }
-#ifdef WN_DEC3_STAMPS
-        long long st2 = clock64();
-#endif
         if (apply_softmax) {
             float m = wave_allmax(v);
             if (lane == 0) red[wv] = m;
@@ -838,20 +806,10 @@ __device__ __forceinline__ void decode_fast3_body(
             s_tok[1] = token;
         }
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
-#ifdef WN_DEC3_STAMPS
-        if (tid == 0) {
-            u64* D = X + nlayers * 64 + 8 * 256;
-            D[0] += (u64)(st1 - st0); D[1] += (u64)(st2 - st1); D[2] += (u64)(clock64() - st2); D[3] += 1;
-        }
-#endif
     }
     if (tid == 0) tok_ring[0] = s_tok[1];
 }
 
-#ifdef WN_DEC3_STAMPS
-static u64* g_dbg_decX = nullptr;        // diagnostic build only: where wn_debug_dec3_stamps finds the last launch's stamps
-static int g_dbg_decL = 0;
-#endif
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(
     const float* __restrict__ P, const float* __restrict__ Ph, const float* __restrict__ hbias,
     const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
@@ -927,9 +885,6 @@ int decode_fast_launch(const float* P, int nlayers, const float* hbias, const fl
         // the exchange entries live behind the packed weights (decode_fast_pack_floats); cleared by a kernel, in stream order
         u64* X = reinterpret_cast<u64*>(const_cast<float*>(P) + (size_t)nlayers * kLayerFloats + 256 * 256);
         const int nx = nlayers * 64 + 8 * 256 + 16;
-#ifdef WN_DEC3_STAMPS
-        g_dbg_decX = X; g_dbg_decL = nlayers;
-#endif
         hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, X, nx);
         hipLaunchKernelGGL(k_decode_fast3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, P,
                            P + (size_t)nlayers * kLayerFloats, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps,
@@ -998,9 +953,3 @@ int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up)
 
 }  // namespace wn
 
-#ifdef WN_DEC3_STAMPS
-extern "C" __attribute__((visibility("default"))) int wn_debug_dec3_stamps(unsigned long long* dst) {
-    if (!wn::g_dbg_decX) return -1;
-    return (int)hipMemcpy(dst, wn::g_dbg_decX + wn::g_dbg_decL * 64 + 8 * 256, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-}
-#endif

@@ -46,7 +46,6 @@ __device__ __forceinline__ void lb_pow2_scale(float mx, float& s, float& inv) {
 // vector-instruction issue.  One instruction per asm statement and no `volatile`: the scheduler moves them as freely as
 // any other VALU instruction (the four-instruction asm chains of an earlier attempt could not be interleaved with the
 // MFMAs and lost 5 %).
-#ifndef WN_SPLIT_C_ONLY
 __device__ __forceinline__ void lb_split16(const float (&v)[16], float s, H2Op& o) {
     typedef unsigned h2_u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -70,19 +69,6 @@ __device__ __forceinline__ void lb_split16(const float (&v)[16], float s, H2Op& 
         o.m[ks] = __builtin_bit_cast(h16x8, mp);
     }
 }
-#else
-__device__ __forceinline__ void lb_split16(const float (&v)[16], float s, H2Op& o) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xs = v[8 * ks + e] * s;
-            const _Float16 hh = (_Float16)xs;
-            o.h[ks][e] = hh;
-            o.m[ks][e] = (_Float16)(xs - (float)hh);
-        }
-}
-#endif
 
 // LDS-DMA of one 1 KB piece (global_load_lds_dwordx4: lane L's 16 bytes at `src` land at lds_dst + 16 L; lds_dst is
 // wave-uniform) as inline asm.  With the builtin, hipcc knows that LDS is written asynchronously and puts `s_waitcnt
@@ -95,18 +81,11 @@ __device__ __forceinline__ void lds_dma16(const void* src, void* lds_dst) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory", "m0");
 }
 
-#if defined(WN_SC_MODE) && WN_SC_MODE == 3
-#define WN_SC_BITS "sc0 sc1"
-#define WN_SC_AUX 17
-#else
-#define WN_SC_BITS "sc1"
-#define WN_SC_AUX 16
-#endif
 // The same request with the sc1 bit: coherent at agent scope (the line is fetched from memory, not from a possibly stale copy
 // in this XCD's L2).  For data another XCD wrote earlier in the SAME launch with st16_sc1.
 __device__ __forceinline__ void lds_dma16_sc1(const void* src, void* lds_dst) {
     const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)lds_dst);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off " WN_SC_BITS ::"v"(src), "s"(m0v) : "memory", "m0");
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" ::"v"(src), "s"(m0v) : "memory", "m0");
 }
 // One dword per lane into LDS (lane L's word at lds_dst + 4 L), sc1: a way to request words whose VALUE is needed later
 // without giving the compiler a register to wait for -- the kernel's own counted s_waitcnt covers the request.
@@ -120,7 +99,7 @@ __device__ __forceinline__ void st16_sc1(float* dst, float a, float b, float c, 
     const h2_f32x4 v = {a, b, c, d};
     // s_nop 1: the two wait states a VALU write of the data registers needs behind a store of more than 8 bytes (gfx940+);
     // hipcc's hazard recogniser does not look inside inline asm
-    asm volatile("global_store_dwordx4 %0, %1, off " WN_SC_BITS "\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
 }
 
 }  // namespace wn

@@ -182,10 +182,6 @@ __global__ __launch_bounds__(256, 2) void k_layer_bwd_p1(
 //   4. (this one) one wave per SIMD, software-pipelined: 45 us.
 // =============================================================================================
 static constexpr int kCWaves = 4;
-#ifdef WN_BWD_STAMPS
-__device__ unsigned long long g_bwd_stamps[1024 * 8];
-#define BST(v) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); } while (0)
-#endif
 static constexpr int kCWaveFloats = 8192;                       // two groups of four 4 KB slots per wave
 static constexpr int kCWFloats = 2048 + 2048 + 1024;            // Wf, Wg, Wp
 static constexpr int kCLdsBytes = (kCWFloats + kCWaves * kCWaveFloats + kCWaves * 64) * 4;   // + 256 B per wave: dataflow words (MULTI)
@@ -194,7 +190,7 @@ static constexpr int kCMaxBlocks = 256;
 #define WN_LDS_DMA16(src, dst) \
     __builtin_amdgcn_global_load_lds((src), (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
 #define WN_LDS_DMA16_SC1(src, dst) \
-    __builtin_amdgcn_global_load_lds((src), (__attribute__((address_space(3))) void*)(dst), 16, 0, WN_SC_AUX)
+    __builtin_amdgcn_global_load_lds((src), (__attribute__((address_space(3))) void*)(dst), 16, 0, 16)
 
 // ---- fp16 x 2 split products for the weight-gradient contractions (H2W) ------------------------------------------------
 // The 80 fp32 MFMAs per tile that contract over time (dWf, dWg: [da; dg] x [x[t-d]; x[t]], dWp: dout x z) are half of the
@@ -288,12 +284,6 @@ struct ChainArgs {
     int n, B, T, dz_t0;
 };
 static constexpr int kChainSyncHead = 2;
-#ifdef WN_MULTI_STAMPS
-__device__ unsigned long long g_multi_stamps[kChainMaxL + 1][256][4];     // [entry][workgroup][wave]: s_memtime when the wave finished the entry's tiles
-__device__ unsigned long long g_multi_spins[kChainMaxL + 1][256][4];      // cycles spent inside dep_wait (<< 20) | number of reloads
-__device__ unsigned long long g_multi_seg[256][4][8];                     // cycles per segment of the layer boundary, summed over entries
-#define MST(v) do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); } while (0)
-#endif
 
 // FROM_Z: the forward saved z and sigmoid only; `f` points at z and tanh is recovered as z / sigmoid (z = tanh * sigmoid was
 // rounded once in fp32, so the quotient is tanh to ~1.2e-7 relative; where sigmoid underflowed, da and dg are 0 anyway).
@@ -314,10 +304,6 @@ __device__ __forceinline__ void chain_body(
     float* lWg = dyn + 2048;
     float* lWp = dyn + 4096;
     float* wbase = dyn + kCWFloats;
-#ifdef WN_BWD_STAMPS
-    unsigned long long st_k0 = 0, st_k1 = 0, st_k2 = 0, st_k3 = 0, st_k4 = 0, st_loop_end = 0;
-    BST(st_k0);
-#endif
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
@@ -436,15 +422,9 @@ __device__ __forceinline__ void chain_body(
                          : "=v"(v) : "v"((unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned*)dep_lds + 4u * (unsigned)lane) : "memory");
         return v;
     };
-#ifdef WN_MULTI_STAMPS
-    unsigned long long dbg_spin = 0;
-#endif
     auto dep_wait = [&](int tile, unsigned v) {
         if constexpr (MULTI) {
             unsigned spins = 0;
-#ifdef WN_MULTI_STAMPS
-            unsigned long long w0; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w0) :: "memory");
-#endif
             // a word still shows an earlier entry?  Every polled value is USED before the loop can be left, and the loop's
             // condition is a scalar: with `while (ballot(v < ..))` the header's compare may be fed by the poll of the back edge,
             // so hipcc puts s_waitcnt vmcnt(0) in front of it ON EVERY PASS -- also the first, whose v came from LDS -- and
@@ -460,10 +440,6 @@ __device__ __forceinline__ void chain_body(
                     late = false;
                 }
             }
-#ifdef WN_MULTI_STAMPS
-            if (spins) { unsigned long long w1; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w1) :: "memory");
-                         dbg_spin += ((w1 - w0) << 20) | spins; }
-#endif
         }
     };
     auto publish = [&](int tile) {
@@ -1021,16 +997,8 @@ __device__ __forceinline__ void chain_body(
     if (!H2W && any) { fetch_a(first, pbase, dza); fetch_x(first, xc, xo); }
     build_images([&]() { if (any) { fetch_a(first, pbase, dza); fetch_x(first, xc, xo); } });
     __syncthreads();                                   // (also drains vmcnt: the first tile has landed)
-#ifdef WN_BWD_STAMPS
-    unsigned long long st_wait = 0, st_take = 0, st_body = 0, st_n = 0, st_t0 = 0, st_t1 = 0;
-    BST(st_k1);
-#endif
     int tile = first;
     int it = 0;
-#ifdef WN_MULTI_STAMPS
-    if constexpr (MULTI) { unsigned long long tt; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-          if (lane == 0 && blockIdx.x < 256) g_multi_stamps[0][blockIdx.x][wv] = tt; }
-#endif
     for (;;) {                                         // MULTI: one pass per layer of the launch
     if (any) {
         if (first + stride < last) {
@@ -1047,26 +1015,16 @@ __device__ __forceinline__ void chain_body(
     // 80 accumulator registers every iteration); the last tile's weight gradients follow the loop.
     it = 0;
     tile = first;
-#ifdef WN_BWD_STAMPS
-    BST(st_t0);
-#endif
     for (; tile + stride < last; tile += stride, ++it) {
         float* grp = pbase + (it & 1) * 4096;          // patches of `tile`
         float* ngrp = pbase + ((it + 1) & 1) * 4096;   // f, g, V, U of tile + stride
         // what the previous body fetched (this tile's x, the next tile's f, g, V, U, dz) has had a whole body to land;
         // its V/U stores were issued last and may stay in flight
-#ifdef WN_BWD_STAMPS
-        unsigned long long c0, c1, c2, c3;
-        BST(c0);
-#endif
         if (stores_in_flight) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (MULTI) {                             // the stores of the tile before `tile` have been counted
             if (pub < tile) { publish(pub); pub += stride; }
         }
-#ifdef WN_BWD_STAMPS
-        BST(c1);
-#endif
         WOps w;
         WOpsT wt;
         float xcw[16], xow[16];                           // this tile's x (the registers are fetched into again below)
@@ -1079,9 +1037,6 @@ __device__ __forceinline__ void chain_body(
             take(tile, grp, xc, xo, w);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the patches are in registers: their slots are free
-#ifdef WN_BWD_STAMPS
-        BST(c2);
-#endif
 #pragma unroll
         for (int q = 0; q < 4; ++q) dza[q] = dzb[q];
         if constexpr (!PL) {
@@ -1102,14 +1057,7 @@ __device__ __forceinline__ void chain_body(
         else wgrad(w);
         phase_a(tile + stride, ngrp, dza);
         stores_in_flight = store_vu(tile + stride);
-#ifdef WN_BWD_STAMPS
-        BST(c3);
-        st_wait += c1 - c0; st_take += c2 - c1; st_body += c3 - c2; ++st_n;
-#endif
     }
-#ifdef WN_BWD_STAMPS
-    BST(st_loop_end);
-#endif
     if (any) {
         if (stores_in_flight) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1138,17 +1086,9 @@ __device__ __forceinline__ void chain_body(
         // LDS (the V / U slots of group 0 and group 1: dead), one LDS-only barrier, fixed-order sum, partial tile; (4) the next
         // layer's weight images; (5) the first tile's V, U as soon as its words allow.
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef WN_MULTI_STAMPS
-        { unsigned long long tt; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-          if (lane == 0 && blockIdx.x < 256) { g_multi_stamps[li + 1][blockIdx.x][wv] = tt; g_multi_spins[li][blockIdx.x][wv] = dbg_spin; }
-          dbg_spin = 0; }
-#endif
         if (any) {
             while (pub <= tile) { publish(pub); pub += stride; }
         }
-#ifdef WN_MULTI_STAMPS
-        unsigned long long sg0, sg1, sg2, sg3, sg4, sg5; MST(sg0);
-#endif
         float* const part_done = part;
         ++li;
         set_layer(li);
@@ -1166,47 +1106,16 @@ __device__ __forceinline__ void chain_body(
         acc_to_lds(pbase + 2048);
 #pragma unroll
         for (int r = 0; r < 16; ++r) { aWf0[r] = 0.f; aWf1[r] = 0.f; aWg0[r] = 0.f; aWg1[r] = 0.f; aWp[r] = 0.f; }
-#ifdef WN_MULTI_STAMPS
-        MST(sg1);
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         sum_to_part(wbase + 2048, kCWaveFloats, part_done + (long long)blockIdx.x * kPartFloats);
-#ifdef WN_MULTI_STAMPS
-        MST(sg2);
-#endif
         build_images([]() {});
-#ifdef WN_MULTI_STAMPS
-        MST(sg3);
-#endif
         if (any) {
             dep_wait(first, dep_0);
             fetch_some(first, pbase, dza, 2, true);
         }
-#ifdef WN_MULTI_STAMPS
-        MST(sg4);
-#endif
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");    // images published, first tile landed
-#ifdef WN_MULTI_STAMPS
-        MST(sg5);
-        if (lane == 0 && blockIdx.x < 256) {
-            unsigned long long* q = g_multi_seg[blockIdx.x][wv];
-            q[0] += sg1 - sg0; q[1] += sg2 - sg1; q[2] += sg3 - sg2; q[3] += sg4 - sg3; q[4] += sg5 - sg4; q[5] += 1;
-        }
-#endif
     }
     }
-#ifdef WN_BWD_STAMPS
-    BST(st_k2);
-    {
-        st_t1 = st_loop_end;
-        const int gw = blockIdx.x * NW + wv;
-        if (lane == 0 && gw < 1024) {
-            g_bwd_stamps[gw * 8 + 0] = st_wait; g_bwd_stamps[gw * 8 + 1] = st_take; g_bwd_stamps[gw * 8 + 2] = st_body;
-            g_bwd_stamps[gw * 8 + 3] = st_n; g_bwd_stamps[gw * 8 + 4] = st_t1 - st_t0;
-            g_bwd_stamps[gw * 8 + 5] = st_k1 - st_k0; g_bwd_stamps[gw * 8 + 6] = st_t0 - st_k1; g_bwd_stamps[gw * 8 + 7] = st_k2 - st_loop_end;
-        }
-    }
-#endif
     // ---- the four waves' accumulators -> LDS (the slot groups are dead), ONE barrier, then every thread adds them in a fixed
     // order for its 20 elements and writes the workgroup's partial tile with coalesced stores.  (The two-level tree it
     // replaces cost four barriers and left the 80 stores of the tile to one wave.)
@@ -1599,20 +1508,3 @@ int mfma_chain_combine(const float* V, const float* U, float* dx, int B, int T, 
 
 }  // namespace wn
 
-#ifdef WN_MULTI_STAMPS
-extern "C" __attribute__((visibility("default"))) int wn_debug_multi_stamps(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wn::g_multi_stamps), sizeof(unsigned long long) * (wn::kChainMaxL + 1) * 256 * 4);
-}
-extern "C" __attribute__((visibility("default"))) int wn_debug_multi_seg(unsigned long long* dst, int zero) {
-    if (zero) { static unsigned long long z[256 * 4 * 8]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(wn::g_multi_seg), z, sizeof(z)); }
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wn::g_multi_seg), sizeof(unsigned long long) * 256 * 4 * 8);
-}
-extern "C" __attribute__((visibility("default"))) int wn_debug_multi_spins(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wn::g_multi_spins), sizeof(unsigned long long) * (wn::kChainMaxL + 1) * 256 * 4);
-}
-#endif
-#ifdef WN_BWD_STAMPS
-extern "C" __attribute__((visibility("default"))) int wn_debug_bwd_stamps(unsigned long long* dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wn::g_bwd_stamps), sizeof(unsigned long long) * 1024 * 8);
-}
-#endif

@@ -461,7 +461,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int ahi = a.R - 1;
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh)
-            dma_pieces<false, true>(tile(buf, mh), lane, w, 8, 2, [&](int r) {
+            dma_pieces<true>(tile(buf, mh), lane, w, 8, 2, [&](int r) {
                 const int t = r0 + r < ahi ? r0 + r : ahi;
                 return ab + (long long)t * a.lda + 128 * mh;
             });
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
             const bf16* bb = pr.Bh[nh] + (long long)b * a.b_rpb * a.ldb;
             const int sh = a.b_r0 + r0 + pr.shift[nh];
             const int bhi = a.b_rpb - 1;
-            dma_pieces<false, true>(tile(buf, 2 + nh), lane, w, 8, 2, [&](int r) {
+            dma_pieces<true>(tile(buf, 2 + nh), lane, w, 8, 2, [&](int r) {
                 int t = sh + r;
                 t = t < 0 ? 0 : (t > bhi ? bhi : t);
                 return bb + (long long)t * a.ldb;
