@@ -65,6 +65,38 @@ def test_argument_errors_do_not_need_a_gpu():
     assert lib.wn_layer_fast_path(32, 32, 2) == 1 and lib.wn_layer_fast_path(16, 16, 2) == 0
 
 
+def test_stack_entry_points_reject_an_unknown_precision():
+    lib = _lib.lib()
+    # the check comes before any other (a valid precision gets as far as the missing descriptor) and before any HIP call
+    for prec in (4, -1, 3):
+        ex = ctypes.byref(_lib.WnExec(precision=prec))
+        for fn, call in (("wn_stack_fwd", lambda: lib.wn_stack_fwd(None, *[None] * 6, 1, 1, 0, 0, 0, ex, None)),
+                         ("wn_stack_bwd", lambda: lib.wn_stack_bwd(None, *[None] * 17, 0, 1, 1, 0, 0, ex, None))):
+            want = b"stack: desc is NULL" if prec == 3 else fn.encode() + b": WnExec.precision must be 0 .. 3"
+            assert call() == _lib.WN_EARG and lib.wn_last_error() == want, (fn, prec, lib.wn_last_error())
+
+
+def test_stack_backward_checks_sizes_and_window_before_any_hip_call():
+    lib = _lib.lib()
+    L = 2
+    w = (ctypes.c_void_p * L)(0x1000, 0x2000)          # never dereferenced: every call below is refused first
+    cd, dil = (ctypes.c_int * L)(32, 32), (ctypes.c_int * L)(1, 2)
+    d = _lib.WnStackDesc(n_layers=L, Cr=32, Cs=256, fw=2, cd=cd, dilation=dil, Wf=w, Wg=w, Wp=w, Ws=w)
+    p = 0x3000
+    for B, T, t_off in ((1, 64, -1), (1, 64, 64), (1, 64, 100), (0, 64, 0), (1, 0, 0)):
+        # x, xs, z, f, g, dout, dskip, dx; dWf .. dbs; ws, ws_bytes
+        rc = lib.wn_stack_bwd(ctypes.byref(d), p, p, p, None, p, None, p, None, w, None, w, None, w, None, None, None,
+                              p, 1 << 40, B, T, t_off, 0, None, None)
+        assert rc == _lib.WN_EARG, (B, T, t_off)
+        assert lib.wn_last_error() == b"wn_stack_bwd: non-positive size or t_off outside [0,T)", (B, T, t_off)
+    # a layer without its skip projection is refused when the call has a skip gradient
+    w0 = (ctypes.c_void_p * L)(0x1000, None)
+    d.Ws = w0
+    rc = lib.wn_stack_bwd(ctypes.byref(d), p, p, p, None, p, None, p, None, w, None, w, None, w, None, None, None,
+                          p, 1 << 40, 1, 64, 0, 0, None, None)
+    assert rc == _lib.WN_EARG and lib.wn_last_error() == b"stack: bad layer 1"
+
+
 def test_params_defaults_and_check():
     p = Params()
     assert p.quantization_steps == 256 and p.residual_conv_channels == [32] * 9 and p.optimizer == "adam"

@@ -12,72 +12,112 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-static thread_local const WnExec* g_exec = nullptr;
-static thread_local int g_exec_depth = 0;
-static thread_local const void* g_absmax_key[64];          // one per word of the scratch tail (kExecTail / 4)
-static thread_local int g_absmax_n = 0;
-static constexpr size_t kExecTail = 256;                  // bytes at the end of the scratch kept for the absmax words
-ExecScope::ExecScope(const WnExec* ex) : prev(g_exec) { g_exec = ex; ++g_exec_depth; }
-ExecScope::~ExecScope() {
-    g_exec = prev;
-    if (--g_exec_depth == 0) g_absmax_n = 0;              // the outermost entry point returns: nothing survives the call
+int check_precision(const char* fn, const WnExec* ex) {
+    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2),
+                 "%s: WnExec.precision must be 0 .. 3", fn);
+    return WN_OK;
 }
-static bool force_generic();
-int gemm_mode() {
-    if (force_generic()) return WN_GEMM_FP32;
-    const int m = g_exec ? g_exec->precision : WN_GEMM_BF16X3;
-    return (m < WN_GEMM_FP32 || m > WN_GEMM_FP16X2) ? WN_GEMM_BF16X3 : m;
+// (the entry points reject a precision outside 0 .. 3 first; the pure queries read one as bf16x3)
+Call::Call(const WnExec* ex)
+    : flags(ex ? ex->flags : 0u), ws(ex ? ex->ws : nullptr), ws_bytes(ex ? ex->ws_bytes : 0),
+      fwd_t1_min_blocks(ex && ex->fwd_t1_min_blocks ? ex->fwd_t1_min_blocks : 512),
+      plan(ex ? reinterpret_cast<StepPlan*>(ex->plan) : nullptr) {
+    const int p = ex ? ex->precision : WN_GEMM_BF16X3;
+    precision = generic() ? WN_GEMM_FP32 : (p < WN_GEMM_FP32 || p > WN_GEMM_FP16X2) ? WN_GEMM_BF16X3 : p;
 }
-StepPlan* exec_plan() { return g_exec ? reinterpret_cast<StepPlan*>(g_exec->plan) : nullptr; }
-const unsigned* exec_absmax(const float* x, long long n, hipStream_t s) {
-    // a READY step plan: the GEMM that wrote x left max |x| in a plan-owned word (the head's dx = dskip): no pass over x
-    if (const unsigned* w = plan_xmax_consumer(x)) return w;
-    if (!g_exec || !g_exec->ws || g_exec->ws_bytes < kExecTail) {
-        set_error("this call needs WnExec scratch (the fp16 split scales its operands by their measured range)");
-        return nullptr;
-    }
-    unsigned* slots = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g_exec->ws) + g_exec->ws_bytes - kExecTail);
-    for (int i = 0; i < g_absmax_n; ++i)
-        if (g_absmax_key[i] == x) return slots + i;
-    if (g_absmax_n >= 64) { set_error("exec_absmax: more than 64 range words in one call"); return nullptr; }
-    if (generic_absmax(x, n, slots + g_absmax_n, s) != WN_OK) return nullptr;
-    g_absmax_key[g_absmax_n] = x;
-    return slots + g_absmax_n++;
+bool Call::layer_fast_path(int Cr, int Cd, int fw) const { return !generic() && mfma_layer_supported(Cr, Cd, fw); }
+bool Call::wide_layer(int Cr, int Cd, int fw) const {
+    return !generic() && !mfma_layer_supported(Cr, Cd, fw) && wide_layer_supported(Cr, Cd, fw);
 }
-unsigned* exec_word(const void* key, bool* fresh, hipStream_t s) {
-    *fresh = false;
-    if (!g_exec || !g_exec->ws || g_exec->ws_bytes < kExecTail) {
-        set_error("this call needs WnExec scratch (the fp16 split scales its operands by their measured range)");
-        return nullptr;
-    }
-    unsigned* slots = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(g_exec->ws) + g_exec->ws_bytes - kExecTail);
-    for (int i = 0; i < g_absmax_n; ++i)
-        if (g_absmax_key[i] == key) return slots + i;
-    if (g_absmax_n >= 64) { set_error("exec_word: more than 64 range words in one call"); return nullptr; }
-    if (generic_zero_word(slots + g_absmax_n, s) != WN_OK) return nullptr;      // (a kernel, not a memset node: generic_kernels.hip)
-    g_absmax_key[g_absmax_n] = key;
-    *fresh = true;
-    return slots + g_absmax_n++;
-}
-bool exec_has_scratch(size_t bytes) { return g_exec && g_exec->ws && g_exec->ws_bytes >= bytes + kExecTail; }
-void* exec_scratch(size_t bytes, const char* what) {
-    bytes += kExecTail;
-    if (!g_exec || !g_exec->ws || g_exec->ws_bytes < bytes) {
+void* Call::scratch(size_t bytes, const char* what) const {
+    if (!has_scratch(bytes)) {
         set_error("this call needs %zu bytes of WnExec scratch for %s (got %zu): size it with wn_exec_workspace_bytes()",
-                  bytes, what, g_exec && g_exec->ws ? g_exec->ws_bytes : (size_t)0);
+                  bytes + kTail, what, ws ? ws_bytes : (size_t)0);
         return nullptr;
     }
-    return g_exec->ws;
+    return ws;
 }
-// WnExec.flags of the current call (no process state: the library reads no environment variable)
-bool exec_flag(unsigned f) { return g_exec && (g_exec->flags & f) != 0; }
-static bool force_generic() { return exec_flag(WN_EXEC_FORCE_GENERIC); }
-int exec_fwd_t1_min_blocks() {
-    const int v = g_exec ? g_exec->fwd_t1_min_blocks : 0;
-    return v == 0 ? 512 : v;
+// the tail word handed out for `key` in this call, else the next one, filled with max |x[0 .. n)| (x != NULL) or zeroed
+unsigned* Call::tail_word(const void* key, const float* x, long long n, bool* fresh, hipStream_t s) {
+    *fresh = false;
+    if (!ws || ws_bytes < kTail) {
+        set_error("this call needs WnExec scratch (the fp16 split scales its operands by their measured range)");
+        return nullptr;
+    }
+    unsigned* slots = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + ws_bytes - kTail);
+    for (int i = 0; i < nkeys_; ++i)
+        if (key_[i] == key) return slots + i;
+    if (nkeys_ >= kWords) {
+        set_error("Call::%s: more than %d range words in one call", x ? "absmax" : "word", kWords);
+        return nullptr;
+    }
+    // (the zeroing is a kernel, not a memset node: generic_kernels.hip)
+    if ((x ? generic_absmax(x, n, slots + nkeys_, s) : generic_zero_word(slots + nkeys_, s)) != WN_OK) return nullptr;
+    key_[nkeys_] = key;
+    *fresh = true;
+    return slots + nkeys_++;
 }
-// the fused 32-channel kernels for this shape, unless the call pins the generic path
-bool layer_fast_path(int Cr, int Cd, int fw) { return !force_generic() && mfma_layer_supported(Cr, Cd, fw); }
+const unsigned* Call::absmax(const float* x, long long n, hipStream_t s) {
+    // a READY step plan: the GEMM that wrote x left max |x| in a plan-owned word (the head's dx = dskip): no pass over x
+    if (const unsigned* w = plan_xmax_consumer(*this, x)) return w;
+    bool fresh;
+    return tail_word(x, x, n, &fresh, s);
+}
+
+// ---- the dispatchers behind the per-layer and skip entry points (wn_stack_* calls them with its own Call) --------------
+int layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg, const float* Wp,
+              const float* bp, float* out, float* z, float* f_save, float* g_save, int B, int T, int Cr, int Cd, int fw,
+              int d, int Z, hipStream_t s) {
+    if (c.layer_fast_path(Cr, Cd, fw))
+        return mfma_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, d, Z, 0, s);
+    if (c.wide_layer(Cr, Cd, fw) && (f_save || Cd <= Cr))
+        return wide_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
+    return generic_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
+}
+
+int layer_bwd(Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg, const float* Wp,
+              const float* dout, const float* dz_skip, float* dx, float* dWf, float* dbf, float* dWg, float* dbg,
+              float* dWp, float* dbp, float* dab_ws, int B, int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s) {
+    if (c.layer_fast_path(Cr, Cd, fw)) {
+        int rc = mfma_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dWg, dWp, dab_ws, B, T, d, Z, s);
+        if (rc) return rc;
+        return generic_layer_bwd_biases(c, dab_ws, dout, dbf, dbg, dbp, B, T, Cr, Cd, Z, s);
+    }
+    if (c.wide_layer(Cr, Cd, fw))
+        return wide_layer_bwd(c, x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T, Cr, Cd,
+                              fw, d, Z, s);
+    return generic_layer_bwd(c, x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T, Cr, Cd,
+                             fw, d, Z, s);
+}
+
+int skip_sum_fwd(Call& c, int L, const float* const* z, const float* const* Ws, const float* const* bs, const int* cd,
+                 float* skip, int B, int T, int t_off, int Tw, int Cs, int accumulate, hipStream_t s) {
+    if (!c.generic() && mfma_skip_supported(L, cd, Cs))
+        return mfma_skip_sum_fwd(c, L, z, Ws, bs, cd, skip, B, T, t_off, Tw, Cs, accumulate, s);
+    return generic_skip_sum_fwd(L, z, Ws, bs, cd, skip, B, T, t_off, Tw, Cs, accumulate, s);
+}
+
+int skip_bwd_dz(Call& c, int L, const float* const* Ws, const int* cd, const float* dskip, float* const* dz, int B, int T,
+                int t_off, int Tw, int Cs, hipStream_t s) {
+    if (!c.generic() && mfma_skip_supported(L, cd, Cs))
+        return mfma_skip_bwd_dz(c, L, Ws, cd, dskip, dz, B, T, t_off, Tw, Cs, false, s);
+    return generic_skip_bwd_dz(L, Ws, cd, dskip, dz, B, T, t_off, Tw, Cs, s);
+}
+
+int skip_bwd_dw(Call& c, int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs,
+                float* const* dbs, int B, int T, int t_off, int Tw, int Cs, hipStream_t s) {
+    if (dWs && !c.generic() && mfma_skip_supported(L, cd, Cs)) {
+        int rc = mfma_skip_bwd_dw(c, L, z, cd, dskip, dWs, B, T, t_off, Tw, Cs, s);
+        if (rc) return rc;
+        dWs = nullptr;
+    }
+    return generic_skip_bwd_dw(c, L, z, cd, dskip, dWs, dbs, B, T, t_off, Tw, Cs, s);
+}
+
+static bool head_xent_supported(const Call& c, int64_t N, int Cin, int Cout) {
+    return N > 0 && (N + 127) / 128 <= kXentBlocks && c.fp16x2() && Cout == 256 && Cin > 0 && Cin % 32 == 0 &&
+           mfma_pointwise_supported(Cin, Cout);
+}
 }  // namespace wn
 
 using namespace wn;
@@ -101,11 +141,10 @@ int wn_embed_fwd(const int32_t* idx, const float* W, const float* bias, float* o
 
 int wn_embed_bwd(const int32_t* idx, const float* dout, float* dW, float* dbias, int B, int T, int Q, int C,
                  int fw, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_embed_bwd", stream);
     NN(idx); NN(dout); NN(dW); POS(B); POS(T); POS(Q); POS(C); POS(fw);
-    return generic_embed_bwd(idx, dout, dW, dbias, B, T, Q, C, fw, as_stream(stream));
+    return generic_embed_bwd(Call(ex), idx, dout, dW, dbias, B, T, Q, C, fw, as_stream(stream));
 }
 
 int wn_conv_fwd(const float* x, const float* W, const float* bias, float* out, int B, int T, int Cin, int Cout,
@@ -127,21 +166,15 @@ int wn_conv_bwd(const float* x, const float* W, const float* dout, float* dx, fl
 int wn_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                  const float* Wp, const float* bp, float* out, float* z, float* f_save, float* g_save, int B,
                  int T, int Cr, int Cd, int fw, int d, int Z, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_layer_fwd", stream);
     NN(x); NN(Wf); NN(Wg); NN(Wp); NN(out); NN(z);
     POS(B); POS(T); POS(Cr); POS(Cd); POS(fw); POS(d);
     WN_CHECK_ARG(Z >= 0, "wn_layer_fwd: Z < 0");
     WN_CHECK_ARG((f_save == nullptr) == (g_save == nullptr), "wn_layer_fwd: f_save and g_save go together");
     WN_CHECK_ARG(out != x, "wn_layer_fwd: out must not alias x (taps read x[t-d])");
-    if (layer_fast_path(Cr, Cd, fw))
-        return mfma_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, d, Z, 0, as_stream(stream));
-    if (!force_generic() && wide_layer_supported(Cr, Cd, fw) && (f_save || Cd <= Cr))
-        return wide_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z,
-                              as_stream(stream));
-    return generic_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z,
-                             as_stream(stream));
+    Call c(ex);
+    return layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, as_stream(stream));
 }
 
 size_t wn_layer_bwd_workspace_floats(int B, int T, int Cr, int Cd, int fw) {
@@ -151,70 +184,53 @@ size_t wn_layer_bwd_workspace_floats(int B, int T, int Cr, int Cd, int fw) {
     return n;
 }
 
-}  // extern "C"
-namespace wn {
-bool wide_layer_in_use(int Cr, int Cd, int fw) {
-    return !layer_fast_path(Cr, Cd, fw) && !force_generic() && wide_layer_supported(Cr, Cd, fw);
-}
-}  // namespace wn
-extern "C" {
-
 int wn_layer_bwd(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                  const float* Wp, const float* dout, const float* dz_skip, float* dx, float* dWf, float* dbf,
                  float* dWg, float* dbg, float* dWp, float* dbp, float* dab_ws, int B, int T, int Cr, int Cd,
                  int fw, int d, int Z, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_layer_bwd", stream);
     NN(x); NN(f); NN(g); NN(Wf); NN(Wg); NN(Wp); NN(dab_ws);
     POS(B); POS(T); POS(Cr); POS(Cd); POS(fw); POS(d);
     WN_CHECK_ARG(Z >= 0, "wn_layer_bwd: Z < 0");
     WN_CHECK_ARG(dout || dz_skip, "wn_layer_bwd: both dout and dz_skip are NULL");
-    if (layer_fast_path(Cr, Cd, fw)) {
-        int rc = mfma_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dWg, dWp, dab_ws, B, T, d, Z,
-                                as_stream(stream));
-        if (rc) return rc;
-        return generic_layer_bwd_biases(dab_ws, dout, dbf, dbg, dbp, B, T, Cr, Cd, Z, as_stream(stream));
-    }
-    if (!force_generic() && wide_layer_supported(Cr, Cd, fw))
-        return wide_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T, Cr, Cd,
-                              fw, d, Z, as_stream(stream));
-    return generic_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T,
-                             Cr, Cd, fw, d, Z, as_stream(stream));
+    Call c(ex);
+    return layer_bwd(c, x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T, Cr, Cd, fw, d, Z,
+                     as_stream(stream));
 }
 
 int wn_pointwise_fwd(const float* x, const float* W, const float* bias, float* out, int N, int Cin, int Cout,
                      int act, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_pointwise_fwd", stream);
     NN(x); NN(W); NN(out); POS(N); POS(Cin); POS(Cout);
     WN_CHECK_ARG(act >= WN_ACT_NONE && act <= WN_ACT_ELU, "wn_pointwise_fwd: bad act %d", act);
-    if (!force_generic() && mfma_pointwise_supported(Cin, Cout))
-        return mfma_pointwise_fwd(x, W, bias, out, N, Cin, Cout, act, as_stream(stream));
+    Call c(ex);
+    if (!c.generic() && mfma_pointwise_supported(Cin, Cout))
+        return mfma_pointwise_fwd(c, x, W, bias, out, N, Cin, Cout, act, as_stream(stream));
     return generic_pointwise_fwd(x, W, bias, out, N, Cin, Cout, act, as_stream(stream));
 }
 
 int wn_pointwise_bwd(const float* x, const float* W, const float* dout, float* dx, float* dW, float* dbias,
                      int N, int Cin, int Cout, int act, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_pointwise_bwd", stream);
     NN(x); NN(W); NN(dout); POS(N); POS(Cin); POS(Cout);
     WN_CHECK_ARG(act >= WN_ACT_NONE && act <= WN_ACT_ELU, "wn_pointwise_bwd: bad act %d", act);
-    if (dx && !force_generic() && mfma_pointwise_supported(Cin, Cout)) {
-        int rc = mfma_pointwise_bwd_dx(x, W, dout, dx, N, Cin, Cout, act, as_stream(stream));
+    Call c(ex);
+    if (dx && !c.generic() && mfma_pointwise_supported(Cin, Cout)) {
+        int rc = mfma_pointwise_bwd_dx(c, x, W, dout, dx, N, Cin, Cout, act, as_stream(stream));
         if (rc) return rc;
         dx = nullptr;
     }
-    if (dW && !force_generic() && mfma_pointwise_supported(Cin, Cout)) {
+    if (dW && !c.generic() && mfma_pointwise_supported(Cin, Cout)) {
         bool bias_done = false;
-        int rc = mfma_pointwise_bwd_dw(x, dout, dW, N, Cin, Cout, act, dbias, &bias_done, as_stream(stream));
+        int rc = mfma_pointwise_bwd_dw(c, x, dout, dW, N, Cin, Cout, act, dbias, &bias_done, as_stream(stream));
         if (rc) return rc;
         dW = nullptr;
         if (bias_done) dbias = nullptr;
     }
-    return generic_pointwise_bwd(x, W, dout, dx, dW, dbias, N, Cin, Cout, act, as_stream(stream));
+    return generic_pointwise_bwd(c, x, W, dout, dx, dW, dbias, N, Cin, Cout, act, as_stream(stream));
 }
 
 static int check_skip(const char* fn, int L, int B, int T, int t_off, int Tw, int Cs) {
@@ -225,49 +241,37 @@ static int check_skip(const char* fn, int L, int B, int T, int t_off, int Tw, in
 
 int wn_skip_sum_fwd(int L, const float* const* z, const float* const* Ws, const float* const* bs, const int* cd,
                     float* skip, int B, int T, int t_off, int Tw, int Cs, int accumulate, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_skip_sum_fwd", stream);
     NN(z); NN(Ws); NN(cd); NN(skip);
     int rc = check_skip("wn_skip_sum_fwd", L, B, T, t_off, Tw, Cs);
     if (rc) return rc;
     for (int l = 0; l < L; ++l) WN_CHECK_ARG(z[l] && Ws[l] && cd[l] > 0, "wn_skip_sum_fwd: bad source %d", l);
-    if (!force_generic() && mfma_skip_supported(L, cd, Cs))
-        return mfma_skip_sum_fwd(L, z, Ws, bs, cd, skip, B, T, t_off, Tw, Cs, accumulate, as_stream(stream));
-    return generic_skip_sum_fwd(L, z, Ws, bs, cd, skip, B, T, t_off, Tw, Cs, accumulate, as_stream(stream));
+    Call c(ex);
+    return skip_sum_fwd(c, L, z, Ws, bs, cd, skip, B, T, t_off, Tw, Cs, accumulate, as_stream(stream));
 }
 
 int wn_skip_sum_bwd_dz(int L, const float* const* Ws, const int* cd, const float* dskip, float* const* dz, int B,
                        int T, int t_off, int Tw, int Cs, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_skip_sum_bwd_dz", stream);
     NN(Ws); NN(cd); NN(dskip); NN(dz);
     int rc = check_skip("wn_skip_sum_bwd_dz", L, B, T, t_off, Tw, Cs);
     if (rc) return rc;
     for (int l = 0; l < L; ++l) WN_CHECK_ARG(dz[l] && Ws[l] && cd[l] > 0, "wn_skip_sum_bwd_dz: bad entry %d", l);
-    bool fast = !force_generic() && Cs % 32 == 0;
-    for (int l = 0; l < L && fast; ++l) fast = cd[l] % 32 == 0;
-    if (fast) return mfma_skip_bwd_dz(L, Ws, cd, dskip, dz, B, T, t_off, Tw, Cs, false, as_stream(stream));
-    return generic_skip_bwd_dz(L, Ws, cd, dskip, dz, B, T, t_off, Tw, Cs, as_stream(stream));
+    Call c(ex);
+    return skip_bwd_dz(c, L, Ws, cd, dskip, dz, B, T, t_off, Tw, Cs, as_stream(stream));
 }
 
 int wn_skip_sum_bwd_dw(int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs,
                        float* const* dbs, int B, int T, int t_off, int Tw, int Cs, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_skip_sum_bwd_dw", stream);
     NN(z); NN(cd); NN(dskip);
     int rc = check_skip("wn_skip_sum_bwd_dw", L, B, T, t_off, Tw, Cs);
     if (rc) return rc;
-    bool fast = !force_generic() && Cs % 32 == 0 && dWs;
-    for (int l = 0; l < L && fast; ++l) fast = cd[l] % 32 == 0;
-    if (fast) {
-        rc = mfma_skip_bwd_dw(L, z, cd, dskip, dWs, B, T, t_off, Tw, Cs, as_stream(stream));
-        if (rc) return rc;
-        dWs = nullptr;
-    }
-    return generic_skip_bwd_dw(L, z, cd, dskip, dWs, dbs, B, T, t_off, Tw, Cs, as_stream(stream));
+    Call c(ex);
+    return skip_bwd_dw(c, L, z, cd, dskip, dWs, dbs, B, T, t_off, Tw, Cs, as_stream(stream));
 }
 
 int wn_softmax_fwd(const float* logits, float* prob, int N, int Q, void* stream) {
@@ -284,24 +288,23 @@ int wn_softmax_xent(const float* logits, const int32_t* target, float* loss, flo
 }
 
 int wn_head_xent_supported(int64_t N, int Cin, int Cout, const WnExec* ex) {
-    wn::ExecScope exec__(ex);
-    return (N > 0 && (N + 127) / 128 <= wn::kXentBlocks && !force_generic() && gemm_mode() == WN_GEMM_FP16X2 && Cout == 256 && Cin > 0 && Cin % 32 == 0 && mfma_pointwise_supported(Cin, Cout)) ? 1 : 0;
+    return head_xent_supported(Call(ex), N, Cin, Cout) ? 1 : 0;
 }
 
 int wn_head_xent(const float* x, const float* W, const float* bias, const int32_t* target, float* loss, float* dlogits,
                  int N, int Cin, int Cout, int act, int64_t n_norm, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    WN_CHECK_ARG(!ex || (ex->precision >= WN_GEMM_FP32 && ex->precision <= WN_GEMM_FP16X2), "%s: WnExec.precision must be 0 .. 3", __func__);
+    if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_head_xent", stream);
     NN(x); NN(W); NN(target); NN(loss); NN(dlogits); POS(N); POS(Cin); POS(Cout);
     WN_CHECK_ARG(act >= WN_ACT_NONE && act <= WN_ACT_ELU, "wn_head_xent: bad act %d", act);
-    WN_CHECK_SHAPE(wn_head_xent_supported(N, Cin, Cout, ex), "wn_head_xent: needs WN_GEMM_FP16X2, 256 outputs, a multiple of 32 "
+    Call c(ex);
+    WN_CHECK_SHAPE(head_xent_supported(c, N, Cin, Cout), "wn_head_xent: needs WN_GEMM_FP16X2, 256 outputs, a multiple of 32 "
                                                           "inputs and at most 253,952 rows (run wn_pointwise_fwd + wn_softmax_xent instead)");
     hipStream_t s = as_stream(stream);
     const long long nn = n_norm > 0 ? n_norm : (n_norm == 0 ? N : -1);
     int ncnt = 0, rc;
     if (nn < 0 && (rc = generic_xent_count(target, N, Cout, loss, &ncnt, s))) return rc;
-    if ((rc = mfma_head_xent(x, W, bias, target, loss, dlogits, N, Cin, Cout, act, nn, ncnt, s))) return rc;
+    if ((rc = mfma_head_xent(c, x, W, bias, target, loss, dlogits, N, Cin, Cout, act, nn, ncnt, s))) return rc;
     return generic_xent_final(loss, (int)((N + 127) / 128), nn, ncnt, s);
 }
 

@@ -864,14 +864,7 @@ int decode_fast_launch(const float* P, int nlayers, const float* hbias, const fl
                        float* arena, int* tok_ring, long long n0, int nsteps, int first_token,
                        const double* uniforms, int32_t* out_tokens, float* prob_out, int prob_stride,
                        int apply_softmax, int do_sample, int head_act, bool three_wgs, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_fast),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)decode_fast_lds_bytes()));
-        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_fast3),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)decode_fast_lds_bytes()));
-        attr = true;
-    }
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast, k_decode_fast3);
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
         // per device, per call: cheap, and a process may drive several devices).  What the count cannot see -- other work
@@ -915,12 +908,7 @@ int decode_fast_launch_batch(int n_utt, const float* const* P, int nlayers, cons
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
         return WN_ESHAPE;
     }
-    static bool attr = false;
-    if (!attr) {
-        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_fast3_batch),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)decode_fast_lds_bytes()));
-        attr = true;
-    }
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch);
     DecBatchArgs a{};
     const int nx = nlayers * 64 + 8 * 256 + 16;
     for (int u = 0; u < n_utt; ++u) {

@@ -4,11 +4,9 @@
 // fallback for everything else and the on-GPU cross-check of the fast kernels.
 #include <cstdlib>
 
-#include "wn_common.hpp"
+#include "wn_kernels.hpp"
 
 namespace wn {
-void* exec_scratch(size_t bytes, const char* what);
-bool exec_has_scratch(size_t bytes);       // api.hip: the current call's WnExec scratch
 
 static constexpr int kThreads = 256;
 
@@ -305,16 +303,15 @@ __global__ void k_colsum_reduce(const float* __restrict__ part, int ny, int M, f
 
 // (the wide weight-gradient kernel's column sums are reduced by the same tree inside k_wgrad_b3w_reduce: mfma_gemm_b3.hip)
 
+// ws_bytes of scratch at ws (may be NULL): room for the partials gives the fixed-order reduction, else atomics
 static int launch_colsum(const float* A, long long a_bs, int a_t0, int lda, int nB, int tmin, int nT,
-                         int M, float* out, hipStream_t s) {
+                         int M, float* out, void* ws, size_t ws_bytes, hipStream_t s) {
     if (nT <= tmin || nB <= 0) return WN_OK;
     int t_chunk = 256;
     int nchunk = (nT - tmin + t_chunk - 1) / t_chunk;
     while ((long long)nB * nchunk > 2048) { t_chunk *= 2; nchunk = (nT - tmin + t_chunk - 1) / t_chunk; }
     dim3 grid(cdiv(M, 64), nB * nchunk);
-    float* part = exec_has_scratch((size_t)grid.y * M * sizeof(float))
-                      ? reinterpret_cast<float*>(exec_scratch((size_t)grid.y * M * sizeof(float), "column-sum partials"))
-                      : nullptr;
+    float* part = ws && ws_bytes >= (size_t)grid.y * M * sizeof(float) ? reinterpret_cast<float*>(ws) : nullptr;
     hipLaunchKernelGGL(k_colsum, grid, dim3(64, 4), 0, s, A, a_bs, a_t0, lda, nB, tmin, nT, M, out, t_chunk, part);
     if (part) hipLaunchKernelGGL(k_colsum_reduce, dim3(cdiv(M, 64)), dim3(64, 16), 0, s, part, (int)grid.y, M, out);
     WN_LAUNCH_CHECK();
@@ -890,12 +887,12 @@ int embed_bwd_mfma(const int32_t* idx, const __bf16* dx, const float* dx_f32, in
 }
 namespace wn {
 
-int generic_embed_bwd(const int32_t* idx, const float* dout, float* dW, float* dbias, int B, int T,
+int generic_embed_bwd(const Call& c, const int32_t* idx, const float* dout, float* dW, float* dbias, int B, int T,
                       int Q, int C, int fw, hipStream_t s) {
     // filter width 2, 256 token values, 32 / 64 / 128 channels (every BASELINE config): matrix cores, fixed summation
     // order (bit-reproducible); anything else, or no scratch: per-block tables in LDS
-    if (fw == 2 && Q == 256 && (C == 32 || C == 64 || C == 128) && exec_has_scratch(w16::embed_bwd_ws_bytes(B, T, C))) {
-        void* ws = exec_scratch(w16::embed_bwd_ws_bytes(B, T, C), "the embedding-gradient partial tables");
+    if (fw == 2 && Q == 256 && (C == 32 || C == 64 || C == 128) && c.has_scratch(w16::embed_bwd_ws_bytes(B, T, C))) {
+        void* ws = c.scratch(w16::embed_bwd_ws_bytes(B, T, C), "the embedding-gradient partial tables");
         return w16::embed_bwd_mfma(idx, nullptr, dout, C, dW, dbias, B, T, ws, s);
     }
     int Cs = C;                                            // channel slice whose table fits in LDS
@@ -910,17 +907,12 @@ int generic_embed_bwd(const int32_t* idx, const float* dout, float* dW, float* d
         int cpb = (int)((ncol + nb - 1) / nb);
         int nblk = (int)((ncol + cpb - 1) / cpb);
         const int nent = Q * fw * Cs + Cs;
-        float* ws = reinterpret_cast<float*>(exec_scratch((size_t)nsl * nblk * nent * sizeof(float),
-                                                          "the per-block embedding-gradient tables"));
+        float* ws = reinterpret_cast<float*>(c.scratch((size_t)nsl * nblk * nent * sizeof(float),
+                                                       "the per-block embedding-gradient tables"));
         if (!ws) return WN_EARG;
 #define EMB_LAUNCH(FW)                                                                                        \
     do {                                                                                                      \
-        static bool attr_set = false;                                                                         \
-        if (!attr_set) {                                                                                      \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_embed_bwd_lds<FW>),                    \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));              \
-            attr_set = true;                                                                                  \
-        }                                                                                                     \
+        WN_MAX_LDS_ONCE(150 * 1024, k_embed_bwd_lds<FW>);                                                     \
         hipLaunchKernelGGL(k_embed_bwd_lds<FW>, dim3(nblk, nsl), dim3(kEmbThreads), lds, s, idx, dout, ws, dbias ? 1 : 0, B, T, \
                            Q, Cs, fw, cpb, C);                                                                \
     } while (0)
@@ -980,7 +972,7 @@ int generic_conv_bwd(const float* x, const float* W, const float* dout, float* d
         int rc = conv_dw(x, dout, Cout, dW, B, T, Cin, Cout, fw, d, Z, s);
         if (rc) return rc;
     }
-    if (dbias) return launch_colsum(dout, (long long)T * Cout, 0, Cout, B, Z, T, Cout, dbias, s);
+    if (dbias) return launch_colsum(dout, (long long)T * Cout, 0, Cout, B, Z, T, Cout, dbias, nullptr, 0, s);
     return WN_OK;
 }
 
@@ -998,7 +990,7 @@ int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const fl
     return WN_OK;
 }
 
-int generic_layer_bwd(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
+int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
                       int fw, int d, int Z, hipStream_t s) {
@@ -1015,8 +1007,8 @@ int generic_layer_bwd(const float* x, const float* f, const float* g, const floa
     int rc;
     if (dWf && (rc = conv_dw(x, dab, 2 * Cd, dWf, B, T, Cr, Cd, fw, d, Z, s))) return rc;
     if (dWg && (rc = conv_dw(x, dab + Cd, 2 * Cd, dWg, B, T, Cr, Cd, fw, d, Z, s))) return rc;
-    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, s))) return rc;
-    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, s))) return rc;
+    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
+    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
     if (dWp) {   // dWp[cr][cd] += dout z^T,  z = f*g
         WgradArgs a{};
         a.A = dout; a.a_bs = (long long)T * Cr; a.a_t0 = 0; a.lda = Cr;
@@ -1025,22 +1017,23 @@ int generic_layer_bwd(const float* x, const float* f, const float* g, const floa
         a.dW = dWp; a.sm = Cd; a.sk = 1;
         if ((rc = launch_wgrad(a, s))) return rc;
     }
-    if (dbp && (rc = launch_colsum(dout, (long long)T * Cr, 0, Cr, B, 0, T, Cr, dbp, s))) return rc;
+    if (dbp && (rc = launch_colsum(dout, (long long)T * Cr, 0, Cr, B, 0, T, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
 
 // out[m] += sum over rows t in [tmin, nT) of every clip of A[b][t][m]  (dense rows of width lda)
-int generic_colsum(const float* A, int nB, int nT, int tmin, int lda, int M, float* out, hipStream_t s) {
-    return launch_colsum(A, (long long)nT * lda, 0, lda, nB, tmin, nT, M, out, s);
+int generic_colsum(const float* A, int nB, int nT, int tmin, int lda, int M, float* out, void* ws, size_t ws_bytes,
+                   hipStream_t s) {
+    return launch_colsum(A, (long long)nT * lda, 0, lda, nB, tmin, nT, M, out, ws, ws_bytes, s);
 }
 
 // bias gradients of a residual layer from the (da,dg) scratch: dbf += sum da, dbg += sum dg, dbp += sum dout
-int generic_layer_bwd_biases(const float* dab, const float* dout, float* dbf, float* dbg, float* dbp, int B,
+int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout, float* dbf, float* dbg, float* dbp, int B,
                              int T, int Cr, int Cd, int Z, hipStream_t s) {
     int rc;
-    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, s))) return rc;
-    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, s))) return rc;
-    if (dbp && dout && (rc = launch_colsum(dout, (long long)T * Cr, 0, Cr, B, 0, T, Cr, dbp, s))) return rc;
+    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
+    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (dbp && dout && (rc = launch_colsum(dout, (long long)T * Cr, 0, Cr, B, 0, T, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
 
@@ -1052,7 +1045,7 @@ int generic_pointwise_fwd(const float* x, const float* W, const float* bias, flo
     return WN_OK;
 }
 
-int generic_pointwise_bwd(const float* x, const float* W, const float* dout, float* dx, float* dW, float* dbias,
+int generic_pointwise_bwd(const Call& c, const float* x, const float* W, const float* dout, float* dx, float* dW, float* dbias,
                           long long N, int Cin, int Cout, int act, hipStream_t s) {
     if (dx) {
         hipLaunchKernelGGL(k_pointwise_bwd_dx, dim3(cdiv(N * Cin, kThreads)), dim3(kThreads), 0, s, x, W, dout,
@@ -1068,7 +1061,7 @@ int generic_pointwise_bwd(const float* x, const float* W, const float* dout, flo
         a.dW = dW; a.sm = Cin; a.sk = 1;
         if ((rc = launch_wgrad(a, s))) return rc;
     }
-    if (dbias && (rc = launch_colsum(dout, 0, 0, Cout, 1, 0, (int)N, Cout, dbias, s))) return rc;
+    if (dbias && (rc = launch_colsum(dout, 0, 0, Cout, 1, 0, (int)N, Cout, dbias, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
 
@@ -1100,7 +1093,7 @@ int generic_skip_bwd_dz(int L, const float* const* Ws, const int* cd, const floa
     return WN_OK;
 }
 
-int generic_skip_bwd_dw(int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs,
+int generic_skip_bwd_dw(const Call& c, int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs,
                         float* const* dbs, int B, int T, int t_off, int Tw, int Cs, hipStream_t s) {
     int rc;
     for (int l = 0; l < L; ++l) {
@@ -1113,7 +1106,7 @@ int generic_skip_bwd_dw(int L, const float* const* z, const int* cd, const float
             if ((rc = launch_wgrad(a, s))) return rc;
         }
         if (dbs && dbs[l] &&
-            (rc = launch_colsum(dskip, (long long)Tw * Cs, 0, Cs, B, 0, Tw, Cs, dbs[l], s)))
+            (rc = launch_colsum(dskip, (long long)Tw * Cs, 0, Cs, B, 0, Tw, Cs, dbs[l], c.ws, c.room(), s)))
             return rc;
     }
     return WN_OK;

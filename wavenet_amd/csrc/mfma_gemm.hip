@@ -166,11 +166,11 @@ __global__ __launch_bounds__(256, 2) void k_colgemm(CGArgs a) {
 }
 
 template <bool MP>
-static int launch_colgemm(CGArgs& a, int nprob, hipStream_t s) {
+static int launch_colgemm(Call& c, CGArgs& a, int nprob, hipStream_t s) {
     const int M = a.M;
     a.nprob = nprob;
-    if (gemm_b3_enabled()) {
-        int rc = launch_colgemm_b3(a, MP ? (M == 32 ? 2 : 1) : 0, nprob, s);
+    if (c.split_b3()) {
+        int rc = launch_colgemm_b3(c, a, MP ? (M == 32 ? 2 : 1) : 0, nprob, s);
         if (rc != WN_ESHAPE) return rc;                 // WN_ESHAPE = shape not covered: use the exact-fp32 kernels
     }
     if (MP && M == 32 && nprob > 1) {          // 32-row problems: 8 per workgroup, X streamed once per 8
@@ -202,7 +202,7 @@ static int launch_colgemm(CGArgs& a, int nprob, hipStream_t s) {
     return WN_OK;
 }
 
-int launch_colgemm_multi(CGArgs& a, hipStream_t s) { return launch_colgemm<false>(a, 1, s); }
+int launch_colgemm_multi(Call& c, CGArgs& a, hipStream_t s) { return launch_colgemm<false>(c, a, 1, s); }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -214,7 +214,7 @@ bool mfma_skip_supported(int L, const int* cd, int Cs) {
     return true;
 }
 
-int mfma_skip_sum_fwd(int L, const float* const* z, const float* const* Ws, const float* const* bs, const int* cd,
+int mfma_skip_sum_fwd(Call& c, int L, const float* const* z, const float* const* Ws, const float* const* bs, const int* cd,
                       float* skip, int B, int T, int t_off, int Tw, int Cs, int accumulate, hipStream_t s) {
     for (int l0 = 0; l0 < L; l0 += WN_MAX_SRC) {
         CGArgs a{};
@@ -229,14 +229,14 @@ int mfma_skip_sum_fwd(int L, const float* const* z, const float* const* Ws, cons
         a.act = WN_ACT_NONE; a.gate_x = nullptr; a.gate_act = 0;
         a.accumulate = (accumulate || l0 > 0) ? 1 : 0;
         a.h2_ok = 1;                                     // z = tanh * sigmoid lies in [-1, 1]
-        int rc = launch_colgemm<false>(a, 1, s);
+        int rc = launch_colgemm<false>(c, a, 1, s);
         if (rc) return rc;
     }
     return WN_OK;
 }
 
 // window_only: compute (and write) columns t >= t_off only; the rows below are left untouched
-int mfma_skip_bwd_dz(int L, const float* const* Ws, const int* cd, const float* dskip, float* const* dz, int B,
+int mfma_skip_bwd_dz(Call& c, int L, const float* const* Ws, const int* cd, const float* dskip, float* const* dz, int B,
                      int T, int t_off, int Tw, int Cs, bool window_only, hipStream_t s) {
     // every layer is cd/32 problems of 32 output rows sharing X = dskip; batches of <= WN_MAX_SRC problems with
     // one row stride (ldo = cd) per launch
@@ -259,8 +259,8 @@ int mfma_skip_bwd_dz(int L, const float* const* Ws, const int* cd, const float* 
             a.N = (long long)B * T; a.rows_out_per_b = T; a.rows_src_per_b = Tw; a.off = -t_off;
         }
         a.act = WN_ACT_NONE; a.gate_x = nullptr; a.accumulate = 0;
-        if (gemm_mode() == WN_GEMM_FP16X2 && !(a.xmax_dev = exec_absmax(dskip, (long long)B * Tw * Cs, s))) return WN_EARG;
-        int rc = launch_colgemm<true>(a, np, s);
+        if (c.fp16x2() && !(a.xmax_dev = c.absmax(dskip, (long long)B * Tw * Cs, s))) return WN_EARG;
+        int rc = launch_colgemm<true>(c, a, np, s);
         if (rc) return rc;
     }
     return WN_OK;
@@ -268,7 +268,7 @@ int mfma_skip_bwd_dz(int L, const float* const* Ws, const int* cd, const float* 
 
 bool mfma_pointwise_supported(int Cin, int Cout) { return Cin % 32 == 0 && Cout % 32 == 0; }
 
-int mfma_pointwise_fwd(const float* x, const float* W, const float* bias, float* out, long long N, int Cin,
+int mfma_pointwise_fwd(Call& c, const float* x, const float* W, const float* bias, float* out, long long N, int Cin,
                        int Cout, int act, hipStream_t s) {
     CGArgs a{};
     a.nsrc = 1; a.X[0] = x; a.W[0] = W; a.bias[0] = bias; a.K[0] = Cin; a.wsm[0] = Cin; a.wsk = 1;
@@ -278,26 +278,26 @@ int mfma_pointwise_fwd(const float* x, const float* W, const float* bias, float*
     a.act = act; a.gate_x = nullptr; a.accumulate = 0;
     // (the head keeps the six-term split under WN_GEMM_FP16X2: its input is bounded only by the weights, and measuring the
     // range -- a 100 MB pass per call -- costs more than the fp16 split saves on a contraction this small: 0.095 -> 0.111 ms)
-    return launch_colgemm<false>(a, 1, s);
+    return launch_colgemm<false>(c, a, 1, s);
 }
 
 // The last head convolution and the loss in one launch (fp16 split, 256 outputs): dlogits = d loss / d (W act(x) + b), the
 // workgroups' loss sums in loss[kXentPart ..] (the caller finalises).  WN_ESHAPE when the shape or the arithmetic mode is not
 // covered: the caller then runs the convolution and the loss as two calls.
-int mfma_head_xent(const float* x, const float* W, const float* bias, const int32_t* target, float* loss, float* dlogits,
+int mfma_head_xent(Call& c, const float* x, const float* W, const float* bias, const int32_t* target, float* loss, float* dlogits,
                    long long N, int Cin, int Cout, int act, long long n_norm, int ncnt, hipStream_t s) {
-    if (Cout != 256 || Cin % 32 || N >= (1ll << 30) || gemm_mode() != WN_GEMM_FP16X2) return WN_ESHAPE;
+    if (Cout != 256 || Cin % 32 || N >= (1ll << 30) || !c.fp16x2()) return WN_ESHAPE;
     CGArgs a{};
     a.nsrc = 1; a.X[0] = x; a.W[0] = W; a.bias[0] = bias; a.K[0] = Cin; a.wsm[0] = Cin; a.wsk = 1;
     a.out[0] = dlogits; a.M = Cout; a.ldo = Cout; a.N = N;
     a.rows_out_per_b = (int)N; a.rows_src_per_b = (int)N; a.off = 0;
     a.act = act; a.gate_x = nullptr; a.accumulate = 0;
     a.xent_target = target; a.xent_loss = loss; a.xent_n_norm = n_norm; a.xent_ncnt = ncnt;
-    return launch_colgemm_b3(a, 6, 1, s);
+    return launch_colgemm_b3(c, a, 6, 1, s);
 }
 
 // dx[n][c] = act'(x[n][c]) * sum_o W[o][c] dout[n][o]
-int mfma_pointwise_bwd_dx(const float* x, const float* W, const float* dout, float* dx, long long N, int Cin,
+int mfma_pointwise_bwd_dx(Call& c, const float* x, const float* W, const float* dout, float* dx, long long N, int Cin,
                           int Cout, int act, hipStream_t s) {
     CGArgs a{};
     a.nsrc = 1; a.X[0] = dout; a.W[0] = W; a.bias[0] = nullptr; a.K[0] = Cout; a.wsm[0] = 1; a.wsk = Cin;
@@ -306,9 +306,9 @@ int mfma_pointwise_bwd_dx(const float* x, const float* W, const float* dout, flo
     a.rows_out_per_b = (int)N; a.rows_src_per_b = (int)N; a.off = 0;
     a.act = WN_ACT_NONE; a.gate_x = (act == WN_ACT_NONE) ? nullptr : x; a.gate_act = act; a.accumulate = 0;
     // step plan: the next consumer of dx (the dz contraction of the skip path, whose fp16 split needs max |dskip|) finds the
-    // range in a plan-owned word instead of making a pass over the array (exec_absmax -> plan_xmax_consumer)
-    a.outmax_dev = plan_xmax_producer();
-    return launch_colgemm<false>(a, 1, s);
+    // range in a plan-owned word instead of making a pass over the array (Call::absmax -> plan_xmax_consumer)
+    a.outmax_dev = plan_xmax_producer(c);
+    return launch_colgemm<false>(c, a, 1, s);
 }
 
 }  // namespace wn
@@ -413,9 +413,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_mfma(WGArgs a) {
             atomicAdd(o + (long long)(m0 + mt * 32 + cg_ch(r, h)) * a.ldo + (long long)j * (a.osk ? a.osk : 1), acc[mt][r]);
 }
 
-int launch_wgrad(WGArgs& a, int M, hipStream_t s);
-static int launch_wgrad_mfma(WGArgs& a, int M, hipStream_t s) { return launch_wgrad(a, M, s); }
-int launch_wgrad(WGArgs& a, int M, hipStream_t s) {
+int launch_wgrad(const Call& c, WGArgs& a, int M, hipStream_t s) {
     int mt = (M % 256 == 0) ? 8 : (M % 128 == 0) ? 4 : (M % 64 == 0) ? 2 : 1;
     // row slabs: enough workgroups to fill the chip, few enough that the atomics stay small
     int groups = cdiv(a.nprob, 4) * (M / (mt * 32));
@@ -428,15 +426,15 @@ int launch_wgrad(WGArgs& a, int M, hipStream_t s) {
     a.rows_per_wg = rows;
     a.wgs_per_b = cdiv(a.rows_A_per_b, rows);
     dim3 grid(a.nB * a.wgs_per_b, cdiv(a.nprob, 4), M / (mt * 32));
-    if (gemm_b3_enabled() && M == 256 && a.nprob >= 8) return launch_wgrad_b3w(a, s);
-    if (gemm_b3_enabled() && M % 256 == 0 && a.nprob >= 8) {      // config 5's 512 skip channels: one wide launch per 256 rows of A
+    if (c.split_b3() && M == 256 && a.nprob >= 8) return launch_wgrad_b3w(c, a, s);
+    if (c.split_b3() && M % 256 == 0 && a.nprob >= 8) {      // config 5's 512 skip channels: one wide launch per 256 rows of A
         for (int m0 = 0; m0 < M; m0 += 256) {
             WGArgs h = a;
             h.A = a.A + m0;
             for (int q = 0; q < a.nprob; ++q) h.out[q] = a.out[q] + (long long)m0 * a.ldo;
             h.colsum = a.colsum ? a.colsum + m0 : nullptr;
             h.colsum_done = 0;
-            int rc = launch_wgrad_b3w(h, s);
+            int rc = launch_wgrad_b3w(c, h, s);
             if (rc) return rc;
             // Whether the wide kernel takes the column sums depends on the arithmetic mode only (six-term form: yes; one-term
             // bf16 / fp16x2: no), so every 256-row slice must answer alike.  "None did" is fine: colsum_done stays 0 and the
@@ -449,10 +447,10 @@ int launch_wgrad(WGArgs& a, int M, hipStream_t s) {
         }
         return WN_OK;
     }
-    if (gemm_b3_enabled()) {          // bf16x3: at most 4 row tiles per workgroup (register budget), more groups in z
+    if (c.split_b3()) {          // bf16x3: at most 4 row tiles per workgroup (register budget), more groups in z
         const int mt3 = mt > 4 ? 4 : mt;
         grid.z = M / (mt3 * 32);
-        return launch_wgrad_b3(a, mt3, grid, s);
+        return launch_wgrad_b3(c, a, mt3, grid, s);
     }
     bool any_b2 = false, all_b2 = true;
     for (int q = 0; q < a.nprob; ++q) { any_b2 |= a.B2p[q] != nullptr; all_b2 &= a.B2p[q] != nullptr; }
@@ -481,7 +479,7 @@ int launch_wgrad(WGArgs& a, int M, hipStream_t s) {
 }
 
 // dWs[l][cs][cd] += sum dskip[b,t',cs] z_l[b,t_off+t',cd]   (cd any multiple of 32: one problem per 32 columns)
-int mfma_skip_bwd_dw(int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs, int B, int T,
+int mfma_skip_bwd_dw(Call& c, int L, const float* const* z, const int* cd, const float* dskip, float* const* dWs, int B, int T,
                      int t_off, int Tw, int Cs, hipStream_t s) {
     int l = 0, j = 0;
     while (l < L) {
@@ -495,18 +493,18 @@ int mfma_skip_bwd_dw(int L, const float* const* z, const int* cd, const float* d
         if (a.nprob == 0) continue;
         a.ldb = width; a.ldo = width; a.osk = 1;
         a.nB = B; a.rows_A_per_b = Tw; a.rows_B_per_b = T; a.off = t_off; a.act = WN_ACT_NONE;
-        if (gemm_mode() == WN_GEMM_FP16X2) {             // A = dskip: measured range; B = z in [-1, 1]
-            if (!(a.amax_dev = exec_absmax(dskip, (long long)B * Tw * Cs, s))) return WN_EARG;
+        if (c.fp16x2()) {             // A = dskip: measured range; B = z in [-1, 1]
+            if (!(a.amax_dev = c.absmax(dskip, (long long)B * Tw * Cs, s))) return WN_EARG;
             a.h2 = 1;
         }
-        int rc = launch_wgrad(a, Cs, s);
+        int rc = launch_wgrad(c, a, Cs, s);
         if (rc) return rc;
     }
     return WN_OK;
 }
 
 // dW[o][c] += sum_n dout[n][o] act(x[n][c])
-int mfma_pointwise_bwd_dw(const float* x, const float* dout, float* dW, long long N, int Cin, int Cout, int act,
+int mfma_pointwise_bwd_dw(const Call& c, const float* x, const float* dout, float* dW, long long N, int Cin, int Cout, int act,
                           float* dbias, bool* dbias_done, hipStream_t s) {
     if (N >= (1ll << 30)) { wn::set_error("pointwise dW: N too large"); return WN_ESHAPE; }
     if (dbias_done) *dbias_done = false;
@@ -520,7 +518,7 @@ int mfma_pointwise_bwd_dw(const float* x, const float* dout, float* dW, long lon
         }
         a.ldb = Cin; a.ldo = Cin;
         a.nB = 1; a.rows_A_per_b = (int)N; a.rows_B_per_b = (int)N; a.off = 0; a.act = act;
-        int rc = launch_wgrad_mfma(a, Cout, s);
+        int rc = launch_wgrad(c, a, Cout, s);
         if (rc) return rc;
         if (a.colsum_done && dbias_done) *dbias_done = true;
     }

@@ -38,7 +38,7 @@ struct CGArgs {
     // fused-layer mode (mode 5 = gate mode + the residual projection, 128/128 channels, one-term products): out[0] (row
     // stride ldo = 128) = Wp z + proj_bias + residual, Wp's image is the kernel's second image argument
     int h2_ok;                       // X is provably within the fp16 split's static range (z = tanh * sigmoid)
-    const unsigned* xmax_dev;        // else: device word with the bits of max |X| (exec_absmax) -> dynamic power-of-two scale
+    const unsigned* xmax_dev;        // else: device word with the bits of max |X| (Call::absmax) -> dynamic power-of-two scale
     const unsigned* wmax_dev;        // fp16 split: bits of max |W| over the launch's weight tiles (launch_colgemm_b3 fills it)
     unsigned* outmax_dev;            // mode 0, k_colgemm_b3 only: atomicMax of the bits of max |out| (a step plan's word), or NULL
     const float* proj_W;             // Wp[128][128], row-major
@@ -78,20 +78,18 @@ struct WGArgs {
     float* colsum; float* colsum_part; int colsum_done;
 };
 
-// 1 unless WAVENET_HIP_GEMM=fp32: contractions use three-way bf16 splits (6 bf16 MFMAs per product term)
-bool gemm_b3_enabled();      // the current call's precision is bf16x3 or bf16
 // mode 0: multi-source, one output; mode 2: nprob problems of 32 rows sharing X.  Returns WN_ESHAPE when
 // the shape is not covered (the caller then uses the exact-fp32 kernel).
-int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s);
+int launch_colgemm_b3(Call& c, CGArgs& a, int mode, int nprob, hipStream_t s);
 
 // dW_p[m*ldo + k*osk] += sum_n A[n][m] * act(B_p[row(n)][k]) (* B2_p);  M rows; picks bf16x3 or exact fp32
-int launch_wgrad(WGArgs& a, int M, hipStream_t s);
+int launch_wgrad(const Call& c, WGArgs& a, int M, hipStream_t s);
 // wide bf16x3 block (M == 256, nprob >= 8)
-int launch_wgrad_b3w(WGArgs& a, hipStream_t s);
+int launch_wgrad_b3w(const Call& c, WGArgs& a, hipStream_t s);
 // one channel GEMM launch (multi-source form); picks bf16x3 or exact fp32
-int launch_colgemm_multi(CGArgs& a, hipStream_t s);
+int launch_colgemm_multi(Call& c, CGArgs& a, hipStream_t s);
 
 // bf16x3 form of k_wgrad_mfma (same grid / arguments)
-int launch_wgrad_b3(const WGArgs& a, int mt, dim3 grid, hipStream_t s);
+int launch_wgrad_b3(const Call& c, const WGArgs& a, int mt, dim3 grid, hipStream_t s);
 
 }  // namespace wn

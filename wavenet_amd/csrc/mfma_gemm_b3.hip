@@ -19,10 +19,6 @@
 
 namespace wn {
 
-bool gemm_b3_enabled() { return gemm_mode() >= 1; }
-static bool one_term() { return gemm_mode() == 2; }
-static bool half2_mode() { return gemm_mode() == 3; }
-
 // the weight tiles of one launch (see split_w.hpp); WMAX: only the largest |w|, into *a.wmax_dev (atomicMax of the bits: a
 // positive float orders like an unsigned)
 template <bool WMAX>
@@ -834,16 +830,16 @@ __global__ __launch_bounds__(256, 2) void k_colgemm_h2q(CGArgs a, const __bf16* 
     }
 }
 
-int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s) {
+int launch_colgemm_b3(Call& c, CGArgs& a, int mode, int nprob, hipStream_t s) {
     if (mode != 0 && mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6) return WN_ESHAPE;
-    if (mode == 6 && !(half2_mode() && a.M == 256 && a.nsrc == 1 && a.xent_target && a.xent_loss && a.out[0] &&
+    if (mode == 6 && !(c.fp16x2() && a.M == 256 && a.nsrc == 1 && a.xent_target && a.xent_loss && a.out[0] &&
                        cdiv(a.N, 128) <= kXentBlocks))
         return WN_ESHAPE;
     int mtiles, nchunks, cps;
     if (mode == 0 || mode >= 3) {
         if (a.M % 32) return WN_ESHAPE;
         if ((mode == 3 || mode == 5) && a.nsrc > WN_GATE_TAPS) return WN_ESHAPE;
-        if (mode == 5 && !(one_term() && a.M == 128 && a.ldo == 128)) return WN_ESHAPE;
+        if (mode == 5 && !(c.one_term() && a.M == 128 && a.ldo == 128)) return WN_ESHAPE;
         for (int i = 0; i < a.nsrc; ++i)
             if (a.K[i] != a.K[0] || a.K[i] % 32) return WN_ESHAPE;
         mtiles = ((mode == 3 || mode == 5) ? 2 : 1) * a.M / 32;
@@ -855,28 +851,28 @@ int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s) {
         cps = a.K[0] / 32;
         nchunks = cps;
     }
-    const bool one = one_term();
+    const bool one = c.one_term();
     // fp16 split: plain contractions whose operands the caller declared range-safe (forward activations); else six terms
-    const bool h2 = half2_mode() && ((a.h2_ok || a.xmax_dev) && (mode == 0 || mode == 2) || mode == 6);
+    const bool h2 = c.fp16x2() && ((a.h2_ok || a.xmax_dev) && (mode == 0 || mode == 2) || mode == 6);
     const size_t bytes = (size_t)nchunks * mtiles * (one ? kTileBytes / 3 : (h2 ? kTileBytes * 2 / 3 : kTileBytes));
     const size_t bytes2 = mode == 5 ? (size_t)16 * (kTileBytes / 3) : 0;        // Wp's image behind the gate image
     // a READY step plan holds this launch's image (and its range word) already: wn_plan_prepare built them at the start of the
     // step; a recording plan notes the job, and this call prepares its own image as ever (plan.hip)
     const __bf16* pimg = nullptr; const unsigned* pwmax = nullptr;
-    const bool planned = plan_split_image(a, mode, mtiles, cps, nchunks, one ? 1 : (h2 ? 3 : 0), bytes, &pimg, &pwmax);
+    const bool planned = plan_split_image(c, a, mode, mtiles, cps, nchunks, one ? 1 : (h2 ? 3 : 0), bytes, &pimg, &pwmax);
     __bf16* img = planned ? const_cast<__bf16*>(pimg)
-                          : reinterpret_cast<__bf16*>(exec_scratch(bytes + bytes2, "the split weight image"));
+                          : reinterpret_cast<__bf16*>(c.scratch(bytes + bytes2, "the split weight image"));
     if (!img) return WN_EARG;
     if (planned) {
         a.wmax_dev = pwmax;
     } else {
     if (h2) {
         // the weights' own range: |w| <= 2^7 was an assumption (a weight above ~254 saturated the fp16 parts silently); one
-        // pass of the same grid over the weight tiles measures it, per entry-point call and weight set
+        // pass of the same grid over the weight tiles measures it, per call and weight set
         bool fresh = false;
         // keyed by the first weight array AND the launch's form: a second launch of the same call that starts at the same
         // array but covers another weight set (more sources, another mode) must measure its own maximum
-        unsigned* wm = exec_word(reinterpret_cast<const char*>(a.W[0]) + (((unsigned)mode & 7u) << 8 | ((unsigned)a.nsrc & 255u)), &fresh, s);
+        unsigned* wm = c.word(reinterpret_cast<const char*>(a.W[0]) + (((unsigned)mode & 7u) << 8 | ((unsigned)a.nsrc & 255u)), &fresh, s);
         if (!wm) return WN_EARG;
         a.wmax_dev = wm;
         if (fresh) hipLaunchKernelGGL(k_split_w<true>, dim3(nchunks * mtiles), dim3(256), 0, s, a, mode, mtiles, cps, img, 3);
@@ -933,7 +929,7 @@ int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s) {
     // the pipelined kernel takes sources that are equally spaced arrays of one chunk each with one row shift (the z of a
     // stack's layers), or a single source
     long long x_stride = 128;
-    bool lean = h2 && mt8 && mode == 0 && (nchunks & 1) == 0 && !exec_flag(WN_EXEC_NO_PIPELINED_GEMM) &&
+    bool lean = h2 && mt8 && mode == 0 && (nchunks & 1) == 0 && !c.flag(WN_EXEC_NO_PIPELINED_GEMM) &&
                 (a.N / a.rows_out_per_b + 1) * (long long)a.rows_src_per_b * (a.ldx ? a.ldx : a.K[0]) * 4 < (1ll << 32);   // 32-bit lane offsets
     if (lean && mode == 0 && a.nsrc > 1) {
         x_stride = (const char*)a.X[1] - (const char*)a.X[0];
@@ -944,15 +940,7 @@ int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s) {
         lean = a.nsrc == 1;
     }
     if (lean) {
-        static bool attr = false;
-        if (!attr) {
-#define Q_ATTR(MODE_, ACT_)                                                                                   \
-    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_colgemm_h2q<MODE_, ACT_>),                      \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kH2qLds))
-            Q_ATTR(0, WN_ACT_NONE); Q_ATTR(0, WN_ACT_RELU); Q_ATTR(0, WN_ACT_ELU);
-#undef Q_ATTR
-            attr = true;
-        }
+        WN_MAX_LDS_ONCE(kH2qLds, k_colgemm_h2q<0, WN_ACT_NONE>, k_colgemm_h2q<0, WN_ACT_RELU>, k_colgemm_h2q<0, WN_ACT_ELU>);
 #define Q_LAUNCH(MODE_, ACT_)                                                                                 \
     hipLaunchKernelGGL((k_colgemm_h2q<MODE_, ACT_>), grid, dim3(256), kH2qLds, s, a, (const __bf16*)img, mtiles, nchunks, x_stride)
         if (a.act == WN_ACT_RELU) Q_LAUNCH(0, WN_ACT_RELU);
@@ -979,7 +967,7 @@ int launch_colgemm_b3(CGArgs& a, int mode, int nprob, hipStream_t s) {
         CG_LAUNCH(4, WN_ACT_NONE);
     } else if (mode == 0) {
         // (k_colgemm_b3's epilogue is the one that fills a.outmax_dev: only now may the plan hand the word to a consumer)
-        if (a.outmax_dev) plan_xmax_written(a.out[0]);
+        if (a.outmax_dev) plan_xmax_written(c, a.out[0]);
         if (a.act == WN_ACT_RELU) CG_LAUNCH(0, WN_ACT_RELU);
         else if (a.act == WN_ACT_ELU) CG_LAUNCH(0, WN_ACT_ELU);
         else if (a.act == WN_ACT_NONE) CG_LAUNCH(0, WN_ACT_NONE);
@@ -1553,22 +1541,13 @@ __global__ void k_wgrad_b3w_reduce(WGArgs a, int nwg_x) {
 }
 
 // M == 256 and at least 8 problems: the wide block.  Picks its own row slabs (one workgroup per CU).
-int launch_wgrad_b3w(WGArgs& a_io, hipStream_t s) {
+int launch_wgrad_b3w(const Call& c, WGArgs& a_io, hipStream_t s) {
     WGArgs a = a_io;
-    static bool attr_set = false;
-    if (!attr_set) {
-#define W_ATTR(B2_, ACT_)                                                                               \
-    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_b3w<B2_, ACT_, 6>),                 \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * kTileBytes));        \
-    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_b3w<B2_, ACT_, 3>),                 \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * kTileBytes));        \
-    WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_b3w<B2_, ACT_, 1>),                 \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * kTileBytes))
-        W_ATTR(false, WN_ACT_NONE); W_ATTR(false, WN_ACT_RELU); W_ATTR(false, WN_ACT_ELU);
-        W_ATTR(true, WN_ACT_NONE); W_ATTR(true, WN_ACT_RELU); W_ATTR(true, WN_ACT_ELU);
-#undef W_ATTR
-        attr_set = true;
-    }
+#define W_KERNELS(B2_, ACT_) k_wgrad_b3w<B2_, ACT_, 6>, k_wgrad_b3w<B2_, ACT_, 3>, k_wgrad_b3w<B2_, ACT_, 1>
+    WN_MAX_LDS_ONCE(2 * 8 * kTileBytes, W_KERNELS(false, WN_ACT_NONE), W_KERNELS(false, WN_ACT_RELU),
+                    W_KERNELS(false, WN_ACT_ELU), W_KERNELS(true, WN_ACT_NONE), W_KERNELS(true, WN_ACT_RELU),
+                    W_KERNELS(true, WN_ACT_ELU));
+#undef W_KERNELS
     const int gy = (a.nprob + 7) / 8;
     int slabs = 256 / gy;                                    // workgroups in flight: one per CU
     if (slabs < 1) slabs = 1;
@@ -1588,12 +1567,12 @@ int launch_wgrad_b3w(WGArgs& a_io, hipStream_t s) {
     // atomics per workgroup into the same addresses -- cost more than the contraction; with long slabs (config 2's dWs: 85
     // chunks) the two cost the same (the partial tiles are ~60 MB of extra traffic) and this form is deterministic.
     const size_t part_bytes = (size_t)grid.x * grid.y * 8 * (8 * 16 * 64) * sizeof(float);
-    const bool one = one_term();
-    const bool h2 = half2_mode() && a.h2 && a.amax_dev && !any_b2;
+    const bool one = c.one_term();
+    const bool h2 = c.fp16x2() && a.h2 && a.amax_dev && !any_b2;
     // the bias gradient rides along in the six-term form (the head convolutions): 2 x slabs rows of 256 column sums
     const bool cs = a.colsum && !one && !h2 && !any_b2;
     const size_t cs_bytes = cs ? (size_t)grid.x * 2 * 256 * sizeof(float) : 0;
-    a.part = reinterpret_cast<float*>(exec_scratch(part_bytes + cs_bytes, "the weight-gradient partial tiles"));
+    a.part = reinterpret_cast<float*>(c.scratch(part_bytes + cs_bytes, "the weight-gradient partial tiles"));
     if (!a.part) return WN_EARG;
     a.colsum_part = cs ? a.part + part_bytes / sizeof(float) : nullptr;
     // the pipelined kernel clamps B's rows to the end of the slab only: every row a chunk can reach must lie inside B's clip,
@@ -1601,14 +1580,8 @@ int launch_wgrad_b3w(WGArgs& a_io, hipStream_t s) {
     // takes k_wgrad_b3w, which masks rows outside the clip
     bool clip_ok = a.off >= 0 && (long long)a.rows_A_per_b + a.off <= a.rows_B_per_b;
     for (int q = 0; q < a.nprob && clip_ok; ++q) clip_ok = a.offp[q] == 0;
-    if (h2 && clip_ok && a.lda == 256 && (long long)a.rows_B_per_b * a.ldb * 4 < (1ll << 31) && !exec_flag(WN_EXEC_NO_PIPELINED_GEMM)) {
-        static bool attr_p = false;
-        if (!attr_p) {
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_h2p<WN_ACT_NONE>), hipFuncAttributeMaxDynamicSharedMemorySize, kWpLds));
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_h2p<WN_ACT_RELU>), hipFuncAttributeMaxDynamicSharedMemorySize, kWpLds));
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_h2p<WN_ACT_ELU>), hipFuncAttributeMaxDynamicSharedMemorySize, kWpLds));
-            attr_p = true;
-        }
+    if (h2 && clip_ok && a.lda == 256 && (long long)a.rows_B_per_b * a.ldb * 4 < (1ll << 31) && !c.flag(WN_EXEC_NO_PIPELINED_GEMM)) {
+        WN_MAX_LDS_ONCE(kWpLds, k_wgrad_h2p<WN_ACT_NONE>, k_wgrad_h2p<WN_ACT_RELU>, k_wgrad_h2p<WN_ACT_ELU>);
         if (a.act == WN_ACT_RELU) hipLaunchKernelGGL((k_wgrad_h2p<WN_ACT_RELU>), grid, dim3(512), kWpLds, s, a);
         else if (a.act == WN_ACT_ELU) hipLaunchKernelGGL((k_wgrad_h2p<WN_ACT_ELU>), grid, dim3(512), kWpLds, s, a);
         else hipLaunchKernelGGL((k_wgrad_h2p<WN_ACT_NONE>), grid, dim3(512), kWpLds, s, a);
@@ -1641,11 +1614,11 @@ int launch_wgrad_b3w(WGArgs& a_io, hipStream_t s) {
     return WN_OK;
 }
 
-int launch_wgrad_b3(const WGArgs& a, int mt, dim3 grid, hipStream_t s) {
+int launch_wgrad_b3(const Call& c, const WGArgs& a, int mt, dim3 grid, hipStream_t s) {
     bool any_b2 = false, all_b2 = true;
     for (int q = 0; q < a.nprob; ++q) { any_b2 |= a.B2p[q] != nullptr; all_b2 &= a.B2p[q] != nullptr; }
     if (any_b2 != all_b2) { wn::set_error("wgrad_b3: the B2 factor must be given for all problems or for none"); return WN_EARG; }
-    const bool one = one_term();
+    const bool one = c.one_term();
 #define WG_LAUNCH_T(MT_, B2_, ACT_)                                                                     \
     do {                                                                                                \
         if (one) hipLaunchKernelGGL((k_wgrad_b3<MT_, B2_, ACT_, true>), grid, dim3(256), 0, s, a);      \

@@ -671,11 +671,10 @@ int mfma_layer_pack_h2(int L, const float* const* Wf, const float* const* Wg, co
 // layer l of a packed stack; only the one-tile-per-wave form exists (small launches take the fp32 kernel)
 // launches of at least this many workgroups (4 tiles each) take the one-tile-per-wave kernels; smaller ones the looping
 // fp32 kernel.  WnExec.fwd_t1_min_blocks overrides the threshold (1 = always, used by the parity tests; < 0 = never).
-static int t1_min_blocks() { return exec_fwd_t1_min_blocks(); }
-bool mfma_layer_fwd_h2_ok(int B, int T, int t_live) {
+bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live) {
     const int tile_lo = t_live > 0 ? t_live / 32 : 0;
     const long long nt = (long long)B * ((T + 31) / 32 - tile_lo);
-    return t1_min_blocks() > 0 && nt > 0 && (nt + 3) / 4 >= t1_min_blocks() && nt < (1ll << 31);
+    return c.fwd_t1_min_blocks > 0 && nt > 0 && (nt + 3) / 4 >= c.fwd_t1_min_blocks && nt < (1ll << 31);
 }
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
                       int d, int Z, int t_live, hipStream_t s) {
@@ -699,7 +698,7 @@ bool mfma_layer_supported(int Cr, int Cd, int fw) { return Cr == 32 && Cd == 32 
 
 // fs / gs: where tanh / sigmoid are saved for the backward: both (any backward), gs only (the chained stack backward,
 // which recovers tanh = z / sigmoid), or neither (inference)
-int mfma_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
+int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                    const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B, int T,
                    int d, int Z, int t_live, hipStream_t s) {
     // columns below t_live (a multiple of 32) are not computed: tiles_per_b counts the live tiles of a clip
@@ -713,7 +712,7 @@ int mfma_layer_fwd(const float* x, const float* Wf, const float* bf, const float
     const bool hb = bf || bg || bp;
     // enough workgroups to give every CU two to four of them (8-16 waves): one tile per wave; otherwise the looping kernel.
     // WnExec.fwd_t1_min_blocks overrides the threshold (1 = always, used by the parity tests; < 0 = never).
-    const int t1_min = t1_min_blocks();
+    const int t1_min = c.fwd_t1_min_blocks;
     if (t1_min > 0 && blocks >= t1_min) {
 #define FWD1_LAUNCH(SAVE, BIAS)                                                                              \
     hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \

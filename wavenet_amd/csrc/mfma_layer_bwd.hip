@@ -1325,11 +1325,11 @@ size_t mfma_layer_bwd_extra_ws_floats() { return (size_t)kMaxBlocks * kPartFloat
 // One layer of the chained backward.  Vin/Uin (either may be NULL): dout[t] = Vin[t] + Uin[t + dU] with rows below
 // vu_t0 taken as 0; columns below t_live are not computed (no gradient reaches them).  Returns the number of
 // workgroups (= partial weight-gradient tiles written to `part`) through *nwg.
-int mfma_layer_bwd_chain(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
+int mfma_layer_bwd_chain(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                          const float* Wp, const float* Vin, const float* Uin, int dU, int vu_t0, const float* dzs,
                          int dz_t0, float* Vout, float* Uout, float* part, int B, int T, int d, int Z, int t_live,
                          int* nwg, hipStream_t s, bool from_z) {
-    const bool h2w = gemm_mode() == WN_GEMM_FP16X2;           // weight-gradient contractions on fp16 x 2 split products
+    const bool h2w = c.fp16x2();        // weight-gradient contractions on fp16 x 2 split products
     const int tiles_all = (T + 31) / 32;
     const int tile_lo = t_live > 0 ? t_live / 32 : 0;
     const int tiles_per_b = tiles_all - tile_lo;
@@ -1344,12 +1344,7 @@ int mfma_layer_bwd_chain(const float* x, const float* f, const float* g, const f
     if (nwg) *nwg = blocks;
 #define CH_LAUNCH3(DO, UU, DZ, FZ, HW)                                                                            \
     do {                                                                                                           \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) {                                                                                           \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_layer_bwd_chainsp<DO, UU, DZ, FZ, HW>),      \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kCLdsBytes));                   \
-            attr_set = true;                                                                                       \
-        }                                                                                                          \
+        WN_MAX_LDS_ONCE(kCLdsBytes, k_layer_bwd_chainsp<DO, UU, DZ, FZ, HW>);                                      \
         hipLaunchKernelGGL((k_layer_bwd_chainsp<DO, UU, DZ, FZ, HW>), dim3(blocks), dim3(256), kCLdsBytes, s,       \
                            x, f, g, Wp, Wf, Wg, Vin, Uin, dU, vu_t0, dzs, dz_t0, Vout, Uout, part, B, T, d, Z,       \
                            tile_lo, tiles_per_b, ntiles);                                                          \
@@ -1391,13 +1386,13 @@ __global__ void k_chain_zero_sync(unsigned* sync, int n) {
 }
 size_t mfma_chain_multi_sync_words(int B, int T) { return (size_t)kChainSyncHead + (size_t)B * ((T + 31) / 32); }
 int mfma_chain_multi_max_layers() { return kChainMaxL; }
-int mfma_layer_bwd_chain_multi(int n, const int* layer, const float* const* Wf, const float* const* Wg,
+int mfma_layer_bwd_chain_multi(const Call& c, int n, const int* layer, const float* const* Wf, const float* const* Wg,
                                const float* const* Wp, const int* d, const int* Z, const int* t_live, const int* vu_t0,
                                const int* dU, const float* x0, const float* xs, const float* z, const float* g,
                                const float* dz, float* const* V, float* const* U, float* part, size_t part_stride,
                                unsigned* sync, int B, int T, int dz_t0, int* nwg, hipStream_t s, bool sync_zeroed) {
     WN_CHECK_ARG(n >= 1 && n <= kChainMaxL, "mfma_layer_bwd_chain_multi: 1..%d layers", kChainMaxL);
-    const bool h2w = gemm_mode() == WN_GEMM_FP16X2;           // else: every product on exact fp32 MFMA (bf16x3 / fp32 modes)
+    const bool h2w = c.fp16x2();        // else: every product on exact fp32 MFMA (bf16x3 / fp32 modes)
     const int tiles_all = (T + 31) / 32;
     ChainArgs a{};
     int blocks = 1;

@@ -65,8 +65,6 @@ static void* plan_alloc(StepPlan* P, size_t bytes, size_t align = 256) {
     return P->dev + off;
 }
 
-StepPlan* exec_plan();                             // api.hip: WnExec.plan of the current call
-
 // ---- hooks for the launchers ---------------------------------------------------------------------------------------
 static bool same_sources(const SplitJob& j, const CGArgs& a, int n, int mode) {
     for (int i = 0; i < n; ++i)
@@ -79,9 +77,9 @@ static bool same_sources(const SplitJob& j, const CGArgs& a, int n, int mode) {
 
 // launch_colgemm_b3: the image of this launch's weight tiles.  READY: true + *img / *wmax when the plan holds it.
 // RECORD: registers the job and returns false (the launcher prepares its own image this time).
-bool plan_split_image(const CGArgs& a, int mode, int mtiles, int cps, int nchunks, int one, size_t bytes,
+bool plan_split_image(const Call& c, const CGArgs& a, int mode, int mtiles, int cps, int nchunks, int one, size_t bytes,
                       const __bf16** img, const unsigned** wmax) {
-    StepPlan* P = exec_plan();
+    StepPlan* P = c.plan;
     if (!P || P->state == kPlanIdle) return false;
     if (!(mode == 0 || mode == 2 || mode == 6)) return false;
     const int nw = (mode == 2) ? mtiles : a.nsrc;                  // entries of W[] the split reads
@@ -111,8 +109,9 @@ bool plan_split_image(const CGArgs& a, int mode, int mtiles, int cps, int nchunk
 }
 
 // wn_stack_fwd: the fp16 x 2 images of the stack's fused layer kernels
-const void* plan_layer_h2_images(int L, const float* const* Wf, const float* const* Wg, const float* const* Wp) {
-    StepPlan* P = exec_plan();
+const void* plan_layer_h2_images(const Call& c, int L, const float* const* Wf, const float* const* Wg,
+                                 const float* const* Wp) {
+    StepPlan* P = c.plan;
     if (!P || P->state == kPlanIdle || L < 1 || L > 64) return nullptr;
     PlanDev& H = P->host;
     if (H.pack_L == L) {
@@ -132,8 +131,8 @@ const void* plan_layer_h2_images(int L, const float* const* Wf, const float* con
 }
 
 // wn_stack_bwd: the multi-layer backward's dataflow words, zeroed (word 1 = ~0) by wn_plan_prepare
-unsigned* plan_sync_words(int nwords) {
-    StepPlan* P = exec_plan();
+unsigned* plan_sync_words(const Call& c, int nwords) {
+    StepPlan* P = c.plan;
     if (!P || P->state == kPlanIdle || nwords < 2) return nullptr;
     if (P->state == kPlanRecord) { if (nwords > P->sync_words) P->sync_words = nwords; return nullptr; }
     if (P->sync && nwords <= P->sync_words) { ++P->hits; return P->sync; }
@@ -142,23 +141,24 @@ unsigned* plan_sync_words(int nwords) {
 }
 
 // a GEMM whose OUTPUT's range a later call of the step needs (the head's dx = dskip): the producer asks for the word
-// (zeroed by wn_plan_prepare) and folds max |out| into it; the consumer (exec_absmax) takes it when the array is the same
-unsigned* plan_xmax_producer() {
-    StepPlan* P = exec_plan();
+// (zeroed by wn_plan_prepare) and folds max |out| into it; the consumer (Call::absmax) takes it when the array is the same
+unsigned* plan_xmax_producer(const Call& c) {
+    StepPlan* P = c.plan;
     if (!P || P->state == kPlanIdle) return nullptr;
     if (P->state == kPlanRecord) { P->want_xmax = true; return nullptr; }
     return P->xmax;
 }
-void plan_xmax_written(const void* out) {           // the launch that fills the word is going out: `out` is what it describes
-    StepPlan* P = exec_plan();
+// the launch that fills the word is going out: `out` is what it describes
+void plan_xmax_written(const Call& c, const void* out) {
+    StepPlan* P = c.plan;
     if (!(P && P->state == kPlanReady && P->xmax)) return;
     // one word, one array: a second producer since wn_plan_prepare (a head of two convolutions) folds ITS maximum into the same
     // word -- an upper bound of either array, but a scale taken from a bound that is too large costs the smaller array its low
     // bits -- so from then on the word describes nothing and the consumer measures its operand itself
     P->xmax_src = (P->xmax_writes++ == 0) ? out : nullptr;
 }
-const unsigned* plan_xmax_consumer(const void* x) {
-    StepPlan* P = exec_plan();
+const unsigned* plan_xmax_consumer(const Call& c, const void* x) {
+    StepPlan* P = c.plan;
     if (!P || P->state != kPlanReady || !P->xmax || !x || P->xmax_src != x) return nullptr;
     ++P->hits;
     return P->xmax;

@@ -1,7 +1,7 @@
 // Whole residual stack in one call (WaveNet.forward_residual_block, wavenet.py:572-582, and its
 // backward): the per-layer loop of the reference runs here, in C++, on one stream, so the host
 // enqueues a 40-layer stack with two calls instead of ~250.  Pure orchestration: every kernel is
-// reached through the per-op entry points of this library.
+// reached through the launchers and dispatchers behind the per-op entry points, with this call's own wn::Call.
 #include <vector>
 
 #include "wn_kernels.hpp"
@@ -17,9 +17,9 @@ static int zero_prefix(int T, int d, int fw) {           // wavenet.py:303-340
 }
 // every layer on the fused 32-channel kernels and no conv / projection bias: the stack backward takes the chained path, which
 // reads z and sigmoid only (tanh = z / sigmoid)
-static bool chain_capable(const WnStackDesc* d) {
+static bool chain_capable(const Call& c, const WnStackDesc* d) {
     for (int l = 0; l < d->n_layers; ++l)
-        if (!layer_fast_path(d->Cr, d->cd[l], d->fw) || (d->bf && d->bf[l]) || (d->bg && d->bg[l]) || (d->bp && d->bp[l]))
+        if (!c.layer_fast_path(d->Cr, d->cd[l], d->fw) || (d->bf && d->bf[l]) || (d->bg && d->bg[l]) || (d->bp && d->bp[l]))
             return false;
     return true;
 }
@@ -29,6 +29,13 @@ static int check_desc(const WnStackDesc* d) {
     WN_CHECK_ARG(d->cd && d->dilation && d->Wf && d->Wg && d->Wp && d->Ws, "stack: NULL table");
     return WN_OK;
 }
+// every layer's width, dilation and weights, and its skip projection when the call runs the skip path
+static int check_layers(const WnStackDesc* d, bool skip) {
+    for (int l = 0; l < d->n_layers; ++l)
+        WN_CHECK_ARG(d->cd[l] > 0 && d->dilation[l] > 0 && d->Wf[l] && d->Wg[l] && d->Wp[l] && (!skip || d->Ws[l]),
+                     "stack: bad layer %d", l);
+    return WN_OK;
+}
 }  // namespace wn
 
 using namespace wn;
@@ -36,8 +43,7 @@ using namespace wn;
 extern "C" {
 
 int wn_stack_saves_tanh(const WnStackDesc* d, const WnExec* ex) {
-    wn::ExecScope exec__(ex);
-    return (check_desc(d) == WN_OK && chain_capable(d)) ? 0 : 1;
+    return (check_desc(d) == WN_OK && chain_capable(Call(ex), d)) ? 0 : 1;
 }
 
 size_t wn_stack_bwd_workspace_bytes(const WnStackDesc* d, int B, int T) {
@@ -62,13 +68,13 @@ size_t wn_stack_bwd_workspace_bytes(const WnStackDesc* d, int B, int T) {
 
 int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, float* f, float* g, float* skip,
                  int B, int T, int t_off, int compat_zero_prefix, int window_only, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    int rc = check_desc(d);
-    if (rc) return rc;
-    WN_CHECK_ARG(x && xs && z && B > 0 && T > 0, "wn_stack_fwd: bad argument");
+    int rc = check_precision(__func__, ex);
+    if (rc || (rc = check_desc(d)) || (rc = check_layers(d, skip != nullptr))) return rc;
+    WN_CHECK_ARG(x && xs && z && xs != x && B > 0 && T > 0, "wn_stack_fwd: bad argument");
     WN_CHECK_ARG(!f || g, "wn_stack_fwd: f without g");
     const bool g_only = g && !f;
-    WN_CHECK_ARG(!g_only || chain_capable(d), "wn_stack_fwd: this stack's backward needs tanh saved (wn_stack_saves_tanh)");
+    Call c(ex);
+    WN_CHECK_ARG(!g_only || chain_capable(c, d), "wn_stack_fwd: this stack's backward needs tanh saved (wn_stack_saves_tanh)");
     WN_CHECK_ARG(t_off >= 0 && t_off < T, "wn_stack_fwd: t_off outside [0,T)");
     const size_t n = (size_t)B * T;
     const int L = d->n_layers;
@@ -85,7 +91,7 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
         // layers without conv / projection biases
         bool fast = true;
         for (int l = 0; l < L && fast; ++l)
-            fast = layer_fast_path(d->Cr, d->cd[l], d->fw) && !(d->bf && d->bf[l]) && !(d->bg && d->bg[l]) &&
+            fast = c.layer_fast_path(d->Cr, d->cd[l], d->fw) && !(d->bf && d->bf[l]) && !(d->bg && d->bg[l]) &&
                    !(d->bp && d->bp[l]);
         if (fast) {
             live[L - 1] = (t_off / 32) * 32;
@@ -99,16 +105,15 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
     // of the fused kernel on weight images split once for the whole stack (into the call's scratch: the skip
     // contraction re-uses it after the last layer)
     const void* h2img = nullptr;
-    if (gemm_mode() == WN_GEMM_FP16X2 && L <= 64 && d->Cr == 32 && d->fw == 2 &&
-        exec_has_scratch(mfma_layer_h2_image_bytes(L))) {
+    if (c.fp16x2() && L <= 64 && d->Cr == 32 && d->fw == 2 && c.has_scratch(mfma_layer_h2_image_bytes(L))) {
         bool ok = true;
         for (int l = 0; l < L && ok; ++l)
             ok = d->cd[l] == 32 && !(d->bf && d->bf[l]) && !(d->bg && d->bg[l]) && !(d->bp && d->bp[l]);
         if (ok) {
             // (a READY step plan built the images at the start of the step: plan.hip)
-            h2img = plan_layer_h2_images(L, d->Wf, d->Wg, d->Wp);
+            h2img = plan_layer_h2_images(c, L, d->Wf, d->Wg, d->Wp);
             if (!h2img) {
-                void* img = exec_scratch(mfma_layer_h2_image_bytes(L), "the fp16 x 2 layer weight images");
+                void* img = c.scratch(mfma_layer_h2_image_bytes(L), "the fp16 x 2 layer weight images");
                 if ((rc = mfma_layer_pack_h2(L, d->Wf, d->Wg, d->Wp, img, as_stream(stream)))) return rc;
                 h2img = img;
             }
@@ -124,7 +129,7 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
             // (fp16 x 2 only.  The same group on exact fp32 MFMA -- k_layer_fwd_f32_grp, round 6 -- was built, bit-identical to
             // the per-layer launches, and 3.5 % SLOWER on the bf16x3 step (3.844 against 3.712 ms, same box): 80 fp32 MFMAs per
             // tile-layer are MFMA-bound at the per-layer kernel's 16 waves per CU already, and the halo tile adds 12.5 %)
-            int ng = (h2img && !exec_flag(WN_EXEC_NO_FWD_GROUPS) && mfma_layer_fwd_h2_ok(B, T, 0))
+            int ng = (h2img && !c.flag(WN_EXEC_NO_FWD_GROUPS) && mfma_layer_fwd_h2_ok(c, B, T, 0))
                          ? mfma_layer_fwd_group_len(d->dilation, l, L) : 0;
             for (int k = 0; k < ng; ++k)
                 if (live[l + k] > 0) ng = 0;
@@ -149,19 +154,20 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
                 l += ng - 1;
                 continue;
             }
-            if (h2img && mfma_layer_fwd_h2_ok(B, T, live[l])) {
+            if (h2img && mfma_layer_fwd_h2_ok(c, B, T, live[l])) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd_h2(in, h2img, l, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr, B, T,
                                        d->dilation[l], Z, live[l], as_stream(stream));
             } else if (live[l] > 0 || g_only) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
-                rc = mfma_layer_fwd(in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr,
+                rc = mfma_layer_fwd(c, in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr,
                                     d->Wp[l], d->bp ? d->bp[l] : nullptr, out, z + zoff, f ? f + zoff : nullptr,
                                     g ? g + zoff : nullptr, B, T, d->dilation[l], Z, live[l], as_stream(stream));
             } else {
-                rc = wn_layer_fwd(in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr, d->Wp[l],
-                                  d->bp ? d->bp[l] : nullptr, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr,
-                                  B, T, d->Cr, d->cd[l], d->fw, d->dilation[l], Z, ex, stream);
+                wn::ProfScope prof__("wn_layer_fwd", stream);
+                rc = layer_fwd(c, in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr, d->Wp[l],
+                               d->bp ? d->bp[l] : nullptr, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr,
+                               B, T, d->Cr, d->cd[l], d->fw, d->dilation[l], Z, as_stream(stream));
             }
             if (rc) return rc;
             zp[l] = z + zoff;
@@ -169,8 +175,10 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
             in = out;
         }
     }
-    if (skip)
-        return wn_skip_sum_fwd(L, zp.data(), d->Ws, d->bs, d->cd, skip, B, T, t_off, T - t_off, d->Cs, 0, ex, stream);
+    if (skip) {
+        wn::ProfScope prof__("wn_skip_sum_fwd", stream);
+        return skip_sum_fwd(c, L, zp.data(), d->Ws, d->bs, d->cd, skip, B, T, t_off, T - t_off, d->Cs, 0, as_stream(stream));
+    }
     return WN_OK;
 }
 
@@ -179,17 +187,18 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
                  float* const* dWf, float* const* dbf, float* const* dWg, float* const* dbg, float* const* dWp,
                  float* const* dbp, float* const* dWs, float* const* dbs, float* ws, size_t ws_bytes, int B, int T,
                  int t_off, int compat_zero_prefix, const WnExec* ex, void* stream) {
-    wn::ExecScope exec__(ex);
-    int rc = check_desc(d);
-    if (rc) return rc;
+    int rc = check_precision(__func__, ex);
+    if (rc || (rc = check_desc(d)) || (rc = check_layers(d, dskip != nullptr))) return rc;
     WN_CHECK_ARG(x && xs && z && g && ws && dWf && dWg && dWp, "wn_stack_bwd: NULL argument");
+    WN_CHECK_ARG(B > 0 && T > 0 && t_off >= 0 && t_off < T, "wn_stack_bwd: non-positive size or t_off outside [0,T)");
+    Call c(ex);
     // ---- chained path: every layer on the MFMA kernels and no conv / projection bias GRADIENTS asked for.  It is the only
     // path that recovers tanh from z / sigmoid, so f may be NULL exactly when it is taken (a desc without biases but with
     // non-NULL dbf / dbg / dbp tables takes the per-layer path, which reads f).
     bool chain = true;
     for (int l = 0; l < d->n_layers && chain; ++l)
-        chain = layer_fast_path(d->Cr, d->cd[l], d->fw) && !(dbf && dbf[l]) && !(dbg && dbg[l]) && !(dbp && dbp[l]);
-    WN_CHECK_ARG(f || (chain && chain_capable(d)),
+        chain = c.layer_fast_path(d->Cr, d->cd[l], d->fw) && !(dbf && dbf[l]) && !(dbg && dbg[l]) && !(dbp && dbp[l]);
+    WN_CHECK_ARG(f || (chain && chain_capable(c, d)),
                  "wn_stack_bwd: this stack's backward needs tanh saved (wn_stack_saves_tanh; bias-gradient tables select the "
                  "per-layer path, which reads f)");
     WN_CHECK_ARG(dout || dskip, "wn_stack_bwd: no incoming gradient");
@@ -214,13 +223,15 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
         if (chain && d->Cs % 32 == 0) {
             // the chained layer kernels take dz as 0 below t_off and never read it there: only the loss window is computed
             wn::ProfScope prof__("wn_skip_sum_bwd_dz", stream);
-            rc = mfma_skip_bwd_dz(L, d->Ws, d->cd, dskip, dzp.data(), B, T, t_off, Tw, d->Cs, true, as_stream(stream));
+            rc = mfma_skip_bwd_dz(c, L, d->Ws, d->cd, dskip, dzp.data(), B, T, t_off, Tw, d->Cs, true, as_stream(stream));
         } else {
-            rc = wn_skip_sum_bwd_dz(L, d->Ws, d->cd, dskip, dzp.data(), B, T, t_off, Tw, d->Cs, ex, stream);
+            wn::ProfScope prof__("wn_skip_sum_bwd_dz", stream);
+            rc = skip_bwd_dz(c, L, d->Ws, d->cd, dskip, dzp.data(), B, T, t_off, Tw, d->Cs, as_stream(stream));
         }
         if (rc) return rc;
         if (dWs) {
-            rc = wn_skip_sum_bwd_dw(L, zp.data(), d->cd, dskip, dWs, dbs, B, T, t_off, Tw, d->Cs, ex, stream);
+            wn::ProfScope prof__("wn_skip_sum_bwd_dw", stream);
+            rc = skip_bwd_dw(c, L, zp.data(), d->cd, dskip, dWs, dbs, B, T, t_off, Tw, d->Cs, as_stream(stream));
             if (rc) return rc;
         }
     }
@@ -239,7 +250,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
         float* vu3 = reinterpret_cast<float*>(sync) + ((mfma_chain_multi_sync_words(B, T) + 63) / 64) * 64;
         // a READY step plan owns the dataflow words and zeroed them at the start of the step (no k_chain_zero_sync launch)
         bool sync_zeroed = false;
-        if (unsigned* ps = plan_sync_words((int)mfma_chain_multi_sync_words(B, T))) { sync = ps; sync_zeroed = true; }
+        if (unsigned* ps = plan_sync_words(c, (int)mfma_chain_multi_sync_words(B, T))) { sync = ps; sync_zeroed = true; }
         float* Vb[3] = {vu, vu + n * d->Cr, vu3};
         float* Ub[3] = {vu + 2 * n * d->Cr, vu + 3 * n * d->Cr, vu3 + n * d->Cr};
         const float* Vin = dout;
@@ -255,8 +266,8 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
         // one) runs in ONE launch of co-resident workgroups following per-tile dataflow words (k_layer_bwd_chain_multi: no grid
         // barrier); the per-layer loop below
         // then only collects their parameters
-        const bool multi = gemm_mode() != WN_GEMM_BF16 && f == nullptr && dskip && d->Cs % 32 == 0 && L >= 3 &&
-                           L - 1 <= mfma_chain_multi_max_layers() && !exec_flag(WN_EXEC_NO_MULTI_LAYER_BWD);
+        const bool multi = !c.one_term() && f == nullptr && dskip && d->Cs % 32 == 0 && L >= 3 &&
+                           L - 1 <= mfma_chain_multi_max_layers() && !c.flag(WN_EXEC_NO_MULTI_LAYER_BWD);
         std::vector<int> m_layer, m_d, m_Z, m_live, m_vu_t0, m_dU;
         std::vector<const float*> m_Wf, m_Wg, m_Wp;
         for (int l = L - 1; l >= 0; --l) {
@@ -268,7 +279,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
                 m_vu_t0.push_back(vu_t0); m_dU.push_back(dU);
                 m_Wf.push_back(d->Wf[l]); m_Wg.push_back(d->Wg[l]); m_Wp.push_back(d->Wp[l]);
             } else {
-                rc = mfma_layer_bwd_chain(in, f ? f + off[l] : z + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], Vin, Uin,
+                rc = mfma_layer_bwd_chain(c, in, f ? f + off[l] : z + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], Vin, Uin,
                                           dU, vu_t0, dskip ? dzp[l] : nullptr, (dskip && d->Cs % 32 == 0) ? t_off : 0,
                                           Vb[l % 3], Ub[l % 3], parts + (size_t)l * mfma_chain_part_floats(), B, T,
                                           d->dilation[l], Z, live, &nwg[l], as_stream(stream), f == nullptr);
@@ -282,7 +293,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
         }
         if (!m_layer.empty()) {
             int grid = 0;
-            rc = mfma_layer_bwd_chain_multi((int)m_layer.size(), m_layer.data(), m_Wf.data(), m_Wg.data(), m_Wp.data(),
+            rc = mfma_layer_bwd_chain_multi(c, (int)m_layer.size(), m_layer.data(), m_Wf.data(), m_Wg.data(), m_Wp.data(),
                                             m_d.data(), m_Z.data(), m_live.data(), m_vu_t0.data(), m_dU.data(), x, xs, z, g,
                                             ws /* dz of layer l at ws + l n 32 */, Vb, Ub, parts, mfma_chain_part_floats(),
                                             sync, B, T, t_off, &grid, as_stream(stream), sync_zeroed);
@@ -291,7 +302,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
                 for (size_t i = 0; i < m_layer.size(); ++i) {
                     const int l = m_layer[i];
                     const float* in = l == 0 ? x : xs + (size_t)(l - 1) * n * d->Cr;
-                    rc = mfma_layer_bwd_chain(in, z + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], Vb[(l + 1) % 3],
+                    rc = mfma_layer_bwd_chain(c, in, z + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], Vb[(l + 1) % 3],
                                               Ub[(l + 1) % 3], m_dU[i], m_vu_t0[i], dzp[l], t_off, Vb[l % 3], Ub[l % 3],
                                               parts + (size_t)l * mfma_chain_part_floats(), B, T, m_d[i], m_Z[i], m_live[i],
                                               &nwg[l], as_stream(stream), true);
@@ -311,16 +322,18 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
         const float* in = l == 0 ? x : xs + (size_t)(l - 1) * n * d->Cr;
         float* gin = (l == 0) ? dx : gbuf[l & 1];
         int Z = compat_zero_prefix ? zero_prefix(T, d->dilation[l], d->fw) : 0;
-        if (wide_layer_in_use(d->Cr, d->cd[l], d->fw)) {      // the stack still holds z = f g: the projection gradient reads it
-            wn::ProfScope prof__("wn_layer_bwd", stream);
-            rc = wide_layer_bwd(in, f + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], gout, dskip ? dzp[l] : nullptr,
+        wn::ProfScope prof__("wn_layer_bwd", stream);
+        if (c.wide_layer(d->Cr, d->cd[l], d->fw)) {      // the stack still holds z = f g: the projection gradient reads it
+            rc = wide_layer_bwd(c, in, f + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], gout, dskip ? dzp[l] : nullptr,
                                 gin, dWf[l], dbf ? dbf[l] : nullptr, dWg[l], dbg ? dbg[l] : nullptr,
                                 gout ? dWp[l] : nullptr, (gout && dbp) ? dbp[l] : nullptr, dab, B, T, d->Cr, d->cd[l],
                                 d->fw, d->dilation[l], Z, as_stream(stream), z + off[l]);
-        } else
-        rc = wn_layer_bwd(in, f + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], gout, dskip ? dzp[l] : nullptr, gin,
-                          dWf[l], dbf ? dbf[l] : nullptr, dWg[l], dbg ? dbg[l] : nullptr, gout ? dWp[l] : nullptr,
-                          (gout && dbp) ? dbp[l] : nullptr, dab, B, T, d->Cr, d->cd[l], d->fw, d->dilation[l], Z, ex, stream);
+        } else {
+            rc = layer_bwd(c, in, f + off[l], g + off[l], d->Wf[l], d->Wg[l], d->Wp[l], gout, dskip ? dzp[l] : nullptr, gin,
+                           dWf[l], dbf ? dbf[l] : nullptr, dWg[l], dbg ? dbg[l] : nullptr, gout ? dWp[l] : nullptr,
+                           (gout && dbp) ? dbp[l] : nullptr, dab, B, T, d->Cr, d->cd[l], d->fw, d->dilation[l], Z,
+                           as_stream(stream));
+        }
         if (rc) return rc;
         gout = gin;
         if (!gin) break;          // l == 0 and the caller does not want dx

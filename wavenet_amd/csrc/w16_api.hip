@@ -340,10 +340,9 @@ int wn16_pointwise_bwd(const uint16_t* x, const uint16_t* WbT, const uint16_t* d
     if (dbias) {
         if (!dout_f32) { wn::set_error("wn16_pointwise_bwd: the bias gradient is summed from the fp32 gradient"); return WN_EARG; }
         // with a workspace the column sums leave per-chunk partials that one kernel adds in a fixed order (no atomics)
-        WnExec ex{WN_GEMM_BF16, 0u, ws ? reinterpret_cast<char*>(ws) + kWgPartBytes : nullptr,
-                  ws ? ws_bytes - kWgPartBytes : (size_t)0, 0, 0};
-        wn::ExecScope scope__(ws ? &ex : nullptr);
-        if ((rc = wn::generic_colsum(dout_f32, 1, (int)N, 0, Cout, Cout, dbias, s))) return rc;
+        void* cs_ws = ws ? reinterpret_cast<char*>(ws) + kWgPartBytes : nullptr;
+        if ((rc = wn::generic_colsum(dout_f32, 1, (int)N, 0, Cout, Cout, dbias, cs_ws, ws ? ws_bytes - kWgPartBytes : 0, s)))
+            return rc;
     }
     return WN_OK;
 }

@@ -180,12 +180,7 @@ int launch_cgemm(CG16& a, hipStream_t s) {
     const int grid = a.n_blocks * (a.M / 128);
 #define CGL(RX, EP, F32)                                                                                          \
     do {                                                                                                          \
-        static bool attr = false;                                                                                 \
-        if (!attr) {                                                                                              \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_cgemm<RX, EP, F32>),                     \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kCgLds));                      \
-            attr = true;                                                                                          \
-        }                                                                                                         \
+        WN_MAX_LDS_ONCE(kCgLds, k16_cgemm<RX, EP, F32>);                                                          \
         hipLaunchKernelGGL((k16_cgemm<RX, EP, F32>), dim3(grid), dim3(512), kCgLds, s, a);                        \
     } while (0)
     const int key = (a.relu_x ? 8 : 0) | (a.ep << 1) | (a.out_f32 ? 1 : 0);
@@ -395,12 +390,7 @@ static int launch_cgemm256(CG16& a, hipStream_t s) {
     a.blocks_per_b = (a.rows_per_b + 255) / 256;
     a.n_blocks = a.B * a.blocks_per_b;
     const int grid = a.n_blocks * (a.M / 256);
-    static bool attr = false;
-    if (!attr) {
-        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_cgemm256), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kCg256Lds));
-        attr = true;
-    }
+    WN_MAX_LDS_ONCE(kCg256Lds, k16_cgemm256);
     hipLaunchKernelGGL(k16_cgemm256, dim3(grid), dim3(512), kCg256Lds, s, a);
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -645,12 +635,7 @@ int launch_wgrad16(const WG16& a_in, int nprob, hipStream_t s) {
     const int grid = (used + 7) & ~7;
 #define WGL(RB)                                                                                                   \
     do {                                                                                                          \
-        static bool attr = false;                                                                                 \
-        if (!attr) {                                                                                              \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_wgrad<RB>),                              \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kWgLds));                      \
-            attr = true;                                                                                          \
-        }                                                                                                         \
+        WN_MAX_LDS_ONCE(kWgLds, k16_wgrad<RB>);                                                                   \
         hipLaunchKernelGGL((k16_wgrad<RB>), dim3(grid), dim3(512), kWgLds, s, a);                                 \
     } while (0)
     if (a.relu_b) WGL(true); else WGL(false);
@@ -1128,12 +1113,7 @@ int embed_fwd16(const int32_t* idx, const float* W, const float* bias, bf16* out
     const long long N = (long long)B * T;
     const size_t lds = (size_t)2 * Q * 64 * sizeof(float);
     if (C % 64 == 0 && lds <= 144 * 1024 && N >= 8 * kEmbTok) {
-        static bool attr = false;
-        if (!attr) {
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_embed_fwd_lds),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-            attr = true;
-        }
+        WN_MAX_LDS_ONCE(144 * 1024, k16_embed_fwd_lds);
         hipLaunchKernelGGL(k16_embed_fwd_lds, dim3((unsigned)((N + kEmbTok - 1) / kEmbTok), C / 64), dim3(256), lds, s, idx, W,
                            bias, out, N, T, Q, C);
         WN_LAUNCH_CHECK();
@@ -1166,12 +1146,7 @@ int embed_bwd_mfma(const int32_t* idx, const bf16* dx, const float* dx_f32, int 
     const int nwg = nch < 256 ? nch : 256;
     float* bsum = dbias ? part + (size_t)nwg * 2 * 256 * C : nullptr;
     if (!dx_f32) {
-        static bool attr = false;
-        if (!attr) {
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_embed_bwd),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kEbLds));
-            attr = true;
-        }
+        WN_MAX_LDS_ONCE(kEbLds, k16_embed_bwd);
         hipLaunchKernelGGL(k16_embed_bwd, dim3(nwg), dim3(512), kEbLds, s, tokp, dx, part, B, T, Tp);
     } else if (C == 32) {
         hipLaunchKernelGGL(k16_embed_bwd_f32<1>, dim3(nwg), dim3(512), 0, s, tokp, dx_f32, part, B, T, Tp);

@@ -727,12 +727,7 @@ static int grid_for(int ntiles, int per_cu) {
 int fwd_layer(const bf16* x, const bf16* img, bf16* out, bf16* z, int B, int T, int d, int Z, hipStream_t s) {
     const int tiles_per_b = (T + kLT - 1) / kLT;
     const int ntiles = B * tiles_per_b;
-    static bool attr = false;
-    if (!attr) {
-        WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   kFwdLds));
-        attr = true;
-    }
+    WN_MAX_LDS_ONCE(kFwdLds, k16_fwd);
     hipLaunchKernelGGL(k16_fwd, dim3(grid_for(ntiles, 2)), dim3(256), kFwdLds, s, x, img, img + kConvA, out, z, B, T, d, Z,
                        tiles_per_b, ntiles);
     WN_LAUNCH_CHECK();
@@ -746,12 +741,7 @@ int gate_bwd_layer(const bf16* x, const bf16* img, const bf16* dout, const bf16*
     const int grid = grid_for(ntiles, 1);
 #define GB_LAUNCH(DO, DZ)                                                                                              \
     do {                                                                                                               \
-        static bool attr = false;                                                                                      \
-        if (!attr) {                                                                                                   \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_gate_bwd<DO, DZ>),                            \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kGateLds));                         \
-            attr = true;                                                                                               \
-        }                                                                                                              \
+        WN_MAX_LDS_ONCE(kGateLds, k16_gate_bwd<DO, DZ>);                                                               \
         hipLaunchKernelGGL((k16_gate_bwd<DO, DZ>), dim3(grid), dim3(512), kGateLds, s, x, img + kOffConvA8,           \
                            img + kOffDzA8, dout, dzs, dz_t0, dadg, B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero);  \
     } while (0)
@@ -774,12 +764,7 @@ int dx_layer(const bf16* dadg, const bf16* img, const bf16* dout, const bf16* zp
     const int grid = dx_grid(B, T);
 #define DX_LAUNCH(DO, ZZ)                                                                                              \
     do {                                                                                                               \
-        static bool attr = false;                                                                                      \
-        if (!attr) {                                                                                                   \
-            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k16_dx<DO, ZZ>),                                  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kDxLds));                           \
-            attr = true;                                                                                               \
-        }                                                                                                              \
+        WN_MAX_LDS_ONCE(kDxLds, k16_dx<DO, ZZ>);                                                                       \
         hipLaunchKernelGGL((k16_dx<DO, ZZ>), dim3(grid), dim3(512), kDxLds, s, dadg, img + kOffDxA, dout,                \
                            zprev, dx, dwp_part, B, T, d, tiles_per_b, ntiles, t_live, t_gate, zero_dead);             \
     } while (0)

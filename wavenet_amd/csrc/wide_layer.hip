@@ -57,7 +57,7 @@ static void base_args(CGArgs& a, int B, int T) {
 }
 
 // one dilated conv: out[b,t,:] = sum_k W[:, :, k] x[b, t-(fw-1-k)d, :] + bias
-static int conv_gemm(const float* x, const float* W, const float* bias, float* out, int B, int T, int Cin, int Cout,
+static int conv_gemm(Call& c, const float* x, const float* W, const float* bias, float* out, int B, int T, int Cin, int Cout,
                      int fw, int d, hipStream_t s) {
     CGArgs a{};
     base_args(a, B, T);
@@ -67,15 +67,15 @@ static int conv_gemm(const float* x, const float* W, const float* bias, float* o
         a.bias[k] = k == 0 ? bias : nullptr;
     }
     a.wsk = fw; a.M = Cout; a.ldo = Cout; a.out[0] = out;
-    return launch_colgemm_multi(a, s);
+    return launch_colgemm_multi(c, a, s);
 }
 
-int wide_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg, const float* Wp,
+int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg, const float* Wp,
                    const float* bp, float* out, float* z, float* fs, float* gs, int B, int T, int Cr, int Cd, int fw,
                    int d, int Z, hipStream_t s) {
     // pre-activations go where f / sigmoid(g) will live (training) or into z / out (inference, needs Cd <= Cr)
     int rc;
-    if (gemm_b3_enabled() && Cd % 64 == 0) {
+    if (c.split_b3() && Cd % 64 == 0) {
         // one launch for both convolutions and the gate: the rows of Wf and Wg interleaved tile by tile, tanh / sigmoid /
         // product in the epilogue -- x is read once per tap, the pre-activations never reach memory
         CGArgs a{};
@@ -87,25 +87,25 @@ int wide_layer_fwd(const float* x, const float* Wf, const float* bf, const float
         }
         a.wsk = fw; a.M = Cd; a.ldo = Cd; a.out[0] = z;
         a.gate_z = z; a.gate_f = fs; a.gate_s = gs; a.gate_Z = Z;
-        if (gemm_mode() == 2 && Cr == 128 && Cd == 128) {
+        if (c.one_term() && Cr == 128 && Cd == 128) {
             // bf16 operands, 128/128 channels (config 5): the residual projection runs in the same kernel, on z taken from
             // registers -- one launch per layer, z is written but never read back
             a.ldo = Cr; a.out[0] = out; a.residual = x; a.proj_W = Wp; a.proj_bias = bp;
-            return launch_colgemm_b3(a, 5, 1, s);
+            return launch_colgemm_b3(c, a, 5, 1, s);
         }
-        if ((rc = launch_colgemm_b3(a, 3, 1, s))) return rc;
+        if ((rc = launch_colgemm_b3(c, a, 3, 1, s))) return rc;
         CGArgs b{};
         base_args(b, B, T);
         b.nsrc = 1; b.X[0] = z; b.K[0] = Cd; b.W[0] = Wp; b.wsm[0] = Cd; b.wsk = 1; b.bias[0] = bp;
         b.M = Cr; b.ldo = Cr; b.out[0] = out; b.residual = x;
-        return launch_colgemm_multi(b, s);
+        return launch_colgemm_multi(c, b, s);
     }
     float* abuf = fs ? fs : z;
     float* gbuf = gs ? gs : out;
     if (!gs && Cd > Cr) { wn::set_error("wide_layer_fwd: inference needs Cd <= Cr"); return WN_ESHAPE; }
-    rc = conv_gemm(x, Wf, bf, abuf, B, T, Cr, Cd, fw, d, s);
+    rc = conv_gemm(c, x, Wf, bf, abuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
-    rc = conv_gemm(x, Wg, bg, gbuf, B, T, Cr, Cd, fw, d, s);
+    rc = conv_gemm(c, x, Wg, bg, gbuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
     const long long n4 = (long long)B * T * Cd / 4;
     hipLaunchKernelGGL(k_wide_gate, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z);
@@ -114,11 +114,11 @@ int wide_layer_fwd(const float* x, const float* Wf, const float* bf, const float
     base_args(a, B, T);
     a.nsrc = 1; a.X[0] = z; a.K[0] = Cd; a.W[0] = Wp; a.wsm[0] = Cd; a.wsk = 1; a.bias[0] = bp;
     a.M = Cr; a.ldo = Cr; a.out[0] = out; a.residual = x;
-    return launch_colgemm_multi(a, s);
+    return launch_colgemm_multi(c, a, s);
 }
 
 // dW[o][c][k] += sum_n A[n][o] * x[n - (fw-1-k)d][c]
-static int conv_wgrad(const float* A, const float* x, float* dW, int B, int T, int Cin, int Cout, int fw, int d,
+static int conv_wgrad(const Call& c, const float* A, const float* x, float* dW, int B, int T, int Cin, int Cout, int fw, int d,
                       hipStream_t s) {
     for (int k = 0; k < fw; ++k)
         for (int c0 = 0; c0 < Cin; c0 += 32 * WN_MAX_SRC) {
@@ -129,7 +129,7 @@ static int conv_wgrad(const float* A, const float* x, float* dW, int B, int T, i
             }
             a.ldb = Cin; a.ldo = Cin * fw; a.osk = fw;
             a.nB = B; a.rows_A_per_b = T; a.rows_B_per_b = T; a.off = -(fw - 1 - k) * d; a.act = WN_ACT_NONE;
-            int rc = launch_wgrad(a, Cout, s);
+            int rc = launch_wgrad(c, a, Cout, s);
             if (rc) return rc;
         }
     return WN_OK;
@@ -140,7 +140,7 @@ static int conv_wgrad(const float* A, const float* x, float* dW, int B, int T, i
 //   * all 2 fw weight-gradient contractions of the layer (dWf_k, dWg_k: 256 rows of [da | dg] against the 32-channel
 //     slices of x at fw tap shifts) are ONE launch of the wide 256-row block, which reads [da | dg] once instead of
 //     2 fw times.
-static int wide_layer_bwd_256(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
+static int wide_layer_bwd_256(Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                               const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                               float* dWg, float* dbg, float* dWp, float* dbp, float* ws, int B, int T, int Cr, int Cd,
                               int fw, int d, int Z, const float* z, hipStream_t s) {
@@ -153,7 +153,7 @@ static int wide_layer_bwd_256(const float* x, const float* f, const float* g, co
         a.nsrc = 1; a.X[0] = dout; a.K[0] = Cr; a.W[0] = Wp; a.wsm[0] = 1; a.wsk = Cd; a.bias[0] = nullptr;
         a.M = Cd; a.ldo = Cd; a.out[0] = dadg; a.residual = dzs;
         a.gate_f = const_cast<float*>(f); a.gate_s = const_cast<float*>(g); a.gate_z = dadg; a.gate_Z = Z;
-        if ((rc = launch_colgemm_b3(a, 4, 1, s))) return rc;
+        if ((rc = launch_colgemm_b3(c, a, 4, 1, s))) return rc;
     } else {
         const long long n4 = n * Cd / 4;
         hipLaunchKernelGGL(k_wide_gate_bwd, dim3(cdiv(n4, 256)), dim3(256), 0, s, dzs, f, g, dadg, dadg + Cd, n4, T, Cd, Z,
@@ -172,7 +172,7 @@ static int wide_layer_bwd_256(const float* x, const float* f, const float* g, co
                 a.soff[i] = (fw - 1 - k) * d; a.bias[i] = nullptr;
             }
         a.wsk = Cr * fw; a.M = Cr; a.ldo = Cr; a.out[0] = dx; a.residual = dout;
-        if ((rc = launch_colgemm_multi(a, s))) return rc;
+        if ((rc = launch_colgemm_multi(c, a, s))) return rc;
     }
     {                                // dWf[o][c][k] += sum da[n][o] x[n-(fw-1-k)d][c];  dWg likewise from the dg half
         WGArgs a{};
@@ -185,7 +185,7 @@ static int wide_layer_bwd_256(const float* x, const float* f, const float* g, co
             }
         a.ldb = Cr; a.ldo = Cr * fw; a.osk = fw;
         a.nB = B; a.rows_A_per_b = T; a.rows_B_per_b = T; a.off = 0; a.act = WN_ACT_NONE;
-        if ((rc = launch_wgrad_b3w(a, s))) return rc;
+        if ((rc = launch_wgrad_b3w(c, a, s))) return rc;
     }
     if (dWp && dout) {               // dWp[cr][cd] += sum dout[n][cr] * (f g)[n][cd]
         WGArgs a{};
@@ -195,21 +195,21 @@ static int wide_layer_bwd_256(const float* x, const float* f, const float* g, co
         }
         a.ldb = Cd; a.ldo = Cd; a.osk = 1;
         a.nB = B; a.rows_A_per_b = T; a.rows_B_per_b = T; a.off = 0; a.act = WN_ACT_NONE;
-        if ((rc = launch_wgrad(a, Cr, s))) return rc;
+        if ((rc = launch_wgrad(c, a, Cr, s))) return rc;
     }
-    if (dbf && (rc = generic_colsum(dadg, B, T, 0, 2 * Cd, Cd, dbf, s))) return rc;
-    if (dbg && (rc = generic_colsum(dadg + Cd, B, T, 0, 2 * Cd, Cd, dbg, s))) return rc;
-    if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, s))) return rc;
+    if (dbf && (rc = generic_colsum(dadg, B, T, 0, 2 * Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
+    if (dbg && (rc = generic_colsum(dadg + Cd, B, T, 0, 2 * Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
 
-int wide_layer_bwd(const float* x, const float* f, const float* g, const float* Wf, const float* Wg, const float* Wp,
+int wide_layer_bwd(Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg, const float* Wp,
                    const float* dout, const float* dzs, float* dx, float* dWf, float* dbf, float* dWg, float* dbg,
                    float* dWp, float* dbp, float* ws, int B, int T, int Cr, int Cd, int fw, int d, int Z,
                    hipStream_t s, const float* z) {
     const long long n = (long long)B * T;
-    if (gemm_b3_enabled() && 2 * Cd == 256 && Cr % 32 == 0 && (Cr / 32) * fw <= 8 && dWf && dWg)
-        return wide_layer_bwd_256(x, f, g, Wf, Wg, Wp, dout, dzs, dx, dWf, dbf, dWg, dbg, dWp, dbp, ws, B, T, Cr, Cd, fw, d,
+    if (c.split_b3() && 2 * Cd == 256 && Cr % 32 == 0 && (Cr / 32) * fw <= 8 && dWf && dWg)
+        return wide_layer_bwd_256(c, x, f, g, Wf, Wg, Wp, dout, dzs, dx, dWf, dbf, dWg, dbg, dWp, dbp, ws, B, T, Cr, Cd, fw, d,
                                   Z, z, s);
     float* da = ws;                  // (B,T,Cd): dz first, then da in place
     float* dg = ws + n * Cd;         // (B,T,Cd)
@@ -220,7 +220,7 @@ int wide_layer_bwd(const float* x, const float* f, const float* g, const float* 
         base_args(a, B, T);
         a.nsrc = 1; a.X[0] = dout; a.K[0] = Cr; a.W[0] = Wp; a.wsm[0] = 1; a.wsk = Cd; a.bias[0] = nullptr;
         a.M = Cd; a.ldo = Cd; a.out[0] = da; a.residual = dzs;
-        if ((rc = launch_colgemm_multi(a, s))) return rc;
+        if ((rc = launch_colgemm_multi(c, a, s))) return rc;
         dz = da;
     }
     const long long n4 = n * Cd / 4;
@@ -237,10 +237,10 @@ int wide_layer_bwd(const float* x, const float* f, const float* g, const float* 
                 a.soff[i] = (fw - 1 - k) * d; a.bias[i] = nullptr;
             }
         a.wsk = Cr * fw; a.M = Cr; a.ldo = Cr; a.out[0] = dx; a.residual = dout;
-        if ((rc = launch_colgemm_multi(a, s))) return rc;
+        if ((rc = launch_colgemm_multi(c, a, s))) return rc;
     }
-    if (dWf && (rc = conv_wgrad(da, x, dWf, B, T, Cr, Cd, fw, d, s))) return rc;
-    if (dWg && (rc = conv_wgrad(dg, x, dWg, B, T, Cr, Cd, fw, d, s))) return rc;
+    if (dWf && (rc = conv_wgrad(c, da, x, dWf, B, T, Cr, Cd, fw, d, s))) return rc;
+    if (dWg && (rc = conv_wgrad(c, dg, x, dWg, B, T, Cr, Cd, fw, d, s))) return rc;
     if (dWp && dout) {               // dWp[cr][cd] += sum dout[n][cr] * (f g)[n][cd]
         for (int c0 = 0; c0 < Cd; c0 += 32 * WN_MAX_SRC) {
             WGArgs a{};
@@ -250,12 +250,12 @@ int wide_layer_bwd(const float* x, const float* f, const float* g, const float* 
             }
             a.ldb = Cd; a.ldo = Cd; a.osk = 1;
             a.nB = B; a.rows_A_per_b = T; a.rows_B_per_b = T; a.off = 0; a.act = WN_ACT_NONE;
-            if ((rc = launch_wgrad(a, Cr, s))) return rc;
+            if ((rc = launch_wgrad(c, a, Cr, s))) return rc;
         }
     }
-    if (dbf && (rc = generic_colsum(da, B, T, 0, Cd, Cd, dbf, s))) return rc;     // da, dg are already 0 for t < Z
-    if (dbg && (rc = generic_colsum(dg, B, T, 0, Cd, Cd, dbg, s))) return rc;
-    if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, s))) return rc;
+    if (dbf && (rc = generic_colsum(da, B, T, 0, Cd, Cd, dbf, c.ws, c.room(), s))) return rc;     // da, dg are already 0 for t < Z
+    if (dbg && (rc = generic_colsum(dg, B, T, 0, Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
 

@@ -50,6 +50,28 @@ void set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Raises the dynamic-LDS limit of each kernel to `bytes`: hipSuccess or the first error.
+template <typename... K>
+static hipError_t set_max_lds(int bytes, K... kernels) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e
+                          : hipFuncSetAttribute(reinterpret_cast<const void*>(kernels),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes)),
+     ...);
+    return e;
+}
+// set_max_lds once per process (a function-local static: thread-safe); a failure is kept and returned as WN_EHIP, with the
+// kernels named, on every call
+#define WN_MAX_LDS_ONCE(bytes, ...)                                                                           \
+    do {                                                                                                      \
+        static const hipError_t lds_e__ = wn::set_max_lds((bytes), __VA_ARGS__);                             \
+        if (lds_e__ != hipSuccess) {                                                                          \
+            wn::set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %d) failed for %s: %s (%s:%d)",    \
+                          (int)(bytes), #__VA_ARGS__, hipGetErrorString(lds_e__), __FILE__, __LINE__);        \
+            return WN_EHIP;                                                                                   \
+        }                                                                                                     \
+    } while (0)
+
 // prof.hip: brackets an entry point's kernels with hipEvents when wn_prof_enable(1) is in effect
 struct ProfScope {
     int id = 0; hipStream_t s = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr; bool on;
