@@ -319,6 +319,27 @@ int wn_decoder_status(void* handle, void* stream);
 /* categorical draw with numpy's algorithm for n independent rows (generate.py:39) */
 int wn_sample_categorical(const float* prob, const double* uniforms, int32_t* out, int n, int Q,
                           void* stream);
+/* Sampling controls (an extension: train_audio/generate.py:39 draws from the raw softmax; ABI stays 5, new functions only).
+ * Per row of fp32 probabilities p, all order-exact (integer ranks, float64 sums in index order):
+ *   order:  j precedes i iff p[j] > p[i], or p[j] == p[i] and j < i; rank(i) = number of tokens preceding i;
+ *   top-k:  pk[i] = rank(i) < top_k ? p[i] : 0                                     (top_k == 0 or >= Q: off)
+ *   top-p:  total = sum pk, before(i) = sum of pk[j] over the j preceding i; keep i iff before(i) < top_p * total, the
+ *           rank-0 token always                                                    (top_p == 1: off)
+ *   draw:   excluded entries are 0.0f, kept entries keep their value (no renormalisation); then generate.py:39's draw as
+ *           wn_sample_categorical makes it.  With both controls off the tokens ARE wn_sample_categorical's.
+ * WN_EARG before any device work: NULL pointer, top_k < 0, top_p outside (0, 1] or NaN.  At most 8192 tokens per row
+ * when a control is on (WN_ESHAPE).  wavenet_amd/sampling.py restates the rule in numpy. */
+int wn_sample_categorical_filtered(const float* prob, const double* uniforms, int32_t* out, int n, int Q, int top_k,
+                                   double top_p, void* stream);
+/* The same controls inside the persistent decode kernels (generate.py:24-43 with --fast, every draw of it): state of the
+ * handle, off at create (temperature 1, top_k 0, top_p 1), honoured by wn_decoder_run and -- per handle, so utterances of one
+ * launch may differ -- by wn_decoder_run_batch.  Temperature: the fp32 logits are multiplied by 1.0f / temperature
+ * (computed once, here, in fp32) in front of the fp32 softmax; prob_trace receives those post-temperature, pre-truncation
+ * probabilities, the very values the truncation and the draw consume.  Whatever is off is skipped, not computed
+ * neutrally: with all three off a run executes what it executed before the controls existed, bit for bit.
+ * wn_decoder_step is NOT affected (it returns probabilities or logits; its caller draws).  WN_EARG: NULL handle, temperature
+ * not finite or <= 0, top_k < 0, top_p outside (0, 1] or NaN. */
+int wn_decoder_set_sampling(void* handle, float temperature, int top_k, double top_p);
 
 /* ---- A2 on the device (optional path; data.py:18-23 and 37-43) --------------------------------------
  * Table lookups: lut65536[v + 32768] is the token of the int16 sample v, table[q] the sample value of token q;

@@ -91,6 +91,8 @@ _SIGS = {
     "wn_decoder_batch_max": (_i, []),
     "wn_decoder_run_batch": (_i, [_p, _i, _p, _p, _i, _p, _p, _i, _p]),
     "wn_sample_categorical": (_i, [_p, _p, _p, _i, _i, _p]),
+    "wn_sample_categorical_filtered": (_i, [_p, _p, _p, _i, _i, _i, C.c_double, _p]),
+    "wn_decoder_set_sampling": (_i, [_p, _f, _i, C.c_double]),
     "wn_sqnorm": (_i, [_p, _p, _i64, _f, _f, _p, _p]),
     "wn_adam_step": (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _p, _f, _f, _p]),
     "wn_adam_step_dev": (_i, [_p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _p, _f, _f, _p]),

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "wn_kernels.hpp"
+#include "sample_filter.hpp"
 
 namespace wn {
 static thread_local char g_err[512] = "";
@@ -324,6 +325,16 @@ int wn_sample_categorical(const float* prob, const double* uniforms, int32_t* ou
     wn::ProfScope prof__("wn_sample_categorical", stream);
     NN(prob); NN(uniforms); NN(out); POS(n); POS(Q);
     return generic_sample(prob, uniforms, out, n, Q, as_stream(stream));
+}
+
+int wn_sample_categorical_filtered(const float* prob, const double* uniforms, int32_t* out, int n, int Q, int top_k,
+                                   double top_p, void* stream) {
+    wn::ProfScope prof__("wn_sample_categorical_filtered", stream);
+    NN(prob); NN(uniforms); NN(out); POS(n); POS(Q);
+    if (int rc = check_sampling(__func__, 1.f, top_k, top_p)) return rc;
+    if ((top_k == 0 || top_k >= Q) && top_p >= 1.0)            // both off: wn_sample_categorical's kernel, its tokens
+        return generic_sample(prob, uniforms, out, n, Q, as_stream(stream));
+    return generic_sample_filtered(prob, uniforms, out, n, Q, top_k >= Q ? 0 : top_k, top_p, as_stream(stream));
 }
 
 int wn_mulaw_encode_pcm16(const int16_t* pcm, const int32_t* lut65536, int32_t* tokens, int64_t n, void* stream) {

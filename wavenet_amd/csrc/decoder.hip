@@ -18,6 +18,7 @@
 
 #include "wn_kernels.hpp"
 #include "decoder_types.hpp"
+#include "sample_filter.hpp"
 
 namespace wn {
 
@@ -42,6 +43,7 @@ struct Decoder {
     int head_bias_off = -1;
     bool three_wgs = true;        // wn_decoder_run on nine workgroups (decoder_fast.hip); WN_DECODER_ONE_WORKGROUP clears it
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
+    SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
 };
@@ -59,6 +61,14 @@ static bool fast_shape(const WnDecoderDesc* d) {
     for (int j = 0; j < d->n_blocks * d->n_layers; ++j)
         if ((d->bf && d->bf[j]) || (d->bg && d->bg[j]) || (d->bp && d->bp[j]) || (d->bs && d->bs[j])) return false;
     return true;
+}
+
+// the handle's sampling controls as the kernels take them: whatever is off has its "skip" value (top_k >= Q keeps every
+// token, so it is off: the all-off launch runs the instruction stream it ran before the controls existed)
+static SampleCtl launch_ctl(const Decoder* D) {
+    SampleCtl c = D->ctl;
+    if (c.top_k >= D->meta.Q) c.top_k = 0;
+    return c;
 }
 
 // ---- packing ---------------------------------------------------------------------------------
@@ -126,9 +136,10 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
     DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
-    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample) {
+    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, NT = blockDim.x;
+    const bool filt = sc.top_k > 0 || sc.top_p < 1.0;      // workgroup-uniform (kernel arguments)
     float* xcur = sm;                    // [maxc] current column of the residual stream / causal stack
     float* xnew = xcur + M.maxc;         // [maxc]
     float* ab = xnew + M.maxc;           // [2*maxc] gate pre-activations
@@ -238,6 +249,9 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
         }
         // hin holds the Q logits
         if (apply_softmax) {
+            // temperature: the fp32 logits times 1/T (a thread only ever touches its own entries up to the barrier below)
+            if (sc.inv_temp != 1.f)
+                for (int q = tid; q < M.Q; q += NT) hin[q] *= sc.inv_temp;
             float m = -INFINITY;
             for (int q = tid; q < M.Q; q += NT) m = fmaxf(m, hin[q]);
             m = block_reduce(m, true, red);
@@ -252,6 +266,8 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
         if (prob_out)
             for (int q = tid; q < M.Q; q += NT) prob_out[(long long)it * prob_stride + q] = hin[q];
         if (do_sample) {
+            if (filt)                    // top-k / top-p: the trace above holds the row as the filter receives it
+                sample_filter<false>(hin, M.Q, tid, NT, sc.top_k, sc.top_p);
             if (tid == 0) {
                 // numpy legacy choice: float64 cumsum, divide by the total, first index with cdf > u
                 double tot = 0.0;
@@ -504,7 +520,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     if (D->fastP) {
         int rc = decode_fast_launch(D->fastP, D->meta.nlayers, D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr,
                                     D->arena + D->causal[0].w, D->d_layers, D->arena, D->tok_ring, D->step, 1, (int)token,
-                                    nullptr, nullptr, prob, D->meta.Q, apply_softmax, 0, D->meta.head_act, false,
+                                    nullptr, nullptr, prob, D->meta.Q, apply_softmax, 0, D->meta.head_act, false, SampleCtl(),
                                     as_stream(stream));
         if (rc) return rc;
         D->step += 1;
@@ -512,7 +528,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     }
     hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, 1, (int)token,
-                       (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0);
+                       (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl());
     WN_LAUNCH_CHECK();
     D->step += 1;
     return WN_OK;
@@ -528,7 +544,7 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
         int rc = decode_fast_launch(D->fastP, D->meta.nlayers, D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr,
                                     D->arena + D->causal[0].w, D->d_layers, D->arena, D->tok_ring, D->step, n,
                                     (int)first_token, uniforms, out_tokens, prob_trace, D->meta.Q, 1, 1,
-                                    D->meta.head_act, D->three_wgs, as_stream(stream));
+                                    D->meta.head_act, D->three_wgs, launch_ctl(D), as_stream(stream));
         if (rc) return rc;
         D->ran_multi = D->three_wgs && n > 1;
         D->step += n;
@@ -536,9 +552,21 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     }
     hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, n, (int)first_token, uniforms,
-                       out_tokens, prob_trace, D->meta.Q, 1, 1);
+                       out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D));
     WN_LAUNCH_CHECK();
     D->step += n;
+    return WN_OK;
+}
+
+int wn_decoder_set_sampling(void* handle, float temperature, int top_k, double top_p) {
+    if (int rc = check_sampling("wn_decoder_set_sampling", temperature, top_k, top_p)) return rc;
+    Decoder* D = (Decoder*)handle;
+    WN_CHECK_ARG(D, "wn_decoder_set_sampling: NULL handle");
+    WN_CHECK_SHAPE(D->meta.Q <= 32 * kDecThreads, "wn_decoder_set_sampling: Q = %d is more than the filter's %d tokens", D->meta.Q,
+                   32 * kDecThreads);
+    D->ctl.inv_temp = 1.0f / temperature;          // once, on the host, in fp32
+    D->ctl.top_k = top_k;
+    D->ctl.top_p = top_p >= 1.0 ? 1.0 : top_p;
     return WN_OK;
 }
 
@@ -549,7 +577,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     WN_CHECK_ARG(handles && first_tokens && uniforms && out_tokens && n_handles >= 1 && n > 0, "wn_decoder_run_batch: bad argument");
     WN_CHECK_SHAPE(n_handles <= kDecMaxBatch, "wn_decoder_run_batch: at most %d utterances per launch", kDecMaxBatch);
     const float* P[kDecMaxBatch]; const float* hb[kDecMaxBatch]; const float* E[kDecMaxBatch]; const DecLayer* ly[kDecMaxBatch];
-    float* ar[kDecMaxBatch]; int* tr[kDecMaxBatch]; long long n0[kDecMaxBatch]; int ft[kDecMaxBatch];
+    float* ar[kDecMaxBatch]; int* tr[kDecMaxBatch]; long long n0[kDecMaxBatch]; int ft[kDecMaxBatch]; SampleCtl ctl[kDecMaxBatch];
     Decoder* D0 = (Decoder*)handles[0];
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
@@ -572,12 +600,12 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
         P[u] = D->fastP; hb[u] = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
         E[u] = D->arena + D->causal[0].w; ly[u] = D->d_layers; ar[u] = D->arena; tr[u] = D->tok_ring; n0[u] = D->step;
-        ft[u] = (int)first_tokens[u];
+        ft[u] = (int)first_tokens[u]; ctl[u] = launch_ctl(D);
     }
     WN_CHECK_SHAPE(decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = decode_fast_launch_batch(n_handles, P, D0->meta.nlayers, hb, E, ly, ar, tr, n0, n, ft, uniforms, out_tokens,
-                                            prob_traces, D0->meta.Q, D0->meta.head_act, same_weights != 0, as_stream(stream));
+                                            prob_traces, D0->meta.Q, D0->meta.head_act, same_weights != 0, ctl, as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];

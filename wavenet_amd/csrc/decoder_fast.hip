@@ -349,7 +349,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
     const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
     int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
     int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act) {
+    int do_sample, int head_act, const SampleCtl sc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* Elds = sm;                                   // [256][2][32] embedding table of the causal layer
     float* xold = Elds + 256 * 2 * 32;                  // [L][32]   x_l[n-d] of every layer, fetched at step start
@@ -476,6 +476,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             v = (p0 + p1) + (p2 + p3);
         }
         if (apply_softmax) {
+            if (sc.inv_temp != 1.f) v *= sc.inv_temp;      // temperature (uniform branch: a kernel argument)
             float m = wave_allmax(v);
             if (lane == 0) red[wv] = m;
             lds_barrier();
@@ -491,6 +492,9 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
         if (prob_out) prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
         if (do_sample) {
+            // top-k / top-p (uniform branch): the row in lg is truncated in place between the barrier above and the draw,
+            // which then runs on it unchanged; LDS only
+            if (sc.top_k > 0 || sc.top_p < 1.0) sample_filter<true>(lg, 256, tid, kFT, sc.top_k, sc.top_p);
             // numpy: cdf = cumsum(float64(p)); cdf /= cdf[-1]; first index with cdf > u.  The running sum is a
             // 256-long dependent chain (9.5 k cycles); a parallel scan associates differently, so its cdf may differ
             // from numpy's by a few ulp (<= 256 * 2^-53).  It is therefore used only when no cdf_i / total lies within
@@ -579,7 +583,7 @@ __device__ __forceinline__ void decode_fast3_body(
     const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
     int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
     int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act, u64* __restrict__ X) {
+    int do_sample, int head_act, u64* __restrict__ X, const SampleCtl sc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
@@ -743,6 +747,7 @@ __device__ __forceinline__ void decode_fast3_body(
             for (int k = 0; k < kD10Skip; ++k) v += __uint_as_float((unsigned)wd[k]);
         }
         if (apply_softmax) {
+            if (sc.inv_temp != 1.f) v *= sc.inv_temp;      // temperature (uniform branch: a kernel argument)
             float m = wave_allmax(v);
             if (lane == 0) red[wv] = m;
             lds_barrier();
@@ -758,6 +763,9 @@ __device__ __forceinline__ void decode_fast3_body(
         if (prob_out) prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
         if (do_sample) {
+            // top-k / top-p (uniform branch): the row in lg is truncated in place between the barrier above and the draw,
+            // which then runs on it unchanged; LDS only
+            if (sc.top_k > 0 || sc.top_p < 1.0) sample_filter<true>(lg, 256, tid, kFT, sc.top_k, sc.top_p);
             double c = wave_scan_f64((double)lg[tid]);
             if (lane == 63) cdf[wv] = c;
             lds_barrier();
@@ -815,9 +823,9 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(
     const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
     int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
     int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act, u64* __restrict__ X) {
+    int do_sample, int head_act, u64* __restrict__ X, const SampleCtl sc) {
     decode_fast3_body((int)blockIdx.x, P, Ph, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps, first_token, uniforms,
-                      out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X);
+                      out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X, sc);
 }
 
 // N independent utterances in ONE launch: nine workgroups each (the single-GPU form of "replicas only", SURVEY 8(e): batch 1
@@ -827,6 +835,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(
 struct DecBatchItem {
     const float* P; const float* hbias; const float* E; const DecLayer* layers; float* arena; int* tok_ring;
     long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out; u64* X; int first_token; int pad;
+    SampleCtl sc;                      // per utterance: its handle's wn_decoder_set_sampling
 };
 struct DecBatchArgs { DecBatchItem it[kDecMaxBatch]; };
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int nsteps, int prob_stride,
@@ -835,7 +844,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArg
     const DecBatchItem& q = a.it[u];
     decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), q.P, q.P + (size_t)nlayers * kLayerFloats, q.hbias, q.E, q.layers,
                       nlayers, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out,
-                      prob_stride, 1, 1, head_act, q.X);
+                      prob_stride, 1, 1, head_act, q.X, q.sc);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
@@ -863,7 +872,7 @@ int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
 int decode_fast_launch(const float* P, int nlayers, const float* hbias, const float* E, const DecLayer* layers,
                        float* arena, int* tok_ring, long long n0, int nsteps, int first_token,
                        const double* uniforms, int32_t* out_tokens, float* prob_out, int prob_stride,
-                       int apply_softmax, int do_sample, int head_act, bool three_wgs, hipStream_t s) {
+                       int apply_softmax, int do_sample, int head_act, bool three_wgs, const SampleCtl& ctl, hipStream_t s) {
     WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast, k_decode_fast3);
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
@@ -881,13 +890,13 @@ int decode_fast_launch(const float* P, int nlayers, const float* hbias, const fl
         hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, X, nx);
         hipLaunchKernelGGL(k_decode_fast3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, P,
                            P + (size_t)nlayers * kLayerFloats, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps,
-                           first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X);
+                           first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X, ctl);
         WN_LAUNCH_CHECK();
         return WN_OK;
     }
     hipLaunchKernelGGL(k_decode_fast, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, P,
                        P + (size_t)nlayers * kLayerFloats, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps,
-                       first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act);
+                       first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, ctl);
     WN_LAUNCH_CHECK();
     return WN_OK;
 }
@@ -903,7 +912,8 @@ int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps) {
 int decode_fast_launch_batch(int n_utt, const float* const* P, int nlayers, const float* const* hbias, const float* const* E,
                              const DecLayer* const* layers, float* const* arena, int* const* tok_ring, const long long* n0,
                              int nsteps, const int* first_token, const double* const* uniforms, int32_t* const* out_tokens,
-                             float* const* prob_out, int prob_stride, int head_act, bool same_weights, hipStream_t s) {
+                             float* const* prob_out, int prob_stride, int head_act, bool same_weights, const SampleCtl* ctl,
+                             hipStream_t s) {
     if (!decode_fast_batch_ok(nlayers, n_utt, nsteps)) {
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
         return WN_ESHAPE;
@@ -920,6 +930,7 @@ int decode_fast_launch_batch(int n_utt, const float* const* P, int nlayers, cons
         q.P = P[wu]; q.hbias = hbias[wu]; q.E = E[wu]; q.layers = layers[u]; q.arena = arena[u]; q.tok_ring = tok_ring[u];
         q.n0 = n0[u]; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_out ? prob_out[u] : nullptr;
         q.first_token = first_token[u];
+        q.sc = ctl[u];
         q.X = reinterpret_cast<u64*>(const_cast<float*>(P[u]) + (size_t)nlayers * kLayerFloats + 256 * 256);
         hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, q.X, nx);
     }

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "wn_kernels.hpp"
+#include "sample_filter.hpp"
 
 namespace wn {
 
@@ -716,6 +717,29 @@ __global__ void k_sample(const float* __restrict__ prob, const double* __restric
     out[i] = idx;
 }
 
+// The same draw behind the decoders' truncation stage (sample_filter.hpp): one workgroup per row, the row in LDS, the
+// very device function the persistent decode kernels call, then k_sample's float64 chain on the truncated row.
+static constexpr int kFiltThreads = 256;
+__global__ __launch_bounds__(kFiltThreads) void k_sample_filtered(const float* __restrict__ prob, const double* __restrict__ u,
+                                                                  int32_t* __restrict__ out, int Q, int top_k, double top_p) {
+    extern __shared__ __attribute__((aligned(16))) float row[];
+    const int tid = threadIdx.x, i = blockIdx.x;
+    for (int q = tid; q < Q; q += kFiltThreads) row[q] = prob[(long long)i * Q + q];
+    __syncthreads();
+    sample_filter<false>(row, Q, tid, kFiltThreads, top_k, top_p);
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int q = 0; q < Q; ++q) tot += (double)row[q];
+        double c = 0.0, uu = u[i];
+        int idx = Q;
+        for (int q = 0; q < Q; ++q) {
+            c += (double)row[q];
+            if (c / tot > uu) { idx = q; break; }
+        }
+        out[i] = idx;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // optimiser step
 // ---------------------------------------------------------------------------------------------
@@ -1205,6 +1229,16 @@ int generic_absmax(const float* x, long long n, unsigned* slot, hipStream_t s) {
 int generic_transpose(const float* src, float* dst, int batch, int R, int Cc, hipStream_t s) {
     dim3 grid(cdiv(Cc, 32), cdiv(R, 32), batch);
     hipLaunchKernelGGL(k_transpose, grid, dim3(32, 8), 0, s, src, dst, R, Cc);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
+}
+
+int generic_sample_filtered(const float* prob, const double* u, int32_t* out, int n, int Q, int top_k, double top_p,
+                            hipStream_t s) {
+    // one bit of a 32-bit mask per token of a thread, and the row in LDS
+    WN_CHECK_SHAPE(Q <= 32 * kFiltThreads, "wn_sample_categorical_filtered: at most %d tokens per row", 32 * kFiltThreads);
+    hipLaunchKernelGGL(k_sample_filtered, dim3(n), dim3(kFiltThreads), (size_t)Q * sizeof(float), s, prob, u, out, Q, top_k,
+                       top_p);
     WN_LAUNCH_CHECK();
     return WN_OK;
 }

@@ -93,6 +93,7 @@ int generic_xent_count(const int32_t* target, long long N, int Q, float* loss, i
 int generic_xent_final(float* loss, int nblocks, long long n_norm, int ncnt, hipStream_t s);
 int generic_transpose(const float* src, float* dst, int batch, int R, int Cc, hipStream_t s);
 int generic_sample(const float*, const double*, int32_t*, int, int, hipStream_t);
+int generic_sample_filtered(const float*, const double*, int32_t*, int, int, int, double, hipStream_t);
 int generic_mulaw_encode_pcm16(const int16_t* pcm, const int32_t* lut, int32_t* tok, long long n, hipStream_t s);
 int generic_mulaw_decode(const int32_t* tok, const float* table, float* out, long long n, int Q, hipStream_t s);
 int generic_sqnorm(const float* g, const float* p, long long n, float gmult, float wd, float* out, hipStream_t s);

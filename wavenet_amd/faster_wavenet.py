@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, sampling
 from ._lib import check, ptr, ptr_array, int_array, stream_ptr, ACT
 from .wavenet import WaveNet, _as_view, _need_gpu
 
@@ -124,6 +124,7 @@ class FasterWaveNet(WaveNet):
             causal_output = self.forward_causal_block(x)
             _, sum_skip = self.forward_residual_block(causal_output)
             out = self.forward_softmax_block(sum_skip, apply_softmax=apply_softmax)
+            self._last_sum_skip = sum_skip                                       # generate(): the first row under a temperature
             tokens = (x if not x.is_floating_point() else x[:, :, 0, :].argmax(dim=1)).to(torch.int32).contiguous()
             W = tokens.shape[1]
             dec = self._decoder()
@@ -194,14 +195,39 @@ class FasterWaveNet(WaveNet):
         return self.to_numpy(out) if as_numpy else out
 
     # -- the whole generate loop on the device (train_audio/generate.py:9-60 with --fast) --------
-    def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False):
+    def _first_row(self, sum_skip, p0, temperature):
+        """(1, Q) probabilities of the first emitted sample (full forward, ReLU head).  Temperature 1: the newest column of
+        the window's softmax ``p0``, as ever; otherwise the same contract as on the device -- the fp32 logits of that
+        column times ``1.0f / temperature``, then ``wn_softmax_fwd``."""
+        Q = self.params.quantization_steps
+        if float(temperature) == 1.0:
+            return p0[0, :, 0, -1].contiguous().view(1, Q)
+        storage, self.storage = self.storage, "fp32"
+        try:
+            with torch.no_grad():
+                lg = self.forward_softmax_block(sum_skip, apply_softmax=False)
+        finally:
+            self.storage = storage
+        row = (lg[0, :, 0, -1].contiguous().view(1, Q) * float(sampling.inv_temperature(temperature))).contiguous()
+        out = torch.empty_like(row)
+        check(_lib.lib().wn_softmax_fwd(ptr(row), ptr(out), 1, Q, stream_ptr()), "wn_softmax_fwd")
+        return out
+
+    def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False,
+                 temperature=1.0, top_k=0, top_p=1.0):
         """Emit ``n_samples`` tokens.  Step 1 is the full forward over the initial window (ReLU head,
         like the reference's first ``_forward_one_step`` call); steps 2.. run inside one persistent
         kernel with the ELU head.  ``uniforms[i]`` is the float64 draw numpy's ``choice`` would make
-        at step i (``RandomState.random_sample``)."""
+        at step i (``RandomState.random_sample``).
+
+        ``temperature`` / ``top_k`` / ``top_p`` (off at 1 / 0 / 1; the rule is wavenet_amd/sampling.py's) act on every
+        draw, on the device; ``return_probs`` then holds the post-temperature, pre-truncation rows.  With all three off the
+        run is the one it was before they existed, bit for bit."""
         p = self.params
         Q = p.quantization_steps
         iw = self.input_width
+        sampling.check_controls(temperature, top_k, top_p)
+        top_k, top_p = int(top_k), float(top_p)
         if initial_tokens is None:
             initial_tokens = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)   # generate.py:21
         tok = torch.as_tensor(np.asarray(initial_tokens, dtype=np.int32).reshape(1, -1)).to(self.device)
@@ -215,15 +241,16 @@ class FasterWaveNet(WaveNet):
             p0 = self.forward_one_step(tok, apply_softmax=True)      # (1,Q,1,W)
         finally:
             self.keep_window = keep
-        first_prob = p0[0, :, 0, -1].contiguous().view(1, Q)
+        first_prob = self._first_row(self._last_sum_skip, p0, temperature)
         out = torch.empty((n_samples,), device=self.device, dtype=torch.int32)
-        check(lib.wn_sample_categorical(ptr(first_prob), ptr(u), ptr(out), 1, Q, stream_ptr()),
-              "wn_sample_categorical")
+        check(lib.wn_sample_categorical_filtered(ptr(first_prob), ptr(u), ptr(out), 1, Q, top_k, top_p, stream_ptr()),
+              "wn_sample_categorical_filtered")
         probs = torch.empty((n_samples, Q), device=self.device, dtype=torch.float32) if return_probs else None
         if return_probs:
             probs[0] = first_prob[0]
         if n_samples > 1:
             first = int(out[0].item())
+            check(lib.wn_decoder_set_sampling(self._decoder(), float(temperature), top_k, top_p), "wn_decoder_set_sampling")
             check(lib.wn_decoder_run(self._decoder(), first, ptr(u[1:]), n_samples - 1, ptr(out[1:]),
                                      ptr(probs[1:]) if return_probs else None, stream_ptr()), "wn_decoder_run")
             # the nine-workgroup run reports a wait that gave up (workgroups not all resident) instead of trapping: its
@@ -236,13 +263,14 @@ class FasterWaveNet(WaveNet):
         return (out, probs) if return_probs else out
 
     # -- N utterances at once (new capability: the reference generates one utterance per process) ------------------------
-    def generate_batch(self, n_samples: int, uniforms, initial_tokens=None):
+    def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0):
         """``uniforms``: (N, n_samples) float64 -- N independent utterances from the same initial window, utterance u drawing
         with ``uniforms[u]``; returns (N, n_samples) int32 tokens on the device.  A single utterance is a strict
         sample-to-sample chain (generate.py:9-60, batch 1: wavenet.py:286,290,354) and occupies nine of the GPU's CUs; the
         batched launch (``wn_decoder_run_batch``) runs up to ``wn_decoder_batch_max()`` = 28 such chains side by side, each with
         a decoder state of its own.  Row u equals ``generate(n_samples, uniforms[u])`` bit for bit.  Step 1 -- the full forward
-        over the initial window -- is the same for every utterance and runs once."""
+        over the initial window -- is the same for every utterance and runs once.  ``temperature`` / ``top_k`` / ``top_p``:
+        as for ``generate``, each a scalar or one value per utterance (row u then equals ``generate`` with utterance u's)."""
         p = self.params
         Q = p.quantization_steps
         iw = self.input_width
@@ -251,6 +279,11 @@ class FasterWaveNet(WaveNet):
             raise Exception("uniforms must be (N, >= n_samples)")
         N = u_np.shape[0]
         lib = _lib.lib()
+        temps = [float(t) for t in sampling.per_utterance(temperature, N, "temperature")]
+        top_ks = [int(k) for k in sampling.per_utterance(top_k, N, "top_k")]
+        top_ps = [float(v) for v in sampling.per_utterance(top_p, N, "top_p")]
+        for i in range(N):
+            sampling.check_controls(temps[i], top_ks[i], top_ps[i])
         if n_samples < 1:
             raise Exception("generate_batch: n_samples must be positive")
         # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
@@ -262,7 +295,7 @@ class FasterWaveNet(WaveNet):
         if N < 1:
             raise Exception("generate_batch: no utterance")
         if not batched:
-            return self._generate_batch_loop(n_samples, u_np, initial_tokens)
+            return self._generate_batch_loop(n_samples, u_np, initial_tokens, temps, top_ks, top_ps)
         if initial_tokens is None:
             initial_tokens = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)   # generate.py:21
         tok = torch.as_tensor(np.asarray(initial_tokens, dtype=np.int32).reshape(1, -1)).to(self.device)
@@ -292,11 +325,21 @@ class FasterWaveNet(WaveNet):
             check(lib.wn_decoder_load_state(
                 self._batch_decs[i], ptr(tokens), tokens.shape[1], ptr_array([t.contiguous() for t in self._last_causal_outputs]),
                 ptr_array(self._last_layer_inputs), stream_ptr()), "wn_decoder_load_state")
-        first_prob = p0[0, :, 0, -1].contiguous().view(1, Q).expand(N, Q).contiguous()
+            check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
         out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
         first = torch.empty((N,), device=self.device, dtype=torch.int32)
-        check(lib.wn_sample_categorical(ptr(first_prob), ptr(u[:, 0].contiguous()), ptr(first), N, Q, stream_ptr()),
-              "wn_sample_categorical")
+        u0 = u[:, 0].contiguous()
+        if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
+            first_prob = p0[0, :, 0, -1].contiguous().view(1, Q).expand(N, Q).contiguous()
+            check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
+        else:
+            # the first draw per utterance, as generate() makes it: a row per distinct temperature, the truncation per utterance
+            rows = {}
+            for i in range(N):
+                if temps[i] not in rows:
+                    rows[temps[i]] = self._first_row(sum_skip, p0, temps[i])
+                check(lib.wn_sample_categorical_filtered(ptr(rows[temps[i]]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1, Q,
+                                                         top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
         out[:, 0] = first
         if n_samples > 1:
             firsts = (C.c_int32 * N)(*[int(v) for v in first.cpu().tolist()])
@@ -307,14 +350,17 @@ class FasterWaveNet(WaveNet):
             rc = lib.wn_decoder_run_batch(handles, N, firsts, ptr_array(rest), n_samples - 1, ptr_array(outs), None, same,
                                           stream_ptr())
             if rc == _lib.WN_ESHAPE:         # a shape the batched launch does not take (e.g. not config 4's): one by one
-                return self._generate_batch_loop(n_samples, u_np, initial_tokens)
+                return self._generate_batch_loop(n_samples, u_np, initial_tokens, temps, top_ks, top_ps)
             check(rc, "wn_decoder_run_batch")
             for i in range(N):
                 check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
                 out[i, 1:] = outs[i]
         return out
 
-    def _generate_batch_loop(self, n_samples, u_np, initial_tokens):
+    def _generate_batch_loop(self, n_samples, u_np, initial_tokens, temperature=1.0, top_k=0, top_p=1.0):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
-        ``generate(n_samples, uniforms[u])`` by definition)."""
-        return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=initial_tokens) for i in range(u_np.shape[0])])
+        ``generate(n_samples, uniforms[u])`` with utterance u's controls by definition)."""
+        N = u_np.shape[0]
+        t, k, pp = (sampling.per_utterance(v, N, n) for v, n in ((temperature, "temperature"), (top_k, "top_k"), (top_p, "top_p")))
+        return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=initial_tokens, temperature=t[i], top_k=k[i],
+                                          top_p=pp[i]) for i in range(N)])

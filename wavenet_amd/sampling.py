@@ -1,0 +1,112 @@
+"""Sampling controls on the host: temperature, top-k and top-p (nucleus) in front of the categorical draw.
+
+The reference draws every sample from the raw softmax (train_audio/generate.py:39: ``np.random.choice(..., p=softmax)``).
+The decode kernels and ``wn_sample_categorical_filtered`` (include/wavenet_hip.h) can truncate the distribution first; this
+module is the same rule in numpy, for callers that sample on the host (the step-by-step loop of train_audio/generate.py)
+and as the statement of the contract.  Given a row ``p`` of float32 probabilities:
+
+1. order: token j precedes token i iff ``p[j] > p[i]``, or ``p[j] == p[i]`` and ``j < i``; ``rank(i)`` is the number of
+   tokens preceding i;
+2. top-k: ``pk[i] = p[i]`` if ``rank(i) < top_k`` else 0 (``top_k == 0`` or ``top_k >= Q``: off);
+3. top-p, relative to the mass top-k kept: ``total`` = float64 sum of ``pk`` in index order, ``before(i)`` = float64 sum, in
+   index order, of ``pk[j]`` over the j preceding i; keep i iff ``before(i) < top_p * total``; the rank-0 token is always
+   kept (``top_p >= 1``: off);
+4. draw: excluded entries become 0.0f, kept entries keep their float32 value (no renormalisation in float32), and numpy's
+   legacy ``choice`` runs on that row: float64 running sum, divide by the last entry, first index with ``cdf > u``.
+
+Everything is integer and float64 arithmetic in a fixed order (``np.cumsum`` adds sequentially), so the token equals the
+device's bit for bit when the probabilities do.  Temperature acts on the logits (``logits * (1.0f / temperature)`` in
+float32, then the softmax): ``inv_temperature`` gives that factor.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+
+def check_controls(temperature=1.0, top_k=0, top_p=1.0) -> None:
+    """The argument rules of ``wn_decoder_set_sampling``: raise ValueError for what the library refuses."""
+    t = float(temperature)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    if int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError("top_k must be an integer >= 0 (0 = off), got %r" % (top_k,))
+    tp = float(top_p)
+    if not (0.0 < tp <= 1.0):                   # False for NaN
+        raise ValueError("top_p must lie in (0, 1], got %r" % (top_p,))
+
+
+def controls_off(temperature=1.0, top_k=0, top_p=1.0, Q=None) -> bool:
+    return float(temperature) == 1.0 and (int(top_k) == 0 or (Q is not None and int(top_k) >= Q)) and float(top_p) >= 1.0
+
+
+def inv_temperature(temperature) -> np.float32:
+    """``1.0f / temperature`` in float32: the factor the logits are multiplied by."""
+    return np.float32(1.0) / np.float32(temperature)
+
+
+def filter_probs(p, top_k=0, top_p=1.0) -> np.ndarray:
+    """Steps 1-3 on one row: the float32 row with the excluded entries set to 0."""
+    check_controls(1.0, top_k, top_p)
+    p = np.asarray(p, dtype=np.float32)
+    if p.ndim != 1:
+        raise ValueError("filter_probs takes one row of probabilities")
+    Q = p.shape[0]
+    top_k, top_p = int(top_k), float(top_p)
+    out = p.copy()
+    if (top_k == 0 or top_k >= Q) and top_p >= 1.0:
+        return out
+    # a stable sort of -p lists the tokens in the order of step 1 (equal values stay in index order)
+    order = np.argsort(-p.astype(np.float64), kind="stable")
+    rank = np.empty(Q, dtype=np.int64)
+    rank[order] = np.arange(Q)
+    if 0 < top_k < Q:
+        out[rank >= top_k] = np.float32(0.0)
+    if top_p < 1.0:
+        pk = out.astype(np.float64)
+        total = np.cumsum(pk)[-1]
+        thr = top_p * total
+        # before(i): the preceding tokens' values added in INDEX order -- a sum per token, as the device forms it (a prefix
+        # sum over the sorted row would add them in rank order and may round differently)
+        keep = np.zeros(Q, dtype=bool)
+        for i in range(Q):
+            pre = (rank < rank[i])
+            sel = np.where(pre, pk, 0.0)
+            before = np.cumsum(sel)[-1]
+            keep[i] = before < thr or rank[i] == 0
+        out[~keep] = np.float32(0.0)
+    return out
+
+
+def choice_from_uniform(p, u) -> int:
+    """numpy's legacy ``RandomState.choice(arange(Q), p=p)`` given its one ``random_sample()`` draw ``u``
+    (generate.py:39)."""
+    cdf = np.cumsum(np.asarray(p, dtype=np.float64))
+    cdf /= cdf[-1]
+    return int(np.searchsorted(cdf, u, side="right"))
+
+
+def sample(p, u, top_k=0, top_p=1.0) -> int:
+    """Steps 1-4: the token drawn from the row ``p`` with the uniform ``u``."""
+    return choice_from_uniform(filter_probs(p, top_k, top_p), u)
+
+
+def apply_temperature(logits, temperature) -> np.ndarray:
+    """float32 softmax of ``logits * (1.0f / temperature)`` over the last axis (host arithmetic: close to, not bit-equal
+    with, the device's ``expf``)."""
+    x = np.asarray(logits, dtype=np.float32)
+    if float(temperature) != 1.0:
+        x = x * inv_temperature(temperature)
+    e = np.exp(x - x.max(axis=-1, keepdims=True))
+    return (e / e.sum(axis=-1, keepdims=True)).astype(np.float32)
+
+
+def per_utterance(value, n, name="control"):
+    """A scalar or a length-``n`` sequence -> a list of ``n`` values."""
+    if np.ndim(value) == 0:
+        return [value] * n
+    vals = list(value)
+    if len(vals) != n:
+        raise ValueError("%s: expected a scalar or %d values, got %d" % (name, n, len(vals)))
+    return vals

@@ -22,11 +22,17 @@ _LOOP_FLAGS = (
     (("--repeat",), int, 500, "updates per file per epoch (train.py:124)"),
     (("--no-graph",), None, False, "launch every update op by op instead of replaying a HIP graph"),
 )
+# sampling controls of generate (wavenet_amd/sampling.py; the reference draws from the raw softmax, generate.py:39): all off
+_SAMPLING_FLAGS = (
+    (("--temperature",), float, 1.0, "divide the logits by this before the softmax (1 = off)"),
+    (("--top-k",), int, 0, "draw from the k most probable values only (0 = off)"),
+    (("--top-p",), float, 1.0, "draw from the smallest set of most probable values holding this share of the mass (1 = off)"),
+)
 
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__)
-    for flags, typ, default, text in _REFERENCE_FLAGS + _LOOP_FLAGS:
+    for flags, typ, default, text in _REFERENCE_FLAGS + _LOOP_FLAGS + _SAMPLING_FLAGS:
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:

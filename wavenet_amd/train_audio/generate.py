@@ -9,14 +9,17 @@ import time
 import numpy as np
 import torch
 
-from .. import data
+from .. import data, sampling
 from . import args as _args
 from . import model as _model
 from .train import input_width_of
 
 
-def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio"):
+def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
+                   temperature=1.0, top_k=0, top_p=1.0):
     Q = params.quantization_steps
+    sampling.check_controls(temperature, top_k, top_p)
+    controls = not sampling.controls_off(temperature, top_k, top_p, Q)
     iw = input_width_of(params)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
     silence = 127 if Q > 127 else Q // 2
@@ -26,14 +29,23 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
     elif fast:
         # one uniform per sample, the draw numpy's choice() makes (generate.py:40); the whole loop runs on the device
         u = np.random.random_sample(n)
-        tokens = net.generate(n, u, initial_tokens=np.full((iw,), silence, np.int32)).cpu().numpy()
+        tokens = net.generate(n, u, initial_tokens=np.full((iw,), silence, np.int32), temperature=temperature, top_k=top_k,
+                              top_p=top_p).cpu().numpy()
     else:
         buf = np.full((iw,), silence, dtype=np.int32)
         for time_step in range(1, n + 1):
             x = torch.as_tensor(buf[-iw:].reshape(1, -1)).to(net.device)
-            with torch.no_grad():
-                softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True)[0, :, 0, -1]
-            buf = np.append(buf, np.random.choice(np.arange(Q), p=softmax))
+            if not controls:
+                with torch.no_grad():
+                    softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True)[0, :, 0, -1]
+                buf = np.append(buf, np.random.choice(np.arange(Q), p=softmax))
+            else:
+                # the same rule the device applies under --fast, on the host: logits / temperature, softmax, truncation, and
+                # choice()'s draw from its one uniform
+                with torch.no_grad():
+                    logits = net.forward_one_step(x, apply_softmax=False, as_numpy=True)[0, :, 0, -1]
+                softmax = sampling.apply_temperature(logits, temperature)
+                buf = np.append(buf, sampling.sample(softmax, np.random.random_sample(), top_k, top_p))
             if time_step % 10 == 0:
                 sys.stdout.write("\rgenerating {:.2f} msec / {:.2f} msec".format(
                     time_step * 1000.0 / sampling_rate, generate_sec * 1000.0))
@@ -51,7 +63,7 @@ def main(argv=None):
     params, net = _model.build(args)
     np.random.seed(args.seed)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
-                          output_dir=args.output_dir)
+                          output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
 
 
 if __name__ == "__main__":
