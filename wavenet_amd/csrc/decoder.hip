@@ -71,6 +71,16 @@ static SampleCtl launch_ctl(const Decoder* D) {
     return c;
 }
 
+// one utterance's launch arguments of the specialised kernels (decoder_fast.hip), from its handle
+static DecUtt fast_utt(const Decoder* D, int first_token, const double* uniforms, int32_t* out_tokens, float* prob_out,
+                       const SampleCtl& sc) {
+    DecUtt q{};
+    q.P = D->fastP; q.hbias = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
+    q.E = D->arena + D->causal[0].w; q.layers = D->d_layers; q.arena = D->arena; q.tok_ring = D->tok_ring; q.n0 = D->step;
+    q.uniforms = uniforms; q.out_tokens = out_tokens; q.prob_out = prob_out; q.first_token = first_token; q.sc = sc;
+    return q;
+}
+
 // ---- packing ---------------------------------------------------------------------------------
 // dst[(k*Cin + c)*ostride + ooff + o] = src[(o*Cin + c)*fw + k]
 __global__ void k_pack_conv_T(const float* __restrict__ src, float* __restrict__ dst, int Cout, int Cin, int fw,
@@ -518,10 +528,8 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     WN_CHECK_ARG(token >= 0 && token < D->meta.Q, "wn_decoder_step: token %d outside [0,%d)", token, D->meta.Q);
     WN_CHECK_ARG(D->step + 1 < (1ll << 31), "wn_decoder_step: step counter overflow");
     if (D->fastP) {
-        int rc = decode_fast_launch(D->fastP, D->meta.nlayers, D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr,
-                                    D->arena + D->causal[0].w, D->d_layers, D->arena, D->tok_ring, D->step, 1, (int)token,
-                                    nullptr, nullptr, prob, D->meta.Q, apply_softmax, 0, D->meta.head_act, false, SampleCtl(),
-                                    as_stream(stream));
+        int rc = decode_fast_launch(fast_utt(D, (int)token, nullptr, nullptr, prob, SampleCtl()), D->meta.nlayers, 1, D->meta.Q,
+                                    apply_softmax, 0, D->meta.head_act, false, as_stream(stream));
         if (rc) return rc;
         D->step += 1;
         return WN_OK;
@@ -541,10 +549,8 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
     WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run: step counter overflow");
     if (D->fastP) {
-        int rc = decode_fast_launch(D->fastP, D->meta.nlayers, D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr,
-                                    D->arena + D->causal[0].w, D->d_layers, D->arena, D->tok_ring, D->step, n,
-                                    (int)first_token, uniforms, out_tokens, prob_trace, D->meta.Q, 1, 1,
-                                    D->meta.head_act, D->three_wgs, launch_ctl(D), as_stream(stream));
+        int rc = decode_fast_launch(fast_utt(D, (int)first_token, uniforms, out_tokens, prob_trace, launch_ctl(D)),
+                                    D->meta.nlayers, n, D->meta.Q, 1, 1, D->meta.head_act, D->three_wgs, as_stream(stream));
         if (rc) return rc;
         D->ran_multi = D->three_wgs && n > 1;
         D->step += n;
@@ -576,8 +582,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
                          int32_t* const* out_tokens, float* const* prob_traces, int same_weights, void* stream) {
     WN_CHECK_ARG(handles && first_tokens && uniforms && out_tokens && n_handles >= 1 && n > 0, "wn_decoder_run_batch: bad argument");
     WN_CHECK_SHAPE(n_handles <= kDecMaxBatch, "wn_decoder_run_batch: at most %d utterances per launch", kDecMaxBatch);
-    const float* P[kDecMaxBatch]; const float* hb[kDecMaxBatch]; const float* E[kDecMaxBatch]; const DecLayer* ly[kDecMaxBatch];
-    float* ar[kDecMaxBatch]; int* tr[kDecMaxBatch]; long long n0[kDecMaxBatch]; int ft[kDecMaxBatch]; SampleCtl ctl[kDecMaxBatch];
+    DecUtt utt[kDecMaxBatch];
     Decoder* D0 = (Decoder*)handles[0];
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
@@ -598,14 +603,12 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
                      "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
-        P[u] = D->fastP; hb[u] = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
-        E[u] = D->arena + D->causal[0].w; ly[u] = D->d_layers; ar[u] = D->arena; tr[u] = D->tok_ring; n0[u] = D->step;
-        ft[u] = (int)first_tokens[u]; ctl[u] = launch_ctl(D);
+        utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
     }
     WN_CHECK_SHAPE(decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
-    const int rc = decode_fast_launch_batch(n_handles, P, D0->meta.nlayers, hb, E, ly, ar, tr, n0, n, ft, uniforms, out_tokens,
-                                            prob_traces, D0->meta.Q, D0->meta.head_act, same_weights != 0, ctl, as_stream(stream));
+    const int rc = decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
+                                            as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];

@@ -174,7 +174,38 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-struct FastLds { const float* xold; float* xcur; float* zall; float* aold; int* ready; int* ready_old; };
+// The LDS of the chain workgroup (the one workgroup of k_decode_fast, workgroup 0 of the nine): the carve-up is defined
+// here once, as byte offsets; the launches ask for kBytes.
+struct ChainLds {
+    static constexpr int L = kMaxFastLayers;
+    static constexpr size_t oElds = 0;                            // float [256][2][32] embedding table of the causal layer
+    static constexpr size_t oXold = oElds + 256 * 2 * 32 * 4;     // float [L][32]   x_l[n-d] of every layer, fetched at step start
+    static constexpr size_t oXcur = oXold + L * 32 * 4;           // float [L+1][32] x_l[n]: input of layer l (output of l-1)
+    static constexpr size_t oZall = oXcur + (L + 1) * 32 * 4;     // float [L][32]   gate output of every layer of this step
+    static constexpr size_t oHvec = oZall + L * 32 * 4;           // float [256]     activated skip sums (one-workgroup form)
+    static constexpr size_t oLg = oHvec + 256 * 4;                // float [256]     logits / probabilities
+    static constexpr size_t oRed = oLg + 256 * 4;                 // float [16]
+    static constexpr size_t oCdf = oRed + 16 * 4;                 // double [256]
+    static constexpr size_t oTok = oCdf + 256 * 8;                // int [4]: current token, previous token
+    static constexpr size_t oRingt = oTok + 4 * 4;                // int [L] ring offset per layer
+    static constexpr size_t oDmask = oRingt + L * 4;              // int [L] d - 1 (d is a power of two: fw = 2)
+    static constexpr size_t oReady = oDmask + L * 4;              // int [4]: layers of this step whose z is in zall | whose aold is there
+    static constexpr size_t oAold = oReady + 4 * 4;               // float [L][64] x[n-d] half of every gate row, from wave 1
+    static constexpr size_t kBytes = oAold + L * 64 * 4;
+    float *Elds, *xold, *xcur, *zall, *hvec, *lg, *red, *aold;
+    double* cdf;
+    int *s_tok, *ringt, *dmask, *ready, *ready_old;
+    template <class T> static __device__ __forceinline__ T* at(float* sm, size_t off) {
+        return reinterpret_cast<T*>(reinterpret_cast<char*>(sm) + off);
+    }
+    __device__ __forceinline__ explicit ChainLds(float* sm)
+        : Elds(at<float>(sm, oElds)), xold(at<float>(sm, oXold)), xcur(at<float>(sm, oXcur)), zall(at<float>(sm, oZall)),
+          hvec(at<float>(sm, oHvec)), lg(at<float>(sm, oLg)), red(at<float>(sm, oRed)), aold(at<float>(sm, oAold)),
+          cdf(at<double>(sm, oCdf)), s_tok(at<int>(sm, oTok)), ringt(at<int>(sm, oRingt)), dmask(at<int>(sm, oDmask)),
+          ready(at<int>(sm, oReady)), ready_old(at<int>(sm, oReady) + 1) {}
+};
+static_assert(ChainLds::kBytes == 152800, "the chain workgroup's LDS (launch attribute, one workgroup per CU) must not move");
+static_assert(ChainLds::oCdf % 8 == 0 && ChainLds::oZall % 16 == 0, "cdf holds doubles; xold and zall are read as float4");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float f4c(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
@@ -205,7 +236,7 @@ __device__ __forceinline__ void wait_count(const int* c, int v) {               
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // wave 1: the x[n-d] half of gate row `lane` of layer l -> aold[l][lane]
-__device__ __forceinline__ void old_layer(const FastLds& S, const OldW& w, int l, int lane) {
+__device__ __forceinline__ void old_layer(const ChainLds& S, const OldW& w, int l, int lane) {
     const float* xo = S.xold + l * 32;                 // same address in every lane: broadcast reads
     f2 A0 = {0.f, 0.f}, A1 = {0.f, 0.f};
 #pragma unroll
@@ -252,7 +283,7 @@ __device__ __forceinline__ float xget(const u64* p, unsigned seq, u64* err, bool
     }
     return __uint_as_float((unsigned)w);
 }
-__device__ __forceinline__ float chain_layer(const FastLds& S, const ChainW& w, float& a_old, int l, const bool more,
+__device__ __forceinline__ float chain_layer(const ChainLds& S, const ChainW& w, float& a_old, int l, const bool more,
                                              int lane, float xc) {
     int c_next = 0;
     float a_next = 0.f;
@@ -306,10 +337,10 @@ __device__ __forceinline__ float chain_layer(const FastLds& S, const ChainW& w, 
     }
     return xn;
 }
-__device__ __forceinline__ void wait_layer(const FastLds& S, int l) { wait_count(S.ready, l); }   // z of layers < l is in zall
+__device__ __forceinline__ void wait_layer(const ChainLds& S, int l) { wait_count(S.ready, l); }   // z of layers < l is in zall
 
 // skip waves: rows 2t and 2t+1 of Ws_l z_l, accumulated over the layers
-__device__ __forceinline__ void skip_layer(const FastLds& S, const SkipW& w, int l, float& s0, float& s1) {
+__device__ __forceinline__ void skip_layer(const ChainLds& S, const SkipW& w, int l, float& s0, float& s1) {
     const float* z = S.zall + l * 32;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -327,7 +358,7 @@ static constexpr int kUnroll = 10;      // layers per trip of the layer loop (on
 // layer l + 1?" are then compile-time facts for nine layers of ten -- each was three scalar branches on the chain's
 // critical path.
 template <bool WHOLE>
-__device__ __forceinline__ float chain_run(const FastLds& S, const float* __restrict__ P, int nlayers, int lane, float xc,
+__device__ __forceinline__ float chain_run(const ChainLds& S, const float* __restrict__ P, int nlayers, int lane, float xc,
                                            float a_old, ChainW (&w)[2], const ChainOff& co) {   // w[0]: layer 0's weights, requested by the caller
     for (int l0 = 0; l0 < nlayers; l0 += kUnroll) {
 #pragma unroll
@@ -344,76 +375,156 @@ __device__ __forceinline__ float chain_run(const FastLds& S, const float* __rest
     return xc;
 }
 
-__global__ __launch_bounds__(kFT, 1) void k_decode_fast(
-    const float* __restrict__ P, const float* __restrict__ Ph, const float* __restrict__ hbias,
-    const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
-    int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
-    int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act, const SampleCtl sc) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* Elds = sm;                                   // [256][2][32] embedding table of the causal layer
-    float* xold = Elds + 256 * 2 * 32;                  // [L][32]   x_l[n-d] of every layer, fetched at step start
-    float* xcur = xold + kMaxFastLayers * 32;           // [L+1][32] x_l[n]: input of layer l (output of l-1)
-    float* zall = xcur + (kMaxFastLayers + 1) * 32;     // [L][32]   gate output of every layer of this step
-    float* hvec = zall + kMaxFastLayers * 32;           // [256]
-    float* lg = hvec + 256;                             // [256] logits / probabilities
-    float* red = lg + 256;                              // [16]
-    double* cdf = reinterpret_cast<double*>(red + 16);  // [256]
-    int* s_tok = reinterpret_cast<int*>(cdf + 256);     // [4]: current token, previous token
-    int* ringt = s_tok + 4;                             // [L] ring offset per layer
-    int* dmask = ringt + kMaxFastLayers;                // [L] d - 1 (d is a power of two: fw = 2)
-    int* ready = dmask + kMaxFastLayers;                // [2] layers of this step whose z is in zall | whose aold is there
-    float* aold = reinterpret_cast<float*>(ready + 4);  // [L][64] x[n-d] half of every gate row, from wave 1
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-
+// ---- the stages of a step that both kernels run in their chain workgroup, once each --------------------------------
+// Prologue: embedding table and ring tables to LDS, the token pair; ends in a barrier.  Returns this thread's head bias.
+__device__ __forceinline__ float chain_prologue(const ChainLds& S, const DecUtt& q, int nlayers, int tid) {
     for (int i = tid; i < 256 * 2 * 32 / 4; i += kFT)
-        reinterpret_cast<float4*>(Elds)[i] = reinterpret_cast<const float4*>(E)[i];
-    for (int i = tid; i < nlayers; i += kFT) { ringt[i] = layers[i].ring; dmask[i] = layers[i].d - 1; }
-    const float hb = hbias ? hbias[tid] : 0.f;
-    if (tid == 0) { s_tok[0] = first_token; s_tok[1] = tok_ring[0]; }     // fwc = 2: ring depth 1
+        reinterpret_cast<float4*>(S.Elds)[i] = reinterpret_cast<const float4*>(q.E)[i];
+    for (int i = tid; i < nlayers; i += kFT) { S.ringt[i] = q.layers[i].ring; S.dmask[i] = q.layers[i].d - 1; }
+    const float hb = q.hbias ? q.hbias[tid] : 0.f;
+    if (tid == 0) { S.s_tok[0] = q.first_token; S.s_tok[1] = q.tok_ring[0]; }     // fwc = 2: ring depth 1
     __syncthreads();
-    FastLds S{xold, xcur, zall, aold, ready, ready + 1};
+    return hb;
+}
+// every layer's x[n-d] was written at least one step ago: fetch them all, off the layer chain
+__device__ __forceinline__ void fetch_xold(const ChainLds& S, const float* __restrict__ arena, int nlayers, unsigned n, int tid) {
+    for (int i = tid; i < nlayers * 32; i += kFT) {
+        const int l = i >> 5;
+        S.xold[i] = arena[S.ringt[l] + (long long)(n & (unsigned)S.dmask[l]) * 32 + (i & 31)];
+    }
+}
+// layer 0's input from the embedding table; nothing of this step is published yet
+__device__ __forceinline__ void open_step(const ChainLds& S, int token, int tprev, int tid) {
+    if (tid < 32) S.xcur[tid] = S.Elds[(tprev * 2 + 0) * 32 + tid] + S.Elds[(token * 2 + 1) * 32 + tid];
+    if (tid == 0) {
+        __hip_atomic_store(S.ready, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(S.ready_old, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+// Waves 0 and 1 of a step.  Each meets ONE workgroup barrier, behind its first weight request: the other waves of the
+// workgroup meet theirs at the same point of the step.
+__device__ __forceinline__ void chain_wave(const ChainLds& S, const float* __restrict__ P, int nlayers, int lane) {
+    ChainW w[2];
+    const ChainOff co = chain_offsets(lane);
+    load_chain(w[0], P, 0, co);
+    __syncthreads();
+    const float xc0 = S.xcur[lane & 31];
+    wait_count(S.ready_old, 1);
+    const float a0 = S.aold[lane];
+    if (nlayers % kUnroll == 0) chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
+    else chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
+}
+__device__ __forceinline__ void old_wave(const ChainLds& S, const float* __restrict__ P, int nlayers, int lane) {
+    OldW wo[2];
+    load_old(wo[0], P, 0, 4u * lane);
+    __syncthreads();
+    for (int l0 = 0; l0 < nlayers; l0 += kUnroll) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int l = l0 + u;
+            if (l < nlayers) {
+                __builtin_amdgcn_s_waitcnt(0x0F70);          // as in the chain wave: exact counters
+                if (l + 1 < nlayers) load_old(wo[(u + 1) & 1], P, l + 1, 4u * lane);
+                old_layer(S, wo[u & 1], l, lane);
+            }
+        }
+    }
+}
+// Thread `tid` holds logit `tid`: temperature, then softmax over the 256.  Returns probability `tid`.  (The three lines
+// that store the row stay with the callers: with them in here, hipcc's k_decode_fast went from 346 VGPRs to 512 and 800 spills.)
+__device__ __forceinline__ float softmax_row(const ChainLds& S, float v, float inv_temp, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
+    if (inv_temp != 1.f) v *= inv_temp;            // temperature (uniform branch: a kernel argument)
+    float m = wave_allmax(v);
+    if (lane == 0) S.red[wv] = m;
+    lds_barrier();
+    m = fmaxf(fmaxf(S.red[0], S.red[1]), fmaxf(S.red[2], S.red[3]));
+    const float e = expf(v - m);
+    float s = wave_allsum(e);
+    if (lane == 0) S.red[4 + wv] = s;
+    lds_barrier();
+    s = S.red[4] + S.red[5] + S.red[6] + S.red[7];
+    return e * (1.f / s);
+}
+// The draw from the row in S.lg with the uniform u_draw: the token to *out_token and into the token pair.
+__device__ __forceinline__ void draw_token(const ChainLds& S, const SampleCtl& sc, double u_draw, int token,
+                                           int32_t* __restrict__ out_token, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
+    float* lg = S.lg;
+    double* cdf = S.cdf;
+    int* red = reinterpret_cast<int*>(S.red);
+    // top-k / top-p (uniform branch): the row in lg is truncated in place between the barrier above and the draw,
+    // which then runs on it unchanged; LDS only
+    if (sc.top_k > 0 || sc.top_p < 1.0) sample_filter<true>(lg, 256, tid, kFT, sc.top_k, sc.top_p);
+    // numpy: cdf = cumsum(float64(p)); cdf /= cdf[-1]; first index with cdf > u.  The running sum is a
+    // 256-long dependent chain (9.5 k cycles); a parallel scan associates differently, so its cdf may differ
+    // from numpy's by a few ulp (<= 256 * 2^-53).  It is therefore used only when no cdf_i / total lies within
+    // 1e-12 of u -- then both orders give the same index, provably -- and the exact chain runs otherwise.
+    double c = wave_scan_f64((double)lg[tid]);
+    if (lane == 63) cdf[wv] = c;                   // wave totals
+    lds_barrier();
+    {
+        const double w0 = cdf[0], w1 = cdf[1], w2 = cdf[2], w3 = cdf[3];
+        c += wv > 0 ? w0 : 0.0;
+        c += wv > 1 ? w1 : 0.0;
+        c += wv > 2 ? w2 : 0.0;
+        const double tot = ((w0 + w1) + w2) + w3;
+        const double q = c / tot;
+        const bool gt = q > u_draw;
+        const bool near = fabs(q - u_draw) < 1e-12;
+        const unsigned long long bal = __ballot(gt), nb = __ballot(near);
+        if (lane == 0) {
+            red[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
+            red[12 + wv] = nb ? 1 : 0;
+        }
+    }
+    lds_barrier();
+    const bool ambiguous = (red[12] | red[13] | red[14] | red[15]) != 0;     // uniform over the workgroup
+    if (ambiguous) {
+        if (tid == 0) {                    // numpy's float64 running sum, in index order
+            double cs = 0.0;
+            for (int i = 0; i < 256; ++i) { cs += (double)lg[i]; cdf[i] = cs; }
+        }
+        lds_barrier();
+        {
+            const double tot = cdf[255];
+            const bool gt = cdf[tid] / tot > u_draw;
+            const unsigned long long bal = __ballot(gt);
+            lds_barrier();
+            if (lane == 0) red[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
+        }
+        lds_barrier();
+    }
+    if (tid == 0) {
+        int idx = min(min(red[8], red[9]), min(red[10], red[11]));
+        if (idx > 255) idx = 255;
+        *out_token = idx;
+        S.s_tok[1] = token;
+        S.s_tok[0] = idx;
+    }
+}
+
+__global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlayers, int nsteps, int prob_stride,
+                                                        int apply_softmax, int do_sample, int head_act) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const ChainLds S(sm);
+    const float* P = q.P;
+    const float* Ph = P + (size_t)nlayers * kLayerFloats;
+    float* hvec = S.hvec;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float hb = chain_prologue(S, q, nlayers, tid);
     const unsigned t4 = 4u * (tid & 127);
 
     for (int it = 0; it < nsteps; ++it) {
-        const unsigned n = (unsigned)(n0 + it);
-        const int token = s_tok[0], tprev = s_tok[1];
-        const double u_draw = do_sample ? uniforms[it] : 0.0;      // fetched here, used after the network
-        // every layer's x[n-d] was written at least one step ago: fetch them all now, off the layer chain
-        for (int i = tid; i < nlayers * 32; i += kFT) {
-            const int l = i >> 5;
-            xold[i] = arena[ringt[l] + (long long)(n & (unsigned)dmask[l]) * 32 + (i & 31)];
-        }
-        if (tid < 32) xcur[tid] = Elds[(tprev * 2 + 0) * 32 + tid] + Elds[(token * 2 + 1) * 32 + tid];
-        if (tid == 0) {
-            __hip_atomic_store(ready, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store(ready + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        const unsigned n = (unsigned)(q.n0 + it);
+        const int token = S.s_tok[0], tprev = S.s_tok[1];
+        const double u_draw = do_sample ? q.uniforms[it] : 0.0;      // fetched here, used after the network
+        fetch_xold(S, q.arena, nlayers, n, tid);
+        open_step(S, token, tprev, tid);
         if (wv == 0) {
-            ChainW w[2];
-            const ChainOff co = chain_offsets(lane);
-            load_chain(w[0], P, 0, co);
-            __syncthreads();
-            const float xc0 = xcur[lane & 31];
-            wait_count(S.ready_old, 1);
-            const float a0 = aold[lane];
-            if (nlayers % kUnroll == 0) chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
-            else chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
+            chain_wave(S, P, nlayers, lane);
         } else if (wv == 1) {
-            OldW wo[2];
-            load_old(wo[0], P, 0, 4u * lane);
-            __syncthreads();
-            for (int l0 = 0; l0 < nlayers; l0 += kUnroll) {
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const int l = l0 + u;
-                    if (l < nlayers) {
-                        __builtin_amdgcn_s_waitcnt(0x0F70);          // as in the chain wave: exact counters
-                        if (l + 1 < nlayers) load_old(wo[(u + 1) & 1], P, l + 1, 4u * lane);
-                        old_layer(S, wo[u & 1], l, lane);
-                    }
-                }
-            }
+            old_wave(S, P, nlayers, lane);
         } else {
             float skip0 = 0.f, skip1 = 0.f;
             SkipW w[2];
@@ -454,7 +565,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
             // this step's x_cur of every layer becomes the newest ring column
             for (int i = tid; i < nlayers * 32; i += kFT) {
                 const int l = i >> 5;
-                arena[ringt[l] + (long long)(n & (unsigned)dmask[l]) * 32 + (i & 31)] = xcur[i];
+                q.arena[S.ringt[l] + (long long)(n & (unsigned)S.dmask[l]) * 32 + (i & 31)] = S.xcur[i];
             }
             float p0 = hb, p1 = 0.f, p2 = 0.f, p3 = 0.f;
 #define HEAD_ACC(W, J0)                                                                                   \
@@ -475,80 +586,15 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(
 #undef HEAD_ACC
             v = (p0 + p1) + (p2 + p3);
         }
-        if (apply_softmax) {
-            if (sc.inv_temp != 1.f) v *= sc.inv_temp;      // temperature (uniform branch: a kernel argument)
-            float m = wave_allmax(v);
-            if (lane == 0) red[wv] = m;
-            lds_barrier();
-            m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            const float e = expf(v - m);
-            float s = wave_allsum(e);
-            if (lane == 0) red[4 + wv] = s;
-            lds_barrier();
-            s = red[4] + red[5] + red[6] + red[7];
-            v = e * (1.f / s);
-        }
-        lg[tid] = v;
-        if (prob_out) prob_out[(long long)it * prob_stride + tid] = v;
+        if (apply_softmax) v = softmax_row(S, v, q.sc.inv_temp, tid);
+        S.lg[tid] = v;
+        if (q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
-        if (do_sample) {
-            // top-k / top-p (uniform branch): the row in lg is truncated in place between the barrier above and the draw,
-            // which then runs on it unchanged; LDS only
-            if (sc.top_k > 0 || sc.top_p < 1.0) sample_filter<true>(lg, 256, tid, kFT, sc.top_k, sc.top_p);
-            // numpy: cdf = cumsum(float64(p)); cdf /= cdf[-1]; first index with cdf > u.  The running sum is a
-            // 256-long dependent chain (9.5 k cycles); a parallel scan associates differently, so its cdf may differ
-            // from numpy's by a few ulp (<= 256 * 2^-53).  It is therefore used only when no cdf_i / total lies within
-            // 1e-12 of u -- then both orders give the same index, provably -- and the exact chain runs otherwise.
-            double c = wave_scan_f64((double)lg[tid]);
-            if (lane == 63) cdf[wv] = c;                   // wave totals
-            lds_barrier();
-            {
-                const double w0 = cdf[0], w1 = cdf[1], w2 = cdf[2], w3 = cdf[3];
-                c += wv > 0 ? w0 : 0.0;
-                c += wv > 1 ? w1 : 0.0;
-                c += wv > 2 ? w2 : 0.0;
-                const double tot = ((w0 + w1) + w2) + w3;
-                const double q = c / tot;
-                const bool gt = q > u_draw;
-                const bool near = fabs(q - u_draw) < 1e-12;
-                const unsigned long long bal = __ballot(gt), nb = __ballot(near);
-                if (lane == 0) {
-                    reinterpret_cast<int*>(red)[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
-                    reinterpret_cast<int*>(red)[12 + wv] = nb ? 1 : 0;
-                }
-            }
-            lds_barrier();
-            const int* rr = reinterpret_cast<const int*>(red);
-            const bool ambiguous = (rr[12] | rr[13] | rr[14] | rr[15]) != 0;     // uniform over the workgroup
-            if (ambiguous) {
-                if (tid == 0) {                    // numpy's float64 running sum, in index order
-                    double cs = 0.0;
-                    for (int i = 0; i < 256; ++i) { cs += (double)lg[i]; cdf[i] = cs; }
-                }
-                lds_barrier();
-                {
-                    const double tot = cdf[255];
-                    const bool gt = cdf[tid] / tot > u_draw;
-                    const unsigned long long bal = __ballot(gt);
-                    lds_barrier();
-                    if (lane == 0) reinterpret_cast<int*>(red)[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
-                }
-                lds_barrier();
-            }
-            if (tid == 0) {
-                const int* r = reinterpret_cast<const int*>(red) + 8;
-                int idx = min(min(r[0], r[1]), min(r[2], r[3]));
-                if (idx > 255) idx = 255;
-                out_tokens[it] = idx;
-                s_tok[1] = token;
-                s_tok[0] = idx;
-            }
-        } else if (tid == 0) {
-            s_tok[1] = token;
-        }
+        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
+        else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
     }
-    if (tid == 0) tok_ring[0] = s_tok[1];          // the token before the next one to be consumed
+    if (tid == 0) q.tok_ring[0] = S.s_tok[1];      // the token before the next one to be consumed
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -574,18 +620,22 @@ static constexpr int kXZ = 0;                                   // X layout (u64
 static constexpr int kD10MaxL = 40;
 static constexpr int kD10Skip = 8;                              // skip workgroups
 __device__ __host__ __forceinline__ int x_pl(int nlayers) { return nlayers * 64; }
-__device__ __host__ __forceinline__ int x_err(int nlayers) { return nlayers * 64 + 8 * 256 + 8; }   // != 0: a wait gave up, the run is void
+__device__ __host__ __forceinline__ int x_err(int nlayers) { return x_pl(nlayers) + kD10Skip * 256 + 8; }   // != 0: a wait gave up, the run is void
+__device__ __host__ __forceinline__ int x_entries(int nlayers) { return x_err(nlayers) + 8; }   // the whole area, error entry inside
+// X lives behind the packed weights of its handle: layers | head | X (decode_fast_pack_floats)
+static u64* x_area(const float* P, int nlayers) {
+    return reinterpret_cast<u64*>(const_cast<float*>(P) + (size_t)nlayers * kLayerFloats + 256 * 256);
+}
 
 // `wg`: this workgroup's role in its utterance's group of nine (0 = chain, 1..8 = skip rows): blockIdx.x for one utterance,
 // blockIdx.x % 9 in the batched launch (k_decode_fast3_batch)
-__device__ __forceinline__ void decode_fast3_body(
-    const int wg, const float* __restrict__ P, const float* __restrict__ Ph, const float* __restrict__ hbias,
-    const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
-    int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
-    int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act, u64* __restrict__ X, const SampleCtl sc) {
+__device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q, int nlayers, int nsteps, int prob_stride,
+                                                  int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* P = q.P;
+    const float* Ph = P + (size_t)nlayers * kLayerFloats;
+    u64* X = q.X;
 
     if (wg >= 1 && wg <= kD10Skip) {
         // ---- 32 skip rows: thread (r = tid / 8, s = tid % 8) holds Ws_l[row][4 s .. 4 s + 3] of every layer ----
@@ -635,75 +685,27 @@ __device__ __forceinline__ void decode_fast3_body(
         return;
     }
     // ---- workgroup 0: the chain, softmax, sampling (k_decode_fast without its skip waves and head) ----
-    float* Elds = sm;                                   // [256][2][32] embedding table of the causal layer
-    float* xold = Elds + 256 * 2 * 32;
-    float* xcur = xold + kMaxFastLayers * 32;
-    float* zall = xcur + (kMaxFastLayers + 1) * 32;
-    float* hvec = zall + kMaxFastLayers * 32;
-    float* lg = hvec + 256;
-    float* red = lg + 256;
-    double* cdf = reinterpret_cast<double*>(red + 16);
-    int* s_tok = reinterpret_cast<int*>(cdf + 256);
-    int* ringt = s_tok + 4;
-    int* dmask = ringt + kMaxFastLayers;
-    int* ready = dmask + kMaxFastLayers;
-    float* aold = reinterpret_cast<float*>(ready + 4);
-    for (int i = tid; i < 256 * 2 * 32 / 4; i += kFT)
-        reinterpret_cast<float4*>(Elds)[i] = reinterpret_cast<const float4*>(E)[i];
-    for (int i = tid; i < nlayers; i += kFT) { ringt[i] = layers[i].ring; dmask[i] = layers[i].d - 1; }
-    if (tid == 0) { s_tok[0] = first_token; s_tok[1] = tok_ring[0]; }
-    const float hb = hbias ? hbias[tid] : 0.f;
-    __syncthreads();
-    FastLds S{xold, xcur, zall, aold, ready, ready + 1};
+    const ChainLds S(sm);
+    const float hb = chain_prologue(S, q, nlayers, tid);
     bool dead0 = false;                                   // this thread's wait for the logit shares gave up: wait for nothing any more
 
     for (int it = 0; it < nsteps; ++it) {
-        const unsigned n = (unsigned)(n0 + it);
+        const unsigned n = (unsigned)(q.n0 + it);
         const unsigned seq = (unsigned)(it + 1);
-        const int token = s_tok[0], tprev = s_tok[1];
-        const double u_draw = do_sample ? uniforms[it] : 0.0;
-        if (it == 0) {                                    // later steps: fetched during the previous step's wait (below)
-            for (int i = tid; i < nlayers * 32; i += kFT) {
-                const int l = i >> 5;
-                xold[i] = arena[ringt[l] + (long long)(n & (unsigned)dmask[l]) * 32 + (i & 31)];
-            }
-        }
-        if (tid < 32) xcur[tid] = Elds[(tprev * 2 + 0) * 32 + tid] + Elds[(token * 2 + 1) * 32 + tid];
-        if (tid == 0) {
-            __hip_atomic_store(ready, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store(ready + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        const int token = S.s_tok[0], tprev = S.s_tok[1];
+        const double u_draw = do_sample ? q.uniforms[it] : 0.0;
+        if (it == 0) fetch_xold(S, q.arena, nlayers, n, tid);   // later steps: fetched during the previous step's wait (below)
+        open_step(S, token, tprev, tid);
         if (wv == 0) {
-            ChainW w[2];
-            const ChainOff co = chain_offsets(lane);
-            load_chain(w[0], P, 0, co);
-            __syncthreads();
-            const float xc0 = xcur[lane & 31];
-            wait_count(S.ready_old, 1);
-            const float a0 = aold[lane];
-            if (nlayers % kUnroll == 0) chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
-            else chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
+            chain_wave(S, P, nlayers, lane);
         } else if (wv == 1) {
-            OldW wo[2];
-            load_old(wo[0], P, 0, 4u * lane);
-            __syncthreads();
-            for (int l0 = 0; l0 < nlayers; l0 += kUnroll) {
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const int l = l0 + u;
-                    if (l < nlayers) {
-                        __builtin_amdgcn_s_waitcnt(0x0F70);
-                        if (l + 1 < nlayers) load_old(wo[(u + 1) & 1], P, l + 1, 4u * lane);
-                        old_layer(S, wo[u & 1], l, lane);
-                    }
-                }
-            }
+            old_wave(S, P, nlayers, lane);
         } else if (wv == 2) {
             __syncthreads();
             // the publisher: follows the chain through the layer counter in LDS and hands every layer's z to the other CUs
             for (int l = 0; l < nlayers; ++l) {
                 wait_layer(S, l + 1);
-                xput(X + kXZ + l * 64 + lane, zall[l * 32 + (lane & 31)], seq);
+                xput(X + kXZ + l * 64 + lane, S.zall[l * 32 + (lane & 31)], seq);
             }
         } else {
             __syncthreads();
@@ -711,13 +713,13 @@ __device__ __forceinline__ void decode_fast3_body(
         lds_barrier();                                    // the chain has written every x_cur
         for (int i = tid; i < nlayers * 32; i += kFT) {   // this step's x_cur of every layer becomes the newest ring column
             const int l = i >> 5;
-            const unsigned dm = (unsigned)dmask[l];
-            float* ring = arena + ringt[l] + (i & 31);
-            const float xn = xcur[i];
+            const unsigned dm = (unsigned)S.dmask[l];
+            float* ring = q.arena + S.ringt[l] + (i & 31);
+            const float xn = S.xcur[i];
             ring[(long long)(n & dm) * 32] = xn;
             // ... and the NEXT step's x[n + 1 - d] is fetched now, under the wait for the logits: with d = 1 it is the value just
             // stored, otherwise a column written d - 1 steps ago (the chain and wave 1 are through with xold: barrier above)
-            xold[i] = dm == 0u ? xn : ring[(long long)((n + 1u) & dm) * 32];
+            S.xold[i] = dm == 0u ? xn : ring[(long long)((n + 1u) & dm) * 32];
         }
         // logit `tid` = bias + the eight workgroups' shares, added in workgroup order.  The eight entries are requested
         // together (one memory round trip), re-requested together until all carry this step's number
@@ -746,117 +748,46 @@ __device__ __forceinline__ void decode_fast3_body(
 #pragma unroll
             for (int k = 0; k < kD10Skip; ++k) v += __uint_as_float((unsigned)wd[k]);
         }
-        if (apply_softmax) {
-            if (sc.inv_temp != 1.f) v *= sc.inv_temp;      // temperature (uniform branch: a kernel argument)
-            float m = wave_allmax(v);
-            if (lane == 0) red[wv] = m;
-            lds_barrier();
-            m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-            const float e = expf(v - m);
-            float s = wave_allsum(e);
-            if (lane == 0) red[4 + wv] = s;
-            lds_barrier();
-            s = red[4] + red[5] + red[6] + red[7];
-            v = e * (1.f / s);
-        }
-        lg[tid] = v;
-        if (prob_out) prob_out[(long long)it * prob_stride + tid] = v;
+        if (apply_softmax) v = softmax_row(S, v, q.sc.inv_temp, tid);
+        S.lg[tid] = v;
+        if (q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
-        if (do_sample) {
-            // top-k / top-p (uniform branch): the row in lg is truncated in place between the barrier above and the draw,
-            // which then runs on it unchanged; LDS only
-            if (sc.top_k > 0 || sc.top_p < 1.0) sample_filter<true>(lg, 256, tid, kFT, sc.top_k, sc.top_p);
-            double c = wave_scan_f64((double)lg[tid]);
-            if (lane == 63) cdf[wv] = c;
-            lds_barrier();
-            {
-                const double w0 = cdf[0], w1 = cdf[1], w2 = cdf[2], w3 = cdf[3];
-                c += wv > 0 ? w0 : 0.0;
-                c += wv > 1 ? w1 : 0.0;
-                c += wv > 2 ? w2 : 0.0;
-                const double tot = ((w0 + w1) + w2) + w3;
-                const double q = c / tot;
-                const bool gt = q > u_draw;
-                const bool near = fabs(q - u_draw) < 1e-12;
-                const unsigned long long bal = __ballot(gt), nb = __ballot(near);
-                if (lane == 0) {
-                    reinterpret_cast<int*>(red)[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
-                    reinterpret_cast<int*>(red)[12 + wv] = nb ? 1 : 0;
-                }
-            }
-            lds_barrier();
-            const int* rr = reinterpret_cast<const int*>(red);
-            const bool ambiguous = (rr[12] | rr[13] | rr[14] | rr[15]) != 0;
-            if (ambiguous) {
-                if (tid == 0) {
-                    double cs = 0.0;
-                    for (int i = 0; i < 256; ++i) { cs += (double)lg[i]; cdf[i] = cs; }
-                }
-                lds_barrier();
-                {
-                    const double tot = cdf[255];
-                    const bool gt = cdf[tid] / tot > u_draw;
-                    const unsigned long long bal = __ballot(gt);
-                    lds_barrier();
-                    if (lane == 0) reinterpret_cast<int*>(red)[8 + wv] = bal ? wv * 64 + __ffsll((long long)bal) - 1 : 256;
-                }
-                lds_barrier();
-            }
-            if (tid == 0) {
-                const int* r = reinterpret_cast<const int*>(red) + 8;
-                int idx = min(min(r[0], r[1]), min(r[2], r[3]));
-                if (idx > 255) idx = 255;
-                out_tokens[it] = idx;
-                s_tok[1] = token;
-                s_tok[0] = idx;
-            }
-        } else if (tid == 0) {
-            s_tok[1] = token;
-        }
+        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
+        else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
     }
-    if (tid == 0) tok_ring[0] = s_tok[1];
+    if (tid == 0) q.tok_ring[0] = S.s_tok[1];
 }
 
-__global__ __launch_bounds__(kFT, 1) void k_decode_fast3(
-    const float* __restrict__ P, const float* __restrict__ Ph, const float* __restrict__ hbias,
-    const float* __restrict__ E, const DecLayer* __restrict__ layers, int nlayers, float* __restrict__ arena,
-    int* __restrict__ tok_ring, long long n0, int nsteps, int first_token, const double* __restrict__ uniforms,
-    int32_t* __restrict__ out_tokens, float* __restrict__ prob_out, int prob_stride, int apply_softmax,
-    int do_sample, int head_act, u64* __restrict__ X, const SampleCtl sc) {
-    decode_fast3_body((int)blockIdx.x, P, Ph, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps, first_token, uniforms,
-                      out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X, sc);
+__global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nlayers, int nsteps, int prob_stride,
+                                                         int apply_softmax, int do_sample, int head_act) {
+    decode_fast3_body((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
 }
 
 // N independent utterances in ONE launch: nine workgroups each (the single-GPU form of "replicas only", SURVEY 8(e): batch 1
 // has a strict sample-to-sample dependency, so the other 247 CUs can only run OTHER utterances).  Every utterance has its own
 // decoder state (rings, token ring, exchange entries, packed weights: a handle each), its own uniforms and outputs; the groups
 // share nothing and never wait for each other, so an utterance's tokens are those of its own wn_decoder_run, bit for bit.
-struct DecBatchItem {
-    const float* P; const float* hbias; const float* E; const DecLayer* layers; float* arena; int* tok_ring;
-    long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out; u64* X; int first_token; int pad;
-    SampleCtl sc;                      // per utterance: its handle's wn_decoder_set_sampling
-};
-struct DecBatchArgs { DecBatchItem it[kDecMaxBatch]; };
+struct DecBatchArgs { DecUtt it[kDecMaxBatch]; };
+static_assert(sizeof(DecBatchArgs) + 4 * sizeof(int) <= 4096, "kernel arguments are passed by value: 4 KB at most");
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int nsteps, int prob_stride,
                                                                int head_act) {
     const int u = blockIdx.x / (kD10Skip + 1);
-    const DecBatchItem& q = a.it[u];
-    decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), q.P, q.P + (size_t)nlayers * kLayerFloats, q.hbias, q.E, q.layers,
-                      nlayers, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out,
-                      prob_stride, 1, 1, head_act, q.X, q.sc);
+    decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, nsteps, prob_stride, 1, 1, head_act);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) X[i] = 0ull;
 }
-
-size_t decode_fast_lds_bytes() {
-    return (size_t)(256 * 2 * 32 + kMaxFastLayers * 32 + (kMaxFastLayers + 1) * 32 + kMaxFastLayers * 32 + 256 + 256 + 16) * 4 +
-           256 * 8 + (4 + 2 * kMaxFastLayers + 4) * 4 + kMaxFastLayers * 64 * 4;
+// the exchange entries are cleared by a kernel, in stream order, before every launch that uses them
+static void zero_x(u64* X, int nlayers, hipStream_t s) {
+    const int nx = x_entries(nlayers);
+    hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, X, nx);
 }
-size_t decode_fast_pack_floats(int nlayers) {            // weights, then the exchange entries of the three-workgroup form (8 bytes each)
-    return (size_t)nlayers * kLayerFloats + 256 * 256 + 2 * ((size_t)nlayers * 64 + 8 * 256 + 16);
+
+size_t decode_fast_lds_bytes() { return ChainLds::kBytes; }
+size_t decode_fast_pack_floats(int nlayers) {            // weights, then the exchange entries of the nine-workgroup form (8 bytes each)
+    return (size_t)nlayers * kLayerFloats + 256 * 256 + 2 * (size_t)x_entries(nlayers);
 }
 
 int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
@@ -869,34 +800,26 @@ int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
     return WN_OK;
 }
 
-int decode_fast_launch(const float* P, int nlayers, const float* hbias, const float* E, const DecLayer* layers,
-                       float* arena, int* tok_ring, long long n0, int nsteps, int first_token,
-                       const double* uniforms, int32_t* out_tokens, float* prob_out, int prob_stride,
-                       int apply_softmax, int do_sample, int head_act, bool three_wgs, const SampleCtl& ctl, hipStream_t s) {
+int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int apply_softmax, int do_sample, int head_act,
+                       bool three_wgs, hipStream_t s) {
     WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast, k_decode_fast3);
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
         // per device, per call: cheap, and a process may drive several devices).  What the count cannot see -- other work
         // holding the CUs for seconds -- ends in a given-up wait that wn_decoder_status reports (no trap, no hang).
         int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < kD10Skip + 1)
-            three_wgs = false;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu >= kD10Skip + 1) {
+            q.X = x_area(q.P, nlayers);
+            zero_x(q.X, nlayers, s);
+            hipLaunchKernelGGL(k_decode_fast3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
+                               prob_stride, apply_softmax, do_sample, head_act);
+            WN_LAUNCH_CHECK();
+            return WN_OK;
+        }
     }
-    if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
-        // the exchange entries live behind the packed weights (decode_fast_pack_floats); cleared by a kernel, in stream order
-        u64* X = reinterpret_cast<u64*>(const_cast<float*>(P) + (size_t)nlayers * kLayerFloats + 256 * 256);
-        const int nx = nlayers * 64 + 8 * 256 + 16;
-        hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, X, nx);
-        hipLaunchKernelGGL(k_decode_fast3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, P,
-                           P + (size_t)nlayers * kLayerFloats, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps,
-                           first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, X, ctl);
-        WN_LAUNCH_CHECK();
-        return WN_OK;
-    }
-    hipLaunchKernelGGL(k_decode_fast, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, P,
-                       P + (size_t)nlayers * kLayerFloats, hbias, E, layers, nlayers, arena, tok_ring, n0, nsteps,
-                       first_token, uniforms, out_tokens, prob_out, prob_stride, apply_softmax, do_sample, head_act, ctl);
+    hipLaunchKernelGGL(k_decode_fast, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
+                       apply_softmax, do_sample, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;
 }
@@ -909,30 +832,23 @@ int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps) {
     return n_utt * (kD10Skip + 1) <= n_cu ? 1 : 0;             // every workgroup resident (one per CU by LDS footprint)
 }
 
-int decode_fast_launch_batch(int n_utt, const float* const* P, int nlayers, const float* const* hbias, const float* const* E,
-                             const DecLayer* const* layers, float* const* arena, int* const* tok_ring, const long long* n0,
-                             int nsteps, const int* first_token, const double* const* uniforms, int32_t* const* out_tokens,
-                             float* const* prob_out, int prob_stride, int head_act, bool same_weights, const SampleCtl* ctl,
-                             hipStream_t s) {
+int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
+                             bool same_weights, hipStream_t s) {
     if (!decode_fast_batch_ok(nlayers, n_utt, nsteps)) {
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
         return WN_ESHAPE;
     }
     WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch);
     DecBatchArgs a{};
-    const int nx = nlayers * 64 + 8 * 256 + 16;
     for (int u = 0; u < n_utt; ++u) {
-        DecBatchItem& q = a.it[u];
+        DecUtt& q = a.it[u];
+        q = utt[u];
+        q.X = x_area(q.P, nlayers);        // the utterance's own exchange entries, whoever's weights it reads
+        zero_x(q.X, nlayers, s);
         // same_weights (the caller's word that every handle was created from the same weights): every utterance reads utterance
         // 0's packed weights, embedding table and head bias -- the 28 chain workgroups then stream ONE 0.96 MB copy per step
         // through the XCDs' L2s instead of 28; the state (rings, token ring, exchange entries) stays per utterance
-        const int wu = same_weights ? 0 : u;
-        q.P = P[wu]; q.hbias = hbias[wu]; q.E = E[wu]; q.layers = layers[u]; q.arena = arena[u]; q.tok_ring = tok_ring[u];
-        q.n0 = n0[u]; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_out ? prob_out[u] : nullptr;
-        q.first_token = first_token[u];
-        q.sc = ctl[u];
-        q.X = reinterpret_cast<u64*>(const_cast<float*>(P[u]) + (size_t)nlayers * kLayerFloats + 256 * 256);
-        hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, q.X, nx);
+        if (same_weights) { q.P = utt[0].P; q.hbias = utt[0].hbias; q.E = utt[0].E; }
     }
     hipLaunchKernelGGL(k_decode_fast3_batch, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
                        nsteps, prob_stride, head_act);
@@ -942,13 +858,11 @@ int decode_fast_launch_batch(int n_utt, const float* const* P, int nlayers, cons
 
 // 0 = the last nine-workgroup run's exchange completed; 1 = a wait gave up (its tokens are void).  Synchronises the stream.
 int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up) {
-    const u64* X = reinterpret_cast<const u64*>(P + (size_t)nlayers * kLayerFloats + 256 * 256);
     u64 w = 0;
-    WN_HIP(hipMemcpyAsync(&w, X + x_err(nlayers), sizeof(w), hipMemcpyDeviceToHost, s));
+    WN_HIP(hipMemcpyAsync(&w, x_area(P, nlayers) + x_err(nlayers), sizeof(w), hipMemcpyDeviceToHost, s));
     WN_HIP(hipStreamSynchronize(s));
     *gave_up = w != 0 ? 1 : 0;
     return WN_OK;
 }
 
 }  // namespace wn
-

@@ -7,8 +7,8 @@
 //           keep i  iff  before(i) < top_p * total  (the rank-0 token always)
 //   result  excluded entries become 0.0f, kept entries keep their fp32 value (no renormalisation: the draw divides by
 //           the float64 total of the row it is given).
-// One device function for every sampler (k_decode, k_decode_fast, workgroup 0 of k_decode_fast3 / _batch, and the
-// standalone k_sample_filtered): the row sits in LDS, all `nt` threads of the workgroup call it behind a
+// One device function for every sampler (k_decode, draw_token -- the one draw of k_decode_fast and of workgroup 0 of
+// k_decode_fast3 / _batch -- and the standalone k_sample_filtered): the row sits in LDS, all `nt` threads of the workgroup call it behind a
 // workgroup-uniform branch, it works in place and holds its decisions in a register bit mask (one bit per token of the
 // thread: Q <= 32 * nt).  No global-memory traffic.
 #pragma once
