@@ -295,17 +295,30 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
  * receives the n emitted tokens; prob_trace (n*Q) is optional.                                  */
 int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, int n,
                    int32_t* out_tokens, float* prob_trace, void* stream);
-/* ABI 4.  n_handles independent utterances in ONE launch, nine workgroups each (generate.py:9-60 is batch 1 with a strict
- * sample-to-sample dependency, wavenet.py:286,290,354: a single utterance can use 9 of the GPU's 256 CUs -- the rest can only
- * run OTHER utterances; SURVEY 8(e) "replicas only", on one GPU).  Every handle is a decoder of its own (wn_decoder_create +
- * wn_decoder_load_state: its rings, its packed weights), all of the same model shape, none created with
- * WN_DECODER_ONE_WORKGROUP; uniforms[u] (n doubles), out_tokens[u] (n) and the optional prob_traces[u] (n * Q; the array
- * itself may be NULL) are device pointers held in HOST arrays, first_tokens is a host array.  At most wn_decoder_batch_max()
- * (28) utterances, and 9 * n_handles workgroups must fit the device's CUs (WN_ESHAPE otherwise); n >= 2.  The groups share
- * nothing: an utterance's tokens are those of its own wn_decoder_run with the same uniforms, bit for bit.  same_weights != 0 is
- * the caller's word that every handle was created from (and updated with) the SAME weights: all utterances then read handle 0's
- * packed weights (one copy through the L2s instead of n_handles; each keeps its own state) -- same tokens, higher rate.
- * wn_decoder_status(handle) reports per utterance as after wn_decoder_run. */
+/* ABI 4.  n_handles independent utterances in ONE launch (generate.py:9-60 is batch 1 with a strict sample-to-sample
+ * dependency, wavenet.py:286,290,354: a single utterance can use 9 of the GPU's 256 CUs at most -- the rest can only run OTHER
+ * utterances; SURVEY 8(e) "replicas only", on one GPU).  Every handle is a decoder of its own (wn_decoder_create +
+ * wn_decoder_load_state: its rings, its packed weights, its wn_decoder_set_sampling), all of the same model shape; uniforms[u]
+ * (n doubles), out_tokens[u] (n) and the optional prob_traces[u] (n * Q; the array itself may be NULL) are device pointers held
+ * in HOST arrays, first_tokens is a host array.  The utterances share nothing: an utterance's tokens and probability trace are
+ * those of its own wn_decoder_run on the same handle with the same uniforms, bit for bit, and every handle's step counter
+ * advances by n.  Handle 0 chooses between two forms, and all handles must be of its form (WN_ESHAPE otherwise):
+ *   - nine workgroups per utterance: handles of the specialised decoder (config 4's shape, no WN_EXEC_FORCE_GENERIC).  At most
+ *     wn_decoder_batch_max() (28) utterances, 9 * n_handles workgroups must fit the device's CUs (WN_ESHAPE otherwise), and
+ *     n >= 2.  same_weights != 0 is the caller's word that every handle was created from (and updated with) the SAME weights:
+ *     all utterances then read handle 0's packed weights (one copy through the L2s instead of n_handles; each keeps its own
+ *     state) -- same tokens, higher rate.  wn_decoder_status(handle) reports per utterance as after wn_decoder_run.
+ *   - one workgroup per utterance: handles of the any-shape decoder (every other shape, or WN_EXEC_FORCE_GENERIC).  At most
+ *     WN_DECODER_BATCH_MAX_ANY utterances, n >= 1; the workgroups never wait for each other, so nothing has to be resident
+ *     and wn_decoder_status stays "synchronise, WN_OK".  The handles must agree in Q, channels, filter widths, every layer's
+ *     dilation and width, and head activation.  same_weights is checked as above and otherwise ignored: each utterance
+ *     reads its own packed weights.  The per-utterance arguments travel in a device table owned by handle 0, allocated at
+ *     the first call and grown only by a larger batch: a repeated call allocates nothing and waits on the host only for the
+ *     previous call's table copy (not its launch) before it rewrites the pinned image of the table.
+ * A handle created with WN_DECODER_ONE_WORKGROUP is refused (WN_ESHAPE): that kernel has no batched form.  Every refusal
+ * comes before any device work. */
+#define WN_DECODER_BATCH_MAX_ANY 1024      /* utterances per launch of the one-workgroup-per-utterance form */
+/* the limit of the nine-workgroup form (28) */
 int wn_decoder_batch_max(void);
 int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms, int n,
                          int32_t* const* out_tokens, float* const* prob_traces, int same_weights, void* stream);

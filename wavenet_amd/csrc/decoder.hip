@@ -44,6 +44,12 @@ struct Decoder {
     bool three_wgs = true;        // wn_decoder_run on nine workgroups (decoder_fast.hip); WN_DECODER_ONE_WORKGROUP clears it
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
     SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
+    // wn_decoder_run_batch on any-shape handles, as handle 0 of the call: the per-utterance table (DecAnyUtt) in device
+    // memory, its pinned host image, and the event behind the last copy of the image (the image is rewritten after it)
+    void* batch_tab = nullptr;
+    void* batch_img = nullptr;
+    int batch_cap = 0;
+    hipEvent_t batch_copied = nullptr;
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
 };
@@ -142,14 +148,17 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
     return r;
 }
 
-__global__ __launch_bounds__(kDecThreads) void k_decode(
-    DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
+// The step loop of one utterance on one workgroup: k_decode runs it for its handle, workgroup u of k_decode_batch for
+// utterance u.  Everything it touches -- arena, token ring, uniforms, outputs -- is the utterance's own; `sc` and the flags
+// are the same for every thread of the workgroup.
+__device__ __forceinline__ void decode_steps(
+    const DecMeta& M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
-    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc) {
+    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl& sc) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, NT = blockDim.x;
-    const bool filt = sc.top_k > 0 || sc.top_p < 1.0;      // workgroup-uniform (kernel arguments)
+    const bool filt = sc.top_k > 0 || sc.top_p < 1.0;      // workgroup-uniform: kernel arguments, or the workgroup's own table entry
     float* xcur = sm;                    // [maxc] current column of the residual stream / causal stack
     float* xnew = xcur + M.maxc;         // [maxc]
     float* ab = xnew + M.maxc;           // [2*maxc] gate pre-activations
@@ -295,6 +304,33 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(kDecThreads) void k_decode(
+    DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
+    const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
+    int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
+    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc) {
+    decode_steps(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
+                 apply_softmax, do_sample, sc);
+}
+
+// One utterance of the batched any-shape launch: what k_decode takes as arguments, from the utterance's own handle.  The
+// table of them lives in device memory (Decoder::batch_tab of handle 0).
+struct DecAnyUtt {
+    const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
+    float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
+    int first_token; int pad;
+    SampleCtl sc;
+};
+
+// wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
+// never wait for each other, so any number of them may be queued behind the CUs.
+__global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int nsteps) {
+    if ((int)blockIdx.x >= n_utt) return;
+    const DecAnyUtt q = tab[blockIdx.x];
+    decode_steps(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens,
+                 q.prob_out, M.Q, 1, 1, q.sc);
 }
 
 // ---- host side -------------------------------------------------------------------------------
@@ -481,6 +517,9 @@ int wn_decoder_destroy(void* handle) {
     if (D->fastP) (void)hipFree(D->fastP);
     if (D->tok_ring) (void)hipFree(D->tok_ring);
     if (D->dmeta) (void)hipFree(D->dmeta);
+    if (D->batch_tab) (void)hipFree(D->batch_tab);
+    if (D->batch_img) (void)hipHostFree(D->batch_img);
+    if (D->batch_copied) (void)hipEventDestroy(D->batch_copied);
     delete D;
     return WN_OK;
 }
@@ -578,33 +617,88 @@ int wn_decoder_set_sampling(void* handle, float temperature, int top_k, double t
 
 int wn_decoder_batch_max(void) { return kDecMaxBatch; }
 
+// the any-shape form of wn_decoder_run_batch, after every check: the utterances' table into handle 0's device buffer (one
+// async copy from its pinned image), then one launch of n_handles workgroups
+static int run_batch_any(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms, int n,
+                         int32_t* const* out_tokens, float* const* prob_traces, hipStream_t s) {
+    Decoder* D0 = (Decoder*)handles[0];
+    if (n_handles > D0->batch_cap) {                   // first use, or a larger batch than ever before
+        if (D0->batch_tab) { WN_HIP(hipFree(D0->batch_tab)); D0->batch_tab = nullptr; }      // hipFree waits for its readers
+        if (D0->batch_img) { WN_HIP(hipHostFree(D0->batch_img)); D0->batch_img = nullptr; }
+        D0->batch_cap = 0;
+        if (!D0->batch_copied) WN_HIP(hipEventCreateWithFlags(&D0->batch_copied, hipEventDisableTiming));
+        WN_HIP(hipMalloc(&D0->batch_tab, (size_t)n_handles * sizeof(DecAnyUtt)));
+        WN_HIP(hipHostMalloc(&D0->batch_img, (size_t)n_handles * sizeof(DecAnyUtt), hipHostMallocDefault));
+        D0->batch_cap = n_handles;
+    } else {
+        // the previous call's copy may still be queued (behind other work of its stream) and reads the image: a host wait
+        // for that COPY, not for the launch behind it; a caller that has read its tokens back finds it done.  (Like the
+        // allocation above, not something a stream capture can hold.)
+        WN_HIP(hipEventSynchronize(D0->batch_copied));
+    }
+    DecAnyUtt* img = (DecAnyUtt*)D0->batch_img;
+    for (int u = 0; u < n_handles; ++u) {
+        const Decoder* D = (const Decoder*)handles[u];
+        DecAnyUtt q{};
+        q.causal = D->d_causal; q.layers = D->d_layers; q.heads = D->d_heads; q.arena = D->arena; q.tok_ring = D->tok_ring;
+        q.n0 = D->step; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_traces ? prob_traces[u] : nullptr;
+        q.first_token = (int)first_tokens[u]; q.sc = launch_ctl(D);
+        img[u] = q;
+    }
+    WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
+    WN_HIP(hipEventRecord(D0->batch_copied, s));
+    hipLaunchKernelGGL(k_decode_batch, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
+                       n_handles, n);
+    WN_LAUNCH_CHECK();
+    for (int u = 0; u < n_handles; ++u) ((Decoder*)handles[u])->step += n;
+    return WN_OK;
+}
+
 int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms, int n,
                          int32_t* const* out_tokens, float* const* prob_traces, int same_weights, void* stream) {
     WN_CHECK_ARG(handles && first_tokens && uniforms && out_tokens && n_handles >= 1 && n > 0, "wn_decoder_run_batch: bad argument");
-    WN_CHECK_SHAPE(n_handles <= kDecMaxBatch, "wn_decoder_run_batch: at most %d utterances per launch", kDecMaxBatch);
-    DecUtt utt[kDecMaxBatch];
     Decoder* D0 = (Decoder*)handles[0];
+    WN_CHECK_ARG(D0, "wn_decoder_run_batch: NULL handle of utterance 0");
+    // handle 0 chooses the form: the nine-workgroup decoder (decoder_fast.hip) or one workgroup of k_decode_batch per utterance
+    const bool any = !D0->fastP;
+    const int limit = any ? WN_DECODER_BATCH_MAX_ANY : kDecMaxBatch;
+    WN_CHECK_SHAPE(n_handles <= limit, "wn_decoder_run_batch: at most %d utterances per launch of %s decoders", limit,
+                   any ? "any-shape" : "nine-workgroup");
+    DecUtt utt[kDecMaxBatch];
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
         WN_CHECK_ARG(D && uniforms[u] && out_tokens[u], "wn_decoder_run_batch: NULL handle / uniforms / out_tokens of utterance %d", u);
         for (int v = 0; v < u; ++v) WN_CHECK_ARG(handles[v] != handles[u], "wn_decoder_run_batch: handle %d given twice", u);
-        WN_CHECK_SHAPE(D->fastP && D->three_wgs, "wn_decoder_run_batch: needs the specialised decoder (config 4's shape) "
-                                                 "without WN_DECODER_ONE_WORKGROUP");
-        WN_CHECK_SHAPE(D->meta.nlayers == D0->meta.nlayers && D->meta.head_act == D0->meta.head_act && D->meta.Q == D0->meta.Q &&
-                           D->meta.Cr == D0->meta.Cr && D->meta.Cs == D0->meta.Cs && D->meta.fw == D0->meta.fw &&
+        WN_CHECK_SHAPE(!D->fastP || D->three_wgs, "wn_decoder_run_batch: utterance %d's decoder was created with WN_DECODER_ONE_WORKGROUP: "
+                                                  "the one-workgroup specialised kernel has no batched form", u);
+        WN_CHECK_SHAPE(!D->fastP == any, "wn_decoder_run_batch: utterance %d is %s decoder, utterance 0 is not: one launch takes one form", u,
+                       D->fastP ? "a nine-workgroup (config 4's shape)" : "an any-shape");
+        const DecMeta &A = D->meta, &B = D0->meta;
+        WN_CHECK_SHAPE(A.nlayers == B.nlayers && A.head_act == B.head_act && A.Q == B.Q && A.Cr == B.Cr && A.Cs == B.Cs && A.fw == B.fw &&
+                           A.fwc == B.fwc && A.ncausal == B.ncausal && A.nhead == B.nhead && A.maxc == B.maxc &&
                            D->layers.size() == D0->layers.size(),
-                       "wn_decoder_run_batch: the utterances' models differ (layers, channels, Q or head activation)");
+                       "wn_decoder_run_batch: utterance %d's model differs from utterance 0's (layers, channels, filter widths, Q or head "
+                       "activation)", u);
         for (size_t l = 0; l < D->layers.size(); ++l)
             WN_CHECK_SHAPE(D->layers[l].d == D0->layers[l].d && D->layers[l].cd == D0->layers[l].cd,
                            "wn_decoder_run_batch: layer %d of utterance %d has another dilation / width than utterance 0's", (int)l, u);
+        for (size_t i = 0; i < D->causal.size(); ++i)
+            WN_CHECK_SHAPE(D->causal[i].cin == D0->causal[i].cin && D->causal[i].cout == D0->causal[i].cout,
+                           "wn_decoder_run_batch: causal layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
+        for (size_t i = 0; i < D->heads.size(); ++i)
+            WN_CHECK_SHAPE(D->heads[i].cin == D0->heads[i].cin && D->heads[i].cout == D0->heads[i].cout,
+                           "wn_decoder_run_batch: head layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
         // same_weights = 1 reads ONE copy of the packed weights (handle 0's) for every utterance: only sound when every
-        // handle was packed from the same model -- the same weight pointers at its last create / update_weights
+        // handle was packed from the same model -- the same weight pointers at its last create / update_weights.  (The
+        // any-shape form checks the claim and then reads each utterance's own copy all the same.)
         WN_CHECK_ARG(!same_weights || D->src_key == D0->src_key,
                      "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
-        utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
+        if (!any)
+            utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
     }
+    if (any) return run_batch_any(handles, n_handles, first_tokens, uniforms, n, out_tokens, prob_traces, as_stream(stream));
     WN_CHECK_SHAPE(decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,

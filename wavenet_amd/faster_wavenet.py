@@ -263,17 +263,65 @@ class FasterWaveNet(WaveNet):
         return (out, probs) if return_probs else out
 
     # -- N utterances at once (new capability: the reference generates one utterance per process) ------------------------
+    def _nine_workgroup_shape(self, flags) -> bool:
+        """Whether ``wn_decoder_create`` gives this model the specialised decoder (csrc/decoder.hip ``fast_shape``: BASELINE
+        config 4's shape with the reference's default biases).  Only a forecast -- it picks the batch limit and the
+        ``n_samples == 2`` rule before any work; the library decides, and refuses a launch it does not take."""
+        p = self.params
+        L = self._flat_layers
+        return (not (flags & _lib.WN_EXEC_FORCE_GENERIC) and p.quantization_steps == 256 and
+                len(p.causal_conv_channels) == 1 and p.causal_conv_filter_width == 2 and p.residual_conv_filter_width == 2 and
+                self._Cr == 32 and self._Cs == 256 and list(p.softmax_conv_channels) == [256, 256] and len(L) <= 128 and
+                all(int(c) == 32 for c in p.residual_conv_channels) and self.causal_conv_layers[0].bshape is None and
+                all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)))
+
+    def _batch_prompts(self, initial_tokens, N):
+        """``generate_batch``'s ``initial_tokens`` -> (the distinct windows, 1-D int32 each; the window index of every
+        utterance).  Raises on anything but None, one 1-D window or an (N, W) integer array."""
+        Q = self.params.quantization_steps
+        if initial_tokens is None:
+            return [np.full((self.input_width,), 127 if Q > 127 else Q // 2, dtype=np.int32)], [0] * N    # generate.py:21
+        try:
+            a = np.asarray(initial_tokens)
+        except ValueError:
+            a = None                                                   # a ragged list
+        if a is None or a.dtype == object or a.ndim not in (1, 2) or a.size == 0:
+            raise Exception("generate_batch: initial_tokens must be None, one 1-D window, or an (N, W) integer array")
+        if a.ndim == 2 and a.dtype.kind not in "iu":
+            raise Exception("generate_batch: an (N, W) initial_tokens must hold integer tokens, got %s" % a.dtype)
+        if a.ndim == 2 and a.shape[0] != N:
+            raise Exception("generate_batch: initial_tokens has %d rows for %d utterances" % (a.shape[0], N))
+        a = np.ascontiguousarray(a.astype(np.int32))
+        if int(a.min()) < 0 or int(a.max()) >= Q:
+            raise Exception("generate_batch: initial_tokens outside [0, %d)" % Q)
+        if a.ndim == 1:
+            return [a], [0] * N
+        seen, prompts, which = {}, [], []
+        for row in a:                                                  # equal rows share one prefill
+            k = row.tobytes()
+            if k not in seen:
+                seen[k] = len(prompts)
+                prompts.append(row)
+            which.append(seen[k])
+        return prompts, which
+
     def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0):
-        """``uniforms``: (N, n_samples) float64 -- N independent utterances from the same initial window, utterance u drawing
-        with ``uniforms[u]``; returns (N, n_samples) int32 tokens on the device.  A single utterance is a strict
-        sample-to-sample chain (generate.py:9-60, batch 1: wavenet.py:286,290,354) and occupies nine of the GPU's CUs; the
-        batched launch (``wn_decoder_run_batch``) runs up to ``wn_decoder_batch_max()`` = 28 such chains side by side, each with
-        a decoder state of its own.  Row u equals ``generate(n_samples, uniforms[u])`` bit for bit.  Step 1 -- the full forward
-        over the initial window -- is the same for every utterance and runs once.  ``temperature`` / ``top_k`` / ``top_p``:
-        as for ``generate``, each a scalar or one value per utterance (row u then equals ``generate`` with utterance u's)."""
+        """``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
+        (N, n_samples) int32 tokens on the device.  ``initial_tokens``: None (silence), one 1-D window for every utterance, or
+        an (N, W) integer array -- a prompt per utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a
+        scalar or one value per utterance.  Row u equals ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's
+        window>, <utterance u's controls>)`` bit for bit.
+
+        A single utterance is a strict sample-to-sample chain (generate.py:9-60, batch 1: wavenet.py:286,290,354); the
+        batched launch (``wn_decoder_run_batch``) runs such chains side by side, each with a decoder state of its own: nine
+        workgroups per utterance and up to ``wn_decoder_batch_max()`` = 28 utterances per launch for config 4's shape, one
+        workgroup per utterance and up to ``WN_DECODER_BATCH_MAX_ANY`` for every other model (any channels, filter widths,
+        causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``).  More utterances run as several launches, one after
+        another.  Step 1 -- the full forward over the window, at batch 1 exactly as ``generate`` runs it -- runs once per
+        DISTINCT window.  What still runs as a loop over ``generate()``, decided before any work: ``WN_DECODER_ONE_WORKGROUP``,
+        ``n_samples == 2`` on the nine-workgroup form, and a device the nine-workgroup launch does not fit."""
         p = self.params
         Q = p.quantization_steps
-        iw = self.input_width
         u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
         if u_np.ndim != 2 or u_np.shape[1] < n_samples:
             raise Exception("uniforms must be (N, >= n_samples)")
@@ -286,81 +334,89 @@ class FasterWaveNet(WaveNet):
             sampling.check_controls(temps[i], top_ks[i], top_ps[i])
         if n_samples < 1:
             raise Exception("generate_batch: n_samples must be positive")
-        # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
-        # decided BEFORE any work is done: n_samples == 2 (the launch runs two steps or more), more utterances than
-        # wn_decoder_batch_max(), a model the specialised decoder does not take, or WN_DECODER_ONE_WORKGROUP
-        flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
-        batched = (1 <= N <= lib.wn_decoder_batch_max() and n_samples != 2 and self.storage != "bf16" and
-                   not (flags & (_lib.WN_DECODER_ONE_WORKGROUP | _lib.WN_EXEC_FORCE_GENERIC)))
         if N < 1:
             raise Exception("generate_batch: no utterance")
-        if not batched:
-            return self._generate_batch_loop(n_samples, u_np, initial_tokens, temps, top_ks, top_ps)
-        if initial_tokens is None:
-            initial_tokens = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)   # generate.py:21
-        tok = torch.as_tensor(np.asarray(initial_tokens, dtype=np.int32).reshape(1, -1)).to(self.device)
+        prompts, which = self._batch_prompts(initial_tokens, N)
+        # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
+        # decided BEFORE any work is done
+        flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        nine = self._nine_workgroup_shape(flags)
+        if nine and (n_samples == 2 or flags & _lib.WN_DECODER_ONE_WORKGROUP):
+            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps)
+        limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
         u = torch.as_tensor(u_np).to(self.device)
-        # one prefill, N decoder states seeded from it
-        self.prev_causal_outputs = None
-        storage, self.storage = self.storage, "fp32"
-        try:
-            with torch.no_grad():
-                causal_output = self.forward_causal_block(tok)
-                _, sum_skip = self.forward_residual_block(causal_output)
-                p0 = self.forward_softmax_block(sum_skip, apply_softmax=True)
-        finally:
-            self.storage = storage
-        tokens = tok.to(torch.int32).contiguous()
-        while len(self._batch_decs) < N:
+        run = n_samples > 1
+        while run and len(self._batch_decs) < N:
             d, keep = self._desc()
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
             self._batch_decs.append(h)
             self._batch_stale.append(False)
-        for i in range(N):
+        for i in range(N if run else 0):
             if self._batch_stale[i]:
                 d, keep = self._desc()
                 check(lib.wn_decoder_update_weights(self._batch_decs[i], C.byref(d), stream_ptr()), "wn_decoder_update_weights")
                 self._batch_stale[i] = False
-            check(lib.wn_decoder_load_state(
-                self._batch_decs[i], ptr(tokens), tokens.shape[1], ptr_array([t.contiguous() for t in self._last_causal_outputs]),
-                ptr_array(self._last_layer_inputs), stream_ptr()), "wn_decoder_load_state")
             check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
+        # one prefill per distinct window, at batch 1 as generate() runs it; the decoder states of its utterances are seeded
+        # from it, and its first row (one per distinct temperature) is what generate() draws the first token from
+        self.prev_causal_outputs = None
+        rows = {}
+        for k, prompt in enumerate(prompts):
+            tok = torch.as_tensor(prompt.reshape(1, -1)).to(self.device)
+            storage, self.storage = self.storage, "fp32"
+            try:
+                with torch.no_grad():
+                    causal_output = self.forward_causal_block(tok)
+                    _, sum_skip = self.forward_residual_block(causal_output)
+                    p0 = self.forward_softmax_block(sum_skip, apply_softmax=True)
+            finally:
+                self.storage = storage
+            tokens = tok.to(torch.int32).contiguous()
+            mine = [i for i in range(N) if which[i] == k]
+            if run:
+                causal_outs = ptr_array([t.contiguous() for t in self._last_causal_outputs])
+                layer_ins = ptr_array(self._last_layer_inputs)
+                for i in mine:
+                    check(lib.wn_decoder_load_state(self._batch_decs[i], ptr(tokens), tokens.shape[1], causal_outs, layer_ins,
+                                                    stream_ptr()), "wn_decoder_load_state")
+            for t in sorted({temps[i] for i in mine}):
+                rows[(k, t)] = self._first_row(sum_skip, p0, t)
         out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
         first = torch.empty((N,), device=self.device, dtype=torch.int32)
         u0 = u[:, 0].contiguous()
         if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
-            first_prob = p0[0, :, 0, -1].contiguous().view(1, Q).expand(N, Q).contiguous()
+            first_prob = torch.cat([rows[(which[i], temps[i])] for i in range(N)], dim=0).contiguous()
             check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
         else:
-            # the first draw per utterance, as generate() makes it: a row per distinct temperature, the truncation per utterance
-            rows = {}
-            for i in range(N):
-                if temps[i] not in rows:
-                    rows[temps[i]] = self._first_row(sum_skip, p0, temps[i])
-                check(lib.wn_sample_categorical_filtered(ptr(rows[temps[i]]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1, Q,
-                                                         top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
+            for i in range(N):                                       # the truncation per utterance, as generate() draws
+                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
+                                                         Q, top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
         out[:, 0] = first
-        if n_samples > 1:
-            firsts = (C.c_int32 * N)(*[int(v) for v in first.cpu().tolist()])
-            handles = (C.c_void_p * N)(*[h.value for h in self._batch_decs[:N]])
+        if run:
+            firsts = [int(v) for v in first.cpu().tolist()]
             rest = [u[i, 1:].contiguous() for i in range(N)]
-            outs = [torch.empty((n_samples - 1,), device=self.device, dtype=torch.int32) for _ in range(N)]
+            # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
+            outs = [torch.empty((n_samples - 1,), device=self.device, dtype=torch.int32) if nine else out[i, 1:] for i in range(N)]
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
-            rc = lib.wn_decoder_run_batch(handles, N, firsts, ptr_array(rest), n_samples - 1, ptr_array(outs), None, same,
-                                          stream_ptr())
-            if rc == _lib.WN_ESHAPE:         # a shape the batched launch does not take (e.g. not config 4's): one by one
-                return self._generate_batch_loop(n_samples, u_np, initial_tokens, temps, top_ks, top_ps)
-            check(rc, "wn_decoder_run_batch")
-            for i in range(N):
+            for c0 in range(0, N, limit):                             # launches of at most `limit`, one after another
+                c1 = min(N, c0 + limit)
+                rc = lib.wn_decoder_run_batch((C.c_void_p * (c1 - c0))(*[h.value for h in self._batch_decs[c0:c1]]), c1 - c0,
+                                              (C.c_int32 * (c1 - c0))(*firsts[c0:c1]), ptr_array(rest[c0:c1]), n_samples - 1,
+                                              ptr_array(outs[c0:c1]), None, same, stream_ptr())
+                if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
+                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps)
+                check(rc, "wn_decoder_run_batch")
+            for i in range(N if nine else 1):                         # any-shape: nothing can give up; one synchronise
                 check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
-                out[i, 1:] = outs[i]
+            if nine:
+                for i in range(N):
+                    out[i, 1:] = outs[i]
         return out
 
-    def _generate_batch_loop(self, n_samples, u_np, initial_tokens, temperature=1.0, top_k=0, top_p=1.0):
+    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
-        ``generate(n_samples, uniforms[u])`` with utterance u's controls by definition)."""
-        N = u_np.shape[0]
-        t, k, pp = (sampling.per_utterance(v, N, n) for v, n in ((temperature, "temperature"), (top_k, "top_k"), (top_p, "top_p")))
-        return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=initial_tokens, temperature=t[i], top_k=k[i],
-                                          top_p=pp[i]) for i in range(N)])
+        ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls by
+        definition)."""
+        return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=prompts[which[i]], temperature=temperature[i],
+                                          top_k=top_k[i], top_p=top_p[i]) for i in range(u_np.shape[0])])

@@ -28,17 +28,44 @@ _SAMPLING_FLAGS = (
     (("--top-k",), int, 0, "draw from the k most probable values only (0 = off)"),
     (("--top-p",), float, 1.0, "draw from the smallest set of most probable values holding this share of the mass (1 = off)"),
 )
+# batched generation (FasterWaveNet.generate_batch; the reference writes one utterance from silence): both off
+_BATCH_FLAGS = (
+    (("--utterances",), int, None, "write this many utterances, generated_000.wav ... (with --fast: one batched run)"),
+)
+_PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation instead of silence; repeatable: one file for "
+                "all utterances, or one per utterance")
 
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__)
-    for flags, typ, default, text in _REFERENCE_FLAGS + _LOOP_FLAGS + _SAMPLING_FLAGS:
+    for flags, typ, default, text in _REFERENCE_FLAGS + _LOOP_FLAGS + _SAMPLING_FLAGS + _BATCH_FLAGS:
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
+    ap.add_argument("--prompt", action="append", default=None, metavar="FILE.wav", help=_PROMPT_HELP)
     return ap
 
 
+def utterance_prompts(args):
+    """(number of utterances, prompt file of each utterance or None for silence) of a parsed command line, or (None, None)
+    when neither --utterances nor --prompt was given: the reference's single ``generated.wav`` from silence."""
+    if args.utterances is None and not args.prompt:
+        return None, None
+    files = list(args.prompt or [])
+    n = args.utterances if args.utterances is not None else max(1, len(files))
+    if n < 1:
+        raise ValueError("--utterances must be at least 1, got %d" % n)
+    if len(files) not in (0, 1, n):
+        raise ValueError("%d --prompt files for %d utterances: give one for all of them, or one each" % (len(files), n))
+    return n, (files * n if len(files) == 1 else files or [None] * n)
+
+
 def parse(argv=None):
-    return build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    try:
+        utterance_prompts(args)
+    except ValueError as e:
+        ap.error(str(e))
+    return args

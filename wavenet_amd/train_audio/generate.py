@@ -1,5 +1,8 @@
 """Generation driver (train_audio/generate.py:9-63): start from ``input_width`` samples of silence (token 127), draw
-``int(sampling_rate * seconds) - 1`` samples one at a time from the softmax, write ``<output_dir>/generated.wav``."""
+``int(sampling_rate * seconds) - 1`` samples one at a time from the softmax, write ``<output_dir>/generated.wav``.
+
+Beyond the reference: ``--utterances N`` and ``--prompt FILE.wav`` write ``generated_000.wav`` ... ``generated_{N-1:03d}.wav``,
+each continuing its prompt (or silence); with ``--fast`` all of them in one ``FasterWaveNet.generate_batch`` run."""
 from __future__ import annotations
 
 import os
@@ -15,42 +18,49 @@ from . import model as _model
 from .train import input_width_of
 
 
+def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, top_p):
+    """The reference's loop (generate.py:24-43) from the given window: one ``forward_one_step`` over the last
+    ``input_width`` tokens and one draw per sample, on the host; returns the ``n`` emitted tokens."""
+    Q = net.params.quantization_steps
+    controls = not sampling.controls_off(temperature, top_k, top_p, Q)
+    iw = len(window)
+    buf = np.array(window, dtype=np.int32)
+    for time_step in range(1, n + 1):
+        x = torch.as_tensor(buf[-iw:].reshape(1, -1)).to(net.device)
+        if not controls:
+            with torch.no_grad():
+                softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True)[0, :, 0, -1]
+            buf = np.append(buf, np.random.choice(np.arange(Q), p=softmax))
+        else:
+            # the same rule the device applies under --fast, on the host: logits / temperature, softmax, truncation, and
+            # choice()'s draw from its one uniform
+            with torch.no_grad():
+                logits = net.forward_one_step(x, apply_softmax=False, as_numpy=True)[0, :, 0, -1]
+            softmax = sampling.apply_temperature(logits, temperature)
+            buf = np.append(buf, sampling.sample(softmax, np.random.random_sample(), top_k, top_p))
+        if time_step % 10 == 0:
+            sys.stdout.write("\rgenerating {:.2f} msec / {:.2f} msec".format(
+                time_step * 1000.0 / sampling_rate, generate_sec * 1000.0))
+            sys.stdout.flush()
+    return buf[iw:]
+
+
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
                    temperature=1.0, top_k=0, top_p=1.0):
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
-    controls = not sampling.controls_off(temperature, top_k, top_p, Q)
     iw = input_width_of(params)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
-    silence = 127 if Q > 127 else Q // 2
+    silence = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)
     start_time = time.time()
     if n <= 0:
         tokens = np.zeros((0,), np.int32)
     elif fast:
         # one uniform per sample, the draw numpy's choice() makes (generate.py:40); the whole loop runs on the device
         u = np.random.random_sample(n)
-        tokens = net.generate(n, u, initial_tokens=np.full((iw,), silence, np.int32), temperature=temperature, top_k=top_k,
-                              top_p=top_p).cpu().numpy()
+        tokens = net.generate(n, u, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p).cpu().numpy()
     else:
-        buf = np.full((iw,), silence, dtype=np.int32)
-        for time_step in range(1, n + 1):
-            x = torch.as_tensor(buf[-iw:].reshape(1, -1)).to(net.device)
-            if not controls:
-                with torch.no_grad():
-                    softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True)[0, :, 0, -1]
-                buf = np.append(buf, np.random.choice(np.arange(Q), p=softmax))
-            else:
-                # the same rule the device applies under --fast, on the host: logits / temperature, softmax, truncation, and
-                # choice()'s draw from its one uniform
-                with torch.no_grad():
-                    logits = net.forward_one_step(x, apply_softmax=False, as_numpy=True)[0, :, 0, -1]
-                softmax = sampling.apply_temperature(logits, temperature)
-                buf = np.append(buf, sampling.sample(softmax, np.random.random_sample(), top_k, top_p))
-            if time_step % 10 == 0:
-                sys.stdout.write("\rgenerating {:.2f} msec / {:.2f} msec".format(
-                    time_step * 1000.0 / sampling_rate, generate_sec * 1000.0))
-                sys.stdout.flush()
-        tokens = buf[iw:]
+        tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p)
     print("\ndone in {:.3f} sec".format(time.time() - start_time))
     os.makedirs(output_dir, exist_ok=True)
     filename = "{}/generated.wav".format(output_dir)
@@ -58,10 +68,55 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
     return filename, tokens
 
 
+def read_prompt(path, params):
+    """The window a generation continues from: the file's tokens as training reads them (``data.load_audio_file``: mu-law,
+    silence trimmed), their last ``input_width``, left-padded with the silence token when the file is shorter."""
+    Q = params.quantization_steps
+    iw = input_width_of(params)
+    tokens, _ = data.load_audio_file(path, quantization_steps=Q)
+    tokens = np.asarray(tokens, dtype=np.int32)[-iw:]
+    silence = 127 if Q > 127 else Q // 2
+    return np.concatenate([np.full((iw - tokens.size,), silence, dtype=np.int32), tokens])
+
+
+def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
+                        temperature=1.0, top_k=0, top_p=1.0):
+    """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
+    ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance."""
+    Q = params.quantization_steps
+    sampling.check_controls(temperature, top_k, top_p)
+    iw = input_width_of(params)
+    N = len(prompt_files)
+    n = int(sampling_rate * generate_sec) - 1
+    silence = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)
+    read = {f: read_prompt(f, params) for f in set(prompt_files) if f is not None}
+    prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
+    start_time = time.time()
+    if n <= 0:
+        tokens = np.zeros((N, 0), np.int32)
+    elif fast:
+        u = np.random.random_sample((N, n))
+        tokens = net.generate_batch(n, u, initial_tokens=prompts, temperature=temperature, top_k=top_k, top_p=top_p).cpu().numpy()
+    else:
+        tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p) for i in range(N)])
+    print("\ndone in {:.3f} sec".format(time.time() - start_time))
+    os.makedirs(output_dir, exist_ok=True)
+    filenames = []
+    for i in range(N):
+        filenames.append("{}/generated_{:03d}.wav".format(output_dir, i))
+        data.save_audio_file(filenames[-1], tokens[i], Q, format="16bit_pcm", sampling_rate=sampling_rate)
+    return filenames, tokens
+
+
 def main(argv=None):
     args = _args.parse(argv)
+    n_utt, prompt_files = _args.utterance_prompts(args)
     params, net = _model.build(args)
     np.random.seed(args.seed)
+    if n_utt is not None:
+        return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
+                                   fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
+                                   top_p=args.top_p)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
 
