@@ -75,9 +75,10 @@ const char* wn_last_error(void);
  * ws / ws_bytes: device scratch, at least wn_exec_workspace_bytes() for the model and batch; its contents are dead when the
  * call's kernels have run, so ONE buffer per stream serves every call on that stream (never one buffer for two streams).
  * flags (ABI 3; the library reads NO environment variable and keeps no switch of its own -- what used to be
- * WAVENET_HIP_FORCE_GENERIC / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here; bits 2 and 32 are unassigned):
+ * WAVENET_HIP_FORCE_GENERIC / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here; bit 2 is unassigned):
  *   WN_EXEC_FORCE_GENERIC   every kernel of the call from the any-shape correctness path (generic_kernels.hip), fp32
  *   WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM, WN_EXEC_NO_MULTI_LAYER_BWD   see the defines
+ *   WN_EXEC_HEAD_ROW_NLL    wn_head_xent only: per-row negative log-likelihoods instead of the gradient (see there)
  * fwd_t1_min_blocks: launch size (workgroups of four 32-column tiles) from which the fused 32-channel layer forward takes its
  * one-tile-per-wave form; 0 = the library's default (512: every CU gets two to four workgroups), n > 0 = n (1 = always:
  * parity tests of that kernel at small sizes), < 0 = never.
@@ -96,6 +97,9 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                           (V, U) rotate through three buffer pairs, the deal of tiles to waves rotates from
                                           layer to layer.  Results agree with the per-layer launches to fp32 summation order
                                           (which wave sums which tiles; ~1e-7) and are bit-reproducible from run to run */
+#define WN_EXEC_HEAD_ROW_NLL 32u /* wn_head_xent: the scoring form -- its sixth argument receives N floats, one negative
+                                    log-likelihood per row, and no gradient is formed or stored.  Every other entry point
+                                    ignores the bit */
 typedef struct WnExec {
     int precision;
     unsigned flags;
@@ -236,7 +240,12 @@ int wn_softmax_xent(const float* logits, const int32_t* target, float* loss, flo
  * and N <= 253,952 rows -- one 128-row workgroup per partial-sum slot of `loss` -- (wn_head_xent_supported, which takes N since
  * ABI 5; WN_ESHAPE otherwise: run wn_pointwise_fwd + wn_softmax_xent, which has no row limit).  The input has no known range: every
  * 32-channel chunk of a wave's 32 columns is scaled by the power of two that fits the wave's own maximum before the fp16 split
- * (error <= 2^-21 per product as elsewhere under FP16X2).  Backward: wn_pointwise_bwd(x, W, dlogits, ...) as after the two calls. */
+ * (error <= 2^-21 per product as elsewhere under FP16X2).  Backward: wn_pointwise_bwd(x, W, dlogits, ...) as after the two calls.
+ * Scoring form (ex->flags & WN_EXEC_HEAD_ROW_NLL; same coverage, same WN_ESHAPE before any device work): the sixth argument
+ * points at N floats and receives row_nll[n] = m + log sum exp(l - m) - l[target[n]] (m = the row's largest logit; what
+ * wn_softmax_xent sums), NOT divided by n_norm, and exactly 0.0f for a row whose target lies outside [0, Cout).  No gradient is
+ * formed or stored and nothing beyond those N floats is written; loss is filled as in the training form (loss[0] = the mean
+ * over the rows that count, n_norm with its three meanings), so a caller can check the rows against the mean. */
 int wn_head_xent_supported(int64_t N, int Cin, int Cout, const WnExec* ex);
 int wn_head_xent(const float* x, const float* W, const float* bias, const int32_t* target, float* loss, float* dlogits,
                  int N, int Cin, int Cout, int act, int64_t n_norm, const WnExec* ex, void* stream);

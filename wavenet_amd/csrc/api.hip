@@ -296,7 +296,11 @@ int wn_head_xent(const float* x, const float* W, const float* bias, const int32_
                  int N, int Cin, int Cout, int act, int64_t n_norm, const WnExec* ex, void* stream) {
     if (int rc = check_precision(__func__, ex)) return rc;
     wn::ProfScope prof__("wn_head_xent", stream);
-    NN(x); NN(W); NN(target); NN(loss); NN(dlogits); POS(N); POS(Cin); POS(Cout);
+    NN(x); NN(W); NN(target); NN(loss);
+    // WN_EXEC_HEAD_ROW_NLL: the sixth argument is the N-float row result, not the (N, Cout) gradient
+    WN_CHECK_ARG(dlogits != nullptr, "%s: %s is NULL", __func__,
+                 ex && (ex->flags & WN_EXEC_HEAD_ROW_NLL) ? "row_nll (WN_EXEC_HEAD_ROW_NLL: the N row values)" : "dlogits");
+    POS(N); POS(Cin); POS(Cout);
     WN_CHECK_ARG(act >= WN_ACT_NONE && act <= WN_ACT_ELU, "wn_head_xent: bad act %d", act);
     Call c(ex);
     WN_CHECK_SHAPE(head_xent_supported(c, N, Cin, Cout), "wn_head_xent: needs WN_GEMM_FP16X2, 256 outputs, a multiple of 32 "

@@ -283,7 +283,8 @@ int mfma_pointwise_fwd(Call& c, const float* x, const float* W, const float* bia
 
 // The last head convolution and the loss in one launch (fp16 split, 256 outputs): dlogits = d loss / d (W act(x) + b), the
 // workgroups' loss sums in loss[kXentPart ..] (the caller finalises).  WN_ESHAPE when the shape or the arithmetic mode is not
-// covered: the caller then runs the convolution and the loss as two calls.
+// covered: the caller then runs the convolution and the loss as two calls.  Under WN_EXEC_HEAD_ROW_NLL `dlogits` is the N-float
+// row result instead (launch_colgemm_b3 reads the flag from the call).
 int mfma_head_xent(Call& c, const float* x, const float* W, const float* bias, const int32_t* target, float* loss, float* dlogits,
                    long long N, int Cin, int Cout, int act, long long n_norm, int ncnt, hipStream_t s) {
     if (Cout != 256 || Cin % 32 || N >= (1ll << 30) || !c.fp16x2()) return WN_ESHAPE;

@@ -98,7 +98,9 @@ __device__ __forceinline__ float act_apply_t(float x) {
 // MT = 8 (one-term mode only: 128 accumulator registers, 16 KB of LDS per buffer) halves the number of times X is
 // re-read when there are 8 or more m-tiles (skip sum, dz, the gate-mode layer GEMM).
 // TM: terms of a product -- 6 (bf16 x 3), 1 (bf16), 3 (fp16 x 2: modes 0 and 2 only)
-template <int MODE, int ACT, int TM, int MT>
+// ROWNLL (mode 6 only, WN_EXEC_HEAD_ROW_NLL): the scoring form of head + loss -- out[0] receives one loss value per column (N
+// floats) and no gradient is formed
+template <int MODE, int ACT, int TM, int MT, bool ROWNLL = false>
 __global__ __launch_bounds__(256, MT == 8 ? 2 : 3) void k_colgemm_b3(CGArgs a, const __bf16* __restrict__ img, int mtiles,
                                                                      int nchunks, int chunks_per_src,
                                                                      const __bf16* __restrict__ img2) {
@@ -113,6 +115,7 @@ __global__ __launch_bounds__(256, MT == 8 ? 2 : 3) void k_colgemm_b3(CGArgs a, c
     // maximum (as the fused layer kernels do), so no range pass and no overflow fallback exist; a chunk's products leave the matrix
     // core in their own scale and join the fp32 logits with one fma per element.
     constexpr bool XENT = MODE == 6;
+    static_assert(!ROWNLL || XENT, "per-row losses: head + loss mode only");
     constexpr int TB = ONE ? kTileBytes / 3 : (H2 ? kTileBytes * 2 / 3 : kTileBytes);   // bytes of one tile image
     __shared__ __attribute__((aligned(16))) char lds[2 * MT * TB];              // double-buffered tile images
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -428,7 +431,8 @@ __global__ __launch_bounds__(256, MT == 8 ? 2 : 3) void k_colgemm_b3(CGArgs a, c
         // ---- head + loss: acc[mt][r] (+ bias) = logit 32 mt + b3_ch(r, h) of column j; lanes j and j + 32 hold 128 logits each.
         // Softmax cross-entropy against the column's label as k_softmax_xent computes it (loss row = m + log sum exp(l - m) - l_t;
         // a label outside [0, 256) -- Chainer's ignore label -1 -- gives no loss and a zero gradient); the logits themselves
-        // never reach memory: out[0] receives d loss / d logits = (softmax - onehot) / (rows that count).
+        // never reach memory: out[0] receives d loss / d logits = (softmax - onehot) / (rows that count) -- or, ROWNLL, nothing but
+        // the columns' own loss rows (N floats, not divided by the count, 0 for a label that does not count).
         const float* bb = a.bias[0];
         if (bb) {
 #pragma unroll
@@ -457,34 +461,40 @@ __global__ __launch_bounds__(256, MT == 8 ? 2 : 3) void k_colgemm_b3(CGArgs a, c
                 ssum += acc[mt][r];
             }
         ssum += __shfl_xor(ssum, 32);
-        // the rows that count: given by the host, or counted on the device from the labels (k_xent_count's integer partials)
-        float cnt;
-        if (a.xent_n_norm < 0) {
-            int cn = lane < a.xent_ncnt ? reinterpret_cast<const int*>(a.xent_loss + kXentPart + kXentBlocks)[lane] : 0;
-            for (int o = 32; o >= 1; o >>= 1) cn += __shfl_xor(cn, o);
-            cnt = (float)(cn > 0 ? cn : 1);
-        } else {
-            cnt = (float)a.xent_n_norm;
-        }
-        const float invN = 1.f / cnt;
-        const float sc = counts ? invN / ssum : 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            float4 t[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float d4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * q + e;
-                    d4[e] = acc[mt][r] * sc - ((counts && mt * 32 + b3_ch(r, h) == tg) ? invN : 0.f);
-                }
-                t[q] = make_float4(d4[0], d4[1], d4[2], d4[3]);
+        if constexpr (!ROWNLL) {
+            // the rows that count: given by the host, or counted on the device from the labels (k_xent_count's integer partials)
+            float cnt;
+            if (a.xent_n_norm < 0) {
+                int cn = lane < a.xent_ncnt ? reinterpret_cast<const int*>(a.xent_loss + kXentPart + kXentBlocks)[lane] : 0;
+                for (int o = 32; o >= 1; o >>= 1) cn += __shfl_xor(cn, o);
+                cnt = (float)(cn > 0 ? cn : 1);
+            } else {
+                cnt = (float)a.xent_n_norm;
             }
-            tile_store_rows(patch, lane, t, a.out[0], a.ldo, mt * 32, rm);
+            const float invN = 1.f / cnt;
+            const float sc = counts ? invN / ssum : 0.f;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                float4 t[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float d4[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 4 * q + e;
+                        d4[e] = acc[mt][r] * sc - ((counts && mt * 32 + b3_ch(r, h) == tg) ? invN : 0.f);
+                    }
+                    t[q] = make_float4(d4[0], d4[1], d4[2], d4[3]);
+                }
+                tile_store_rows(patch, lane, t, a.out[0], a.ldo, mt * 32, rm);
+            }
         }
         // this workgroup's loss sum: columns in lane order (lanes 0..31 carry a column each), waves in order -- a fixed tree
         float rl = (counts && h == 0) ? m + __logf(ssum) - lt : 0.f;
+        if constexpr (ROWNLL) {
+            // lanes 0..31 hold the 32 consecutive columns of this wave: one 128-byte store, valid columns only
+            if (h == 0 && nvalid) a.out[0][no] = rl;
+        }
         for (int o = 32; o >= 1; o >>= 1) rl += __shfl_xor(rl, o);
         __syncthreads();                                            // every wave is done with its patch
         float* red = reinterpret_cast<float*>(lds);
@@ -901,11 +911,15 @@ int launch_colgemm_b3(Call& c, CGArgs& a, int mode, int nprob, hipStream_t s) {
     const bool mt8 = (one || h2) && mtiles >= 8;
     dim3 grid(cdiv(a.N, 128) * cdiv(mtiles, mt8 ? 8 : 4));
     if (mode == 6) {
-#define X_LAUNCH(ACT_) hipLaunchKernelGGL((k_colgemm_b3<6, ACT_, 3, 8>), grid, dim3(256), 0, s, a, (const __bf16*)img, mtiles,   \
-                                          nchunks, cps, (const __bf16*)nullptr)
-        if (a.act == WN_ACT_RELU) X_LAUNCH(WN_ACT_RELU);
-        else if (a.act == WN_ACT_ELU) X_LAUNCH(WN_ACT_ELU);
-        else X_LAUNCH(WN_ACT_NONE);
+#define X_LAUNCH(ACT_, ROWS_) hipLaunchKernelGGL((k_colgemm_b3<6, ACT_, 3, 8, ROWS_>), grid, dim3(256), 0, s, a, (const __bf16*)img, \
+                                                 mtiles, nchunks, cps, (const __bf16*)nullptr)
+        if (c.flag(WN_EXEC_HEAD_ROW_NLL)) {               // the scoring form: a.out[0] is N floats (wn_head_xent)
+            if (a.act == WN_ACT_RELU) X_LAUNCH(WN_ACT_RELU, true);
+            else if (a.act == WN_ACT_ELU) X_LAUNCH(WN_ACT_ELU, true);
+            else X_LAUNCH(WN_ACT_NONE, true);
+        } else if (a.act == WN_ACT_RELU) X_LAUNCH(WN_ACT_RELU, false);
+        else if (a.act == WN_ACT_ELU) X_LAUNCH(WN_ACT_ELU, false);
+        else X_LAUNCH(WN_ACT_NONE, false);
 #undef X_LAUNCH
         WN_LAUNCH_CHECK();
         return WN_OK;

@@ -1,0 +1,68 @@
+"""Evaluation driver (new; the reference has none): the model's negative log-likelihood on every .wav file of a directory,
+teacher-forced, in nats and bits per sample -- the held-out number that tells overfitting from learning.
+
+    python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model [--json scores.json]
+
+Files are read as training reads them (mu-law tokens, silence trimmed) and scored by ``WaveNet.score``.  The command has
+its own parser: it shares ``-g / -w / -m`` with train and generate and takes none of their other flags."""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+
+from .. import data, scoring
+from . import model as _model
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("-g", "--gpu_device", type=int, default=0, help="HIP device index")
+    ap.add_argument("-w", "--wav-dir", type=str, default="wav", help="directory of .wav files to score")
+    ap.add_argument("-m", "--model-dir", type=str, default="model", help="wavenet.json + checkpoints")
+    ap.add_argument("--chunk-width", type=int, default=16384, help="scored samples per piece of a file")
+    ap.add_argument("--batch-size", type=int, default=8, help="pieces per launch")
+    ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
+    return ap
+
+
+def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True):
+    """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
+    "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
+    samples, and prints one line per file and one for the total unless ``verbose`` is off."""
+    files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
+    if not files:
+        raise Exception("no .wav file in {}".format(wav_dir))
+    rows, nats, samples = [], 0.0, 0
+    for fn in files:
+        tokens, _ = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
+        row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size))
+        rows.append(dict(file=fn, **row))
+        nats += row["nats_per_sample"] * row["samples"]
+        samples += row["samples"]
+    mean = nats / samples if samples else 0.0
+    table = {"files": rows, "total": {"samples": samples, "nats_per_sample": mean,
+                                      "bits_per_sample": mean / math.log(2.0)}}
+    if verbose:
+        for r in rows + [dict(file="total", **table["total"])]:
+            sys.stdout.write("{:<32} {:>10d} samples  {:.6f} nats/sample  {:.6f} bits/sample\n".format(
+                r["file"], r["samples"], r["nats_per_sample"], r["bits_per_sample"]))
+        sys.stdout.flush()
+    return table
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    args.fast, args.seed = False, None                       # what train_audio.model.build reads beyond the shared flags
+    params, net = _model.build(args)
+    table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(table, f, indent=2)
+    return table
+
+
+if __name__ == "__main__":
+    main()

@@ -729,11 +729,12 @@ class WaveNet(object):
     def _weights_changed(self):
         self._w16_stale = True
 
-    def _exec(self, B: int = 8, T: int = 0):
+    def _exec(self, B: int = 8, T: int = 0, call_flags: int = 0):
         """WnExec for a library call on the current stream: this model's GEMM precision (``self.gemm_precision``, or the
         module default), its flags, and a scratch buffer owned by (model, stream), sized by ``wn_exec_workspace_bytes``
         for the largest (B, T) seen so far.  Buffers are never freed or moved once handed out -- a captured graph keeps
-        the pointer -- a larger batch or a longer window gets a new, larger one."""
+        the pointer -- a larger batch or a longer window gets a new, larger one.  ``call_flags``: WN_EXEC_* bits of this one
+        call, on top of the model's."""
         lib = _lib.lib()
         key = (stream_ptr() or 0, self._arena.device.index)
         ent = self._scratch.get(key)
@@ -748,7 +749,7 @@ class WaveNet(object):
             ent = (buf, B, T)
             self._scratch[key] = ent
         ex = _lib.WnExec()
-        ex.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        ex.flags = (_lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)) | int(call_flags)
         prec = self.gemm_precision or _lib.get_gemm_precision()
         ex.precision = _lib.GEMM_PRECISIONS.index("fp32" if ex.flags & _lib.WN_EXEC_FORCE_GENERIC else prec)
         ex.ws, ex.ws_bytes = ent[0].data_ptr(), ent[0].numel()
@@ -1094,6 +1095,62 @@ class WaveNet(object):
         if out.shape[1] != tgt.shape[1]:
             raise Exception("raw_network_output.width != target.width")
         return _HeadXentFn.apply(out, lay.W, lay.b, tgt.to(torch.int32).reshape(-1).contiguous(), act, n_norm, self)
+
+    # -- scoring: per-position negative log-likelihoods, no autograd (new capability; wavenet_amd/scoring.py) -------------------
+    def head_token_nll(self, sum_skip, target):
+        """The per-position form of :meth:`head_cross_entropy`: (B, T') float32 on the device, entry (b, t) the negative
+        log-likelihood in nats of ``target[b, t]`` under the head's softmax at that column, and 0 for a label outside
+        [0, Q) (the ignore label -1).  Runs without autograd.  Where ``head_cross_entropy`` would fuse (fp32 storage,
+        ``fuse_head_loss``, ``wn_head_xent_supported``) the last head convolution and the rows are ONE launch,
+        ``wn_head_xent`` under WN_EXEC_HEAD_ROW_NLL: neither logits nor a gradient reach memory.  Everywhere else:
+        ``forward_softmax_block(apply_softmax=False)``, then logsumexp - gather in torch."""
+        with torch.no_grad():
+            x = self.to_variable(sum_skip)
+            _need_gpu(x)
+            tgt = self.to_variable(np.asarray(target) if not isinstance(target, torch.Tensor) else target)
+            if tgt.dim() != 2 or x.shape[0] != tgt.shape[0] or x.shape[3] != tgt.shape[1]:
+                raise Exception("head_token_nll: target must be (B, T') like the skip sum, got %s for %s"
+                                % (tuple(tgt.shape), tuple(x.shape)))
+            B, Tw = int(tgt.shape[0]), int(tgt.shape[1])
+            lay = self.softmax_conv_layers[-1]
+            Q = lay.W.shape[0]
+            fused = (self.storage != "bf16" and self.fuse_head_loss and B * Tw > 0 and
+                     _lib.lib().wn_head_xent_supported(B * Tw, lay.W.shape[1], Q, self._exec()) == 1)
+            if not fused:
+                rows = _to_btc(self.forward_softmax_block(x, apply_softmax=False)).to(torch.float32)      # (B, T', Q)
+                lab = tgt.to(torch.int64)
+                counts = (lab >= 0) & (lab < Q)
+                picked = rows.gather(2, lab.clamp(0, Q - 1).unsqueeze(2)).squeeze(2)
+                return torch.where(counts, torch.logsumexp(rows, dim=2) - picked, torch.zeros_like(picked))
+            act = ACT[self.head_activation]
+            out = _to_btc(x)
+            for l2 in self.softmax_conv_layers[:-1]:
+                out = _PointwiseFn.apply(out, l2.W, l2.b, act, self)
+            x2 = out.reshape(B * Tw, out.shape[-1]).contiguous()
+            buf = torch.empty((_lib.XENT_LOSS_WORDS,), device=x.device, dtype=torch.float32)
+            nll = torch.empty((B, Tw), device=x.device, dtype=torch.float32)
+            # n_norm = 0: the mean in buf[0] runs over all rows (nobody reads it here; no counting launch)
+            check(_lib.lib().wn_head_xent(ptr(x2), ptr(lay.W), ptr(lay.b), ptr(tgt.to(torch.int32).reshape(-1).contiguous()),
+                                          ptr(buf), ptr(nll), B * Tw, x2.shape[1], Q, act, 0,
+                                          self._exec(call_flags=_lib.WN_EXEC_HEAD_ROW_NLL), stream_ptr()), "wn_head_xent")
+            return nll
+
+    def token_nll(self, x, tgt):
+        """The per-position form of ``graph.default_loss``: (B, tgt.shape[1]) float32 negative log-likelihoods of ``tgt``
+        under the last ``tgt.shape[1]`` output columns of the window ``x`` (tokens (B, T) or a one-hot image).  Inference
+        form: nothing is saved for a backward."""
+        with torch.no_grad():
+            c = self.forward_causal_block(x)
+            _, s = self.forward_residual_block(c, t_off=int(c.shape[3]) - int(tgt.shape[1]))
+            return self.head_token_nll(s, tgt)
+
+    def score(self, tokens, chunk_width: int = 16384, batch_size: int = 8):
+        """(n,) float32 on the device: the negative log-likelihood in nats of every sample of the 1-D token sequence
+        ``tokens``, each given all samples before it (silence before the first), teacher-forced.  See
+        :func:`wavenet_amd.scoring.score` for the definition and the two knobs, which do not change the result beyond
+        arithmetic."""
+        from . import scoring
+        return scoring.score(self, tokens, chunk_width=chunk_width, batch_size=batch_size)
 
     # -- the deferred skip projection -----------------------------------------------------------
     def _skip_sum(self, zs: Sequence[torch.Tensor], skip: torch.Tensor, B, T, t_off, Tw):
