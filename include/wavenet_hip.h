@@ -408,9 +408,18 @@ int wn_adam_step_dev(float* param, const float* grad, float* m, float* v, int64_
  *   RMSprop      ms += (1-hyper)(g^2-ms); p -= lr g/(sqrt(ms)+eps)
  *   AdaDelta     msg += (1-hyper)(g^2-msg); dx = sqrt((msdx+eps)/(msg+eps)) g; msdx += (1-hyper)(dx^2-msdx); p -= dx
  * s1 = v / h / ms / msg, s2 = msdx (AdaDelta only, else NULL); hyper = momentum / alpha / rho.  lr_dev != NULL: the
- * learning rate is read from device memory at execution time (graph replay), `lr` is ignored.                       */
+ * learning rate is read from device memory at execution time (graph replay), `lr` is ignored.
+ *
+ * WN_RULE_EMA is no optimiser: it keeps an exponential moving average of the weights, one more elementwise pass over
+ * the flat arena.  param = the average e (read and written), grad = the current weights w (read only), lr (or *lr_dev)
+ * = the rate r = 1 - decay_t:
+ *   e += r (w - e)        in fp32, as fma(r, w, fma(-r, e, e)): two roundings; r == 0 leaves e, r == 1 stores w exactly
+ * s1, s2 (both may be NULL), hyper and eps are ignored.  weight_decay != 0 or grad_mult != 1 is WN_EARG: they are hooks
+ * on a gradient, and w is not one.  A rate passed by value must be finite and lie in [0, 1], else WN_EARG; a rate read
+ * from device memory is taken as it is.  sqnorm != NULL && clip > 0 does ONLY the skip of ABI 4 -- sqrt(*sqnorm) not
+ * finite: nothing is written, so a step the optimiser skipped is a step the average skips -- and never scales w.    */
 enum { WN_RULE_SGD = 0, WN_RULE_MOMENTUM_SGD = 1, WN_RULE_ADAGRAD = 2, WN_RULE_ADADELTA = 3, WN_RULE_NESTEROV = 4,
-       WN_RULE_RMSPROP = 5 };
+       WN_RULE_RMSPROP = 5, WN_RULE_EMA = 6 };
 int wn_rule_step(int rule, float* param, const float* grad, float* s1, float* s2, int64_t n, float lr,
                  const float* lr_dev, float hyper, float eps, float weight_decay, const float* sqnorm, float clip,
                  float grad_mult, void* stream);

@@ -15,6 +15,7 @@ XENT_LOSS_WORDS = 2056      # WN_XENT_LOSS_WORDS: loss[0] + per-workgroup sums o
 SQNORM_WORDS = 1040          # WN_SQNORM_WORDS: out[0] + per-workgroup partial sums of wn_sqnorm
 
 WN_ACT_NONE, WN_ACT_RELU, WN_ACT_ELU = 0, 1, 2
+WN_RULE_EMA = 6             # wn_rule_step: the weight average (rules 0-5 are the optimisers of wavenet.RuleState.RULES)
 ACT = {"none": WN_ACT_NONE, None: WN_ACT_NONE, "relu": WN_ACT_RELU, "elu": WN_ACT_ELU}
 
 _p = C.c_void_p

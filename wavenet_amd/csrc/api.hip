@@ -398,8 +398,15 @@ int wn_rule_step(int rule, float* param, const float* grad, float* s1, float* s2
     wn::ProfScope prof__("wn_adam_step", stream);
     NN(param); NN(grad);
     WN_CHECK_ARG(n > 0, "wn_rule_step: n <= 0");
-    WN_CHECK_ARG(rule >= WN_RULE_SGD && rule <= WN_RULE_RMSPROP, "wn_rule_step: unknown rule");
-    WN_CHECK_ARG(rule == WN_RULE_SGD || s1, "wn_rule_step: this rule needs s1");
+    WN_CHECK_ARG(rule >= WN_RULE_SGD && rule <= WN_RULE_EMA, "wn_rule_step: unknown rule");
+    WN_CHECK_ARG(rule == WN_RULE_SGD || rule == WN_RULE_EMA || s1, "wn_rule_step: this rule needs s1");
+    if (rule == WN_RULE_EMA) {
+        // param = the average, grad = the weights: the hooks of a gradient have no meaning on them
+        WN_CHECK_ARG(weight_decay == 0.f && grad_mult == 1.f,
+                     "wn_rule_step: WN_RULE_EMA takes weight_decay == 0 and grad_mult == 1 (grad is the weights, not a gradient)");
+        WN_CHECK_ARG(lr_dev || (lr >= 0.f && lr <= 1.f),                      // false for NaN
+                     "wn_rule_step: WN_RULE_EMA needs a rate 1 - decay in [0, 1]");
+    }
     WN_CHECK_ARG(rule != WN_RULE_ADADELTA || s2, "wn_rule_step: AdaDelta needs s2");
     return generic_rule(rule, param, grad, s1, s2, n, lr, hyper, eps, weight_decay, sqnorm, clip, grad_mult, lr_dev,
                         as_stream(stream));

@@ -862,6 +862,37 @@ __global__ void k_rule(float* __restrict__ p, const float* __restrict__ g, float
     }
 }
 
+// Rule 6: the exponential moving average of the weights, e += r (w - e), r = 1 - decay_t from the host or from device
+// memory.  It shares only the skip with the rules above (a step the optimiser skipped is a step the average skips); w is
+// no gradient, so no clipping rate, weight decay or multiplier exists here.  Evaluated as (e - r e) + r w in two fused
+// multiply-adds: two roundings, each of a term no larger than max(|e|, |w|, |e_new|), and exact at both ends -- r == 0
+// leaves e, r == 1 stores w (e + (w - e) would not: the difference is rounded) -- with no case of its own for either.
+__device__ __forceinline__ float ema_one(float e, float w, float r) {
+    return __fmaf_rn(r, w, __fmaf_rn(-r, e, e));
+}
+// n4 > 0 only when both pointers are 16-byte aligned: n4 float4 per array, block 0 takes the n - 4 n4 elements after them.
+__global__ void k_ema(float* __restrict__ e, const float* __restrict__ w, long long n4, long long n, float r,
+                      const float* __restrict__ sqnorm, float clip, const float* __restrict__ r_dev) {
+    if (r_dev) r = *r_dev;
+    if (sqnorm && clip > 0.f) {
+        float nrm = sqrtf(*sqnorm);
+        if (!(nrm < 3.0e38f)) return;      // non-finite gradient norm: the update is skipped (see k_adam)
+    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        float4 a = reinterpret_cast<float4*>(e)[i];
+        const float4 b = reinterpret_cast<const float4*>(w)[i];
+        a.x = ema_one(a.x, b.x, r); a.y = ema_one(a.y, b.y, r);
+        a.z = ema_one(a.z, b.z, r); a.w = ema_one(a.w, b.w, r);
+        reinterpret_cast<float4*>(e)[i] = a;
+    }
+    if (n4 == 0) {
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+            e[i] = ema_one(e[i], w[i], r);
+    } else if (blockIdx.x == 0) {
+        for (long long i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) e[i] = ema_one(e[i], w[i], r);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // A2 on the device: table lookups (the 65,536-entry encode table and the Q-entry decode table are built on the host
 // with the reference's float64 formulas, data.py:18-23 / 37-43, so the device results are theirs bit for bit)
@@ -1300,7 +1331,19 @@ int generic_rule(int rule, float* p, const float* g, float* s1, float* s2, long 
         case 2: RULE_LAUNCH(2); break;
         case 3: RULE_LAUNCH(3); break;
         case 4: RULE_LAUNCH(4); break;
-        default: RULE_LAUNCH(5); break;
+        case 5: RULE_LAUNCH(5); break;
+        case 6: {
+            // float4 when both arrays allow it, else one scalar grid-stride loop; the grid is sized for what it runs
+            const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+            const long long n4 = al ? n / 4 : 0;
+            const long long work = n4 > 0 ? n4 : n;
+            blocks = (int)((work + 255) / 256);
+            if (blocks > 2048) blocks = 2048;
+            if (blocks < 1) blocks = 1;
+            hipLaunchKernelGGL(k_ema, dim3(blocks), dim3(256), 0, s, p, g, n4, n, lr, sqnorm, clip, lr_dev);
+            break;
+        }
+        default: wn::set_error("generic_rule: unknown rule %d", rule); return WN_EARG;
     }
 #undef RULE_LAUNCH
     WN_LAUNCH_CHECK();

@@ -26,12 +26,21 @@ class DataParallel(object):
     def broadcast_weights(self, src: int = 0):
         """Every replica starts from rank ``src``'s weights and optimiser state: the moment arrays, the step counter
         (Adam's bias correction depends on it: a rank that resumed a checkpoint must not run ahead of the others) and the
-        host scalars of the rule in use (alpha / lr / momentum, Eve's loss-feedback pair d, f)."""
-        opt = self.net.optimizer
+        host scalars of the rule in use (alpha / lr / momentum, Eve's loss-feedback pair d, f).  With ``enable_ema`` (on every
+        rank or on none) the weight average, its clock, decay and warm-up switch travel too; after that it needs no collective of
+        its own: every rank averages identical weights."""
+        opt, net = self.net.optimizer, self.net
         with torch.no_grad():
             dist.broadcast(self.net._arena, src, group=self.group)
             dist.broadcast(opt.m, src, group=self.group)
             dist.broadcast(opt.v, src, group=self.group)
+            if net.ema_enabled:
+                dist.broadcast(net._ema_arena, src, group=self.group)
+                ema = torch.tensor([float(net._ema_t), net._ema_decay, float(net._ema_warmup)], dtype=torch.float64,
+                                   device=net._arena.device)
+                dist.broadcast(ema, src, group=self.group)
+                t, decay, warm = ema.tolist()
+                net._ema_t, net._ema_decay, net._ema_warmup = int(round(t)), decay, bool(warm)
         names = [k for k in ("t", "alpha", "beta1", "beta2", "beta3", "eps", "lr", "hyper", "d", "f")
                  if k in vars(opt)]                        # instance attributes only (Adam's `lr` is a derived property)
         vals = torch.tensor([float(getattr(opt, k)) for k in names], dtype=torch.float64, device=self.net._arena.device)

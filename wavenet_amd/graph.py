@@ -7,7 +7,8 @@ on the stream our C-ABI calls are issued on) and replayed, the step is one graph
 
 What changes from step to step lives in device memory, never in kernel arguments:
   * the batch: copied into the graph's static input buffers;
-  * Adam's bias-corrected step size alpha_t: a device scalar written before each replay (``wn_adam_step_dev``).
+  * Adam's bias-corrected step size alpha_t: a device scalar written before each replay (``wn_adam_step_dev``);
+  * the rate 1 - decay_t of the weight average (``WaveNet.enable_ema``), likewise.
 With data parallelism the gradient all-reduce stays OUTSIDE the graphs (forward+backward graph -> RCCL all-reduce ->
 optimiser graph), so nothing here depends on capturing a collective.
 """
@@ -16,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from .ema import ema_rate_at
 
 
 def default_loss(net, x, tgt, window_only: bool = False):
@@ -41,12 +43,16 @@ class TrainStepGraph(object):
         self.tgt = tgt.clone()
         opt = net.optimizer
         self._lr = torch.zeros((1,), device=x.device, dtype=torch.float32)
+        self._ema_rate = torch.zeros((1,), device=x.device, dtype=torch.float32)      # 0: the warm-up steps leave the average alone
         self._one = None
         dp = net._dp_group is not None
         self._gmult = 1.0 / net._dp_group.world if dp else 1.0
         # warm-up on the capture stream (per-stream scratch, function attributes, allocator pools), then put the
         # training state back: the warm-up steps are not training steps
-        keep = (net._arena.clone(), opt.m.clone(), opt.v.clone(), opt.t)
+        if net._ema_swapped:
+            raise _lib.WaveNetHipError("TrainStepGraph inside ema_weights(): the weights are the average there, not the iterate")
+        keep = (net._arena.clone(), opt.m.clone(), opt.v.clone(), opt.t,
+                net._ema_arena.clone() if net.ema_enabled else None, net._ema_t)
         self._stream = torch.cuda.Stream(device=x.device)
         self._keep_graph = bool(keep_graph)
         self._g1 = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
@@ -72,6 +78,8 @@ class TrainStepGraph(object):
             torch.cuda.synchronize()
             with torch.no_grad():
                 net._arena.copy_(keep[0]); opt.m.copy_(keep[1]); opt.v.copy_(keep[2])
+                if keep[4] is not None:
+                    net._ema_arena.copy_(keep[4])
             # whatever images the warm-up derived from the weights (the bf16 operand images of storage='bf16') are stale
             # now, and must be rebuilt INSIDE the capture: a replay has no host code that could repack them
             net._weights_changed()
@@ -92,7 +100,9 @@ class TrainStepGraph(object):
             torch.cuda.synchronize()
             with torch.no_grad():
                 net._arena.copy_(keep[0]); opt.m.copy_(keep[1]); opt.v.copy_(keep[2])
-            opt.t = keep[3]
+                if keep[4] is not None and net._ema_arena is not None:
+                    net._ema_arena.copy_(keep[4])
+            opt.t, net._ema_t = keep[3], keep[5]
             net._weights_changed()
             # outside this object's graphs nobody runs wn_plan_prepare: eager calls must not take the plan's (stale) images
             if getattr(self, "_use_plan", False):
@@ -103,7 +113,8 @@ class TrainStepGraph(object):
         the old value (only the batch and the learning rate travel through device memory)."""
         opt, p = self.net.optimizer, self.net.params
         return tuple(getattr(opt, k, None) for k in ("beta1", "beta2", "beta3", "eps", "hyper")) + \
-            (p.gradient_clipping, p.weight_decay, self.net.gemm_precision or _lib.get_gemm_precision())
+            (p.gradient_clipping, p.weight_decay, self.net.gemm_precision or _lib.get_gemm_precision(),
+             self.net.ema_enabled)              # ... and whether the averaging launch is among the captured nodes
 
     def _fwd_bwd(self):
         if getattr(self, "_use_plan", False) and self._planned:
@@ -127,6 +138,8 @@ class TrainStepGraph(object):
 
     def _opt(self):
         self.net.optimizer.update(self._gmult, lr_dev=self._lr)
+        if self.net.ema_enabled:
+            self.net._ema_step(rate_dev=self._ema_rate)
         self.net._weights_changed()
 
     def step(self, x=None, tgt=None):
@@ -135,14 +148,19 @@ class TrainStepGraph(object):
         net, opt = self.net, self.net.optimizer
         if self._hyper() != self._snap:
             raise _lib.WaveNetHipError(
-                "momentum / eps / gradient_clipping / weight_decay / GEMM precision changed after the step was captured "
+                "momentum / eps / gradient_clipping / weight_decay / GEMM precision / enable_ema changed after the step was captured "
                 "(%r -> %r): capture a new TrainStepGraph" % (self._snap, self._hyper()))
+        if net._ema_swapped:
+            raise _lib.WaveNetHipError("TrainStepGraph.step() inside ema_weights(): the weights are the average there")
         if x is not None:
             self.x.copy_(x, non_blocking=True)
         if tgt is not None:
             self.tgt.copy_(tgt, non_blocking=True)
         opt.t += 1                                   # update() is not called on replay: keep Adam's clock here
         self._lr.fill_(opt.lr)
+        if net.ema_enabled:                          # the schedule's clock, like Adam's: it also advances for a step skipped on the device
+            self._ema_rate.fill_(float(ema_rate_at(net._ema_t, net._ema_decay, net._ema_warmup)))
+            net._ema_t += 1
         self._g1.replay()
         if self._g2 is not None:
             net._dp_group.all_reduce_grads(net._grad_arena)

@@ -32,8 +32,23 @@ _SAMPLING_FLAGS = (
 _BATCH_FLAGS = (
     (("--utterances",), int, None, "write this many utterances, generated_000.wav ... (with --fast: one batched run)"),
 )
+# the exponential moving average of the weights (WaveNet.enable_ema; the reference trains and generates from the raw
+# iterates): all off.  A command line without them parses to what it parsed to before they existed: they are attributes of
+# the namespace only when given, and read as their defaults (the class attributes of ``Args``) when not.
+_EMA_FLAGS = (
+    (("--ema-decay",), float, 0.0, "train: keep an exponential moving average of the weights with this decay, saved as "
+                                   "wavenet.ema.npz (0 = off; 0.999 - 0.9999 is usual)"),
+    (("--valid-wav-dir",), str, None, "train: after every epoch, print the negative log-likelihood of this directory's .wav "
+                                      "files (and, with --ema-decay, that of the averaged weights)"),
+    (("--ema",), None, False, "generate: use the checkpoint's averaged weights (wavenet.ema.npz)"),
+)
 _PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation instead of silence; repeatable: one file for "
                 "all utterances, or one per utterance")
+
+
+class Args(argparse.Namespace):
+    """What :func:`parse` returns: the defaults of ``_EMA_FLAGS`` live here, not in the instance."""
+    ema_decay, valid_wav_dir, ema = 0.0, None, False
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -43,6 +58,12 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
+    for flags, typ, default, text in _EMA_FLAGS:
+        assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
+        if typ is None:
+            ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
+        else:
+            ap.add_argument(*flags, type=typ, default=argparse.SUPPRESS, help=text + " (default: %r)" % (default,))
     ap.add_argument("--prompt", action="append", default=None, metavar="FILE.wav", help=_PROMPT_HELP)
     return ap
 
@@ -63,9 +84,11 @@ def utterance_prompts(args):
 
 def parse(argv=None):
     ap = build_parser()
-    args = ap.parse_args(argv)
+    args = ap.parse_args(argv, namespace=Args())
     try:
         utterance_prompts(args)
     except ValueError as e:
         ap.error(str(e))
+    if not (0.0 <= args.ema_decay < 1.0):
+        ap.error("--ema-decay must lie in [0, 1), got %r" % (args.ema_decay,))
     return args

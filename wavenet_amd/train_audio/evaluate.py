@@ -1,7 +1,7 @@
 """Evaluation driver (new; the reference has none): the model's negative log-likelihood on every .wav file of a directory,
 teacher-forced, in nats and bits per sample -- the held-out number that tells overfitting from learning.
 
-    python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model [--json scores.json]
+    python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model [--ema] [--json scores.json]
 
 Files are read as training reads them (mu-law tokens, silence trimmed) and scored by ``WaveNet.score``.  The command has
 its own parser: it shares ``-g / -w / -m`` with train and generate and takes none of their other flags."""
@@ -24,6 +24,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-m", "--model-dir", type=str, default="model", help="wavenet.json + checkpoints")
     ap.add_argument("--chunk-width", type=int, default=16384, help="scored samples per piece of a file")
     ap.add_argument("--batch-size", type=int, default=8, help="pieces per launch")
+    # present in the namespace only when given (train_audio.model.build reads it with a default of off)
+    ap.add_argument("--ema", action="store_true", default=argparse.SUPPRESS,
+                    help="score the checkpoint's averaged weights (wavenet.ema.npz, written by train --ema-decay)")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
     return ap
 

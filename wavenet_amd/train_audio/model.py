@@ -50,11 +50,29 @@ def load_params(model_dir: str) -> Params:
 
 def build(args):
     """-> (params, wavenet) on ``cuda:<args.gpu_device>``.  There is no CPU mode (``-g -1`` in the reference): the product
-    path is the HIP library and fails loudly without a device."""
+    path is the HIP library and fails loudly without a device.
+
+    ``args.ema_decay`` > 0 (train) keeps a weight average, resumed from the checkpoint's ``wavenet.ema.npz`` when it is there;
+    ``args.ema`` (generate, evaluate) loads that file's averaged weights as the model's weights.  Both are read with a
+    default, so that a caller with a parser of its own need not know them."""
     params = load_params(args.model_dir)
     net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed)
     params.dump()
-    net.load(args.model_dir)
+    ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    use_ema = bool(getattr(args, "ema", False))
+    if use_ema and ema_decay > 0:
+        raise Exception("--ema loads the averaged weights as the model's weights; it does not go with --ema-decay")
+    if ema_decay > 0:
+        net.enable_ema(ema_decay)
+    if use_ema:
+        try:
+            net.load(args.model_dir, weights="ema")
+        except FileNotFoundError as e:
+            raise SystemExit("--ema: {}".format(e))
+    else:
+        net.load(args.model_dir)
+    if ema_decay > 0:
+        net.enable_ema(ema_decay)                  # the command line wins over the decay the checkpoint was written with
     if args.gpu_device < 0:
         raise Exception("--gpu_device -1 (CPU) is not supported: this engine runs on a HIP device only")
     torch.cuda.set_device(args.gpu_device)

@@ -13,6 +13,7 @@ from .. import TrainStepGraph, data
 from ..graph import default_loss
 from . import args as _args
 from . import model as _model
+from .evaluate import evaluate_dir
 
 
 HEALTH_EVERY = 100      # updates between two reads of WaveNet.last_update_applied() (a host synchronisation each)
@@ -88,8 +89,23 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     return float(sum_loss.item())
 
 
+def validate(net, params, wav_dir, epoch):
+    """The held-out negative log-likelihood after an epoch: one line for the weights being trained and, when a weight
+    average is kept, one for the averaged weights."""
+    def line(what, total):
+        sys.stdout.write("epoch: {} - held-out {}: {:.6f} nats/sample  {:.6f} bits/sample  ({} samples)\n".format(
+            epoch, what, total["nats_per_sample"], total["bits_per_sample"], total["samples"]))
+    line("weights", evaluate_dir(net, params, wav_dir, verbose=False)["total"])
+    if net.ema_enabled:
+        with net.ema_weights():
+            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False)["total"])
+    sys.stdout.flush()
+
+
 def main(argv=None):
     args = _args.parse(argv)
+    if args.ema:
+        raise Exception("--ema belongs to generate and evaluate; train keeps an average with --ema-decay")
     params, net = _model.build(args)
     np.random.seed(args.seed)
     net.update_laerning_rate(args.lr)
@@ -118,6 +134,8 @@ def main(argv=None):
             epoch, average_loss, int((time.time() - start_time) / 60)))
         sys.stdout.flush()
         net.save(args.model_dir)
+        if args.valid_wav_dir:
+            validate(net, params, args.valid_wav_dir, epoch)
     return average_loss
 
 

@@ -14,6 +14,7 @@ the hot path.  T-contiguous inputs (numpy one-hot images) are converted once at 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import math
@@ -586,6 +587,9 @@ class _StepPlan(object):
             pass
 
 
+EMA_FILE = "wavenet.ema.npz"       # the weight average of enable_ema, next to wavenet.model.npz
+
+
 class WaveNet(object):
     """Drop-in for wavenet.py:370-639."""
 
@@ -615,6 +619,8 @@ class WaveNet(object):
         self._anchor = torch.zeros((1,), requires_grad=True)
         self._dp_group = None
         self._last_layer_inputs = None
+        self._ema_arena, self._ema_t, self._ema_decay, self._ema_warmup = None, 0, 0.0, True     # enable_ema
+        self._ema_swapped = False           # True inside ema_weights()
         self.create_network()
         self._allocate(seed)
         self.setup_optimizer()
@@ -880,7 +886,13 @@ class WaveNet(object):
         self._grad_arena.zero_()
 
     def backprop(self, loss):
-        """cleargrads -> backward -> [DP all-reduce] -> WeightDecay, GradientClipping -> Adam."""
+        """cleargrads -> backward -> [DP all-reduce] -> WeightDecay, GradientClipping -> Adam -> [weight average].
+
+        With :meth:`enable_ema` the average then takes one step towards the new weights, behind the same non-finite-norm
+        guard as the optimiser step: a step skipped on the device moves neither.  Like Adam's ``t``, the host clock
+        ``_ema_t`` (the schedule of ``ema.ema_decay_at``) advances for such a skipped step too."""
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("backprop() inside ema_weights(): the weights are the average there, not the iterate")
         self.zero_grads()
         if callable(loss):
             loss = loss()
@@ -895,7 +907,101 @@ class WaveNet(object):
             self.optimizer.update(gmult, loss=lv)
         else:
             self.optimizer.update(gmult)
+        if self._ema_arena is not None:
+            self._ema_step()
+            self._ema_t += 1
         self._weights_changed()
+
+    # -- exponential moving average of the weights (new capability; schedule: ema.py) ------------
+    def enable_ema(self, decay: float = 0.9999, warmup: bool = True):
+        """Keep an exponential moving average of the weights: after every optimiser step (``backprop``,
+        ``TrainStepGraph.step``) ``e += (1 - decay_t) (w - e)`` with ``decay_t = ema.ema_decay_at(_ema_t, decay, warmup)``,
+        one more elementwise launch on the flat arena.  The average starts at the current weights.  Calling this again
+        changes ``decay`` / ``warmup`` and keeps the average and its clock.  Evaluate and generate from it inside
+        :meth:`ema_weights`; :meth:`save` / :meth:`load` carry it in ``wavenet.ema.npz``."""
+        from . import ema
+        decay = ema.check_decay(decay)
+        if self._ema_arena is None:
+            self._ema_arena = self._arena.detach().clone()
+            self._ema_t = 0
+        self._ema_decay, self._ema_warmup = decay, bool(warmup)
+
+    def disable_ema(self):
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("disable_ema() inside ema_weights()")
+        self._ema_arena, self._ema_t = None, 0
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self._ema_arena is not None
+
+    def _ema_step(self, rate_dev=None):
+        """The averaging launch.  The rate is taken by value from the schedule at ``_ema_t``, or read from ``rate_dev`` (a
+        1-element device tensor: graph replay).  It gets the norm word and clip of the optimiser step just issued, so that a
+        step the optimiser skipped is a step the average skips.  Does not advance ``_ema_t``."""
+        from . import ema
+        _need_gpu(self._arena)
+        p = self.params
+        clip = float(p.gradient_clipping) if p.gradient_clipping and p.gradient_clipping > 0 else 0.0
+        rate = 0.0 if rate_dev is not None else float(ema.ema_rate_at(self._ema_t, self._ema_decay, self._ema_warmup))
+        check(_lib.lib().wn_rule_step(_lib.WN_RULE_EMA, ptr(self._ema_arena), ptr(self._arena), None, None,
+                                      self._arena.numel(), rate, ptr(rate_dev) if rate_dev is not None else None,
+                                      0.0, 0.0, 0.0, ptr(self.optimizer._norm) if clip > 0 else None, clip, 1.0,
+                                      stream_ptr()), "wn_rule_step")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with net.ema_weights(): ...``: the model computes with the averaged weights -- ``score``, ``generate``,
+        ``state_dict`` -- and with its own again afterwards.  The CONTENTS of the two arenas are exchanged; the pointers,
+        which plans, graphs and decoder handles keep, stay put.  Training inside is refused."""
+        if self._ema_arena is None:
+            raise _lib.WaveNetHipError("ema_weights(): no average is kept (enable_ema)")
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("ema_weights() does not nest")
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
+
+    def _ema_swap(self):
+        with torch.no_grad():
+            tmp = self._arena.clone()
+            self._arena.copy_(self._ema_arena)
+            self._ema_arena.copy_(tmp)
+        self._weights_changed()
+
+    def ema_state_dict(self) -> Dict[str, np.ndarray]:
+        """The average under the keys of :meth:`state_dict`, plus ``ema/t``, ``ema/decay`` and ``ema/warmup``."""
+        if self._ema_arena is None:
+            raise _lib.WaveNetHipError("ema_state_dict(): no average is kept (enable_ema)")
+        src = self._arena if self._ema_swapped else self._ema_arena          # inside ema_weights() the average sits in _arena
+        sd = {"%s/%s" % (ln.name, kind): src[o:o + n].view(shape).detach().cpu().numpy().copy()
+              for ln, kind, o, n, shape in self._spans}
+        sd.update({"ema/t": np.array(self._ema_t), "ema/decay": np.array(self._ema_decay),
+                   "ema/warmup": np.array(self._ema_warmup)})
+        return sd
+
+    def load_ema_state_dict(self, sd: Dict[str, np.ndarray]):
+        """The inverse of :meth:`ema_state_dict`: average, clock, decay and warm-up switch all come from ``sd``."""
+        if self._ema_arena is None:
+            raise _lib.WaveNetHipError("load_ema_state_dict(): no average is kept (enable_ema)")
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("load_ema_state_dict() inside ema_weights()")
+        from . import ema
+        decay = ema.check_decay(float(sd["ema/decay"]))
+        with torch.no_grad():
+            for ln, kind, o, n, shape in self._spans:
+                key = "%s/%s" % (ln.name, kind)
+                if key not in sd:
+                    raise KeyError(key)
+                a = np.asarray(sd[key], dtype=np.float32)
+                if a.shape != tuple(shape):
+                    raise Exception("shape of %s is %s, expected %s" % (key, a.shape, tuple(shape)))
+                self._ema_arena[o:o + n].copy_(torch.from_numpy(a.reshape(-1)))
+        self._ema_t, self._ema_decay, self._ema_warmup = int(sd["ema/t"]), decay, bool(sd["ema/warmup"])
 
     def last_update_applied(self) -> bool:
         """False when the most recent optimiser step was SKIPPED on the device because the global gradient norm was not
@@ -921,6 +1027,8 @@ class WaveNet(object):
         dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self._arena = self._arena.detach().to(dev)
         self._grad_arena = self._grad_arena.to(dev)
+        if self._ema_arena is not None:
+            self._ema_arena = self._ema_arena.to(dev)
         self._bind()
         self._anchor = torch.zeros((1,), device=dev, requires_grad=True)
         self.optimizer.to(dev)
@@ -1167,13 +1275,17 @@ class WaveNet(object):
         """When an HDF5 library is at hand, the weights as ``wavenet.model`` in the reference's own container -- the file its
         ``load`` opens (wavenet.py:627-633) -- and THEN ``wavenet.model.npz`` + ``wavenet.opt.npz``: written last, the .npz is
         the newer of the two weight files, so :meth:`load` takes it after every ``save`` and needs no HDF5 library for a
-        checkpoint this package wrote."""
+        checkpoint this package wrote.  With :meth:`enable_ema`, also the average as ``wavenet.ema.npz``."""
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("save() inside ema_weights(): the two weight files would change places")
         os.makedirs(model_dir, exist_ok=True)
         from . import hdf5_io
         if hdf5_io.available():
             self.save_hdf5(os.path.join(model_dir, "wavenet.model"))
         np.savez(os.path.join(model_dir, "wavenet.model.npz"), **self.state_dict())
         np.savez(os.path.join(model_dir, "wavenet.opt.npz"), **self.optimizer.state_dict())
+        if self._ema_arena is not None:
+            np.savez(os.path.join(model_dir, EMA_FILE), **self.ema_state_dict())
 
     def save_hdf5(self, filename):
         """The weights in the file format and layout of the reference's ``serializers.save_hdf5(model_dir +
@@ -1205,13 +1317,34 @@ class WaveNet(object):
             sd = hdf5_io.read_datasets(filename)
         self.load_state_dict({k: v for k, v in sd.items() if k in self.state_dict()})
 
-    def load(self, model_dir="./"):
+    def load(self, model_dir="./", weights: str = "model"):
         """wavenet.py:627-639.  Two weight files may sit in the directory: the reference's own HDF5 ``wavenet.model`` and this
         package's ``wavenet.model.npz``.  The HDF5 file is loaded when it is the only one or the NEWER one (modification time:
         a reference-written checkpoint dropped next to an older .npz must not be ignored silently -- that case is announced);
         :meth:`save` writes the .npz last, so a directory this package saved loads from the .npz without a word and without an
         HDF5 library.  If the HDF5 file is newer but no HDF5 library can be found, the .npz next to it is loaded with a
-        warning instead of failing."""
+        warning instead of failing.
+
+        With :meth:`enable_ema` the average comes from ``wavenet.ema.npz``; when weights were loaded and that file is not
+        there, the average starts again from them (``_ema_t = 0``), which is announced.  Without it the file is ignored.
+        ``weights="ema"`` loads the AVERAGED weights of that file as the model's weights -- evaluation and generation from a
+        checkpoint -- and nothing else (no optimiser state: it belongs to the iterate); it raises when the file is absent."""
+        if weights not in ("model", "ema"):
+            raise ValueError("weights must be 'model' or 'ema', got %r" % (weights,))
+        if self._ema_swapped:
+            raise _lib.WaveNetHipError("load() inside ema_weights()")
+        ema_fn = os.path.join(model_dir, EMA_FILE)
+        if weights == "ema":
+            if not os.path.isfile(ema_fn):
+                raise FileNotFoundError("%s: this checkpoint holds no averaged weights (it was trained without --ema-decay / "
+                                        "enable_ema)" % ema_fn)
+            print("loading", ema_fn, "...")
+            with np.load(ema_fn) as z:
+                sd = {k: z[k] for k in z.files}
+            self.load_state_dict(sd)
+            if self._ema_arena is not None:
+                self.load_ema_state_dict(sd)
+            return
         h5 = os.path.join(model_dir, "wavenet.model")
         nz = os.path.join(model_dir, "wavenet.model.npz")
         have_h5, have_nz = os.path.isfile(h5), os.path.isfile(nz)
@@ -1236,6 +1369,16 @@ class WaveNet(object):
             print("loading", fn, "...")
             with np.load(fn) as z:
                 self.optimizer.load_state_dict({k: z[k] for k in z.files})
+        if self._ema_arena is not None:
+            if os.path.isfile(ema_fn):
+                print("loading", ema_fn, "...")
+                with np.load(ema_fn) as z:
+                    self.load_ema_state_dict({k: z[k] for k in z.files})
+            elif use_h5 or have_nz:
+                print("no %s: the weight average starts again from the weights just loaded" % ema_fn)
+                with torch.no_grad():
+                    self._ema_arena.copy_(self._arena)
+                self._ema_t = 0
 
     # -- data parallel (new capability) -----------------------------------
     def enable_data_parallel(self, group=None, always_reduce: bool = False):
