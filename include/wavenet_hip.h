@@ -75,8 +75,9 @@ const char* wn_last_error(void);
  * ws / ws_bytes: device scratch, at least wn_exec_workspace_bytes() for the model and batch; its contents are dead when the
  * call's kernels have run, so ONE buffer per stream serves every call on that stream (never one buffer for two streams).
  * flags (ABI 3; the library reads NO environment variable and keeps no switch of its own -- what used to be
- * WAVENET_HIP_FORCE_GENERIC / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here; bit 2 is unassigned):
+ * WAVENET_HIP_FORCE_GENERIC / _FWD_T1_MIN_BLOCKS inside the .so are per-call fields here):
  *   WN_EXEC_FORCE_GENERIC   every kernel of the call from the any-shape correctness path (generic_kernels.hip), fp32
+ *   WN_EXEC_BIAS_PER_CLIP   wn_layer_* / wn_stack_*: one row of gate biases per clip (global conditioning; see the define)
  *   WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM, WN_EXEC_NO_MULTI_LAYER_BWD   see the defines
  *   WN_EXEC_HEAD_ROW_NLL    wn_head_xent only: per-row negative log-likelihoods instead of the gradient (see there)
  * fwd_t1_min_blocks: launch size (workgroups of four 32-column tiles) from which the fused 32-channel layer forward takes its
@@ -87,6 +88,27 @@ const char* wn_last_error(void);
  * otherwise. */
 enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 3 };
 #define WN_EXEC_FORCE_GENERIC 1u
+#define WN_EXEC_BIAS_PER_CLIP 2u   /* Global conditioning (van den Oord et al. 2016, eq. 3: z = tanh(Wf*x + Vf h) sigmoid(Wg*x + Vg h), h one
+                                      vector per clip): to a layer Vf h / Vg h are a convolution bias that is constant over time
+                                      and differs from clip to clip.  Honoured by wn_layer_fwd / wn_layer_bwd / wn_stack_fwd /
+                                      wn_stack_bwd; every other entry point ignores the bit.  WnExec.reserved is then the stride,
+                                      in floats, between consecutive clips' rows:
+                                        forward   bf / bg (per layer: bf[l] / bg[l]) point at clip 0's row of cd floats, clip b
+                                                  reads ptr + b * stride; bp / bs stay per channel.  The zero prefix is
+                                                  unchanged: for t < Z neither the convolution nor the bias contributes.
+                                        backward  dbf / dbg (dbf[l] / dbg[l]) point at clip 0's row; row b is accumulated (+=)
+                                                  with the sums of da[b, t, :] / dg[b, t, :] over t >= Z of that clip only.  One
+                                                  launch per layer writes both gates (k_colsum_per_clip: a fixed summation
+                                                  order -- the order of the shared-bias column sums of a B = 1 call --, no float
+                                                  atomics, no scratch: bit-reproducible from run to run).
+                                      WN_EARG before any device work: stride < cd, a NULL bf / bg (forward) or dbf / dbg
+                                      (backward) entry.  The fp16 x 2 stack forward loads a lane's bias values as float4: there
+                                      the stride must be a multiple of 4 floats and the rows 16-byte aligned (WN_EARG with a
+                                      message otherwise, never another path); it adds them in fp32 AFTER the accumulator is
+                                      rescaled -- they never pass through the power-of-two tile scale -- and runs every layer as
+                                      its own launch, as under WN_EXEC_NO_FWD_GROUPS.  The stack backward takes the per-layer
+                                      path (bias-gradient tables always do), so wn_stack_saves_tanh is 1.  wn16_* (bf16 storage)
+                                      keeps refusing biases.  A step plan holds weight images only, never a bias pointer */
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
 #define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
@@ -106,7 +128,7 @@ typedef struct WnExec {
     void* ws;
     size_t ws_bytes;
     int fwd_t1_min_blocks;
-    int reserved;                     /* 0 */
+    int reserved;                     /* WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bias rows; ignored otherwise */
     void* plan;                       /* ABI 5: a step plan (wn_plan_create) or NULL -- see "step plan" below */
 } WnExec;
 /* 1 if the fused MFMA kernels cover this residual-layer shape (a pure shape query; a call with WN_EXEC_FORCE_GENERIC

@@ -18,11 +18,19 @@ int check_precision(const char* fn, const WnExec* ex) {
                  "%s: WnExec.precision must be 0 .. 3", fn);
     return WN_OK;
 }
+int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f, const void* row_g, const char* names) {
+    if (!ex || !(ex->flags & WN_EXEC_BIAS_PER_CLIP)) return WN_OK;
+    WN_CHECK_ARG(ex->reserved >= Cd, "%s: WN_EXEC_BIAS_PER_CLIP with a row stride (WnExec.reserved = %d) below cd = %d", fn,
+                 ex->reserved, Cd);
+    WN_CHECK_ARG(row_f && row_g, "%s: WN_EXEC_BIAS_PER_CLIP needs both %s", fn, names);
+    return WN_OK;
+}
 // (the entry points reject a precision outside 0 .. 3 first; the pure queries read one as bf16x3)
 Call::Call(const WnExec* ex)
     : flags(ex ? ex->flags : 0u), ws(ex ? ex->ws : nullptr), ws_bytes(ex ? ex->ws_bytes : 0),
       fwd_t1_min_blocks(ex && ex->fwd_t1_min_blocks ? ex->fwd_t1_min_blocks : 512),
-      plan(ex ? reinterpret_cast<StepPlan*>(ex->plan) : nullptr) {
+      plan(ex ? reinterpret_cast<StepPlan*>(ex->plan) : nullptr),
+      bias_stride(ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP) ? (long long)ex->reserved : 0) {
     const int p = ex ? ex->precision : WN_GEMM_BF16X3;
     precision = generic() ? WN_GEMM_FP32 : (p < WN_GEMM_FP32 || p > WN_GEMM_FP16X2) ? WN_GEMM_BF16X3 : p;
 }
@@ -73,14 +81,15 @@ int layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, const f
         return mfma_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, d, Z, 0, s);
     if (c.wide_layer(Cr, Cd, fw) && (f_save || Cd <= Cr))
         return wide_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
-    return generic_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
+    return generic_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s, c.bias_stride);
 }
 
 int layer_bwd(Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg, const float* Wp,
               const float* dout, const float* dz_skip, float* dx, float* dWf, float* dbf, float* dWg, float* dbg,
               float* dWp, float* dbp, float* dab_ws, int B, int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s) {
     if (c.layer_fast_path(Cr, Cd, fw)) {
-        int rc = mfma_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dWg, dWp, dab_ws, B, T, d, Z, s);
+        int rc = mfma_layer_bwd(x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dWg, dWp, dab_ws, B, T, d, Z, s,
+                                c.bias_per_clip());
         if (rc) return rc;
         return generic_layer_bwd_biases(c, dab_ws, dout, dbf, dbg, dbp, B, T, Cr, Cd, Z, s);
     }
@@ -174,6 +183,7 @@ int wn_layer_fwd(const float* x, const float* Wf, const float* bf, const float* 
     WN_CHECK_ARG(Z >= 0, "wn_layer_fwd: Z < 0");
     WN_CHECK_ARG((f_save == nullptr) == (g_save == nullptr), "wn_layer_fwd: f_save and g_save go together");
     WN_CHECK_ARG(out != x, "wn_layer_fwd: out must not alias x (taps read x[t-d])");
+    if (int rc = check_bias_rows(__func__, ex, Cd, bf, bg, "bf and bg")) return rc;
     Call c(ex);
     return layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, as_stream(stream));
 }
@@ -195,6 +205,7 @@ int wn_layer_bwd(const float* x, const float* f, const float* g, const float* Wf
     POS(B); POS(T); POS(Cr); POS(Cd); POS(fw); POS(d);
     WN_CHECK_ARG(Z >= 0, "wn_layer_bwd: Z < 0");
     WN_CHECK_ARG(dout || dz_skip, "wn_layer_bwd: both dout and dz_skip are NULL");
+    if (int rc = check_bias_rows(__func__, ex, Cd, dbf, dbg, "dbf and dbg")) return rc;
     Call c(ex);
     return layer_bwd(c, x, f, g, Wf, Wg, Wp, dout, dz_skip, dx, dWf, dbf, dWg, dbg, dWp, dbp, dab_ws, B, T, Cr, Cd, fw, d, Z,
                      as_stream(stream));

@@ -319,6 +319,63 @@ static int launch_colsum(const float* A, long long a_bs, int a_t0, int lda, int 
     return WN_OK;
 }
 
+// Per-clip column sums of both gates in one launch (WN_EXEC_BIAS_PER_CLIP): workgroup (x, b) owns 64 of the 2 Cd columns
+// [da | dg] of clip b and adds them in the order k_colsum + k_colsum_reduce use for ONE clip -- chunks of t_chunk rows, four
+// row lanes per chunk (rows t0 + k, t0 + k + 4, ...) combined as (p0 + p1) + (p2 + p3), chunk y on reduction lane y % 16 in
+// ascending order, the 16 lane sums in index order -- so row b is bit for bit what a B = 1 call of the shared-bias form adds
+// to its dbf / dbg.  No atomics, no scratch.  blockDim = (64 columns, 16 reduction lanes).
+// (B x 2 Cd / 64 workgroups: at config 2 that is 8 workgroups reading 33 MB per layer, and the launch is the largest single
+// part of what a conditioned step costs -- DESIGN "Global conditioning".  A form with 16 columns per workgroup and four
+// chunks in flight per lane was measured and was SLOWER; the next form to try splits a clip's chunks over workgroups and
+// lets the last one to finish add the partials in this same order.)
+__global__ __launch_bounds__(1024) void k_colsum_per_clip(const float* __restrict__ da, const float* __restrict__ dg, int lda,
+                                                          int T, int tmin, int Cd, float* __restrict__ dbf,
+                                                          float* __restrict__ dbg, long long stride, int t_chunk) {
+    __shared__ float red[16][64];
+    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
+    const int b = blockIdx.y;
+    const bool ok = m < 2 * Cd;
+    const bool gate = m >= Cd;
+    const int mm = gate ? m - Cd : m;
+    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
+    const int nchunk = (T - tmin + t_chunk - 1) / t_chunk;
+    float sum = 0.f;
+    if (ok)
+        for (int y = threadIdx.y; y < nchunk; y += 16) {
+            const int t0 = tmin + y * t_chunk, t1 = min(T, t0 + t_chunk);
+            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+            int t = t0;
+            for (; t + 3 < t1; t += 4) {
+                p0 += A[(long long)t * lda]; p1 += A[(long long)(t + 1) * lda];
+                p2 += A[(long long)(t + 2) * lda]; p3 += A[(long long)(t + 3) * lda];
+            }
+            if (t < t1) p0 += A[(long long)t * lda];
+            if (t + 1 < t1) p1 += A[(long long)(t + 1) * lda];
+            if (t + 2 < t1) p2 += A[(long long)(t + 2) * lda];
+            sum += (p0 + p1) + (p2 + p3);
+        }
+    red[threadIdx.y][threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.y == 0 && ok) {
+        float tot = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
+        float* out = gate ? dbg : dbf;
+        if (out) out[(long long)b * stride + mm] += tot;
+    }
+}
+int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
+                            long long stride, hipStream_t s) {
+    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
+    WN_CHECK_SHAPE(B <= 65535, "per-clip bias gradients: at most 65,535 clips per call");
+    int t_chunk = 256;                                      // launch_colsum's choice for one clip
+    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
+    hipLaunchKernelGGL(k_colsum_per_clip, dim3(cdiv(2 * Cd, 64), B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd, dbf, dbg,
+                       stride, t_chunk);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // A7  residual layer, generic
 // ---------------------------------------------------------------------------------------------
@@ -326,7 +383,7 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
                            const float* __restrict__ bf, const float* __restrict__ Wg,
                            const float* __restrict__ bg, float* __restrict__ z,
                            float* __restrict__ fs, float* __restrict__ gs,
-                           int B, int T, int Cr, int Cd, int fw, int d, int Z) {
+                           int B, int T, int Cr, int Cd, int fw, int d, int Z, long long bias_stride) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long total = (long long)B * T * Cd;
     if (i >= total) return;
@@ -336,8 +393,8 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
     int b = (int)(bt / T);
     float a = 0.f, g = 0.f;
     if (t >= Z) {
-        a = bf ? bf[o] : 0.f;
-        g = bg ? bg[o] : 0.f;
+        a = bf ? bf[b * bias_stride + o] : 0.f;        // bias_stride != 0: one bias row per clip (WN_EXEC_BIAS_PER_CLIP)
+        g = bg ? bg[b * bias_stride + o] : 0.f;
         const float* wf = Wf + (long long)o * Cr * fw;
         const float* wg = Wg + (long long)o * Cr * fw;
         for (int k = 0; k < fw; ++k) {
@@ -1033,10 +1090,10 @@ int generic_conv_bwd(const float* x, const float* W, const float* dout, float* d
 
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s) {
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride) {
     long long tot = (long long)B * T * Cd;
     hipLaunchKernelGGL(k_gate_fwd, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
-                       gs, B, T, Cr, Cd, fw, d, Z);
+                       gs, B, T, Cr, Cd, fw, d, Z, bias_stride);
     WN_LAUNCH_CHECK();
     long long N = (long long)B * T;
     hipLaunchKernelGGL(k_proj_res_fwd, dim3(cdiv(N * Cr, kThreads)), dim3(kThreads), 0, s, x, z, Wp, bp, out,
@@ -1062,8 +1119,12 @@ int generic_layer_bwd(const Call& c, const float* x, const float* f, const float
     int rc;
     if (dWf && (rc = conv_dw(x, dab, 2 * Cd, dWf, B, T, Cr, Cd, fw, d, Z, s))) return rc;
     if (dWg && (rc = conv_dw(x, dab + Cd, 2 * Cd, dWg, B, T, Cr, Cd, fw, d, Z, s))) return rc;
-    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
-    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (c.bias_per_clip()) {
+        if ((rc = generic_colsum_per_clip(dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+    } else {
+        if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
+        if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
+    }
     if (dWp) {   // dWp[cr][cd] += dout z^T,  z = f*g
         WgradArgs a{};
         a.A = dout; a.a_bs = (long long)T * Cr; a.a_t0 = 0; a.lda = Cr;
@@ -1086,8 +1147,12 @@ int generic_colsum(const float* A, int nB, int nT, int tmin, int lda, int M, flo
 int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout, float* dbf, float* dbg, float* dbp, int B,
                              int T, int Cr, int Cd, int Z, hipStream_t s) {
     int rc;
-    if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
-    if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (c.bias_per_clip()) {
+        if ((rc = generic_colsum_per_clip(dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+    } else {
+        if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
+        if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
+    }
     if (dbp && dout && (rc = launch_colsum(dout, (long long)T * Cr, 0, Cr, B, 0, T, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }

@@ -406,12 +406,41 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_mfma(WGArgs a) {
         }
     }
     if (!active) return;
+    if (a.fixed_part) {                   // fixed-order form: plain stores of this workgroup's tiles (see WGArgs.fixed_part)
+        const long long M = (long long)gridDim.z * (MT * 32);
+        float* __restrict__ q = a.fixed_part + (((long long)blockIdx.x * a.nprob + p) * M) * 32 + j;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) q[(long long)(m0 + mt * 32 + cg_ch(r, h)) * 32] = acc[mt][r];
+        return;
+    }
     float* __restrict__ o = a.out[p];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
             atomicAdd(o + (long long)(m0 + mt * 32 + cg_ch(r, h)) * a.ldo + (long long)j * (a.osk ? a.osk : 1), acc[mt][r]);
+}
+
+// dW_p[m][j] += the workgroups' tiles of WGArgs.fixed_part, added in workgroup order: one thread per element, no atomics
+__global__ void k_wgrad_fixed_reduce(WGArgs a, int nx, int M) {
+    const long long n = (long long)a.nprob * M * 32;
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float* __restrict__ q = a.fixed_part + e;
+    float s0 = 0.f;
+    for (int x = 0; x < nx; ++x) s0 += q[(long long)x * n];
+    const int p = (int)(e / ((long long)M * 32));
+    const int rem = (int)(e - (long long)p * M * 32);
+    const int m = rem >> 5, j = rem & 31;
+    a.out[p][(long long)m * a.ldo + (long long)j * (a.osk ? a.osk : 1)] += s0;
+}
+static int wgrad_fixed_reduce(const WGArgs& a, int nx, int M, hipStream_t s) {
+    const long long n = (long long)a.nprob * M * 32;
+    hipLaunchKernelGGL(k_wgrad_fixed_reduce, dim3(cdiv(n, 256)), dim3(256), 0, s, a, nx, M);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
 }
 
 int launch_wgrad(const Call& c, WGArgs& a, int M, hipStream_t s) {
@@ -448,10 +477,26 @@ int launch_wgrad(const Call& c, WGArgs& a, int M, hipStream_t s) {
         }
         return WN_OK;
     }
+    // a call with per-clip bias rows (a globally conditioned training step) must be bit-reproducible: the two kernels below
+    // then store per-workgroup tiles into the call's scratch and k_wgrad_fixed_reduce adds them in workgroup order
+    const bool fixed = c.bias_per_clip();
+    if (fixed) {
+        // fewer, longer row slabs until the tiles fit the call's scratch (one slab per clip at the least)
+        while (!c.has_scratch((size_t)grid.x * a.nprob * M * 32 * sizeof(float)) && a.wgs_per_b > 1) {
+            a.rows_per_wg *= 2;
+            a.wgs_per_b = cdiv(a.rows_A_per_b, a.rows_per_wg);
+            grid.x = a.nB * a.wgs_per_b;
+        }
+        const size_t bytes = (size_t)grid.x * a.nprob * M * 32 * sizeof(float);
+        a.fixed_part = reinterpret_cast<float*>(c.scratch(bytes, "the fixed-order weight-gradient tiles"));
+        if (!a.fixed_part) return WN_EARG;
+    }
     if (c.split_b3()) {          // bf16x3: at most 4 row tiles per workgroup (register budget), more groups in z
         const int mt3 = mt > 4 ? 4 : mt;
         grid.z = M / (mt3 * 32);
-        return launch_wgrad_b3(c, a, mt3, grid, s);
+        int rc = launch_wgrad_b3(c, a, mt3, grid, s);
+        if (rc || !fixed) return rc;
+        return wgrad_fixed_reduce(a, (int)grid.x, M, s);
     }
     bool any_b2 = false, all_b2 = true;
     for (int q = 0; q < a.nprob; ++q) { any_b2 |= a.B2p[q] != nullptr; all_b2 &= a.B2p[q] != nullptr; }
@@ -476,6 +521,7 @@ int launch_wgrad(const Call& c, WGArgs& a, int M, hipStream_t s) {
 #undef WG_LAUNCH
 #undef WGF_LAUNCH
     WN_LAUNCH_CHECK();
+    if (fixed) return wgrad_fixed_reduce(a, (int)grid.x, M, s);
     return WN_OK;
 }
 

@@ -76,6 +76,10 @@ struct WGArgs {
     // 1x1 convolution whose weight gradient this launch is) from the A values the kernel loads anyway; launch_wgrad_b3w sets
     // colsum_done when it took the request (other kernels ignore it), colsum_part is its scratch
     float* colsum; float* colsum_part; int colsum_done;
+    // k_wgrad_mfma / k_wgrad_b3 (the forms that otherwise leave with float atomics): non-NULL = workgroup x stores its tiles at
+    // fixed_part[((x * nprob + p) * M + m) * 32 + j] instead, and k_wgrad_fixed_reduce adds the workgroups in index order --
+    // bit-reproducible; what a call with per-clip bias rows (a globally conditioned training step) asks for
+    float* fixed_part;
 };
 
 // mode 0: multi-source, one output; mode 2: nprob problems of 32 rows sharing X.  Returns WN_ESHAPE when

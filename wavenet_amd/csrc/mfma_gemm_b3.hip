@@ -1141,6 +1141,15 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_b3(WGArgs a) {
         }
     }
     if (!active) return;
+    if (a.fixed_part) {                   // fixed-order form: plain stores of this workgroup's tiles (see WGArgs.fixed_part)
+        const long long M = (long long)gridDim.z * (MT * 32);
+        float* __restrict__ q = a.fixed_part + (((long long)blockIdx.x * a.nprob + p) * M) * 32 + j;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) q[(long long)(m0 + mt * 32 + b3_ch(r, h)) * 32] = acc[mt][r];
+        return;
+    }
     float* __restrict__ o = a.out[p];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles) {
+    int ntiles, long long bstride) {            // bstride != 0: bf / bg are clip 0's rows, clip b's lie b * bstride floats on
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;      // time column inside the tile (B/D operand), weight row (A operand)
     const int h = lane >> 5;
@@ -138,8 +138,8 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
         f32x16 aa, ag;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            aa[r] = (HAS_BIAS && bf) ? bf[ch_of(r, h)] : 0.f;
-            ag[r] = (HAS_BIAS && bg) ? bg[ch_of(r, h)] : 0.f;
+            aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;      // a tile belongs to one clip
+            ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles) {
+    int ntiles, long long bstride) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
     const int h = lane >> 5;
@@ -256,8 +256,8 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     f32x16 aa, ag;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        aa[r] = (HAS_BIAS && bf) ? bf[ch_of(r, h)] : 0.f;
-        ag[r] = (HAS_BIAS && bg) ? bg[ch_of(r, h)] : 0.f;
+        aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;          // a tile belongs to one clip
+        ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
     }
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -319,11 +319,16 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
     layer_pack_h2_block(a, img_all, (int)blockIdx.x);
 }
 
-template <int SAVE>
+// COND (WN_EXEC_BIAS_PER_CLIP, global conditioning): bf / bg point at clip 0's row of 32 gate biases, clip b's row lies
+// b * bstride floats on (16-byte aligned, bstride % 4 == 0).  Accumulator register r of lane (., h) is channel ch(r, h) =
+// 8 (r >> 2) + 4 h + (r & 3): the 16 values a lane needs per gate are four float4.  They are requested in front of the MFMA
+// block, land under it, and are added in fp32 AFTER the accumulator is rescaled -- fmaf(aa[r], uc, bias) -- so they never
+// pass through the tile's power-of-two scale or an fp16 split.  For t < Z neither the convolution nor the bias counts.
+template <int SAVE, bool COND>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     const float* __restrict__ x, const char* __restrict__ img_g, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles) {
+    int ntiles, const float* __restrict__ bf, const float* __restrict__ bg, long long bstride) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
     const int h = lane >> 5;
@@ -355,6 +360,15 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
             const float4 o = *reinterpret_cast<const float4*>(x + rowo + 8 * q);
             xc[4 * q + 0] = v.x * mc; xc[4 * q + 1] = v.y * mc; xc[4 * q + 2] = v.z * mc; xc[4 * q + 3] = v.w * mc;
             xo[4 * q + 0] = o.x * mo; xo[4 * q + 1] = o.y * mo; xo[4 * q + 2] = o.z * mo; xo[4 * q + 3] = o.w * mo;
+        }
+    }
+    float4 cf[4], cg[4];
+    if (COND) {
+        const long long rowb = (long long)b * bstride + 4 * h;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            cf[q] = *reinterpret_cast<const float4*>(bf + rowb + 8 * q);
+            cg[q] = *reinterpret_cast<const float4*>(bg + rowb + 8 * q);
         }
     }
 #pragma unroll
@@ -402,8 +416,15 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             const int r = 4 * q + m;
-            f4[m] = fast_tanh(live ? aa[r] * uc : 0.f);
-            g4[m] = fast_sigmoid(live ? ag[r] * uc : 0.f);
+            if (COND) {
+                const float vf = m == 0 ? cf[q].x : m == 1 ? cf[q].y : m == 2 ? cf[q].z : cf[q].w;
+                const float vg = m == 0 ? cg[q].x : m == 1 ? cg[q].y : m == 2 ? cg[q].z : cg[q].w;
+                f4[m] = fast_tanh(live ? fmaf(aa[r], uc, vf) : 0.f);
+                g4[m] = fast_sigmoid(live ? fmaf(ag[r], uc, vg) : 0.f);
+            } else {
+                f4[m] = fast_tanh(live ? aa[r] * uc : 0.f);
+                g4[m] = fast_sigmoid(live ? ag[r] * uc : 0.f);
+            }
             zz[r] = f4[m] * g4[m];
         }
         if (valid) {
@@ -677,18 +698,27 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live) {
     return c.fwd_t1_min_blocks > 0 && nt > 0 && (nt + 3) / 4 >= c.fwd_t1_min_blocks && nt < (1ll << 31);
 }
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
-                      int d, int Z, int t_live, hipStream_t s) {
+                      int d, int Z, int t_live, hipStream_t s, const float* bf, const float* bg, long long bias_stride) {
     const int tile_lo = t_live > 0 ? t_live / 32 : 0;
     const int tiles_per_b = (T + 31) / 32 - tile_lo;
     const int ntiles = B * tiles_per_b;
     const int blocks = (ntiles + 3) / 4;
     const char* im = reinterpret_cast<const char*>(img) + (size_t)l * kH2ImgStride;
-#define FWDH_LAUNCH(SAVE)                                                                                        \
-    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
-                       tile_lo, tiles_per_b, ntiles)
-    if (fs) FWDH_LAUNCH(1);
-    else if (gs) FWDH_LAUNCH(2);
-    else FWDH_LAUNCH(0);
+    const bool cond = bf != nullptr;
+    if (cond)
+        WN_CHECK_ARG(bg && bias_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(bf) & 15) == 0 &&
+                         (reinterpret_cast<uintptr_t>(bg) & 15) == 0,
+                     "fp16 x 2 layer forward with per-clip bias rows: the rows must be 16-byte aligned and their stride a "
+                     "multiple of 4 floats (stride %lld)", bias_stride);
+#define FWDH_LAUNCH(SAVE, COND)                                                                                            \
+    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
+                       tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride)
+    if (fs && cond) FWDH_LAUNCH(1, true);
+    else if (fs) FWDH_LAUNCH(1, false);
+    else if (gs && cond) FWDH_LAUNCH(2, true);
+    else if (gs) FWDH_LAUNCH(2, false);
+    else if (cond) FWDH_LAUNCH(0, true);
+    else FWDH_LAUNCH(0, false);
 #undef FWDH_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -716,7 +746,7 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     if (t1_min > 0 && blocks >= t1_min) {
 #define FWD1_LAUNCH(SAVE, BIAS)                                                                              \
     hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles)
+                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride)
         if (fs && hb) FWD1_LAUNCH(1, true);
         else if (fs) FWD1_LAUNCH(1, false);
         else if (gs && hb) FWD1_LAUNCH(2, true);
@@ -730,7 +760,7 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     if (blocks > 512) blocks = 512;          // 256 CUs x 2 resident workgroups; waves stride over tiles
 #define FWD_LAUNCH(SAVE, BIAS)                                                                               \
     hipLaunchKernelGGL((k_layer_fwd_mfma32<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles)
+                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride)
     if (fs && hb) FWD_LAUNCH(1, true);
     else if (fs) FWD_LAUNCH(1, false);
     else if (gs && hb) FWD_LAUNCH(2, true);

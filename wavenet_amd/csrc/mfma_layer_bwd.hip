@@ -1170,6 +1170,39 @@ __global__ void k_layer_bwd_reduce(const float* __restrict__ part, int nwg, floa
     }
 }
 
+// The same sum without atomics, for the steps that must be bit-reproducible on the per-layer path (per-clip bias rows: a
+// globally conditioned model trains through it).  A block owns 64 elements; its four waves each sum a quarter of the
+// workgroups' tiles in index order, the quarters are added in a fixed order through LDS, and the owner adds the total to dW.
+__global__ __launch_bounds__(256) void k_layer_bwd_reduce_fixed(const float* __restrict__ part, int nwg,
+                                                                float* __restrict__ dWf, float* __restrict__ dWg,
+                                                                float* __restrict__ dWp) {
+    __shared__ float red[4][64];
+    const int lane = threadIdx.x & 63, sp = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;                     // kPartFloats is a multiple of 64
+    const float* __restrict__ p = part + e;
+    const int per = (nwg + 3) / 4;
+    const int w0 = sp * per, w1 = min(nwg, w0 + per);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int w = w0;
+    for (; w + 4 <= w1; w += 4) {
+        s0 += p[(long long)(w + 0) * kPartFloats]; s1 += p[(long long)(w + 1) * kPartFloats];
+        s2 += p[(long long)(w + 2) * kPartFloats]; s3 += p[(long long)(w + 3) * kPartFloats];
+    }
+    for (; w < w1; ++w) s0 += p[(long long)w * kPartFloats];
+    red[sp][lane] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (sp != 0) return;
+    const float acc = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    const int tile = e >> 10, r = (e >> 6) & 15, ln = e & 63;   // k_layer_bwd_p1's partial-tile layout: tile * 1024 + r * 64 + lane
+    const int j = ln & 31, i = bch(r, ln >> 5);
+    if (tile < 4) {
+        float* dW = tile < 2 ? dWf : dWg;
+        if (dW) dW[(i * 32 + j) * 2 + (tile & 1)] += acc;
+    } else if (dWp) {
+        dWp[i * 32 + j] += acc;
+    }
+}
+
 // The same sum for up to kRedAllMax layers in one launch (blockIdx.z = layer): the stack's chained backward keeps
 // every layer's partial tiles and reduces them all at the end, instead of 40 small launches between the layer kernels.
 static constexpr int kRedAllMax = 64;
@@ -1293,7 +1326,7 @@ __global__ __launch_bounds__(256, 2) void k_layer_bwd_p2(
 
 int mfma_layer_bwd(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                    const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dWg,
-                   float* dWp, float* dab, int B, int T, int d, int Z, hipStream_t s) {
+                   float* dWp, float* dab, int B, int T, int d, int Z, hipStream_t s, bool fixed_order) {
     const int tiles_per_b = (T + 31) / 32;
     const long long nt = (long long)B * tiles_per_b;
     WN_CHECK_SHAPE(nt < (1ll << 31), "mfma_layer_bwd: too many tiles");
@@ -1309,8 +1342,12 @@ int mfma_layer_bwd(const float* x, const float* f, const float* g, const float* 
     else P1_LAUNCH(false, true);
 #undef P1_LAUNCH
     WN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_layer_bwd_reduce, dim3(kPartFloats / 256, kRedParts), dim3(256), 0, s, part, blocks, dWf, dWg,
-                       dout ? dWp : (float*)nullptr);
+    if (fixed_order)
+        hipLaunchKernelGGL(k_layer_bwd_reduce_fixed, dim3(kPartFloats / 64), dim3(256), 0, s, part, blocks, dWf, dWg,
+                           dout ? dWp : (float*)nullptr);
+    else
+        hipLaunchKernelGGL(k_layer_bwd_reduce, dim3(kPartFloats / 256, kRedParts), dim3(256), 0, s, part, blocks, dWf, dWg,
+                           dout ? dWp : (float*)nullptr);
     WN_LAUNCH_CHECK();
     if (dx) {
         hipLaunchKernelGGL(k_layer_bwd_p2, dim3(blocks), dim3(256), 0, s, Wf, Wg, dout, dab, dx, B, T, d,

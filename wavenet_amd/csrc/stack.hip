@@ -36,6 +36,15 @@ static int check_layers(const WnStackDesc* d, bool skip) {
                      "stack: bad layer %d", l);
     return WN_OK;
 }
+// WN_EXEC_BIAS_PER_CLIP: every layer's row stride covers its width and both row tables are complete (before any device work)
+static int check_bias_tables(const char* fn, const WnStackDesc* d, const WnExec* ex, const float* const* tf,
+                             const float* const* tg, const char* names) {
+    if (!ex || !(ex->flags & WN_EXEC_BIAS_PER_CLIP)) return WN_OK;
+    WN_CHECK_ARG(tf && tg, "%s: WN_EXEC_BIAS_PER_CLIP needs the %s tables", fn, names);
+    for (int l = 0; l < d->n_layers; ++l)
+        if (int rc = check_bias_rows(fn, ex, d->cd[l], tf[l], tg[l], names)) return rc;
+    return WN_OK;
+}
 }  // namespace wn
 
 using namespace wn;
@@ -76,6 +85,8 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
     Call c(ex);
     WN_CHECK_ARG(!g_only || chain_capable(c, d), "wn_stack_fwd: this stack's backward needs tanh saved (wn_stack_saves_tanh)");
     WN_CHECK_ARG(t_off >= 0 && t_off < T, "wn_stack_fwd: t_off outside [0,T)");
+    if ((rc = check_bias_tables(__func__, d, ex, d->bf, d->bg, "bf and bg"))) return rc;
+    const bool per_clip = c.bias_per_clip();
     const size_t n = (size_t)B * T;
     const int L = d->n_layers;
     std::vector<const float*> zp(L);
@@ -103,12 +114,20 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
     }
     // fp16 x 2 split products (WN_GEMM_FP16X2): 32-channel layers without conv / projection biases run the f16-MFMA form
     // of the fused kernel on weight images split once for the whole stack (into the call's scratch: the skip
-    // contraction re-uses it after the last layer)
+    // contraction re-uses it after the last layer).  Per-clip gate biases (WN_EXEC_BIAS_PER_CLIP) are admitted: the COND
+    // form of the per-layer kernel adds them behind the rescale; a projection bias still disqualifies.
     const void* h2img = nullptr;
     if (c.fp16x2() && L <= 64 && d->Cr == 32 && d->fw == 2 && c.has_scratch(mfma_layer_h2_image_bytes(L))) {
         bool ok = true;
         for (int l = 0; l < L && ok; ++l)
-            ok = d->cd[l] == 32 && !(d->bf && d->bf[l]) && !(d->bg && d->bg[l]) && !(d->bp && d->bp[l]);
+            ok = d->cd[l] == 32 && (per_clip || (!(d->bf && d->bf[l]) && !(d->bg && d->bg[l]))) && !(d->bp && d->bp[l]);
+        if (ok && per_clip) {          // the COND kernels load a lane's biases as float4: refused here, never another path
+            WN_CHECK_ARG(c.bias_stride % 4 == 0, "wn_stack_fwd: the fp16 x 2 layers need a bias row stride that is a multiple "
+                                                 "of 4 floats (got %lld)", c.bias_stride);
+            for (int l = 0; l < L; ++l)
+                WN_CHECK_ARG(((reinterpret_cast<uintptr_t>(d->bf[l]) | reinterpret_cast<uintptr_t>(d->bg[l])) & 15) == 0,
+                             "wn_stack_fwd: the fp16 x 2 layers need 16-byte aligned bias rows (layer %d)", l);
+        }
         if (ok) {
             // (a READY step plan built the images at the start of the step: plan.hip)
             h2img = plan_layer_h2_images(c, L, d->Wf, d->Wg, d->Wp);
@@ -129,7 +148,8 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
             // (fp16 x 2 only.  The same group on exact fp32 MFMA -- k_layer_fwd_f32_grp, round 6 -- was built, bit-identical to
             // the per-layer launches, and 3.5 % SLOWER on the bf16x3 step (3.844 against 3.712 ms, same box): 80 fp32 MFMAs per
             // tile-layer are MFMA-bound at the per-layer kernel's 16 waves per CU already, and the halo tile adds 12.5 %)
-            int ng = (h2img && !c.flag(WN_EXEC_NO_FWD_GROUPS) && mfma_layer_fwd_h2_ok(c, B, T, 0))
+            // (per-clip biases: every layer its own launch -- k_layer_fwd_h2_grp sits at its register limit and has no COND form)
+            int ng = (h2img && !per_clip && !c.flag(WN_EXEC_NO_FWD_GROUPS) && mfma_layer_fwd_h2_ok(c, B, T, 0))
                          ? mfma_layer_fwd_group_len(d->dilation, l, L) : 0;
             for (int k = 0; k < ng; ++k)
                 if (live[l + k] > 0) ng = 0;
@@ -157,7 +177,8 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
             if (h2img && mfma_layer_fwd_h2_ok(c, B, T, live[l])) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd_h2(in, h2img, l, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr, B, T,
-                                       d->dilation[l], Z, live[l], as_stream(stream));
+                                       d->dilation[l], Z, live[l], as_stream(stream), per_clip ? d->bf[l] : nullptr,
+                                       per_clip ? d->bg[l] : nullptr, c.bias_stride);
             } else if (live[l] > 0 || g_only) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd(c, in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr,
@@ -191,6 +212,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
     if (rc || (rc = check_desc(d)) || (rc = check_layers(d, dskip != nullptr))) return rc;
     WN_CHECK_ARG(x && xs && z && g && ws && dWf && dWg && dWp, "wn_stack_bwd: NULL argument");
     WN_CHECK_ARG(B > 0 && T > 0 && t_off >= 0 && t_off < T, "wn_stack_bwd: non-positive size or t_off outside [0,T)");
+    if ((rc = check_bias_tables(__func__, d, ex, dbf, dbg, "dbf and dbg"))) return rc;
     Call c(ex);
     // ---- chained path: every layer on the MFMA kernels and no conv / projection bias GRADIENTS asked for.  It is the only
     // path that recovers tanh from z / sigmoid, so f may be NULL exactly when it is taken (a desc without biases but with

@@ -17,12 +17,22 @@
 
 namespace wn {
 
+// bf / bg != NULL (WN_EXEC_BIAS_PER_CLIP): clip b's bias row, bias_stride floats apart, is added to the pre-activations here --
+// the GEMMs in front then ran without a bias
 __global__ void k_wide_gate(float* __restrict__ a, float* __restrict__ g, float* __restrict__ z, float* __restrict__ fs,
-                            float* __restrict__ gs, long long n4, int T, int Cd, int Z) {
+                            float* __restrict__ gs, long long n4, int T, int Cd, int Z, const float* __restrict__ bf,
+                            const float* __restrict__ bg, long long bias_stride) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // float4 index
     if (i >= n4) return;
-    const int t = (int)((i * 4 / Cd) % T);
+    const long long bt = i * 4 / Cd;
+    const int t = (int)(bt % T);
     float4 av = reinterpret_cast<const float4*>(a)[i], gv = reinterpret_cast<const float4*>(g)[i];
+    if (bf) {
+        const float* rf = bf + (bt / T) * bias_stride + (i * 4 - bt * Cd);
+        const float* rg = bg + (bt / T) * bias_stride + (i * 4 - bt * Cd);
+        av.x += rf[0]; av.y += rf[1]; av.z += rf[2]; av.w += rf[3];
+        gv.x += rg[0]; gv.y += rg[1]; gv.z += rg[2]; gv.w += rg[3];
+    }
     if (t < Z) { av = make_float4(0, 0, 0, 0); gv = av; }                      // reference zero prefix
     const float4 f = make_float4(fast_tanh(av.x), fast_tanh(av.y), fast_tanh(av.z), fast_tanh(av.w));
     const float4 s = make_float4(fast_sigmoid(gv.x), fast_sigmoid(gv.y), fast_sigmoid(gv.z), fast_sigmoid(gv.w));
@@ -75,7 +85,8 @@ int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, co
                    int d, int Z, hipStream_t s) {
     // pre-activations go where f / sigmoid(g) will live (training) or into z / out (inference, needs Cd <= Cr)
     int rc;
-    if (c.split_b3() && Cd % 64 == 0) {
+    const bool per_clip = c.bias_per_clip();     // the GEMM epilogues add one bias row to every column: per-clip rows go through k_wide_gate
+    if (!per_clip && c.split_b3() && Cd % 64 == 0) {
         // one launch for both convolutions and the gate: the rows of Wf and Wg interleaved tile by tile, tanh / sigmoid /
         // product in the epilogue -- x is read once per tap, the pre-activations never reach memory
         CGArgs a{};
@@ -103,12 +114,13 @@ int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, co
     float* abuf = fs ? fs : z;
     float* gbuf = gs ? gs : out;
     if (!gs && Cd > Cr) { wn::set_error("wide_layer_fwd: inference needs Cd <= Cr"); return WN_ESHAPE; }
-    rc = conv_gemm(c, x, Wf, bf, abuf, B, T, Cr, Cd, fw, d, s);
+    rc = conv_gemm(c, x, Wf, per_clip ? nullptr : bf, abuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
-    rc = conv_gemm(c, x, Wg, bg, gbuf, B, T, Cr, Cd, fw, d, s);
+    rc = conv_gemm(c, x, Wg, per_clip ? nullptr : bg, gbuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
     const long long n4 = (long long)B * T * Cd / 4;
-    hipLaunchKernelGGL(k_wide_gate, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z);
+    hipLaunchKernelGGL(k_wide_gate, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z,
+                       per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride);
     WN_LAUNCH_CHECK();
     CGArgs a{};
     base_args(a, B, T);
@@ -197,8 +209,12 @@ static int wide_layer_bwd_256(Call& c, const float* x, const float* f, const flo
         a.nB = B; a.rows_A_per_b = T; a.rows_B_per_b = T; a.off = 0; a.act = WN_ACT_NONE;
         if ((rc = launch_wgrad(c, a, Cr, s))) return rc;
     }
-    if (dbf && (rc = generic_colsum(dadg, B, T, 0, 2 * Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
-    if (dbg && (rc = generic_colsum(dadg + Cd, B, T, 0, 2 * Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (c.bias_per_clip()) {
+        if ((rc = generic_colsum_per_clip(dadg, dadg + Cd, 2 * Cd, B, T, 0, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+    } else {
+        if (dbf && (rc = generic_colsum(dadg, B, T, 0, 2 * Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
+        if (dbg && (rc = generic_colsum(dadg + Cd, B, T, 0, 2 * Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    }
     if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }
@@ -253,8 +269,12 @@ int wide_layer_bwd(Call& c, const float* x, const float* f, const float* g, cons
             if ((rc = launch_wgrad(c, a, Cr, s))) return rc;
         }
     }
-    if (dbf && (rc = generic_colsum(da, B, T, 0, Cd, Cd, dbf, c.ws, c.room(), s))) return rc;     // da, dg are already 0 for t < Z
-    if (dbg && (rc = generic_colsum(dg, B, T, 0, Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    if (c.bias_per_clip()) {                                                                       // da, dg are already 0 for t < Z
+        if ((rc = generic_colsum_per_clip(da, dg, Cd, B, T, 0, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+    } else {
+        if (dbf && (rc = generic_colsum(da, B, T, 0, Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
+        if (dbg && (rc = generic_colsum(dg, B, T, 0, Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
+    }
     if (dbp && dout && (rc = generic_colsum(dout, B, T, 0, Cr, Cr, dbp, c.ws, c.room(), s))) return rc;
     return WN_OK;
 }

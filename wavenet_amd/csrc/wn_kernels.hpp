@@ -7,6 +7,8 @@ namespace wn {
 // ---- one entry-point call: its WnExec resolved once by the entry point and handed down the host-side call tree ----------
 struct StepPlan;
 int check_precision(const char* fn, const WnExec* ex);   // WN_EARG + error text unless ex is NULL or its precision is 0 .. 3
+// WN_EXEC_BIAS_PER_CLIP: WN_EARG + error text unless the stride covers a row of Cd floats and both rows are given
+int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f, const void* row_g, const char* names);
 struct Call {
     explicit Call(const WnExec* ex);     // ex == NULL: bf16x3, no flags, no scratch, no plan
     int precision;                       // WN_GEMM_*; WN_GEMM_FP32 under WN_EXEC_FORCE_GENERIC
@@ -15,9 +17,11 @@ struct Call {
     size_t ws_bytes;
     int fwd_t1_min_blocks;               // WnExec.fwd_t1_min_blocks with the default (512) filled in
     StepPlan* plan;                      // WnExec.plan, or NULL
+    long long bias_stride;               // WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bf / bg (dbf / dbg) rows; else 0
 
     static constexpr size_t kTail = 256;
     bool flag(unsigned f) const { return (flags & f) != 0; }
+    bool bias_per_clip() const { return flag(WN_EXEC_BIAS_PER_CLIP); }
     bool generic() const { return flag(WN_EXEC_FORCE_GENERIC); }
     bool split_b3() const { return precision != WN_GEMM_FP32; }   // the bf16-split GEMM kernels (every precision but fp32)
     bool one_term() const { return precision == WN_GEMM_BF16; }
@@ -66,7 +70,7 @@ int generic_conv_bwd(const float*, const float*, const float*, float*, float*, f
                      int, int, hipStream_t);
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s);
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0);
 int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
@@ -124,8 +128,10 @@ size_t mfma_layer_h2_image_bytes(int L);
 int mfma_layer_pack_h2(int L, const float* const* Wf, const float* const* Wg, const float* const* Wp, void* img,
                        hipStream_t s);
 bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live);
+// bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, bias_stride % 4 == 0), the COND kernels
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
-                      int d, int Z, int t_live, hipStream_t s);
+                      int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr,
+                      long long bias_stride = 0);
 int mfma_layer_fwd_group_len(const int* dil, int l0, int L);   // layers from l0 on that one group launch can chain
 int mfma_layer_fwd_h2_group(const float* x, const void* img, int l0, int nl, float* const* outs, float* const* zs,
                             float* const* fs, float* const* gs, const int* dil, const int* Zs, int B, int T, hipStream_t s);
@@ -136,7 +142,9 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
 // ---- mfma_layer_bwd.hip: backward of the same shape; bias gradients come from the scratch -----
 int mfma_layer_bwd(const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                    const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dWg,
-                   float* dWp, float* dab, int B, int T, int d, int Z, hipStream_t s);
+                   float* dWp, float* dab, int B, int T, int d, int Z, hipStream_t s, bool fixed_order = false);
+// (fixed_order: the workgroups' partial weight-gradient tiles are summed without atomics -- bit-reproducible; what a call
+// with per-clip bias rows asks for)
 size_t mfma_layer_bwd_extra_ws_floats();
 // Chained backward of the fused layer (mfma_layer_bwd.hip).  dout[t] = Vin[t] + Uin[t + dU], rows below vu_t0 taken as
 // 0; dzs (may be NULL) is dz_skip for columns t >= dz_t0; columns below t_live are not computed.
@@ -158,6 +166,10 @@ int mfma_chain_reduce_all(const float* part, int L, const int* nwg, float* const
 int mfma_chain_combine(const float* V, const float* U, float* dx, int B, int T, int dU, int vu_t0, hipStream_t s);
 int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout, float* dbf, float* dbg, float* dbp, int B,
                              int T, int Cr, int Cd, int Z, hipStream_t s);
+// WN_EXEC_BIAS_PER_CLIP: dbf[b * stride + m] += sum_{t in [tmin, T)} da[(b T + t) lda + m], dbg likewise from dg, m < Cd: one
+// launch for both gates, the summation order of the shared-bias column sums of a B = 1 call, no atomics, no scratch
+int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
+                            long long stride, hipStream_t s);
 
 // ---- wide_layer.hip: residual layer for any Cr, Cd multiple of 32 and any fw, composed from the channel GEMMs
 bool wide_layer_supported(int Cr, int Cd, int fw);

@@ -40,18 +40,22 @@ class _RingState(object):
 class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
 
-    def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32"):
+    def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
+                 condition_classes: int = 0, condition_channels: int = 0):
         self._dec = None
         self._dec_keep = None
         self._dec_stale = True
+        self._dec_class = None             # globally conditioned model: the class whose folded biases the handle holds
         self._batch_decs = []              # decoder handles of generate_batch (one per utterance), created on demand
         self._batch_stale = []
+        self._batch_class = []
         self.prev_causal_outputs = None
         self.prev_residual_outputs = None
         self.keep_window = True            # keep the logits of the whole window on the device: _forward_one_step's reference shape
         self._hist = None                  # (W, Q) ring of ELU-head logits, oldest column at _hist_pos
         self._hist_pos = 0
-        super().__init__(params, compat_zero_prefix=compat_zero_prefix, seed=seed, storage=storage)
+        super().__init__(params, compat_zero_prefix=compat_zero_prefix, seed=seed, storage=storage,
+                         condition_classes=condition_classes, condition_channels=condition_channels)
 
     def __del__(self):
         try:
@@ -68,7 +72,10 @@ class FasterWaveNet(WaveNet):
         self._batch_stale = [True] * len(getattr(self, "_batch_decs", []))
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self):
+    def _desc(self, cond=None):
+        """``cond``: [(bf, bg)] per residual layer (``condition_biases``) -- a globally conditioned model's handle holds ONE
+        class's folded gate biases, copied like any bias at create / update time.  Biased layers select the any-shape decoder
+        (one workgroup per utterance): a conditioned model of config 4's shape does not get the nine-workgroup kernel."""
         p = self.params
         L = self._flat_layers
         keep = dict(
@@ -82,6 +89,8 @@ class FasterWaveNet(WaveNet):
             Ws=ptr_array([l.projection_softmax.W for l in L]), bs=ptr_array([l.projection_softmax.b for l in L]),
             head_W=ptr_array([l.W for l in self.softmax_conv_layers]),
             head_b=ptr_array([l.b for l in self.softmax_conv_layers]))
+        if cond is not None:
+            keep.update(bf=ptr_array([b[0] for b in cond]), bg=ptr_array([b[1] for b in cond]), cond=cond)
         d = _lib.WnDecoderDesc()
         d.Q, d.fw_causal, d.n_causal = p.quantization_steps, p.causal_conv_filter_width, len(p.causal_conv_channels)
         d.fw, d.n_blocks, d.n_layers = p.residual_conv_filter_width, p.residual_num_blocks, len(p.residual_conv_channels)
@@ -93,41 +102,62 @@ class FasterWaveNet(WaveNet):
         d.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         return d, keep
 
-    def _decoder(self):
+    def _class_id(self, condition):
+        """``condition=`` of the batch-1 methods (an id, or a sequence holding one) -> int, or None for an unconditioned model."""
+        if condition is not None and np.ndim(condition) > 0:
+            c = np.asarray(condition).reshape(-1)
+            if c.size != 1:
+                raise Exception("one utterance takes ONE class id, got %d" % c.size)
+            condition = c[0]
+        ids = self._condition_ids(None if condition is None else [int(condition)], 1)
+        return None if ids is None else int(condition)
+
+    def _decoder(self, class_id=None):
+        """The batch-1 handle; for a conditioned model holding ``class_id``'s biases (default: the class it holds already)."""
         lib = _lib.lib()
+        if self.condition_classes and class_id is None:
+            class_id = self._dec_class
+            if class_id is None:
+                raise Exception("this model is globally conditioned: prefill with condition= first")
+        cond = None
+        if self.condition_classes and (self._dec is None or self._dec_stale or self._dec_class != class_id):
+            cond = self.condition_biases(class_id)
         if self._dec is None:
-            d, keep = self._desc()
+            d, keep = self._desc(cond)
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
-            self._dec, self._dec_stale = h, False
-        elif self._dec_stale:
-            d, keep = self._desc()
+            self._dec, self._dec_stale, self._dec_class = h, False, class_id
+        elif self._dec_stale or self._dec_class != class_id:
+            d, keep = self._desc(cond)
             check(lib.wn_decoder_update_weights(self._dec, C.byref(d), stream_ptr()), "wn_decoder_update_weights")
-            self._dec_stale = False
+            self._dec_stale, self._dec_class = False, class_id
         return self._dec
 
     # -- the reference's face -------------------------------------------------------------------
-    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False):
-        """Full forward over the window that also seeds the decoder state (faster_wavenet.py:13-47)."""
+    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None):
+        """Full forward over the window that also seeds the decoder state (faster_wavenet.py:13-47).  ``condition``: the
+        utterance's class id (globally conditioned models): the prefill runs the ordinary forward with it and the decoder
+        handle is created or updated with that class's folded biases."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
         if x.shape[0] != 1:
             raise Exception("FasterWaveNet generates one utterance at a time (batch 1), like the reference")
+        class_id = self._class_id(condition)
         storage, self.storage = self.storage, "fp32"               # the decoder state is seeded from fp32 activations
         try:
-            return self._prefill(x, apply_softmax, as_numpy)
+            return self._prefill(x, apply_softmax, as_numpy, class_id)
         finally:
             self.storage = storage
 
-    def _prefill(self, x, apply_softmax, as_numpy):
+    def _prefill(self, x, apply_softmax, as_numpy, class_id=None):
         with torch.no_grad():
             causal_output = self.forward_causal_block(x)
-            _, sum_skip = self.forward_residual_block(causal_output)
+            _, sum_skip = self.forward_residual_block(causal_output, condition=None if class_id is None else [class_id])
             out = self.forward_softmax_block(sum_skip, apply_softmax=apply_softmax)
             self._last_sum_skip = sum_skip                                       # generate(): the first row under a temperature
             tokens = (x if not x.is_floating_point() else x[:, :, 0, :].argmax(dim=1)).to(torch.int32).contiguous()
             W = tokens.shape[1]
-            dec = self._decoder()
+            dec = self._decoder(class_id)
             check(_lib.lib().wn_decoder_load_state(
                 dec, ptr(tokens), W, ptr_array([t.contiguous() for t in self._last_causal_outputs]),
                 ptr_array(self._last_layer_inputs), stream_ptr()), "wn_decoder_load_state")
@@ -214,7 +244,7 @@ class FasterWaveNet(WaveNet):
         return out
 
     def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False,
-                 temperature=1.0, top_k=0, top_p=1.0):
+                 temperature=1.0, top_k=0, top_p=1.0, condition=None):
         """Emit ``n_samples`` tokens.  Step 1 is the full forward over the initial window (ReLU head,
         like the reference's first ``_forward_one_step`` call); steps 2.. run inside one persistent
         kernel with the ELU head.  ``uniforms[i]`` is the float64 draw numpy's ``choice`` would make
@@ -222,10 +252,14 @@ class FasterWaveNet(WaveNet):
 
         ``temperature`` / ``top_k`` / ``top_p`` (off at 1 / 0 / 1; the rule is wavenet_amd/sampling.py's) act on every
         draw, on the device; ``return_probs`` then holds the post-temperature, pre-truncation rows.  With all three off the
-        run is the one it was before they existed, bit for bit."""
+        run is the one it was before they existed, bit for bit.
+
+        ``condition``: the class id (speaker) of a globally conditioned model.  Tokens and probabilities are those of an
+        ordinary biased model holding ``condition_biases(condition)``, bit for bit."""
         p = self.params
         Q = p.quantization_steps
         iw = self.input_width
+        class_id = self._class_id(condition)
         sampling.check_controls(temperature, top_k, top_p)
         top_k, top_p = int(top_k), float(top_p)
         if initial_tokens is None:
@@ -238,7 +272,7 @@ class FasterWaveNet(WaveNet):
         self.prev_causal_outputs = None
         keep, self.keep_window = self.keep_window, False             # the run below never builds the window (and drops it)
         try:
-            p0 = self.forward_one_step(tok, apply_softmax=True)      # (1,Q,1,W)
+            p0 = self.forward_one_step(tok, apply_softmax=True, condition=class_id)      # (1,Q,1,W)
         finally:
             self.keep_window = keep
         first_prob = self._first_row(self._last_sum_skip, p0, temperature)
@@ -273,7 +307,8 @@ class FasterWaveNet(WaveNet):
                 len(p.causal_conv_channels) == 1 and p.causal_conv_filter_width == 2 and p.residual_conv_filter_width == 2 and
                 self._Cr == 32 and self._Cs == 256 and list(p.softmax_conv_channels) == [256, 256] and len(L) <= 128 and
                 all(int(c) == 32 for c in p.residual_conv_channels) and self.causal_conv_layers[0].bshape is None and
-                all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)))
+                all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)) and
+                not self.condition_classes)          # a conditioned model's handles hold gate biases: the any-shape decoder
 
     def _batch_prompts(self, initial_tokens, N):
         """``generate_batch``'s ``initial_tokens`` -> (the distinct windows, 1-D int32 each; the window index of every
@@ -305,7 +340,8 @@ class FasterWaveNet(WaveNet):
             which.append(seen[k])
         return prompts, which
 
-    def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0):
+    def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
+                       condition=None):
         """``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
         (N, n_samples) int32 tokens on the device.  ``initial_tokens``: None (silence), one 1-D window for every utterance, or
         an (N, W) integer array -- a prompt per utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a
@@ -319,7 +355,13 @@ class FasterWaveNet(WaveNet):
         causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``).  More utterances run as several launches, one after
         another.  Step 1 -- the full forward over the window, at batch 1 exactly as ``generate`` runs it -- runs once per
         DISTINCT window.  What still runs as a loop over ``generate()``, decided before any work: ``WN_DECODER_ONE_WORKGROUP``,
-        ``n_samples == 2`` on the nine-workgroup form, and a device the nine-workgroup launch does not fit."""
+        ``n_samples == 2`` on the nine-workgroup form, and a device the nine-workgroup launch does not fit.
+
+        ``condition`` (globally conditioned models): one class id for all utterances or one each -- a voice per utterance.
+        Every handle owns its packed weights, so utterance u's handle simply holds ``condition_biases(condition[u])``; such
+        handles are any-shape ones (one workgroup per utterance, up to 1,024 per launch -- a conditioned model of config 4's
+        shape does not get the nine-workgroup kernel), one prefill runs per distinct (window, class) pair, and
+        ``same_weights`` is 0 when the ids differ."""
         p = self.params
         Q = p.quantization_steps
         u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
@@ -337,43 +379,54 @@ class FasterWaveNet(WaveNet):
         if N < 1:
             raise Exception("generate_batch: no utterance")
         prompts, which = self._batch_prompts(initial_tokens, N)
+        if self.condition_classes:
+            if condition is None:
+                self._condition_ids(None, N)                                      # raises: a conditioned model needs ids
+            cids = [self._class_id(c) for c in sampling.per_utterance(condition, N, "condition")]
+        else:
+            self._condition_ids(condition, N)                                     # raises when ids were given
+            cids = [None] * N
         # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
         # decided BEFORE any work is done
         flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         nine = self._nine_workgroup_shape(flags)
         if nine and (n_samples == 2 or flags & _lib.WN_DECODER_ONE_WORKGROUP):
-            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps)
+            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids)
         limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
         u = torch.as_tensor(u_np).to(self.device)
         run = n_samples > 1
+        biases = {c: self.condition_biases(c) for c in sorted(set(cids))} if run and self.condition_classes else {None: None}
         while run and len(self._batch_decs) < N:
-            d, keep = self._desc()
+            c = cids[len(self._batch_decs)]
+            d, keep = self._desc(biases[c])
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
             self._batch_decs.append(h)
             self._batch_stale.append(False)
+            self._batch_class.append(c)
         for i in range(N if run else 0):
-            if self._batch_stale[i]:
-                d, keep = self._desc()
+            if self._batch_stale[i] or self._batch_class[i] != cids[i]:
+                d, keep = self._desc(biases[cids[i]])
                 check(lib.wn_decoder_update_weights(self._batch_decs[i], C.byref(d), stream_ptr()), "wn_decoder_update_weights")
-                self._batch_stale[i] = False
+                self._batch_stale[i], self._batch_class[i] = False, cids[i]
             check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
         # one prefill per distinct window, at batch 1 as generate() runs it; the decoder states of its utterances are seeded
         # from it, and its first row (one per distinct temperature) is what generate() draws the first token from
         self.prev_causal_outputs = None
         rows = {}
-        for k, prompt in enumerate(prompts):
+        for k, cid in sorted({(which[i], cids[i]) for i in range(N)}, key=lambda kc: (kc[0], -1 if kc[1] is None else kc[1])):
+            prompt = prompts[k]
             tok = torch.as_tensor(prompt.reshape(1, -1)).to(self.device)
             storage, self.storage = self.storage, "fp32"
             try:
                 with torch.no_grad():
                     causal_output = self.forward_causal_block(tok)
-                    _, sum_skip = self.forward_residual_block(causal_output)
+                    _, sum_skip = self.forward_residual_block(causal_output, condition=None if cid is None else [cid])
                     p0 = self.forward_softmax_block(sum_skip, apply_softmax=True)
             finally:
                 self.storage = storage
             tokens = tok.to(torch.int32).contiguous()
-            mine = [i for i in range(N) if which[i] == k]
+            mine = [i for i in range(N) if which[i] == k and cids[i] == cid]
             if run:
                 causal_outs = ptr_array([t.contiguous() for t in self._last_causal_outputs])
                 layer_ins = ptr_array(self._last_layer_inputs)
@@ -381,16 +434,16 @@ class FasterWaveNet(WaveNet):
                     check(lib.wn_decoder_load_state(self._batch_decs[i], ptr(tokens), tokens.shape[1], causal_outs, layer_ins,
                                                     stream_ptr()), "wn_decoder_load_state")
             for t in sorted({temps[i] for i in mine}):
-                rows[(k, t)] = self._first_row(sum_skip, p0, t)
+                rows[(k, cid, t)] = self._first_row(sum_skip, p0, t)
         out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
         first = torch.empty((N,), device=self.device, dtype=torch.int32)
         u0 = u[:, 0].contiguous()
         if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
-            first_prob = torch.cat([rows[(which[i], temps[i])] for i in range(N)], dim=0).contiguous()
+            first_prob = torch.cat([rows[(which[i], cids[i], temps[i])] for i in range(N)], dim=0).contiguous()
             check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
         else:
             for i in range(N):                                       # the truncation per utterance, as generate() draws
-                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
+                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], cids[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
                                                          Q, top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
         out[:, 0] = first
         if run:
@@ -399,13 +452,15 @@ class FasterWaveNet(WaveNet):
             # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
             outs = [torch.empty((n_samples - 1,), device=self.device, dtype=torch.int32) if nine else out[i, 1:] for i in range(N)]
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
+            if len(set(cids)) > 1:
+                same = 0                                              # ... but hold different classes' biases
             for c0 in range(0, N, limit):                             # launches of at most `limit`, one after another
                 c1 = min(N, c0 + limit)
                 rc = lib.wn_decoder_run_batch((C.c_void_p * (c1 - c0))(*[h.value for h in self._batch_decs[c0:c1]]), c1 - c0,
                                               (C.c_int32 * (c1 - c0))(*firsts[c0:c1]), ptr_array(rest[c0:c1]), n_samples - 1,
                                               ptr_array(outs[c0:c1]), None, same, stream_ptr())
                 if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
-                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps)
+                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids)
                 check(rc, "wn_decoder_run_batch")
             for i in range(N if nine else 1):                         # any-shape: nothing can give up; one synchronise
                 check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
@@ -414,9 +469,9 @@ class FasterWaveNet(WaveNet):
                     out[i, 1:] = outs[i]
         return out
 
-    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p):
+    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p, cids):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
         ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls by
         definition)."""
         return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=prompts[which[i]], temperature=temperature[i],
-                                          top_k=top_k[i], top_p=top_p[i]) for i in range(u_np.shape[0])])
+                                          top_k=top_k[i], top_p=top_p[i], condition=cids[i]) for i in range(u_np.shape[0])])

@@ -8,7 +8,10 @@ on the stream our C-ABI calls are issued on) and replayed, the step is one graph
 What changes from step to step lives in device memory, never in kernel arguments:
   * the batch: copied into the graph's static input buffers;
   * Adam's bias-corrected step size alpha_t: a device scalar written before each replay (``wn_adam_step_dev``);
-  * the rate 1 - decay_t of the weight average (``WaveNet.enable_ema``), likewise.
+  * the rate 1 - decay_t of the weight average (``WaveNet.enable_ema``), likewise;
+  * the class ids of a globally conditioned model: a static buffer next to the batch's.  The conditioning node and the
+    per-clip bias rows it feeds are captured with the step; the step plan holds weight images only, never a bias pointer, so a
+    conditioned step runs WITH the plan.
 With data parallelism the gradient all-reduce stays OUTSIDE the graphs (forward+backward graph -> RCCL all-reduce ->
 optimiser graph), so nothing here depends on capturing a collective.
 """
@@ -20,11 +23,12 @@ from . import _lib
 from .ema import ema_rate_at
 
 
-def default_loss(net, x, tgt, window_only: bool = False):
+def default_loss(net, x, tgt, window_only: bool = False, condition=None):
     """train_audio/train.py:60-75: loss over the last ``tgt.shape[1]`` columns of the window.  ``window_only`` also skips
-    the columns that window cannot see (WaveNet.forward_residual_block); same loss, same gradients."""
+    the columns that window cannot see (WaveNet.forward_residual_block); same loss, same gradients.  ``condition``: one class
+    id per clip, for a globally conditioned model."""
     c = net.forward_causal_block(x)
-    _, s = net.forward_residual_block(c, t_off=x.shape[1] - tgt.shape[1], window_only=window_only)
+    _, s = net.forward_residual_block(c, t_off=x.shape[1] - tgt.shape[1], window_only=window_only, condition=condition)
     # forward_softmax_block(apply_softmax=False) + cross_entropy, the last head convolution and the loss in one launch where covered
     return net.head_cross_entropy(s, tgt)
 
@@ -33,14 +37,17 @@ class TrainStepGraph(object):
     """``g = TrainStepGraph(net, x, tgt); loss = g.step(x, tgt)`` -- same result as
     ``net.backprop(default_loss(net, x, tgt))`` for batches of the captured shape."""
 
-    def __init__(self, net, x, tgt, loss_fn=default_loss, warmup: int = 2, keep_graph: bool = False):
+    def __init__(self, net, x, tgt, loss_fn=default_loss, warmup: int = 2, keep_graph: bool = False, condition=None):
         """``keep_graph``: keep the captured hipGraph_t next to the executable graph so that :meth:`node_counts` can walk it
-        (measurement aid: bench.py counts the kernel nodes of the step it times)."""
+        (measurement aid: bench.py counts the kernel nodes of the step it times).  ``condition``: one class id per clip for a
+        globally conditioned model; ``loss_fn`` is then called with ``condition=`` the static id buffer."""
         if not (net.gpu_enabled and x.is_cuda and tgt.is_cuda):
             raise _lib.WaveNetHipError("TrainStepGraph needs the network and the batch on a HIP device")
         self.net, self.loss_fn = net, loss_fn
         self.x = x.clone()
         self.tgt = tgt.clone()
+        ids = net._condition_ids(condition, int(x.shape[0]))          # raises when the model and the argument disagree
+        self.condition = None if ids is None else ids.clone()
         opt = net.optimizer
         self._lr = torch.zeros((1,), device=x.device, dtype=torch.float32)
         self._ema_rate = torch.zeros((1,), device=x.device, dtype=torch.float32)      # 0: the warm-up steps leave the average alone
@@ -128,7 +135,10 @@ class TrainStepGraph(object):
             self.net._unit_upstream = False
 
     def _fwd_bwd_body(self):
-        loss = self.loss_fn(self.net, self.x, self.tgt)
+        if self.condition is None:
+            loss = self.loss_fn(self.net, self.x, self.tgt)
+        else:
+            loss = self.loss_fn(self.net, self.x, self.tgt, condition=self.condition)
         # the upstream gradient of the loss is a tensor made ONCE (in the warm-up pass, outside the capture): `loss.backward()`
         # would fill a fresh one in every replay -- a kernel at the launch floor (4.6 us) for one float
         if self._one is None or self._one.shape != loss.shape:
@@ -142,9 +152,10 @@ class TrainStepGraph(object):
             self.net._ema_step(rate_dev=self._ema_rate)
         self.net._weights_changed()
 
-    def step(self, x=None, tgt=None):
+    def step(self, x=None, tgt=None, condition=None):
         """One training step on (x, tgt) (default: the batch already in the static buffers).  Returns the loss
-        (a device scalar that the next step overwrites)."""
+        (a device scalar that the next step overwrites).  ``condition``: the clips' class ids (conditioned models; default: the
+        ids already in the static buffer)."""
         net, opt = self.net, self.net.optimizer
         if self._hyper() != self._snap:
             raise _lib.WaveNetHipError(
@@ -156,6 +167,10 @@ class TrainStepGraph(object):
             self.x.copy_(x, non_blocking=True)
         if tgt is not None:
             self.tgt.copy_(tgt, non_blocking=True)
+        if condition is not None:
+            if self.condition is None:
+                raise _lib.WaveNetHipError("condition= was given, but the captured step is unconditioned")
+            self.condition.copy_(self.net._condition_ids(condition, int(self.x.shape[0])), non_blocking=True)
         opt.t += 1                                   # update() is not called on replay: keep Adam's clock here
         self._lr.fill_(opt.lr)
         if net.ema_enabled:                          # the schedule's clock, like Adam's: it also advances for a step skipped on the device

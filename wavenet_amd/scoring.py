@@ -61,8 +61,9 @@ def summarize(nll) -> Dict[str, float]:
     return {"samples": int(a.size), "nats_per_sample": nats, "bits_per_sample": nats / math.log(2.0)}
 
 
-def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8):
-    """(n,) float32 on the device: see the module text.  ``tokens``: a 1-D integer numpy array or tensor."""
+def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None):
+    """(n,) float32 on the device: see the module text.  ``tokens``: a 1-D integer numpy array or tensor.  ``condition``: the
+    class id of the sequence (every piece of it), for a globally conditioned model."""
     import torch
     t = net.to_variable(np.asarray(tokens) if not isinstance(tokens, torch.Tensor) else tokens)
     if t.dim() != 1 or t.is_floating_point():
@@ -70,6 +71,9 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8):
     if not t.is_cuda:
         raise Exception("score: the network is not on a HIP device (call to_gpu() first)")
     n = int(t.shape[0])
+    if condition is not None and np.ndim(condition) != 0:
+        raise Exception("score: condition must be ONE class id (the sequence is one clip)")
+    net._condition_ids(None if condition is None else [int(condition)], 1)      # raises on a mismatch before any work
     out = torch.empty((n,), device=t.device, dtype=torch.float32)
     C = context_width(net.params)
     t = t.to(torch.int32)
@@ -79,5 +83,6 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8):
         # piece (start, w): inputs s[start : start + C - 1 + w]; output column C - 1 + k predicts s[start + C + k] = tokens[start + k]
         x = torch.stack([s[a:a + C - 1 + w] for a, _ in launch])
         tgt = torch.stack([t[a:a + w] for a, _ in launch])
-        out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt).reshape(-1)
+        cond = None if condition is None else [int(condition)] * len(launch)
+        out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt, condition=cond).reshape(-1)
     return out

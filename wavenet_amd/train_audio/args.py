@@ -42,6 +42,15 @@ _EMA_FLAGS = (
                                       "files (and, with --ema-decay, that of the averaged weights)"),
     (("--ema",), None, False, "generate: use the checkpoint's averaged weights (wavenet.ema.npz)"),
 )
+# global conditioning on a speaker label (WaveNet(..., condition_classes, condition_channels); train_audio/speakers.py): all
+# off, and -- like the flags above -- attributes of the namespace only when given
+_SPEAKER_FLAGS = (
+    (("--speaker-prefix",), None, False, "train: condition on the speaker, a file's base name up to the first '_' "
+                                         "(p225_001.wav -> p225); the label table goes to <model-dir>/speakers.json"),
+    (("--condition-channels",), int, None, "train --speaker-prefix: width H of the learned speaker embedding"),
+)
+_SPEAKER_HELP = ("generate: the speaker label to generate as (a conditioned checkpoint needs one); repeatable: one label for all "
+                 "utterances, or one per utterance")
 _PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation instead of silence; repeatable: one file for "
                 "all utterances, or one per utterance")
 
@@ -49,6 +58,7 @@ _PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation 
 class Args(argparse.Namespace):
     """What :func:`parse` returns: the defaults of ``_EMA_FLAGS`` live here, not in the instance."""
     ema_decay, valid_wav_dir, ema = 0.0, None, False
+    speaker_prefix, condition_channels, speaker = False, None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -58,13 +68,14 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=argparse.SUPPRESS, help=text + " (default: %r)" % (default,))
     ap.add_argument("--prompt", action="append", default=None, metavar="FILE.wav", help=_PROMPT_HELP)
+    ap.add_argument("--speaker", action="append", default=argparse.SUPPRESS, metavar="LABEL", help=_SPEAKER_HELP)
     return ap
 
 
@@ -91,4 +102,14 @@ def parse(argv=None):
         ap.error(str(e))
     if not (0.0 <= args.ema_decay < 1.0):
         ap.error("--ema-decay must lie in [0, 1), got %r" % (args.ema_decay,))
+    if args.speaker_prefix and (args.condition_channels is None or args.condition_channels < 1):
+        ap.error("--speaker-prefix needs --condition-channels H with H >= 1")
+    if args.condition_channels is not None and not args.speaker_prefix:
+        ap.error("--condition-channels goes with --speaker-prefix")
+    if args.speaker:
+        from .speakers import utterance_speakers
+        try:
+            utterance_speakers(args.speaker, utterance_prompts(args)[0] or 1)
+        except ValueError as e:
+            ap.error(str(e))
     return args

@@ -15,6 +15,7 @@ import sys
 
 from .. import data, scoring
 from . import model as _model
+from . import speakers as _speakers
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -34,14 +35,17 @@ def build_parser() -> argparse.ArgumentParser:
 def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True):
     """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
     "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
-    samples, and prints one line per file and one for the total unless ``verbose`` is off."""
+    samples, and prints one line per file and one for the total unless ``verbose`` is off.  A checkpoint conditioned on
+    speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run."""
     files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
     if not files:
         raise Exception("no .wav file in {}".format(wav_dir))
     rows, nats, samples = [], 0.0, 0
+    labels = getattr(net, "speakers", None)
+    cids = {fn: None if labels is None else _speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files}
     for fn in files:
         tokens, _ = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
-        row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size))
+        row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn]))
         rows.append(dict(file=fn, **row))
         nats += row["nats_per_sample"] * row["samples"]
         samples += row["samples"]

@@ -15,27 +15,29 @@ import torch
 from .. import data, sampling
 from . import args as _args
 from . import model as _model
+from . import speakers as _speakers
 from .train import input_width_of
 
 
-def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, top_p):
+def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition=None):
     """The reference's loop (generate.py:24-43) from the given window: one ``forward_one_step`` over the last
     ``input_width`` tokens and one draw per sample, on the host; returns the ``n`` emitted tokens."""
     Q = net.params.quantization_steps
     controls = not sampling.controls_off(temperature, top_k, top_p, Q)
     iw = len(window)
     buf = np.array(window, dtype=np.int32)
+    cond = {} if condition is None else {"condition": [condition]}
     for time_step in range(1, n + 1):
         x = torch.as_tensor(buf[-iw:].reshape(1, -1)).to(net.device)
         if not controls:
             with torch.no_grad():
-                softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True)[0, :, 0, -1]
+                softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True, **cond)[0, :, 0, -1]
             buf = np.append(buf, np.random.choice(np.arange(Q), p=softmax))
         else:
             # the same rule the device applies under --fast, on the host: logits / temperature, softmax, truncation, and
             # choice()'s draw from its one uniform
             with torch.no_grad():
-                logits = net.forward_one_step(x, apply_softmax=False, as_numpy=True)[0, :, 0, -1]
+                logits = net.forward_one_step(x, apply_softmax=False, as_numpy=True, **cond)[0, :, 0, -1]
             softmax = sampling.apply_temperature(logits, temperature)
             buf = np.append(buf, sampling.sample(softmax, np.random.random_sample(), top_k, top_p))
         if time_step % 10 == 0:
@@ -46,7 +48,7 @@ def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, 
 
 
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                   temperature=1.0, top_k=0, top_p=1.0):
+                   temperature=1.0, top_k=0, top_p=1.0, condition=None):
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     iw = input_width_of(params)
@@ -58,9 +60,10 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
     elif fast:
         # one uniform per sample, the draw numpy's choice() makes (generate.py:40); the whole loop runs on the device
         u = np.random.random_sample(n)
-        tokens = net.generate(n, u, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p).cpu().numpy()
+        tokens = net.generate(n, u, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
+                              condition=condition).cpu().numpy()
     else:
-        tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p)
+        tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition)
     print("\ndone in {:.3f} sec".format(time.time() - start_time))
     os.makedirs(output_dir, exist_ok=True)
     filename = "{}/generated.wav".format(output_dir)
@@ -80,7 +83,7 @@ def read_prompt(path, params):
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                        temperature=1.0, top_k=0, top_p=1.0):
+                        temperature=1.0, top_k=0, top_p=1.0, conditions=None):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance."""
     Q = params.quantization_steps
@@ -96,9 +99,11 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
         tokens = np.zeros((N, 0), np.int32)
     elif fast:
         u = np.random.random_sample((N, n))
-        tokens = net.generate_batch(n, u, initial_tokens=prompts, temperature=temperature, top_k=top_k, top_p=top_p).cpu().numpy()
+        tokens = net.generate_batch(n, u, initial_tokens=prompts, temperature=temperature, top_k=top_k, top_p=top_p,
+                                    condition=conditions).cpu().numpy()
     else:
-        tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p) for i in range(N)])
+        tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p,
+                                      None if conditions is None else conditions[i]) for i in range(N)])
     print("\ndone in {:.3f} sec".format(time.time() - start_time))
     os.makedirs(output_dir, exist_ok=True)
     filenames = []
@@ -111,14 +116,20 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
 def main(argv=None):
     args = _args.parse(argv)
     n_utt, prompt_files = _args.utterance_prompts(args)
+    # the speaker of every utterance, checked against the checkpoint's table before the model is built: an unknown label,
+    # --speaker on an unconditioned checkpoint and its absence on a conditioned one all stop here with a clear message
+    table = _speakers.load_table(args.model_dir)
+    names = _speakers.utterance_speakers(args.speaker, n_utt or 1)
+    cids = [_speakers.class_id(table[0] if table else None, s, "generate") for s in names]
     params, net = _model.build(args)
     np.random.seed(args.seed)
     if n_utt is not None:
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
-                                   top_p=args.top_p)
+                                   top_p=args.top_p, conditions=cids if table else None)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
-                          output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+                          output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                          condition=cids[0])
 
 
 if __name__ == "__main__":

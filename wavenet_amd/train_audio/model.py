@@ -8,6 +8,7 @@ import os
 import torch
 
 from .. import FasterWaveNet, Params, WaveNet
+from . import speakers as _speakers
 
 
 def default_params() -> Params:
@@ -54,9 +55,20 @@ def build(args):
 
     ``args.ema_decay`` > 0 (train) keeps a weight average, resumed from the checkpoint's ``wavenet.ema.npz`` when it is there;
     ``args.ema`` (generate, evaluate) loads that file's averaged weights as the model's weights.  Both are read with a
-    default, so that a caller with a parser of its own need not know them."""
+    default, so that a caller with a parser of its own need not know them.
+
+    Speakers: ``args.speaker_prefix`` (train) takes the label table from the .wav files of ``args.wav_dir`` and writes it, with
+    ``args.condition_channels``, to ``speakers.json`` -- or checks it against the one already there.  Whenever that file
+    exists the network is built globally conditioned on its labels, and ``net.speakers`` is the table (None otherwise)."""
     params = load_params(args.model_dir)
-    net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed)
+    if bool(getattr(args, "speaker_prefix", False)):
+        wavs = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
+        table = _speakers.ensure_table(args.model_dir, _speakers.label_table(wavs), getattr(args, "condition_channels", None))
+    else:
+        table = _speakers.load_table(args.model_dir)
+    cond = dict(condition_classes=len(table[0]), condition_channels=table[1]) if table else {}
+    net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed, **cond)
+    net.speakers = table[0] if table else None
     params.dump()
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     use_ema = bool(getattr(args, "ema", False))

@@ -14,6 +14,7 @@ from ..graph import default_loss
 from . import args as _args
 from . import model as _model
 from .evaluate import evaluate_dir
+from . import speakers as _speakers
 
 
 HEALTH_EVERY = 100      # updates between two reads of WaveNet.last_update_applied() (a host synchronisation each)
@@ -51,6 +52,12 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     silence = 127 if params.quantization_steps > 127 else params.quantization_steps // 2
     signals = np.concatenate([np.full((iw,), silence, dtype=np.int32), signals.astype(np.int32)])   # train.py:53
     crops = _Crops(signals, iw, train_width, net.device)
+    # a conditioned model: every crop carries the label of the file it came from
+    labels = getattr(net, "speakers", None)
+    cond = None
+    if labels is not None:
+        cid = _speakers.class_id(labels, _speakers.speaker_label(path_to_file), os.path.basename(path_to_file))
+        cond = torch.full((batch_size,), cid, device=net.device, dtype=torch.int64)
     sum_loss = torch.zeros((), device=net.device, dtype=torch.float64)
     graph = None
     skipped = 0
@@ -61,12 +68,12 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
             key = (batch_size, iw + train_width)
             graph = None if state is None else state.get(key)
             if graph is None:
-                graph = TrainStepGraph(net, x, tgt)
+                graph = TrainStepGraph(net, x, tgt, condition=cond)
                 if state is not None:
                     state[key] = graph
-            loss = graph.step(x, tgt)
+            loss = graph.step(x, tgt, condition=cond)
         else:
-            loss = default_loss(net, x, tgt)
+            loss = default_loss(net, x, tgt, condition=cond)
             net.backprop(loss)
             loss = loss.detach()
         sum_loss += loss                                            # on the device: no host sync per update

@@ -282,27 +282,39 @@ class _StackFn(_Fn):
     (WaveNet.forward_residual_block, wavenet.py:572-582)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, net, t_off, train, window_only=False):
+    def forward(ctx, x, anchor, net, t_off, train, window_only=False, cond=None):
         # `anchor` is a dummy leaf that requires grad: it keeps this node on the tape even when x
         # does not require grad, because the weights are not tensor inputs of the node.
+        # `cond` (global conditioning): the (B, sum 2 cd) block of per-clip gate biases of _CondFn -- layer l's filter row at
+        # net._cond_offsets[l][0], its gate row at [l][1] -- handed to the library as bias rows one block row apart
+        # (WN_EXEC_BIAS_PER_CLIP); the backward returns the block's gradient.
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
         desc = net._stack_desc()
+        ex = lambda: net._exec(B, T)
+        if cond is not None:
+            cond = cond.contiguous()
+            if tuple(cond.shape) != (B, net._cond_rows):
+                raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (tuple(cond.shape), (B, net._cond_rows)))
+            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg")
+            desc = C.byref(cdesc)
+            ex = lambda: net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=net._cond_rows)
         L = len(net._flat_layers)
         ncd = sum(lay.cd for lay in net._flat_layers)
         dev_ = x.device
         xs = torch.empty((L, B, T, Cr), device=dev_, dtype=torch.float32)
         z = torch.empty((B * T * ncd,), device=dev_, dtype=torch.float32)
         # tanh is saved only when the backward cannot take the chained path (which recovers it as z / sigmoid)
-        f = torch.empty_like(z) if train and _lib.lib().wn_stack_saves_tanh(desc, net._exec(B, T)) else None
+        f = torch.empty_like(z) if train and _lib.lib().wn_stack_saves_tanh(desc, ex()) else None
         g = torch.empty_like(z) if train else None
         skip = torch.empty((B, T - t_off, net._Cs), device=dev_, dtype=torch.float32)
         check(_lib.lib().wn_stack_fwd(desc, ptr(x), ptr(xs), ptr(z), ptr(f), ptr(g), ptr(skip), B, T, t_off,
-                                      1 if net.compat_zero_prefix else 0, 1 if window_only else 0, net._exec(B, T),
+                                      1 if net.compat_zero_prefix else 0, 1 if window_only else 0, ex(),
                                       stream_ptr()), "wn_stack_fwd")
         ctx.net, ctx.t_off, ctx.shape, ctx.window_only = net, t_off, (B, T, Cr), bool(window_only)
         ctx.saved = (x, xs, z, f, g) if train else None
+        ctx.cond = cond if train else None
         net._last_layer_inputs = [x] + [xs[l] for l in range(L - 1)]      # FasterWaveNet seeds its rings from these
         return xs[L - 1], skip
 
@@ -313,6 +325,7 @@ class _StackFn(_Fn):
         if ctx.saved is None:
             raise _lib.WaveNetHipError("backward through a forward that ran without grad enabled")
         x, xs, z, f, g = ctx.saved
+        cond = ctx.cond
         if ctx.window_only and dout is not None:
             raise _lib.WaveNetHipError("forward_residual_block(window_only=True) computed only what the skip window needs: "
                                        "the residual output cannot carry a gradient")
@@ -324,12 +337,53 @@ class _StackFn(_Fn):
         dout = None if dout is None else dout.contiguous()
         dskip = None if dskip is None else dskip.contiguous()
         dx = torch.empty((B, T, Cr), device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        dcond, ex, dbf, dbg = None, net._exec(B, T), gt["bf"], gt["bg"]
+        if cond is not None:
+            # per-clip bias-gradient rows accumulate (+=) into a zeroed block: the gradient of the conditioning block
+            dcond = torch.zeros_like(cond)
+            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg")
+            desc = C.byref(cdesc)
+            dbf, dbg = net._cond_rows_of(dcond)
+            ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=net._cond_rows)
         check(lib.wn_stack_bwd(desc, ptr(x), ptr(xs), ptr(z), ptr(f), ptr(g), ptr(dout), ptr(dskip), ptr(dx),
-                               gt["wf"], gt["bf"], gt["wg"], gt["bg"], gt["wp"], gt["bp"], gt["ws"], gt["bs"],
-                               ptr(ws), nbytes, B, T, t_off, 1 if net.compat_zero_prefix else 0, net._exec(B, T),
+                               gt["wf"], dbf, gt["wg"], dbg, gt["wp"], gt["bp"], gt["ws"], gt["bs"],
+                               ptr(ws), nbytes, B, T, t_off, 1 if net.compat_zero_prefix else 0, ex,
                                stream_ptr()), "wn_stack_bwd")
-        ctx.saved = None
-        return dx, None, None, None, None, None
+        ctx.saved = ctx.cond = None
+        return dx, None, None, None, None, None, dcond
+
+
+class _CondFn(_Fn):
+    """Global conditioning (van den Oord et al. 2016, eq. 3): class ids (B,) -> the block (B, sum_l 2 cd_l) of per-clip gate
+    biases V E[id] -- an embedding gather and one small projection (``wn_pointwise_*``; B x channels x rows, tiny).  The
+    projection's gradient goes straight into the gradient arena like every other weight's; the embedding's is formed without
+    atomics -- a (classes, B) one-hot mask times the (B, channels) gradient, summed over B in a fixed order -- so it is
+    bit-reproducible, and the rows of classes absent from the batch receive exactly 0.  Static shapes: capturable."""
+
+    @staticmethod
+    def forward(ctx, ids, E, V, net):
+        h = E.view(E.shape[0], E.shape[1]).index_select(0, ids).contiguous()          # (B, channels)
+        B, H = h.shape
+        R = V.shape[0]
+        out = torch.empty((B, R), device=h.device, dtype=torch.float32)
+        check(_lib.lib().wn_pointwise_fwd(ptr(h), ptr(V), None, ptr(out), B, H, R, ACT["none"], net._exec(), stream_ptr()),
+              "wn_pointwise_fwd")
+        ctx.save_for_backward(ids, h)
+        ctx.E, ctx.V, ctx.net = E, V, net
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ids, h = ctx.saved_tensors
+        E, V = ctx.E, ctx.V
+        B, H = h.shape
+        dout = dout.contiguous()
+        dh = torch.empty_like(h)
+        check(_lib.lib().wn_pointwise_bwd(ptr(h), ptr(V), ptr(dout), ptr(dh), ptr(V.grad), None, B, H, V.shape[0],
+                                          ACT["none"], ctx.net._exec(), stream_ptr()), "wn_pointwise_bwd")
+        mask = (torch.arange(E.shape[0], device=ids.device).unsqueeze(1) == ids.unsqueeze(0)).to(torch.float32)   # (classes, B)
+        E.grad.view(E.shape[0], H).add_((mask.unsqueeze(2) * dh.unsqueeze(0)).sum(dim=1))
+        return None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------------
@@ -530,6 +584,7 @@ class ResidualConvLayer(object):
         return self.wf.dilation
 
     def _run(self, xb, save):
+        self.net._no_single_layer_condition()
         B, T, Cr = xb.shape
         out = torch.empty_like(xb)
         z = torch.empty((B, T, self.cd), device=xb.device, dtype=torch.float32)
@@ -552,6 +607,7 @@ class ResidualConvLayer(object):
         """Newest column only (wavenet.py:350-356): (1,Cr,1,1), (1,Cs,1,1)."""
         x = self.net.to_variable(x)
         _need_gpu(x)
+        self.net._no_single_layer_condition()
         fw, d = self.fw, self.dilation
         cols = [x.shape[3] - 1 - (fw - 1 - k) * d for k in range(fw)]
         taps = _to_btc(x[0:1, :, :, cols]).contiguous()             # (1, fw, Cr)
@@ -595,12 +651,31 @@ class WaveNet(object):
 
     head_activation = "relu"          # wavenet.py:588
 
-    def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32"):
+    def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
+                 condition_classes: int = 0, condition_channels: int = 0):
         """``storage="bf16"`` (BASELINE config 5; not in the reference): activations in bfloat16, fp32 accumulation, fp32
-        master weights; for 128 residual / dilation channels, filter width 2, a multiple of 256 skip channels."""
+        master weights; for 128 residual / dilation channels, filter width 2, a multiple of 256 skip channels.
+
+        ``condition_classes`` / ``condition_channels`` (both 0: off, and the model is byte for byte the unconditioned one):
+        global conditioning, the open item of the reference's own to-do list.  Every residual layer becomes
+        z = tanh(Wf * x + Vf h) sigmoid(Wg * x + Vg h) with h = the learned ``condition_channels``-wide embedding row of the
+        clip's integer class id (a speaker).  Two more links, registered AFTER the head so that no existing arena offset or
+        seeded draw moves: ``global_condition_embed/W`` (classes, channels, 1, 1) and ``global_condition_projection/W``
+        (sum_l 2 cd_l, channels, 1, 1), rows layer-major, a layer's filter rows before its gate rows.  They are not
+        ``Params`` fields (``Params().to_dict()`` is the reference's key set).  The forward methods then take
+        ``condition=`` -- one class id per clip."""
         params.check()
         if storage not in ("fp32", "bf16"):
             raise Exception("storage must be 'fp32' or 'bf16'")
+        self.condition_classes, self.condition_channels = int(condition_classes), int(condition_channels)
+        if (self.condition_classes > 0) != (self.condition_channels > 0) or self.condition_classes < 0 or self.condition_channels < 0:
+            raise Exception("global conditioning needs condition_classes > 0 and condition_channels > 0 (or both 0: off), got "
+                            "%d and %d" % (self.condition_classes, self.condition_channels))
+        if self.condition_classes and storage == "bf16":
+            raise Exception("global conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases)")
+        if self.condition_classes and not params.residual_conv_dilation_no_bias:
+            raise Exception("global conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
+                            "convolutions' bias; a second, shared one is not supported)")
         self.params = params
         self.storage = storage
         self.gemm_precision = None          # None: the module default (wavenet_amd.set_gemm_precision) at call time
@@ -662,13 +737,27 @@ class WaveNet(object):
                                                            nobias=p.softmax_conv_no_bias))
         self._flat_layers = [lay for blk in self.residual_blocks for lay in blk]
         self._Cr, self._Cs = n_in, n_skip
+        # global conditioning: layer l's filter biases are rows off .. off + cd_l of the projection, its gate biases the next cd_l
+        self.global_condition_embed = self.global_condition_projection = None
+        self._cond_offsets, self._cond_rows = [], 0
+        if self.condition_classes:
+            for lay in self._flat_layers:
+                self._cond_offsets.append((self._cond_rows, self._cond_rows + lay.cd))
+                self._cond_rows += 2 * lay.cd
+            self.global_condition_embed = _Link("global_condition_embed",
+                                                (self.condition_classes, self.condition_channels, 1, 1), None)
+            self.global_condition_projection = _Link("global_condition_projection",
+                                                     (self._cond_rows, self.condition_channels, 1, 1), None)
 
     def links(self) -> List[_Link]:
         """All parameter holders in the reference's registration order (wavenet.py:461-472)."""
         out: List[_Link] = list(self.causal_conv_layers)
         for lay in self._flat_layers:
             out += [lay.wf, lay.wg, lay.projection_block, lay.projection_softmax]
-        return out + list(self.softmax_conv_layers)
+        out += list(self.softmax_conv_layers)
+        if self.condition_classes:                                   # after the head: existing offsets and draws stay put
+            out += [self.global_condition_embed, self.global_condition_projection]
+        return out
 
     # -- parameters: one flat arena (what the DP all-reduce and the optimiser kernel see) -----
     def _allocate(self, seed):
@@ -720,7 +809,18 @@ class WaveNet(object):
         return {"%s/%s" % (ln.name, kind): self._arena[o:o + n].view(shape).detach().cpu().numpy().copy()
                 for ln, kind, o, n, shape in self._spans}
 
+    def _check_condition_keys(self, sd):
+        """A conditioned checkpoint does not fit an unconditioned model, nor the reverse: say so instead of a KeyError."""
+        cond_keys = sorted(k for k in sd if k.startswith("global_condition_"))
+        if cond_keys and not self.condition_classes:
+            raise Exception("this checkpoint is globally conditioned (%s) and the model is not: construct the model with "
+                            "condition_classes / condition_channels" % ", ".join(cond_keys))
+        if self.condition_classes and not cond_keys:
+            raise Exception("this model is globally conditioned and the checkpoint is not (it holds no "
+                            "global_condition_embed/W and global_condition_projection/W)")
+
     def load_state_dict(self, sd: Dict[str, np.ndarray]):
+        self._check_condition_keys(sd)
         with torch.no_grad():
             for ln, kind, o, n, shape in self._spans:
                 key = "%s/%s" % (ln.name, kind)
@@ -735,7 +835,7 @@ class WaveNet(object):
     def _weights_changed(self):
         self._w16_stale = True
 
-    def _exec(self, B: int = 8, T: int = 0, call_flags: int = 0):
+    def _exec(self, B: int = 8, T: int = 0, call_flags: int = 0, bias_stride: int = 0):
         """WnExec for a library call on the current stream: this model's GEMM precision (``self.gemm_precision``, or the
         module default), its flags, and a scratch buffer owned by (model, stream), sized by ``wn_exec_workspace_bytes``
         for the largest (B, T) seen so far.  Buffers are never freed or moved once handed out -- a captured graph keeps
@@ -762,6 +862,7 @@ class WaveNet(object):
         ex.fwd_t1_min_blocks = (_lib.default_fwd_t1_min_blocks() if self.fwd_t1_min_blocks is None
                                 else int(self.fwd_t1_min_blocks))
         ex.plan = self._plan if self._plan_on else None
+        ex.reserved = int(bias_stride)          # WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bias rows
         return C.byref(ex)
 
     # -- step plan (include/wavenet_hip.h, "step plan"): the weight-only preparation of a training step in two launches --------
@@ -849,6 +950,70 @@ class WaveNet(object):
     def _grad_tables(self):
         self._stack_desc()
         return self._gt
+
+    # -- global conditioning --------------------------------------------------------------------------------------------------
+    def _cond_rows_of(self, block):
+        """(bf, bg) pointer tables into clip 0's row of a (B, sum 2 cd) block: layer l's filter and gate rows."""
+        p0 = block.data_ptr()
+        L = len(self._cond_offsets)
+        bf = (C.c_void_p * L)(*[p0 + 4 * of for of, _ in self._cond_offsets])
+        bg = (C.c_void_p * L)(*[p0 + 4 * og for _, og in self._cond_offsets])
+        return bf, bg
+
+    def _cond_tables(self, cls, base, block, name_f, name_g):
+        """A copy of the descriptor ``base`` whose bias tables point into ``block``; (descriptor, what must stay alive)."""
+        d = cls()
+        for name, _ in cls._fields_:
+            setattr(d, name, getattr(base, name))
+        bf, bg = self._cond_rows_of(block)
+        setattr(d, name_f, C.cast(bf, C.POINTER(C.c_void_p)))
+        setattr(d, name_g, C.cast(bg, C.POINTER(C.c_void_p)))
+        return d, (bf, bg, block)
+
+    def _condition_ids(self, condition, B):
+        """``condition=`` of the forward methods -> (B,) int64 class ids on the device, or None for an unconditioned model.
+        A conditioned model called without ids raises, and so does an unconditioned one called with them."""
+        if not self.condition_classes:
+            if condition is not None:
+                raise Exception("condition= was given, but this model has no global conditioning (condition_classes = 0)")
+            return None
+        if condition is None:
+            raise Exception("this model is globally conditioned (%d classes): pass condition= (one class id per clip)"
+                            % self.condition_classes)
+        if isinstance(condition, torch.Tensor):
+            ids = condition
+        else:
+            a = np.asarray(condition).reshape(-1)
+            if a.dtype.kind not in "iu":
+                raise Exception("condition= takes integer class ids, got %s" % a.dtype)
+            if a.size and (int(a.min()) < 0 or int(a.max()) >= self.condition_classes):
+                raise Exception("condition= class ids must lie in [0, %d)" % self.condition_classes)
+            ids = torch.from_numpy(a.astype(np.int64))
+        ids = self.to_variable(ids).reshape(-1).to(torch.int64)
+        if ids.shape[0] != B:
+            raise Exception("condition= holds %d class ids for %d clips" % (ids.shape[0], B))
+        return ids
+
+    def _condition_block(self, condition, B):
+        """The (B, sum 2 cd) block of per-clip gate biases (an autograd node over the two conditioning links), or None."""
+        ids = self._condition_ids(condition, B)
+        if ids is None:
+            return None
+        _need_gpu(ids)
+        return _CondFn.apply(ids, self.global_condition_embed.W, self.global_condition_projection.W, self)
+
+    def _no_single_layer_condition(self):
+        if self.condition_classes:
+            raise Exception("a globally conditioned model runs its layers through forward_residual_block(condition=...) only")
+
+    def condition_biases(self, class_id: int):
+        """[(bf, bg)] per residual layer, each (cd,) float32 on the device: the gate biases V E[class_id] that conditioning on
+        ``class_id`` adds to every layer -- what an ordinary biased model (``residual_conv_dilation_no_bias = False``) would
+        hold as ``wf/b`` and ``wg/b``.  Computed on the device by the node the forward uses."""
+        with torch.no_grad():
+            row = self._condition_block([int(class_id)], 1)[0]
+        return [(row[of:of + lay.cd].clone(), row[og:og + lay.cd].clone())
+                for lay, (of, og) in zip(self._flat_layers, self._cond_offsets)]
 
     # -- optimiser (wavenet.py:457-519) ---------------------------------------------------------
     def setup_optimizer(self):
@@ -992,6 +1157,7 @@ class WaveNet(object):
             raise _lib.WaveNetHipError("load_ema_state_dict() inside ema_weights()")
         from . import ema
         decay = ema.check_decay(float(sd["ema/decay"]))
+        self._check_condition_keys(sd)
         with torch.no_grad():
             for ln, kind, o, n, shape in self._spans:
                 key = "%s/%s" % (ln.name, kind)
@@ -1074,9 +1240,9 @@ class WaveNet(object):
         return zero_prefix(T, d, fw) if self.compat_zero_prefix else 0
 
     # -- forward (wavenet.py:556-593) -----------------------------------------------------------
-    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False):
+    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None):
         causal_output = self.forward_causal_block(x_batch)
-        _, sum_skip_connections = self.forward_residual_block(causal_output)
+        _, sum_skip_connections = self.forward_residual_block(causal_output, condition=condition)
         softmax_output = self.forward_softmax_block(sum_skip_connections, apply_softmax=apply_softmax)
         if as_numpy:
             return self.to_numpy(softmax_output)
@@ -1112,20 +1278,22 @@ class WaveNet(object):
         self._last_causal_outputs = outs                          # FasterWaveNet seeds its rings from these
         return _as_view(out)
 
-    def forward_residual_block(self, x_batch, t_off: int = 0, window_only: bool = False):
+    def forward_residual_block(self, x_batch, t_off: int = 0, window_only: bool = False, condition=None):
         """(output, sum_skip_connections).  ``t_off`` > 0 (an extension) computes the skip sum for
         columns t_off.. only -- what train.py:73 keeps -- instead of slicing it afterwards.
         ``window_only`` (training, where train.py:72 discards the residual output): columns that cannot influence
         ``skip[t_off:]`` are not computed at all, so the returned residual output is UNDEFINED below the window's
-        receptive field and must not be used; loss and gradients are unchanged."""
+        receptive field and must not be used; loss and gradients are unchanged.
+        ``condition``: one class id per clip, for a globally conditioned model (and only for one)."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
+        cond = self._condition_block(condition, int(x.shape[0]))
         if self.storage == "bf16":
             self._pack16_if_stale()
             out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled())
             return _as_view(out), _as_view(skip)
         out, skip = _StackFn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled(),
-                                   bool(window_only))
+                                   bool(window_only), cond)
         return _as_view(out), _as_view(skip)
 
     def forward_softmax_block(self, x_batch, apply_softmax=True, activation: Optional[str] = None):
@@ -1243,22 +1411,22 @@ class WaveNet(object):
                                           self._exec(call_flags=_lib.WN_EXEC_HEAD_ROW_NLL), stream_ptr()), "wn_head_xent")
             return nll
 
-    def token_nll(self, x, tgt):
+    def token_nll(self, x, tgt, condition=None):
         """The per-position form of ``graph.default_loss``: (B, tgt.shape[1]) float32 negative log-likelihoods of ``tgt``
         under the last ``tgt.shape[1]`` output columns of the window ``x`` (tokens (B, T) or a one-hot image).  Inference
         form: nothing is saved for a backward."""
         with torch.no_grad():
             c = self.forward_causal_block(x)
-            _, s = self.forward_residual_block(c, t_off=int(c.shape[3]) - int(tgt.shape[1]))
+            _, s = self.forward_residual_block(c, t_off=int(c.shape[3]) - int(tgt.shape[1]), condition=condition)
             return self.head_token_nll(s, tgt)
 
-    def score(self, tokens, chunk_width: int = 16384, batch_size: int = 8):
+    def score(self, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None):
         """(n,) float32 on the device: the negative log-likelihood in nats of every sample of the 1-D token sequence
         ``tokens``, each given all samples before it (silence before the first), teacher-forced.  See
         :func:`wavenet_amd.scoring.score` for the definition and the two knobs, which do not change the result beyond
-        arithmetic."""
+        arithmetic.  ``condition``: the class id of the whole sequence, for a globally conditioned model."""
         from . import scoring
-        return scoring.score(self, tokens, chunk_width=chunk_width, batch_size=batch_size)
+        return scoring.score(self, tokens, chunk_width=chunk_width, batch_size=batch_size, condition=condition)
 
     # -- the deferred skip projection -----------------------------------------------------------
     def _skip_sum(self, zs: Sequence[torch.Tensor], skip: torch.Tensor, B, T, t_off, Tw):
@@ -1315,6 +1483,7 @@ class WaveNet(object):
         else:
             from . import hdf5_io
             sd = hdf5_io.read_datasets(filename)
+        self._check_condition_keys(sd)
         self.load_state_dict({k: v for k, v in sd.items() if k in self.state_dict()})
 
     def load(self, model_dir="./", weights: str = "model"):
