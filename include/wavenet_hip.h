@@ -108,7 +108,28 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                       rescaled -- they never pass through the power-of-two tile scale -- and runs every layer as
                                       its own launch, as under WN_EXEC_NO_FWD_GROUPS.  The stack backward takes the per-layer
                                       path (bias-gradient tables always do), so wn_stack_saves_tanh is 1.  wn16_* (bf16 storage)
-                                      keeps refusing biases.  A step plan holds weight images only, never a bias pointer */
+                                      keeps refusing biases.  A step plan holds weight images only, never a bias pointer.
+                                      Local conditioning (eq. 4 with y = the features repeated over time): wn_stack_fwd /
+                                      wn_stack_bwd read three trailing WnStackDesc fields under this flag.  bias_hop = h > 0
+                                      turns clip b's row into a block of n = ceil((T + bias_phase) / h) rows: bf[l] / bg[l]
+                                      point at (clip 0, frame 0), clip b's block starts b * WnExec.reserved floats on, frame
+                                      f lies f * bias_frame_stride floats on inside the block, and position t of every clip
+                                      -- t counted inside the call's T columns, whatever t_off / window_only say -- reads
+                                      frame (t + bias_phase) / h.  For t < Z neither the convolution nor the bias counts.
+                                        backward  dbf[l] / dbg[l] point at (clip 0, frame 0) of a gradient block of the same
+                                                  geometry; row (b, f) is accumulated (+=) with the sums of da[b, t, :] /
+                                                  dg[b, t, :] over the t >= Z of clip b that read frame f
+                                                  (k_colsum_per_frame: one launch per layer, a workgroup per 64 columns of a
+                                                  (clip, frame) segment, a fixed order, no float atomics, no scratch; a
+                                                  segment that covers a whole clip adds exactly what the per-clip form
+                                                  adds).  Rows of frames wholly below Z are not touched.  The path is the one
+                                                  per-clip rows select: nothing is order-dependent.
+                                      WN_EARG before any device work: bias_hop < 0; bias_phase outside [0, bias_hop);
+                                      T + bias_phase beyond 32 bits; bias_frame_stride below a layer's cd;
+                                      reserved < n * bias_frame_stride; bias_hop > 0 without the flag; on the fp16 x 2 path rows that are not 16-byte aligned or a clip /
+                                      frame stride that is no multiple of 4 floats (refused, never sent down another path).
+                                      bias_hop == 0: the other two fields are ignored.  wn_layer_fwd / wn_layer_bwd take no
+                                      descriptor and keep per-clip rows only; wn16_* keeps refusing biases */
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
 #define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
@@ -216,6 +237,10 @@ typedef struct WnStackDesc {
     /* host arrays (n_layers) of device pointers; bias tables or entries may be NULL             */
     const float* const* Wf; const float* const* bf; const float* const* Wg; const float* const* bg;
     const float* const* Wp; const float* const* bp; const float* const* Ws; const float* const* bs;
+    /* local conditioning (read only under WN_EXEC_BIAS_PER_CLIP -- see the define; all 0 = one row per clip) */
+    int bias_hop;                          /* > 0: a bias row per (clip, frame); position t reads frame (t + bias_phase) / bias_hop */
+    int bias_phase;                        /* 0 <= bias_phase < bias_hop, one value per call                                       */
+    int bias_frame_stride;                 /* floats between consecutive frames' rows inside a clip's block (>= the layer's cd)    */
 } WnStackDesc;
 /* xs (n_layers,B,T,Cr) receives every layer's output (xs[n_layers-1] is the stack output); z, f, g
  * are layer-major (layer l at offset sum_{i<l} B*T*cd[i]); f/g NULL for inference; skip (B,T-t_off,Cs)
@@ -305,6 +330,20 @@ typedef struct WnDecoderDesc {
                                          same products, another summation order for the skip rows and the logits --
                                          probabilities agree to ~1e-7, sampled tokens can differ at a near-tie of the
                                          cumulative distribution; each form is deterministic */
+    /* Local conditioning (trailing fields; frame_bias == NULL: every decode kernel executes what it executed before).  Applied
+     * by wn_decoder_create and wn_decoder_update_weights; the handle COPIES the table, as it copies weights.  frame_bias: a
+     * device pointer to n_frames rows, frame_stride floats apart; inside a row flat layer l (block-major, as bf / bg are
+     * ordered) holds its cd filter values at offset sum_{i<l} 2 cd_i, then its cd gate values.  The k-th step run on the handle
+     * (k = 0, 1, ...) since the create / update call that set the table -- whichever of wn_decoder_step, wn_decoder_run or
+     * wn_decoder_run_batch runs it -- adds row (frame_phase + k) / frame_hop to every layer's gate pre-activations, in fp32, on
+     * top of the static bf / bg where those exist: per output (static bias or 0) + frame value, then the taps, so a table of
+     * zeros changes no bit.  A run that would read past row n_frames - 1 is refused with WN_EARG before any device work (no
+     * clamping).  A handle with a table is an any-shape one, as with biased layers (a handle created WITHOUT one on config 4's
+     * shape runs the specialised kernels and refuses a table in wn_decoder_update_weights); an update without a table drops
+     * it.  wn_decoder_run_batch: the handles must agree on having a table and on frame_hop; phase, row count and contents are
+     * per utterance. */
+    const float* frame_bias;
+    int n_frames, frame_hop, frame_phase, frame_stride;
 } WnDecoderDesc;
 
 int wn_decoder_create(void** handle, const WnDecoderDesc* desc, void* stream);

@@ -50,6 +50,11 @@ struct Decoder {
     void* batch_img = nullptr;
     int batch_cap = 0;
     hipEvent_t batch_copied = nullptr;
+    // local conditioning (WnDecoderDesc.frame_bias): the handle's own compact copy of the table -- n_frames rows of frame_row
+    // floats (sum_l 2 cd_l) --, its hop and phase, and how many steps have run since the create / update call that set it
+    float* frame_tab = nullptr;
+    int frame_cap = 0, n_frames = 0, frame_hop = 0, frame_phase = 0, frame_row = 0;
+    long long frame_pos = 0;
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
 };
@@ -62,6 +67,7 @@ static bool fast_shape(const WnDecoderDesc* d) {
           d->n_blocks * d->n_layers <= 128))
         return false;
     if (d->causal_b && d->causal_b[0]) return false;
+    if (d->frame_bias) return false;               // a frame table selects the any-shape decoder, as biased layers do
     for (int l = 0; l < d->n_layers; ++l)
         if (d->cd[l] != 32) return false;
     for (int j = 0; j < d->n_blocks * d->n_layers; ++j)
@@ -131,6 +137,10 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 }
 
 // ---- the step loop ---------------------------------------------------------------------------
+// Local conditioning: the frame table of one utterance as the step loop takes it.  tab == NULL: no table, and the loop
+// executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the handle's
+// frame_phase + the steps run since the table was set -- to every layer's gate pre-activations.
+struct DecFrames { const float* tab; int hop; int row; long long pos0; };
 __device__ __forceinline__ int pmod(long long a, int D) {
     long long r = a % D;
     return (int)(r < 0 ? r + D : r);
@@ -155,7 +165,7 @@ __device__ __forceinline__ void decode_steps(
     const DecMeta& M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
-    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl& sc) {
+    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl& sc, const DecFrames& fr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int tid = threadIdx.x, NT = blockDim.x;
     const bool filt = sc.top_k > 0 || sc.top_p < 1.0;      // workgroup-uniform: kernel arguments, or the workgroup's own table entry
@@ -213,6 +223,8 @@ __device__ __forceinline__ void decode_steps(
             __syncthreads();
         }
         for (int o = tid; o < M.Cs; o += NT) skip[o] = 0.f;
+        // the step's frame row, computed once per step (workgroup-uniform); layer j's 2 cd values lie at the running offset
+        const float* __restrict__ frow = fr.tab ? fr.tab + ((fr.pos0 + it) / fr.hop) * (long long)fr.row : nullptr;
         // ---- residual layers ------------------------------------------------------------------
         for (int j = 0; j < M.nlayers; ++j) {
             const DecLayer L = layers[j];
@@ -221,6 +233,7 @@ __device__ __forceinline__ void decode_steps(
             // gate: ab[o2] = b + sum_k sum_c WfgT[k*Cr+c][o2] x[n-(fw-1-k)d][c]
             for (int o = tid; o < n2; o += NT) {
                 float acc = L.bfg >= 0 ? arena[L.bfg + o] : 0.f;
+                if (frow) acc += frow[o];      // (static bias or 0) + frame value, then the taps: a table of zeros changes no bit
                 for (int k = 0; k < M.fw; ++k) {
                     int m = M.fw - 1 - k;
                     const float* w = arena + L.wfg + (long long)k * M.Cr * n2 + o;
@@ -251,6 +264,7 @@ __device__ __forceinline__ void decode_steps(
             __syncthreads();
             for (int c = tid; c < M.Cr; c += NT) xcur[c] = xnew[c];
             __syncthreads();
+            if (frow) frow += n2;
         }
         // ---- head on the newest column only ---------------------------------------------------
         float* hin = skip;
@@ -310,9 +324,9 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
     DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
-    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc) {
+    float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc, const DecFrames fr) {
     decode_steps(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
-                 apply_softmax, do_sample, sc);
+                 apply_softmax, do_sample, sc, fr);
 }
 
 // One utterance of the batched any-shape launch: what k_decode takes as arguments, from the utterance's own handle.  The
@@ -322,6 +336,7 @@ struct DecAnyUtt {
     float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
     int first_token; int pad;
     SampleCtl sc;
+    DecFrames fr;
 };
 
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
@@ -330,7 +345,7 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const D
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
     decode_steps(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens,
-                 q.prob_out, M.Q, 1, 1, q.sc);
+                 q.prob_out, M.Q, 1, 1, q.sc, q.fr);
 }
 
 // ---- host side -------------------------------------------------------------------------------
@@ -351,6 +366,51 @@ static int validate(const WnDecoderDesc* d) {
 }
 
 static inline long long align64(long long x) { return (x + 63) & ~63ll; }
+
+// ---- local conditioning: the handle's frame table ----------------------------------------------
+static DecFrames launch_frames(const Decoder* D) {
+    DecFrames f{};
+    if (D->n_frames > 0) { f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->frame_pos; }
+    return f;
+}
+// n more steps must not read past row n_frames - 1 (refused before any device work; no clamping)
+static int check_frames(const char* fn, const Decoder* D, long long n) {
+    if (D->n_frames <= 0) return WN_OK;
+    const long long last = (D->frame_phase + D->frame_pos + n - 1) / D->frame_hop;
+    WN_CHECK_ARG(last < D->n_frames, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
+                                     "run on it)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->frame_pos);
+    return WN_OK;
+}
+static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
+    if (!d->frame_bias) return WN_OK;
+    int row = 0;
+    for (const DecLayer& L : D->layers) row += 2 * L.cd;
+    WN_CHECK_ARG(d->n_frames > 0 && d->frame_hop > 0, "decoder: a frame table needs n_frames > 0 and frame_hop > 0 (got %d, %d)",
+                 d->n_frames, d->frame_hop);
+    WN_CHECK_ARG(d->frame_phase >= 0 && d->frame_phase < d->frame_hop, "decoder: frame_phase = %d outside [0, frame_hop = %d)",
+                 d->frame_phase, d->frame_hop);
+    WN_CHECK_ARG(d->frame_stride >= row, "decoder: frame_stride = %d below the row width %d (sum of 2 cd over the layers)",
+                 d->frame_stride, row);
+    WN_CHECK_ARG(!D->fastP, "decoder: this handle runs the specialised 32/256-channel kernels, which take no frame table: create the "
+                            "handle with the table");
+    return WN_OK;
+}
+// copy the table (after check_frame_desc), or drop it when the description has none; the step count starts again
+static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
+    D->frame_pos = 0;
+    if (!d->frame_bias) { D->n_frames = 0; return WN_OK; }
+    int row = 0;
+    for (const DecLayer& L : D->layers) row += 2 * L.cd;
+    if (d->n_frames > D->frame_cap || row != D->frame_row) {
+        if (D->frame_tab) { WN_HIP(hipFree(D->frame_tab)); D->frame_tab = nullptr; D->frame_cap = 0; }
+        WN_HIP(hipMalloc(&D->frame_tab, (size_t)d->n_frames * row * sizeof(float)));
+        D->frame_cap = d->n_frames;
+    }
+    WN_HIP(hipMemcpy2DAsync(D->frame_tab, (size_t)row * sizeof(float), d->frame_bias, (size_t)d->frame_stride * sizeof(float),
+                            (size_t)row * sizeof(float), (size_t)d->n_frames, hipMemcpyDeviceToDevice, s));
+    D->n_frames = d->n_frames; D->frame_hop = d->frame_hop; D->frame_phase = d->frame_phase; D->frame_row = row;
+    return WN_OK;
+}
 
 static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     const int T = 256;
@@ -504,7 +564,9 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
         D->three_wgs = !(d->flags & WN_DECODER_ONE_WORKGROUP);
     }
 #undef DEC_HIP
-    rc = pack_weights(D, d, s);
+    rc = check_frame_desc(D, d);
+    if (!rc) rc = pack_weights(D, d, s);
+    if (!rc) rc = take_frames(D, d, s);
     if (rc) { wn_decoder_destroy(D); return rc; }
     *handle = D;
     return WN_OK;
@@ -517,6 +579,7 @@ int wn_decoder_destroy(void* handle) {
     if (D->fastP) (void)hipFree(D->fastP);
     if (D->tok_ring) (void)hipFree(D->tok_ring);
     if (D->dmeta) (void)hipFree(D->dmeta);
+    if (D->frame_tab) (void)hipFree(D->frame_tab);
     if (D->batch_tab) (void)hipFree(D->batch_tab);
     if (D->batch_img) (void)hipHostFree(D->batch_img);
     if (D->batch_copied) (void)hipEventDestroy(D->batch_copied);
@@ -532,7 +595,9 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
     WN_CHECK_ARG(d->n_blocks * d->n_layers == D->meta.nlayers && d->Cr == D->meta.Cr && d->Cs == D->meta.Cs &&
                      d->Q == D->meta.Q && d->n_causal == D->meta.ncausal && d->n_head == D->meta.nhead,
                  "wn_decoder_update_weights: topology differs from the handle's");
-    return pack_weights(D, d, as_stream(stream));
+    if ((rc = check_frame_desc(D, d))) return rc;
+    if ((rc = pack_weights(D, d, as_stream(stream)))) return rc;
+    return take_frames(D, d, as_stream(stream));
 }
 
 int wn_decoder_load_state(void* handle, const int32_t* tokens, int W, const float* const* causal_out,
@@ -566,6 +631,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     WN_CHECK_ARG(D && prob, "wn_decoder_step: bad argument");
     WN_CHECK_ARG(token >= 0 && token < D->meta.Q, "wn_decoder_step: token %d outside [0,%d)", token, D->meta.Q);
     WN_CHECK_ARG(D->step + 1 < (1ll << 31), "wn_decoder_step: step counter overflow");
+    if (int rc = check_frames("wn_decoder_step", D, 1)) return rc;
     if (D->fastP) {
         int rc = decode_fast_launch(fast_utt(D, (int)token, nullptr, nullptr, prob, SampleCtl()), D->meta.nlayers, 1, D->meta.Q,
                                     apply_softmax, 0, D->meta.head_act, false, as_stream(stream));
@@ -575,9 +641,10 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     }
     hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, 1, (int)token,
-                       (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl());
+                       (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl(), launch_frames(D));
     WN_LAUNCH_CHECK();
     D->step += 1;
+    D->frame_pos += 1;
     return WN_OK;
 }
 
@@ -587,6 +654,7 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     WN_CHECK_ARG(D && uniforms && out_tokens && n > 0, "wn_decoder_run: bad argument");
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
     WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run: step counter overflow");
+    if (int rc = check_frames("wn_decoder_run", D, n)) return rc;
     if (D->fastP) {
         int rc = decode_fast_launch(fast_utt(D, (int)first_token, uniforms, out_tokens, prob_trace, launch_ctl(D)),
                                     D->meta.nlayers, n, D->meta.Q, 1, 1, D->meta.head_act, D->three_wgs, as_stream(stream));
@@ -597,9 +665,10 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     }
     hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, n, (int)first_token, uniforms,
-                       out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D));
+                       out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D), launch_frames(D));
     WN_LAUNCH_CHECK();
     D->step += n;
+    D->frame_pos += n;
     return WN_OK;
 }
 
@@ -642,7 +711,7 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
         DecAnyUtt q{};
         q.causal = D->d_causal; q.layers = D->d_layers; q.heads = D->d_heads; q.arena = D->arena; q.tok_ring = D->tok_ring;
         q.n0 = D->step; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_traces ? prob_traces[u] : nullptr;
-        q.first_token = (int)first_tokens[u]; q.sc = launch_ctl(D);
+        q.first_token = (int)first_tokens[u]; q.sc = launch_ctl(D); q.fr = launch_frames(D);
         img[u] = q;
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
@@ -650,7 +719,7 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     hipLaunchKernelGGL(k_decode_batch, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
                        n_handles, n);
     WN_LAUNCH_CHECK();
-    for (int u = 0; u < n_handles; ++u) ((Decoder*)handles[u])->step += n;
+    for (int u = 0; u < n_handles; ++u) { ((Decoder*)handles[u])->step += n; ((Decoder*)handles[u])->frame_pos += n; }
     return WN_OK;
 }
 
@@ -695,6 +764,9 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
                      "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
+        WN_CHECK_ARG((D->n_frames > 0) == (D0->n_frames > 0) && (D->n_frames <= 0 || D->frame_hop == D0->frame_hop),
+                     "wn_decoder_run_batch: utterance %d and utterance 0 disagree on having a frame table or on its hop", u);
+        if (int rcf = check_frames("wn_decoder_run_batch", D, n)) return rcf;
         if (!any)
             utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
     }

@@ -376,6 +376,72 @@ int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, in
     return WN_OK;
 }
 
+// Per-frame column sums of both gates in one launch (local conditioning): workgroup (x, f, b) owns 64 of the 2 Cd columns
+// [da | dg] of the segment of clip b that reads frame f -- rows max(tmin, f hop - phase) .. min(T, (f + 1) hop - phase) - 1 --
+// and adds its rows by k_colsum_per_clip's rule started at the segment's first row: chunks of t_chunk rows, four row lanes per
+// chunk combined as (p0 + p1) + (p2 + p3), chunk y on reduction lane y % 16 in ascending order, the 16 lane sums in index
+// order.  A segment that covers a whole clip therefore adds exactly what k_colsum_per_clip adds for that clip.  A segment
+// wholly below tmin has no rows: its workgroup leaves without touching the row.  No atomics, no scratch: B x frames x
+// 2 Cd / 64 independent workgroups (512 at config 2 with hop 256 against the per-clip form's 8).
+__global__ __launch_bounds__(1024) void k_colsum_per_frame(const float* __restrict__ da, const float* __restrict__ dg, int lda,
+                                                           int T, int tmin, int Cd, float* __restrict__ dbf,
+                                                           float* __restrict__ dbg, long long stride, BiasFrames fr,
+                                                           int t_chunk) {
+    __shared__ float red[16][64];
+    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
+    const int f = blockIdx.y, b = blockIdx.z;
+    const long long lo = (long long)f * fr.hop - fr.phase, hi = lo + fr.hop;
+    const int ta = lo > tmin ? (int)lo : tmin, tb = hi < T ? (int)hi : T;
+    if (tb <= ta) return;                                 // (uniform over the workgroup)
+    const bool ok = m < 2 * Cd;
+    const bool gate = m >= Cd;
+    const int mm = gate ? m - Cd : m;
+    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
+    const int nchunk = (tb - ta + t_chunk - 1) / t_chunk;
+    float sum = 0.f;
+    if (ok)
+        for (int y = threadIdx.y; y < nchunk; y += 16) {
+            const int t0 = ta + y * t_chunk, t1 = min(tb, t0 + t_chunk);
+            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+            int t = t0;
+            for (; t + 3 < t1; t += 4) {
+                p0 += A[(long long)t * lda]; p1 += A[(long long)(t + 1) * lda];
+                p2 += A[(long long)(t + 2) * lda]; p3 += A[(long long)(t + 3) * lda];
+            }
+            if (t < t1) p0 += A[(long long)t * lda];
+            if (t + 1 < t1) p1 += A[(long long)(t + 1) * lda];
+            if (t + 2 < t1) p2 += A[(long long)(t + 2) * lda];
+            sum += (p0 + p1) + (p2 + p3);
+        }
+    red[threadIdx.y][threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.y == 0 && ok) {
+        float tot = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
+        float* out = gate ? dbg : dbf;
+        if (out) out[(long long)b * stride + (long long)f * fr.stride + mm] += tot;
+    }
+}
+int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
+                             long long stride, BiasFrames fr, hipStream_t s) {
+    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
+    const int frames = (int)(((long long)T + fr.phase + fr.hop - 1) / fr.hop);
+    WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
+    WN_CHECK_SHAPE(frames <= 65535, "per-frame bias gradients: at most 65,535 frames per clip and call");
+    int t_chunk = 256;                                      // generic_colsum_per_clip's choice, from the same rows
+    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
+    hipLaunchKernelGGL(k_colsum_per_frame, dim3(cdiv(2 * Cd, 64), frames, B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd, dbf,
+                       dbg, stride, fr, t_chunk);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
+}
+int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
+                             float* dbf, float* dbg, hipStream_t s) {
+    if (c.frames.hop > 0) return generic_colsum_per_frame(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames, s);
+    return generic_colsum_per_clip(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, s);
+}
+
 // ---------------------------------------------------------------------------------------------
 // A7  residual layer, generic
 // ---------------------------------------------------------------------------------------------
@@ -383,7 +449,7 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
                            const float* __restrict__ bf, const float* __restrict__ Wg,
                            const float* __restrict__ bg, float* __restrict__ z,
                            float* __restrict__ fs, float* __restrict__ gs,
-                           int B, int T, int Cr, int Cd, int fw, int d, int Z, long long bias_stride) {
+                           int B, int T, int Cr, int Cd, int fw, int d, int Z, long long bias_stride, BiasFrames fr) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long total = (long long)B * T * Cd;
     if (i >= total) return;
@@ -393,8 +459,10 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
     int b = (int)(bt / T);
     float a = 0.f, g = 0.f;
     if (t >= Z) {
-        a = bf ? bf[b * bias_stride + o] : 0.f;        // bias_stride != 0: one bias row per clip (WN_EXEC_BIAS_PER_CLIP)
-        g = bg ? bg[b * bias_stride + o] : 0.f;
+        // bias_stride != 0: one bias row per clip (WN_EXEC_BIAS_PER_CLIP); fr.hop != 0: per (clip, frame of t)
+        const long long brow = b * bias_stride + bias_frame_off(fr, t) + o;
+        a = bf ? bf[brow] : 0.f;
+        g = bg ? bg[brow] : 0.f;
         const float* wf = Wf + (long long)o * Cr * fw;
         const float* wg = Wg + (long long)o * Cr * fw;
         for (int k = 0; k < fw; ++k) {
@@ -1090,10 +1158,10 @@ int generic_conv_bwd(const float* x, const float* W, const float* dout, float* d
 
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride) {
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride, BiasFrames frames) {
     long long tot = (long long)B * T * Cd;
     hipLaunchKernelGGL(k_gate_fwd, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
-                       gs, B, T, Cr, Cd, fw, d, Z, bias_stride);
+                       gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
     WN_LAUNCH_CHECK();
     long long N = (long long)B * T;
     hipLaunchKernelGGL(k_proj_res_fwd, dim3(cdiv(N * Cr, kThreads)), dim3(kThreads), 0, s, x, z, Wp, bp, out,
@@ -1120,7 +1188,7 @@ int generic_layer_bwd(const Call& c, const float* x, const float* f, const float
     if (dWf && (rc = conv_dw(x, dab, 2 * Cd, dWf, B, T, Cr, Cd, fw, d, Z, s))) return rc;
     if (dWg && (rc = conv_dw(x, dab + Cd, 2 * Cd, dWg, B, T, Cr, Cd, fw, d, Z, s))) return rc;
     if (c.bias_per_clip()) {
-        if ((rc = generic_colsum_per_clip(dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+        if ((rc = generic_colsum_bias_rows(c, dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, s))) return rc;
     } else {
         if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
         if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;
@@ -1148,7 +1216,7 @@ int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout,
                              int T, int Cr, int Cd, int Z, hipStream_t s) {
     int rc;
     if (c.bias_per_clip()) {
-        if ((rc = generic_colsum_per_clip(dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+        if ((rc = generic_colsum_bias_rows(c, dab, dab + Cd, 2 * Cd, B, T, Z, Cd, dbf, dbg, s))) return rc;
     } else {
         if (dbf && (rc = launch_colsum(dab, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbf, c.ws, c.room(), s))) return rc;
         if (dbg && (rc = launch_colsum(dab + Cd, (long long)T * 2 * Cd, 0, 2 * Cd, B, Z, T, Cd, dbg, c.ws, c.room(), s))) return rc;

@@ -32,13 +32,16 @@ __device__ __forceinline__ int ch_of(int s, int h) { return (s & 3) + 8 * (s >> 
 static constexpr int kWRow = 66;     // LDS row stride of W[i][.][.] (64 floats + 2: rows land on different banks)
 static constexpr int kPRow = 33;     // LDS row stride of Wp[i][.]
 
-template <int SAVE, bool HAS_BIAS>
+// FRAME (with HAS_BIAS; local conditioning): bf / bg hold a row per (clip, frame) and the accumulator seed is per lane -- a
+// lane owns one column, so it is the row of the lane's own frame.  A compile-time mode: without it the kernel is what it was.
+template <int SAVE, bool HAS_BIAS, bool FRAME = false>
 __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
     const float* __restrict__ x, const float* __restrict__ Wf, const float* __restrict__ bf,
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles, long long bstride) {            // bstride != 0: bf / bg are clip 0's rows, clip b's lie b * bstride floats on
+    int ntiles, long long bstride, BiasFrames fr) {   // bstride != 0: bf / bg are clip 0's rows, clip b's lie b * bstride floats
+                                                      // on; fr.hop != 0: a row per frame inside the clip's block (local conditioning)
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;      // time column inside the tile (B/D operand), weight row (A operand)
     const int h = lane >> 5;
@@ -136,10 +139,19 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
         const bool more = tile + stride < last;
         if (more) load_tile(tile + stride, xcn, xon);
         f32x16 aa, ag;
+        if (HAS_BIAS && FRAME) {       // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
+            const long long brow = b * bstride + bias_frame_off(fr, valid ? t : T - 1);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;      // a tile belongs to one clip
-            ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
+            for (int r = 0; r < 16; ++r) {
+                aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
+                ag[r] = bg ? bg[brow + ch_of(r, h)] : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;      // a tile belongs to one clip
+                ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
+            }
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
@@ -192,13 +204,13 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
 // others instead of under one sibling's.  No tile loop, no prefetch, no tile-count quantisation: a workgroup is four
 // consecutive tiles.
 // ---------------------------------------------------------------------------------------------
-template <int SAVE, bool HAS_BIAS>
+template <int SAVE, bool HAS_BIAS, bool FRAME = false>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     const float* __restrict__ x, const float* __restrict__ Wf, const float* __restrict__ bf,
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
     const float* __restrict__ bp, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles, long long bstride) {
+    int ntiles, long long bstride, BiasFrames fr) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
     const int h = lane >> 5;
@@ -254,10 +266,19 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     __syncthreads();
 
     f32x16 aa, ag;
+    if (HAS_BIAS && FRAME) {           // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
+        const long long brow = b * bstride + bias_frame_off(fr, tc);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;          // a tile belongs to one clip
-        ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
+            ag[r] = bg ? bg[brow + ch_of(r, h)] : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;          // a tile belongs to one clip
+            ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
+        }
     }
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
@@ -324,11 +345,17 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // 8 (r >> 2) + 4 h + (r & 3): the 16 values a lane needs per gate are four float4.  They are requested in front of the MFMA
 // block, land under it, and are added in fp32 AFTER the accumulator is rescaled -- fmaf(aa[r], uc, bias) -- so they never
 // pass through the tile's power-of-two scale or an fp16 split.  For t < Z neither the convolution nor the bias counts.
-template <int SAVE, bool COND>
+// COND is one of three compile-time modes: kCondNone, kCondClip (the above) and kCondFrame (local conditioning: clip b's row
+// becomes a block of rows fr.stride floats apart and a lane, which owns ONE time step, reads the row of its own frame
+// (tc + fr.phase) / fr.hop -- the same eight float4 requests; lanes of one frame read one address, so a wave fetches one row
+// per frame it spans.  The frame index is one plain 32-bit division per lane: a reciprocal multiply was not tried, the
+// kernel's time is its MFMA block and x traffic).
+enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2 };
+template <int SAVE, int COND>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     const float* __restrict__ x, const char* __restrict__ img_g, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
-    int ntiles, const float* __restrict__ bf, const float* __restrict__ bg, long long bstride) {
+    int ntiles, const float* __restrict__ bf, const float* __restrict__ bg, long long bstride, BiasFrames fr) {
     const int lane = threadIdx.x & 63;
     const int j = lane & 31;
     const int h = lane >> 5;
@@ -364,7 +391,8 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     }
     float4 cf[4], cg[4];
     if (COND) {
-        const long long rowb = (long long)b * bstride + 4 * h;
+        long long rowb = (long long)b * bstride + 4 * h;
+        if (COND == kCondFrame) rowb += (long long)((tc + fr.phase) / fr.hop) * fr.stride;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             cf[q] = *reinterpret_cast<const float4*>(bf + rowb + 8 * q);
@@ -698,7 +726,8 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live) {
     return c.fwd_t1_min_blocks > 0 && nt > 0 && (nt + 3) / 4 >= c.fwd_t1_min_blocks && nt < (1ll << 31);
 }
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
-                      int d, int Z, int t_live, hipStream_t s, const float* bf, const float* bg, long long bias_stride) {
+                      int d, int Z, int t_live, hipStream_t s, const float* bf, const float* bg, long long bias_stride,
+                      BiasFrames frames) {
     const int tile_lo = t_live > 0 ? t_live / 32 : 0;
     const int tiles_per_b = (T + 31) / 32 - tile_lo;
     const int ntiles = B * tiles_per_b;
@@ -707,18 +736,27 @@ int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float*
     const bool cond = bf != nullptr;
     if (cond)
         WN_CHECK_ARG(bg && bias_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(bf) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(bg) & 15) == 0,
+                         (reinterpret_cast<uintptr_t>(bg) & 15) == 0 && (frames.hop == 0 || frames.stride % 4 == 0),
                      "fp16 x 2 layer forward with per-clip bias rows: the rows must be 16-byte aligned and their stride a "
-                     "multiple of 4 floats (stride %lld)", bias_stride);
+                     "multiple of 4 floats (stride %lld, frame stride %lld)", bias_stride, frames.hop ? frames.stride : 0ll);
+    const int mode = !cond ? kCondNone : frames.hop > 0 ? kCondFrame : kCondClip;
 #define FWDH_LAUNCH(SAVE, COND)                                                                                            \
     hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
-                       tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride)
-    if (fs && cond) FWDH_LAUNCH(1, true);
-    else if (fs) FWDH_LAUNCH(1, false);
-    else if (gs && cond) FWDH_LAUNCH(2, true);
-    else if (gs) FWDH_LAUNCH(2, false);
-    else if (cond) FWDH_LAUNCH(0, true);
-    else FWDH_LAUNCH(0, false);
+                       tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
+#define FWDH_MODES(SAVE)                                        \
+    do {                                                        \
+        if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame);  \
+        else if (mode == kCondClip) FWDH_LAUNCH(SAVE, kCondClip); \
+        else FWDH_LAUNCH(SAVE, kCondNone);                      \
+    } while (0)
+    // (sigmoid-only saving, SAVE = 2, belongs to stacks whose backward recovers tanh: a stack with bias rows is never one, and
+    // wn_stack_fwd refuses the combination; the per-clip form is kept as it was, a per-frame one is not instantiated)
+    if (fs) FWDH_MODES(1);
+    else if (gs && mode == kCondFrame) { wn::set_error("fp16 x 2 layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+    else if (gs && mode == kCondClip) FWDH_LAUNCH(2, kCondClip);
+    else if (gs) FWDH_LAUNCH(2, kCondNone);
+    else FWDH_MODES(0);
+#undef FWDH_MODES
 #undef FWDH_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -746,8 +784,17 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     if (t1_min > 0 && blocks >= t1_min) {
 #define FWD1_LAUNCH(SAVE, BIAS)                                                                              \
     hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride)
-        if (fs && hb) FWD1_LAUNCH(1, true);
+                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
+        // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
+        const bool frame = hb && c.frames.hop > 0;
+        if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+        if (frame && fs)
+            hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<1, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
+                               B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+        else if (frame)
+            hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<0, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
+                               B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+        else if (fs && hb) FWD1_LAUNCH(1, true);
         else if (fs) FWD1_LAUNCH(1, false);
         else if (gs && hb) FWD1_LAUNCH(2, true);
         else if (gs) FWD1_LAUNCH(2, false);
@@ -760,8 +807,17 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     if (blocks > 512) blocks = 512;          // 256 CUs x 2 resident workgroups; waves stride over tiles
 #define FWD_LAUNCH(SAVE, BIAS)                                                                               \
     hipLaunchKernelGGL((k_layer_fwd_mfma32<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride)
-    if (fs && hb) FWD_LAUNCH(1, true);
+                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
+    // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
+    const bool frame = hb && c.frames.hop > 0;
+    if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+    if (frame && fs)
+        hipLaunchKernelGGL((k_layer_fwd_mfma32<1, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
+                           B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+    else if (frame)
+        hipLaunchKernelGGL((k_layer_fwd_mfma32<0, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
+                           B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+    else if (fs && hb) FWD_LAUNCH(1, true);
     else if (fs) FWD_LAUNCH(1, false);
     else if (gs && hb) FWD_LAUNCH(2, true);
     else if (gs) FWD_LAUNCH(2, false);

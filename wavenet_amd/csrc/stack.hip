@@ -45,6 +45,28 @@ static int check_bias_tables(const char* fn, const WnStackDesc* d, const WnExec*
         if (int rc = check_bias_rows(fn, ex, d->cd[l], tf[l], tg[l], names)) return rc;
     return WN_OK;
 }
+// Local conditioning: the descriptor's per-frame geometry (WnStackDesc.bias_hop / bias_phase / bias_frame_stride), checked
+// before any device work and handed to the call.  bias_hop == 0: one row per clip, the other two fields are not read.
+static int take_bias_frames(const char* fn, const WnStackDesc* d, const WnExec* ex, int T, Call& c) {
+    WN_CHECK_ARG(d->bias_hop >= 0, "%s: WnStackDesc.bias_hop = %d is negative", fn, d->bias_hop);
+    if (d->bias_hop == 0) return WN_OK;
+    WN_CHECK_ARG(ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP), "%s: WnStackDesc.bias_hop = %d without WN_EXEC_BIAS_PER_CLIP", fn,
+                 d->bias_hop);
+    WN_CHECK_ARG(d->bias_phase >= 0 && d->bias_phase < d->bias_hop, "%s: WnStackDesc.bias_phase = %d outside [0, bias_hop = %d)",
+                 fn, d->bias_phase, d->bias_hop);
+    for (int l = 0; l < d->n_layers; ++l)
+        WN_CHECK_ARG(d->bias_frame_stride >= d->cd[l], "%s: WnStackDesc.bias_frame_stride = %d below cd = %d (layer %d)", fn,
+                     d->bias_frame_stride, d->cd[l], l);
+    // (the kernels form t + bias_phase in 32 bits)
+    WN_CHECK_ARG((long long)T + d->bias_phase <= 2147483647ll, "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn,
+                 (long long)T + d->bias_phase);
+    const long long frames = ((long long)T + d->bias_phase + d->bias_hop - 1) / d->bias_hop;
+    WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
+                 "%s: the clip stride (WnExec.reserved = %d) is below %lld frames x bias_frame_stride = %d", fn, ex->reserved,
+                 frames, d->bias_frame_stride);
+    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride};
+    return WN_OK;
+}
 }  // namespace wn
 
 using namespace wn;
@@ -86,6 +108,7 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
     WN_CHECK_ARG(!g_only || chain_capable(c, d), "wn_stack_fwd: this stack's backward needs tanh saved (wn_stack_saves_tanh)");
     WN_CHECK_ARG(t_off >= 0 && t_off < T, "wn_stack_fwd: t_off outside [0,T)");
     if ((rc = check_bias_tables(__func__, d, ex, d->bf, d->bg, "bf and bg"))) return rc;
+    if ((rc = take_bias_frames(__func__, d, ex, T, c))) return rc;
     const bool per_clip = c.bias_per_clip();
     const size_t n = (size_t)B * T;
     const int L = d->n_layers;
@@ -124,6 +147,8 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
         if (ok && per_clip) {          // the COND kernels load a lane's biases as float4: refused here, never another path
             WN_CHECK_ARG(c.bias_stride % 4 == 0, "wn_stack_fwd: the fp16 x 2 layers need a bias row stride that is a multiple "
                                                  "of 4 floats (got %lld)", c.bias_stride);
+            WN_CHECK_ARG(c.frames.stride % 4 == 0, "wn_stack_fwd: the fp16 x 2 layers need a bias frame stride that is a "
+                                                   "multiple of 4 floats (got %lld)", c.frames.stride);
             for (int l = 0; l < L; ++l)
                 WN_CHECK_ARG(((reinterpret_cast<uintptr_t>(d->bf[l]) | reinterpret_cast<uintptr_t>(d->bg[l])) & 15) == 0,
                              "wn_stack_fwd: the fp16 x 2 layers need 16-byte aligned bias rows (layer %d)", l);
@@ -178,7 +203,7 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd_h2(in, h2img, l, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr, B, T,
                                        d->dilation[l], Z, live[l], as_stream(stream), per_clip ? d->bf[l] : nullptr,
-                                       per_clip ? d->bg[l] : nullptr, c.bias_stride);
+                                       per_clip ? d->bg[l] : nullptr, c.bias_stride, c.frames);
             } else if (live[l] > 0 || g_only) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd(c, in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr,
@@ -214,6 +239,7 @@ int wn_stack_bwd(const WnStackDesc* d, const float* x, const float* xs, const fl
     WN_CHECK_ARG(B > 0 && T > 0 && t_off >= 0 && t_off < T, "wn_stack_bwd: non-positive size or t_off outside [0,T)");
     if ((rc = check_bias_tables(__func__, d, ex, dbf, dbg, "dbf and dbg"))) return rc;
     Call c(ex);
+    if ((rc = take_bias_frames(__func__, d, ex, T, c))) return rc;
     // ---- chained path: every layer on the MFMA kernels and no conv / projection bias GRADIENTS asked for.  It is the only
     // path that recovers tanh from z / sigmoid, so f may be NULL exactly when it is taken (a desc without biases but with
     // non-NULL dbf / dbg / dbp tables takes the per-layer path, which reads f).

@@ -21,15 +21,16 @@ namespace wn {
 // the GEMMs in front then ran without a bias
 __global__ void k_wide_gate(float* __restrict__ a, float* __restrict__ g, float* __restrict__ z, float* __restrict__ fs,
                             float* __restrict__ gs, long long n4, int T, int Cd, int Z, const float* __restrict__ bf,
-                            const float* __restrict__ bg, long long bias_stride) {
+                            const float* __restrict__ bg, long long bias_stride, BiasFrames fr) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // float4 index
     if (i >= n4) return;
     const long long bt = i * 4 / Cd;
     const int t = (int)(bt % T);
     float4 av = reinterpret_cast<const float4*>(a)[i], gv = reinterpret_cast<const float4*>(g)[i];
     if (bf) {
-        const float* rf = bf + (bt / T) * bias_stride + (i * 4 - bt * Cd);
-        const float* rg = bg + (bt / T) * bias_stride + (i * 4 - bt * Cd);
+        const long long brow = (bt / T) * bias_stride + bias_frame_off(fr, t) + (i * 4 - bt * Cd);   // (clip, frame of t)
+        const float* rf = bf + brow;
+        const float* rg = bg + brow;
         av.x += rf[0]; av.y += rf[1]; av.z += rf[2]; av.w += rf[3];
         gv.x += rg[0]; gv.y += rg[1]; gv.z += rg[2]; gv.w += rg[3];
     }
@@ -120,7 +121,7 @@ int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, co
     if (rc) return rc;
     const long long n4 = (long long)B * T * Cd / 4;
     hipLaunchKernelGGL(k_wide_gate, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z,
-                       per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride);
+                       per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride, c.frames);
     WN_LAUNCH_CHECK();
     CGArgs a{};
     base_args(a, B, T);
@@ -210,7 +211,7 @@ static int wide_layer_bwd_256(Call& c, const float* x, const float* f, const flo
         if ((rc = launch_wgrad(c, a, Cr, s))) return rc;
     }
     if (c.bias_per_clip()) {
-        if ((rc = generic_colsum_per_clip(dadg, dadg + Cd, 2 * Cd, B, T, 0, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+        if ((rc = generic_colsum_bias_rows(c, dadg, dadg + Cd, 2 * Cd, B, T, 0, Cd, dbf, dbg, s))) return rc;
     } else {
         if (dbf && (rc = generic_colsum(dadg, B, T, 0, 2 * Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
         if (dbg && (rc = generic_colsum(dadg + Cd, B, T, 0, 2 * Cd, Cd, dbg, c.ws, c.room(), s))) return rc;
@@ -270,7 +271,7 @@ int wide_layer_bwd(Call& c, const float* x, const float* f, const float* g, cons
         }
     }
     if (c.bias_per_clip()) {                                                                       // da, dg are already 0 for t < Z
-        if ((rc = generic_colsum_per_clip(da, dg, Cd, B, T, 0, Cd, dbf, dbg, c.bias_stride, s))) return rc;
+        if ((rc = generic_colsum_bias_rows(c, da, dg, Cd, B, T, 0, Cd, dbf, dbg, s))) return rc;
     } else {
         if (dbf && (rc = generic_colsum(da, B, T, 0, Cd, Cd, dbf, c.ws, c.room(), s))) return rc;
         if (dbg && (rc = generic_colsum(dg, B, T, 0, Cd, Cd, dbg, c.ws, c.room(), s))) return rc;

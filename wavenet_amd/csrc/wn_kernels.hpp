@@ -9,6 +9,12 @@ struct StepPlan;
 int check_precision(const char* fn, const WnExec* ex);   // WN_EARG + error text unless ex is NULL or its precision is 0 .. 3
 // WN_EXEC_BIAS_PER_CLIP: WN_EARG + error text unless the stride covers a row of Cd floats and both rows are given
 int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f, const void* row_g, const char* names);
+// Local conditioning (WnStackDesc.bias_hop > 0 under WN_EXEC_BIAS_PER_CLIP): a clip's bias row becomes a block of rows, one per
+// frame of `hop` positions, `stride` floats apart; position t reads frame (t + phase) / hop.  hop == 0: one row per clip.
+struct BiasFrames { int hop, phase; long long stride; };
+__host__ __device__ __forceinline__ long long bias_frame_off(const BiasFrames& fr, int t) {
+    return fr.hop ? (long long)((t + fr.phase) / fr.hop) * fr.stride : 0;
+}
 struct Call {
     explicit Call(const WnExec* ex);     // ex == NULL: bf16x3, no flags, no scratch, no plan
     int precision;                       // WN_GEMM_*; WN_GEMM_FP32 under WN_EXEC_FORCE_GENERIC
@@ -18,6 +24,7 @@ struct Call {
     int fwd_t1_min_blocks;               // WnExec.fwd_t1_min_blocks with the default (512) filled in
     StepPlan* plan;                      // WnExec.plan, or NULL
     long long bias_stride;               // WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bf / bg (dbf / dbg) rows; else 0
+    BiasFrames frames = {0, 0, 0};       // set by wn_stack_fwd / wn_stack_bwd from the descriptor (per-frame rows); else hop == 0
 
     static constexpr size_t kTail = 256;
     bool flag(unsigned f) const { return (flags & f) != 0; }
@@ -70,7 +77,8 @@ int generic_conv_bwd(const float*, const float*, const float*, float*, float*, f
                      int, int, hipStream_t);
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0);
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0,
+                      BiasFrames frames = {0, 0, 0});
 int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
@@ -131,7 +139,7 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live);
 // bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, bias_stride % 4 == 0), the COND kernels
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
                       int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr,
-                      long long bias_stride = 0);
+                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0});
 int mfma_layer_fwd_group_len(const int* dil, int l0, int L);   // layers from l0 on that one group launch can chain
 int mfma_layer_fwd_h2_group(const float* x, const void* img, int l0, int nl, float* const* outs, float* const* zs,
                             float* const* fs, float* const* gs, const int* dil, const int* Zs, int B, int T, hipStream_t s);
@@ -170,6 +178,13 @@ int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout,
 // launch for both gates, the summation order of the shared-bias column sums of a B = 1 call, no atomics, no scratch
 int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
                             long long stride, hipStream_t s);
+// The same with a row per (clip, frame): dbf[b * stride + f * fr.stride + m] += the sum over the t in [tmin, T) with
+// (t + fr.phase) / fr.hop == f, in a fixed order (k_colsum_per_frame); rows of frames wholly below tmin are not touched
+int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
+                             long long stride, BiasFrames fr, hipStream_t s);
+// what the layer backwards call: the per-frame form when c.frames.hop > 0, the per-clip form otherwise
+int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
+                             float* dbf, float* dbg, hipStream_t s);
 
 // ---- wide_layer.hip: residual layer for any Cr, Cd multiple of 32 and any fw, composed from the channel GEMMs
 bool wide_layer_supported(int Cr, int Cd, int fw);

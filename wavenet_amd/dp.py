@@ -68,7 +68,9 @@ class DataParallel(object):
     def shard(self, global_batch: int):
         """Clip indices [lo, hi) of this rank for a global batch (equal shards).  A globally conditioned model's class ids are
         per clip, so they are sharded with the clips: rank r trains ``x[lo:hi]`` under ``condition=ids[lo:hi]``; the two
-        conditioning tensors live in the flat arena and travel in the one all-reduce like every other gradient."""
+        conditioning tensors live in the flat arena and travel in the one all-reduce like every other gradient.  A locally
+        conditioned model's features are per clip too and are sharded the same way: ``local=feats[lo:hi]``; its projection
+        lives in the arena as well."""
         if global_batch % self.world:
             raise ValueError("global batch %d is not divisible by world size %d" % (global_batch, self.world))
         per = global_batch // self.world

@@ -41,7 +41,7 @@ class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
-                 condition_classes: int = 0, condition_channels: int = 0):
+                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0):
         self._dec = None
         self._dec_keep = None
         self._dec_stale = True
@@ -49,13 +49,15 @@ class FasterWaveNet(WaveNet):
         self._batch_decs = []              # decoder handles of generate_batch (one per utterance), created on demand
         self._batch_stale = []
         self._batch_class = []
+        self._dec_table = False            # locally conditioned model: whether the batch-1 handle holds a frame table
         self.prev_causal_outputs = None
         self.prev_residual_outputs = None
         self.keep_window = True            # keep the logits of the whole window on the device: _forward_one_step's reference shape
         self._hist = None                  # (W, Q) ring of ELU-head logits, oldest column at _hist_pos
         self._hist_pos = 0
         super().__init__(params, compat_zero_prefix=compat_zero_prefix, seed=seed, storage=storage,
-                         condition_classes=condition_classes, condition_channels=condition_channels)
+                         condition_classes=condition_classes, condition_channels=condition_channels,
+                         local_channels=local_channels, local_hop=local_hop)
 
     def __del__(self):
         try:
@@ -72,8 +74,11 @@ class FasterWaveNet(WaveNet):
         self._batch_stale = [True] * len(getattr(self, "_batch_decs", []))
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self, cond=None):
-        """``cond``: [(bf, bg)] per residual layer (``condition_biases``) -- a globally conditioned model's handle holds ONE
+    def _desc(self, cond=None, table=None):
+        """``table``: (rows (n, sum 2 cd) float32 on the device, hop, phase) -- a locally conditioned model's handle copies one
+        utterance's frame table (``WnDecoderDesc.frame_bias``) at create / update time and counts its steps from there; such
+        handles are any-shape ones too.
+        ``cond``: [(bf, bg)] per residual layer (``condition_biases``) -- a globally conditioned model's handle holds ONE
         class's folded gate biases, copied like any bias at create / update time.  Biased layers select the any-shape decoder
         (one workgroup per utterance): a conditioned model of config 4's shape does not get the nine-workgroup kernel."""
         p = self.params
@@ -100,7 +105,42 @@ class FasterWaveNet(WaveNet):
             setattr(d, k, C.cast(keep[k], C.POINTER(C.c_void_p)))
         d.head_act = ACT[self.fast_head_activation]
         d.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        if table is not None:
+            rows, hop, phase = table
+            keep["table"] = rows
+            d.frame_bias, d.n_frames, d.frame_stride = rows.data_ptr(), int(rows.shape[0]), int(rows.shape[1])
+            d.frame_hop, d.frame_phase = int(hop), int(phase)
         return d, keep
+
+    # -- local conditioning: one utterance's features -> what the prefill and the decoder handle take ------------------------
+    def _utterance_local(self, local, local_phase, W, n_samples, what="generate"):
+        """``local=`` (F, n) of one utterance, covering it from its first sample (prompt included), ``local_phase`` the
+        position of that sample inside column 0 -> (features (1, F, n) on the device, phase) or (None, 0).  Raises when the
+        features do not cover the W prompt positions and the n_samples - 1 decoded ones -- before anything runs."""
+        if not self.local_channels:
+            self._local_features(local, 1, W, local_phase)                    # raises when features were given
+            return None, 0
+        if local is not None and not isinstance(local, torch.Tensor):
+            local = np.asarray(local, dtype=np.float32)
+        if local is not None and len(local.shape) == 2:
+            local = local[None]
+        total = W + max(int(n_samples) - 1, 0)
+        try:
+            return self._local_features(local, 1, total, local_phase)
+        except Exception as e:
+            if local is None or "feature columns" not in str(e):
+                raise
+            raise Exception("%s: the features cover fewer samples than asked for (%d prompt + %d generated): %s"
+                            % (what, W, max(int(n_samples) - 1, 0), e))
+
+    def _decoder_table(self, feats, phase, W):
+        """The decoder's table after a prefill over W positions: the step that consumes the sample at absolute position
+        p = phase + W + k reads column p // hop, so the handle gets the rows from column (phase + W) // hop on and the phase
+        (phase + W) % hop."""
+        col, ph = divmod(int(phase) + int(W), self.local_hop)
+        rows = self.local_biases(feats[0], phase)
+        col = min(col, int(rows.shape[0]) - 1)            # (n_samples == 1: nothing is decoded, any row will do)
+        return rows[col:].contiguous(), self.local_hop, ph
 
     def _class_id(self, condition):
         """``condition=`` of the batch-1 methods (an id, or a sequence holding one) -> int, or None for an unconditioned model."""
@@ -112,52 +152,65 @@ class FasterWaveNet(WaveNet):
         ids = self._condition_ids(None if condition is None else [int(condition)], 1)
         return None if ids is None else int(condition)
 
-    def _decoder(self, class_id=None):
-        """The batch-1 handle; for a conditioned model holding ``class_id``'s biases (default: the class it holds already)."""
+    def _decoder(self, class_id=None, table=None):
+        """The batch-1 handle; for a conditioned model holding ``class_id``'s biases (default: the class it holds already); for
+        a locally conditioned one ``table`` (``_decoder_table``) is copied into it and its step count starts again (default:
+        the table it holds, continued)."""
         lib = _lib.lib()
+        if self.local_channels and table is None and not self._dec_table:
+            raise Exception("this model is locally conditioned: prefill with local= first")
         if self.condition_classes and class_id is None:
             class_id = self._dec_class
             if class_id is None:
                 raise Exception("this model is globally conditioned: prefill with condition= first")
         cond = None
-        if self.condition_classes and (self._dec is None or self._dec_stale or self._dec_class != class_id):
+        if self.local_channels and table is None and self._dec_stale:
+            raise Exception("the weights changed since the last prefill: prefill with local= again")
+        if self.condition_classes and (self._dec is None or self._dec_stale or self._dec_class != class_id or table is not None):
             cond = self.condition_biases(class_id)
         if self._dec is None:
-            d, keep = self._desc(cond)
+            d, keep = self._desc(cond, table)
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
             self._dec, self._dec_stale, self._dec_class = h, False, class_id
-        elif self._dec_stale or self._dec_class != class_id:
-            d, keep = self._desc(cond)
+        elif self._dec_stale or self._dec_class != class_id or table is not None:
+            d, keep = self._desc(cond, table)
             check(lib.wn_decoder_update_weights(self._dec, C.byref(d), stream_ptr()), "wn_decoder_update_weights")
             self._dec_stale, self._dec_class = False, class_id
+        if table is not None:
+            self._dec_table = True
         return self._dec
 
     # -- the reference's face -------------------------------------------------------------------
-    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None):
+    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None, local=None, local_phase=0):
         """Full forward over the window that also seeds the decoder state (faster_wavenet.py:13-47).  ``condition``: the
         utterance's class id (globally conditioned models): the prefill runs the ordinary forward with it and the decoder
-        handle is created or updated with that class's folded biases."""
+        handle is created or updated with that class's folded biases.  ``local`` / ``local_phase`` (locally conditioned
+        models): the utterance's features (F, n) from the window's first sample on -- as many columns as the steps that follow
+        will read -- and the position of that sample inside column 0; the prefill runs the ordinary forward over the window
+        with them, and the handle receives the table of the columns behind the window (``local_alignment``'s rule)."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
         if x.shape[0] != 1:
             raise Exception("FasterWaveNet generates one utterance at a time (batch 1), like the reference")
         class_id = self._class_id(condition)
+        feats, phase = self._utterance_local(local, local_phase, int(x.shape[1] if x.dim() == 2 else x.shape[3]), 1, "forward_one_step")
         storage, self.storage = self.storage, "fp32"               # the decoder state is seeded from fp32 activations
         try:
-            return self._prefill(x, apply_softmax, as_numpy, class_id)
+            return self._prefill(x, apply_softmax, as_numpy, class_id, feats, phase)
         finally:
             self.storage = storage
 
-    def _prefill(self, x, apply_softmax, as_numpy, class_id=None):
+    def _prefill(self, x, apply_softmax, as_numpy, class_id=None, feats=None, phase=0):
         with torch.no_grad():
             causal_output = self.forward_causal_block(x)
-            _, sum_skip = self.forward_residual_block(causal_output, condition=None if class_id is None else [class_id])
+            _, sum_skip = self.forward_residual_block(causal_output, condition=None if class_id is None else [class_id],
+                                                      local=feats, local_phase=phase)
             out = self.forward_softmax_block(sum_skip, apply_softmax=apply_softmax)
             self._last_sum_skip = sum_skip                                       # generate(): the first row under a temperature
             tokens = (x if not x.is_floating_point() else x[:, :, 0, :].argmax(dim=1)).to(torch.int32).contiguous()
             W = tokens.shape[1]
-            dec = self._decoder(class_id)
+            dec = self._decoder(class_id, None if feats is None else self._decoder_table(feats, phase, W))
             check(_lib.lib().wn_decoder_load_state(
                 dec, ptr(tokens), W, ptr_array([t.contiguous() for t in self._last_causal_outputs]),
                 ptr_array(self._last_layer_inputs), stream_ptr()), "wn_decoder_load_state")
@@ -244,7 +297,7 @@ class FasterWaveNet(WaveNet):
         return out
 
     def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False,
-                 temperature=1.0, top_k=0, top_p=1.0, condition=None):
+                 temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, local_phase=0):
         """Emit ``n_samples`` tokens.  Step 1 is the full forward over the initial window (ReLU head,
         like the reference's first ``_forward_one_step`` call); steps 2.. run inside one persistent
         kernel with the ELU head.  ``uniforms[i]`` is the float64 draw numpy's ``choice`` would make
@@ -255,7 +308,11 @@ class FasterWaveNet(WaveNet):
         run is the one it was before they existed, bit for bit.
 
         ``condition``: the class id (speaker) of a globally conditioned model.  Tokens and probabilities are those of an
-        ordinary biased model holding ``condition_biases(condition)``, bit for bit."""
+        ordinary biased model holding ``condition_biases(condition)``, bit for bit.
+
+        ``local`` (locally conditioned models): the utterance's (F, n) features from its first sample on, prompt included;
+        ``local_phase``: where that sample lies inside column 0.  Generating more samples than the features cover raises
+        before anything runs."""
         p = self.params
         Q = p.quantization_steps
         iw = self.input_width
@@ -268,11 +325,13 @@ class FasterWaveNet(WaveNet):
         u = torch.as_tensor(np.asarray(uniforms, dtype=np.float64)).to(self.device)
         if u.numel() < n_samples:
             raise Exception("need one uniform per emitted sample")
+        feats, phase = self._utterance_local(local, local_phase, int(tok.shape[1]), n_samples)
         lib = _lib.lib()
         self.prev_causal_outputs = None
         keep, self.keep_window = self.keep_window, False             # the run below never builds the window (and drops it)
         try:
-            p0 = self.forward_one_step(tok, apply_softmax=True, condition=class_id)      # (1,Q,1,W)
+            p0 = self.forward_one_step(tok, apply_softmax=True, condition=class_id, local=None if feats is None else feats[0],
+                                       local_phase=phase)      # (1,Q,1,W)
         finally:
             self.keep_window = keep
         first_prob = self._first_row(self._last_sum_skip, p0, temperature)
@@ -308,7 +367,8 @@ class FasterWaveNet(WaveNet):
                 self._Cr == 32 and self._Cs == 256 and list(p.softmax_conv_channels) == [256, 256] and len(L) <= 128 and
                 all(int(c) == 32 for c in p.residual_conv_channels) and self.causal_conv_layers[0].bshape is None and
                 all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)) and
-                not self.condition_classes)          # a conditioned model's handles hold gate biases: the any-shape decoder
+                not self.condition_classes and      # a conditioned model's handles hold gate biases: the any-shape decoder
+                not self.local_channels)             # ... and a locally conditioned model's a frame table
 
     def _batch_prompts(self, initial_tokens, N):
         """``generate_batch``'s ``initial_tokens`` -> (the distinct windows, 1-D int32 each; the window index of every
@@ -341,7 +401,7 @@ class FasterWaveNet(WaveNet):
         return prompts, which
 
     def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
-                       condition=None):
+                       condition=None, local=None, local_phase=0):
         """``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
         (N, n_samples) int32 tokens on the device.  ``initial_tokens``: None (silence), one 1-D window for every utterance, or
         an (N, W) integer array -- a prompt per utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a
@@ -361,7 +421,12 @@ class FasterWaveNet(WaveNet):
         Every handle owns its packed weights, so utterance u's handle simply holds ``condition_biases(condition[u])``; such
         handles are any-shape ones (one workgroup per utterance, up to 1,024 per launch -- a conditioned model of config 4's
         shape does not get the nine-workgroup kernel), one prefill runs per distinct (window, class) pair, and
-        ``same_weights`` is 0 when the ids differ."""
+        ``same_weights`` is 0 when the ids differ.
+
+        ``local`` / ``local_phase`` (locally conditioned models): one (F, n) array for all utterances or a list of one per
+        utterance, each covering its utterance from its first sample on, prompt included; the phases likewise.  Every
+        handle copies its utterance's table, one prefill runs per distinct (window, class, features, phase), and
+        ``same_weights`` is 0 when the tables differ."""
         p = self.params
         Q = p.quantization_steps
         u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
@@ -386,27 +451,54 @@ class FasterWaveNet(WaveNet):
         else:
             self._condition_ids(condition, N)                                     # raises when ids were given
             cids = [None] * N
+        # local conditioning: utterance i's features are locs[lid[i]] (distinct arrays, by identity) at phase phs[i]
+        if isinstance(local, (list, tuple)):
+            if len(local) != N:
+                raise Exception("generate_batch: local= holds %d feature arrays for %d utterances" % (len(local), N))
+            per = list(local)
+        else:
+            per = [local] * N
+        phs = [int(v) for v in sampling.per_utterance(local_phase, N, "local_phase")]
+        locs, lid, seen_l = [], [], {}
+        for i in range(N):
+            if id(per[i]) not in seen_l:
+                seen_l[id(per[i])] = len(locs)
+                locs.append(per[i])
+            lid.append(seen_l[id(per[i])])
+        W_of = [int(prompts[k].shape[0]) for k in which]
+        lfeats = {}
+        for i in range(N):                                                    # every check before any work
+            key = (which[i], lid[i], phs[i])
+            if key not in lfeats:
+                lfeats[key] = self._utterance_local(locs[lid[i]], phs[i], W_of[i], n_samples, "generate_batch")
         # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
         # decided BEFORE any work is done
         flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         nine = self._nine_workgroup_shape(flags)
         if nine and (n_samples == 2 or flags & _lib.WN_DECODER_ONE_WORKGROUP):
-            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids)
+            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids, per, phs)
         limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
         u = torch.as_tensor(u_np).to(self.device)
         run = n_samples > 1
         biases = {c: self.condition_biases(c) for c in sorted(set(cids))} if run and self.condition_classes else {None: None}
+        fresh = set()                                     # handles created in this call hold their weights and table already
         while run and len(self._batch_decs) < N:
-            c = cids[len(self._batch_decs)]
-            d, keep = self._desc(biases[c])
+            i = len(self._batch_decs)
+            fresh.add(i)
+            c = cids[i]
+            ft, ph = lfeats[(which[i], lid[i], phs[i])]       # (a handle is created WITH its table: that selects the any-shape decoder)
+            d, keep = self._desc(biases[c], None if ft is None else self._decoder_table(ft, ph, W_of[i]))
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
             self._batch_decs.append(h)
             self._batch_stale.append(False)
             self._batch_class.append(c)
         for i in range(N if run else 0):
-            if self._batch_stale[i] or self._batch_class[i] != cids[i]:
-                d, keep = self._desc(biases[cids[i]])
+            # (a locally conditioned model's other handles are updated in every call: the table and its step count belong to the
+            # utterance, and the library's one way to set them is wn_decoder_update_weights, which also re-packs the weights)
+            if i not in fresh and (self._batch_stale[i] or self._batch_class[i] != cids[i] or self.local_channels):
+                ft, ph = lfeats[(which[i], lid[i], phs[i])]
+                d, keep = self._desc(biases[cids[i]], None if ft is None else self._decoder_table(ft, ph, W_of[i]))
                 check(lib.wn_decoder_update_weights(self._batch_decs[i], C.byref(d), stream_ptr()), "wn_decoder_update_weights")
                 self._batch_stale[i], self._batch_class[i] = False, cids[i]
             check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
@@ -414,19 +506,22 @@ class FasterWaveNet(WaveNet):
         # from it, and its first row (one per distinct temperature) is what generate() draws the first token from
         self.prev_causal_outputs = None
         rows = {}
-        for k, cid in sorted({(which[i], cids[i]) for i in range(N)}, key=lambda kc: (kc[0], -1 if kc[1] is None else kc[1])):
+        for k, cid, li, ph in sorted({(which[i], cids[i], lid[i], phs[i]) for i in range(N)},
+                                     key=lambda kc: (kc[0], -1 if kc[1] is None else kc[1], kc[2], kc[3])):
             prompt = prompts[k]
+            ft = lfeats[(k, li, ph)][0]
             tok = torch.as_tensor(prompt.reshape(1, -1)).to(self.device)
             storage, self.storage = self.storage, "fp32"
             try:
                 with torch.no_grad():
                     causal_output = self.forward_causal_block(tok)
-                    _, sum_skip = self.forward_residual_block(causal_output, condition=None if cid is None else [cid])
+                    _, sum_skip = self.forward_residual_block(causal_output, condition=None if cid is None else [cid],
+                                                              local=ft, local_phase=ph)
                     p0 = self.forward_softmax_block(sum_skip, apply_softmax=True)
             finally:
                 self.storage = storage
             tokens = tok.to(torch.int32).contiguous()
-            mine = [i for i in range(N) if which[i] == k and cids[i] == cid]
+            mine = [i for i in range(N) if which[i] == k and cids[i] == cid and lid[i] == li and phs[i] == ph]
             if run:
                 causal_outs = ptr_array([t.contiguous() for t in self._last_causal_outputs])
                 layer_ins = ptr_array(self._last_layer_inputs)
@@ -434,16 +529,16 @@ class FasterWaveNet(WaveNet):
                     check(lib.wn_decoder_load_state(self._batch_decs[i], ptr(tokens), tokens.shape[1], causal_outs, layer_ins,
                                                     stream_ptr()), "wn_decoder_load_state")
             for t in sorted({temps[i] for i in mine}):
-                rows[(k, cid, t)] = self._first_row(sum_skip, p0, t)
+                rows[(k, cid, li, ph, t)] = self._first_row(sum_skip, p0, t)
         out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
         first = torch.empty((N,), device=self.device, dtype=torch.int32)
         u0 = u[:, 0].contiguous()
         if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
-            first_prob = torch.cat([rows[(which[i], cids[i], temps[i])] for i in range(N)], dim=0).contiguous()
+            first_prob = torch.cat([rows[(which[i], cids[i], lid[i], phs[i], temps[i])] for i in range(N)], dim=0).contiguous()
             check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
         else:
             for i in range(N):                                       # the truncation per utterance, as generate() draws
-                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], cids[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
+                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], cids[i], lid[i], phs[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
                                                          Q, top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
         out[:, 0] = first
         if run:
@@ -454,13 +549,15 @@ class FasterWaveNet(WaveNet):
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
             if len(set(cids)) > 1:
                 same = 0                                              # ... but hold different classes' biases
+            if self.local_channels and len({(which[i], lid[i], phs[i]) for i in range(N)}) > 1:
+                same = 0                                              # ... or different frame tables
             for c0 in range(0, N, limit):                             # launches of at most `limit`, one after another
                 c1 = min(N, c0 + limit)
                 rc = lib.wn_decoder_run_batch((C.c_void_p * (c1 - c0))(*[h.value for h in self._batch_decs[c0:c1]]), c1 - c0,
                                               (C.c_int32 * (c1 - c0))(*firsts[c0:c1]), ptr_array(rest[c0:c1]), n_samples - 1,
                                               ptr_array(outs[c0:c1]), None, same, stream_ptr())
                 if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
-                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids)
+                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids, per, phs)
                 check(rc, "wn_decoder_run_batch")
             for i in range(N if nine else 1):                         # any-shape: nothing can give up; one synchronise
                 check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
@@ -469,9 +566,10 @@ class FasterWaveNet(WaveNet):
                     out[i, 1:] = outs[i]
         return out
 
-    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p, cids):
+    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p, cids, locals_, phases):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
         ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls by
         definition)."""
         return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=prompts[which[i]], temperature=temperature[i],
-                                          top_k=top_k[i], top_p=top_p[i], condition=cids[i]) for i in range(u_np.shape[0])])
+                                          top_k=top_k[i], top_p=top_p[i], condition=cids[i], local=locals_[i],
+                                          local_phase=phases[i]) for i in range(u_np.shape[0])])

@@ -11,7 +11,11 @@ What changes from step to step lives in device memory, never in kernel arguments
   * the rate 1 - decay_t of the weight average (``WaveNet.enable_ema``), likewise;
   * the class ids of a globally conditioned model: a static buffer next to the batch's.  The conditioning node and the
     per-clip bias rows it feeds are captured with the step; the step plan holds weight images only, never a bias pointer, so a
-    conditioned step runs WITH the plan.
+    conditioned step runs WITH the plan;
+  * the features of a locally conditioned model: a static (B, F, n) buffer that ``step(local=)`` refills.  The projection node
+    and the per-frame bias block are captured with the step, likewise WITH the plan.  The phase is a field of the stack
+    descriptor -- a kernel argument, not device memory -- so it is fixed at capture; ``step(local_phase=)`` with another value
+    raises (training draws clip starts at multiples of the hop: phase 0).
 With data parallelism the gradient all-reduce stays OUTSIDE the graphs (forward+backward graph -> RCCL all-reduce ->
 optimiser graph), so nothing here depends on capturing a collective.
 """
@@ -23,12 +27,14 @@ from . import _lib
 from .ema import ema_rate_at
 
 
-def default_loss(net, x, tgt, window_only: bool = False, condition=None):
+def default_loss(net, x, tgt, window_only: bool = False, condition=None, local=None, local_phase: int = 0):
     """train_audio/train.py:60-75: loss over the last ``tgt.shape[1]`` columns of the window.  ``window_only`` also skips
     the columns that window cannot see (WaveNet.forward_residual_block); same loss, same gradients.  ``condition``: one class
-    id per clip, for a globally conditioned model."""
+    id per clip, for a globally conditioned model; ``local`` / ``local_phase``: the clips' features and phase, for a locally
+    conditioned one."""
     c = net.forward_causal_block(x)
-    _, s = net.forward_residual_block(c, t_off=x.shape[1] - tgt.shape[1], window_only=window_only, condition=condition)
+    _, s = net.forward_residual_block(c, t_off=x.shape[1] - tgt.shape[1], window_only=window_only, condition=condition,
+                                      local=local, local_phase=local_phase)
     # forward_softmax_block(apply_softmax=False) + cross_entropy, the last head convolution and the loss in one launch where covered
     return net.head_cross_entropy(s, tgt)
 
@@ -37,10 +43,13 @@ class TrainStepGraph(object):
     """``g = TrainStepGraph(net, x, tgt); loss = g.step(x, tgt)`` -- same result as
     ``net.backprop(default_loss(net, x, tgt))`` for batches of the captured shape."""
 
-    def __init__(self, net, x, tgt, loss_fn=default_loss, warmup: int = 2, keep_graph: bool = False, condition=None):
+    def __init__(self, net, x, tgt, loss_fn=default_loss, warmup: int = 2, keep_graph: bool = False, condition=None,
+                 local=None, local_phase: int = 0):
         """``keep_graph``: keep the captured hipGraph_t next to the executable graph so that :meth:`node_counts` can walk it
         (measurement aid: bench.py counts the kernel nodes of the step it times).  ``condition``: one class id per clip for a
-        globally conditioned model; ``loss_fn`` is then called with ``condition=`` the static id buffer."""
+        globally conditioned model; ``loss_fn`` is then called with ``condition=`` the static id buffer.  ``local`` /
+        ``local_phase``: the clips' features (B, F, n) and phase for a locally conditioned model; ``loss_fn`` is then called
+        with ``local=`` the static feature buffer and ``local_phase=`` the captured phase."""
         if not (net.gpu_enabled and x.is_cuda and tgt.is_cuda):
             raise _lib.WaveNetHipError("TrainStepGraph needs the network and the batch on a HIP device")
         self.net, self.loss_fn = net, loss_fn
@@ -48,6 +57,8 @@ class TrainStepGraph(object):
         self.tgt = tgt.clone()
         ids = net._condition_ids(condition, int(x.shape[0]))          # raises when the model and the argument disagree
         self.condition = None if ids is None else ids.clone()
+        feats, self.local_phase = net._local_features(local, int(x.shape[0]), int(x.shape[1]), local_phase)   # raises likewise
+        self.local = None if feats is None else feats.clone()
         opt = net.optimizer
         self._lr = torch.zeros((1,), device=x.device, dtype=torch.float32)
         self._ema_rate = torch.zeros((1,), device=x.device, dtype=torch.float32)      # 0: the warm-up steps leave the average alone
@@ -135,10 +146,12 @@ class TrainStepGraph(object):
             self.net._unit_upstream = False
 
     def _fwd_bwd_body(self):
-        if self.condition is None:
-            loss = self.loss_fn(self.net, self.x, self.tgt)
-        else:
-            loss = self.loss_fn(self.net, self.x, self.tgt, condition=self.condition)
+        kw = {}
+        if self.condition is not None:
+            kw["condition"] = self.condition
+        if self.local is not None:
+            kw["local"], kw["local_phase"] = self.local, self.local_phase
+        loss = self.loss_fn(self.net, self.x, self.tgt, **kw)
         # the upstream gradient of the loss is a tensor made ONCE (in the warm-up pass, outside the capture): `loss.backward()`
         # would fill a fresh one in every replay -- a kernel at the launch floor (4.6 us) for one float
         if self._one is None or self._one.shape != loss.shape:
@@ -152,10 +165,11 @@ class TrainStepGraph(object):
             self.net._ema_step(rate_dev=self._ema_rate)
         self.net._weights_changed()
 
-    def step(self, x=None, tgt=None, condition=None):
+    def step(self, x=None, tgt=None, condition=None, local=None, local_phase=None):
         """One training step on (x, tgt) (default: the batch already in the static buffers).  Returns the loss
         (a device scalar that the next step overwrites).  ``condition``: the clips' class ids (conditioned models; default: the
-        ids already in the static buffer)."""
+        ids already in the static buffer).  ``local``: the clips' features, of the captured shape (locally conditioned models;
+        default: those already in the static buffer); ``local_phase`` must be the captured one."""
         net, opt = self.net, self.net.optimizer
         if self._hyper() != self._snap:
             raise _lib.WaveNetHipError(
@@ -171,6 +185,17 @@ class TrainStepGraph(object):
             if self.condition is None:
                 raise _lib.WaveNetHipError("condition= was given, but the captured step is unconditioned")
             self.condition.copy_(self.net._condition_ids(condition, int(self.x.shape[0])), non_blocking=True)
+        if local_phase is not None and int(local_phase) != self.local_phase:
+            raise _lib.WaveNetHipError("local_phase = %d, but the step was captured with phase %d (the phase is a kernel "
+                                       "argument: capture another step)" % (int(local_phase), self.local_phase))
+        if local is not None:
+            if self.local is None:
+                raise _lib.WaveNetHipError("local= was given, but the captured step is not locally conditioned")
+            feats, _ = self.net._local_features(local, int(self.x.shape[0]), int(self.x.shape[1]), self.local_phase)
+            if tuple(feats.shape) != tuple(self.local.shape):
+                raise _lib.WaveNetHipError("local= is %s, but the step was captured with features of shape %s"
+                                           % (tuple(feats.shape), tuple(self.local.shape)))
+            self.local.copy_(feats, non_blocking=True)
         opt.t += 1                                   # update() is not called on replay: keep Adam's clock here
         self._lr.fill_(opt.lr)
         if net.ema_enabled:                          # the schedule's clock, like Adam's: it also advances for a step skipped on the device

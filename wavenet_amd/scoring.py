@@ -61,9 +61,14 @@ def summarize(nll) -> Dict[str, float]:
     return {"samples": int(a.size), "nats_per_sample": nats, "bits_per_sample": nats / math.log(2.0)}
 
 
-def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None):
+def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None, local=None):
     """(n,) float32 on the device: see the module text.  ``tokens``: a 1-D integer numpy array or tensor.  ``condition``: the
-    class id of the sequence (every piece of it), for a globally conditioned model."""
+    class id of the sequence (every piece of it), for a globally conditioned model.
+
+    ``local``: the sequence's (F, >= ceil(n / H)) features for a locally conditioned model (hop H): sample i of the sequence,
+    as a network input, reads column i // H (``local_alignment`` with s0 = the piece's first sample); the silence in front of
+    the first sample reads column 0.  The pieces of one launch share one phase, so ``chunk_width`` must be a multiple of H
+    (raises otherwise); the result still does not depend on ``chunk_width`` or ``batch_size`` beyond arithmetic."""
     import torch
     t = net.to_variable(np.asarray(tokens) if not isinstance(tokens, torch.Tensor) else tokens)
     if t.dim() != 1 or t.is_floating_point():
@@ -74,8 +79,25 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
     if condition is not None and np.ndim(condition) != 0:
         raise Exception("score: condition must be ONE class id (the sequence is one clip)")
     net._condition_ids(None if condition is None else [int(condition)], 1)      # raises on a mismatch before any work
-    out = torch.empty((n,), device=t.device, dtype=torch.float32)
     C = context_width(net.params)
+    ext = None
+    if getattr(net, "local_channels", 0):
+        H = net.local_hop
+        if local is None:
+            net._local_features(None, 1, 1)                                      # raises: a locally conditioned model needs features
+        if int(chunk_width) % H:
+            raise Exception("score: a locally conditioned model needs chunk_width %% local_hop == 0 (the pieces of one launch "
+                            "share a phase), got chunk_width = %d, hop = %d" % (int(chunk_width), H))
+        f = local if isinstance(local, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(local, dtype=np.float32)))
+        if f.dim() != 2:
+            raise Exception("score: local must be (F, frames) features of the one sequence, got %s" % (tuple(f.shape),))
+        f = net._local_features(f[None], 1, max(n, 1), 0)[0][0]                  # raises on channels, dtype or too few columns
+        pad_cols = (C + H - 1) // H                                              # the silence in front reads column 0
+        ext = torch.cat([f[:, :1].expand(f.shape[0], pad_cols), f], dim=1)
+        shift = pad_cols * H - C                                                 # input j of `s` below sits at extended position j + shift
+    elif local is not None:
+        net._local_features(local, 1, 1)                                         # raises: features for a model that takes none
+    out = torch.empty((n,), device=t.device, dtype=torch.float32)
     t = t.to(torch.int32)
     s = torch.cat([torch.full((C,), silence_token(net.params.quantization_steps), device=t.device, dtype=torch.int32), t])
     for launch in plan_chunks(n, int(chunk_width), int(batch_size)):
@@ -84,5 +106,11 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
         x = torch.stack([s[a:a + C - 1 + w] for a, _ in launch])
         tgt = torch.stack([t[a:a + w] for a, _ in launch])
         cond = None if condition is None else [int(condition)] * len(launch)
-        out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt, condition=cond).reshape(-1)
+        kw = {}
+        if ext is not None:
+            ph = (launch[0][0] + shift) % H
+            need = (C - 1 + w + ph + H - 1) // H
+            kw = dict(local=torch.stack([ext[:, (a + shift) // H:(a + shift) // H + need] for a, _ in launch]).contiguous(),
+                      local_phase=ph)
+        out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt, condition=cond, **kw).reshape(-1)
     return out

@@ -49,6 +49,16 @@ _SPEAKER_FLAGS = (
                                          "(p225_001.wav -> p225); the label table goes to <model-dir>/speakers.json"),
     (("--condition-channels",), int, None, "train --speaker-prefix: width H of the learned speaker embedding"),
 )
+# local conditioning on feature files (WaveNet(..., local_channels, local_hop); train_audio/local.py): off, and attributes of
+# the namespace only when given
+_LOCAL_FLAGS = (
+    (("--local-dir",), str, None, "train: condition on the feature file <local-dir>/NAME.npy of every NAME.wav, a float (F, frames) "
+                                  "array with one column per --local-hop samples (python -m wavenet_amd.train_audio.features "
+                                  "writes log-mel ones); F and the hop go to <model-dir>/local.json"),
+    (("--local-hop",), int, None, "train --local-dir: samples per feature column (256 unless local.json says otherwise)"),
+)
+_LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
+               "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
 _SPEAKER_HELP = ("generate: the speaker label to generate as (a conditioned checkpoint needs one); repeatable: one label for all "
                  "utterances, or one per utterance")
 _PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation instead of silence; repeatable: one file for "
@@ -59,6 +69,7 @@ class Args(argparse.Namespace):
     """What :func:`parse` returns: the defaults of ``_EMA_FLAGS`` live here, not in the instance."""
     ema_decay, valid_wav_dir, ema = 0.0, None, False
     speaker_prefix, condition_channels, speaker = False, None, None
+    local_dir, local_hop, local = None, None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -68,7 +79,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
@@ -76,6 +87,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, type=typ, default=argparse.SUPPRESS, help=text + " (default: %r)" % (default,))
     ap.add_argument("--prompt", action="append", default=None, metavar="FILE.wav", help=_PROMPT_HELP)
     ap.add_argument("--speaker", action="append", default=argparse.SUPPRESS, metavar="LABEL", help=_SPEAKER_HELP)
+    ap.add_argument("--local", action="append", default=argparse.SUPPRESS, metavar="FILE.npy", help=_LOCAL_HELP)
     return ap
 
 
@@ -106,6 +118,12 @@ def parse(argv=None):
         ap.error("--speaker-prefix needs --condition-channels H with H >= 1")
     if args.condition_channels is not None and not args.speaker_prefix:
         ap.error("--condition-channels goes with --speaker-prefix")
+    if args.local_hop is not None and (args.local_dir is None or args.local_hop < 1):
+        ap.error("--local-hop H goes with --local-dir and needs H >= 1")
+    if args.local:
+        n = utterance_prompts(args)[0] or 1
+        if len(args.local) not in (1, n):
+            ap.error("%d --local files for %d utterances: give one for all of them, or one each" % (len(args.local), n))
     if args.speaker:
         from .speakers import utterance_speakers
         try:

@@ -14,6 +14,7 @@ import os
 import sys
 
 from .. import data, scoring
+from . import local as _local
 from . import model as _model
 from . import speakers as _speakers
 
@@ -28,15 +29,23 @@ def build_parser() -> argparse.ArgumentParser:
     # present in the namespace only when given (train_audio.model.build reads it with a default of off)
     ap.add_argument("--ema", action="store_true", default=argparse.SUPPRESS,
                     help="score the checkpoint's averaged weights (wavenet.ema.npz, written by train --ema-decay)")
+    ap.add_argument("--local-dir", type=str, default=argparse.SUPPRESS, metavar="FEAT_DIR",
+                    help="the files' features, NAME.npy per NAME.wav (a locally conditioned checkpoint needs them)")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
     return ap
 
 
-def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True):
+def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None):
     """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
     "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
     samples, and prints one line per file and one for the total unless ``verbose`` is off.  A checkpoint conditioned on
-    speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run."""
+    speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run.
+    A locally conditioned checkpoint scores every file under its feature file in ``local_dir`` (train_audio/local.py); the
+    pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop."""
+    local = getattr(net, "local", None)
+    _local.require_match(local, local_dir is not None, "evaluate", "--local-dir FEAT_DIR")
+    if local is not None:
+        chunk_width = -(-int(chunk_width) // local[1]) * local[1]
     files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
     if not files:
         raise Exception("no .wav file in {}".format(wav_dir))
@@ -45,7 +54,8 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     cids = {fn: None if labels is None else _speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files}
     for fn in files:
         tokens, _ = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
-        row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn]))
+        lkw = {} if local is None else {"local": _local.file_features(local_dir, fn, tokens.size, local[0], local[1])}
+        row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn], **lkw))
         rows.append(dict(file=fn, **row))
         nats += row["nats_per_sample"] * row["samples"]
         samples += row["samples"]
@@ -64,7 +74,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     args.fast, args.seed = False, None                       # what train_audio.model.build reads beyond the shared flags
     params, net = _model.build(args)
-    table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size)
+    table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
+                         local_dir=getattr(args, "local_dir", None))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(table, f, indent=2)

@@ -14,12 +14,13 @@ import torch
 
 from .. import data, sampling
 from . import args as _args
+from . import local as _local
 from . import model as _model
 from . import speakers as _speakers
 from .train import input_width_of
 
 
-def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition=None):
+def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition=None, local=None):
     """The reference's loop (generate.py:24-43) from the given window: one ``forward_one_step`` over the last
     ``input_width`` tokens and one draw per sample, on the host; returns the ``n`` emitted tokens."""
     Q = net.params.quantization_steps
@@ -27,8 +28,13 @@ def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, 
     iw = len(window)
     buf = np.array(window, dtype=np.int32)
     cond = {} if condition is None else {"condition": [condition]}
+    hop = net.local_hop if local is not None else 0
     for time_step in range(1, n + 1):
         x = torch.as_tensor(buf[-iw:].reshape(1, -1)).to(net.device)
+        if local is not None:
+            # the window's first sample is sample time_step - 1 of the utterance (prompt included): local_alignment's rule
+            col, ph = divmod(time_step - 1, hop)
+            cond["local"], cond["local_phase"] = local[None, :, col:], ph
         if not controls:
             with torch.no_grad():
                 softmax = net.forward_one_step(x, apply_softmax=True, as_numpy=True, **cond)[0, :, 0, -1]
@@ -48,7 +54,7 @@ def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, 
 
 
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                   temperature=1.0, top_k=0, top_p=1.0, condition=None):
+                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None):
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     iw = input_width_of(params)
@@ -60,10 +66,11 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
     elif fast:
         # one uniform per sample, the draw numpy's choice() makes (generate.py:40); the whole loop runs on the device
         u = np.random.random_sample(n)
+        lkw = {} if local is None else {"local": local}
         tokens = net.generate(n, u, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
-                              condition=condition).cpu().numpy()
+                              condition=condition, **lkw).cpu().numpy()
     else:
-        tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition)
+        tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition, local)
     print("\ndone in {:.3f} sec".format(time.time() - start_time))
     os.makedirs(output_dir, exist_ok=True)
     filename = "{}/generated.wav".format(output_dir)
@@ -83,7 +90,7 @@ def read_prompt(path, params):
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                        temperature=1.0, top_k=0, top_p=1.0, conditions=None):
+                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance."""
     Q = params.quantization_steps
@@ -99,11 +106,13 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
         tokens = np.zeros((N, 0), np.int32)
     elif fast:
         u = np.random.random_sample((N, n))
+        lkw = {} if locals_ is None else {"local": list(locals_)}
         tokens = net.generate_batch(n, u, initial_tokens=prompts, temperature=temperature, top_k=top_k, top_p=top_p,
-                                    condition=conditions).cpu().numpy()
+                                    condition=conditions, **lkw).cpu().numpy()
     else:
         tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p,
-                                      None if conditions is None else conditions[i]) for i in range(N)])
+                                      None if conditions is None else conditions[i],
+                                      None if locals_ is None else locals_[i]) for i in range(N)])
     print("\ndone in {:.3f} sec".format(time.time() - start_time))
     os.makedirs(output_dir, exist_ok=True)
     filenames = []
@@ -113,23 +122,52 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     return filenames, tokens
 
 
+def _seconds_given(argv) -> bool:
+    """Whether the command line names -s / --seconds (its default, 1.0, is a length like any other when it is given)."""
+    import argparse
+    import sys as _sys
+    probe = argparse.ArgumentParser(add_help=False)
+    probe.add_argument("-s", "--seconds", type=float, default=None)
+    return probe.parse_known_args(_sys.argv[1:] if argv is None else list(argv))[0].seconds is not None
+
+
 def main(argv=None):
     args = _args.parse(argv)
+    seconds_given = _seconds_given(argv)
     n_utt, prompt_files = _args.utterance_prompts(args)
     # the speaker of every utterance, checked against the checkpoint's table before the model is built: an unknown label,
     # --speaker on an unconditioned checkpoint and its absence on a conditioned one all stop here with a clear message
     table = _speakers.load_table(args.model_dir)
     names = _speakers.utterance_speakers(args.speaker, n_utt or 1)
     cids = [_speakers.class_id(table[0] if table else None, s, "generate") for s in names]
+    # features: checked against the checkpoint's local.json before the model is built, like the speakers
+    config = _local.load_config(args.model_dir)
+    _local.require_match(config, bool(args.local), "generate", "--local FILE.npy")
+    feats = None
+    if config is not None:
+        distinct = {f: _local.read_features(f, config[0]) for f in set(args.local)}
+        feats = [distinct[f] for f in (args.local * (n_utt or 1) if len(args.local) == 1 else args.local)]
     params, net = _model.build(args)
     np.random.seed(args.seed)
+    if feats is not None:
+        # the features cover an utterance from its first sample, the window of input_width samples included; the length
+        # generated defaults to what they cover (-s left at its default), and more than that is refused before anything runs
+        iw = input_width_of(params)
+        cover = min(f.shape[1] for f in feats) * config[1] - iw + 1          # samples that can be emitted
+        if cover < 1:
+            raise SystemExit("generate: the features cover {} samples, fewer than the {} of the window".format(cover + iw - 1, iw))
+        if not seconds_given:
+            args.seconds = (cover + 1.5) / float(params.sampling_rate)            # int(rate * seconds) - 1 == cover
+        elif int(params.sampling_rate * args.seconds) - 1 > cover:
+            raise SystemExit("generate: -s {} asks for {} samples, the features cover {}".format(
+                args.seconds, int(params.sampling_rate * args.seconds) - 1, cover))
     if n_utt is not None:
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
-                                   top_p=args.top_p, conditions=cids if table else None)
+                                   top_p=args.top_p, conditions=cids if table else None, locals_=feats)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                          condition=cids[0])
+                          condition=cids[0], local=None if feats is None else feats[0])
 
 
 if __name__ == "__main__":

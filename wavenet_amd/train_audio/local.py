@@ -1,0 +1,102 @@
+"""Local conditioning on the command line: feature files next to the .wav files, and ``model/local.json``.
+
+A feature file is ``FEAT_DIR/NAME.npy`` for ``WAV_DIR/NAME.wav``: a float (F, frames) array with one column per ``hop``
+samples OF THE TOKENS AS TRAINING READS THEM (``data.load_audio_file``: mu-law, silence trimmed) -- column k belongs to
+tokens k * hop .. (k + 1) * hop - 1.  ``python -m wavenet_amd.train_audio.features`` writes log-mel files of that kind.
+
+``local.json`` holds ``{"channels": F, "hop": H}``: whenever it exists the network is built locally conditioned
+(``wavenet.json`` is unchanged), and a resumed run must find the same values."""
+from __future__ import annotations
+
+import json
+import os
+from typing import Optional, Tuple
+
+import numpy as np
+
+FILE = "local.json"
+DEFAULT_HOP = 256
+
+
+def load_config(model_dir: str) -> Optional[Tuple[int, int]]:
+    """(channels, hop) of ``<model_dir>/local.json``, or None when the checkpoint is not locally conditioned."""
+    filename = os.path.join(model_dir, FILE)
+    if not os.path.isfile(filename):
+        return None
+    try:
+        with open(filename) as f:
+            d = json.load(f)
+        channels, hop = int(d["channels"]), int(d["hop"])
+    except Exception:
+        raise Exception("could not load {}".format(filename))
+    if channels < 1 or hop < 1:
+        raise Exception("{}: expected channels >= 1 and hop >= 1".format(filename))
+    return channels, hop
+
+
+def ensure_config(model_dir: str, channels: int, hop: int) -> Tuple[int, int]:
+    """train --local-dir: write the file on the first run; a resumed run must find the SAME values or it stops."""
+    have = load_config(model_dir)
+    if have is None:
+        os.makedirs(model_dir, exist_ok=True)
+        with open(os.path.join(model_dir, FILE), "w") as f:
+            json.dump({"channels": int(channels), "hop": int(hop)}, f)
+        return int(channels), int(hop)
+    if have != (int(channels), int(hop)):
+        raise SystemExit("{}: this checkpoint was trained on {} feature channels at hop {}, the command line gives {} at hop {}: "
+                         "a resumed run must find the same values".format(os.path.join(model_dir, FILE), have[0], have[1],
+                                                                          int(channels), int(hop)))
+    return have
+
+
+def feature_path(feat_dir: str, wav_name: str) -> str:
+    return os.path.join(feat_dir, os.path.splitext(os.path.basename(wav_name))[0] + ".npy")
+
+
+def read_features(filename: str, channels: Optional[int] = None) -> np.ndarray:
+    """A (F, frames) float32 array; stops with a message naming the file when it is missing or has another shape."""
+    if not os.path.isfile(filename):
+        raise SystemExit("local conditioning: the feature file {} is missing".format(filename))
+    a = np.load(filename)
+    if a.ndim != 2 or a.shape[1] < 1 or a.dtype.kind != "f":
+        raise SystemExit("local conditioning: {} must hold a float (F, frames) array, got {} {}".format(filename, a.dtype, a.shape))
+    if channels is not None and a.shape[0] != channels:
+        raise SystemExit("local conditioning: {} has {} feature channels, the model takes {}".format(filename, a.shape[0], channels))
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def file_features(feat_dir: str, wav_name: str, n_samples: int, channels: int, hop: int) -> np.ndarray:
+    """The features of one .wav file, checked against its ``n_samples`` tokens: at least ceil(n_samples / hop) columns."""
+    filename = feature_path(feat_dir, wav_name)
+    a = read_features(filename, channels)
+    need = (int(n_samples) + hop - 1) // hop
+    if a.shape[1] < need:
+        raise SystemExit("local conditioning: {} has {} columns, but the {} samples of {} need {} at hop {}".format(
+            filename, a.shape[1], n_samples, os.path.basename(wav_name), need, hop))
+    return a
+
+
+def directory_channels(feat_dir: str, wav_names) -> int:
+    """F, read from the feature file of the first .wav file."""
+    names = list(wav_names)
+    if not names:
+        raise SystemExit("--local-dir: no .wav file to look up a feature file for")
+    return int(read_features(feature_path(feat_dir, names[0])).shape[0])
+
+
+def padded(features: np.ndarray, pad_samples: int, hop: int) -> Tuple[np.ndarray, int]:
+    """Training pads a file with ``pad_samples`` tokens of silence in front; they read the file's column 0.  Returns the
+    features with ceil(pad_samples / hop) copies of column 0 in front, and the shift that takes an index into the padded
+    tokens to its position on that feature grid (position // hop = column)."""
+    cols = (int(pad_samples) + hop - 1) // hop
+    ext = np.concatenate([np.repeat(features[:, :1], cols, axis=1), features], axis=1)
+    return np.ascontiguousarray(ext), cols * hop - int(pad_samples)
+
+
+def require_match(config, given: bool, what: str, flag: str):
+    """A checkpoint with local.json used without features, or features given to one without it: stop with a clear message."""
+    if config is not None and not given:
+        raise SystemExit("{}: this checkpoint is locally conditioned ({} feature channels at hop {}): give {}".format(
+            what, config[0], config[1], flag))
+    if config is None and given:
+        raise SystemExit("{}: {} was given, but this checkpoint is not locally conditioned (no {})".format(what, flag, FILE))

@@ -8,6 +8,7 @@ import os
 import torch
 
 from .. import FasterWaveNet, Params, WaveNet
+from . import local as _local
 from . import speakers as _speakers
 
 
@@ -49,7 +50,7 @@ def load_params(model_dir: str) -> Params:
     return params
 
 
-def build(args):
+def build(args, train: bool = False):
     """-> (params, wavenet) on ``cuda:<args.gpu_device>``.  There is no CPU mode (``-g -1`` in the reference): the product
     path is the HIP library and fails loudly without a device.
 
@@ -59,16 +60,31 @@ def build(args):
 
     Speakers: ``args.speaker_prefix`` (train) takes the label table from the .wav files of ``args.wav_dir`` and writes it, with
     ``args.condition_channels``, to ``speakers.json`` -- or checks it against the one already there.  Whenever that file
-    exists the network is built globally conditioned on its labels, and ``net.speakers`` is the table (None otherwise)."""
+    exists the network is built globally conditioned on its labels, and ``net.speakers`` is the table (None otherwise).
+
+    Features: ``args.local_dir`` with ``train`` (the training driver) reads the channel count F from the feature file of the first .wav file and writes it,
+    with the hop, to ``local.json`` -- or checks both against the one already there.  Whenever that file exists the network
+    is built locally conditioned, and ``net.local`` is (F, hop) (None otherwise)."""
     params = load_params(args.model_dir)
+    local_dir = getattr(args, "local_dir", None)
+    if local_dir is not None and train:                                     # (evaluate and generate read the config only)
+        wavs = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
+        have = _local.load_config(args.model_dir)
+        hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
+        local = _local.ensure_config(args.model_dir, _local.directory_channels(local_dir, wavs), hop)
+    else:
+        local = _local.load_config(args.model_dir)
     if bool(getattr(args, "speaker_prefix", False)):
         wavs = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
         table = _speakers.ensure_table(args.model_dir, _speakers.label_table(wavs), getattr(args, "condition_channels", None))
     else:
         table = _speakers.load_table(args.model_dir)
     cond = dict(condition_classes=len(table[0]), condition_channels=table[1]) if table else {}
+    if local:
+        cond.update(local_channels=local[0], local_hop=local[1])
     net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed, **cond)
     net.speakers = table[0] if table else None
+    net.local = local
     params.dump()
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     use_ema = bool(getattr(args, "ema", False))

@@ -14,6 +14,7 @@ from ..graph import default_loss
 from . import args as _args
 from . import model as _model
 from .evaluate import evaluate_dir
+from . import local as _local
 from . import speakers as _speakers
 
 
@@ -30,7 +31,15 @@ class _Crops(object):
     """train.py:14-22 with the signal resident on the device: the start offsets are drawn on the host from numpy's
     global generator (the draw the reference makes, so ``--seed`` selects the same crops), the gather runs on the GPU."""
 
-    def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device):
+    def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device, features=None, hop=0, shift=0):
+        """``features`` (F, columns) on the grid ``local.padded`` describes (index into ``signal`` + ``shift`` = position,
+        position // hop = column): starts are then drawn so that every crop begins on a column border (phase 0), and ``draw``
+        also returns the crops' (B, F, ceil((input_width + target_width) / hop)) columns."""
+        self.hop, self.shift = int(hop), int(shift)
+        self.features = None
+        if features is not None:
+            self.features = torch.as_tensor(features).to(device)
+            self.fcol = torch.arange((input_width + target_width + hop - 1) // hop, device=device)
         self.n = int(signal.size)
         self.iw, self.tw = input_width, target_width
         if self.n - target_width - input_width - 1 <= 0:
@@ -39,19 +48,41 @@ class _Crops(object):
         self.col = torch.arange(input_width + target_width + 1, device=device)
 
     def draw(self, batch_size: int):
-        starts = np.random.randint(0, self.n - self.tw - self.iw - 1, size=batch_size)
+        hi = self.n - self.tw - self.iw - 1
+        feats = None
+        if self.features is None:
+            starts = np.random.randint(0, hi, size=batch_size)
+        else:
+            # starts r, r + hop, r + 2 hop, ... below hi, r the first index whose position is a multiple of the hop: one draw,
+            # as above
+            r = (-self.shift) % self.hop
+            if hi - r <= 0:
+                raise Exception("signal too short for a crop that starts on a feature column")
+            starts = r + self.hop * np.random.randint(0, (hi - r + self.hop - 1) // self.hop, size=batch_size)
+            first = torch.as_tensor((starts + self.shift) // self.hop).to(self.col.device)
+            feats = self.features[:, first[:, None] + self.fcol[None, :]].permute(1, 0, 2).contiguous()
         idx = torch.as_tensor(starts).to(self.col.device)[:, None] + self.col[None, :]
         win = self.signal[idx]                                     # (B, iw + tw + 1)
-        return win[:, :self.iw + self.tw].contiguous(), win[:, self.iw + 1:].contiguous()
+        x, tgt = win[:, :self.iw + self.tw].contiguous(), win[:, self.iw + 1:].contiguous()
+        return (x, tgt) if self.features is None else (x, tgt, feats)
 
 
-def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None):
-    """One file: returns the summed loss of its ``repeat`` updates (train.py:24-90)."""
+def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None,
+                local_dir=None):
+    """One file: returns the summed loss of its ``repeat`` updates (train.py:24-90).  ``local_dir``: where the file's feature
+    file lies (a locally conditioned model); crops then start on a feature column border."""
     signals, _ = data.load_audio_file(path_to_file, quantization_steps=params.quantization_steps)
     iw = input_width_of(params)
     silence = 127 if params.quantization_steps > 127 else params.quantization_steps // 2
+    local = getattr(net, "local", None)
+    _local.require_match(local, local_dir is not None, "train", "--local-dir FEAT_DIR")
+    fkw = {}
+    if local is not None:
+        feats = _local.file_features(local_dir, path_to_file, signals.size, local[0], local[1])
+        ext, shift = _local.padded(feats, iw, local[1])
+        fkw = dict(features=ext, hop=local[1], shift=shift)
     signals = np.concatenate([np.full((iw,), silence, dtype=np.int32), signals.astype(np.int32)])   # train.py:53
-    crops = _Crops(signals, iw, train_width, net.device)
+    crops = _Crops(signals, iw, train_width, net.device, **fkw)
     # a conditioned model: every crop carries the label of the file it came from
     labels = getattr(net, "speakers", None)
     cond = None
@@ -63,17 +94,19 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     skipped = 0
     name = os.path.basename(path_to_file)
     for batch_index in range(repeat):
-        x, tgt = crops.draw(batch_size)
+        drawn = crops.draw(batch_size)
+        x, tgt = drawn[0], drawn[1]
+        lkw = {} if local is None else {"local": drawn[2]}
         if use_graph and str(params.optimizer).lower() != "eve":     # Eve needs the loss on the host every update
             key = (batch_size, iw + train_width)
             graph = None if state is None else state.get(key)
             if graph is None:
-                graph = TrainStepGraph(net, x, tgt, condition=cond)
+                graph = TrainStepGraph(net, x, tgt, condition=cond, **lkw)
                 if state is not None:
                     state[key] = graph
-            loss = graph.step(x, tgt, condition=cond)
+            loss = graph.step(x, tgt, condition=cond, **lkw)
         else:
-            loss = default_loss(net, x, tgt, condition=cond)
+            loss = default_loss(net, x, tgt, condition=cond, **lkw)
             net.backprop(loss)
             loss = loss.detach()
         sum_loss += loss                                            # on the device: no host sync per update
@@ -96,16 +129,16 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     return float(sum_loss.item())
 
 
-def validate(net, params, wav_dir, epoch):
+def validate(net, params, wav_dir, epoch, local_dir=None):
     """The held-out negative log-likelihood after an epoch: one line for the weights being trained and, when a weight
     average is kept, one for the averaged weights."""
     def line(what, total):
         sys.stdout.write("epoch: {} - held-out {}: {:.6f} nats/sample  {:.6f} bits/sample  ({} samples)\n".format(
             epoch, what, total["nats_per_sample"], total["bits_per_sample"], total["samples"]))
-    line("weights", evaluate_dir(net, params, wav_dir, verbose=False)["total"])
+    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir)["total"])
     if net.ema_enabled:
         with net.ema_weights():
-            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False)["total"])
+            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir)["total"])
     sys.stdout.flush()
 
 
@@ -113,7 +146,8 @@ def main(argv=None):
     args = _args.parse(argv)
     if args.ema:
         raise Exception("--ema belongs to generate and evaluate; train keeps an average with --ema-decay")
-    params, net = _model.build(args)
+    params, net = _model.build(args, train=True)
+    _local.require_match(net.local, args.local_dir is not None, "train", "--local-dir FEAT_DIR")
     np.random.seed(args.seed)
     net.update_laerning_rate(args.lr)
     files = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
@@ -134,7 +168,7 @@ def main(argv=None):
         for fn in files:
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
-                                        use_graph=not args.no_graph, state=graphs)
+                                        use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir)
             net.save(args.model_dir)
         average_loss /= len(files)
         sys.stdout.write("\033[2K\repoch: {} - {:.4e} loss - {} min\n".format(
@@ -142,7 +176,7 @@ def main(argv=None):
         sys.stdout.flush()
         net.save(args.model_dir)
         if args.valid_wav_dir:
-            validate(net, params, args.valid_wav_dir, epoch)
+            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir)
     return average_loss
 
 

@@ -282,12 +282,14 @@ class _StackFn(_Fn):
     (WaveNet.forward_residual_block, wavenet.py:572-582)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, net, t_off, train, window_only=False, cond=None):
+    def forward(ctx, x, anchor, net, t_off, train, window_only=False, cond=None, frames=None):
         # `anchor` is a dummy leaf that requires grad: it keeps this node on the tape even when x
         # does not require grad, because the weights are not tensor inputs of the node.
         # `cond` (global conditioning): the (B, sum 2 cd) block of per-clip gate biases of _CondFn -- layer l's filter row at
         # net._cond_offsets[l][0], its gate row at [l][1] -- handed to the library as bias rows one block row apart
         # (WN_EXEC_BIAS_PER_CLIP); the backward returns the block's gradient.
+        # `frames` = (hop, phase) (local conditioning): `cond` is then the (B, n, sum 2 cd) block of _LocalFn, a row per (clip,
+        # frame) -- clips n block rows apart, frames one (WnStackDesc.bias_hop / bias_phase / bias_frame_stride).
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
@@ -295,11 +297,17 @@ class _StackFn(_Fn):
         ex = lambda: net._exec(B, T)
         if cond is not None:
             cond = cond.contiguous()
-            if tuple(cond.shape) != (B, net._cond_rows):
+            if frames is None and tuple(cond.shape) != (B, net._cond_rows):
                 raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (tuple(cond.shape), (B, net._cond_rows)))
-            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg")
+            if frames is not None:
+                need = frames_needed(T, frames[0], frames[1])
+                if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != net._cond_rows or cond.shape[1] < need:
+                    raise _lib.WaveNetHipError("local conditioning block is %s, expected (%d, >= %d, %d)"
+                                               % (tuple(cond.shape), B, need, net._cond_rows))
+            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg", frames)
             desc = C.byref(cdesc)
-            ex = lambda: net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=net._cond_rows)
+            stride = net._cond_rows if frames is None else int(cond.shape[1]) * net._cond_rows
+            ex = lambda: net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=stride)
         L = len(net._flat_layers)
         ncd = sum(lay.cd for lay in net._flat_layers)
         dev_ = x.device
@@ -315,6 +323,7 @@ class _StackFn(_Fn):
         ctx.net, ctx.t_off, ctx.shape, ctx.window_only = net, t_off, (B, T, Cr), bool(window_only)
         ctx.saved = (x, xs, z, f, g) if train else None
         ctx.cond = cond if train else None
+        ctx.frames = frames
         net._last_layer_inputs = [x] + [xs[l] for l in range(L - 1)]      # FasterWaveNet seeds its rings from these
         return xs[L - 1], skip
 
@@ -341,16 +350,64 @@ class _StackFn(_Fn):
         if cond is not None:
             # per-clip bias-gradient rows accumulate (+=) into a zeroed block: the gradient of the conditioning block
             dcond = torch.zeros_like(cond)
-            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg")
+            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg", ctx.frames)
             desc = C.byref(cdesc)
             dbf, dbg = net._cond_rows_of(dcond)
-            ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=net._cond_rows)
+            stride = net._cond_rows if ctx.frames is None else int(cond.shape[1]) * net._cond_rows
+            ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=stride)
         check(lib.wn_stack_bwd(desc, ptr(x), ptr(xs), ptr(z), ptr(f), ptr(g), ptr(dout), ptr(dskip), ptr(dx),
                                gt["wf"], dbf, gt["wg"], dbg, gt["wp"], gt["bp"], gt["ws"], gt["bs"],
                                ptr(ws), nbytes, B, T, t_off, 1 if net.compat_zero_prefix else 0, ex,
                                stream_ptr()), "wn_stack_bwd")
         ctx.saved = ctx.cond = None
-        return dx, None, None, None, None, None, dcond
+        return dx, None, None, None, None, None, dcond, None
+
+
+def frames_needed(T: int, hop: int, phase: int = 0) -> int:
+    """Feature columns a window of ``T`` positions reads at ``hop`` positions per column, the first position ``phase`` positions
+    into its column: ceil((T + phase) / hop)."""
+    return (int(T) + int(phase) + int(hop) - 1) // int(hop)
+
+
+def local_alignment(s0: int, hop: int):
+    """THE alignment rule of local conditioning, in one place: network input position t of a clip whose first input sample is
+    sample ``s0`` of its file reads feature column (s0 + t) // hop.  Returns (first column, phase) = (s0 // hop, s0 % hop): the
+    caller passes the file's columns from the first one on, with ``local_phase=`` the phase.  The decoder follows the same
+    rule: the step that consumes the sample at absolute position p reads column p // hop."""
+    if hop <= 0 or s0 < 0:
+        raise Exception("local_alignment: hop must be positive and s0 non-negative, got hop = %d, s0 = %d" % (hop, s0))
+    return int(s0) // int(hop), int(s0) % int(hop)
+
+
+class _LocalFn(_Fn):
+    """Local conditioning (van den Oord et al. 2016, eq. 4, with y = the features repeated over time -- "use Vf * h and repeat
+    these values across time"): features (B, F, n), one column per ``local_hop`` positions -> the block (B, n, sum_l 2 cd_l) of
+    per-(clip, frame) gate biases V h, one small projection over the B n rows (``wn_pointwise_*``).  Nothing of size
+    B x T x sum 2 cd exists: the layer kernels index the block by (clip, frame of t).  The projection's gradient goes straight
+    into the gradient arena; the features receive theirs when they require grad (the hook for a learned feature network)."""
+
+    @staticmethod
+    def forward(ctx, feats, V, net):
+        B, F, n = feats.shape
+        h = feats.permute(0, 2, 1).contiguous().view(B * n, F)
+        R = V.shape[0]
+        out = torch.empty((B, n, R), device=h.device, dtype=torch.float32)
+        check(_lib.lib().wn_pointwise_fwd(ptr(h), ptr(V), None, ptr(out), B * n, F, R, ACT["none"], net._exec(), stream_ptr()),
+              "wn_pointwise_fwd")
+        ctx.save_for_backward(h)
+        ctx.V, ctx.net, ctx.shape = V, net, (B, F, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (h,) = ctx.saved_tensors
+        V = ctx.V
+        B, F, n = ctx.shape
+        dout = dout.contiguous()
+        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
+        check(_lib.lib().wn_pointwise_bwd(ptr(h), ptr(V), ptr(dout), ptr(dh), ptr(V.grad), None, B * n, F, V.shape[0],
+                                          ACT["none"], ctx.net._exec(), stream_ptr()), "wn_pointwise_bwd")
+        return (None if dh is None else dh.view(B, n, F).permute(0, 2, 1)), None, None
 
 
 class _CondFn(_Fn):
@@ -652,7 +709,7 @@ class WaveNet(object):
     head_activation = "relu"          # wavenet.py:588
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
-                 condition_classes: int = 0, condition_channels: int = 0):
+                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0):
         """``storage="bf16"`` (BASELINE config 5; not in the reference): activations in bfloat16, fp32 accumulation, fp32
         master weights; for 128 residual / dilation channels, filter width 2, a multiple of 256 skip channels.
 
@@ -663,7 +720,18 @@ class WaveNet(object):
         seeded draw moves: ``global_condition_embed/W`` (classes, channels, 1, 1) and ``global_condition_projection/W``
         (sum_l 2 cd_l, channels, 1, 1), rows layer-major, a layer's filter rows before its gate rows.  They are not
         ``Params`` fields (``Params().to_dict()`` is the reference's key set).  The forward methods then take
-        ``condition=`` -- one class id per clip."""
+        ``condition=`` -- one class id per clip.
+
+        ``local_channels`` = F / ``local_hop`` = H (both 0: off, and the model is byte for byte what it was; both > 0
+        together): local conditioning, the last open item of that list and what makes the network a vocoder.  A sequence of
+        features h -- a log-mel spectrogram, say, one F-wide column every H samples -- steers every layer sample by sample:
+        z = tanh(Wf * x + Vf y) sigmoid(Wg * x + Vg y) (eq. 4) with y = h repeated over time.  One more link, registered behind
+        the global conditioning links so that no existing arena offset or seeded draw moves:
+        ``local_condition_projection/W`` (sum_l 2 cd_l, F, 1, 1), rows laid out like the global projection's.  The forward
+        methods then take ``local=`` -- float32 features (B, F, n), n >= ceil((T + phase) / H), surplus columns ignored -- and
+        ``local_phase=`` (an int, default 0).  Alignment (``local_alignment``): network input position t of a clip whose first
+        input sample is sample s0 of its file reads feature column (s0 + t) // H; the caller passes the columns from s0 // H
+        on, with phase s0 % H.  With global conditioning also on, the clip's row is added to every frame row of its clip."""
         params.check()
         if storage not in ("fp32", "bf16"):
             raise Exception("storage must be 'fp32' or 'bf16'")
@@ -675,6 +743,15 @@ class WaveNet(object):
             raise Exception("global conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases)")
         if self.condition_classes and not params.residual_conv_dilation_no_bias:
             raise Exception("global conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
+                            "convolutions' bias; a second, shared one is not supported)")
+        self.local_channels, self.local_hop = int(local_channels), int(local_hop)
+        if (self.local_channels > 0) != (self.local_hop > 0) or self.local_channels < 0 or self.local_hop < 0:
+            raise Exception("local conditioning needs local_channels > 0 and local_hop > 0 (or both 0: off), got %d and %d"
+                            % (self.local_channels, self.local_hop))
+        if self.local_channels and storage == "bf16":
+            raise Exception("local conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases)")
+        if self.local_channels and not params.residual_conv_dilation_no_bias:
+            raise Exception("local conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
                             "convolutions' bias; a second, shared one is not supported)")
         self.params = params
         self.storage = storage
@@ -740,10 +817,14 @@ class WaveNet(object):
         # global conditioning: layer l's filter biases are rows off .. off + cd_l of the projection, its gate biases the next cd_l
         self.global_condition_embed = self.global_condition_projection = None
         self._cond_offsets, self._cond_rows = [], 0
-        if self.condition_classes:
+        if self.condition_classes or self.local_channels:
             for lay in self._flat_layers:
                 self._cond_offsets.append((self._cond_rows, self._cond_rows + lay.cd))
                 self._cond_rows += 2 * lay.cd
+        self.local_condition_projection = None
+        if self.local_channels:
+            self.local_condition_projection = _Link("local_condition_projection", (self._cond_rows, self.local_channels, 1, 1), None)
+        if self.condition_classes:
             self.global_condition_embed = _Link("global_condition_embed",
                                                 (self.condition_classes, self.condition_channels, 1, 1), None)
             self.global_condition_projection = _Link("global_condition_projection",
@@ -757,6 +838,8 @@ class WaveNet(object):
         out += list(self.softmax_conv_layers)
         if self.condition_classes:                                   # after the head: existing offsets and draws stay put
             out += [self.global_condition_embed, self.global_condition_projection]
+        if self.local_channels:                                      # last of all, with or without global conditioning
+            out.append(self.local_condition_projection)
         return out
 
     # -- parameters: one flat arena (what the DP all-reduce and the optimiser kernel see) -----
@@ -818,6 +901,13 @@ class WaveNet(object):
         if self.condition_classes and not cond_keys:
             raise Exception("this model is globally conditioned and the checkpoint is not (it holds no "
                             "global_condition_embed/W and global_condition_projection/W)")
+        has_local = any(k.startswith("local_condition_") for k in sd)
+        if has_local and not self.local_channels:
+            raise Exception("this checkpoint is locally conditioned (local_condition_projection/W) and the model is not: "
+                            "construct the model with local_channels / local_hop")
+        if self.local_channels and not has_local:
+            raise Exception("this model is locally conditioned and the checkpoint is not (it holds no "
+                            "local_condition_projection/W)")
 
     def load_state_dict(self, sd: Dict[str, np.ndarray]):
         self._check_condition_keys(sd)
@@ -960,14 +1050,17 @@ class WaveNet(object):
         bg = (C.c_void_p * L)(*[p0 + 4 * og for _, og in self._cond_offsets])
         return bf, bg
 
-    def _cond_tables(self, cls, base, block, name_f, name_g):
-        """A copy of the descriptor ``base`` whose bias tables point into ``block``; (descriptor, what must stay alive)."""
+    def _cond_tables(self, cls, base, block, name_f, name_g, frames=None):
+        """A copy of the descriptor ``base`` whose bias tables point into ``block``; (descriptor, what must stay alive).
+        ``frames`` = (hop, phase): ``block`` holds a row per (clip, frame), frames one block row apart."""
         d = cls()
         for name, _ in cls._fields_:
             setattr(d, name, getattr(base, name))
         bf, bg = self._cond_rows_of(block)
         setattr(d, name_f, C.cast(bf, C.POINTER(C.c_void_p)))
         setattr(d, name_g, C.cast(bg, C.POINTER(C.c_void_p)))
+        if frames is not None:
+            d.bias_hop, d.bias_phase, d.bias_frame_stride = int(frames[0]), int(frames[1]), self._cond_rows
         return d, (bf, bg, block)
 
     def _condition_ids(self, condition, B):
@@ -1005,6 +1098,56 @@ class WaveNet(object):
     def _no_single_layer_condition(self):
         if self.condition_classes:
             raise Exception("a globally conditioned model runs its layers through forward_residual_block(condition=...) only")
+        if self.local_channels:
+            raise Exception("a locally conditioned model runs its layers through forward_residual_block(local=...) only")
+
+    # -- local conditioning ---------------------------------------------------------------------------------------------------
+    def _local_features(self, local, B, T, phase=0):
+        """``local=`` / ``local_phase=`` of the forward methods -> ((B, F, n) float32 features on the device, phase), or
+        (None, 0) for a model without local conditioning.  A locally conditioned model called without features raises, and so
+        does any other model called with them; so do too few columns (surplus ones are ignored)."""
+        if not self.local_channels:
+            if local is not None:
+                raise Exception("local= was given, but this model has no local conditioning (local_channels = 0)")
+            if phase:
+                raise Exception("local_phase= was given, but this model has no local conditioning (local_channels = 0)")
+            return None, 0
+        if local is None:
+            raise Exception("this model is locally conditioned (%d channels, hop %d): pass local= (features of shape "
+                            "(clips, %d, frames))" % (self.local_channels, self.local_hop, self.local_channels))
+        phase = int(phase)
+        if not 0 <= phase < self.local_hop:
+            raise Exception("local_phase= must lie in [0, local_hop = %d), got %d" % (self.local_hop, phase))
+        f = local if isinstance(local, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(local, dtype=np.float32)))
+        f = self.to_variable(f)
+        if f.dim() != 3 or f.shape[0] != B or f.shape[1] != self.local_channels or f.dtype != torch.float32:
+            raise Exception("local= must be float32 of shape (%d, %d, frames), got %s %s"
+                            % (B, self.local_channels, f.dtype, tuple(f.shape)))
+        need = frames_needed(T, self.local_hop, phase)
+        if f.shape[2] < need:
+            raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d"
+                            % (f.shape[2], T, self.local_hop, phase, need))
+        return f, phase
+
+    def _local_block(self, feats, glob=None):
+        """The (B, n, sum 2 cd) block of per-(clip, frame) gate biases (an autograd node over the projection); with global
+        conditioning also on, the clip's row ``glob`` (B, sum 2 cd) is added to every frame row of its clip -- a torch op on a
+        small tensor, whose backward sums the block's gradient over frames."""
+        _need_gpu(feats)
+        blk = _LocalFn.apply(feats, self.local_condition_projection.W, self)
+        return blk if glob is None else blk + glob.unsqueeze(1)
+
+    def local_biases(self, features, phase: int = 0):
+        """(n, sum 2 cd) float32 on the device: the table of one utterance -- row f holds, for flat layer l, its cd filter
+        biases at offset sum_{i<l} 2 cd_i and then its cd gate biases, the values V h[:, f] that feature column f adds to
+        every layer.  ``features``: (F, n).  Computed on the device by the node the forward uses; ``phase`` is only checked
+        (it travels next to the table)."""
+        f = np.asarray(features, dtype=np.float32) if not isinstance(features, torch.Tensor) else features
+        if len(f.shape) != 2:
+            raise Exception("local_biases: features must be (F, frames), got %s" % (tuple(f.shape),))
+        feats, _ = self._local_features(f[None], 1, 1, phase)
+        with torch.no_grad():
+            return self._local_block(feats)[0].contiguous()
 
     def condition_biases(self, class_id: int):
         """[(bf, bg)] per residual layer, each (cd,) float32 on the device: the gate biases V E[class_id] that conditioning on
@@ -1240,9 +1383,10 @@ class WaveNet(object):
         return zero_prefix(T, d, fw) if self.compat_zero_prefix else 0
 
     # -- forward (wavenet.py:556-593) -----------------------------------------------------------
-    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None):
+    def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None, local=None, local_phase=0):
         causal_output = self.forward_causal_block(x_batch)
-        _, sum_skip_connections = self.forward_residual_block(causal_output, condition=condition)
+        _, sum_skip_connections = self.forward_residual_block(causal_output, condition=condition, local=local,
+                                                              local_phase=local_phase)
         softmax_output = self.forward_softmax_block(sum_skip_connections, apply_softmax=apply_softmax)
         if as_numpy:
             return self.to_numpy(softmax_output)
@@ -1278,22 +1422,29 @@ class WaveNet(object):
         self._last_causal_outputs = outs                          # FasterWaveNet seeds its rings from these
         return _as_view(out)
 
-    def forward_residual_block(self, x_batch, t_off: int = 0, window_only: bool = False, condition=None):
+    def forward_residual_block(self, x_batch, t_off: int = 0, window_only: bool = False, condition=None, local=None,
+                               local_phase: int = 0):
         """(output, sum_skip_connections).  ``t_off`` > 0 (an extension) computes the skip sum for
         columns t_off.. only -- what train.py:73 keeps -- instead of slicing it afterwards.
         ``window_only`` (training, where train.py:72 discards the residual output): columns that cannot influence
         ``skip[t_off:]`` are not computed at all, so the returned residual output is UNDEFINED below the window's
         receptive field and must not be used; loss and gradients are unchanged.
-        ``condition``: one class id per clip, for a globally conditioned model (and only for one)."""
+        ``condition``: one class id per clip, for a globally conditioned model (and only for one).
+        ``local`` / ``local_phase``: (B, F, n) float32 features and the phase of position 0 inside its feature column, for a
+        locally conditioned model (and only for one); see ``local_alignment``."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
         cond = self._condition_block(condition, int(x.shape[0]))
+        feats, phase = self._local_features(local, int(x.shape[0]), int(x.shape[3]), local_phase)
+        frames = None
+        if feats is not None:
+            cond, frames = self._local_block(feats, cond), (self.local_hop, phase)
         if self.storage == "bf16":
             self._pack16_if_stale()
             out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled())
             return _as_view(out), _as_view(skip)
         out, skip = _StackFn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled(),
-                                   bool(window_only), cond)
+                                   bool(window_only), cond, frames)
         return _as_view(out), _as_view(skip)
 
     def forward_softmax_block(self, x_batch, apply_softmax=True, activation: Optional[str] = None):
@@ -1411,22 +1562,24 @@ class WaveNet(object):
                                           self._exec(call_flags=_lib.WN_EXEC_HEAD_ROW_NLL), stream_ptr()), "wn_head_xent")
             return nll
 
-    def token_nll(self, x, tgt, condition=None):
+    def token_nll(self, x, tgt, condition=None, local=None, local_phase=0):
         """The per-position form of ``graph.default_loss``: (B, tgt.shape[1]) float32 negative log-likelihoods of ``tgt``
         under the last ``tgt.shape[1]`` output columns of the window ``x`` (tokens (B, T) or a one-hot image).  Inference
         form: nothing is saved for a backward."""
         with torch.no_grad():
             c = self.forward_causal_block(x)
-            _, s = self.forward_residual_block(c, t_off=int(c.shape[3]) - int(tgt.shape[1]), condition=condition)
+            _, s = self.forward_residual_block(c, t_off=int(c.shape[3]) - int(tgt.shape[1]), condition=condition, local=local,
+                                               local_phase=local_phase)
             return self.head_token_nll(s, tgt)
 
-    def score(self, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None):
+    def score(self, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=None, local=None):
         """(n,) float32 on the device: the negative log-likelihood in nats of every sample of the 1-D token sequence
         ``tokens``, each given all samples before it (silence before the first), teacher-forced.  See
         :func:`wavenet_amd.scoring.score` for the definition and the two knobs, which do not change the result beyond
-        arithmetic.  ``condition``: the class id of the whole sequence, for a globally conditioned model."""
+        arithmetic.  ``condition``: the class id of the whole sequence, for a globally conditioned model.  ``local``: the
+        sequence's (F, frames) features, for a locally conditioned one."""
         from . import scoring
-        return scoring.score(self, tokens, chunk_width=chunk_width, batch_size=batch_size, condition=condition)
+        return scoring.score(self, tokens, chunk_width=chunk_width, batch_size=batch_size, condition=condition, local=local)
 
     # -- the deferred skip projection -----------------------------------------------------------
     def _skip_sum(self, zs: Sequence[torch.Tensor], skip: torch.Tensor, B, T, t_off, Tw):
