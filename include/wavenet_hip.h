@@ -129,7 +129,28 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                       reserved < n * bias_frame_stride; bias_hop > 0 without the flag; on the fp16 x 2 path rows that are not 16-byte aligned or a clip /
                                       frame stride that is no multiple of 4 floats (refused, never sent down another path).
                                       bias_hop == 0: the other two fields are ignored.  wn_layer_fwd / wn_layer_bwd take no
-                                      descriptor and keep per-clip rows only; wn16_* keeps refusing biases */
+                                      descriptor and keep per-clip rows only; wn16_* keeps refusing biases.
+                                      Linear interpolation between frames (WnStackDesc.bias_interp = 1; 0, the default, is
+                                      the above, unchanged): row k is ANCHORED at the first position of its frame, k * h --
+                                      the alignment rule above is untouched, a value is reached exactly at its frame's first
+                                      sample and the next frame's is approached over the frame.  With p = t + bias_phase,
+                                      j = p / h and alpha = float32(p % h) / float32(h), position t reads
+                                          y(t) = r[j] + alpha * (r[j + 1] - r[j])
+                                      three separately rounded fp32 operations in every kernel, so equal neighbours and
+                                      alpha = 0 give r[j] bit for bit.  The last position reads row j + 1 too: a block holds
+                                      n + 1 rows and WN_EARG is returned for reserved < (n + 1) * bias_frame_stride -- the
+                                      library never clamps.  On the fp16 x 2 path the interpolated value is formed in fp32
+                                      and added where the per-frame one is: behind the rescale.
+                                        backward  row (b, f), f = 0 .. n, is accumulated (+=) with the sum of
+                                                  (1 - alpha_t) d[b, t, :] over the t >= Z of frame f plus the sum of
+                                                  alpha_t d[b, t, :] over the t >= Z of frame f - 1, d = da and dg
+                                                  (k_colsum_per_frame_lerp: one launch per layer, a workgroup per 64 columns
+                                                  of a (clip, row); the first segment on reduction lanes 0 .. 7, the second
+                                                  on lanes 8 .. 15, chunks of 32 rows in ascending order, the 16 partials in
+                                                  index order; no float atomics, no scratch, bit-reproducible).
+                                                  A row whose two segments hold no t >= Z is not touched.
+                                      WN_EARG before any device work: bias_interp outside {0, 1}; bias_interp != 0 with
+                                      bias_hop == 0 */
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
 #define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
@@ -238,6 +259,8 @@ typedef struct WnStackDesc {
     const float* const* Wf; const float* const* bf; const float* const* Wg; const float* const* bg;
     const float* const* Wp; const float* const* bp; const float* const* Ws; const float* const* bs;
     /* local conditioning (read only under WN_EXEC_BIAS_PER_CLIP -- see the define; all 0 = one row per clip) */
+    int bias_interp;                       /* 0: position t reads its frame's row; 1: linear interpolation towards the next row
+                                              (declared at the head of the group; descriptors are filled by field name)         */
     int bias_hop;                          /* > 0: a bias row per (clip, frame); position t reads frame (t + bias_phase) / bias_hop */
     int bias_phase;                        /* 0 <= bias_phase < bias_hop, one value per call                                       */
     int bias_frame_stride;                 /* floats between consecutive frames' rows inside a clip's block (>= the layer's cd)    */
@@ -341,7 +364,13 @@ typedef struct WnDecoderDesc {
      * clamping).  A handle with a table is an any-shape one, as with biased layers (a handle created WITHOUT one on config 4's
      * shape runs the specialised kernels and refuses a table in wn_decoder_update_weights); an update without a table drops
      * it.  wn_decoder_run_batch: the handles must agree on having a table and on frame_hop; phase, row count and contents are
-     * per utterance. */
+     * per utterance.
+     * frame_interp = 1 (0, the default: the above, unchanged; read only with a table): linear interpolation, the rule of
+     * WnStackDesc.bias_interp with rows anchored at the first step of their frame -- step k, p = frame_phase + k, j = p /
+     * frame_hop, alpha = float32(p % frame_hop) / float32(frame_hop), adds (static bias or 0) + (r[j] + alpha * (r[j + 1] -
+     * r[j])).  A run whose last step would read row j + 1 > n_frames - 1 is refused with WN_EARG and leaves the handle's
+     * state alone; a value outside {0, 1} is refused; wn_decoder_run_batch also demands agreement on it. */
+    int frame_interp;                 /* declared at the head of the group; descriptors are filled by field name */
     const float* frame_bias;
     int n_frames, frame_hop, frame_phase, frame_stride;
 } WnDecoderDesc;

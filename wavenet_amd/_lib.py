@@ -36,6 +36,7 @@ class WnDecoderDesc(C.Structure):
         ("Wf", _pp), ("bf", _pp), ("Wg", _pp), ("bg", _pp), ("Wp", _pp), ("bp", _pp), ("Ws", _pp), ("bs", _pp),
         ("head_W", _pp), ("head_b", _pp),
         ("head_act", _i), ("flags", C.c_uint),
+        ("frame_interp", _i),                                                                # 0 = repeat, 1 = linear interpolation
         ("frame_bias", _p), ("n_frames", _i), ("frame_hop", _i), ("frame_phase", _i), ("frame_stride", _i),   # local conditioning
     ]
 
@@ -53,6 +54,7 @@ class WnStackDesc(C.Structure):
     _fields_ = [
         ("n_layers", _i), ("Cr", _i), ("Cs", _i), ("fw", _i), ("cd", _ip), ("dilation", _ip),
         ("Wf", _pp), ("bf", _pp), ("Wg", _pp), ("bg", _pp), ("Wp", _pp), ("bp", _pp), ("Ws", _pp), ("bs", _pp),
+        ("bias_interp", _i),                                                  # 0 = repeat, 1 = linear interpolation between frames
         ("bias_hop", _i), ("bias_phase", _i), ("bias_frame_stride", _i),     # local conditioning: a bias row per (clip, frame)
     ]
 

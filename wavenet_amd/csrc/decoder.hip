@@ -53,7 +53,7 @@ struct Decoder {
     // local conditioning (WnDecoderDesc.frame_bias): the handle's own compact copy of the table -- n_frames rows of frame_row
     // floats (sum_l 2 cd_l) --, its hop and phase, and how many steps have run since the create / update call that set it
     float* frame_tab = nullptr;
-    int frame_cap = 0, n_frames = 0, frame_hop = 0, frame_phase = 0, frame_row = 0;
+    int frame_cap = 0, n_frames = 0, frame_hop = 0, frame_phase = 0, frame_row = 0, frame_interp = 0;
     long long frame_pos = 0;
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
@@ -140,7 +140,9 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 // Local conditioning: the frame table of one utterance as the step loop takes it.  tab == NULL: no table, and the loop
 // executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the handle's
 // frame_phase + the steps run since the table was set -- to every layer's gate pre-activations.
-struct DecFrames { const float* tab; int hop; int row; long long pos0; };
+// interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
+// float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
+struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
 __device__ __forceinline__ int pmod(long long a, int D) {
     long long r = a % D;
     return (int)(r < 0 ? r + D : r);
@@ -161,6 +163,7 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
 // The step loop of one utterance on one workgroup: k_decode runs it for its handle, workgroup u of k_decode_batch for
 // utterance u.  Everything it touches -- arena, token ring, uniforms, outputs -- is the utterance's own; `sc` and the flags
 // are the same for every thread of the workgroup.
+template <bool LERP>         // LERP: the table is interpolated (DecFrames.interp); without it the loop is what it was
 __device__ __forceinline__ void decode_steps(
     const DecMeta& M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
@@ -225,6 +228,9 @@ __device__ __forceinline__ void decode_steps(
         for (int o = tid; o < M.Cs; o += NT) skip[o] = 0.f;
         // the step's frame row, computed once per step (workgroup-uniform); layer j's 2 cd values lie at the running offset
         const float* __restrict__ frow = fr.tab ? fr.tab + ((fr.pos0 + it) / fr.hop) * (long long)fr.row : nullptr;
+        // linear interpolation: the next row and its weight, likewise once per step
+        const float* __restrict__ fnext = LERP && frow ? frow + fr.row : nullptr;
+        const float falpha = fnext ? __fdiv_rn((float)(int)((fr.pos0 + it) % fr.hop), (float)fr.hop) : 0.f;
         // ---- residual layers ------------------------------------------------------------------
         for (int j = 0; j < M.nlayers; ++j) {
             const DecLayer L = layers[j];
@@ -233,7 +239,9 @@ __device__ __forceinline__ void decode_steps(
             // gate: ab[o2] = b + sum_k sum_c WfgT[k*Cr+c][o2] x[n-(fw-1-k)d][c]
             for (int o = tid; o < n2; o += NT) {
                 float acc = L.bfg >= 0 ? arena[L.bfg + o] : 0.f;
-                if (frow) acc += frow[o];      // (static bias or 0) + frame value, then the taps: a table of zeros changes no bit
+                // (static bias or 0) + frame value, then the taps: a table of zeros changes no bit
+                if (LERP && fnext) acc += bias_lerp(frow[o], fnext[o], falpha);
+                else if (frow) acc += frow[o];
                 for (int k = 0; k < M.fw; ++k) {
                     int m = M.fw - 1 - k;
                     const float* w = arena + L.wfg + (long long)k * M.Cr * n2 + o;
@@ -265,6 +273,7 @@ __device__ __forceinline__ void decode_steps(
             for (int c = tid; c < M.Cr; c += NT) xcur[c] = xnew[c];
             __syncthreads();
             if (frow) frow += n2;
+            if (LERP && fnext) fnext += n2;
         }
         // ---- head on the newest column only ---------------------------------------------------
         float* hin = skip;
@@ -320,12 +329,13 @@ __device__ __forceinline__ void decode_steps(
     }
 }
 
+template <bool LERP>
 __global__ __launch_bounds__(kDecThreads) void k_decode(
     DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
     float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc, const DecFrames fr) {
-    decode_steps(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
+    decode_steps<LERP>(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
                  apply_softmax, do_sample, sc, fr);
 }
 
@@ -341,10 +351,11 @@ struct DecAnyUtt {
 
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
 // never wait for each other, so any number of them may be queued behind the CUs.
+template <bool LERP>
 __global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int nsteps) {
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
-    decode_steps(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens,
+    decode_steps<LERP>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens,
                  q.prob_out, M.Q, 1, 1, q.sc, q.fr);
 }
 
@@ -370,15 +381,21 @@ static inline long long align64(long long x) { return (x + 63) & ~63ll; }
 // ---- local conditioning: the handle's frame table ----------------------------------------------
 static DecFrames launch_frames(const Decoder* D) {
     DecFrames f{};
-    if (D->n_frames > 0) { f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->frame_pos; }
+    if (D->n_frames > 0) {
+        f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->frame_pos;
+        f.interp = D->frame_interp;
+    }
     return f;
 }
+static bool lerp_table(const Decoder* D) { return D->n_frames > 0 && D->frame_interp != 0; }   // the LERP kernels
 // n more steps must not read past row n_frames - 1 (refused before any device work; no clamping)
 static int check_frames(const char* fn, const Decoder* D, long long n) {
     if (D->n_frames <= 0) return WN_OK;
-    const long long last = (D->frame_phase + D->frame_pos + n - 1) / D->frame_hop;
+    // (linear interpolation: the last step reads row j + 1 as well)
+    const long long last = (D->frame_phase + D->frame_pos + n - 1) / D->frame_hop + (D->frame_interp ? 1 : 0);
     WN_CHECK_ARG(last < D->n_frames, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
-                                     "run on it)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->frame_pos);
+                                     "run on it%s)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->frame_pos,
+                 D->frame_interp ? "; linear interpolation reads the row after the step's own" : "");
     return WN_OK;
 }
 static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
@@ -389,6 +406,8 @@ static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
                  d->n_frames, d->frame_hop);
     WN_CHECK_ARG(d->frame_phase >= 0 && d->frame_phase < d->frame_hop, "decoder: frame_phase = %d outside [0, frame_hop = %d)",
                  d->frame_phase, d->frame_hop);
+    WN_CHECK_ARG(d->frame_interp == 0 || d->frame_interp == 1, "decoder: frame_interp = %d is neither 0 (repeat) nor 1 (linear)",
+                 d->frame_interp);
     WN_CHECK_ARG(d->frame_stride >= row, "decoder: frame_stride = %d below the row width %d (sum of 2 cd over the layers)",
                  d->frame_stride, row);
     WN_CHECK_ARG(!D->fastP, "decoder: this handle runs the specialised 32/256-channel kernels, which take no frame table: create the "
@@ -409,6 +428,7 @@ static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     WN_HIP(hipMemcpy2DAsync(D->frame_tab, (size_t)row * sizeof(float), d->frame_bias, (size_t)d->frame_stride * sizeof(float),
                             (size_t)row * sizeof(float), (size_t)d->n_frames, hipMemcpyDeviceToDevice, s));
     D->n_frames = d->n_frames; D->frame_hop = d->frame_hop; D->frame_phase = d->frame_phase; D->frame_row = row;
+    D->frame_interp = d->frame_interp;
     return WN_OK;
 }
 
@@ -639,7 +659,8 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
         D->step += 1;
         return WN_OK;
     }
-    hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
+    const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, 1, (int)token,
                        (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl(), launch_frames(D));
     WN_LAUNCH_CHECK();
@@ -663,7 +684,8 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
         D->step += n;
         return WN_OK;
     }
-    hipLaunchKernelGGL(k_decode, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
+    const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
+    hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
                        D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, n, (int)first_token, uniforms,
                        out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D), launch_frames(D));
     WN_LAUNCH_CHECK();
@@ -716,7 +738,8 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
-    hipLaunchKernelGGL(k_decode_batch, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
+    const auto kern = lerp_table(D0) ? k_decode_batch<true> : k_decode_batch<false>;     // (the handles agree on the mode)
+    hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
                        n_handles, n);
     WN_LAUNCH_CHECK();
     for (int u = 0; u < n_handles; ++u) { ((Decoder*)handles[u])->step += n; ((Decoder*)handles[u])->frame_pos += n; }
@@ -766,6 +789,8 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
         WN_CHECK_ARG((D->n_frames > 0) == (D0->n_frames > 0) && (D->n_frames <= 0 || D->frame_hop == D0->frame_hop),
                      "wn_decoder_run_batch: utterance %d and utterance 0 disagree on having a frame table or on its hop", u);
+        WN_CHECK_ARG(D->n_frames <= 0 || D->frame_interp == D0->frame_interp,
+                     "wn_decoder_run_batch: utterance %d and utterance 0 disagree on frame_interp (repeat / linear)", u);
         if (int rcf = check_frames("wn_decoder_run_batch", D, n)) return rcf;
         if (!any)
             utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));

@@ -436,8 +436,89 @@ int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, i
     WN_LAUNCH_CHECK();
     return WN_OK;
 }
+// The weighted form for linear interpolation (BiasFrames.interp == 1): position t of frame j = (t + phase) / hop read
+// r[j] + alpha_t (r[j + 1] - r[j]), alpha_t = float((t + phase) % hop) / float(hop), so row f of a clip's gradient block -- f =
+// 0 .. frames, one row more than the per-frame form -- receives
+//     segment A  sum over the t >= tmin of frame f      of (1 - alpha_t) d[t]
+//   + segment B  sum over the t >= tmin of frame f - 1  of      alpha_t  d[t].
+// Workgroup (x, f, b) owns 64 of the 2 Cd columns [da | dg] of row (b, f) and adds both segments in a fixed order: each
+// segment is cut into chunks of t_chunk rows from its first row, four row lanes per chunk combined as (p0 + p1) + (p2 + p3);
+// reduction lanes 0 .. 7 belong to segment A and 8 .. 15 to segment B -- the two run side by side --, lane y of a half adding
+// its segment's chunks y, y + 8, ... in ascending order; the 16 partials are added in index order.  Chunks are 32 rows (the
+// per-frame form's 256 would leave a 256-sample frame to one lane): a frame of 256 rows keeps all 16 lanes busy.  A row whose
+// two segments hold no t >= tmin is left untouched.  No atomics, no scratch; B x (frames + 1) x 2 Cd / 64 independent
+// workgroups, each reading its two segments once (a (da | dg) row is read by two workgroups).
+__device__ __forceinline__ float colsum_weighted_segment(const float* __restrict__ A, int lda, int ta, int tb, int t_chunk,
+                                                         long long lo, float hop, bool next) {
+    // rows ta .. tb - 1 of a frame whose first position is lo; weight alpha (next) or 1 - alpha of the row's own position
+    auto w = [&](int t) {
+        const float al = __fdiv_rn((float)(int)(t - lo), hop);
+        return next ? al : 1.f - al;
+    };
+    const int nchunk = (tb - ta + t_chunk - 1) / t_chunk;
+    float sum = 0.f;
+    for (int y = threadIdx.y & 7; y < nchunk; y += 8) {
+        const int t0 = ta + y * t_chunk, t1 = min(tb, t0 + t_chunk);
+        float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+        int t = t0;
+        for (; t + 3 < t1; t += 4) {
+            p0 += w(t) * A[(long long)t * lda]; p1 += w(t + 1) * A[(long long)(t + 1) * lda];
+            p2 += w(t + 2) * A[(long long)(t + 2) * lda]; p3 += w(t + 3) * A[(long long)(t + 3) * lda];
+        }
+        if (t < t1) p0 += w(t) * A[(long long)t * lda];
+        if (t + 1 < t1) p1 += w(t + 1) * A[(long long)(t + 1) * lda];
+        if (t + 2 < t1) p2 += w(t + 2) * A[(long long)(t + 2) * lda];
+        sum += (p0 + p1) + (p2 + p3);
+    }
+    return sum;
+}
+__global__ __launch_bounds__(1024) void k_colsum_per_frame_lerp(const float* __restrict__ da, const float* __restrict__ dg,
+                                                                int lda, int T, int tmin, int Cd, float* __restrict__ dbf,
+                                                                float* __restrict__ dbg, long long stride, BiasFrames fr,
+                                                                int t_chunk) {
+    __shared__ float red[16][64];
+    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
+    const int f = blockIdx.y, b = blockIdx.z;
+    const long long loA = (long long)f * fr.hop - fr.phase, loB = loA - fr.hop;      // first positions of frames f and f - 1
+    const int taA = loA > tmin ? (int)loA : tmin, tbA = loA + fr.hop < T ? (int)(loA + fr.hop) : T;
+    const int taB = loB > tmin ? (int)loB : tmin, tbB = loA < T ? (int)loA : T;
+    if (tbA <= taA && tbB <= taB) return;                 // (uniform over the workgroup)
+    const bool ok = m < 2 * Cd;
+    const bool gate = m >= Cd;
+    const int mm = gate ? m - Cd : m;
+    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
+    float sum = 0.f;
+    if (ok) {                                             // (threadIdx.y >> 3 is uniform over a wave: a wave is one row of 64)
+        if (threadIdx.y < 8) { if (tbA > taA) sum = colsum_weighted_segment(A, lda, taA, tbA, t_chunk, loA, (float)fr.hop, false); }
+        else if (tbB > taB) sum = colsum_weighted_segment(A, lda, taB, tbB, t_chunk, loB, (float)fr.hop, true);
+    }
+    red[threadIdx.y][threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.y == 0 && ok) {
+        float tot = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
+        float* out = gate ? dbg : dbf;
+        if (out) out[(long long)b * stride + (long long)f * fr.stride + mm] += tot;
+    }
+}
+int generic_colsum_per_frame_lerp(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf,
+                                  float* dbg, long long stride, BiasFrames fr, hipStream_t s) {
+    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
+    const int rows = (int)(((long long)T + fr.phase + fr.hop - 1) / fr.hop) + 1;
+    WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
+    WN_CHECK_SHAPE(rows <= 65535, "interpolated per-frame bias gradients: at most 65,534 frames per clip and call");
+    int t_chunk = 32;
+    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
+    hipLaunchKernelGGL(k_colsum_per_frame_lerp, dim3(cdiv(2 * Cd, 64), rows, B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd,
+                       dbf, dbg, stride, fr, t_chunk);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
+}
 int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
                              float* dbf, float* dbg, hipStream_t s) {
+    if (c.frames.hop > 0 && c.frames.interp)
+        return generic_colsum_per_frame_lerp(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames, s);
     if (c.frames.hop > 0) return generic_colsum_per_frame(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames, s);
     return generic_colsum_per_clip(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, s);
 }
@@ -445,6 +526,7 @@ int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, in
 // ---------------------------------------------------------------------------------------------
 // A7  residual layer, generic
 // ---------------------------------------------------------------------------------------------
+template <bool LERP>          // LERP: bias rows interpolated between frames (BiasFrames.interp); <false> is the kernel as it was
 __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict__ Wf,
                            const float* __restrict__ bf, const float* __restrict__ Wg,
                            const float* __restrict__ bg, float* __restrict__ z,
@@ -460,9 +542,15 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
     float a = 0.f, g = 0.f;
     if (t >= Z) {
         // bias_stride != 0: one bias row per clip (WN_EXEC_BIAS_PER_CLIP); fr.hop != 0: per (clip, frame of t)
+        // fr.interp != 0: interpolated between that row and the next one (bias_lerp)
         const long long brow = b * bias_stride + bias_frame_off(fr, t) + o;
         a = bf ? bf[brow] : 0.f;
         g = bg ? bg[brow] : 0.f;
+        if (LERP) {
+            const float al = bias_frame_alpha(fr, t);
+            if (bf) a = bias_lerp(a, bf[brow + fr.stride], al);
+            if (bg) g = bias_lerp(g, bg[brow + fr.stride], al);
+        }
         const float* wf = Wf + (long long)o * Cr * fw;
         const float* wg = Wg + (long long)o * Cr * fw;
         for (int k = 0; k < fw; ++k) {
@@ -1160,8 +1248,12 @@ int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const fl
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
                       int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride, BiasFrames frames) {
     long long tot = (long long)B * T * Cd;
-    hipLaunchKernelGGL(k_gate_fwd, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
-                       gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
+    if (frames.hop > 0 && frames.interp)
+        hipLaunchKernelGGL(k_gate_fwd<true>, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
+                           gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
+    else
+        hipLaunchKernelGGL(k_gate_fwd<false>, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
+                           gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
     WN_LAUNCH_CHECK();
     long long N = (long long)B * T;
     hipLaunchKernelGGL(k_proj_res_fwd, dim3(cdiv(N * Cr, kThreads)), dim3(kThreads), 0, s, x, z, Wp, bp, out,

@@ -34,7 +34,8 @@ static constexpr int kPRow = 33;     // LDS row stride of Wp[i][.]
 
 // FRAME (with HAS_BIAS; local conditioning): bf / bg hold a row per (clip, frame) and the accumulator seed is per lane -- a
 // lane owns one column, so it is the row of the lane's own frame.  A compile-time mode: without it the kernel is what it was.
-template <int SAVE, bool HAS_BIAS, bool FRAME = false>
+// FRAME == 2 (linear interpolation, WnStackDesc.bias_interp): the seed is bias_lerp of the rows of frames j and j + 1.
+template <int SAVE, bool HAS_BIAS, int FRAME = 0>
 __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
     const float* __restrict__ x, const float* __restrict__ Wf, const float* __restrict__ bf,
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
@@ -139,7 +140,16 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
         const bool more = tile + stride < last;
         if (more) load_tile(tile + stride, xcn, xon);
         f32x16 aa, ag;
-        if (HAS_BIAS && FRAME) {       // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
+        if (HAS_BIAS && FRAME == 2) {  // ... interpolated between the rows of the lane's frame and the next one
+            const int tb = valid ? t : T - 1;
+            const long long brow = b * bstride + bias_frame_off(fr, tb);
+            const float al = bias_frame_alpha(fr, tb);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+                ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+            }
+        } else if (HAS_BIAS && FRAME) {       // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
             const long long brow = b * bstride + bias_frame_off(fr, valid ? t : T - 1);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
 // others instead of under one sibling's.  No tile loop, no prefetch, no tile-count quantisation: a workgroup is four
 // consecutive tiles.
 // ---------------------------------------------------------------------------------------------
-template <int SAVE, bool HAS_BIAS, bool FRAME = false>
+template <int SAVE, bool HAS_BIAS, int FRAME = 0>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     const float* __restrict__ x, const float* __restrict__ Wf, const float* __restrict__ bf,
     const float* __restrict__ Wg, const float* __restrict__ bg, const float* __restrict__ Wp,
@@ -266,7 +276,15 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     __syncthreads();
 
     f32x16 aa, ag;
-    if (HAS_BIAS && FRAME) {           // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
+    if (HAS_BIAS && FRAME == 2) {      // ... interpolated between the rows of the lane's frame and the next one
+        const long long brow = b * bstride + bias_frame_off(fr, tc);
+        const float al = bias_frame_alpha(fr, tc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+            ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+        }
+    } else if (HAS_BIAS && FRAME) {           // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
         const long long brow = b * bstride + bias_frame_off(fr, tc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -350,7 +368,11 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // (tc + fr.phase) / fr.hop -- the same eight float4 requests; lanes of one frame read one address, so a wave fetches one row
 // per frame it spans.  The frame index is one plain 32-bit division per lane: a reciprocal multiply was not tried, the
 // kernel's time is its MFMA block and x traffic).
-enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2 };
+// kCondLinear (WnStackDesc.bias_interp == 1) reads the rows of frames j and j + 1 -- sixteen float4 requests -- and forms
+// r[j] + alpha (r[j + 1] - r[j]) in fp32 (bias_lerp) in front of the MFMA block, so that no more registers than kCondFrame's
+// stay live under it (row j + 1 is requested behind the weight image's barrier: requested with row j it spilled 92 bytes a
+// lane); the interpolated value is added where the per-frame one is: behind the rescale.
+enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2, kCondLinear = 3 };
 template <int SAVE, int COND>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     const float* __restrict__ x, const char* __restrict__ img_g, float* __restrict__ out, float* __restrict__ zout,
@@ -392,7 +414,7 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     float4 cf[4], cg[4];
     if (COND) {
         long long rowb = (long long)b * bstride + 4 * h;
-        if (COND == kCondFrame) rowb += (long long)((tc + fr.phase) / fr.hop) * fr.stride;
+        if (COND == kCondFrame || COND == kCondLinear) rowb += (long long)((tc + fr.phase) / fr.hop) * fr.stride;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             cf[q] = *reinterpret_cast<const float4*>(bf + rowb + 8 * q);
@@ -402,6 +424,21 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
 #pragma unroll
     for (int k = 0; k < 5; ++k) reinterpret_cast<u32x4_t*>(img)[threadIdx.x + 256 * k] = stage[k];
     __syncthreads();
+    if (COND == kCondLinear) {
+        // the next frame's rows are requested only here, where the staged weight image has left its registers, and folded
+        // into cf / cg at once: under the MFMA block this mode holds what kCondFrame holds
+        const long long rown = (long long)b * bstride + 4 * h + (long long)((tc + fr.phase) / fr.hop + 1) * fr.stride;
+        const float al = bias_frame_alpha(fr, tc);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 nf = *reinterpret_cast<const float4*>(bf + rown + 8 * q);
+            const float4 ng = *reinterpret_cast<const float4*>(bg + rown + 8 * q);
+            cf[q] = make_float4(bias_lerp(cf[q].x, nf.x, al), bias_lerp(cf[q].y, nf.y, al), bias_lerp(cf[q].z, nf.z, al),
+                                bias_lerp(cf[q].w, nf.w, al));
+            cg[q] = make_float4(bias_lerp(cg[q].x, ng.x, al), bias_lerp(cg[q].y, ng.y, al), bias_lerp(cg[q].z, ng.z, al),
+                                bias_lerp(cg[q].w, ng.w, al));
+        }
+    }
 
     float mx = 0.f;
 #pragma unroll
@@ -739,7 +776,7 @@ int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float*
                          (reinterpret_cast<uintptr_t>(bg) & 15) == 0 && (frames.hop == 0 || frames.stride % 4 == 0),
                      "fp16 x 2 layer forward with per-clip bias rows: the rows must be 16-byte aligned and their stride a "
                      "multiple of 4 floats (stride %lld, frame stride %lld)", bias_stride, frames.hop ? frames.stride : 0ll);
-    const int mode = !cond ? kCondNone : frames.hop > 0 ? kCondFrame : kCondClip;
+    const int mode = !cond ? kCondNone : frames.hop > 0 ? (frames.interp ? kCondLinear : kCondFrame) : kCondClip;
 #define FWDH_LAUNCH(SAVE, COND)                                                                                            \
     hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
                        tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
@@ -747,12 +784,13 @@ int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float*
     do {                                                        \
         if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame);  \
         else if (mode == kCondClip) FWDH_LAUNCH(SAVE, kCondClip); \
-        else FWDH_LAUNCH(SAVE, kCondNone);                      \
+        else if (mode == kCondNone) FWDH_LAUNCH(SAVE, kCondNone); \
+        else FWDH_LAUNCH(SAVE, kCondLinear);                    \
     } while (0)
     // (sigmoid-only saving, SAVE = 2, belongs to stacks whose backward recovers tanh: a stack with bias rows is never one, and
     // wn_stack_fwd refuses the combination; the per-clip form is kept as it was, a per-frame one is not instantiated)
     if (fs) FWDH_MODES(1);
-    else if (gs && mode == kCondFrame) { wn::set_error("fp16 x 2 layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+    else if (gs && (mode == kCondFrame || mode == kCondLinear)) { wn::set_error("fp16 x 2 layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
     else if (gs && mode == kCondClip) FWDH_LAUNCH(2, kCondClip);
     else if (gs) FWDH_LAUNCH(2, kCondNone);
     else FWDH_MODES(0);
@@ -788,12 +826,14 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
         // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
         const bool frame = hb && c.frames.hop > 0;
         if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
-        if (frame && fs)
-            hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<1, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
-                               B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
-        else if (frame)
-            hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<0, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
-                               B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+        const bool lerp = frame && c.frames.interp != 0;          // linear interpolation between frames: FRAME == 2
+#define FWDF_LAUNCH(SAVE, MODE)                                                                                        \
+    hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, true, MODE>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs, \
+                       B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
+        if (frame && !lerp && fs) FWDF_LAUNCH(1, 1);
+        else if (frame && !lerp) FWDF_LAUNCH(0, 1);
+        else if (lerp && fs) FWDF_LAUNCH(1, 2);
+        else if (lerp) FWDF_LAUNCH(0, 2);
         else if (fs && hb) FWD1_LAUNCH(1, true);
         else if (fs) FWD1_LAUNCH(1, false);
         else if (gs && hb) FWD1_LAUNCH(2, true);
@@ -801,6 +841,7 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
         else if (hb) FWD1_LAUNCH(0, true);
         else FWD1_LAUNCH(0, false);
 #undef FWD1_LAUNCH
+#undef FWDF_LAUNCH
         WN_LAUNCH_CHECK();
         return WN_OK;
     }
@@ -811,12 +852,14 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
     const bool frame = hb && c.frames.hop > 0;
     if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
-    if (frame && fs)
-        hipLaunchKernelGGL((k_layer_fwd_mfma32<1, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
-                           B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
-    else if (frame)
-        hipLaunchKernelGGL((k_layer_fwd_mfma32<0, true, true>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs,
-                           B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames);
+    const bool lerp = frame && c.frames.interp != 0;          // linear interpolation between frames: FRAME == 2
+#define FWDF_LAUNCH(SAVE, MODE)                                                                                        \
+    hipLaunchKernelGGL((k_layer_fwd_mfma32<SAVE, true, MODE>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs, \
+                       B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
+    if (frame && !lerp && fs) FWDF_LAUNCH(1, 1);
+    else if (frame && !lerp) FWDF_LAUNCH(0, 1);
+    else if (lerp && fs) FWDF_LAUNCH(1, 2);
+    else if (lerp) FWDF_LAUNCH(0, 2);
     else if (fs && hb) FWD_LAUNCH(1, true);
     else if (fs) FWD_LAUNCH(1, false);
     else if (gs && hb) FWD_LAUNCH(2, true);
@@ -824,6 +867,7 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     else if (hb) FWD_LAUNCH(0, true);
     else FWD_LAUNCH(0, false);
 #undef FWD_LAUNCH
+#undef FWDF_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
 }

@@ -49,6 +49,12 @@ static int check_bias_tables(const char* fn, const WnStackDesc* d, const WnExec*
 // before any device work and handed to the call.  bias_hop == 0: one row per clip, the other two fields are not read.
 static int take_bias_frames(const char* fn, const WnStackDesc* d, const WnExec* ex, int T, Call& c) {
     WN_CHECK_ARG(d->bias_hop >= 0, "%s: WnStackDesc.bias_hop = %d is negative", fn, d->bias_hop);
+    if (ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP)) {        // bias_interp is read under the flag only
+        WN_CHECK_ARG(d->bias_interp == 0 || d->bias_interp == 1, "%s: WnStackDesc.bias_interp = %d is neither 0 (repeat) nor 1 "
+                                                                 "(linear)", fn, d->bias_interp);
+        WN_CHECK_ARG(d->bias_interp == 0 || d->bias_hop > 0, "%s: WnStackDesc.bias_interp = %d without frames (bias_hop = 0)", fn,
+                     d->bias_interp);
+    }
     if (d->bias_hop == 0) return WN_OK;
     WN_CHECK_ARG(ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP), "%s: WnStackDesc.bias_hop = %d without WN_EXEC_BIAS_PER_CLIP", fn,
                  d->bias_hop);
@@ -60,11 +66,12 @@ static int take_bias_frames(const char* fn, const WnStackDesc* d, const WnExec* 
     // (the kernels form t + bias_phase in 32 bits)
     WN_CHECK_ARG((long long)T + d->bias_phase <= 2147483647ll, "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn,
                  (long long)T + d->bias_phase);
-    const long long frames = ((long long)T + d->bias_phase + d->bias_hop - 1) / d->bias_hop;
+    // linear interpolation reads row j + 1 at the last position too: one row more, and never a clamp
+    const long long frames = ((long long)T + d->bias_phase + d->bias_hop - 1) / d->bias_hop + (d->bias_interp ? 1 : 0);
     WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
-                 "%s: the clip stride (WnExec.reserved = %d) is below %lld frames x bias_frame_stride = %d", fn, ex->reserved,
-                 frames, d->bias_frame_stride);
-    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride};
+                 "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d", fn, ex->reserved,
+                 frames, d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride);
+    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride, d->bias_interp};
     return WN_OK;
 }
 }  // namespace wn

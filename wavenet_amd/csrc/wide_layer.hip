@@ -19,6 +19,7 @@ namespace wn {
 
 // bf / bg != NULL (WN_EXEC_BIAS_PER_CLIP): clip b's bias row, bias_stride floats apart, is added to the pre-activations here --
 // the GEMMs in front then ran without a bias
+template <bool LERP>          // LERP: linear interpolation between the frame's row and the next (BiasFrames.interp; bias_lerp)
 __global__ void k_wide_gate(float* __restrict__ a, float* __restrict__ g, float* __restrict__ z, float* __restrict__ fs,
                             float* __restrict__ gs, long long n4, int T, int Cd, int Z, const float* __restrict__ bf,
                             const float* __restrict__ bg, long long bias_stride, BiasFrames fr) {
@@ -31,8 +32,18 @@ __global__ void k_wide_gate(float* __restrict__ a, float* __restrict__ g, float*
         const long long brow = (bt / T) * bias_stride + bias_frame_off(fr, t) + (i * 4 - bt * Cd);   // (clip, frame of t)
         const float* rf = bf + brow;
         const float* rg = bg + brow;
-        av.x += rf[0]; av.y += rf[1]; av.z += rf[2]; av.w += rf[3];
-        gv.x += rg[0]; gv.y += rg[1]; gv.z += rg[2]; gv.w += rg[3];
+        if (LERP) {
+            const float al = bias_frame_alpha(fr, t);
+            const float* nf = rf + fr.stride;
+            const float* ng = rg + fr.stride;
+            av.x += bias_lerp(rf[0], nf[0], al); av.y += bias_lerp(rf[1], nf[1], al);
+            av.z += bias_lerp(rf[2], nf[2], al); av.w += bias_lerp(rf[3], nf[3], al);
+            gv.x += bias_lerp(rg[0], ng[0], al); gv.y += bias_lerp(rg[1], ng[1], al);
+            gv.z += bias_lerp(rg[2], ng[2], al); gv.w += bias_lerp(rg[3], ng[3], al);
+        } else {
+            av.x += rf[0]; av.y += rf[1]; av.z += rf[2]; av.w += rf[3];
+            gv.x += rg[0]; gv.y += rg[1]; gv.z += rg[2]; gv.w += rg[3];
+        }
     }
     if (t < Z) { av = make_float4(0, 0, 0, 0); gv = av; }                      // reference zero prefix
     const float4 f = make_float4(fast_tanh(av.x), fast_tanh(av.y), fast_tanh(av.z), fast_tanh(av.w));
@@ -120,8 +131,12 @@ int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, co
     rc = conv_gemm(c, x, Wg, per_clip ? nullptr : bg, gbuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
     const long long n4 = (long long)B * T * Cd / 4;
-    hipLaunchKernelGGL(k_wide_gate, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z,
-                       per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride, c.frames);
+    if (per_clip && c.frames.hop > 0 && c.frames.interp)
+        hipLaunchKernelGGL(k_wide_gate<true>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z, bf, bg,
+                           c.bias_stride, c.frames);
+    else
+        hipLaunchKernelGGL(k_wide_gate<false>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z,
+                           per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride, c.frames);
     WN_LAUNCH_CHECK();
     CGArgs a{};
     base_args(a, B, T);

@@ -11,9 +11,21 @@ int check_precision(const char* fn, const WnExec* ex);   // WN_EARG + error text
 int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f, const void* row_g, const char* names);
 // Local conditioning (WnStackDesc.bias_hop > 0 under WN_EXEC_BIAS_PER_CLIP): a clip's bias row becomes a block of rows, one per
 // frame of `hop` positions, `stride` floats apart; position t reads frame (t + phase) / hop.  hop == 0: one row per clip.
-struct BiasFrames { int hop, phase; long long stride; };
+// interp == 1 (WnStackDesc.bias_interp, linear interpolation between frames): with p = t + phase, j = p / hop and
+// alpha = float(p % hop) / float(hop), position t reads  r[j] + alpha * (r[j + 1] - r[j])  -- bias_lerp, three separately
+// rounded fp32 operations, so equal neighbours (and alpha == 0) give r[j] exactly; a block holds one row more than the frames
+// the call covers.  interp == 0: the row of the frame, as before.
+struct BiasFrames { int hop, phase; long long stride; int interp; };
 __host__ __device__ __forceinline__ long long bias_frame_off(const BiasFrames& fr, int t) {
     return fr.hop ? (long long)((t + fr.phase) / fr.hop) * fr.stride : 0;
+}
+// the weight of row j + 1 at position t (fr.hop > 0): float(p % hop) / float(hop), an IEEE fp32 division
+__device__ __forceinline__ float bias_frame_alpha(const BiasFrames& fr, int t) {
+    const int p = t + fr.phase;
+    return __fdiv_rn((float)(p - (p / fr.hop) * fr.hop), (float)fr.hop);
+}
+__device__ __forceinline__ float bias_lerp(float a, float b, float alpha) {      // a + alpha (b - a), never contracted
+    return __fadd_rn(a, __fmul_rn(alpha, __fsub_rn(b, a)));
 }
 struct Call {
     explicit Call(const WnExec* ex);     // ex == NULL: bf16x3, no flags, no scratch, no plan
@@ -24,7 +36,7 @@ struct Call {
     int fwd_t1_min_blocks;               // WnExec.fwd_t1_min_blocks with the default (512) filled in
     StepPlan* plan;                      // WnExec.plan, or NULL
     long long bias_stride;               // WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bf / bg (dbf / dbg) rows; else 0
-    BiasFrames frames = {0, 0, 0};       // set by wn_stack_fwd / wn_stack_bwd from the descriptor (per-frame rows); else hop == 0
+    BiasFrames frames = {0, 0, 0, 0};    // set by wn_stack_fwd / wn_stack_bwd from the descriptor (per-frame rows); else hop == 0
 
     static constexpr size_t kTail = 256;
     bool flag(unsigned f) const { return (flags & f) != 0; }
@@ -78,7 +90,7 @@ int generic_conv_bwd(const float*, const float*, const float*, float*, float*, f
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
                       int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0,
-                      BiasFrames frames = {0, 0, 0});
+                      BiasFrames frames = {0, 0, 0, 0});
 int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
@@ -139,7 +151,7 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live);
 // bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, bias_stride % 4 == 0), the COND kernels
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
                       int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr,
-                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0});
+                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0, 0});
 int mfma_layer_fwd_group_len(const int* dil, int l0, int L);   // layers from l0 on that one group launch can chain
 int mfma_layer_fwd_h2_group(const float* x, const void* img, int l0, int nl, float* const* outs, float* const* zs,
                             float* const* fs, float* const* gs, const int* dil, const int* Zs, int B, int T, hipStream_t s);
@@ -182,7 +194,11 @@ int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, in
 // (t + fr.phase) / fr.hop == f, in a fixed order (k_colsum_per_frame); rows of frames wholly below tmin are not touched
 int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
                              long long stride, BiasFrames fr, hipStream_t s);
-// what the layer backwards call: the per-frame form when c.frames.hop > 0, the per-clip form otherwise
+// Linear interpolation (fr.interp == 1): row f of a block of frames + 1 rows receives  sum (1 - alpha_t) d[t]  over the t >= tmin
+// of frame f  +  sum alpha_t d[t]  over those of frame f - 1 (k_colsum_per_frame_lerp, the same grid idea with one row more)
+int generic_colsum_per_frame_lerp(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf,
+                                  float* dbg, long long stride, BiasFrames fr, hipStream_t s);
+// what the layer backwards call: the per-frame forms when c.frames.hop > 0 (by c.frames.interp), the per-clip form otherwise
 int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
                              float* dbf, float* dbg, hipStream_t s);
 

@@ -41,7 +41,8 @@ class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
-                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0):
+                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
+                 local_interp: str = "repeat"):
         self._dec = None
         self._dec_keep = None
         self._dec_stale = True
@@ -57,7 +58,7 @@ class FasterWaveNet(WaveNet):
         self._hist_pos = 0
         super().__init__(params, compat_zero_prefix=compat_zero_prefix, seed=seed, storage=storage,
                          condition_classes=condition_classes, condition_channels=condition_channels,
-                         local_channels=local_channels, local_hop=local_hop)
+                         local_channels=local_channels, local_hop=local_hop, local_interp=local_interp)
 
     def __del__(self):
         try:
@@ -110,6 +111,7 @@ class FasterWaveNet(WaveNet):
             keep["table"] = rows
             d.frame_bias, d.n_frames, d.frame_stride = rows.data_ptr(), int(rows.shape[0]), int(rows.shape[1])
             d.frame_hop, d.frame_phase = int(hop), int(phase)
+            d.frame_interp = 1 if self.local_interp == "linear" else 0
         return d, keep
 
     # -- local conditioning: one utterance's features -> what the prefill and the decoder handle take ------------------------
@@ -136,7 +138,8 @@ class FasterWaveNet(WaveNet):
     def _decoder_table(self, feats, phase, W):
         """The decoder's table after a prefill over W positions: the step that consumes the sample at absolute position
         p = phase + W + k reads column p // hop, so the handle gets the rows from column (phase + W) // hop on and the phase
-        (phase + W) % hop."""
+        (phase + W) % hop.  With linear interpolation a step also reads the column after its own; the rows go on to the last
+        column given, so the one after the last that is needed is there (``_utterance_local`` has checked it)."""
         col, ph = divmod(int(phase) + int(W), self.local_hop)
         rows = self.local_biases(feats[0], phase)
         col = min(col, int(rows.shape[0]) - 1)            # (n_samples == 1: nothing is decoded, any row will do)

@@ -68,7 +68,9 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
     ``local``: the sequence's (F, >= ceil(n / H)) features for a locally conditioned model (hop H): sample i of the sequence,
     as a network input, reads column i // H (``local_alignment`` with s0 = the piece's first sample); the silence in front of
     the first sample reads column 0.  The pieces of one launch share one phase, so ``chunk_width`` must be a multiple of H
-    (raises otherwise); the result still does not depend on ``chunk_width`` or ``batch_size`` beyond arithmetic."""
+    (raises otherwise); the result still does not depend on ``chunk_width`` or ``batch_size`` beyond arithmetic.  With
+    ``local_interp="linear"`` every sample also reads the column after its own, so ``local`` needs ceil(n / H) + 1 columns
+    and neighbouring pieces overlap by one column."""
     import torch
     t = net.to_variable(np.asarray(tokens) if not isinstance(tokens, torch.Tensor) else tokens)
     if t.dim() != 1 or t.is_floating_point():
@@ -109,7 +111,7 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
         kw = {}
         if ext is not None:
             ph = (launch[0][0] + shift) % H
-            need = (C - 1 + w + ph + H - 1) // H
+            need = (C - 1 + w + ph + H - 1) // H + (1 if getattr(net, "local_interp", "repeat") == "linear" else 0)
             kw = dict(local=torch.stack([ext[:, (a + shift) // H:(a + shift) // H + need] for a, _ in launch]).contiguous(),
                       local_phase=ph)
         out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt, condition=cond, **kw).reshape(-1)

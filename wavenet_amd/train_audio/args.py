@@ -56,6 +56,9 @@ _LOCAL_FLAGS = (
                                   "array with one column per --local-hop samples (python -m wavenet_amd.train_audio.features "
                                   "writes log-mel ones); F and the hop go to <model-dir>/local.json"),
     (("--local-hop",), int, None, "train --local-dir: samples per feature column (256 unless local.json says otherwise)"),
+    (("--local-interp",), str, None, "train --local-dir: how the features reach the sample rate, 'repeat' (a column holds for "
+                                     "its hop samples) or 'linear' (interpolated between neighbouring columns, a column anchored "
+                                     "at the first sample of its frame); stored in local.json, which generate and evaluate follow"),
 )
 _LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
                "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
@@ -69,7 +72,7 @@ class Args(argparse.Namespace):
     """What :func:`parse` returns: the defaults of ``_EMA_FLAGS`` live here, not in the instance."""
     ema_decay, valid_wav_dir, ema = 0.0, None, False
     speaker_prefix, condition_channels, speaker = False, None, None
-    local_dir, local_hop, local = None, None, None
+    local_dir, local_hop, local, local_interp = None, None, None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -120,6 +123,8 @@ def parse(argv=None):
         ap.error("--condition-channels goes with --speaker-prefix")
     if args.local_hop is not None and (args.local_dir is None or args.local_hop < 1):
         ap.error("--local-hop H goes with --local-dir and needs H >= 1")
+    if args.local_interp is not None and (args.local_dir is None or args.local_interp not in ("repeat", "linear")):
+        ap.error("--local-interp {repeat,linear} goes with --local-dir")
     if args.local:
         n = utterance_prompts(args)[0] or 1
         if len(args.local) not in (1, n):

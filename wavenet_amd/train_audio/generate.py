@@ -154,6 +154,9 @@ def main(argv=None):
         # generated defaults to what they cover (-s left at its default), and more than that is refused before anything runs
         iw = input_width_of(params)
         cover = min(f.shape[1] for f in feats) * config[1] - iw + 1          # samples that can be emitted
+        # (linear interpolation: the column behind the last is the driver's to supply -- the file's last one again -- so n
+        # columns still give n * hop samples)
+        feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir)) for f in feats]
         if cover < 1:
             raise SystemExit("generate: the features cover {} samples, fewer than the {} of the window".format(cover + iw - 1, iw))
         if not seconds_given:

@@ -5,7 +5,13 @@ samples OF THE TOKENS AS TRAINING READS THEM (``data.load_audio_file``: mu-law, 
 tokens k * hop .. (k + 1) * hop - 1.  ``python -m wavenet_amd.train_audio.features`` writes log-mel files of that kind.
 
 ``local.json`` holds ``{"channels": F, "hop": H}``: whenever it exists the network is built locally conditioned
-(``wavenet.json`` is unchanged), and a resumed run must find the same values."""
+(``wavenet.json`` is unchanged), and a resumed run must find the same values.  ``train --local-interp linear`` adds
+``"interp": "linear"`` -- the key is written ONLY then, so a repeat-mode file is byte for byte what it always was; a file
+without it means "repeat" (``load_interp``).
+
+Linear interpolation reads, at every position, the column after the position's own, so a window needs one more column than it
+spans.  The library never clamps: the drivers supply that column by repeating the file's last one (``with_extra_column``);
+``file_features`` still asks a file for ceil(samples / hop) columns only."""
 from __future__ import annotations
 
 import json
@@ -16,6 +22,7 @@ import numpy as np
 
 FILE = "local.json"
 DEFAULT_HOP = 256
+INTERP = ("repeat", "linear")
 
 
 def load_config(model_dir: str) -> Optional[Tuple[int, int]]:
@@ -34,14 +41,44 @@ def load_config(model_dir: str) -> Optional[Tuple[int, int]]:
     return channels, hop
 
 
-def ensure_config(model_dir: str, channels: int, hop: int) -> Tuple[int, int]:
-    """train --local-dir: write the file on the first run; a resumed run must find the SAME values or it stops."""
+def load_interp(model_dir: str) -> Optional[str]:
+    """"repeat" or "linear": how ``<model_dir>/local.json`` says the features reach the sample rate (no "interp" key:
+    "repeat"); None when the checkpoint is not locally conditioned."""
+    if load_config(model_dir) is None:
+        return None
+    filename = os.path.join(model_dir, FILE)
+    with open(filename) as f:
+        interp = json.load(f).get("interp", "repeat")
+    if interp not in INTERP:
+        raise Exception("{}: \"interp\" must be one of {}, got {!r}".format(filename, list(INTERP), interp))
+    return interp
+
+
+def with_extra_column(features: np.ndarray, interp: Optional[str]) -> np.ndarray:
+    """The features as the network takes them: with ``interp == "linear"`` the last column once more behind the others (the
+    column that the last position's interpolation reads); unchanged otherwise."""
+    if interp != "linear":
+        return features
+    return np.ascontiguousarray(np.concatenate([features, features[:, -1:]], axis=1))
+
+
+def ensure_config(model_dir: str, channels: int, hop: int, interp: Optional[str] = None) -> Tuple[int, int]:
+    """train --local-dir: write the file on the first run; a resumed run must find the SAME values or it stops.  ``interp``:
+    what --local-interp gave (None: not given -- a first run then trains "repeat", a resumed one keeps the file's mode)."""
     have = load_config(model_dir)
+    if interp is not None and interp not in INTERP:
+        raise SystemExit("--local-interp must be one of {}, got {!r}".format(list(INTERP), interp))
     if have is None:
         os.makedirs(model_dir, exist_ok=True)
+        d = {"channels": int(channels), "hop": int(hop)}
+        if interp == "linear":
+            d["interp"] = "linear"
         with open(os.path.join(model_dir, FILE), "w") as f:
-            json.dump({"channels": int(channels), "hop": int(hop)}, f)
+            json.dump(d, f)
         return int(channels), int(hop)
+    if interp is not None and interp != load_interp(model_dir):
+        raise SystemExit("{}: this checkpoint was trained with --local-interp {}, the command line gives {}: a resumed run must "
+                         "find the same mode".format(os.path.join(model_dir, FILE), load_interp(model_dir), interp))
     if have != (int(channels), int(hop)):
         raise SystemExit("{}: this checkpoint was trained on {} feature channels at hop {}, the command line gives {} at hop {}: "
                          "a resumed run must find the same values".format(os.path.join(model_dir, FILE), have[0], have[1],

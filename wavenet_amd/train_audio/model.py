@@ -64,14 +64,16 @@ def build(args, train: bool = False):
 
     Features: ``args.local_dir`` with ``train`` (the training driver) reads the channel count F from the feature file of the first .wav file and writes it,
     with the hop, to ``local.json`` -- or checks both against the one already there.  Whenever that file exists the network
-    is built locally conditioned, and ``net.local`` is (F, hop) (None otherwise)."""
+    is built locally conditioned, and ``net.local`` is (F, hop) (None otherwise); ``args.local_interp`` (train) goes into the
+    file the same way and ``net.local_interp`` is the file's mode."""
     params = load_params(args.model_dir)
     local_dir = getattr(args, "local_dir", None)
     if local_dir is not None and train:                                     # (evaluate and generate read the config only)
         wavs = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
         have = _local.load_config(args.model_dir)
         hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
-        local = _local.ensure_config(args.model_dir, _local.directory_channels(local_dir, wavs), hop)
+        local = _local.ensure_config(args.model_dir, _local.directory_channels(local_dir, wavs), hop,
+                                     getattr(args, "local_interp", None))
     else:
         local = _local.load_config(args.model_dir)
     if bool(getattr(args, "speaker_prefix", False)):
@@ -81,7 +83,7 @@ def build(args, train: bool = False):
         table = _speakers.load_table(args.model_dir)
     cond = dict(condition_classes=len(table[0]), condition_channels=table[1]) if table else {}
     if local:
-        cond.update(local_channels=local[0], local_hop=local[1])
+        cond.update(local_channels=local[0], local_hop=local[1], local_interp=_local.load_interp(args.model_dir))
     net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed, **cond)
     net.speakers = table[0] if table else None
     net.local = local

@@ -31,15 +31,17 @@ class _Crops(object):
     """train.py:14-22 with the signal resident on the device: the start offsets are drawn on the host from numpy's
     global generator (the draw the reference makes, so ``--seed`` selects the same crops), the gather runs on the GPU."""
 
-    def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device, features=None, hop=0, shift=0):
+    def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device, features=None, hop=0, shift=0,
+                 extra_column=False):
         """``features`` (F, columns) on the grid ``local.padded`` describes (index into ``signal`` + ``shift`` = position,
         position // hop = column): starts are then drawn so that every crop begins on a column border (phase 0), and ``draw``
-        also returns the crops' (B, F, ceil((input_width + target_width) / hop)) columns."""
+        also returns the crops' (B, F, ceil((input_width + target_width) / hop)) columns -- one more with ``extra_column``
+        (linear interpolation; ``features`` then ends with the repeated last column of ``local.with_extra_column``)."""
         self.hop, self.shift = int(hop), int(shift)
         self.features = None
         if features is not None:
             self.features = torch.as_tensor(features).to(device)
-            self.fcol = torch.arange((input_width + target_width + hop - 1) // hop, device=device)
+            self.fcol = torch.arange((input_width + target_width + hop - 1) // hop + int(extra_column), device=device)
         self.n = int(signal.size)
         self.iw, self.tw = input_width, target_width
         if self.n - target_width - input_width - 1 <= 0:
@@ -79,8 +81,9 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     fkw = {}
     if local is not None:
         feats = _local.file_features(local_dir, path_to_file, signals.size, local[0], local[1])
-        ext, shift = _local.padded(feats, iw, local[1])
-        fkw = dict(features=ext, hop=local[1], shift=shift)
+        interp = getattr(net, "local_interp", "repeat")
+        ext, shift = _local.padded(_local.with_extra_column(feats, interp), iw, local[1])
+        fkw = dict(features=ext, hop=local[1], shift=shift, extra_column=interp == "linear")
     signals = np.concatenate([np.full((iw,), silence, dtype=np.int32), signals.astype(np.int32)])   # train.py:53
     crops = _Crops(signals, iw, train_width, net.device, **fkw)
     # a conditioned model: every crop carries the label of the file it came from

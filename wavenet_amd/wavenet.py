@@ -289,7 +289,8 @@ class _StackFn(_Fn):
         # net._cond_offsets[l][0], its gate row at [l][1] -- handed to the library as bias rows one block row apart
         # (WN_EXEC_BIAS_PER_CLIP); the backward returns the block's gradient.
         # `frames` = (hop, phase) (local conditioning): `cond` is then the (B, n, sum 2 cd) block of _LocalFn, a row per (clip,
-        # frame) -- clips n block rows apart, frames one (WnStackDesc.bias_hop / bias_phase / bias_frame_stride).
+        # frame) -- clips n block rows apart, frames one (WnStackDesc.bias_hop / bias_phase / bias_frame_stride).  A third entry
+        # 1 selects linear interpolation between the rows (WnStackDesc.bias_interp), which reads one row more.
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
@@ -300,7 +301,7 @@ class _StackFn(_Fn):
             if frames is None and tuple(cond.shape) != (B, net._cond_rows):
                 raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (tuple(cond.shape), (B, net._cond_rows)))
             if frames is not None:
-                need = frames_needed(T, frames[0], frames[1])
+                need = frames_needed(T, frames[0], frames[1], "linear" if len(frames) > 2 and frames[2] else "repeat")
                 if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != net._cond_rows or cond.shape[1] < need:
                     raise _lib.WaveNetHipError("local conditioning block is %s, expected (%d, >= %d, %d)"
                                                % (tuple(cond.shape), B, need, net._cond_rows))
@@ -363,17 +364,25 @@ class _StackFn(_Fn):
         return dx, None, None, None, None, None, dcond, None
 
 
-def frames_needed(T: int, hop: int, phase: int = 0) -> int:
+LOCAL_INTERP = ("repeat", "linear")
+
+
+def frames_needed(T: int, hop: int, phase: int = 0, interp: str = "repeat") -> int:
     """Feature columns a window of ``T`` positions reads at ``hop`` positions per column, the first position ``phase`` positions
-    into its column: ceil((T + phase) / hop)."""
-    return (int(T) + int(phase) + int(hop) - 1) // int(hop)
+    into its column: ceil((T + phase) / hop); one more with ``interp="linear"``, where every position also reads the column
+    after its own."""
+    if interp not in LOCAL_INTERP:
+        raise Exception("interp must be 'repeat' or 'linear', got %r" % (interp,))
+    return (int(T) + int(phase) + int(hop) - 1) // int(hop) + (1 if interp == "linear" else 0)
 
 
 def local_alignment(s0: int, hop: int):
     """THE alignment rule of local conditioning, in one place: network input position t of a clip whose first input sample is
     sample ``s0`` of its file reads feature column (s0 + t) // hop.  Returns (first column, phase) = (s0 // hop, s0 % hop): the
     caller passes the file's columns from the first one on, with ``local_phase=`` the phase.  The decoder follows the same
-    rule: the step that consumes the sample at absolute position p reads column p // hop."""
+    rule: the step that consumes the sample at absolute position p reads column p // hop.  Linear interpolation
+    (``local_interp="linear"``) keeps the rule: column k is anchored at the FIRST sample of its frame, position k * hop, and a
+    position p inside the frame reads column p // hop moved towards column p // hop + 1 by the fraction (p % hop) / hop."""
     if hop <= 0 or s0 < 0:
         raise Exception("local_alignment: hop must be positive and s0 non-negative, got hop = %d, s0 = %d" % (hop, s0))
     return int(s0) // int(hop), int(s0) % int(hop)
@@ -709,7 +718,8 @@ class WaveNet(object):
     head_activation = "relu"          # wavenet.py:588
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
-                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0):
+                 condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
+                 local_interp: str = "repeat"):
         """``storage="bf16"`` (BASELINE config 5; not in the reference): activations in bfloat16, fp32 accumulation, fp32
         master weights; for 128 residual / dilation channels, filter width 2, a multiple of 256 skip channels.
 
@@ -731,7 +741,16 @@ class WaveNet(object):
         methods then take ``local=`` -- float32 features (B, F, n), n >= ceil((T + phase) / H), surplus columns ignored -- and
         ``local_phase=`` (an int, default 0).  Alignment (``local_alignment``): network input position t of a clip whose first
         input sample is sample s0 of its file reads feature column (s0 + t) // H; the caller passes the columns from s0 // H
-        on, with phase s0 % H.  With global conditioning also on, the clip's row is added to every frame row of its clip."""
+        on, with phase s0 % H.  With global conditioning also on, the clip's row is added to every frame row of its clip.
+
+        ``local_interp`` ("repeat", the default and the above; or "linear"): how the features reach the sample rate.  "linear"
+        interpolates between neighbouring columns instead of repeating one -- the parameter-free form of the paper's learned
+        upsampling.  Column k is anchored at the first sample of its frame, position k H (a decision: the alignment rule and
+        the decoder's "position p reads column p // H" stay what they are); position p reads
+        r[j] + alpha (r[j + 1] - r[j]) with j = p // H and alpha = float32(p % H) / float32(H), r the projected rows (V is
+        linear, so interpolating the features is interpolating the rows; nothing of size B x T x sum 2 cd exists).  Every
+        window then needs ONE MORE column, ``frames_needed(T, H, phase, "linear")``: the library never clamps, the caller
+        supplies the column after the last (the command-line drivers repeat the file's last one)."""
         params.check()
         if storage not in ("fp32", "bf16"):
             raise Exception("storage must be 'fp32' or 'bf16'")
@@ -753,6 +772,11 @@ class WaveNet(object):
         if self.local_channels and not params.residual_conv_dilation_no_bias:
             raise Exception("local conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
                             "convolutions' bias; a second, shared one is not supported)")
+        if local_interp not in LOCAL_INTERP:
+            raise Exception("local_interp must be 'repeat' or 'linear', got %r" % (local_interp,))
+        if local_interp != "repeat" and not self.local_channels:
+            raise Exception("local_interp = %r needs local conditioning (local_channels / local_hop)" % (local_interp,))
+        self.local_interp = local_interp
         self.params = params
         self.storage = storage
         self.gemm_precision = None          # None: the module default (wavenet_amd.set_gemm_precision) at call time
@@ -1061,6 +1085,7 @@ class WaveNet(object):
         setattr(d, name_g, C.cast(bg, C.POINTER(C.c_void_p)))
         if frames is not None:
             d.bias_hop, d.bias_phase, d.bias_frame_stride = int(frames[0]), int(frames[1]), self._cond_rows
+            d.bias_interp = int(frames[2]) if len(frames) > 2 else 0
         return d, (bf, bg, block)
 
     def _condition_ids(self, condition, B):
@@ -1123,10 +1148,12 @@ class WaveNet(object):
         if f.dim() != 3 or f.shape[0] != B or f.shape[1] != self.local_channels or f.dtype != torch.float32:
             raise Exception("local= must be float32 of shape (%d, %d, frames), got %s %s"
                             % (B, self.local_channels, f.dtype, tuple(f.shape)))
-        need = frames_needed(T, self.local_hop, phase)
+        need = frames_needed(T, self.local_hop, phase, self.local_interp)
         if f.shape[2] < need:
-            raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d"
-                            % (f.shape[2], T, self.local_hop, phase, need))
+            raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d%s"
+                            % (f.shape[2], T, self.local_hop, phase, need,
+                               " (linear interpolation reads the column after the last position's own)"
+                               if self.local_interp == "linear" else ""))
         return f, phase
 
     def _local_block(self, feats, glob=None):
@@ -1438,7 +1465,7 @@ class WaveNet(object):
         feats, phase = self._local_features(local, int(x.shape[0]), int(x.shape[3]), local_phase)
         frames = None
         if feats is not None:
-            cond, frames = self._local_block(feats, cond), (self.local_hop, phase)
+            cond, frames = self._local_block(feats, cond), (self.local_hop, phase, 1 if self.local_interp == "linear" else 0)
         if self.storage == "bf16":
             self._pack16_if_stale()
             out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled())
