@@ -150,7 +150,24 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                                   index order; no float atomics, no scratch, bit-reproducible).
                                                   A row whose two segments hold no t >= Z is not touched.
                                       WN_EARG before any device work: bias_interp outside {0, 1}; bias_interp != 0 with
-                                      bias_hop == 0 */
+                                      bias_hop == 0
+                                      A phase per clip (WnStackDesc.bias_phase_tab != NULL; NULL, the default, is all of the
+                                      above, the same kernels and the same bits): a device array of B int32, read when the
+                                      kernels run -- one captured step serves crops that start at any sample.  Position t of
+                                      clip b uses p = t + bias_phase_tab[b] wherever it used t + bias_phase: the frame index
+                                      p / h and, with bias_interp = 1, alpha = float32(p % h) / float32(h).  Row layout and
+                                      strides are unchanged; the per-frame column sums of the backward add, for a clip of
+                                      phase p, exactly the rows in exactly the chunks a bias_phase = p call adds.  The host
+                                      cannot see the values, so the geometry is sized for the worst phase h - 1: a clip's
+                                      block (and its gradient block) holds n_max = ceil((T + h - 1) / h) rows, one more with
+                                      bias_interp = 1, and WN_EARG is returned for reserved < n_max * bias_frame_stride.
+                                      Rows that no position of a clip reads are neither read nor written.  The caller passes
+                                      values in [0, h).  As a FENCE, not a feature, every kernel reduces the value it reads
+                                      to (unsigned) v % h -- once per tile or workgroup where the clip is uniform -- so a
+                                      garbage value cannot take an access outside the clip's block.
+                                      WN_EARG before any device work, each naming bias_phase_tab: a table with bias_hop == 0;
+                                      a table without the flag; a table together with bias_phase != 0 (ambiguous); a pointer
+                                      that is not 4-byte aligned; T + bias_hop - 1 beyond 32 bits */
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
 #define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
@@ -258,11 +275,16 @@ typedef struct WnStackDesc {
     /* host arrays (n_layers) of device pointers; bias tables or entries may be NULL             */
     const float* const* Wf; const float* const* bf; const float* const* Wg; const float* const* bg;
     const float* const* Wp; const float* const* bp; const float* const* Ws; const float* const* bs;
+    const int* bias_phase_tab;             /* NULL (the default): bias_phase below holds for every clip.  Else a DEVICE pointer to B
+                                              int32 values, the phase of clip b, read when the kernels run: position t of clip b
+                                              uses p = t + bias_phase_tab[b] wherever it used t + bias_phase (see the define).
+                                              Declared ahead of the local-conditioning group; descriptors are filled by field name */
     /* local conditioning (read only under WN_EXEC_BIAS_PER_CLIP -- see the define; all 0 = one row per clip) */
-    int bias_interp;                       /* 0: position t reads its frame's row; 1: linear interpolation towards the next row
+    int bias_interp;                      /* 0: position t reads its frame's row; 1: linear interpolation towards the next row
                                               (declared at the head of the group; descriptors are filled by field name)         */
     int bias_hop;                          /* > 0: a bias row per (clip, frame); position t reads frame (t + bias_phase) / bias_hop */
-    int bias_phase;                        /* 0 <= bias_phase < bias_hop, one value per call                                       */
+    int bias_phase;                        /* 0 <= bias_phase < bias_hop, one value per call (a phase per clip: bias_phase_tab
+                                              above, and this field 0)                                                             */
     int bias_frame_stride;                 /* floats between consecutive frames' rows inside a clip's block (>= the layer's cd)    */
 } WnStackDesc;
 /* xs (n_layers,B,T,Cr) receives every layer's output (xs[n_layers-1] is the stack output); z, f, g

@@ -54,6 +54,7 @@ class WnStackDesc(C.Structure):
     _fields_ = [
         ("n_layers", _i), ("Cr", _i), ("Cs", _i), ("fw", _i), ("cd", _ip), ("dilation", _ip),
         ("Wf", _pp), ("bf", _pp), ("Wg", _pp), ("bg", _pp), ("Wp", _pp), ("bp", _pp), ("Ws", _pp), ("bs", _pp),
+        ("bias_phase_tab", _p),                                               # device int32 (B,): a phase per clip; NULL = bias_phase
         ("bias_interp", _i),                                                  # 0 = repeat, 1 = linear interpolation between frames
         ("bias_hop", _i), ("bias_phase", _i), ("bias_frame_stride", _i),     # local conditioning: a bias row per (clip, frame)
     ]

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(1024) void k_colsum_per_frame(const float* __restri
     __shared__ float red[16][64];
     const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
     const int f = blockIdx.y, b = blockIdx.z;
-    const long long lo = (long long)f * fr.hop - fr.phase, hi = lo + fr.hop;
+    const long long lo = (long long)f * fr.hop - frame_phase(fr, b), hi = lo + fr.hop;   // (the clip is blockIdx.z: one scalar load)
     const int ta = lo > tmin ? (int)lo : tmin, tb = hi < T ? (int)hi : T;
     if (tb <= ta) return;                                 // (uniform over the workgroup)
     const bool ok = m < 2 * Cd;
@@ -426,7 +426,9 @@ __global__ __launch_bounds__(1024) void k_colsum_per_frame(const float* __restri
 int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
                              long long stride, BiasFrames fr, hipStream_t s) {
     if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
-    const int frames = (int)(((long long)T + fr.phase + fr.hop - 1) / fr.hop);
+    // (a table's values are not known here: the grid covers the n_max frames of phase hop - 1; a workgroup whose segment
+    // holds no row leaves without touching its row)
+    const int frames = (int)(((long long)T + (fr.tab ? fr.hop - 1 : fr.phase) + fr.hop - 1) / fr.hop);
     WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
     WN_CHECK_SHAPE(frames <= 65535, "per-frame bias gradients: at most 65,535 frames per clip and call");
     int t_chunk = 256;                                      // generic_colsum_per_clip's choice, from the same rows
@@ -479,7 +481,7 @@ __global__ __launch_bounds__(1024) void k_colsum_per_frame_lerp(const float* __r
     __shared__ float red[16][64];
     const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
     const int f = blockIdx.y, b = blockIdx.z;
-    const long long loA = (long long)f * fr.hop - fr.phase, loB = loA - fr.hop;      // first positions of frames f and f - 1
+    const long long loA = (long long)f * fr.hop - frame_phase(fr, b), loB = loA - fr.hop;      // first positions of frames f and f - 1
     const int taA = loA > tmin ? (int)loA : tmin, tbA = loA + fr.hop < T ? (int)(loA + fr.hop) : T;
     const int taB = loB > tmin ? (int)loB : tmin, tbB = loA < T ? (int)loA : T;
     if (tbA <= taA && tbB <= taB) return;                 // (uniform over the workgroup)
@@ -505,7 +507,7 @@ __global__ __launch_bounds__(1024) void k_colsum_per_frame_lerp(const float* __r
 int generic_colsum_per_frame_lerp(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf,
                                   float* dbg, long long stride, BiasFrames fr, hipStream_t s) {
     if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
-    const int rows = (int)(((long long)T + fr.phase + fr.hop - 1) / fr.hop) + 1;
+    const int rows = (int)(((long long)T + (fr.tab ? fr.hop - 1 : fr.phase) + fr.hop - 1) / fr.hop) + 1;   // (n_max + 1 with a table)
     WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
     WN_CHECK_SHAPE(rows <= 65535, "interpolated per-frame bias gradients: at most 65,534 frames per clip and call");
     int t_chunk = 32;
@@ -543,11 +545,12 @@ __global__ void k_gate_fwd(const float* __restrict__ x, const float* __restrict_
     if (t >= Z) {
         // bias_stride != 0: one bias row per clip (WN_EXEC_BIAS_PER_CLIP); fr.hop != 0: per (clip, frame of t)
         // fr.interp != 0: interpolated between that row and the next one (bias_lerp)
-        const long long brow = b * bias_stride + bias_frame_off(fr, t) + o;
+        const int ph = frame_phase(fr, b);                 // the clip is bt / T: per lane here
+        const long long brow = b * bias_stride + bias_frame_off(fr, ph, t) + o;
         a = bf ? bf[brow] : 0.f;
         g = bg ? bg[brow] : 0.f;
         if (LERP) {
-            const float al = bias_frame_alpha(fr, t);
+            const float al = bias_frame_alpha(fr, ph, t);
             if (bf) a = bias_lerp(a, bf[brow + fr.stride], al);
             if (bg) g = bias_lerp(g, bg[brow + fr.stride], al);
         }

@@ -142,15 +142,16 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
         f32x16 aa, ag;
         if (HAS_BIAS && FRAME == 2) {  // ... interpolated between the rows of the lane's frame and the next one
             const int tb = valid ? t : T - 1;
-            const long long brow = b * bstride + bias_frame_off(fr, tb);
-            const float al = bias_frame_alpha(fr, tb);
+            const int ph = frame_phase(fr, b);             // a tile belongs to one clip: one scalar load
+            const long long brow = b * bstride + bias_frame_off(fr, ph, tb);
+            const float al = bias_frame_alpha(fr, ph, tb);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
                 ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
             }
         } else if (HAS_BIAS && FRAME) {       // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
-            const long long brow = b * bstride + bias_frame_off(fr, valid ? t : T - 1);
+            const long long brow = b * bstride + bias_frame_off(fr, frame_phase(fr, b), valid ? t : T - 1);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
@@ -277,15 +278,16 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
 
     f32x16 aa, ag;
     if (HAS_BIAS && FRAME == 2) {      // ... interpolated between the rows of the lane's frame and the next one
-        const long long brow = b * bstride + bias_frame_off(fr, tc);
-        const float al = bias_frame_alpha(fr, tc);
+        const int ph = frame_phase(fr, b);                 // a tile belongs to one clip: one scalar load
+        const long long brow = b * bstride + bias_frame_off(fr, ph, tc);
+        const float al = bias_frame_alpha(fr, ph, tc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
             ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
         }
     } else if (HAS_BIAS && FRAME) {           // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
-        const long long brow = b * bstride + bias_frame_off(fr, tc);
+        const long long brow = b * bstride + bias_frame_off(fr, frame_phase(fr, b), tc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
@@ -365,7 +367,7 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // pass through the tile's power-of-two scale or an fp16 split.  For t < Z neither the convolution nor the bias counts.
 // COND is one of three compile-time modes: kCondNone, kCondClip (the above) and kCondFrame (local conditioning: clip b's row
 // becomes a block of rows fr.stride floats apart and a lane, which owns ONE time step, reads the row of its own frame
-// (tc + fr.phase) / fr.hop -- the same eight float4 requests; lanes of one frame read one address, so a wave fetches one row
+// (tc + phase) / fr.hop (phase: frame_phase, the call's or the clip's own) -- the same eight float4 requests; lanes of one frame read one address, so a wave fetches one row
 // per frame it spans.  The frame index is one plain 32-bit division per lane: a reciprocal multiply was not tried, the
 // kernel's time is its MFMA block and x traffic).
 // kCondLinear (WnStackDesc.bias_interp == 1) reads the rows of frames j and j + 1 -- sixteen float4 requests -- and forms
@@ -373,7 +375,10 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // stay live under it (row j + 1 is requested behind the weight image's barrier: requested with row j it spilled 92 bytes a
 // lane); the interpolated value is added where the per-frame one is: behind the rescale.
 enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2, kCondLinear = 3 };
-template <int SAVE, int COND>
+// TAB (with kCondFrame / kCondLinear): the phase is the clip's own, read from BiasFrames.tab (WnStackDesc.bias_phase_tab) -- a
+// compile-time mode, so the instantiations without a table are the code they were (decided at run time, the pointer moved
+// kCondLinear's register count: 118 -> 122 with tanh saved).
+template <int SAVE, int COND, bool TAB = false>
 __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     const float* __restrict__ x, const char* __restrict__ img_g, float* __restrict__ out, float* __restrict__ zout,
     float* __restrict__ fout, float* __restrict__ gout, int B, int T, int d, int Z, int tile_lo, int tiles_per_b,
@@ -412,9 +417,11 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
         }
     }
     float4 cf[4], cg[4];
+    // the tile's clip is uniform over the wave: its phase is one scalar load in front of the bias requests (frame_phase)
+    const int ph = (COND == kCondFrame || COND == kCondLinear) ? frame_phase_as<TAB>(fr, b) : 0;
     if (COND) {
         long long rowb = (long long)b * bstride + 4 * h;
-        if (COND == kCondFrame || COND == kCondLinear) rowb += (long long)((tc + fr.phase) / fr.hop) * fr.stride;
+        if (COND == kCondFrame || COND == kCondLinear) rowb += (long long)((tc + ph) / fr.hop) * fr.stride;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             cf[q] = *reinterpret_cast<const float4*>(bf + rowb + 8 * q);
@@ -427,8 +434,8 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_h2_t1(
     if (COND == kCondLinear) {
         // the next frame's rows are requested only here, where the staged weight image has left its registers, and folded
         // into cf / cg at once: under the MFMA block this mode holds what kCondFrame holds
-        const long long rown = (long long)b * bstride + 4 * h + (long long)((tc + fr.phase) / fr.hop + 1) * fr.stride;
-        const float al = bias_frame_alpha(fr, tc);
+        const long long rown = (long long)b * bstride + 4 * h + (long long)((tc + ph) / fr.hop + 1) * fr.stride;
+        const float al = bias_frame_alpha(fr, ph, tc);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float4 nf = *reinterpret_cast<const float4*>(bf + rown + 8 * q);
@@ -780,9 +787,14 @@ int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float*
 #define FWDH_LAUNCH(SAVE, COND)                                                                                            \
     hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
                        tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
+#define FWDH_LAUNCH_TAB(SAVE, COND)                                                                                        \
+    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND, true>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, \
+                       Z, tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
 #define FWDH_MODES(SAVE)                                        \
     do {                                                        \
-        if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame);  \
+        if (mode == kCondFrame && frames.tab) FWDH_LAUNCH_TAB(SAVE, kCondFrame);  \
+        else if (mode == kCondLinear && frames.tab) FWDH_LAUNCH_TAB(SAVE, kCondLinear);  \
+        else if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame);  \
         else if (mode == kCondClip) FWDH_LAUNCH(SAVE, kCondClip); \
         else if (mode == kCondNone) FWDH_LAUNCH(SAVE, kCondNone); \
         else FWDH_LAUNCH(SAVE, kCondLinear);                    \
@@ -795,6 +807,7 @@ int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float*
     else if (gs) FWDH_LAUNCH(2, kCondNone);
     else FWDH_MODES(0);
 #undef FWDH_MODES
+#undef FWDH_LAUNCH_TAB
 #undef FWDH_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;

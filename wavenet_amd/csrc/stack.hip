@@ -55,23 +55,40 @@ static int take_bias_frames(const char* fn, const WnStackDesc* d, const WnExec* 
         WN_CHECK_ARG(d->bias_interp == 0 || d->bias_hop > 0, "%s: WnStackDesc.bias_interp = %d without frames (bias_hop = 0)", fn,
                      d->bias_interp);
     }
+    // a phase per clip (bias_phase_tab): a device pointer the host never dereferences
+    const bool per_clip = ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP);
+    const int* tab = d->bias_phase_tab;
+    WN_CHECK_ARG(!tab || per_clip, "%s: WnStackDesc.bias_phase_tab without WN_EXEC_BIAS_PER_CLIP", fn);
+    WN_CHECK_ARG(!tab || d->bias_hop > 0, "%s: WnStackDesc.bias_phase_tab without frames (bias_hop = 0)", fn);
     if (d->bias_hop == 0) return WN_OK;
-    WN_CHECK_ARG(ex && (ex->flags & WN_EXEC_BIAS_PER_CLIP), "%s: WnStackDesc.bias_hop = %d without WN_EXEC_BIAS_PER_CLIP", fn,
-                 d->bias_hop);
+    WN_CHECK_ARG(per_clip, "%s: WnStackDesc.bias_hop = %d without WN_EXEC_BIAS_PER_CLIP", fn, d->bias_hop);
     WN_CHECK_ARG(d->bias_phase >= 0 && d->bias_phase < d->bias_hop, "%s: WnStackDesc.bias_phase = %d outside [0, bias_hop = %d)",
                  fn, d->bias_phase, d->bias_hop);
+    WN_CHECK_ARG(!tab || d->bias_phase == 0, "%s: WnStackDesc.bias_phase_tab together with bias_phase = %d is ambiguous (a table "
+                                             "goes with bias_phase = 0)", fn, d->bias_phase);
+    WN_CHECK_ARG((reinterpret_cast<uintptr_t>(tab) & 3) == 0, "%s: WnStackDesc.bias_phase_tab is not 4-byte aligned", fn);
     for (int l = 0; l < d->n_layers; ++l)
         WN_CHECK_ARG(d->bias_frame_stride >= d->cd[l], "%s: WnStackDesc.bias_frame_stride = %d below cd = %d (layer %d)", fn,
                      d->bias_frame_stride, d->cd[l], l);
-    // (the kernels form t + bias_phase in 32 bits)
-    WN_CHECK_ARG((long long)T + d->bias_phase <= 2147483647ll, "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn,
-                 (long long)T + d->bias_phase);
+    // (the kernels form t + phase in 32 bits); the host cannot see a table's values: everything is sized for phase hop - 1
+    const int worst = tab ? d->bias_hop - 1 : d->bias_phase;
+    if (tab)
+        WN_CHECK_ARG((long long)T + worst <= 2147483647ll, "%s: T + WnStackDesc.bias_hop - 1 = %lld does not fit 32 bits (a "
+                     "bias_phase_tab entry may be bias_hop - 1)", fn, (long long)T + worst);
+    else
+        WN_CHECK_ARG((long long)T + worst <= 2147483647ll, "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn,
+                     (long long)T + worst);
     // linear interpolation reads row j + 1 at the last position too: one row more, and never a clamp
-    const long long frames = ((long long)T + d->bias_phase + d->bias_hop - 1) / d->bias_hop + (d->bias_interp ? 1 : 0);
+    const long long frames = ((long long)T + worst + d->bias_hop - 1) / d->bias_hop + (d->bias_interp ? 1 : 0);
+    if (tab)
+        WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
+                     "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d (WnStackDesc.bias_phase_tab: "
+                     "sized for the worst phase, bias_hop - 1)", fn, ex->reserved, frames,
+                     d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride);
     WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
                  "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d", fn, ex->reserved,
                  frames, d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride);
-    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride, d->bias_interp};
+    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride, d->bias_interp, tab};
     return WN_OK;
 }
 }  // namespace wn

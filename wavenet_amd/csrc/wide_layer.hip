@@ -29,11 +29,12 @@ __global__ void k_wide_gate(float* __restrict__ a, float* __restrict__ g, float*
     const int t = (int)(bt % T);
     float4 av = reinterpret_cast<const float4*>(a)[i], gv = reinterpret_cast<const float4*>(g)[i];
     if (bf) {
-        const long long brow = (bt / T) * bias_stride + bias_frame_off(fr, t) + (i * 4 - bt * Cd);   // (clip, frame of t)
+        const int ph = frame_phase(fr, (int)(bt / T));                              // the clip is bt / T: per lane here
+        const long long brow = (bt / T) * bias_stride + bias_frame_off(fr, ph, t) + (i * 4 - bt * Cd);   // (clip, frame of t)
         const float* rf = bf + brow;
         const float* rg = bg + brow;
         if (LERP) {
-            const float al = bias_frame_alpha(fr, t);
+            const float al = bias_frame_alpha(fr, ph, t);
             const float* nf = rf + fr.stride;
             const float* ng = rg + fr.stride;
             av.x += bias_lerp(rf[0], nf[0], al); av.y += bias_lerp(rf[1], nf[1], al);

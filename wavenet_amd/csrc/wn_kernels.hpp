@@ -15,13 +15,28 @@ int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f,
 // alpha = float(p % hop) / float(hop), position t reads  r[j] + alpha * (r[j + 1] - r[j])  -- bias_lerp, three separately
 // rounded fp32 operations, so equal neighbours (and alpha == 0) give r[j] exactly; a block holds one row more than the frames
 // the call covers.  interp == 0: the row of the frame, as before.
-struct BiasFrames { int hop, phase; long long stride; int interp; };
-__host__ __device__ __forceinline__ long long bias_frame_off(const BiasFrames& fr, int t) {
-    return fr.hop ? (long long)((t + fr.phase) / fr.hop) * fr.stride : 0;
+// tab != NULL (WnStackDesc.bias_phase_tab): a phase per clip in device memory, tab[b] for clip b; `phase` is then 0 and unused.
+struct BiasFrames { int hop, phase; long long stride; int interp; const int* tab; };
+// THE phase of clip b -- everything that needs one asks here.  Without a table it is the call's one value.  With one, the
+// value read is reduced into [0, hop): callers pass values inside that range, the reduction is a fence that keeps a garbage
+// value from taking an access outside the clip's block (the geometry is sized for phase hop - 1), not a feature.  Where b is
+// uniform over a wave (a tile, a workgroup) this is one scalar load.
+// frame_phase_as<TAB>: "has a table" as a compile-time mode, for a kernel whose scalar-phase instantiation must stay
+// the code it was (k_layer_fwd_h2_t1, which sits near its register limit); frame_phase decides at run time.
+template <bool TAB>
+__device__ __forceinline__ int frame_phase_as(const BiasFrames& fr, int b) {
+    return TAB ? (int)((unsigned)fr.tab[b] % (unsigned)fr.hop) : fr.phase;
+}
+__device__ __forceinline__ int frame_phase(const BiasFrames& fr, int b) {
+    return fr.tab ? frame_phase_as<true>(fr, b) : frame_phase_as<false>(fr, b);
+}
+// ph = frame_phase(fr, clip of t)
+__device__ __forceinline__ long long bias_frame_off(const BiasFrames& fr, int ph, int t) {
+    return fr.hop ? (long long)((t + ph) / fr.hop) * fr.stride : 0;
 }
 // the weight of row j + 1 at position t (fr.hop > 0): float(p % hop) / float(hop), an IEEE fp32 division
-__device__ __forceinline__ float bias_frame_alpha(const BiasFrames& fr, int t) {
-    const int p = t + fr.phase;
+__device__ __forceinline__ float bias_frame_alpha(const BiasFrames& fr, int ph, int t) {
+    const int p = t + ph;
     return __fdiv_rn((float)(p - (p / fr.hop) * fr.hop), (float)fr.hop);
 }
 __device__ __forceinline__ float bias_lerp(float a, float b, float alpha) {      // a + alpha (b - a), never contracted
@@ -36,7 +51,7 @@ struct Call {
     int fwd_t1_min_blocks;               // WnExec.fwd_t1_min_blocks with the default (512) filled in
     StepPlan* plan;                      // WnExec.plan, or NULL
     long long bias_stride;               // WN_EXEC_BIAS_PER_CLIP: floats between consecutive clips' bf / bg (dbf / dbg) rows; else 0
-    BiasFrames frames = {0, 0, 0, 0};    // set by wn_stack_fwd / wn_stack_bwd from the descriptor (per-frame rows); else hop == 0
+    BiasFrames frames = {0, 0, 0, 0, nullptr};    // set by wn_stack_fwd / wn_stack_bwd from the descriptor (per-frame rows); else hop == 0
 
     static constexpr size_t kTail = 256;
     bool flag(unsigned f) const { return (flags & f) != 0; }
@@ -90,7 +105,7 @@ int generic_conv_bwd(const float*, const float*, const float*, float*, float*, f
 int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
                       int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0,
-                      BiasFrames frames = {0, 0, 0, 0});
+                      BiasFrames frames = {0, 0, 0, 0, nullptr});
 int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
@@ -151,7 +166,7 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live);
 // bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, bias_stride % 4 == 0), the COND kernels
 int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
                       int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr,
-                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0, 0});
+                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0, 0, nullptr});
 int mfma_layer_fwd_group_len(const int* dil, int l0, int L);   // layers from l0 on that one group launch can chain
 int mfma_layer_fwd_h2_group(const float* x, const void* img, int l0, int nl, float* const* outs, float* const* zs,
                             float* const* fs, float* const* gs, const int* dil, const int* Zs, int B, int T, hipStream_t s);

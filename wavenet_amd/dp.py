@@ -70,7 +70,8 @@ class DataParallel(object):
         per clip, so they are sharded with the clips: rank r trains ``x[lo:hi]`` under ``condition=ids[lo:hi]``; the two
         conditioning tensors live in the flat arena and travel in the one all-reduce like every other gradient.  A locally
         conditioned model's features are per clip too and are sharded the same way: ``local=feats[lo:hi]``; its projection
-        lives in the arena as well."""
+        lives in the arena as well.  So are per-clip phases: ``local_phase=phases[lo:hi]`` -- a rank's clips keep their own
+        phases (they travel in device memory, ``WnStackDesc.bias_phase_tab``), and the ranks need not agree on one."""
         if global_batch % self.world:
             raise ValueError("global batch %d is not divisible by world size %d" % (global_batch, self.world))
         per = global_batch // self.world

@@ -15,7 +15,10 @@ What changes from step to step lives in device memory, never in kernel arguments
   * the features of a locally conditioned model: a static (B, F, n) buffer that ``step(local=)`` refills.  The projection node
     and the per-frame bias block are captured with the step, likewise WITH the plan.  The phase is a field of the stack
     descriptor -- a kernel argument, not device memory -- so it is fixed at capture; ``step(local_phase=)`` with another value
-    raises (training draws clip starts at multiples of the hop: phase 0).
+    raises (training draws clip starts at multiples of the hop: phase 0);
+  * the phases of a locally conditioned model captured with ONE PHASE PER CLIP (``local_phase=`` a sequence): a static int32
+    buffer that the kernels read when they run (``WnStackDesc.bias_phase_tab``).  ``step(local_phase=seq)`` refills it, so
+    one captured step serves crops that start at any sample; the table adds no launch.
 With data parallelism the gradient all-reduce stays OUTSIDE the graphs (forward+backward graph -> RCCL all-reduce ->
 optimiser graph), so nothing here depends on capturing a collective.
 """
@@ -25,13 +28,14 @@ import torch
 
 from . import _lib
 from .ema import ema_rate_at
+from .wavenet import LocalPhases, _one_phase, check_local_phases
 
 
-def default_loss(net, x, tgt, window_only: bool = False, condition=None, local=None, local_phase: int = 0):
+def default_loss(net, x, tgt, window_only: bool = False, condition=None, local=None, local_phase=0):
     """train_audio/train.py:60-75: loss over the last ``tgt.shape[1]`` columns of the window.  ``window_only`` also skips
     the columns that window cannot see (WaveNet.forward_residual_block); same loss, same gradients.  ``condition``: one class
-    id per clip, for a globally conditioned model; ``local`` / ``local_phase``: the clips' features and phase, for a locally
-    conditioned one."""
+    id per clip, for a globally conditioned model; ``local`` / ``local_phase``: the clips' features and phase (an int, or one
+    phase per clip), for a locally conditioned one."""
     c = net.forward_causal_block(x)
     _, s = net.forward_residual_block(c, t_off=x.shape[1] - tgt.shape[1], window_only=window_only, condition=condition,
                                       local=local, local_phase=local_phase)
@@ -44,12 +48,14 @@ class TrainStepGraph(object):
     ``net.backprop(default_loss(net, x, tgt))`` for batches of the captured shape."""
 
     def __init__(self, net, x, tgt, loss_fn=default_loss, warmup: int = 2, keep_graph: bool = False, condition=None,
-                 local=None, local_phase: int = 0):
+                 local=None, local_phase=0):
         """``keep_graph``: keep the captured hipGraph_t next to the executable graph so that :meth:`node_counts` can walk it
         (measurement aid: bench.py counts the kernel nodes of the step it times).  ``condition``: one class id per clip for a
         globally conditioned model; ``loss_fn`` is then called with ``condition=`` the static id buffer.  ``local`` /
         ``local_phase``: the clips' features (B, F, n) and phase for a locally conditioned model; ``loss_fn`` is then called
-        with ``local=`` the static feature buffer and ``local_phase=`` the captured phase."""
+        with ``local=`` the static feature buffer and ``local_phase=`` the captured phase.  ``local_phase`` an int: the
+        phase is fixed at capture.  A sequence with one phase per clip: the phases live in a static int32 buffer
+        (``loss_fn`` receives it as a ``LocalPhases``) that :meth:`step` refills."""
         if not (net.gpu_enabled and x.is_cuda and tgt.is_cuda):
             raise _lib.WaveNetHipError("TrainStepGraph needs the network and the batch on a HIP device")
         self.net, self.loss_fn = net, loss_fn
@@ -59,6 +65,8 @@ class TrainStepGraph(object):
         self.condition = None if ids is None else ids.clone()
         feats, self.local_phase = net._local_features(local, int(x.shape[0]), int(x.shape[1]), local_phase)   # raises likewise
         self.local = None if feats is None else feats.clone()
+        if isinstance(self.local_phase, LocalPhases):           # this object's own static buffer, never the caller's tensor
+            self.local_phase = LocalPhases(self.local_phase.tab.clone(), self.local_phase.hop)
         opt = net.optimizer
         self._lr = torch.zeros((1,), device=x.device, dtype=torch.float32)
         self._ema_rate = torch.zeros((1,), device=x.device, dtype=torch.float32)      # 0: the warm-up steps leave the average alone
@@ -169,7 +177,9 @@ class TrainStepGraph(object):
         """One training step on (x, tgt) (default: the batch already in the static buffers).  Returns the loss
         (a device scalar that the next step overwrites).  ``condition``: the clips' class ids (conditioned models; default: the
         ids already in the static buffer).  ``local``: the clips' features, of the captured shape (locally conditioned models;
-        default: those already in the static buffer); ``local_phase`` must be the captured one."""
+        default: those already in the static buffer); ``local_phase`` must be the captured one when the step was captured
+        with an int; a step captured with one phase per clip takes any phases here (a sequence, or an int for all clips;
+        default: those already in the static buffer)."""
         net, opt = self.net, self.net.optimizer
         if self._hyper() != self._snap:
             raise _lib.WaveNetHipError(
@@ -185,7 +195,22 @@ class TrainStepGraph(object):
             if self.condition is None:
                 raise _lib.WaveNetHipError("condition= was given, but the captured step is unconditioned")
             self.condition.copy_(self.net._condition_ids(condition, int(self.x.shape[0])), non_blocking=True)
-        if local_phase is not None and int(local_phase) != self.local_phase:
+        per_clip = isinstance(self.local_phase, LocalPhases)
+        phases = None
+        if local_phase is not None and per_clip:
+            # checked on the host before anything is refilled: features and phases of one step change together or not at all
+            B = int(self.x.shape[0])
+            if isinstance(local_phase, LocalPhases):
+                phases = check_local_phases(local_phase.tab, B, self.local_phase.hop)
+            elif _one_phase(local_phase):
+                phases = check_local_phases([int(local_phase)] * B, B, self.local_phase.hop)     # an int is broadcast
+            else:
+                phases = check_local_phases(local_phase, B, self.local_phase.hop)
+        elif local_phase is not None and not _one_phase(local_phase):
+            raise _lib.WaveNetHipError("local_phase= holds one phase per clip, but the step was captured with the int phase %d "
+                                       "(the phase is a kernel argument there: capture a step with a sequence)"
+                                       % self.local_phase)
+        elif local_phase is not None and int(local_phase) != self.local_phase:
             raise _lib.WaveNetHipError("local_phase = %d, but the step was captured with phase %d (the phase is a kernel "
                                        "argument: capture another step)" % (int(local_phase), self.local_phase))
         if local is not None:
@@ -196,6 +221,8 @@ class TrainStepGraph(object):
                 raise _lib.WaveNetHipError("local= is %s, but the step was captured with features of shape %s"
                                            % (tuple(feats.shape), tuple(self.local.shape)))
             self.local.copy_(feats, non_blocking=True)
+        if phases is not None:
+            self.local_phase.fill(phases)
         opt.t += 1                                   # update() is not called on replay: keep Adam's clock here
         self._lr.fill_(opt.lr)
         if net.ema_enabled:                          # the schedule's clock, like Adam's: it also advances for a step skipped on the device

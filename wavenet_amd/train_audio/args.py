@@ -59,6 +59,9 @@ _LOCAL_FLAGS = (
     (("--local-interp",), str, None, "train --local-dir: how the features reach the sample rate, 'repeat' (a column holds for "
                                      "its hop samples) or 'linear' (interpolated between neighbouring columns, a column anchored "
                                      "at the first sample of its frame); stored in local.json, which generate and evaluate follow"),
+    (("--local-crop",), str, None, "train --local-dir: where crops start, 'frame' (on a feature column border, the default) or "
+                                   "'sample' (anywhere, as without features: one --seed selects the same crops; every crop "
+                                   "carries its own phase).  A property of the run, not of the checkpoint"),
 )
 _LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
                "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
@@ -72,7 +75,7 @@ class Args(argparse.Namespace):
     """What :func:`parse` returns: the defaults of ``_EMA_FLAGS`` live here, not in the instance."""
     ema_decay, valid_wav_dir, ema = 0.0, None, False
     speaker_prefix, condition_channels, speaker = False, None, None
-    local_dir, local_hop, local, local_interp = None, None, None, None
+    local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -125,6 +128,8 @@ def parse(argv=None):
         ap.error("--local-hop H goes with --local-dir and needs H >= 1")
     if args.local_interp is not None and (args.local_dir is None or args.local_interp not in ("repeat", "linear")):
         ap.error("--local-interp {repeat,linear} goes with --local-dir")
+    if args.local_crop is not None and (args.local_dir is None or args.local_crop not in ("frame", "sample")):
+        ap.error("--local-crop {frame,sample} goes with --local-dir")
     if args.local:
         n = utterance_prompts(args)[0] or 1
         if len(args.local) not in (1, n):

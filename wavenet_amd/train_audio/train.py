@@ -32,16 +32,24 @@ class _Crops(object):
     global generator (the draw the reference makes, so ``--seed`` selects the same crops), the gather runs on the GPU."""
 
     def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device, features=None, hop=0, shift=0,
-                 extra_column=False):
+                 extra_column=False, crop="frame"):
         """``features`` (F, columns) on the grid ``local.padded`` describes (index into ``signal`` + ``shift`` = position,
         position // hop = column): starts are then drawn so that every crop begins on a column border (phase 0), and ``draw``
         also returns the crops' (B, F, ceil((input_width + target_width) / hop)) columns -- one more with ``extra_column``
-        (linear interpolation; ``features`` then ends with the repeated last column of ``local.with_extra_column``)."""
-        self.hop, self.shift = int(hop), int(shift)
+        (linear interpolation; ``features`` then ends with the repeated last column of ``local.with_extra_column``).
+        ``crop="sample"`` (``--local-crop sample``): starts are drawn as they are without features -- any sample, the very
+        ``np.random.randint`` call, so one ``--seed`` selects the same crops with and without features -- and ``draw`` also
+        returns every crop's phase (start + shift) % hop; the columns run from (start + shift) // hop on and there are as
+        many as the worst phase needs, ceil((input_width + target_width + hop - 1) / hop) (one more with ``extra_column``),
+        the file's last column repeated where that runs past the file."""
+        if crop not in ("frame", "sample"):
+            raise Exception("crop must be 'frame' or 'sample', got %r" % (crop,))
+        self.hop, self.shift, self.crop = int(hop), int(shift), crop
         self.features = None
         if features is not None:
             self.features = torch.as_tensor(features).to(device)
-            self.fcol = torch.arange((input_width + target_width + hop - 1) // hop + int(extra_column), device=device)
+            worst = hop - 1 if crop == "sample" else 0
+            self.fcol = torch.arange((input_width + target_width + worst + hop - 1) // hop + int(extra_column), device=device)
         self.n = int(signal.size)
         self.iw, self.tw = input_width, target_width
         if self.n - target_width - input_width - 1 <= 0:
@@ -52,8 +60,17 @@ class _Crops(object):
     def draw(self, batch_size: int):
         hi = self.n - self.tw - self.iw - 1
         feats = None
+        phases = None
         if self.features is None:
             starts = np.random.randint(0, hi, size=batch_size)
+        elif self.crop == "sample":
+            starts = np.random.randint(0, hi, size=batch_size)        # the feature-less draw: same seed, same crops
+            pos = starts + self.shift
+            phases = (pos % self.hop).astype(np.int32)
+            first = torch.as_tensor(pos // self.hop).to(self.col.device)
+            # the worst-case column count may run past the file's columns: the last one is repeated, never an index beyond
+            cols = torch.clamp(first[:, None] + self.fcol[None, :], max=int(self.features.shape[1]) - 1)
+            feats = self.features[:, cols].permute(1, 0, 2).contiguous()
         else:
             # starts r, r + hop, r + 2 hop, ... below hi, r the first index whose position is a multiple of the hop: one draw,
             # as above
@@ -66,13 +83,16 @@ class _Crops(object):
         idx = torch.as_tensor(starts).to(self.col.device)[:, None] + self.col[None, :]
         win = self.signal[idx]                                     # (B, iw + tw + 1)
         x, tgt = win[:, :self.iw + self.tw].contiguous(), win[:, self.iw + 1:].contiguous()
+        if phases is not None:
+            return x, tgt, feats, phases
         return (x, tgt) if self.features is None else (x, tgt, feats)
 
 
 def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None,
-                local_dir=None):
+                local_dir=None, local_crop="frame"):
     """One file: returns the summed loss of its ``repeat`` updates (train.py:24-90).  ``local_dir``: where the file's feature
-    file lies (a locally conditioned model); crops then start on a feature column border."""
+    file lies (a locally conditioned model); crops then start on a feature column border (``local_crop="frame"``) or at any
+    sample, each with its own phase (``"sample"``: the crops a run without features draws)."""
     signals, _ = data.load_audio_file(path_to_file, quantization_steps=params.quantization_steps)
     iw = input_width_of(params)
     silence = 127 if params.quantization_steps > 127 else params.quantization_steps // 2
@@ -83,7 +103,7 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
         feats = _local.file_features(local_dir, path_to_file, signals.size, local[0], local[1])
         interp = getattr(net, "local_interp", "repeat")
         ext, shift = _local.padded(_local.with_extra_column(feats, interp), iw, local[1])
-        fkw = dict(features=ext, hop=local[1], shift=shift, extra_column=interp == "linear")
+        fkw = dict(features=ext, hop=local[1], shift=shift, extra_column=interp == "linear", crop=local_crop)
     signals = np.concatenate([np.full((iw,), silence, dtype=np.int32), signals.astype(np.int32)])   # train.py:53
     crops = _Crops(signals, iw, train_width, net.device, **fkw)
     # a conditioned model: every crop carries the label of the file it came from
@@ -100,6 +120,8 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
         drawn = crops.draw(batch_size)
         x, tgt = drawn[0], drawn[1]
         lkw = {} if local is None else {"local": drawn[2]}
+        if len(drawn) > 3:
+            lkw["local_phase"] = drawn[3]                           # a phase per crop (--local-crop sample)
         if use_graph and str(params.optimizer).lower() != "eve":     # Eve needs the loss on the host every update
             key = (batch_size, iw + train_width)
             graph = None if state is None else state.get(key)
@@ -171,7 +193,8 @@ def main(argv=None):
         for fn in files:
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
-                                        use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir)
+                                        use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir,
+                                        local_crop=args.local_crop or "frame")
             net.save(args.model_dir)
         average_loss /= len(files)
         sys.stdout.write("\033[2K\repoch: {} - {:.4e} loss - {} min\n".format(

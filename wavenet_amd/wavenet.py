@@ -291,6 +291,8 @@ class _StackFn(_Fn):
         # `frames` = (hop, phase) (local conditioning): `cond` is then the (B, n, sum 2 cd) block of _LocalFn, a row per (clip,
         # frame) -- clips n block rows apart, frames one (WnStackDesc.bias_hop / bias_phase / bias_frame_stride).  A third entry
         # 1 selects linear interpolation between the rows (WnStackDesc.bias_interp), which reads one row more.
+        # `phase` a LocalPhases (a phase per clip): its int32 device tensor becomes WnStackDesc.bias_phase_tab in both calls
+        # (bias_phase stays 0); ctx.frames keeps it alive for the backward.
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
@@ -301,7 +303,9 @@ class _StackFn(_Fn):
             if frames is None and tuple(cond.shape) != (B, net._cond_rows):
                 raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (tuple(cond.shape), (B, net._cond_rows)))
             if frames is not None:
-                need = frames_needed(T, frames[0], frames[1], "linear" if len(frames) > 2 and frames[2] else "repeat")
+                # (a phase per clip: the columns of the worst phase, whatever the phases are)
+                worst = frames[0] - 1 if isinstance(frames[1], LocalPhases) else frames[1]
+                need = frames_needed(T, frames[0], worst, "linear" if len(frames) > 2 and frames[2] else "repeat")
                 if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != net._cond_rows or cond.shape[1] < need:
                     raise _lib.WaveNetHipError("local conditioning block is %s, expected (%d, >= %d, %d)"
                                                % (tuple(cond.shape), B, need, net._cond_rows))
@@ -365,6 +369,47 @@ class _StackFn(_Fn):
 
 
 LOCAL_INTERP = ("repeat", "linear")
+
+
+class LocalPhases(object):
+    """A phase per clip, checked and on the device: ``tab`` is an int32 (B,) tensor whose entries lie in [0, ``hop``).  What
+    ``_local_features`` makes of a ``local_phase=`` sequence and what the stack node points ``WnStackDesc.bias_phase_tab`` at.
+    Passing one as ``local_phase=`` hands the tensor through as it stands -- no copy, no read-back: ``TrainStepGraph`` keeps
+    one as the static buffer its captured step reads and refills it (``fill``) between replays."""
+
+    def __init__(self, tab, hop):
+        self.tab, self.hop = tab, int(hop)
+
+    def __len__(self):
+        return int(self.tab.shape[0])
+
+    def fill(self, values):
+        """Refill the device buffer from a checked host array (``check_local_phases``)."""
+        self.tab.copy_(torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32)), non_blocking=False)
+
+
+def _one_phase(phase) -> bool:
+    """True for the int form of ``local_phase=`` (anything 0-dimensional), False for a phase per clip."""
+    if isinstance(phase, LocalPhases):
+        return False
+    return phase.dim() == 0 if isinstance(phase, torch.Tensor) else np.ndim(phase) == 0
+
+
+def check_local_phases(phase, B, hop):
+    """``local_phase=`` given as a 1-D sequence, numpy array or integer torch tensor -> int32 numpy (B,), every entry in
+    [0, hop); anything else raises before any device work and names the first offending clip.  (A device tensor is read
+    back for the check: pass a ``LocalPhases`` where that matters.)"""
+    a = phase.detach().cpu().numpy() if isinstance(phase, torch.Tensor) else np.asarray(phase)
+    if a.ndim != 1:
+        raise Exception("local_phase= takes an int or one phase per clip (a 1-D sequence), got shape %s" % (tuple(a.shape),))
+    if a.shape[0] != B:
+        raise Exception("local_phase= holds %d phases for %d clips" % (a.shape[0], B))
+    if a.dtype.kind not in "iu":
+        raise Exception("local_phase= takes integer phases, got %s (clip 0)" % a.dtype)
+    bad = np.nonzero((a < 0) | (a >= hop))[0]
+    if bad.size:
+        raise Exception("local_phase= must lie in [0, local_hop = %d), got %d for clip %d" % (hop, int(a[bad[0]]), int(bad[0])))
+    return a.astype(np.int32)
 
 
 def frames_needed(T: int, hop: int, phase: int = 0, interp: str = "repeat") -> int:
@@ -750,7 +795,14 @@ class WaveNet(object):
         r[j] + alpha (r[j + 1] - r[j]) with j = p // H and alpha = float32(p % H) / float32(H), r the projected rows (V is
         linear, so interpolating the features is interpolating the rows; nothing of size B x T x sum 2 cd exists).  Every
         window then needs ONE MORE column, ``frames_needed(T, H, phase, "linear")``: the library never clamps, the caller
-        supplies the column after the last (the command-line drivers repeat the file's last one)."""
+        supplies the column after the last (the command-line drivers repeat the file's last one).
+
+        A phase per clip: ``local_phase=`` of ``forward_one_step``, ``forward_residual_block``, ``token_nll``,
+        ``graph.default_loss`` and ``TrainStepGraph`` also takes a 1-D sequence, numpy array or integer tensor with one entry
+        per clip, each in [0, H) (anything else raises before any device work and names the first offending clip).  The
+        phases then live in device memory (``WnStackDesc.bias_phase_tab``) and are read when the kernels run, so one batch --
+        and one captured step -- holds clips that start at any sample.  Every clip then needs
+        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase."""
         params.check()
         if storage not in ("fp32", "bf16"):
             raise Exception("storage must be 'fp32' or 'bf16'")
@@ -1084,9 +1136,16 @@ class WaveNet(object):
         setattr(d, name_f, C.cast(bf, C.POINTER(C.c_void_p)))
         setattr(d, name_g, C.cast(bg, C.POINTER(C.c_void_p)))
         if frames is not None:
-            d.bias_hop, d.bias_phase, d.bias_frame_stride = int(frames[0]), int(frames[1]), self._cond_rows
+            tab = frames[1] if isinstance(frames[1], LocalPhases) else None
+            d.bias_hop, d.bias_frame_stride = int(frames[0]), self._cond_rows
+            d.bias_phase = 0 if tab is not None else int(frames[1])
+            d.bias_phase_tab = None if tab is None else tab.tab.data_ptr()
             d.bias_interp = int(frames[2]) if len(frames) > 2 else 0
-        return d, (bf, bg, block)
+            if tab is not None and (len(tab) != block.shape[0] or tab.hop != int(frames[0]) or tab.tab.dtype != torch.int32
+                                    or tab.tab.device != block.device or not tab.tab.is_contiguous()):
+                raise _lib.WaveNetHipError("the per-clip phases must be a contiguous int32 (%d,) tensor on the block's device, "
+                                           "checked against hop %d" % (block.shape[0], int(frames[0])))
+        return d, (bf, bg, block, frames)
 
     def _condition_ids(self, condition, B):
         """``condition=`` of the forward methods -> (B,) int64 class ids on the device, or None for an unconditioned model.
@@ -1129,32 +1188,49 @@ class WaveNet(object):
     # -- local conditioning ---------------------------------------------------------------------------------------------------
     def _local_features(self, local, B, T, phase=0):
         """``local=`` / ``local_phase=`` of the forward methods -> ((B, F, n) float32 features on the device, phase), or
-        (None, 0) for a model without local conditioning.  A locally conditioned model called without features raises, and so
+        (None, 0) for a model without local conditioning.  ``phase``: an int, or one phase per clip (a 1-D sequence, numpy
+        array or integer tensor; returned as a ``LocalPhases``).  A locally conditioned model called without features raises, and so
         does any other model called with them; so do too few columns (surplus ones are ignored)."""
         if not self.local_channels:
             if local is not None:
                 raise Exception("local= was given, but this model has no local conditioning (local_channels = 0)")
-            if phase:
+            if not _one_phase(phase) or phase:
                 raise Exception("local_phase= was given, but this model has no local conditioning (local_channels = 0)")
             return None, 0
         if local is None:
             raise Exception("this model is locally conditioned (%d channels, hop %d): pass local= (features of shape "
                             "(clips, %d, frames))" % (self.local_channels, self.local_hop, self.local_channels))
-        phase = int(phase)
-        if not 0 <= phase < self.local_hop:
-            raise Exception("local_phase= must lie in [0, local_hop = %d), got %d" % (self.local_hop, phase))
+        # an int: one phase for the call.  A sequence / array / integer tensor: a phase per clip, checked here on the host
+        # (before any device work); the call then needs the columns of the worst phase, local_hop - 1, whatever the phases
+        # are, so that a captured step stays valid for any later ones.
+        tab = None
+        if isinstance(phase, LocalPhases):
+            if len(phase) != B or phase.hop != self.local_hop:
+                raise Exception("local_phase= holds %d phases checked against hop %d for %d clips at hop %d"
+                                % (len(phase), phase.hop, B, self.local_hop))
+            tab = phase
+        elif _one_phase(phase):
+            phase = int(phase)
+            if not 0 <= phase < self.local_hop:
+                raise Exception("local_phase= must lie in [0, local_hop = %d), got %d" % (self.local_hop, phase))
+        else:
+            tab = check_local_phases(phase, B, self.local_hop)
         f = local if isinstance(local, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(local, dtype=np.float32)))
         f = self.to_variable(f)
         if f.dim() != 3 or f.shape[0] != B or f.shape[1] != self.local_channels or f.dtype != torch.float32:
             raise Exception("local= must be float32 of shape (%d, %d, frames), got %s %s"
                             % (B, self.local_channels, f.dtype, tuple(f.shape)))
-        need = frames_needed(T, self.local_hop, phase, self.local_interp)
+        worst = phase if tab is None else self.local_hop - 1
+        need = frames_needed(T, self.local_hop, worst, self.local_interp)
         if f.shape[2] < need:
-            raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d%s"
-                            % (f.shape[2], T, self.local_hop, phase, need,
+            raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d%s%s"
+                            % (f.shape[2], T, self.local_hop, worst, need,
                                " (linear interpolation reads the column after the last position's own)"
-                               if self.local_interp == "linear" else ""))
-        return f, phase
+                               if self.local_interp == "linear" else "",
+                               "" if tab is None else " (a phase per clip is sized for the worst phase, local_hop - 1)"))
+        if tab is not None and not isinstance(tab, LocalPhases):
+            tab = LocalPhases(torch.from_numpy(tab).to(f.device), self.local_hop)
+        return f, (phase if tab is None else tab)
 
     def _local_block(self, feats, glob=None):
         """The (B, n, sum 2 cd) block of per-(clip, frame) gate biases (an autograd node over the projection); with global
@@ -1458,7 +1534,10 @@ class WaveNet(object):
         receptive field and must not be used; loss and gradients are unchanged.
         ``condition``: one class id per clip, for a globally conditioned model (and only for one).
         ``local`` / ``local_phase``: (B, F, n) float32 features and the phase of position 0 inside its feature column, for a
-        locally conditioned model (and only for one); see ``local_alignment``."""
+        locally conditioned model (and only for one); see ``local_alignment``.  ``local_phase`` is an int (every clip at that
+        phase) or one phase per clip -- a 1-D sequence, numpy array or integer tensor, each entry in [0, local_hop): the
+        phases then travel in device memory (``WnStackDesc.bias_phase_tab``) and every clip needs
+        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
         cond = self._condition_block(condition, int(x.shape[0]))
