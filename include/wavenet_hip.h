@@ -170,8 +170,9 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                       that is not 4-byte aligned; T + bias_hop - 1 beyond 32 bits */
 #define WN_EXEC_NO_FWD_GROUPS 4u   /* fp16x2 stack forward: every layer its own launch (no k_layer_fwd_h2_grp); same results,
                                       bit for bit -- A/B timing and the parity tests of the per-layer kernel */
-#define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions: the older kernels (k_colgemm_b3, k_wgrad_b3w) instead of
-                                        k_colgemm_h2q / k_wgrad_h2p; same results, bit for bit -- A/B timing, parity tests */
+#define WN_EXEC_NO_PIPELINED_GEMM 8u /* fp16x2 skip contractions (skip sum, dz, dWs): the older kernels (k_colgemm_b3,
+                                        k_wgrad_b3w) instead of k_colgemm_h2q / k_dz_ws / k_wgrad_h2p; same results, bit for
+                                        bit -- A/B timing, parity tests */
 #define WN_EXEC_NO_MULTI_LAYER_BWD 16u /* fp16x2 chained stack backward: one launch per layer instead of the multi-layer
                                           launch (k_layer_bwd_chain_multi).  That launch has NO grid barrier: co-resident
                                           workgroups follow one dataflow word per 32-column tile ("layers completed"),

@@ -630,7 +630,8 @@ __global__ __launch_bounds__(256, MT == 8 ? 2 : 3) void k_colgemm_b3(CGArgs a, c
 //     per chunk (the launcher checks that the sources are equally spaced arrays of one chunk each with one row shift -- the
 //     layers' z of a stack -- or one array), M0 comes from scalar arithmetic.
 // Same results as k_colgemm_b3<0, ., 3, 8>, bit for bit (same products in the same order); config 2's skip sum 0.255 ->
-// 0.242 ms.  `dz` (mode 2: 8 chunks per workgroup, prologue and epilogue dominate) measured equal and stays on the older kernel.
+// 0.242 ms.  `dz` (mode 2: 8 chunks per workgroup, prologue and epilogue dominate) measured equal in this form; its own kernel
+// is k_dz_ws below.
 // =============================================================================================
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void asm_load16(f32x4& dst, const float* p) {
@@ -840,6 +841,211 @@ __global__ __launch_bounds__(256, 2) void k_colgemm_h2q(CGArgs a, const __bf16* 
     }
 }
 
+// =============================================================================================
+// k_dz_ws: mode 2 with 32-row problems and K = 256 (dz of the skip path: dz_l = Ws_l^T dskip for every layer l) with the
+// WEIGHTS STATIONARY.  One layer's fp16-split weight tile is 16 k-steps x 2 planes x 4 registers = 128 VGPRs: a wave owns one
+// layer, loads that layer's A operands from the split image once and keeps them in registers for the whole launch; nothing of A
+// touches LDS.  A workgroup is eight waves (two per SIMD, 256 registers each) = eight layers (a layer GROUP) and walks a range
+// of 32-column tiles of X:
+//   * per step the waves together fetch one 256 x 32 tile of X (16 consecutive k of one column per thread), scale and split it
+//     (same values as k_colgemm_b3's split2h) and write the high and low planes to LDS as B-operand fragments
+//     [k-step 16][plane 2][lane 64][8 fp16] = 32 KB, in a ring of two: the tile of step n + 1 is split and written under the
+//     MFMAs of step n, its global loads were issued a step before that.  A thread's (column, k-step) is dealt so that eight
+//     consecutive lanes write eight consecutive 16-byte slots (ds_write_b128: groups of 8 lanes, 128-byte bank window) and a
+//     fragment read is 64 consecutive slots (ds_read_b128): both conflict-free without a swizzle;
+//   * every wave reads the 32 fragments (two k-steps ahead of their use) and runs 16 k-steps x 3 terms in the term and k order
+//     of k_colgemm_b3<2, 0, 3, 8>: the results are IDENTICAL to that kernel's, bit for bit;
+//   * the finished 32 x 32 tile goes through the wave's 4 KB patch and leaves as whole 128-byte rows in the middle of the NEXT
+//     step, so that the stores are in flight under its MFMAs;
+//   * one s_barrier per step (it publishes tile n + 1 and retires tile n); no synchronisation between workgroups.
+// Grid: persistent, (layer groups) x (column ranges); the groups of one column range sit on the same XCD at consecutive
+// dispatch slots (as in k_colgemm_b3), so that X comes from HBM once and from that XCD's L2 for the other groups.  A group
+// past the last layer has idle waves: they take part in the fetch, the split and the barriers, and run no MFMA and no store.
+// =============================================================================================
+static constexpr int kWsTile = 32 * 1024;                    // one split tile of X
+static constexpr int kWsLds = 2 * kWsTile + 8 * 4096;        // the ring and the waves' row patches
+static constexpr int kWsAhead = 2;                           // fragment reads run this many k-steps ahead of their MFMAs
+
+__global__ __launch_bounds__(512, 1) void k_dz_ws(CGArgs a, const __bf16* __restrict__ img, int mtiles, int ntiles, int nranges) {
+    extern __shared__ __attribute__((aligned(16))) char ldsw[];
+    const float h2sx = h2_scale(a.xmax_dev, kH2ScaleX);
+    const float h2sw = h2_scale(a.wmax_dev, kH2ScaleW);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    int range, grp;
+    {   // the layer groups of one column range on the same XCD at consecutive slots
+        const int ng = (mtiles + 7) >> 3;
+        const int id = blockIdx.x;
+        const int full = nranges & ~7;
+        if (id < full * ng) {
+            const int g = id / (8 * ng), rem = id - g * 8 * ng;
+            range = g * 8 + (rem & 7);
+            grp = rem >> 3;
+        } else {
+            const int t = id - full * ng;
+            grp = t % ng;
+            range = full + t / ng;
+        }
+    }
+    const int t_lo = (int)((long long)range * ntiles / nranges), t_hi = (int)((long long)(range + 1) * ntiles / nranges);
+    if (t_lo >= t_hi) return;
+    const int layer = grp * 8 + wave;
+    const bool live = layer < mtiles;
+    // every argument the loop needs, read once (a scalar load inside the loop would turn the counted LDS waits into full ones)
+    const int N = (int)a.N, rows_out = a.rows_out_per_b, rows_src = a.rows_src_per_b, shift = a.off + a.soff[0];
+    const int ldo = a.ldo;
+    const long long ldx = a.ldx ? a.ldx : a.K[0];
+    const float* __restrict__ X = a.X[0];
+    float* __restrict__ og = a.out[live ? layer : 0];
+
+    f16x8 A[16][2];                                         // [k-step][plane]: this wave's layer, the launch's A operands
+    {
+        const char* ip = reinterpret_cast<const char*>(img) + (long long)(live ? layer : mtiles - 1) * kH2qTB + lane * 16;
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+                A[kk][pl] = *reinterpret_cast<const f16x8*>(ip + (long long)(kk >> 1) * mtiles * kH2qTB + (kk & 1) * kH2qHalf + pl * 1024);
+    }
+
+    // the column `by` (<= 32 <= rows_out) further on: n = b rows_out + r
+    auto advance = [&](int& n, int& b, int& r, int by) {
+        n += by; r += by;
+        const bool wrap = r >= rows_out;
+        r -= wrap ? rows_out : 0;
+        b += wrap ? 1 : 0;
+    };
+    // ---- the fetch: thread -> (column lcol of the tile, k = 16 kseg .. 16 kseg + 15) ----
+    const int lcol = (tid & 7) | ((tid >> 7) << 3), kseg = (tid >> 3) & 15;
+    int ln = t_lo * 32 + lcol, lb = ln / rows_out, lr = ln - lb * rows_out;
+    float4 raw[4];
+    float rsc = 0.f;                                        // the scale of the tile in `raw`; 0 for a column that reads as zero
+    auto load_raw = [&]() {                                 // a tile past the range's end is fetched and never used; a column
+        const int rs = lr + shift;                          // past N reads row 0
+        const bool rv = ln < N && rs >= 0 && rs < rows_src;
+        rsc = rv ? h2sx : 0.f;
+        const float* p = X + (rv ? (long long)lb * rows_src + rs : 0ll) * ldx + 16 * kseg;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) raw[i] = reinterpret_cast<const float4*>(p)[i];
+        advance(ln, lb, lr, 32);
+    };
+    auto split_write = [&](char* buf) {
+        float v[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float x = (e & 3) == 0 ? raw[e >> 2].x : (e & 3) == 1 ? raw[e >> 2].y : (e & 3) == 2 ? raw[e >> 2].z : raw[e >> 2].w;
+            v[e] = fminf(fmaxf(x * rsc, -65000.f), 65000.f);            // split2h's clamp
+        }
+        H2Op o;
+        lb_split16(v, 1.f, o);                              // v[0..7]: k-half 0 (lanes j), v[8..15]: k-half 1 (lanes j + 32)
+        char* d = buf + kseg * 2048 + lcol * 16;
+        *reinterpret_cast<f16x8*>(d) = o.h[0];
+        *reinterpret_cast<f16x8*>(d + 512) = o.h[1];
+        *reinterpret_cast<f16x8*>(d + 1024) = o.m[0];
+        *reinterpret_cast<f16x8*>(d + 1536) = o.m[1];
+    };
+    // ---- the stores: tile rows 8 it + lane / 8 of the tile whose result sits in this wave's patch ----
+    float* patch = reinterpret_cast<float*>(ldsw + 2 * kWsTile) + wave * 1024;
+    const int orows = a.out_rows_per_b ? a.out_rows_per_b : rows_out, orow0 = a.out_rows_per_b ? a.out_row0 : 0;
+    int sn[4], sb[4], sr[4];
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        sn[it] = t_lo * 32 + it * 8 + (lane >> 3);
+        sb[it] = sn[it] / rows_out;
+        sr[it] = sn[it] - sb[it] * rows_out;
+    }
+    float4 pv0, pv1, pv2, pv3;
+    auto patch_read = [&]() {
+        pv0 = *reinterpret_cast<const float4*>(patch_rows(patch, lane, 0));
+        pv1 = *reinterpret_cast<const float4*>(patch_rows(patch, lane, 1));
+        pv2 = *reinterpret_cast<const float4*>(patch_rows(patch, lane, 2));
+        pv3 = *reinterpret_cast<const float4*>(patch_rows(patch, lane, 3));
+    };
+    auto store_rows = [&](const float4 v, int& n, int& b, int& r, bool en) {
+        const long long no = (long long)b * orows + orow0 + r;
+        if (en && n < N) *reinterpret_cast<float4*>(og + no * ldo + ((lane & 7) << 2)) = v;
+        advance(n, b, r, en ? 32 : 0);
+    };
+    auto store_tile = [&](bool en) {                        // en (uniform): false = nothing to store yet, the state stays
+        store_rows(pv0, sn[0], sb[0], sr[0], en);
+        store_rows(pv1, sn[1], sb[1], sr[1], en);
+        store_rows(pv2, sn[2], sb[2], sr[2], en);
+        store_rows(pv3, sn[3], sb[3], sr[3], en);
+    };
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float inv = 1.f / (h2sw * h2sx);                  // exact: a power of two
+
+    // one 32-column step; LIVE: this wave has a layer (else it only fetches, splits and meets the barriers)
+    auto step = [&](auto live_tag, int t) {
+        constexpr bool LIVE = decltype(live_tag)::value;
+        char* nxt = ldsw + ((t - t_lo + 1) & 1) * kWsTile;
+        const char* rd = ldsw + ((t - t_lo) & 1) * kWsTile + lane * 16;
+        f16x8 fr[kWsAhead + 1][2];
+        auto ldB = [&](int kk, f16x8 (&f)[2]) {
+            f[0] = *reinterpret_cast<const f16x8*>(rd + kk * 2048);
+            f[1] = *reinterpret_cast<const f16x8*>(rd + kk * 2048 + 1024);
+        };
+        if (LIVE) {
+#pragma unroll
+            for (int kk = 0; kk < kWsAhead; ++kk) ldB(kk, fr[kk]);
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) {
+            if (LIVE) {
+                f16x8 (&f)[2] = fr[kk % (kWsAhead + 1)];
+                asm volatile("" ::"v"(f[0]));               // the wait for this k-step's fragments sits here, in front of the
+                asm volatile("" ::"v"(f[1]));               // requests for a later one (see k_colgemm_b3)
+                if (kk + kWsAhead < 16) ldB(kk + kWsAhead, fr[(kk + kWsAhead) % (kWsAhead + 1)]);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[kk][1], f[0], acc, 0, 0, 0);      // wm xh + wh xm + wh xh
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[kk][0], f[1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[kk][0], f[0], acc, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (kk == 5) {                                  // tile t + 1 (requested a step ago) into the other buffer
+                split_write(nxt);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (kk == 6 && LIVE) {                          // tile t - 1 leaves: out of the patch (a k-step ahead of the stores),
+                patch_read();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (kk == 7) {                                  // into memory; then the request for tile t + 2
+                if (LIVE) store_tile(t > t_lo);
+                load_raw();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (LIVE) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                *reinterpret_cast<float4*>(patch_tile(patch, j, h, q)) =
+                    make_float4(acc[4 * q] * inv, acc[4 * q + 1] * inv, acc[4 * q + 2] * inv, acc[4 * q + 3] * inv);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                       // tile t + 1 is complete; every wave is done with tile t
+    };
+
+    load_raw();
+    split_write(ldsw);
+    load_raw();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (live) {
+        for (int t = t_lo; t < t_hi; ++t) step(std::true_type{}, t);
+        patch_read();
+        store_tile(true);
+    } else {
+        for (int t = t_lo; t < t_hi; ++t) step(std::false_type{}, t);
+    }
+}
+
 int launch_colgemm_b3(Call& c, CGArgs& a, int mode, int nprob, hipStream_t s) {
     if (mode != 0 && mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6) return WN_ESHAPE;
     if (mode == 6 && !(c.fp16x2() && a.M == 256 && a.nsrc == 1 && a.xent_target && a.xent_loss && a.out[0] &&
@@ -908,6 +1114,31 @@ int launch_colgemm_b3(Call& c, CGArgs& a, int mode, int nprob, hipStream_t s) {
     // measured: HBM fetch 179 -> 131 MB, the call - 2 ... - 6 % stand-alone, the training step +- 0 (2.888 against 2.882 ms, same
     // box); without its stores it still took 180 of 225 us against 84 us of MFMA time: neither the writes nor the re-split bound
     // this contraction.  Not kept.  DESIGN.md, round 6.)
+    // Mode 2 with the WEIGHTS STATIONARY -- k_dz_ws: 32-row problems with K = 256 under the fp16 split (dz of the skip path).
+    // Bit-identical to k_colgemm_b3<2, 0, 3, 8>, which WN_EXEC_NO_PIPELINED_GEMM selects and every other shape keeps.
+    if (h2 && mode == 2 && nchunks == 8 && a.ldo == 32 && !a.accumulate && !c.flag(WN_EXEC_NO_PIPELINED_GEMM) &&
+        a.N < (1ll << 30) && a.rows_out_per_b >= 32 &&
+        (a.N / a.rows_out_per_b + 2) * (long long)(a.out_rows_per_b > a.rows_out_per_b ? a.out_rows_per_b : a.rows_out_per_b) < (1ll << 31)) {
+        int dev = 0;
+        WN_HIP(hipGetDevice(&dev));
+        static int capacity[64];                          // workgroups resident on the device; 0 = not asked yet (a benign race)
+        if (dev < 0 || dev >= 64) { wn::set_error("colgemm_b3: device index %d", dev); return WN_ESHAPE; }
+        if (!capacity[dev]) {
+            int n_cu = 0, per_cu = 0;
+            WN_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+            WN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dz_ws), hipFuncAttributeMaxDynamicSharedMemorySize, kWsLds));
+            WN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_dz_ws, 512, kWsLds));
+            capacity[dev] = n_cu * per_cu > 0 ? n_cu * per_cu : -1;
+        }
+        const int ng = cdiv(mtiles, 8), ntiles = cdiv(a.N, 32);
+        int nranges = capacity[dev] / ng;
+        if (nranges > ntiles) nranges = ntiles;
+        if (nranges >= 1) {
+            hipLaunchKernelGGL(k_dz_ws, dim3(ng * nranges), dim3(512), kWsLds, s, a, (const __bf16*)img, mtiles, ntiles, nranges);
+            WN_LAUNCH_CHECK();
+            return WN_OK;
+        }
+    }
     const bool mt8 = (one || h2) && mtiles >= 8;
     dim3 grid(cdiv(a.N, 128) * cdiv(mtiles, mt8 ? 8 : 4));
     if (mode == 6) {
