@@ -79,3 +79,52 @@ def stack_row_grads(p, w, x, rows, hop, phase, dout, dskip, t_off, dtype=torch.f
 
 state_dict = LR.state_dict
 rows_of = LR.rows_of
+colsum_in_kernel_order = LR.colsum_in_kernel_order
+
+
+def _fma32(w, d, p):
+    """(float32 fma(w, d, p), entries that are not certain) for float32 arrays, through float64.  w * d is exact in float64 (two
+    24-bit significands); the float64 sum is rounded to 53 bits and then to 24, which can differ from the single rounding of a
+    fused multiply-add only when the float64 sum sits exactly on a float32 tie (its low 29 significand bits are 1 << 28) and
+    was itself rounded.  TwoSum gives the float64 addition's error exactly: on such a tie the sum is nudged one float64 step
+    towards the true value before the second rounding, which then falls on the right side.  Below the float32 normal range
+    the tie lies elsewhere: those entries are reported, not trusted."""
+    prod, p64 = np.atleast_1d(np.float64(w) * np.float64(d)), np.atleast_1d(np.float64(p))
+    s = prod + p64
+    bb = s - prod
+    err = (prod - (s - bb)) + (p64 - bb)
+    tie = (s.view(np.uint64) & np.uint64((1 << 29) - 1)) == np.uint64(1 << 28)
+    fix = tie & (err != 0)
+    s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32), (np.abs(s) < 2.0 ** -126) & (s != 0)
+
+
+def colsum_lerp_in_kernel_order(a, f, hop, phase, tmin=0, t_chunk=32):
+    """(float32 (M,) sum, number of suspect roundings): what k_colsum_per_frame_lerp adds to row ``f`` of a clip's gradient block
+    from ``a`` (T, M), the clip's (da | dg) rows, in the documented order.  Two halves of 8 reduction lanes: the first takes
+    the rows t >= tmin of frame f with weight 1 - alpha_t (one float32 subtraction), the second those of frame f - 1 with weight
+    alpha_t, alpha_t = fl32(fl32(t - lo) / fl32(hop)) for a frame whose first position is lo.  Each segment is cut into chunks of
+    ``t_chunk`` rows from its first row; a chunk's rows go to four row lanes, each row as ONE fused multiply-add p = fma(w, d,
+    p), combined as (p0 + p1) + (p2 + p3); chunk y on lane y % 8 of its half in ascending order; the 16 partials added in index
+    order.  The count is of the float64-emulated multiply-adds ``_fma32`` could not vouch for: 0 means the sum is the kernel's,
+    bit for bit."""
+    a = np.asarray(a, np.float32)
+    T, M = a.shape
+    lanes = np.zeros((16, M), np.float32)
+    suspect = 0
+    lo_own = f * hop - phase
+    for half, lo in ((0, lo_own), (1, lo_own - hop)):
+        ta, tb = max(lo, tmin), min(lo + hop, T)
+        for y in range(max(0, (tb - ta + t_chunk - 1) // t_chunk)):
+            t0 = ta + y * t_chunk
+            p = np.zeros((4, M), np.float32)
+            for t in range(t0, min(tb, t0 + t_chunk)):
+                al = np.float32(t - lo) / np.float32(hop)
+                w = al if half else np.float32(1) - al
+                p[(t - t0) % 4], bad = _fma32(w, a[t], p[(t - t0) % 4])
+                suspect += int(bad.sum())
+            lanes[8 * half + y % 8] = lanes[8 * half + y % 8] + ((p[0] + p[1]) + (p[2] + p[3]))
+    tot = np.zeros((M,), np.float32)
+    for k in range(16):
+        tot = tot + lanes[k]
+    return tot, suspect

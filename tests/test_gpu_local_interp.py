@@ -148,6 +148,31 @@ def test_segments_longer_than_eight_chunks():
     _grad_rows_against_reference(st, x, block, "fp32", 0, hop=600, phase=0)
 
 
+def test_interpolated_gradient_rows_in_the_documented_order():
+    """test_segments_longer_than_eight_chunks's shape (B = 2, T = 1,300, hop 600, one 16 / 24-channel layer, generic path): a
+    reduction lane adds more than one chunk and the last frame is ragged.  Layer 0's rows -- the (da | dg) scratch the
+    workspace still holds when the call returns -- are bit-equal to the float32 sums formed on the host in the documented
+    order of k_colsum_per_frame_lerp (LI.colsum_lerp_in_kernel_order: halves of 8 lanes, chunks of 32 rows, weights 1 - alpha /
+    alpha, one fused multiply-add per row, the 16 partials in index order), added to the value the rows started from."""
+    over = dict(quantization_steps=256, causal_conv_channels=[16], residual_conv_channels=[24], residual_num_blocks=1,
+                softmax_conv_channels=[64, 256])
+    Bn, Tn, hop = 2, 1300, 600
+    st, x, block = _case(over, seed=9, hop=hop, phase=0, pad=2, Bn=Bn, Tn=Tn)
+    assert block.shape[1] == 4 and st.frames[2] == 50
+    grad, ws, _, _, _, _ = _grad_rows(st, x, block, "fp32", 0)
+    zoff = Bn * Tn * st.ncd
+    dab = to_np(ws[zoff:zoff + Bn * Tn * 48]).reshape(Bn, Tn, 48)
+    got = to_np(grad)
+    for b in range(Bn):
+        for f in range(4):
+            tot, suspect = LI.colsum_lerp_in_kernel_order(dab[b], f, hop, 0)
+            assert suspect == 0, (b, f)                    # (the host emulation vouches for every fused multiply-add)
+            want = np.float32(0.25) + tot
+            assert np.abs(want - 0.25).max() > 1e-3       # (every row receives something: the last one the ragged frame's alpha part)
+            assert np.array_equal(got[b, f, :48], want), (b, f, np.abs(got[b, f, :48] - want).max())
+    assert float((grad[:, :, 48:] - 0.25).abs().max()) == 0.0
+
+
 @pytest.mark.parametrize("prec,t1", [("fp32", 1), ("fp16x2", 1)])
 def test_a_hop_longer_than_the_clip(prec, t1):
     """hop 100, phase 40: hop > T, two frames (the border at t = 60) and three rows; the first segment lies partly below the

@@ -81,7 +81,7 @@ int layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, const f
         return mfma_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, d, Z, 0, s);
     if (c.wide_layer(Cr, Cd, fw) && (f_save || Cd <= Cr))
         return wide_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
-    return generic_layer_fwd(x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s, c.bias_stride, c.frames);
+    return generic_layer_fwd(c, x, Wf, bf, Wg, bg, Wp, bp, out, z, f_save, g_save, B, T, Cr, Cd, fw, d, Z, s);
 }
 
 int layer_bwd(Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg, const float* Wp,

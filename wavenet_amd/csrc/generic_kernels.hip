@@ -319,11 +319,69 @@ static int launch_colsum(const float* A, long long a_bs, int a_t0, int lda, int 
     return WN_OK;
 }
 
-// Per-clip column sums of both gates in one launch (WN_EXEC_BIAS_PER_CLIP): workgroup (x, b) owns 64 of the 2 Cd columns
-// [da | dg] of clip b and adds them in the order k_colsum + k_colsum_reduce use for ONE clip -- chunks of t_chunk rows, four
-// row lanes per chunk (rows t0 + k, t0 + k + 4, ...) combined as (p0 + p1) + (p2 + p3), chunk y on reduction lane y % 16 in
-// ascending order, the 16 lane sums in index order -- so row b is bit for bit what a B = 1 call of the shared-bias form adds
-// to its dbf / dbg.  No atomics, no scratch.  blockDim = (64 columns, 16 reduction lanes).
+// Bias-gradient rows (WN_EXEC_BIAS_PER_CLIP): column sums of both gates' (da | dg) in one launch, per clip, per (clip, frame),
+// or per (clip, frame) weighted for linear interpolation.  No atomics, no scratch.  blockDim = (64 columns, 16 reduction
+// lanes); a workgroup owns 64 of the 2 Cd columns [da | dg] of one output row.  THE summation order lives in the two
+// functions below; the three kernels only choose their rows.
+//
+// colsum_rows<LANES, W>: what reduction lane `lane` (0 .. LANES - 1) adds for rows [ta, tb) of a column (0 when !ok).  The rows are cut
+// into chunks of t_chunk rows from ta; a chunk goes to four row lanes (rows t0 + k, t0 + k + 4, ... on lane k) combined as
+// (p0 + p1) + (p2 + p3); the lane adds its chunks lane, lane + LANES, ... in ascending order.  W is a row's weight: kRowUnit (a
+// plain sum), or, for a frame whose first position is lo, with alpha_t = float(t - lo) / float(hop) (an IEEE division:
+// bias_frame_alpha's value), kRowOwn = 1 - alpha_t (one rounded subtraction) or kRowNext = alpha_t.  A weighted row enters as
+// ONE fused multiply-add, p = fma(w, d, p), spelled out like bias_lerp so that no contraction flag decides the bits.
+enum { kRowUnit = 0, kRowOwn = 1, kRowNext = 2 };
+template <int LANES, int W>
+__device__ __forceinline__ float colsum_rows(bool ok, const float* __restrict__ A, int lda, int ta, int tb, int t_chunk, int lane,
+                                             long long lo = 0, float hop = 1.f) {
+    auto add = [&](float p, int t) {
+        const float d = A[(long long)t * lda];
+        if (W == kRowUnit) return p + d;
+        const float al = __fdiv_rn((float)(int)(t - lo), hop);
+        return __fmaf_rn(W == kRowNext ? al : __fsub_rn(1.f, al), d, p);
+    };
+    const int nchunk = (tb - ta + t_chunk - 1) / t_chunk;      // (no row: no chunk)
+    float sum = 0.f;
+    if (ok)                                                    // (the column exists)
+        for (int y = lane; y < nchunk; y += LANES) {
+            const int t0 = ta + y * t_chunk, t1 = min(tb, t0 + t_chunk);
+            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+            int t = t0;
+            for (; t + 3 < t1; t += 4) {
+                p0 = add(p0, t); p1 = add(p1, t + 1);
+                p2 = add(p2, t + 2); p3 = add(p3, t + 3);
+            }
+            if (t < t1) p0 = add(p0, t);
+            if (t + 1 < t1) p1 = add(p1, t + 1);
+            if (t + 2 < t1) p2 = add(p2, t + 2);
+            sum += (p0 + p1) + (p2 + p3);
+        }
+    return sum;
+}
+// column blockIdx.x * 64 + threadIdx.x of clip b's [da | dg]: its first row, and the gate's gradient rows with the column there
+struct BiasColumn { bool ok; const float* A; float* out; int mm; };
+__device__ __forceinline__ BiasColumn bias_column(const float* __restrict__ da, const float* __restrict__ dg, int lda, int T,
+                                                  int Cd, float* __restrict__ dbf, float* __restrict__ dbg, int b) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    const bool gate = m >= Cd;
+    const int mm = gate ? m - Cd : m;
+    return BiasColumn{m < 2 * Cd, (gate ? dg : da) + (long long)b * T * lda + mm, gate ? dbg : dbf, mm};
+}
+// the workgroup's 16 lane sums added in index order, then += into the column's entry of the row `off` floats into the tables
+__device__ __forceinline__ void colsum_finish(float sum, const BiasColumn& col, long long off) {
+    __shared__ float red[16][64];
+    red[threadIdx.y][threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.y == 0 && col.ok) {
+        float tot = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
+        if (col.out) col.out[off + col.mm] += tot;
+    }
+}
+
+// Per clip: workgroup (x, b) adds rows tmin .. T - 1 of clip b, 16 lanes -- with t_chunk = 256 the order k_colsum +
+// k_colsum_reduce use for ONE clip, so row b is bit for bit what a B = 1 call of the shared-bias form adds to its dbf / dbg.
 // (B x 2 Cd / 64 workgroups: at config 2 that is 8 workgroups reading 33 MB per layer, and the launch is the largest single
 // part of what a conditioned step costs -- DESIGN "Global conditioning".  A form with 16 columns per workgroup and four
 // chunks in flight per lane was measured and was SLOWER; the next form to try splits a clip's chunks over workgroups and
@@ -331,198 +389,78 @@ static int launch_colsum(const float* A, long long a_bs, int a_t0, int lda, int 
 __global__ __launch_bounds__(1024) void k_colsum_per_clip(const float* __restrict__ da, const float* __restrict__ dg, int lda,
                                                           int T, int tmin, int Cd, float* __restrict__ dbf,
                                                           float* __restrict__ dbg, long long stride, int t_chunk) {
-    __shared__ float red[16][64];
-    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
     const int b = blockIdx.y;
-    const bool ok = m < 2 * Cd;
-    const bool gate = m >= Cd;
-    const int mm = gate ? m - Cd : m;
-    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
-    const int nchunk = (T - tmin + t_chunk - 1) / t_chunk;
-    float sum = 0.f;
-    if (ok)
-        for (int y = threadIdx.y; y < nchunk; y += 16) {
-            const int t0 = tmin + y * t_chunk, t1 = min(T, t0 + t_chunk);
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-            int t = t0;
-            for (; t + 3 < t1; t += 4) {
-                p0 += A[(long long)t * lda]; p1 += A[(long long)(t + 1) * lda];
-                p2 += A[(long long)(t + 2) * lda]; p3 += A[(long long)(t + 3) * lda];
-            }
-            if (t < t1) p0 += A[(long long)t * lda];
-            if (t + 1 < t1) p1 += A[(long long)(t + 1) * lda];
-            if (t + 2 < t1) p2 += A[(long long)(t + 2) * lda];
-            sum += (p0 + p1) + (p2 + p3);
-        }
-    red[threadIdx.y][threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.y == 0 && ok) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
-        float* out = gate ? dbg : dbf;
-        if (out) out[(long long)b * stride + mm] += tot;
-    }
+    const BiasColumn col = bias_column(da, dg, lda, T, Cd, dbf, dbg, b);
+    const float sum = colsum_rows<16, kRowUnit>(col.ok, col.A, lda, tmin, T, t_chunk, threadIdx.y);
+    colsum_finish(sum, col, (long long)b * stride);
 }
-int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
-                            long long stride, hipStream_t s) {
-    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
-    WN_CHECK_SHAPE(B <= 65535, "per-clip bias gradients: at most 65,535 clips per call");
-    int t_chunk = 256;                                      // launch_colsum's choice for one clip
-    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
-    hipLaunchKernelGGL(k_colsum_per_clip, dim3(cdiv(2 * Cd, 64), B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd, dbf, dbg,
-                       stride, t_chunk);
-    WN_LAUNCH_CHECK();
-    return WN_OK;
-}
-
-// Per-frame column sums of both gates in one launch (local conditioning): workgroup (x, f, b) owns 64 of the 2 Cd columns
-// [da | dg] of the segment of clip b that reads frame f -- rows max(tmin, f hop - phase) .. min(T, (f + 1) hop - phase) - 1 --
-// and adds its rows by k_colsum_per_clip's rule started at the segment's first row: chunks of t_chunk rows, four row lanes per
-// chunk combined as (p0 + p1) + (p2 + p3), chunk y on reduction lane y % 16 in ascending order, the 16 lane sums in index
-// order.  A segment that covers a whole clip therefore adds exactly what k_colsum_per_clip adds for that clip.  A segment
-// wholly below tmin has no rows: its workgroup leaves without touching the row.  No atomics, no scratch: B x frames x
-// 2 Cd / 64 independent workgroups (512 at config 2 with hop 256 against the per-clip form's 8).
+// Per frame (local conditioning): workgroup (x, f, b) adds the segment of clip b that reads frame f -- rows max(tmin, f hop -
+// phase) .. min(T, (f + 1) hop - phase) - 1 --, 16 lanes, started at the segment's first row.  A segment that covers a whole
+// clip therefore adds exactly what k_colsum_per_clip adds for that clip.  A segment wholly below tmin has no rows: its
+// workgroup leaves without touching the row.  B x frames x 2 Cd / 64 independent workgroups (512 at config 2 with hop 256
+// against the per-clip form's 8).
 __global__ __launch_bounds__(1024) void k_colsum_per_frame(const float* __restrict__ da, const float* __restrict__ dg, int lda,
                                                            int T, int tmin, int Cd, float* __restrict__ dbf,
                                                            float* __restrict__ dbg, long long stride, BiasFrames fr,
                                                            int t_chunk) {
-    __shared__ float red[16][64];
-    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
     const int f = blockIdx.y, b = blockIdx.z;
     const long long lo = (long long)f * fr.hop - frame_phase(fr, b), hi = lo + fr.hop;   // (the clip is blockIdx.z: one scalar load)
     const int ta = lo > tmin ? (int)lo : tmin, tb = hi < T ? (int)hi : T;
     if (tb <= ta) return;                                 // (uniform over the workgroup)
-    const bool ok = m < 2 * Cd;
-    const bool gate = m >= Cd;
-    const int mm = gate ? m - Cd : m;
-    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
-    const int nchunk = (tb - ta + t_chunk - 1) / t_chunk;
-    float sum = 0.f;
-    if (ok)
-        for (int y = threadIdx.y; y < nchunk; y += 16) {
-            const int t0 = ta + y * t_chunk, t1 = min(tb, t0 + t_chunk);
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-            int t = t0;
-            for (; t + 3 < t1; t += 4) {
-                p0 += A[(long long)t * lda]; p1 += A[(long long)(t + 1) * lda];
-                p2 += A[(long long)(t + 2) * lda]; p3 += A[(long long)(t + 3) * lda];
-            }
-            if (t < t1) p0 += A[(long long)t * lda];
-            if (t + 1 < t1) p1 += A[(long long)(t + 1) * lda];
-            if (t + 2 < t1) p2 += A[(long long)(t + 2) * lda];
-            sum += (p0 + p1) + (p2 + p3);
-        }
-    red[threadIdx.y][threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.y == 0 && ok) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
-        float* out = gate ? dbg : dbf;
-        if (out) out[(long long)b * stride + (long long)f * fr.stride + mm] += tot;
-    }
+    const BiasColumn col = bias_column(da, dg, lda, T, Cd, dbf, dbg, b);
+    const float sum = colsum_rows<16, kRowUnit>(col.ok, col.A, lda, ta, tb, t_chunk, threadIdx.y);
+    colsum_finish(sum, col, (long long)b * stride + (long long)f * fr.stride);
 }
-int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
-                             long long stride, BiasFrames fr, hipStream_t s) {
-    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
-    // (a table's values are not known here: the grid covers the n_max frames of phase hop - 1; a workgroup whose segment
-    // holds no row leaves without touching its row)
-    const int frames = (int)(((long long)T + (fr.tab ? fr.hop - 1 : fr.phase) + fr.hop - 1) / fr.hop);
-    WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
-    WN_CHECK_SHAPE(frames <= 65535, "per-frame bias gradients: at most 65,535 frames per clip and call");
-    int t_chunk = 256;                                      // generic_colsum_per_clip's choice, from the same rows
-    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
-    hipLaunchKernelGGL(k_colsum_per_frame, dim3(cdiv(2 * Cd, 64), frames, B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd, dbf,
-                       dbg, stride, fr, t_chunk);
-    WN_LAUNCH_CHECK();
-    return WN_OK;
-}
-// The weighted form for linear interpolation (BiasFrames.interp == 1): position t of frame j = (t + phase) / hop read
-// r[j] + alpha_t (r[j + 1] - r[j]), alpha_t = float((t + phase) % hop) / float(hop), so row f of a clip's gradient block -- f =
-// 0 .. frames, one row more than the per-frame form -- receives
-//     segment A  sum over the t >= tmin of frame f      of (1 - alpha_t) d[t]
-//   + segment B  sum over the t >= tmin of frame f - 1  of      alpha_t  d[t].
-// Workgroup (x, f, b) owns 64 of the 2 Cd columns [da | dg] of row (b, f) and adds both segments in a fixed order: each
-// segment is cut into chunks of t_chunk rows from its first row, four row lanes per chunk combined as (p0 + p1) + (p2 + p3);
-// reduction lanes 0 .. 7 belong to segment A and 8 .. 15 to segment B -- the two run side by side --, lane y of a half adding
-// its segment's chunks y, y + 8, ... in ascending order; the 16 partials are added in index order.  Chunks are 32 rows (the
-// per-frame form's 256 would leave a 256-sample frame to one lane): a frame of 256 rows keeps all 16 lanes busy.  A row whose
-// two segments hold no t >= tmin is left untouched.  No atomics, no scratch; B x (frames + 1) x 2 Cd / 64 independent
-// workgroups, each reading its two segments once (a (da | dg) row is read by two workgroups).
-__device__ __forceinline__ float colsum_weighted_segment(const float* __restrict__ A, int lda, int ta, int tb, int t_chunk,
-                                                         long long lo, float hop, bool next) {
-    // rows ta .. tb - 1 of a frame whose first position is lo; weight alpha (next) or 1 - alpha of the row's own position
-    auto w = [&](int t) {
-        const float al = __fdiv_rn((float)(int)(t - lo), hop);
-        return next ? al : 1.f - al;
-    };
-    const int nchunk = (tb - ta + t_chunk - 1) / t_chunk;
-    float sum = 0.f;
-    for (int y = threadIdx.y & 7; y < nchunk; y += 8) {
-        const int t0 = ta + y * t_chunk, t1 = min(tb, t0 + t_chunk);
-        float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-        int t = t0;
-        for (; t + 3 < t1; t += 4) {
-            p0 += w(t) * A[(long long)t * lda]; p1 += w(t + 1) * A[(long long)(t + 1) * lda];
-            p2 += w(t + 2) * A[(long long)(t + 2) * lda]; p3 += w(t + 3) * A[(long long)(t + 3) * lda];
-        }
-        if (t < t1) p0 += w(t) * A[(long long)t * lda];
-        if (t + 1 < t1) p1 += w(t + 1) * A[(long long)(t + 1) * lda];
-        if (t + 2 < t1) p2 += w(t + 2) * A[(long long)(t + 2) * lda];
-        sum += (p0 + p1) + (p2 + p3);
-    }
-    return sum;
-}
+// Linear interpolation (BiasFrames.interp == 1): position t of frame j = (t + phase) / hop read r[j] + alpha_t (r[j + 1] - r[j]),
+// so row f of a clip's gradient block -- f = 0 .. frames, one row more than the per-frame form -- receives
+//     segment A  sum over the t >= tmin of frame f      of (1 - alpha_t) d[t]        reduction lanes 0 .. 7
+//   + segment B  sum over the t >= tmin of frame f - 1  of      alpha_t  d[t]        reduction lanes 8 .. 15
+// The two segments run side by side, each cut into chunks from its own first row and added by its 8 lanes.  Chunks are 32 rows
+// (the per-frame form's 256 would leave a 256-sample frame to one lane): a frame of 256 rows keeps all 16 lanes busy.  A row
+// whose two segments hold no t >= tmin is left untouched.  B x (frames + 1) x 2 Cd / 64 independent workgroups, each reading
+// its two segments once (a (da | dg) row is read by two workgroups).
 __global__ __launch_bounds__(1024) void k_colsum_per_frame_lerp(const float* __restrict__ da, const float* __restrict__ dg,
                                                                 int lda, int T, int tmin, int Cd, float* __restrict__ dbf,
                                                                 float* __restrict__ dbg, long long stride, BiasFrames fr,
                                                                 int t_chunk) {
-    __shared__ float red[16][64];
-    const int m = blockIdx.x * 64 + threadIdx.x;          // column of [da | dg]
     const int f = blockIdx.y, b = blockIdx.z;
     const long long loA = (long long)f * fr.hop - frame_phase(fr, b), loB = loA - fr.hop;      // first positions of frames f and f - 1
     const int taA = loA > tmin ? (int)loA : tmin, tbA = loA + fr.hop < T ? (int)(loA + fr.hop) : T;
     const int taB = loB > tmin ? (int)loB : tmin, tbB = loA < T ? (int)loA : T;
     if (tbA <= taA && tbB <= taB) return;                 // (uniform over the workgroup)
-    const bool ok = m < 2 * Cd;
-    const bool gate = m >= Cd;
-    const int mm = gate ? m - Cd : m;
-    const float* A = (gate ? dg : da) + (long long)b * T * lda + mm;
-    float sum = 0.f;
-    if (ok) {                                             // (threadIdx.y >> 3 is uniform over a wave: a wave is one row of 64)
-        if (threadIdx.y < 8) { if (tbA > taA) sum = colsum_weighted_segment(A, lda, taA, tbA, t_chunk, loA, (float)fr.hop, false); }
-        else if (tbB > taB) sum = colsum_weighted_segment(A, lda, taB, tbB, t_chunk, loB, (float)fr.hop, true);
-    }
-    red[threadIdx.y][threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.y == 0 && ok) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k][threadIdx.x];
-        float* out = gate ? dbg : dbf;
-        if (out) out[(long long)b * stride + (long long)f * fr.stride + mm] += tot;
-    }
+    const BiasColumn col = bias_column(da, dg, lda, T, Cd, dbf, dbg, b);
+    const float sum = threadIdx.y < 8            // (threadIdx.y >> 3 is uniform over a wave: a wave is one row of 64)
+        ? colsum_rows<8, kRowOwn>(col.ok, col.A, lda, taA, tbA, t_chunk, threadIdx.y, loA, (float)fr.hop)
+        : colsum_rows<8, kRowNext>(col.ok, col.A, lda, taB, tbB, t_chunk, threadIdx.y - 8, loB, (float)fr.hop);
+    colsum_finish(sum, col, (long long)b * stride + (long long)f * fr.stride);
 }
-int generic_colsum_per_frame_lerp(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf,
-                                  float* dbg, long long stride, BiasFrames fr, hipStream_t s) {
-    if (T <= tmin || B <= 0 || (!dbf && !dbg)) return WN_OK;
-    const int rows = (int)(((long long)T + (fr.tab ? fr.hop - 1 : fr.phase) + fr.hop - 1) / fr.hop) + 1;   // (n_max + 1 with a table)
-    WN_CHECK_SHAPE(B <= 65535, "per-frame bias gradients: at most 65,535 clips per call");
-    WN_CHECK_SHAPE(rows <= 65535, "interpolated per-frame bias gradients: at most 65,534 frames per clip and call");
-    int t_chunk = 32;
-    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
-    hipLaunchKernelGGL(k_colsum_per_frame_lerp, dim3(cdiv(2 * Cd, 64), rows, B), dim3(64, 16), 0, s, da, dg, lda, T, tmin, Cd,
-                       dbf, dbg, stride, fr, t_chunk);
-    WN_LAUNCH_CHECK();
-    return WN_OK;
-}
+// what the layer backwards call: the kernel of c.bias_mode(dbf, dbg).  Chunks start at 256 rows (launch_colsum's choice for one
+// clip) or, interpolated, at 32, and double while a clip would have more than 2,048 of them.
 int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
                              float* dbf, float* dbg, hipStream_t s) {
-    if (c.frames.hop > 0 && c.frames.interp)
-        return generic_colsum_per_frame_lerp(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames, s);
-    if (c.frames.hop > 0) return generic_colsum_per_frame(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames, s);
-    return generic_colsum_per_clip(da, dg, lda, B, T, tmin, Cd, dbf, dbg, c.bias_stride, s);
+    const int mode = c.bias_mode(dbf, dbg);
+    if (T <= tmin || B <= 0 || mode == kCondNone) return WN_OK;
+    const bool clip = mode == kCondClip, lerp = mode == kCondLinear;
+    // (a table's values are not known here: the grid covers the rows of phase hop - 1; a workgroup whose segments hold no row
+    // leaves without touching its row)
+    const long long rows = clip ? 1 : c.frames.rows(T);
+    WN_CHECK_SHAPE(B <= 65535, clip ? "per-clip bias gradients: at most 65,535 clips per call"
+                                    : "per-frame bias gradients: at most 65,535 clips per call");
+    WN_CHECK_SHAPE(rows <= 65535, lerp ? "interpolated per-frame bias gradients: at most 65,534 frames per clip and call"
+                                       : "per-frame bias gradients: at most 65,535 frames per clip and call");
+    int t_chunk = lerp ? 32 : 256;
+    while ((T - tmin + t_chunk - 1) / t_chunk > 2048) t_chunk *= 2;
+    const dim3 grid(cdiv(2 * Cd, 64), clip ? B : (unsigned)rows, clip ? 1 : B), block(64, 16);
+    if (clip)
+        hipLaunchKernelGGL(k_colsum_per_clip, grid, block, 0, s, da, dg, lda, T, tmin, Cd, dbf, dbg, c.bias_stride, t_chunk);
+    else if (lerp)
+        hipLaunchKernelGGL(k_colsum_per_frame_lerp, grid, block, 0, s, da, dg, lda, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames,
+                           t_chunk);
+    else
+        hipLaunchKernelGGL(k_colsum_per_frame, grid, block, 0, s, da, dg, lda, T, tmin, Cd, dbf, dbg, c.bias_stride, c.frames,
+                           t_chunk);
+    WN_LAUNCH_CHECK();
+    return WN_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1247,16 +1185,16 @@ int generic_conv_bwd(const float* x, const float* W, const float* dout, float* d
     return WN_OK;
 }
 
-int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
+int generic_layer_fwd(const Call& c, const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride, BiasFrames frames) {
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s) {
     long long tot = (long long)B * T * Cd;
-    if (frames.hop > 0 && frames.interp)
+    if (c.bias_mode(bf, bg) == kCondLinear)
         hipLaunchKernelGGL(k_gate_fwd<true>, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
-                           gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
+                           gs, B, T, Cr, Cd, fw, d, Z, c.bias_stride, c.frames);
     else
         hipLaunchKernelGGL(k_gate_fwd<false>, dim3(cdiv(tot, kThreads)), dim3(kThreads), 0, s, x, Wf, bf, Wg, bg, z, fs,
-                           gs, B, T, Cr, Cd, fw, d, Z, bias_stride, frames);
+                           gs, B, T, Cr, Cd, fw, d, Z, c.bias_stride, c.frames);
     WN_LAUNCH_CHECK();
     long long N = (long long)B * T;
     hipLaunchKernelGGL(k_proj_res_fwd, dim3(cdiv(N * Cr, kThreads)), dim3(kThreads), 0, s, x, z, Wp, bp, out,

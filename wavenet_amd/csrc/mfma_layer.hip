@@ -35,6 +35,39 @@ static constexpr int kPRow = 33;     // LDS row stride of Wp[i][.]
 // FRAME (with HAS_BIAS; local conditioning): bf / bg hold a row per (clip, frame) and the accumulator seed is per lane -- a
 // lane owns one column, so it is the row of the lane's own frame.  A compile-time mode: without it the kernel is what it was.
 // FRAME == 2 (linear interpolation, WnStackDesc.bias_interp): the seed is bias_lerp of the rows of frames j and j + 1.
+// gate_seed: THE accumulator seed of both fp32 kernels, for the lane (., h) whose column is position t (clamped into the clip)
+// of clip b -- register r is channel ch_of(r, h).  A tile belongs to one clip: b and the phase are uniform over the wave.
+// (returned by value: filled through references, the looping kernel's unbiased forms compiled to other code than before)
+struct GateSeed { f32x16 aa, ag; };
+template <bool HAS_BIAS, int FRAME>
+__device__ __forceinline__ GateSeed gate_seed(const float* bf, const float* bg, int b, int t, int h, long long bstride,
+                                              const BiasFrames& fr) {
+    f32x16 aa, ag;
+    if (HAS_BIAS && FRAME == 2) {             // interpolated between the rows of the lane's frame and the next one
+        const int ph = frame_phase(fr, b);
+        const long long brow = b * bstride + bias_frame_off(fr, ph, t);
+        const float al = bias_frame_alpha(fr, ph, t);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+            ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
+        }
+    } else if (HAS_BIAS && FRAME) {           // the row of the lane's own frame
+        const long long brow = b * bstride + bias_frame_off(fr, frame_phase(fr, b), t);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
+            ag[r] = bg ? bg[brow + ch_of(r, h)] : 0.f;
+        }
+    } else {                                  // the clip's row (bstride == 0: the shared one), or nothing
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;
+            ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
+        }
+    }
+    return GateSeed{aa, ag};
+}
 template <int SAVE, bool HAS_BIAS, int FRAME = 0>
 __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
     const float* __restrict__ x, const float* __restrict__ Wf, const float* __restrict__ bf,
@@ -139,31 +172,8 @@ __global__ __launch_bounds__(256, 2) void k_layer_fwd_mfma32(
         // the next tile's columns are fetched while this tile computes
         const bool more = tile + stride < last;
         if (more) load_tile(tile + stride, xcn, xon);
-        f32x16 aa, ag;
-        if (HAS_BIAS && FRAME == 2) {  // ... interpolated between the rows of the lane's frame and the next one
-            const int tb = valid ? t : T - 1;
-            const int ph = frame_phase(fr, b);             // a tile belongs to one clip: one scalar load
-            const long long brow = b * bstride + bias_frame_off(fr, ph, tb);
-            const float al = bias_frame_alpha(fr, ph, tb);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
-                ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
-            }
-        } else if (HAS_BIAS && FRAME) {       // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
-            const long long brow = b * bstride + bias_frame_off(fr, frame_phase(fr, b), valid ? t : T - 1);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
-                ag[r] = bg ? bg[brow + ch_of(r, h)] : 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;      // a tile belongs to one clip
-                ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
-            }
-        }
+        const GateSeed seed = gate_seed<HAS_BIAS, FRAME>(bf, bg, b, valid ? t : T - 1, h, bstride, fr);
+        f32x16 aa = seed.aa, ag = seed.ag;
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
             aa = __builtin_amdgcn_mfma_f32_32x32x2f32(wf0[s], xo[s], aa, 0, 0, 0);
@@ -276,30 +286,8 @@ __global__ __launch_bounds__(256, 4) void k_layer_fwd_mfma32_t1(
     }
     __syncthreads();
 
-    f32x16 aa, ag;
-    if (HAS_BIAS && FRAME == 2) {      // ... interpolated between the rows of the lane's frame and the next one
-        const int ph = frame_phase(fr, b);                 // a tile belongs to one clip: one scalar load
-        const long long brow = b * bstride + bias_frame_off(fr, ph, tc);
-        const float al = bias_frame_alpha(fr, ph, tc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            aa[r] = bf ? bias_lerp(bf[brow + ch_of(r, h)], bf[brow + fr.stride + ch_of(r, h)], al) : 0.f;
-            ag[r] = bg ? bias_lerp(bg[brow + ch_of(r, h)], bg[brow + fr.stride + ch_of(r, h)], al) : 0.f;
-        }
-    } else if (HAS_BIAS && FRAME) {           // per-frame rows: a lane owns one column, the seed is the row of the lane's own frame
-        const long long brow = b * bstride + bias_frame_off(fr, frame_phase(fr, b), tc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            aa[r] = bf ? bf[brow + ch_of(r, h)] : 0.f;
-            ag[r] = bg ? bg[brow + ch_of(r, h)] : 0.f;
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            aa[r] = (HAS_BIAS && bf) ? bf[b * bstride + ch_of(r, h)] : 0.f;          // a tile belongs to one clip
-            ag[r] = (HAS_BIAS && bg) ? bg[b * bstride + ch_of(r, h)] : 0.f;
-        }
-    }
+    const GateSeed seed = gate_seed<HAS_BIAS, FRAME>(bf, bg, b, tc, h, bstride, fr);
+    f32x16 aa = seed.aa, ag = seed.ag;
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
         // W[i = j][c = ch(s,h)][k = 0,1]: one 8-byte LDS read gives both taps
@@ -365,7 +353,7 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // 8 (r >> 2) + 4 h + (r & 3): the 16 values a lane needs per gate are four float4.  They are requested in front of the MFMA
 // block, land under it, and are added in fp32 AFTER the accumulator is rescaled -- fmaf(aa[r], uc, bias) -- so they never
 // pass through the tile's power-of-two scale or an fp16 split.  For t < Z neither the convolution nor the bias counts.
-// COND is one of three compile-time modes: kCondNone, kCondClip (the above) and kCondFrame (local conditioning: clip b's row
+// COND is Call::bias_mode's value (wn_kernels.hpp) as a compile-time mode: kCondNone, kCondClip (the above) and kCondFrame (local conditioning: clip b's row
 // becomes a block of rows fr.stride floats apart and a lane, which owns ONE time step, reads the row of its own frame
 // (tc + phase) / fr.hop (phase: frame_phase, the call's or the clip's own) -- the same eight float4 requests; lanes of one frame read one address, so a wave fetches one row
 // per frame it spans.  The frame index is one plain 32-bit division per lane: a reciprocal multiply was not tried, the
@@ -374,7 +362,6 @@ __global__ __launch_bounds__(256) void k_layer_pack_h2(PackH2Args a, char* __res
 // r[j] + alpha (r[j + 1] - r[j]) in fp32 (bias_lerp) in front of the MFMA block, so that no more registers than kCondFrame's
 // stay live under it (row j + 1 is requested behind the weight image's barrier: requested with row j it spilled 92 bytes a
 // lane); the interpolated value is added where the per-frame one is: behind the rescale.
-enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2, kCondLinear = 3 };
 // TAB (with kCondFrame / kCondLinear): the phase is the clip's own, read from BiasFrames.tab (WnStackDesc.bias_phase_tab) -- a
 // compile-time mode, so the instantiations without a table are the code they were (decided at run time, the pointer moved
 // kCondLinear's register count: 118 -> 122 with tanh saved).
@@ -769,45 +756,41 @@ bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live) {
     const long long nt = (long long)B * ((T + 31) / 32 - tile_lo);
     return c.fwd_t1_min_blocks > 0 && nt > 0 && (nt + 3) / 4 >= c.fwd_t1_min_blocks && nt < (1ll << 31);
 }
-int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
-                      int d, int Z, int t_live, hipStream_t s, const float* bf, const float* bg, long long bias_stride,
-                      BiasFrames frames) {
+int mfma_layer_fwd_h2(const Call& c, const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B,
+                      int T, int d, int Z, int t_live, hipStream_t s, const float* bf, const float* bg) {
     const int tile_lo = t_live > 0 ? t_live / 32 : 0;
     const int tiles_per_b = (T + 31) / 32 - tile_lo;
     const int ntiles = B * tiles_per_b;
     const int blocks = (ntiles + 3) / 4;
     const char* im = reinterpret_cast<const char*>(img) + (size_t)l * kH2ImgStride;
-    const bool cond = bf != nullptr;
-    if (cond)
-        WN_CHECK_ARG(bg && bias_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(bf) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(bg) & 15) == 0 && (frames.hop == 0 || frames.stride % 4 == 0),
+    const int mode = c.bias_mode(bf, bg);
+    const bool framed = mode == kCondFrame || mode == kCondLinear;
+    if (mode != kCondNone)
+        WN_CHECK_ARG(bf && bg && c.bias_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(bf) & 15) == 0 &&
+                         (reinterpret_cast<uintptr_t>(bg) & 15) == 0 && (!framed || c.frames.stride % 4 == 0),
                      "fp16 x 2 layer forward with per-clip bias rows: the rows must be 16-byte aligned and their stride a "
-                     "multiple of 4 floats (stride %lld, frame stride %lld)", bias_stride, frames.hop ? frames.stride : 0ll);
-    const int mode = !cond ? kCondNone : frames.hop > 0 ? (frames.interp ? kCondLinear : kCondFrame) : kCondClip;
-#define FWDH_LAUNCH(SAVE, COND)                                                                                            \
-    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
-                       tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
-#define FWDH_LAUNCH_TAB(SAVE, COND)                                                                                        \
-    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND, true>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, \
-                       Z, tile_lo, tiles_per_b, ntiles, bf, bg, bias_stride, frames)
-#define FWDH_MODES(SAVE)                                        \
-    do {                                                        \
-        if (mode == kCondFrame && frames.tab) FWDH_LAUNCH_TAB(SAVE, kCondFrame);  \
-        else if (mode == kCondLinear && frames.tab) FWDH_LAUNCH_TAB(SAVE, kCondLinear);  \
-        else if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame);  \
-        else if (mode == kCondClip) FWDH_LAUNCH(SAVE, kCondClip); \
-        else if (mode == kCondNone) FWDH_LAUNCH(SAVE, kCondNone); \
-        else FWDH_LAUNCH(SAVE, kCondLinear);                    \
-    } while (0)
+                     "multiple of 4 floats (stride %lld, frame stride %lld)", c.bias_stride, framed ? c.frames.stride : 0ll);
     // (sigmoid-only saving, SAVE = 2, belongs to stacks whose backward recovers tanh: a stack with bias rows is never one, and
     // wn_stack_fwd refuses the combination; the per-clip form is kept as it was, a per-frame one is not instantiated)
+    if (gs && !fs && framed) { wn::set_error("fp16 x 2 layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+#define FWDH_LAUNCH(SAVE, COND, TAB)                                                                                       \
+    hipLaunchKernelGGL((k_layer_fwd_h2_t1<SAVE, COND, TAB>), dim3(blocks), dim3(256), 0, s, x, im, out, z, fs, gs, B, T, d, Z, \
+                       tile_lo, tiles_per_b, ntiles, bf, bg, c.bias_stride, c.frames)
+#define FWDH_MODES(SAVE)                                                                \
+    do {                                                                                \
+        if (framed && c.phase_from_table()) {                                           \
+            if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame, true);                \
+            else FWDH_LAUNCH(SAVE, kCondLinear, true);                                  \
+        } else if (mode == kCondFrame) FWDH_LAUNCH(SAVE, kCondFrame, false);            \
+        else if (mode == kCondLinear) FWDH_LAUNCH(SAVE, kCondLinear, false);            \
+        else if (mode == kCondClip) FWDH_LAUNCH(SAVE, kCondClip, false);                \
+        else FWDH_LAUNCH(SAVE, kCondNone, false);                                       \
+    } while (0)
     if (fs) FWDH_MODES(1);
-    else if (gs && (mode == kCondFrame || mode == kCondLinear)) { wn::set_error("fp16 x 2 layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
-    else if (gs && mode == kCondClip) FWDH_LAUNCH(2, kCondClip);
-    else if (gs) FWDH_LAUNCH(2, kCondNone);
+    else if (gs && mode == kCondClip) FWDH_LAUNCH(2, kCondClip, false);
+    else if (gs) FWDH_LAUNCH(2, kCondNone, false);
     else FWDH_MODES(0);
 #undef FWDH_MODES
-#undef FWDH_LAUNCH_TAB
 #undef FWDH_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -831,56 +814,35 @@ int mfma_layer_fwd(const Call& c, const float* x, const float* Wf, const float* 
     const bool hb = bf || bg || bp;
     // enough workgroups to give every CU two to four of them (8-16 waves): one tile per wave; otherwise the looping kernel.
     // WnExec.fwd_t1_min_blocks overrides the threshold (1 = always, used by the parity tests; < 0 = never).
-    const int t1_min = c.fwd_t1_min_blocks;
-    if (t1_min > 0 && blocks >= t1_min) {
-#define FWD1_LAUNCH(SAVE, BIAS)                                                                              \
-    hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
-        // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
-        const bool frame = hb && c.frames.hop > 0;
-        if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
-        const bool lerp = frame && c.frames.interp != 0;          // linear interpolation between frames: FRAME == 2
-#define FWDF_LAUNCH(SAVE, MODE)                                                                                        \
-    hipLaunchKernelGGL((k_layer_fwd_mfma32_t1<SAVE, true, MODE>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs, \
+    const bool t1 = c.fwd_t1_min_blocks > 0 && blocks >= c.fwd_t1_min_blocks;
+    if (!t1 && blocks > 512) blocks = 512;   // 256 CUs x 2 resident workgroups; waves stride over tiles
+    // per-frame rows (always with biases, never with sigmoid-only saving): the FRAME instantiations, 2 = interpolated
+    const int mode = c.bias_mode(bf, bg);
+    const bool framed = mode == kCondFrame || mode == kCondLinear;
+    if (framed && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
+    // the ladder over (save form, mode), for either kernel family
+#define FWD_LAUNCH(KERNEL, SAVE, BIAS, FRAME)                                                                              \
+    hipLaunchKernelGGL((KERNEL<SAVE, BIAS, FRAME>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs, \
                        B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
-        if (frame && !lerp && fs) FWDF_LAUNCH(1, 1);
-        else if (frame && !lerp) FWDF_LAUNCH(0, 1);
-        else if (lerp && fs) FWDF_LAUNCH(1, 2);
-        else if (lerp) FWDF_LAUNCH(0, 2);
-        else if (fs && hb) FWD1_LAUNCH(1, true);
-        else if (fs) FWD1_LAUNCH(1, false);
-        else if (gs && hb) FWD1_LAUNCH(2, true);
-        else if (gs) FWD1_LAUNCH(2, false);
-        else if (hb) FWD1_LAUNCH(0, true);
-        else FWD1_LAUNCH(0, false);
-#undef FWD1_LAUNCH
-#undef FWDF_LAUNCH
-        WN_LAUNCH_CHECK();
-        return WN_OK;
-    }
-    if (blocks > 512) blocks = 512;          // 256 CUs x 2 resident workgroups; waves stride over tiles
-#define FWD_LAUNCH(SAVE, BIAS)                                                                               \
-    hipLaunchKernelGGL((k_layer_fwd_mfma32<SAVE, BIAS>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, \
-                       out, z, fs, gs, B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
-    // per-frame rows (c.frames.hop > 0; always with biases, never with sigmoid-only saving): the FRAME instantiations
-    const bool frame = hb && c.frames.hop > 0;
-    if (frame && gs && !fs) { wn::set_error("fused layer forward: per-frame bias rows with sigmoid-only saving"); return WN_EARG; }
-    const bool lerp = frame && c.frames.interp != 0;          // linear interpolation between frames: FRAME == 2
-#define FWDF_LAUNCH(SAVE, MODE)                                                                                        \
-    hipLaunchKernelGGL((k_layer_fwd_mfma32<SAVE, true, MODE>), dim3(blocks), dim3(256), 0, s, x, Wf, bf, Wg, bg, Wp, bp, out, z, fs, gs, \
-                       B, T, d, Z, tile_lo, tiles_per_b, ntiles, c.bias_stride, c.frames)
-    if (frame && !lerp && fs) FWDF_LAUNCH(1, 1);
-    else if (frame && !lerp) FWDF_LAUNCH(0, 1);
-    else if (lerp && fs) FWDF_LAUNCH(1, 2);
-    else if (lerp) FWDF_LAUNCH(0, 2);
-    else if (fs && hb) FWD_LAUNCH(1, true);
-    else if (fs) FWD_LAUNCH(1, false);
-    else if (gs && hb) FWD_LAUNCH(2, true);
-    else if (gs) FWD_LAUNCH(2, false);
-    else if (hb) FWD_LAUNCH(0, true);
-    else FWD_LAUNCH(0, false);
+#define FWD_MODES(KERNEL, SAVE)                                          \
+    do {                                                                 \
+        if (mode == kCondFrame) FWD_LAUNCH(KERNEL, SAVE, true, 1);       \
+        else if (mode == kCondLinear) FWD_LAUNCH(KERNEL, SAVE, true, 2); \
+        else if (hb) FWD_LAUNCH(KERNEL, SAVE, true, 0);                  \
+        else FWD_LAUNCH(KERNEL, SAVE, false, 0);                         \
+    } while (0)
+#define FWD_SAVES(KERNEL)                                   \
+    do {                                                    \
+        if (fs) FWD_MODES(KERNEL, 1);                       \
+        else if (gs && hb) FWD_LAUNCH(KERNEL, 2, true, 0);  \
+        else if (gs) FWD_LAUNCH(KERNEL, 2, false, 0);       \
+        else FWD_MODES(KERNEL, 0);                          \
+    } while (0)
+    if (t1) FWD_SAVES(k_layer_fwd_mfma32_t1);
+    else FWD_SAVES(k_layer_fwd_mfma32);
+#undef FWD_SAVES
+#undef FWD_MODES
 #undef FWD_LAUNCH
-#undef FWDF_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
 }

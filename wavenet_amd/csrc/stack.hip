@@ -71,24 +71,18 @@ static int take_bias_frames(const char* fn, const WnStackDesc* d, const WnExec* 
         WN_CHECK_ARG(d->bias_frame_stride >= d->cd[l], "%s: WnStackDesc.bias_frame_stride = %d below cd = %d (layer %d)", fn,
                      d->bias_frame_stride, d->cd[l], l);
     // (the kernels form t + phase in 32 bits); the host cannot see a table's values: everything is sized for phase hop - 1
-    const int worst = tab ? d->bias_hop - 1 : d->bias_phase;
-    if (tab)
-        WN_CHECK_ARG((long long)T + worst <= 2147483647ll, "%s: T + WnStackDesc.bias_hop - 1 = %lld does not fit 32 bits (a "
-                     "bias_phase_tab entry may be bias_hop - 1)", fn, (long long)T + worst);
-    else
-        WN_CHECK_ARG((long long)T + worst <= 2147483647ll, "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn,
-                     (long long)T + worst);
+    const BiasFrames fr{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride, d->bias_interp, tab};
+    const long long last = (long long)T + fr.worst_phase();
+    WN_CHECK_ARG(last <= 2147483647ll,
+                 tab ? "%s: T + WnStackDesc.bias_hop - 1 = %lld does not fit 32 bits (a bias_phase_tab entry may be bias_hop - 1)"
+                     : "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn, last);
     // linear interpolation reads row j + 1 at the last position too: one row more, and never a clamp
-    const long long frames = ((long long)T + worst + d->bias_hop - 1) / d->bias_hop + (d->bias_interp ? 1 : 0);
-    if (tab)
-        WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
-                     "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d (WnStackDesc.bias_phase_tab: "
-                     "sized for the worst phase, bias_hop - 1)", fn, ex->reserved, frames,
-                     d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride);
+    const long long frames = fr.rows(T);
     WN_CHECK_ARG((long long)ex->reserved >= frames * d->bias_frame_stride,
-                 "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d", fn, ex->reserved,
-                 frames, d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride);
-    c.frames = BiasFrames{d->bias_hop, d->bias_phase, (long long)d->bias_frame_stride, d->bias_interp, tab};
+                 "%s: the clip stride (WnExec.reserved = %d) is below %lld %s x bias_frame_stride = %d%s", fn, ex->reserved,
+                 frames, d->bias_interp ? "rows (frames + 1, linear interpolation)" : "frames", d->bias_frame_stride,
+                 tab ? " (WnStackDesc.bias_phase_tab: sized for the worst phase, bias_hop - 1)" : "");
+    c.frames = fr;
     return WN_OK;
 }
 }  // namespace wn
@@ -147,11 +141,7 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
     if (window_only && skip && t_off > 0) {
         // the same condition under which wn_stack_bwd takes the chained path (which honours these ranges): fused
         // layers without conv / projection biases
-        bool fast = true;
-        for (int l = 0; l < L && fast; ++l)
-            fast = c.layer_fast_path(d->Cr, d->cd[l], d->fw) && !(d->bf && d->bf[l]) && !(d->bg && d->bg[l]) &&
-                   !(d->bp && d->bp[l]);
-        if (fast) {
+        if (chain_capable(c, d)) {
             live[L - 1] = (t_off / 32) * 32;
             for (int l = L - 2; l >= 0; --l) {
                 int v = live[l + 1] - (d->fw - 1) * d->dilation[l + 1];
@@ -225,9 +215,9 @@ int wn_stack_fwd(const WnStackDesc* d, const float* x, float* xs, float* z, floa
             }
             if (h2img && mfma_layer_fwd_h2_ok(c, B, T, live[l])) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
-                rc = mfma_layer_fwd_h2(in, h2img, l, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr, B, T,
+                rc = mfma_layer_fwd_h2(c, in, h2img, l, out, z + zoff, f ? f + zoff : nullptr, g ? g + zoff : nullptr, B, T,
                                        d->dilation[l], Z, live[l], as_stream(stream), per_clip ? d->bf[l] : nullptr,
-                                       per_clip ? d->bg[l] : nullptr, c.bias_stride, c.frames);
+                                       per_clip ? d->bg[l] : nullptr);
             } else if (live[l] > 0 || g_only) {
                 wn::ProfScope prof__("wn_layer_fwd", stream);
                 rc = mfma_layer_fwd(c, in, d->Wf[l], d->bf ? d->bf[l] : nullptr, d->Wg[l], d->bg ? d->bg[l] : nullptr,

@@ -132,12 +132,14 @@ int wide_layer_fwd(Call& c, const float* x, const float* Wf, const float* bf, co
     rc = conv_gemm(c, x, Wg, per_clip ? nullptr : bg, gbuf, B, T, Cr, Cd, fw, d, s);
     if (rc) return rc;
     const long long n4 = (long long)B * T * Cd / 4;
-    if (per_clip && c.frames.hop > 0 && c.frames.interp)
-        hipLaunchKernelGGL(k_wide_gate<true>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z, bf, bg,
+    const float* rf = per_clip ? bf : nullptr;   // (shared rows went into the GEMMs)
+    const float* rg = per_clip ? bg : nullptr;
+    if (c.bias_mode(rf, rg) == kCondLinear)
+        hipLaunchKernelGGL(k_wide_gate<true>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z, rf, rg,
                            c.bias_stride, c.frames);
     else
-        hipLaunchKernelGGL(k_wide_gate<false>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z,
-                           per_clip ? bf : nullptr, per_clip ? bg : nullptr, c.bias_stride, c.frames);
+        hipLaunchKernelGGL(k_wide_gate<false>, dim3(cdiv(n4, 256)), dim3(256), 0, s, abuf, gbuf, z, fs, gs, n4, T, Cd, Z, rf, rg,
+                           c.bias_stride, c.frames);
     WN_LAUNCH_CHECK();
     CGArgs a{};
     base_args(a, B, T);

@@ -16,7 +16,18 @@ int check_bias_rows(const char* fn, const WnExec* ex, int Cd, const void* row_f,
 // rounded fp32 operations, so equal neighbours (and alpha == 0) give r[j] exactly; a block holds one row more than the frames
 // the call covers.  interp == 0: the row of the frame, as before.
 // tab != NULL (WnStackDesc.bias_phase_tab): a phase per clip in device memory, tab[b] for clip b; `phase` is then 0 and unused.
-struct BiasFrames { int hop, phase; long long stride; int interp; const int* tab; };
+struct BiasFrames {
+    int hop, phase; long long stride; int interp; const int* tab;
+    // host side, hop > 0.  The largest phase a clip can have: a table's values are not known on the host, so with one
+    // everything is sized for hop - 1
+    int worst_phase() const { return tab ? hop - 1 : phase; }
+    // rows of a clip's block that a call of T positions covers: its frames at the worst phase, one more with interpolation
+    long long rows(int T) const { return ((long long)T + worst_phase() + hop - 1) / hop + (interp ? 1 : 0); }
+};
+// How a layer's gate bias rows (bf, bg) are addressed -- Call::bias_mode, THE place that derives it; every launcher maps the
+// value to its own kernel's template arguments.  kCondClip: one row, shared (Call.bias_stride == 0) or per clip;
+// kCondFrame: a row per (clip, frame); kCondLinear: interpolated between the frame's row and the next.
+enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2, kCondLinear = 3 };
 // THE phase of clip b -- everything that needs one asks here.  Without a table it is the call's one value.  With one, the
 // value read is reduced into [0, hop): callers pass values inside that range, the reduction is a fence that keeps a garbage
 // value from taking an access outside the clip's block (the geometry is sized for phase hop - 1), not a feature.  Where b is
@@ -56,6 +67,11 @@ struct Call {
     static constexpr size_t kTail = 256;
     bool flag(unsigned f) const { return (flags & f) != 0; }
     bool bias_per_clip() const { return flag(WN_EXEC_BIAS_PER_CLIP); }
+    int bias_mode(const float* bf, const float* bg) const {      // kCond*, for a layer whose gate bias rows are (bf, bg)
+        if (!bf && !bg) return kCondNone;
+        return frames.hop <= 0 ? kCondClip : frames.interp ? kCondLinear : kCondFrame;
+    }
+    bool phase_from_table() const { return frames.tab != nullptr; }   // (kCondFrame / kCondLinear) a phase per clip, read on the device
     bool generic() const { return flag(WN_EXEC_FORCE_GENERIC); }
     bool split_b3() const { return precision != WN_GEMM_FP32; }   // the bf16-split GEMM kernels (every precision but fp32)
     bool one_term() const { return precision == WN_GEMM_BF16; }
@@ -102,10 +118,9 @@ int generic_conv_fwd(const float*, const float*, const float*, float*, int, int,
                      hipStream_t);
 int generic_conv_bwd(const float*, const float*, const float*, float*, float*, float*, int, int, int, int, int,
                      int, int, hipStream_t);
-int generic_layer_fwd(const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
+int generic_layer_fwd(const Call& c, const float* x, const float* Wf, const float* bf, const float* Wg, const float* bg,
                       const float* Wp, const float* bp, float* out, float* z, float* fs, float* gs, int B,
-                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s, long long bias_stride = 0,
-                      BiasFrames frames = {0, 0, 0, 0, nullptr});
+                      int T, int Cr, int Cd, int fw, int d, int Z, hipStream_t s);
 int generic_layer_bwd(const Call& c, const float* x, const float* f, const float* g, const float* Wf, const float* Wg,
                       const float* Wp, const float* dout, const float* dzs, float* dx, float* dWf, float* dbf,
                       float* dWg, float* dbg, float* dWp, float* dbp, float* dab, int B, int T, int Cr, int Cd,
@@ -163,10 +178,9 @@ size_t mfma_layer_h2_image_bytes(int L);
 int mfma_layer_pack_h2(int L, const float* const* Wf, const float* const* Wg, const float* const* Wp, void* img,
                        hipStream_t s);
 bool mfma_layer_fwd_h2_ok(const Call& c, int B, int T, int t_live);
-// bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, bias_stride % 4 == 0), the COND kernels
-int mfma_layer_fwd_h2(const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B, int T,
-                      int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr,
-                      long long bias_stride = 0, BiasFrames frames = {0, 0, 0, 0, nullptr});
+// bf / bg != NULL: per-clip bias rows (WN_EXEC_BIAS_PER_CLIP; 16-byte aligned, c.bias_stride % 4 == 0), the COND kernels
+int mfma_layer_fwd_h2(const Call& c, const float* x, const void* img, int l, float* out, float* z, float* fs, float* gs, int B,
+                      int T, int d, int Z, int t_live, hipStream_t s, const float* bf = nullptr, const float* bg = nullptr);
 int mfma_layer_fwd_group_len(const int* dil, int l0, int L);   // layers from l0 on that one group launch can chain
 int mfma_layer_fwd_h2_group(const float* x, const void* img, int l0, int nl, float* const* outs, float* const* zs,
                             float* const* fs, float* const* gs, const int* dil, const int* Zs, int B, int T, hipStream_t s);
@@ -201,19 +215,11 @@ int mfma_chain_reduce_all(const float* part, int L, const int* nwg, float* const
 int mfma_chain_combine(const float* V, const float* U, float* dx, int B, int T, int dU, int vu_t0, hipStream_t s);
 int generic_layer_bwd_biases(const Call& c, const float* dab, const float* dout, float* dbf, float* dbg, float* dbp, int B,
                              int T, int Cr, int Cd, int Z, hipStream_t s);
-// WN_EXEC_BIAS_PER_CLIP: dbf[b * stride + m] += sum_{t in [tmin, T)} da[(b T + t) lda + m], dbg likewise from dg, m < Cd: one
-// launch for both gates, the summation order of the shared-bias column sums of a B = 1 call, no atomics, no scratch
-int generic_colsum_per_clip(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
-                            long long stride, hipStream_t s);
-// The same with a row per (clip, frame): dbf[b * stride + f * fr.stride + m] += the sum over the t in [tmin, T) with
-// (t + fr.phase) / fr.hop == f, in a fixed order (k_colsum_per_frame); rows of frames wholly below tmin are not touched
-int generic_colsum_per_frame(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf, float* dbg,
-                             long long stride, BiasFrames fr, hipStream_t s);
-// Linear interpolation (fr.interp == 1): row f of a block of frames + 1 rows receives  sum (1 - alpha_t) d[t]  over the t >= tmin
-// of frame f  +  sum alpha_t d[t]  over those of frame f - 1 (k_colsum_per_frame_lerp, the same grid idea with one row more)
-int generic_colsum_per_frame_lerp(const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd, float* dbf,
-                                  float* dbg, long long stride, BiasFrames fr, hipStream_t s);
-// what the layer backwards call: the per-frame forms when c.frames.hop > 0 (by c.frames.interp), the per-clip form otherwise
+// WN_EXEC_BIAS_PER_CLIP: the bias gradients of both gates, one launch, no atomics, no scratch, by c.bias_mode(dbf, dbg).
+// kCondClip: dbf[b * c.bias_stride + m] += sum_{t in [tmin, T)} da[(b T + t) lda + m], dbg likewise from dg, m < Cd, in the
+// summation order of the shared-bias column sums of a B = 1 call.  kCondFrame: row f of the clip's block receives the t of
+// frame f; rows of frames wholly below tmin are not touched.  kCondLinear: row f of a block of frames + 1 rows receives
+// sum (1 - alpha_t) d[t] over the t of frame f + sum alpha_t d[t] over those of frame f - 1.  The orders: generic_kernels.hip.
 int generic_colsum_bias_rows(const Call& c, const float* da, const float* dg, int lda, int B, int T, int tmin, int Cd,
                              float* dbf, float* dbg, hipStream_t s);
 

@@ -282,53 +282,36 @@ class _StackFn(_Fn):
     (WaveNet.forward_residual_block, wavenet.py:572-582)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, net, t_off, train, window_only=False, cond=None, frames=None):
+    def forward(ctx, x, anchor, net, t_off, train, window_only=False, cond=None, rows=None):
         # `anchor` is a dummy leaf that requires grad: it keeps this node on the tape even when x
         # does not require grad, because the weights are not tensor inputs of the node.
-        # `cond` (global conditioning): the (B, sum 2 cd) block of per-clip gate biases of _CondFn -- layer l's filter row at
-        # net._cond_offsets[l][0], its gate row at [l][1] -- handed to the library as bias rows one block row apart
-        # (WN_EXEC_BIAS_PER_CLIP); the backward returns the block's gradient.
-        # `frames` = (hop, phase) (local conditioning): `cond` is then the (B, n, sum 2 cd) block of _LocalFn, a row per (clip,
-        # frame) -- clips n block rows apart, frames one (WnStackDesc.bias_hop / bias_phase / bias_frame_stride).  A third entry
-        # 1 selects linear interpolation between the rows (WnStackDesc.bias_interp), which reads one row more.
-        # `phase` a LocalPhases (a phase per clip): its int32 device tensor becomes WnStackDesc.bias_phase_tab in both calls
-        # (bias_phase stays 0); ctx.frames keeps it alive for the backward.
+        # `cond` (conditioning): the block of gate biases of _CondFn / _LocalFn, handed to the library as bias rows
+        # (WN_EXEC_BIAS_PER_CLIP); the backward returns the block's gradient.  `rows` is its GateBiasRows -- how the block is
+        # addressed -- and goes with it: both or neither.
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
-        desc = net._stack_desc()
-        ex = lambda: net._exec(B, T)
-        if cond is not None:
-            cond = cond.contiguous()
-            if frames is None and tuple(cond.shape) != (B, net._cond_rows):
-                raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (tuple(cond.shape), (B, net._cond_rows)))
-            if frames is not None:
-                # (a phase per clip: the columns of the worst phase, whatever the phases are)
-                worst = frames[0] - 1 if isinstance(frames[1], LocalPhases) else frames[1]
-                need = frames_needed(T, frames[0], worst, "linear" if len(frames) > 2 and frames[2] else "repeat")
-                if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] != net._cond_rows or cond.shape[1] < need:
-                    raise _lib.WaveNetHipError("local conditioning block is %s, expected (%d, >= %d, %d)"
-                                               % (tuple(cond.shape), B, need, net._cond_rows))
-            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg", frames)
-            desc = C.byref(cdesc)
-            stride = net._cond_rows if frames is None else int(cond.shape[1]) * net._cond_rows
-            ex = lambda: net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=stride)
+        if rows is None:
+            desc, ex = net._stack_desc(), net._exec(B, T)
+        else:
+            rows.check(B, T)
+            desc, ex, ckeep = rows.call(B, T)
         L = len(net._flat_layers)
         ncd = sum(lay.cd for lay in net._flat_layers)
         dev_ = x.device
         xs = torch.empty((L, B, T, Cr), device=dev_, dtype=torch.float32)
         z = torch.empty((B * T * ncd,), device=dev_, dtype=torch.float32)
         # tanh is saved only when the backward cannot take the chained path (which recovers it as z / sigmoid)
-        f = torch.empty_like(z) if train and _lib.lib().wn_stack_saves_tanh(desc, ex()) else None
+        f = torch.empty_like(z) if train and _lib.lib().wn_stack_saves_tanh(desc, ex) else None
         g = torch.empty_like(z) if train else None
         skip = torch.empty((B, T - t_off, net._Cs), device=dev_, dtype=torch.float32)
         check(_lib.lib().wn_stack_fwd(desc, ptr(x), ptr(xs), ptr(z), ptr(f), ptr(g), ptr(skip), B, T, t_off,
-                                      1 if net.compat_zero_prefix else 0, 1 if window_only else 0, ex(),
+                                      1 if net.compat_zero_prefix else 0, 1 if window_only else 0, ex,
                                       stream_ptr()), "wn_stack_fwd")
         ctx.net, ctx.t_off, ctx.shape, ctx.window_only = net, t_off, (B, T, Cr), bool(window_only)
         ctx.saved = (x, xs, z, f, g) if train else None
         ctx.cond = cond if train else None
-        ctx.frames = frames
+        ctx.rows = rows
         net._last_layer_inputs = [x] + [xs[l] for l in range(L - 1)]      # FasterWaveNet seeds its rings from these
         return xs[L - 1], skip
 
@@ -355,11 +338,8 @@ class _StackFn(_Fn):
         if cond is not None:
             # per-clip bias-gradient rows accumulate (+=) into a zeroed block: the gradient of the conditioning block
             dcond = torch.zeros_like(cond)
-            cdesc, ckeep = net._cond_tables(_lib.WnStackDesc, net._sdesc, cond, "bf", "bg", ctx.frames)
-            desc = C.byref(cdesc)
-            dbf, dbg = net._cond_rows_of(dcond)
-            stride = net._cond_rows if ctx.frames is None else int(cond.shape[1]) * net._cond_rows
-            ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=stride)
+            desc, ex, ckeep = ctx.rows.call(B, T)
+            dbf, dbg = ctx.rows.grad_tables(dcond)
         check(lib.wn_stack_bwd(desc, ptr(x), ptr(xs), ptr(z), ptr(f), ptr(g), ptr(dout), ptr(dskip), ptr(dx),
                                gt["wf"], dbf, gt["wg"], dbg, gt["wp"], gt["bp"], gt["ws"], gt["bs"],
                                ptr(ws), nbytes, B, T, t_off, 1 if net.compat_zero_prefix else 0, ex,
@@ -386,6 +366,71 @@ class LocalPhases(object):
     def fill(self, values):
         """Refill the device buffer from a checked host array (``check_local_phases``)."""
         self.tab.copy_(torch.from_numpy(np.ascontiguousarray(values, dtype=np.int32)), non_blocking=False)
+
+
+class GateBiasRows(object):
+    """The gate-bias rows one stack call reads (and its backward accumulates), with how they are addressed: what the library
+    is told through WN_EXEC_BIAS_PER_CLIP and WnStackDesc.bias_*.  ``block`` (contiguous, on the device) is (B, sum 2 cd), a row
+    per clip -- global conditioning, ``hop`` = 0 -- or (B, n, sum 2 cd), a row per (clip, frame of ``hop`` positions), frames
+    one block row apart -- local conditioning.  Layer l's filter row lies at ``net._cond_offsets[l][0]`` of a block row, its
+    gate row at ``[l][1]``.  ``phase``: an int, or a ``LocalPhases``, whose int32 device tensor becomes
+    ``WnStackDesc.bias_phase_tab`` (bias_phase stays 0; this object keeps it alive for the backward).  ``interp`` = 1: linear
+    interpolation between the rows (``WnStackDesc.bias_interp``), which reads one row more."""
+
+    def __init__(self, net, block, hop=0, phase=0, interp=0):
+        self.net, self.block, self.hop, self.phase, self.interp = net, block, int(hop), phase, int(interp)
+        self.tab = phase if isinstance(phase, LocalPhases) else None
+
+    @property
+    def worst_phase(self) -> int:
+        """The largest phase a clip can have: with a phase per clip, the columns of hop - 1, whatever the phases are."""
+        return self.hop - 1 if self.tab is not None else int(self.phase)
+
+    @property
+    def clip_stride(self) -> int:
+        """Floats between consecutive clips' rows (WnExec.reserved)."""
+        return self.net._cond_rows * (int(self.block.shape[1]) if self.hop else 1)
+
+    def check(self, B, T):
+        """The block's shape against a call of B clips of T positions."""
+        shape, width = tuple(self.block.shape), self.net._cond_rows
+        if not self.hop:
+            if shape != (B, width):
+                raise _lib.WaveNetHipError("conditioning block is %s, expected %s" % (shape, (B, width)))
+            return
+        need = frames_needed(T, self.hop, self.worst_phase, LOCAL_INTERP[self.interp])
+        if len(shape) != 3 or shape[0] != B or shape[2] != width or shape[1] < need:
+            raise _lib.WaveNetHipError("local conditioning block is %s, expected (%d, >= %d, %d)" % (shape, B, need, width))
+
+    def grad_tables(self, block):
+        """(bf, bg) pointer tables into clip 0's rows of ``block`` (this block, or a gradient block of its shape): layer l's
+        filter and gate rows."""
+        p0, offsets = block.data_ptr(), self.net._cond_offsets
+        bf = (C.c_void_p * len(offsets))(*[p0 + 4 * of for of, _ in offsets])
+        bg = (C.c_void_p * len(offsets))(*[p0 + 4 * og for _, og in offsets])
+        return bf, bg
+
+    def call(self, B, T):
+        """(descriptor, WnExec, what must stay alive) of a forward or backward call on these rows: a copy of the model's stack
+        descriptor whose bf / bg tables point into the block, and the call's WN_EXEC_BIAS_PER_CLIP context."""
+        net = self.net
+        net._stack_desc()
+        d = _lib.WnStackDesc()
+        for name, _ in _lib.WnStackDesc._fields_:
+            setattr(d, name, getattr(net._sdesc, name))
+        bf, bg = self.grad_tables(self.block)
+        d.bf, d.bg = C.cast(bf, C.POINTER(C.c_void_p)), C.cast(bg, C.POINTER(C.c_void_p))
+        if self.hop:
+            tab = self.tab
+            if tab is not None and (len(tab) != self.block.shape[0] or tab.hop != self.hop or tab.tab.dtype != torch.int32
+                                    or tab.tab.device != self.block.device or not tab.tab.is_contiguous()):
+                raise _lib.WaveNetHipError("the per-clip phases must be a contiguous int32 (%d,) tensor on the block's device, "
+                                           "checked against hop %d" % (self.block.shape[0], self.hop))
+            d.bias_hop, d.bias_frame_stride, d.bias_interp = self.hop, net._cond_rows, self.interp
+            d.bias_phase = 0 if tab is not None else int(self.phase)
+            d.bias_phase_tab = None if tab is None else tab.tab.data_ptr()
+        ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=self.clip_stride)
+        return C.byref(d), ex, (d, bf, bg)
 
 
 def _one_phase(phase) -> bool:
@@ -1118,35 +1163,6 @@ class WaveNet(object):
         return self._gt
 
     # -- global conditioning --------------------------------------------------------------------------------------------------
-    def _cond_rows_of(self, block):
-        """(bf, bg) pointer tables into clip 0's row of a (B, sum 2 cd) block: layer l's filter and gate rows."""
-        p0 = block.data_ptr()
-        L = len(self._cond_offsets)
-        bf = (C.c_void_p * L)(*[p0 + 4 * of for of, _ in self._cond_offsets])
-        bg = (C.c_void_p * L)(*[p0 + 4 * og for _, og in self._cond_offsets])
-        return bf, bg
-
-    def _cond_tables(self, cls, base, block, name_f, name_g, frames=None):
-        """A copy of the descriptor ``base`` whose bias tables point into ``block``; (descriptor, what must stay alive).
-        ``frames`` = (hop, phase): ``block`` holds a row per (clip, frame), frames one block row apart."""
-        d = cls()
-        for name, _ in cls._fields_:
-            setattr(d, name, getattr(base, name))
-        bf, bg = self._cond_rows_of(block)
-        setattr(d, name_f, C.cast(bf, C.POINTER(C.c_void_p)))
-        setattr(d, name_g, C.cast(bg, C.POINTER(C.c_void_p)))
-        if frames is not None:
-            tab = frames[1] if isinstance(frames[1], LocalPhases) else None
-            d.bias_hop, d.bias_frame_stride = int(frames[0]), self._cond_rows
-            d.bias_phase = 0 if tab is not None else int(frames[1])
-            d.bias_phase_tab = None if tab is None else tab.tab.data_ptr()
-            d.bias_interp = int(frames[2]) if len(frames) > 2 else 0
-            if tab is not None and (len(tab) != block.shape[0] or tab.hop != int(frames[0]) or tab.tab.dtype != torch.int32
-                                    or tab.tab.device != block.device or not tab.tab.is_contiguous()):
-                raise _lib.WaveNetHipError("the per-clip phases must be a contiguous int32 (%d,) tensor on the block's device, "
-                                           "checked against hop %d" % (block.shape[0], int(frames[0])))
-        return d, (bf, bg, block, frames)
-
     def _condition_ids(self, condition, B):
         """``condition=`` of the forward methods -> (B,) int64 class ids on the device, or None for an unconditioned model.
         A conditioned model called without ids raises, and so does an unconditioned one called with them."""
@@ -1542,15 +1558,19 @@ class WaveNet(object):
         _need_gpu(x)
         cond = self._condition_block(condition, int(x.shape[0]))
         feats, phase = self._local_features(local, int(x.shape[0]), int(x.shape[3]), local_phase)
-        frames = None
+        rows = None
         if feats is not None:
-            cond, frames = self._local_block(feats, cond), (self.local_hop, phase, 1 if self.local_interp == "linear" else 0)
+            cond = self._local_block(feats, cond).contiguous()
+            rows = GateBiasRows(self, cond, self.local_hop, phase, LOCAL_INTERP.index(self.local_interp))
+        elif cond is not None:
+            cond = cond.contiguous()
+            rows = GateBiasRows(self, cond)
         if self.storage == "bf16":
             self._pack16_if_stale()
             out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled())
             return _as_view(out), _as_view(skip)
         out, skip = _StackFn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled(),
-                                   bool(window_only), cond, frames)
+                                   bool(window_only), cond, rows)
         return _as_view(out), _as_view(skip)
 
     def forward_softmax_block(self, x_batch, apply_softmax=True, activation: Optional[str] = None):
