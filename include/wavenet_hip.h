@@ -376,6 +376,15 @@ typedef struct WnDecoderDesc {
                                          same products, another summation order for the skip rows and the logits --
                                          probabilities agree to ~1e-7, sampled tokens can differ at a near-tie of the
                                          cumulative distribution; each form is deterministic */
+    /* A length per utterance (declared ahead of the local-conditioning group; descriptors are filled by field name).  Applied by
+     * wn_decoder_create and wn_decoder_update_weights, as the frame table is.  0, the default: no limit -- every call executes
+     * what it executed before the field existed.  Negative: WN_EARG before any device work.  L > 0: the handle runs at most L
+     * steps since the create / update call that set it, counted by the ONE counter the frame table uses ("steps run since the
+     * create / update call": that call sets both, and resets the count with or without a table).  wn_decoder_step and
+     * wn_decoder_run never clamp: more steps than are left is WN_EARG before any device work, the handle's state left alone --
+     * the rule of a frame-table overrun.  wn_decoder_run_batch clamps per utterance (see there).  wn_decoder_update_weights is
+     * the one way to set a new limit (or to start the count again); it re-packs the weights, as it does for a new table. */
+    int step_limit;
     /* Local conditioning (trailing fields; frame_bias == NULL: every decode kernel executes what it executed before).  Applied
      * by wn_decoder_create and wn_decoder_update_weights; the handle COPIES the table, as it copies weights.  frame_bias: a
      * device pointer to n_frames rows, frame_stride floats apart; inside a row flat layer l (block-major, as bf / bg are
@@ -438,7 +447,18 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
  *     the first call and grown only by a larger batch: a repeated call allocates nothing and waits on the host only for the
  *     previous call's table copy (not its launch) before it rewrites the pinned image of the table.
  * A handle created with WN_DECODER_ONE_WORKGROUP is refused (WN_ESHAPE): that kernel has no batched form.  Every refusal
- * comes before any device work. */
+ * comes before any device work.
+ * A length per utterance (WnDecoderDesc.step_limit).  Utterance u runs n_u = min(n, left_u) steps, left_u = its handle's
+ * step_limit minus the steps run since the create / update call that set it (the counter the frame table shares), or n without a
+ * limit; handles with and without a limit may share a launch.  Everything per utterance uses n_u: the frame-table check, the
+ * step-counter overflow check, the advance of the handle's counters; uniforms[u] needs n_u doubles; out_tokens[u][n_u .. n) and
+ * rows n_u .. n of a probability trace are NOT written; the first n_u tokens and rows are those of the utterance's own
+ * wn_decoder_run(..., n_u, ...), bit for bit.  WN_EARG before any device work, the message naming the utterance: a handle with
+ * left_u == 0 (the caller leaves finished utterances out), and on the nine-workgroup form a handle whose limit leaves it n_u < 2.
+ * In the kernels the count is a word of the utterance's entry (read by all nine workgroups of its group; by its one workgroup
+ * in the any-shape form); the batched kernels take NO launch-wide step count any more -- n remains the host-side bound of the
+ * checks.  With every n_u == n a launch computes what it computed before.  same_weights != 0: an utterance 0 that ends first
+ * leaves its packed weights in place, and the others keep reading them.  wn_decoder_status is unchanged. */
 #define WN_DECODER_BATCH_MAX_ANY 1024      /* utterances per launch of the one-workgroup-per-utterance form */
 /* the limit of the nine-workgroup form (28) */
 int wn_decoder_batch_max(void);

@@ -36,6 +36,7 @@ class WnDecoderDesc(C.Structure):
         ("Wf", _pp), ("bf", _pp), ("Wg", _pp), ("bg", _pp), ("Wp", _pp), ("bp", _pp), ("Ws", _pp), ("bs", _pp),
         ("head_W", _pp), ("head_b", _pp),
         ("head_act", _i), ("flags", C.c_uint),
+        ("step_limit", _i),                                                                  # 0 = no limit; L: at most L steps since create / update
         ("frame_interp", _i),                                                                # 0 = repeat, 1 = linear interpolation
         ("frame_bias", _p), ("n_frames", _i), ("frame_hop", _i), ("frame_phase", _i), ("frame_stride", _i),   # local conditioning
     ]

@@ -51,10 +51,13 @@ struct Decoder {
     int batch_cap = 0;
     hipEvent_t batch_copied = nullptr;
     // local conditioning (WnDecoderDesc.frame_bias): the handle's own compact copy of the table -- n_frames rows of frame_row
-    // floats (sum_l 2 cd_l) --, its hop and phase, and how many steps have run since the create / update call that set it
+    // floats (sum_l 2 cd_l) --, its hop and phase
     float* frame_tab = nullptr;
     int frame_cap = 0, n_frames = 0, frame_hop = 0, frame_phase = 0, frame_row = 0, frame_interp = 0;
-    long long frame_pos = 0;
+    // steps run since the last create / update call -- the call that sets the frame table AND the step limit, so one counter
+    // serves both: the table row of a step and the steps left under WnDecoderDesc.step_limit (0: no limit)
+    long long since_set = 0;
+    int step_limit = 0;
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
 };
@@ -139,7 +142,7 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 // ---- the step loop ---------------------------------------------------------------------------
 // Local conditioning: the frame table of one utterance as the step loop takes it.  tab == NULL: no table, and the loop
 // executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the handle's
-// frame_phase + the steps run since the table was set -- to every layer's gate pre-activations.
+// frame_phase + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
 // interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
 // float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
 struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
@@ -344,18 +347,19 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
 struct DecAnyUtt {
     const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
     float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
-    int first_token; int pad;
+    int first_token; int nsteps;       // nsteps: the utterance's own step count, min(n, steps left under its step_limit)
     SampleCtl sc;
     DecFrames fr;
 };
 
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
-// never wait for each other, so any number of them may be queued behind the CUs.
+// never wait for each other, so any number of them may be queued behind the CUs -- and each runs its utterance's own step
+// count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.
 template <bool LERP>
-__global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int nsteps) {
+__global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt) {
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
-    decode_steps<LERP>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, nsteps, q.first_token, q.uniforms, q.out_tokens,
+    decode_steps<LERP>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
                  q.prob_out, M.Q, 1, 1, q.sc, q.fr);
 }
 
@@ -373,6 +377,7 @@ static int validate(const WnDecoderDesc* d) {
                  "decoder: head channels must run Cs ... Q");
     WN_CHECK_ARG(d->head_act == WN_ACT_RELU || d->head_act == WN_ACT_ELU || d->head_act == WN_ACT_NONE,
                  "decoder: bad head_act");
+    WN_CHECK_ARG(d->step_limit >= 0, "decoder: step_limit = %d is negative (0: no limit)", d->step_limit);
     return WN_OK;
 }
 
@@ -382,7 +387,7 @@ static inline long long align64(long long x) { return (x + 63) & ~63ll; }
 static DecFrames launch_frames(const Decoder* D) {
     DecFrames f{};
     if (D->n_frames > 0) {
-        f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->frame_pos;
+        f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->since_set;
         f.interp = D->frame_interp;
     }
     return f;
@@ -392,11 +397,25 @@ static bool lerp_table(const Decoder* D) { return D->n_frames > 0 && D->frame_in
 static int check_frames(const char* fn, const Decoder* D, long long n) {
     if (D->n_frames <= 0) return WN_OK;
     // (linear interpolation: the last step reads row j + 1 as well)
-    const long long last = (D->frame_phase + D->frame_pos + n - 1) / D->frame_hop + (D->frame_interp ? 1 : 0);
+    const long long last = (D->frame_phase + D->since_set + n - 1) / D->frame_hop + (D->frame_interp ? 1 : 0);
     WN_CHECK_ARG(last < D->n_frames, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
-                                     "run on it%s)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->frame_pos,
+                                     "run on it%s)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->since_set,
                  D->frame_interp ? "; linear interpolation reads the row after the step's own" : "");
     return WN_OK;
+}
+// WnDecoderDesc.step_limit: n more steps must not pass it.  The single-utterance entry points refuse before any device work
+// and never clamp -- the rule of a frame-table overrun; wn_decoder_run_batch clamps per utterance instead (steps_left).
+static int check_limit(const char* fn, const Decoder* D, long long n) {
+    WN_CHECK_ARG(D->step_limit <= 0 || D->since_set + n <= D->step_limit,
+                 "%s: n = %lld more steps would pass step_limit = %d (%lld steps run since it was set)", fn, n, D->step_limit,
+                 D->since_set);
+    return WN_OK;
+}
+// how many of n steps the handle may still run: all of them without a limit
+static long long steps_left(const Decoder* D, long long n) {
+    if (D->step_limit <= 0) return n;
+    const long long left = D->step_limit - D->since_set;
+    return left < n ? left : n;
 }
 static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
     if (!d->frame_bias) return WN_OK;
@@ -414,9 +433,11 @@ static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
                             "handle with the table");
     return WN_OK;
 }
-// copy the table (after check_frame_desc), or drop it when the description has none; the step count starts again
+// copy the table (after check_frame_desc), or drop it when the description has none, and take the step limit; the step count
+// that both are measured against starts again, with or without a table
 static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
-    D->frame_pos = 0;
+    D->since_set = 0;
+    D->step_limit = d->step_limit;
     if (!d->frame_bias) { D->n_frames = 0; return WN_OK; }
     int row = 0;
     for (const DecLayer& L : D->layers) row += 2 * L.cd;
@@ -652,11 +673,13 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     WN_CHECK_ARG(token >= 0 && token < D->meta.Q, "wn_decoder_step: token %d outside [0,%d)", token, D->meta.Q);
     WN_CHECK_ARG(D->step + 1 < (1ll << 31), "wn_decoder_step: step counter overflow");
     if (int rc = check_frames("wn_decoder_step", D, 1)) return rc;
+    if (int rc = check_limit("wn_decoder_step", D, 1)) return rc;
     if (D->fastP) {
         int rc = decode_fast_launch(fast_utt(D, (int)token, nullptr, nullptr, prob, SampleCtl()), D->meta.nlayers, 1, D->meta.Q,
                                     apply_softmax, 0, D->meta.head_act, false, as_stream(stream));
         if (rc) return rc;
         D->step += 1;
+        D->since_set += 1;
         return WN_OK;
     }
     const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
@@ -665,7 +688,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
                        (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl(), launch_frames(D));
     WN_LAUNCH_CHECK();
     D->step += 1;
-    D->frame_pos += 1;
+    D->since_set += 1;
     return WN_OK;
 }
 
@@ -676,12 +699,14 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
     WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run: step counter overflow");
     if (int rc = check_frames("wn_decoder_run", D, n)) return rc;
+    if (int rc = check_limit("wn_decoder_run", D, n)) return rc;
     if (D->fastP) {
         int rc = decode_fast_launch(fast_utt(D, (int)first_token, uniforms, out_tokens, prob_trace, launch_ctl(D)),
                                     D->meta.nlayers, n, D->meta.Q, 1, 1, D->meta.head_act, D->three_wgs, as_stream(stream));
         if (rc) return rc;
         D->ran_multi = D->three_wgs && n > 1;
         D->step += n;
+        D->since_set += n;
         return WN_OK;
     }
     const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
@@ -690,7 +715,7 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
                        out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D), launch_frames(D));
     WN_LAUNCH_CHECK();
     D->step += n;
-    D->frame_pos += n;
+    D->since_set += n;
     return WN_OK;
 }
 
@@ -709,9 +734,9 @@ int wn_decoder_set_sampling(void* handle, float temperature, int top_k, double t
 int wn_decoder_batch_max(void) { return kDecMaxBatch; }
 
 // the any-shape form of wn_decoder_run_batch, after every check: the utterances' table into handle 0's device buffer (one
-// async copy from its pinned image), then one launch of n_handles workgroups
-static int run_batch_any(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms, int n,
-                         int32_t* const* out_tokens, float* const* prob_traces, hipStream_t s) {
+// async copy from its pinned image), then one launch of n_handles workgroups.  nsteps[u]: utterance u's own step count
+static int run_batch_any(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms,
+                         const int* nsteps, int32_t* const* out_tokens, float* const* prob_traces, hipStream_t s) {
     Decoder* D0 = (Decoder*)handles[0];
     if (n_handles > D0->batch_cap) {                   // first use, or a larger batch than ever before
         if (D0->batch_tab) { WN_HIP(hipFree(D0->batch_tab)); D0->batch_tab = nullptr; }      // hipFree waits for its readers
@@ -733,16 +758,16 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
         DecAnyUtt q{};
         q.causal = D->d_causal; q.layers = D->d_layers; q.heads = D->d_heads; q.arena = D->arena; q.tok_ring = D->tok_ring;
         q.n0 = D->step; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_traces ? prob_traces[u] : nullptr;
-        q.first_token = (int)first_tokens[u]; q.sc = launch_ctl(D); q.fr = launch_frames(D);
+        q.first_token = (int)first_tokens[u]; q.nsteps = nsteps[u]; q.sc = launch_ctl(D); q.fr = launch_frames(D);
         img[u] = q;
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
     const auto kern = lerp_table(D0) ? k_decode_batch<true> : k_decode_batch<false>;     // (the handles agree on the mode)
     hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
-                       n_handles, n);
+                       n_handles);
     WN_LAUNCH_CHECK();
-    for (int u = 0; u < n_handles; ++u) { ((Decoder*)handles[u])->step += n; ((Decoder*)handles[u])->frame_pos += n; }
+    for (int u = 0; u < n_handles; ++u) { ((Decoder*)handles[u])->step += nsteps[u]; ((Decoder*)handles[u])->since_set += nsteps[u]; }
     return WN_OK;
 }
 
@@ -757,6 +782,8 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     WN_CHECK_SHAPE(n_handles <= limit, "wn_decoder_run_batch: at most %d utterances per launch of %s decoders", limit,
                    any ? "any-shape" : "nine-workgroup");
     DecUtt utt[kDecMaxBatch];
+    // utterance u runs nu[u] = min(n, steps left under its handle's step_limit) steps: n without a limit
+    int nu[WN_DECODER_BATCH_MAX_ANY];
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
         WN_CHECK_ARG(D && uniforms[u] && out_tokens[u], "wn_decoder_run_batch: NULL handle / uniforms / out_tokens of utterance %d", u);
@@ -786,16 +813,26 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_ARG(!same_weights || D->src_key == D0->src_key,
                      "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
-        WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
+        const long long left = steps_left(D, n);
+        WN_CHECK_ARG(left > 0, "wn_decoder_run_batch: utterance %d has run all %d steps of its step_limit: leave a finished utterance "
+                               "out of the launch", u, D->step_limit);
+        // the nine-workgroup form runs two steps at least: its existing rule, here per utterance (a launch whose own n is below
+        // 2 is refused as ever, below)
+        WN_CHECK_ARG(any || left == n || left >= 2, "wn_decoder_run_batch: utterance %d has %lld step left under its step_limit = %d: "
+                                                    "the nine-workgroup form runs 2 at least", u, left, D->step_limit);
+        nu[u] = (int)left;
+        WN_CHECK_ARG(D->step + nu[u] < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
         WN_CHECK_ARG((D->n_frames > 0) == (D0->n_frames > 0) && (D->n_frames <= 0 || D->frame_hop == D0->frame_hop),
                      "wn_decoder_run_batch: utterance %d and utterance 0 disagree on having a frame table or on its hop", u);
         WN_CHECK_ARG(D->n_frames <= 0 || D->frame_interp == D0->frame_interp,
                      "wn_decoder_run_batch: utterance %d and utterance 0 disagree on frame_interp (repeat / linear)", u);
-        if (int rcf = check_frames("wn_decoder_run_batch", D, n)) return rcf;
-        if (!any)
+        if (int rcf = check_frames("wn_decoder_run_batch", D, nu[u])) return rcf;
+        if (!any) {
             utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
+            utt[u].nsteps = nu[u];
+        }
     }
-    if (any) return run_batch_any(handles, n_handles, first_tokens, uniforms, n, out_tokens, prob_traces, as_stream(stream));
+    if (any) return run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream));
     WN_CHECK_SHAPE(decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
@@ -804,7 +841,8 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
         D->ran_multi = true;
-        D->step += n;
+        D->step += nu[u];
+        D->since_set += nu[u];
     }
     return WN_OK;
 }

@@ -768,12 +768,15 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nla
 // has a strict sample-to-sample dependency, so the other 247 CUs can only run OTHER utterances).  Every utterance has its own
 // decoder state (rings, token ring, exchange entries, packed weights: a handle each), its own uniforms and outputs; the groups
 // share nothing and never wait for each other, so an utterance's tokens are those of its own wn_decoder_run, bit for bit.
+// The launch has no step count of its own: utterance u runs a.it[u].nsteps steps.  All nine workgroups of the utterance read
+// that ONE word, and decode_fast3_body has one step loop per role -- the eight skip workgroups' and the chain workgroup's, whose
+// publisher wave runs inside the chain's loop --, each bounded by the same argument: no workgroup of a group runs a step its
+// partners do not, so no wait is left without its entry, and a group that ends early simply ends.
 struct DecBatchArgs { DecUtt it[kDecMaxBatch]; };
 static_assert(sizeof(DecBatchArgs) + 4 * sizeof(int) <= 4096, "kernel arguments are passed by value: 4 KB at most");
-__global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int nsteps, int prob_stride,
-                                                               int head_act) {
+__global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int prob_stride, int head_act) {
     const int u = blockIdx.x / (kD10Skip + 1);
-    decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, nsteps, prob_stride, 1, 1, head_act);
+    decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
@@ -838,6 +841,11 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
         return WN_ESHAPE;
     }
+    for (int u = 0; u < n_utt; ++u)        // every group of nine runs 2 steps at least, n at most (wn_decoder_run_batch has checked it)
+        if (utt[u].nsteps < 2 || utt[u].nsteps > nsteps) {
+            wn::set_error("decode batch: utterance %d's step count %d outside [2, %d]", u, utt[u].nsteps, nsteps);
+            return WN_EARG;
+        }
     WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch);
     DecBatchArgs a{};
     for (int u = 0; u < n_utt; ++u) {
@@ -847,11 +855,13 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
         zero_x(q.X, nlayers, s);
         // same_weights (the caller's word that every handle was created from the same weights): every utterance reads utterance
         // 0's packed weights, embedding table and head bias -- the 28 chain workgroups then stream ONE 0.96 MB copy per step
-        // through the XCDs' L2s instead of 28; the state (rings, token ring, exchange entries) stays per utterance
+        // through the XCDs' L2s instead of 28; the state (rings, token ring, exchange entries) stays per utterance.  An
+        // utterance 0 that ends before the others leaves its packed weights in place -- a launch frees and rewrites nothing of
+        // a handle's weights -- and the others keep reading them.
         if (same_weights) { q.P = utt[0].P; q.hbias = utt[0].hbias; q.E = utt[0].E; }
     }
     hipLaunchKernelGGL(k_decode_fast3_batch, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
-                       nsteps, prob_stride, head_act);
+                       prob_stride, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;
 }

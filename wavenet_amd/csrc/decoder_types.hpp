@@ -15,7 +15,9 @@ struct DecUtt {
     const float* P; const float* hbias; const float* E; const DecLayer* layers; float* arena; int* tok_ring;
     long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
     unsigned long long* X;             // exchange entries of the nine-workgroup form: set by the launch, from P
-    int first_token; int pad;
+    int first_token;
+    int nsteps;                        // batched launch: the utterance's own step count, the ONE word all nine of its workgroups
+                                       // read (single runs pass theirs as a kernel argument and leave this 0)
     SampleCtl sc;                      // per utterance: its handle's wn_decoder_set_sampling
 };
 size_t decode_fast_pack_floats(int nlayers);
@@ -24,6 +26,7 @@ int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int a
                        bool three_wgs, hipStream_t s);
 static constexpr int kDecMaxBatch = 28;                    // utterances per batched launch: 28 x 9 workgroups on 256 CUs
 int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps);
+// (nsteps: the launch's n, an upper bound of the utterances' counts, for the checks only: the kernel reads DecUtt.nsteps)
 int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
                              bool same_weights, hipStream_t s);
 int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up);

@@ -37,8 +37,53 @@ class _RingState(object):
         return "<device ring state: %s>" % self.what
 
 
+def deal_launches(lengths, limit, longest_first=True):
+    """Deal utterances of ``lengths[i]`` decode steps to launches of at most ``limit`` utterances each: sorted longest first
+    (stable: equal lengths keep the caller's order), then cut into runs of ``limit``.  Returns ``[(n, [i, ...]), ...]`` -- a
+    launch's step count ``n`` (its longest utterance's) and the caller's indices of its utterances in the order their handles
+    are passed, longest first.  Every index appears exactly once, so results go back to the caller's order by index.  Utterances
+    of similar length share a launch: the launch lasts as long as its longest one.  ``longest_first=False`` (the other side of
+    tools/time_ragged_decode.py's comparison) keeps the same launches and passes each one's handles in the caller's order."""
+    lengths = [int(v) for v in lengths]
+    limit = int(limit)
+    if limit < 1:
+        raise ValueError("deal_launches: limit must be at least 1, got %d" % limit)
+    order = sorted(range(len(lengths)), key=lambda i: -lengths[i])             # sorted() is stable
+    launches = [(lengths[order[c0]], order[c0:c0 + limit]) for c0 in range(0, len(order), limit)]
+    return launches if longest_first else [(n, sorted(idx)) for n, idx in launches]
+
+
+def _ragged_lengths(n_samples, uniforms):
+    """``generate_batch``'s sequence form: (lengths, one 1-D float64 array of uniforms per utterance), every check made and
+    every message naming the first offending utterance."""
+    if np.ndim(n_samples) != 1:
+        raise Exception("generate_batch: n_samples must be an int or a sequence of one positive int per utterance")
+    ns = list(n_samples)
+    if isinstance(uniforms, np.ndarray) or isinstance(uniforms, torch.Tensor):
+        rows = np.asarray(uniforms.cpu() if isinstance(uniforms, torch.Tensor) else uniforms, dtype=np.float64)
+        if rows.ndim != 2:
+            raise Exception("generate_batch: uniforms must be an (N, >= max(n_samples)) array or a list of N 1-D arrays")
+        rows = list(rows)
+    else:
+        rows = [np.asarray(r, dtype=np.float64).reshape(-1) for r in uniforms]
+    N = len(rows)
+    if len(ns) != N:
+        raise Exception("generate_batch: n_samples holds %d lengths for %d utterances (utterance %d has %s)"
+                        % (len(ns), N, min(len(ns), N), "no length" if len(ns) < N else "no uniforms"))
+    for i, v in enumerate(ns):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise Exception("generate_batch: n_samples of utterance %d must be a positive integer, got %r" % (i, v))
+    ns = [int(v) for v in ns]
+    for i in range(N):
+        if rows[i].size < ns[i]:
+            raise Exception("generate_batch: utterance %d has %d uniforms for its %d samples: one per emitted sample"
+                            % (i, rows[i].size, ns[i]))
+    return ns, [np.ascontiguousarray(rows[i][:ns[i]]) for i in range(N)]
+
+
 class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
+    batch_longest_first = True         # generate_batch: a launch's handles longest first (deal_launches; False: caller's order)
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
                  condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
@@ -75,8 +120,10 @@ class FasterWaveNet(WaveNet):
         self._batch_stale = [True] * len(getattr(self, "_batch_decs", []))
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self, cond=None, table=None):
-        """``table``: (rows (n, sum 2 cd) float32 on the device, hop, phase) -- a locally conditioned model's handle copies one
+    def _desc(self, cond=None, table=None, step_limit=0):
+        """``step_limit``: ``WnDecoderDesc.step_limit`` -- a handle of a ragged ``generate_batch`` call ends after its own
+        utterance's steps (0: no limit).
+        ``table``: (rows (n, sum 2 cd) float32 on the device, hop, phase) -- a locally conditioned model's handle copies one
         utterance's frame table (``WnDecoderDesc.frame_bias``) at create / update time and counts its steps from there; such
         handles are any-shape ones too.
         ``cond``: [(bf, bg)] per residual layer (``condition_biases``) -- a globally conditioned model's handle holds ONE
@@ -106,6 +153,7 @@ class FasterWaveNet(WaveNet):
             setattr(d, k, C.cast(keep[k], C.POINTER(C.c_void_p)))
         d.head_act = ACT[self.fast_head_activation]
         d.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        d.step_limit = int(step_limit)
         if table is not None:
             rows, hop, phase = table
             keep["table"] = rows
@@ -403,9 +451,9 @@ class FasterWaveNet(WaveNet):
             which.append(seen[k])
         return prompts, which
 
-    def generate_batch(self, n_samples: int, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
+    def generate_batch(self, n_samples, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
                        condition=None, local=None, local_phase=0):
-        """``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
+        """``n_samples`` an int -- ``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
         (N, n_samples) int32 tokens on the device.  ``initial_tokens``: None (silence), one 1-D window for every utterance, or
         an (N, W) integer array -- a prompt per utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a
         scalar or one value per utterance.  Row u equals ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's
@@ -429,20 +477,39 @@ class FasterWaveNet(WaveNet):
         ``local`` / ``local_phase`` (locally conditioned models): one (F, n) array for all utterances or a list of one per
         utterance, each covering its utterance from its first sample on, prompt included; the phases likewise.  Every
         handle copies its utterance's table, one prefill runs per distinct (window, class, features, phase), and
-        ``same_weights`` is 0 when the tables differ."""
+        ``same_weights`` is 0 when the tables differ.
+
+        A length per utterance: ``n_samples`` a sequence of N positive ints, ``uniforms`` an (N, >= max) array or a list of N
+        1-D arrays (utterance u needs ``n_samples[u]`` values).  Returns a LIST of N 1-D int32 device tensors, tensor u of length
+        ``n_samples[u]`` and equal, bit for bit, to ``generate(n_samples[u], uniforms[u][:n_samples[u]], initial_tokens=<u's
+        window>, <u's controls, class, features, phase>)``; the features are checked per utterance against its own length.
+        A wrong number of lengths, a non-integer or non-positive one, too few uniforms or features that do not cover an
+        utterance raise before any device work, naming the first such utterance.  The utterances are dealt to launches longest
+        first (``deal_launches``): a launch's step count is its longest utterance's, every handle carries ``step_limit`` =
+        its own ``n_samples[u] - 1`` and its workgroups end there.  An utterance of length 1 decodes nothing and joins no
+        launch; on the nine-workgroup form any utterance of length 2 sends the whole call to the loop over ``generate()``,
+        as ``n_samples == 2`` does.  An int ``n_samples`` is the call it always was (no limit on any handle)."""
         p = self.params
         Q = p.quantization_steps
-        u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
-        if u_np.ndim != 2 or u_np.shape[1] < n_samples:
-            raise Exception("uniforms must be (N, >= n_samples)")
-        N = u_np.shape[0]
+        ragged = not isinstance(n_samples, (int, np.integer))
+        if ragged:
+            ns, u_rows = _ragged_lengths(n_samples, uniforms)
+            N = len(ns)
+            u_np = None
+        else:
+            u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
+            if u_np.ndim != 2 or u_np.shape[1] < n_samples:
+                raise Exception("uniforms must be (N, >= n_samples)")
+            N = u_np.shape[0]
+            ns, u_rows = [int(n_samples)] * N, u_np
+            n_samples = int(n_samples)
         lib = _lib.lib()
         temps = [float(t) for t in sampling.per_utterance(temperature, N, "temperature")]
         top_ks = [int(k) for k in sampling.per_utterance(top_k, N, "top_k")]
         top_ps = [float(v) for v in sampling.per_utterance(top_p, N, "top_p")]
         for i in range(N):
             sampling.check_controls(temps[i], top_ks[i], top_ps[i])
-        if n_samples < 1:
+        if not ragged and n_samples < 1:
             raise Exception("generate_batch: n_samples must be positive")
         if N < 1:
             raise Exception("generate_batch: no utterance")
@@ -469,20 +536,34 @@ class FasterWaveNet(WaveNet):
                 locs.append(per[i])
             lid.append(seen_l[id(per[i])])
         W_of = [int(prompts[k].shape[0]) for k in which]
-        lfeats = {}
+        lfeats, covered = {}, {}
         for i in range(N):                                                    # every check before any work
             key = (which[i], lid[i], phs[i])
-            if key not in lfeats:
-                lfeats[key] = self._utterance_local(locs[lid[i]], phs[i], W_of[i], n_samples, "generate_batch")
+            # (the features are checked against each utterance's own length: again only for a longer utterance than the
+            # key's longest so far, so the first utterance they do not cover is the one that raises)
+            if key not in lfeats or ns[i] > covered[key]:
+                try:
+                    lfeats[key] = self._utterance_local(locs[lid[i]], phs[i], W_of[i], ns[i], "generate_batch")
+                except Exception as e:
+                    if not ragged:
+                        raise
+                    raise Exception("generate_batch: utterance %d: %s" % (i, e))
+                covered[key] = ns[i]
         # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
         # decided BEFORE any work is done
         flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         nine = self._nine_workgroup_shape(flags)
-        if nine and (n_samples == 2 or flags & _lib.WN_DECODER_ONE_WORKGROUP):
-            return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids, per, phs)
+        loop_args = (ns if ragged else n_samples, u_rows, prompts, which, temps, top_ks, top_ps, cids, per, phs)
+        if nine and (any(n == 2 for n in ns) or flags & _lib.WN_DECODER_ONE_WORKGROUP):
+            return self._generate_batch_loop(*loop_args)
         limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
-        u = torch.as_tensor(u_np).to(self.device)
-        run = n_samples > 1
+        if ragged:
+            u_dev = [torch.as_tensor(r).to(self.device) for r in u_rows]
+        else:
+            u = torch.as_tensor(u_np).to(self.device)
+        run = max(ns) > 1
+        # a ragged call: every handle ends after its own utterance's decode steps (the first sample comes from the prefill)
+        limits = [n - 1 if ragged else 0 for n in ns]
         biases = {c: self.condition_biases(c) for c in sorted(set(cids))} if run and self.condition_classes else {None: None}
         fresh = set()                                     # handles created in this call hold their weights and table already
         while run and len(self._batch_decs) < N:
@@ -490,7 +571,7 @@ class FasterWaveNet(WaveNet):
             fresh.add(i)
             c = cids[i]
             ft, ph = lfeats[(which[i], lid[i], phs[i])]       # (a handle is created WITH its table: that selects the any-shape decoder)
-            d, keep = self._desc(biases[c], None if ft is None else self._decoder_table(ft, ph, W_of[i]))
+            d, keep = self._desc(biases[c], None if ft is None else self._decoder_table(ft, ph, W_of[i]), limits[i])
             h = C.c_void_p()
             check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
             self._batch_decs.append(h)
@@ -499,11 +580,15 @@ class FasterWaveNet(WaveNet):
         for i in range(N if run else 0):
             # (a locally conditioned model's other handles are updated in every call: the table and its step count belong to the
             # utterance, and the library's one way to set them is wn_decoder_update_weights, which also re-packs the weights)
-            if i not in fresh and (self._batch_stale[i] or self._batch_class[i] != cids[i] or self.local_channels):
+            # (a ragged call updates them all as well: the update is the library's one way to set a step limit and to start its
+            # count again.  A handle that holds a limit stays marked stale, so that a later int call takes the limit off.)
+            if i not in fresh and (self._batch_stale[i] or self._batch_class[i] != cids[i] or self.local_channels or ragged):
                 ft, ph = lfeats[(which[i], lid[i], phs[i])]
-                d, keep = self._desc(biases[cids[i]], None if ft is None else self._decoder_table(ft, ph, W_of[i]))
+                d, keep = self._desc(biases[cids[i]], None if ft is None else self._decoder_table(ft, ph, W_of[i]), limits[i])
                 check(lib.wn_decoder_update_weights(self._batch_decs[i], C.byref(d), stream_ptr()), "wn_decoder_update_weights")
                 self._batch_stale[i], self._batch_class[i] = False, cids[i]
+            if limits[i]:
+                self._batch_stale[i] = True
             check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
         # one prefill per distinct window, at batch 1 as generate() runs it; the decoder states of its utterances are seeded
         # from it, and its first row (one per distinct temperature) is what generate() draws the first token from
@@ -533,9 +618,13 @@ class FasterWaveNet(WaveNet):
                                                     stream_ptr()), "wn_decoder_load_state")
             for t in sorted({temps[i] for i in mine}):
                 rows[(k, cid, li, ph, t)] = self._first_row(sum_skip, p0, t)
-        out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
+        if ragged:
+            res = [torch.empty((ns[i],), device=self.device, dtype=torch.int32) for i in range(N)]
+            u0 = torch.as_tensor(np.array([r[0] for r in u_rows], dtype=np.float64)).to(self.device)
+        else:
+            out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
+            u0 = u[:, 0].contiguous()
         first = torch.empty((N,), device=self.device, dtype=torch.int32)
-        u0 = u[:, 0].contiguous()
         if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
             first_prob = torch.cat([rows[(which[i], cids[i], lid[i], phs[i], temps[i])] for i in range(N)], dim=0).contiguous()
             check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
@@ -543,36 +632,48 @@ class FasterWaveNet(WaveNet):
             for i in range(N):                                       # the truncation per utterance, as generate() draws
                 check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], cids[i], lid[i], phs[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
                                                          Q, top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
-        out[:, 0] = first
+        if ragged:
+            for i in range(N):
+                res[i][:1] = first[i:i + 1]
+        else:
+            out[:, 0] = first
         if run:
             firsts = [int(v) for v in first.cpu().tolist()]
-            rest = [u[i, 1:].contiguous() for i in range(N)]
+            rest = [u_dev[i][1:] if ragged else u[i, 1:].contiguous() for i in range(N)]
             # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
-            outs = [torch.empty((n_samples - 1,), device=self.device, dtype=torch.int32) if nine else out[i, 1:] for i in range(N)]
+            outs = [torch.empty((ns[i] - 1,), device=self.device, dtype=torch.int32) if nine else
+                    (res[i][1:] if ragged else out[i, 1:]) for i in range(N)]
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
             if len(set(cids)) > 1:
                 same = 0                                              # ... but hold different classes' biases
             if self.local_channels and len({(which[i], lid[i], phs[i]) for i in range(N)}) > 1:
                 same = 0                                              # ... or different frame tables
-            for c0 in range(0, N, limit):                             # launches of at most `limit`, one after another
-                c1 = min(N, c0 + limit)
-                rc = lib.wn_decoder_run_batch((C.c_void_p * (c1 - c0))(*[h.value for h in self._batch_decs[c0:c1]]), c1 - c0,
-                                              (C.c_int32 * (c1 - c0))(*firsts[c0:c1]), ptr_array(rest[c0:c1]), n_samples - 1,
-                                              ptr_array(outs[c0:c1]), None, same, stream_ptr())
+            # launches of at most `limit` utterances, one after another: the utterances that decode at all (length 1 is the
+            # prefill's sample alone), dealt longest first -- equal lengths: the caller's order, cut into runs of `limit`.
+            # Inside a launch the handles go longest first too: on the any-shape form that is roughly the order workgroups are
+            # dispatched in when they outnumber what the device holds, so the longest start first.
+            live = [i for i in range(N) if ns[i] > 1]
+            for n_launch, idx in deal_launches([ns[i] - 1 for i in live], limit, self.batch_longest_first):
+                sel = [live[j] for j in idx]
+                rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._batch_decs[i].value for i in sel]), len(sel),
+                                              (C.c_int32 * len(sel))(*[firsts[i] for i in sel]), ptr_array([rest[i] for i in sel]),
+                                              n_launch, ptr_array([outs[i] for i in sel]), None, same, stream_ptr())
                 if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
-                    return self._generate_batch_loop(n_samples, u_np, prompts, which, temps, top_ks, top_ps, cids, per, phs)
+                    return self._generate_batch_loop(*loop_args)
                 check(rc, "wn_decoder_run_batch")
-            for i in range(N if nine else 1):                         # any-shape: nothing can give up; one synchronise
+            for i in (live if nine else live[:1]):                    # any-shape: nothing can give up; one synchronise
                 check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
             if nine:
-                for i in range(N):
-                    out[i, 1:] = outs[i]
-        return out
+                for i in live:
+                    (res[i] if ragged else out[i])[1:] = outs[i]
+        return res if ragged else out
 
-    def _generate_batch_loop(self, n_samples, u_np, prompts, which, temperature, top_k, top_p, cids, locals_, phases):
+    def _generate_batch_loop(self, n_samples, u_rows, prompts, which, temperature, top_k, top_p, cids, locals_, phases):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
         ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls by
-        definition)."""
-        return torch.stack([self.generate(n_samples, u_np[i], initial_tokens=prompts[which[i]], temperature=temperature[i],
-                                          top_k=top_k[i], top_p=top_p[i], condition=cids[i], local=locals_[i],
-                                          local_phase=phases[i]) for i in range(u_np.shape[0])])
+        definition).  ``n_samples`` a list: a length per utterance, and a list of rows comes back."""
+        ragged = isinstance(n_samples, list)
+        rows = [self.generate(n_samples[i] if ragged else n_samples, u_rows[i], initial_tokens=prompts[which[i]],
+                              temperature=temperature[i], top_k=top_k[i], top_p=top_p[i], condition=cids[i], local=locals_[i],
+                              local_phase=phases[i]) for i in range(len(u_rows))]
+        return rows if ragged else torch.stack(rows)

@@ -54,7 +54,9 @@ _SPEAKER_FLAGS = (
 _LOCAL_FLAGS = (
     (("--local-dir",), str, None, "train: condition on the feature file <local-dir>/NAME.npy of every NAME.wav, a float (F, frames) "
                                   "array with one column per --local-hop samples (python -m wavenet_amd.train_audio.features "
-                                  "writes log-mel ones); F and the hop go to <model-dir>/local.json"),
+                                  "writes log-mel ones); F and the hop go to <model-dir>/local.json.  generate --fast: vocode "
+                                  "every NAME.npy of the directory into <output_dir>/NAME.wav, each at the length its features "
+                                  "cover (-s caps them), in one batched run; excludes --local"),
     (("--local-hop",), int, None, "train --local-dir: samples per feature column (256 unless local.json says otherwise)"),
     (("--local-interp",), str, None, "train --local-dir: how the features reach the sample rate, 'repeat' (a column holds for "
                                      "its hop samples) or 'linear' (interpolated between neighbouring columns, a column anchored "
@@ -130,6 +132,8 @@ def parse(argv=None):
         ap.error("--local-interp {repeat,linear} goes with --local-dir")
     if args.local_crop is not None and (args.local_dir is None or args.local_crop not in ("frame", "sample")):
         ap.error("--local-crop {frame,sample} goes with --local-dir")
+    if args.local and args.local_dir is not None:
+        ap.error("--local-dir FEAT_DIR (every feature file of a directory) and --local FILE.npy exclude each other")
     if args.local:
         n = utterance_prompts(args)[0] or 1
         if len(args.local) not in (1, n):

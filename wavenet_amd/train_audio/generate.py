@@ -2,7 +2,9 @@
 ``int(sampling_rate * seconds) - 1`` samples one at a time from the softmax, write ``<output_dir>/generated.wav``.
 
 Beyond the reference: ``--utterances N`` and ``--prompt FILE.wav`` write ``generated_000.wav`` ... ``generated_{N-1:03d}.wav``,
-each continuing its prompt (or silence); with ``--fast`` all of them in one ``FasterWaveNet.generate_batch`` run."""
+each continuing its prompt (or silence); with ``--fast`` all of them in one ``FasterWaveNet.generate_batch`` run.
+``--fast --local-dir FEAT_DIR`` vocodes a directory: ``<output_dir>/NAME.wav`` for every ``FEAT_DIR/NAME.npy``, each at the
+length its own features cover, all in one ragged ``generate_batch`` run."""
 from __future__ import annotations
 
 import os
@@ -122,6 +124,65 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     return filenames, tokens
 
 
+def directory_job(args, seconds_given):
+    """``generate --fast --local-dir FEAT_DIR``: every check that needs no model, made before one is built.  Returns
+    (names, features as the network takes them, samples to emit per file, class id per file or None)."""
+    what = "generate --local-dir"
+    if not args.fast:
+        raise SystemExit("{}: vocoding a directory is one batched run on the device: give --fast".format(what))
+    if args.utterances is not None or args.prompt or args.speaker:
+        raise SystemExit("{}: one utterance per feature file, from silence, labelled by its file name: --utterances, --prompt "
+                         "and --speaker do not go with it".format(what))
+    config = _local.load_config(args.model_dir)
+    _local.require_match(config, True, "generate", "--local-dir FEAT_DIR")
+    names = _local.directory_features(args.local_dir)
+    # a speaker-conditioned checkpoint labels every file by its name, as evaluate does; an unknown label stops here
+    table = _speakers.load_table(args.model_dir)
+    cids = [_speakers.class_id(table[0], _speakers.speaker_label(name), name + ".npy") for name in names] if table else None
+    params = _model.load_params(args.model_dir)
+    iw = input_width_of(params)
+    cap = int(params.sampling_rate * args.seconds) - 1 if seconds_given else None
+    if cap is not None and cap < 1:
+        raise SystemExit("{}: -s {} asks for {} samples".format(what, args.seconds, cap))
+    interp = _local.load_interp(args.model_dir)
+    feats, lengths = [], []
+    for name in names:
+        f = _local.read_features(os.path.join(args.local_dir, name + ".npy"), config[0])
+        # the rule of one --local file without -s, per file: what the features cover behind the window; -s caps it
+        cover = _local.samples_covered(f.shape[1], config[1], iw)
+        if cover < 1:
+            raise SystemExit("generate: the features of {}.npy cover {} samples, fewer than the {} of the window".format(
+                name, cover + iw - 1, iw))
+        lengths.append(cover if cap is None else min(cover, cap))
+        feats.append(_local.with_extra_column(f, interp))
+    return names, feats, lengths, cids
+
+
+def generate_directory(net, params, names, feats, lengths, cids, seed=None, output_dir="generated_audio", temperature=1.0,
+                       top_k=0, top_p=1.0):
+    """One ragged ``generate_batch`` run over the whole directory, from silence; ``<output_dir>/NAME.wav`` per feature file,
+    each at its own length.  With a seed every file draws what its own ``generate --fast --local NAME.npy`` run draws."""
+    Q = params.quantization_steps
+    sampling.check_controls(temperature, top_k, top_p)
+    silence = np.full((input_width_of(params),), 127 if Q > 127 else Q // 2, dtype=np.int32)
+    uniforms = []
+    for n in lengths:
+        if seed is not None:
+            np.random.seed(seed)
+        uniforms.append(np.random.random_sample(n))
+    start_time = time.time()
+    rows = net.generate_batch(list(lengths), uniforms, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
+                              condition=cids, local=list(feats))
+    tokens = [r.cpu().numpy() for r in rows]
+    print("\ndone in {:.3f} sec".format(time.time() - start_time))
+    os.makedirs(output_dir, exist_ok=True)
+    filenames = []
+    for name, t in zip(names, tokens):
+        filenames.append("{}/{}.wav".format(output_dir, name))
+        data.save_audio_file(filenames[-1], t, Q, format="16bit_pcm", sampling_rate=params.sampling_rate)
+    return filenames, tokens
+
+
 def _seconds_given(argv) -> bool:
     """Whether the command line names -s / --seconds (its default, 1.0, is a length like any other when it is given)."""
     import argparse
@@ -134,6 +195,11 @@ def _seconds_given(argv) -> bool:
 def main(argv=None):
     args = _args.parse(argv)
     seconds_given = _seconds_given(argv)
+    if args.local_dir is not None:
+        names, feats, lengths, cids = directory_job(args, seconds_given)
+        params, net = _model.build(args)
+        return generate_directory(net, params, names, feats, lengths, cids, seed=args.seed, output_dir=args.output_dir,
+                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
     n_utt, prompt_files = _args.utterance_prompts(args)
     # the speaker of every utterance, checked against the checkpoint's table before the model is built: an unknown label,
     # --speaker on an unconditioned checkpoint and its absence on a conditioned one all stop here with a clear message

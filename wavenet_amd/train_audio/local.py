@@ -121,6 +121,22 @@ def directory_channels(feat_dir: str, wav_names) -> int:
     return int(read_features(feature_path(feat_dir, names[0])).shape[0])
 
 
+def directory_features(feat_dir: str):
+    """generate --local-dir: the names NAME of the ``NAME.npy`` files of ``feat_dir``, sorted; stops when there is none."""
+    if not os.path.isdir(feat_dir):
+        raise SystemExit("--local-dir: {} is not a directory".format(feat_dir))
+    names = sorted(fn[:-4] for fn in os.listdir(feat_dir) if fn.endswith(".npy"))
+    if not names:
+        raise SystemExit("--local-dir: no .npy feature file in {}".format(feat_dir))
+    return names
+
+
+def samples_covered(frames: int, hop: int, input_width: int) -> int:
+    """How many samples generation can emit from ``frames`` feature columns: they cover the utterance from its first sample,
+    the window of ``input_width`` samples included, and the first emitted sample is read off the window's last position."""
+    return int(frames) * int(hop) - int(input_width) + 1
+
+
 def padded(features: np.ndarray, pad_samples: int, hop: int) -> Tuple[np.ndarray, int]:
     """Training pads a file with ``pad_samples`` tokens of silence in front; they read the file's column 0.  Returns the
     features with ceil(pad_samples / hop) copies of column 0 in front, and the shift that takes an index into the padded
