@@ -339,3 +339,91 @@ def test_c_abi_refusals_of_the_any_shape_form_touch_nothing():
     for h in hA + hB:
         assert lib.wn_decoder_status(h, None) == _lib.WN_OK
         lib.wn_decoder_destroy(h)
+
+
+_COUNTED = ("wn_decoder_create", "wn_decoder_update_weights", "wn_decoder_load_state", "wn_decoder_run_batch")
+
+
+class _CountingLib(object):
+    """What ``_lib.lib()`` returns, with the decoder-handle entry points counted (every other name is the library's own)."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, dict.fromkeys(_COUNTED, 0)
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in _COUNTED:
+            return fn
+
+        def counted(*a):
+            self.calls[name] += 1
+            return fn(*a)
+        return counted
+
+
+def _handle_calls(monkeypatch):
+    """-> count(net, call): (creates, updates, load_states, launches, prefills) of one call, through a counting proxy of
+    the library and a spy on the net's ``forward_residual_block`` (one call of it per prefill)."""
+    proxy = _CountingLib(_lib.lib())
+    monkeypatch.setattr(_lib, "lib", lambda: proxy)
+
+    def count(net, call):
+        before, prefills, inner = dict(proxy.calls), [0], net.forward_residual_block
+
+        def spy(*a, **kw):
+            prefills[0] += 1
+            return inner(*a, **kw)
+        net.forward_residual_block = spy
+        try:
+            call()
+        finally:
+            del net.forward_residual_block
+        return tuple(proxy.calls[k] - before[k] for k in _COUNTED) + (prefills[0],)
+    return count
+
+
+def test_handles_are_created_once_and_updated_only_when_they_must_be(monkeypatch):
+    """The handle rules, which equality of tokens cannot see (re-packing every handle in every call gives the same tokens):
+    counts of (create, update_weights, load_state, run_batch, prefills) per call, N = 3 and n = 4 on a model of its own."""
+    count = _handle_calls(monkeypatch)
+    net = build(A, cls=FasterWaveNet)[2]
+    N, n = 3, 4
+    rs = np.random.RandomState(81)
+    u = rs.random_sample((N, n))
+    with no_loop(net):
+        assert count(net, lambda: net.generate_batch(n, u)) == (3, 0, 3, 1, 1)             # 1. three handles, created current
+        assert count(net, lambda: net.generate_batch(n, u)) == (0, 0, 3, 1, 1)             # 2. ... and still current
+        net.load_state_dict(net.state_dict())
+        assert count(net, lambda: net.generate_batch(n, u)) == (0, 3, 3, 1, 1)             # 3. new weights: every handle
+        assert count(net, lambda: net.generate_batch([2, 3, 4], u)) == (0, 3, 3, 1, 1)     # 4. a limit each
+        assert count(net, lambda: net.generate_batch(n, u)) == (0, 3, 3, 1, 1)             # 5. the limits come off
+        assert count(net, lambda: net.generate_batch(n, u)) == (0, 0, 3, 1, 1)             # 6. ... once
+        prompts = rs.randint(0, 256, (2, net.input_width)).astype(np.int32)[[0, 1, 0]]
+        assert count(net, lambda: net.generate_batch(n, u, initial_tokens=prompts)) == (0, 0, 3, 1, 2)    # 7. two prompts
+        # 8. nothing decodes: no handle is created for it, nothing is launched
+        fresh = build(A, cls=FasterWaveNet)[2]
+        assert count(fresh, lambda: fresh.generate_batch([1, 1, 1], u)) == (0, 0, 0, 0, 1)
+        assert count(fresh, lambda: fresh.generate_batch(1, u)) == (0, 0, 0, 0, 1)
+        assert len(fresh._batch_decs) == 0 and len(net._batch_decs) == 3
+
+
+def test_another_class_for_one_utterance_updates_that_handle_alone(monkeypatch):
+    """9. a globally conditioned model: a handle holds one class's folded biases, and only a handle whose class changes is
+    packed again."""
+    import cond_ref
+    count = _handle_calls(monkeypatch)
+    p = R.make_params(**cond_ref.TINY)
+    E, V = cond_ref.init_condition(p, seed=99)
+    net = FasterWaveNet(Params(p), seed=0, condition_classes=cond_ref.CLASSES, condition_channels=cond_ref.CHANNELS)
+    net.load_state_dict(cond_ref.state_dict(R.init_weights(p, 1234), E, V))
+    net.to_gpu()
+    u = np.random.RandomState(82).random_sample((3, 4))
+    with no_loop(net):
+        assert count(net, lambda: net.generate_batch(4, u, condition=[0, 2, 1])) == (3, 0, 3, 1, 3)
+        assert count(net, lambda: net.generate_batch(4, u, condition=[0, 2, 1])) == (0, 0, 3, 1, 3)
+        got = [None]
+
+        def call():
+            got[0] = net.generate_batch(4, u, condition=[0, 1, 1])
+        assert count(net, call) == (0, 1, 3, 1, 2)
+    np.testing.assert_array_equal(to_np(got[0][1]), to_np(net.generate(4, u[1], condition=1)))

@@ -154,9 +154,7 @@ def main():
         for lib, m in nets:                                     # a library's handles are destroyed by that library
             if m is not net:
                 use(lib)()
-                for h in m._batch_decs + ([m._dec] if m._dec is not None else []):
-                    lib.wn_decoder_destroy(h)
-                m._batch_decs, m._dec = [], None
+                m.close()
         del nets, sides
         gc.collect()
     use(branch_lib)()

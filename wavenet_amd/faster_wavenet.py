@@ -15,6 +15,8 @@ What a caller can observe:
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -81,6 +83,48 @@ def _ragged_lengths(n_samples, uniforms):
     return ns, [np.ascontiguousarray(rows[i][:ns[i]]) for i in range(N)]
 
 
+def silence_window(params_or_Q, width):
+    """``width`` tokens of silence, what a generation starts from (generate.py:21); ``params_or_Q``: the params or their
+    ``quantization_steps``."""
+    Q = params_or_Q if isinstance(params_or_Q, (int, np.integer)) else params_or_Q.quantization_steps
+    return np.full((width,), 127 if Q > 127 else Q // 2, dtype=np.int32)
+
+
+class _Handle(object):
+    """A decoder handle of the library and what the host knows about it: whether the weights changed since it was packed
+    (``stale``; a handle that holds a step limit stays stale, so that the next call takes the limit off), the class whose
+    folded gate biases it holds, and whether it holds a frame table."""
+
+    def __init__(self):
+        self.h, self.stale, self.class_id, self.has_table = None, True, None, False
+
+    def bring(self, net, class_id, cond_of, table=None, step_limit=None):
+        """Create the handle, or update it when it is stale, holds another class, or is given a table or a limit (the
+        update is the library's one way to set either and to start their step count again; it also re-packs the weights);
+        otherwise nothing.  ``cond_of(class_id)``: the class's folded biases, asked for only when they are packed."""
+        if self.h is not None and not (self.stale or self.class_id != class_id or table is not None or step_limit is not None):
+            return
+        d, keep = net._desc(cond_of(class_id), table, step_limit or 0)
+        if self.h is None:
+            h = C.c_void_p()
+            check(_lib.lib().wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
+            self.h = h
+        else:
+            check(_lib.lib().wn_decoder_update_weights(self.h, C.byref(d), stream_ptr()), "wn_decoder_update_weights")
+        self.stale, self.class_id, self.has_table = bool(step_limit), class_id, self.has_table or table is not None
+
+    def destroy(self):
+        if self.h is not None:
+            _lib.lib().wn_decoder_destroy(self.h)
+            self.h = None
+
+
+# one utterance of a generate_batch call: its length, uniforms, controls, class id, features as the caller gave them and their
+# phase, its window, and ``group`` -- (index of the distinct window, class, index of the distinct feature array by identity,
+# phase): utterances of one group share a prefill
+_Utterance = collections.namedtuple("_Utterance", "n u temperature top_k top_p class_id local phase window group")
+
+
 class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
     batch_longest_first = True         # generate_batch: a launch's handles longest first (deal_launches; False: caller's order)
@@ -88,14 +132,8 @@ class FasterWaveNet(WaveNet):
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
                  condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
                  local_interp: str = "repeat"):
-        self._dec = None
-        self._dec_keep = None
-        self._dec_stale = True
-        self._dec_class = None             # globally conditioned model: the class whose folded biases the handle holds
-        self._batch_decs = []              # decoder handles of generate_batch (one per utterance), created on demand
-        self._batch_stale = []
-        self._batch_class = []
-        self._dec_table = False            # locally conditioned model: whether the batch-1 handle holds a frame table
+        self._dec = _Handle()              # the batch-1 handle
+        self._handles = []                 # generate_batch's handles (one per utterance), created on demand
         self.prev_causal_outputs = None
         self.prev_residual_outputs = None
         self.keep_window = True            # keep the logits of the whole window on the device: _forward_one_step's reference shape
@@ -105,19 +143,36 @@ class FasterWaveNet(WaveNet):
                          condition_classes=condition_classes, condition_channels=condition_channels,
                          local_channels=local_channels, local_hop=local_hop, local_interp=local_interp)
 
+    def close(self):
+        """Destroy every decoder handle (under the library that is loaded now) and forget them."""
+        for h in [self._dec] + self._handles:
+            h.destroy()
+        self._dec, self._handles = _Handle(), []
+
     def __del__(self):
         try:
-            if self._dec is not None:
-                _lib.lib().wn_decoder_destroy(self._dec)
-            for h in getattr(self, "_batch_decs", []):
-                _lib.lib().wn_decoder_destroy(h)
+            self.close()
         except Exception:
             pass
 
+    @property
+    def _batch_decs(self):
+        """generate_batch's raw handles, in creation order."""
+        return [h.h for h in self._handles]
+
     def _weights_changed(self):
         super()._weights_changed()
-        self._dec_stale = True
-        self._batch_stale = [True] * len(getattr(self, "_batch_decs", []))
+        for h in [self._dec] + self._handles:
+            h.stale = True
+
+    @contextlib.contextmanager
+    def _fp32_storage(self):
+        """The decoder state and the first row come from fp32 activations, whatever the model's storage."""
+        storage, self.storage = self.storage, "fp32"
+        try:
+            yield
+        finally:
+            self.storage = storage
 
     # -- decoder handle -------------------------------------------------------------------------
     def _desc(self, cond=None, table=None, step_limit=0):
@@ -207,30 +262,17 @@ class FasterWaveNet(WaveNet):
         """The batch-1 handle; for a conditioned model holding ``class_id``'s biases (default: the class it holds already); for
         a locally conditioned one ``table`` (``_decoder_table``) is copied into it and its step count starts again (default:
         the table it holds, continued)."""
-        lib = _lib.lib()
-        if self.local_channels and table is None and not self._dec_table:
+        dec = self._dec
+        if self.local_channels and table is None and not dec.has_table:
             raise Exception("this model is locally conditioned: prefill with local= first")
         if self.condition_classes and class_id is None:
-            class_id = self._dec_class
+            class_id = dec.class_id
             if class_id is None:
                 raise Exception("this model is globally conditioned: prefill with condition= first")
-        cond = None
-        if self.local_channels and table is None and self._dec_stale:
+        if self.local_channels and table is None and dec.stale:
             raise Exception("the weights changed since the last prefill: prefill with local= again")
-        if self.condition_classes and (self._dec is None or self._dec_stale or self._dec_class != class_id or table is not None):
-            cond = self.condition_biases(class_id)
-        if self._dec is None:
-            d, keep = self._desc(cond, table)
-            h = C.c_void_p()
-            check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
-            self._dec, self._dec_stale, self._dec_class = h, False, class_id
-        elif self._dec_stale or self._dec_class != class_id or table is not None:
-            d, keep = self._desc(cond, table)
-            check(lib.wn_decoder_update_weights(self._dec, C.byref(d), stream_ptr()), "wn_decoder_update_weights")
-            self._dec_stale, self._dec_class = False, class_id
-        if table is not None:
-            self._dec_table = True
-        return self._dec
+        dec.bring(self, class_id, self.condition_biases if self.condition_classes else lambda c: None, table)
+        return dec.h
 
     # -- the reference's face -------------------------------------------------------------------
     def forward_one_step(self, x_batch, apply_softmax=True, as_numpy=False, condition=None, local=None, local_phase=0):
@@ -246,32 +288,42 @@ class FasterWaveNet(WaveNet):
             raise Exception("FasterWaveNet generates one utterance at a time (batch 1), like the reference")
         class_id = self._class_id(condition)
         feats, phase = self._utterance_local(local, local_phase, int(x.shape[1] if x.dim() == 2 else x.shape[3]), 1, "forward_one_step")
-        storage, self.storage = self.storage, "fp32"               # the decoder state is seeded from fp32 activations
-        try:
+        with self._fp32_storage():
             return self._prefill(x, apply_softmax, as_numpy, class_id, feats, phase)
-        finally:
-            self.storage = storage
 
-    def _prefill(self, x, apply_softmax, as_numpy, class_id=None, feats=None, phase=0):
-        with torch.no_grad():
-            causal_output = self.forward_causal_block(x)
+    def _seed(self, tok, class_id, feats, phase, handles, apply_softmax=True):
+        """The one prefill: the forward over a window (tokens or one-hot, batch 1) at fp32 storage -- causal block, residual
+        block, head -- and the state of every handle in ``handles`` (raw ones; or a function giving them, called after the
+        forward) loaded from it.  -> (the head's output over the window, the skip sum)."""
+        with self._fp32_storage(), torch.no_grad():
+            causal_output = self.forward_causal_block(tok)
             _, sum_skip = self.forward_residual_block(causal_output, condition=None if class_id is None else [class_id],
                                                       local=feats, local_phase=phase)
-            out = self.forward_softmax_block(sum_skip, apply_softmax=apply_softmax)
-            self._last_sum_skip = sum_skip                                       # generate(): the first row under a temperature
-            tokens = (x if not x.is_floating_point() else x[:, :, 0, :].argmax(dim=1)).to(torch.int32).contiguous()
-            W = tokens.shape[1]
-            dec = self._decoder(class_id, None if feats is None else self._decoder_table(feats, phase, W))
-            check(_lib.lib().wn_decoder_load_state(
-                dec, ptr(tokens), W, ptr_array([t.contiguous() for t in self._last_causal_outputs]),
-                ptr_array(self._last_layer_inputs), stream_ptr()), "wn_decoder_load_state")
-            self._hist = None
-            if self.keep_window:
-                # the reference's next step re-evaluates EVERY cached column with the fast path's ELU head
-                # (faster_wavenet.py:100-112): the window's logits under that head, once, from the skip sum just computed
+            p0 = self.forward_softmax_block(sum_skip, apply_softmax=apply_softmax)
+        tokens = (tok if not tok.is_floating_point() else tok[:, :, 0, :].argmax(dim=1)).to(torch.int32).contiguous()
+        handles = handles() if callable(handles) else handles
+        if handles:
+            causal_outs = ptr_array([t.contiguous() for t in self._last_causal_outputs])
+            layer_ins = ptr_array(self._last_layer_inputs)
+            for h in handles:
+                check(_lib.lib().wn_decoder_load_state(h, ptr(tokens), tokens.shape[1], causal_outs, layer_ins, stream_ptr()),
+                      "wn_decoder_load_state")
+        return p0, sum_skip
+
+    def _prefill(self, x, apply_softmax, as_numpy, class_id=None, feats=None, phase=0):
+        W = int(x.shape[1] if x.dim() == 2 else x.shape[3])
+        # (the batch-1 handle is created or updated behind the forward: a function)
+        out, sum_skip = self._seed(x, class_id, feats, phase, lambda: [
+            self._decoder(class_id, None if feats is None else self._decoder_table(feats, phase, W))], apply_softmax)
+        self._last_sum_skip = sum_skip                                           # generate(): the first row under a temperature
+        self._hist = None
+        if self.keep_window:
+            # the reference's next step re-evaluates EVERY cached column with the fast path's ELU head
+            # (faster_wavenet.py:100-112): the window's logits under that head, once, from the skip sum just computed
+            with torch.no_grad():
                 lg = self.forward_softmax_block(sum_skip, apply_softmax=False, activation=self.fast_head_activation)
-                self._hist = lg[0, :, 0, :].t().contiguous()                     # (W, Q), column 0 = oldest
-                self._hist_pos = 0
+            self._hist = lg[0, :, 0, :].t().contiguous()                     # (W, Q), column 0 = oldest
+            self._hist_pos = 0
         self.prev_causal_outputs = _RingState("causal")
         self.prev_residual_outputs = _RingState("residual")
         return self.to_numpy(out) if as_numpy else out
@@ -336,12 +388,8 @@ class FasterWaveNet(WaveNet):
         Q = self.params.quantization_steps
         if float(temperature) == 1.0:
             return p0[0, :, 0, -1].contiguous().view(1, Q)
-        storage, self.storage = self.storage, "fp32"
-        try:
-            with torch.no_grad():
-                lg = self.forward_softmax_block(sum_skip, apply_softmax=False)
-        finally:
-            self.storage = storage
+        with self._fp32_storage(), torch.no_grad():
+            lg = self.forward_softmax_block(sum_skip, apply_softmax=False)
         row = (lg[0, :, 0, -1].contiguous().view(1, Q) * float(sampling.inv_temperature(temperature))).contiguous()
         out = torch.empty_like(row)
         check(_lib.lib().wn_softmax_fwd(ptr(row), ptr(out), 1, Q, stream_ptr()), "wn_softmax_fwd")
@@ -364,14 +412,12 @@ class FasterWaveNet(WaveNet):
         ``local`` (locally conditioned models): the utterance's (F, n) features from its first sample on, prompt included;
         ``local_phase``: where that sample lies inside column 0.  Generating more samples than the features cover raises
         before anything runs."""
-        p = self.params
-        Q = p.quantization_steps
-        iw = self.input_width
+        Q = self.params.quantization_steps
         class_id = self._class_id(condition)
         sampling.check_controls(temperature, top_k, top_p)
         top_k, top_p = int(top_k), float(top_p)
         if initial_tokens is None:
-            initial_tokens = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)   # generate.py:21
+            initial_tokens = silence_window(Q, self.input_width)
         tok = torch.as_tensor(np.asarray(initial_tokens, dtype=np.int32).reshape(1, -1)).to(self.device)
         u = torch.as_tensor(np.asarray(uniforms, dtype=np.float64)).to(self.device)
         if u.numel() < n_samples:
@@ -426,7 +472,7 @@ class FasterWaveNet(WaveNet):
         utterance).  Raises on anything but None, one 1-D window or an (N, W) integer array."""
         Q = self.params.quantization_steps
         if initial_tokens is None:
-            return [np.full((self.input_width,), 127 if Q > 127 else Q // 2, dtype=np.int32)], [0] * N    # generate.py:21
+            return [silence_window(Q, self.input_width)], [0] * N
         try:
             a = np.asarray(initial_tokens)
         except ValueError:
@@ -453,57 +499,120 @@ class FasterWaveNet(WaveNet):
 
     def generate_batch(self, n_samples, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
                        condition=None, local=None, local_phase=0):
-        """``n_samples`` an int -- ``uniforms``: (N, n_samples) float64 -- N independent utterances, utterance u drawing with ``uniforms[u]``; returns
-        (N, n_samples) int32 tokens on the device.  ``initial_tokens``: None (silence), one 1-D window for every utterance, or
-        an (N, W) integer array -- a prompt per utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a
-        scalar or one value per utterance.  Row u equals ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's
-        window>, <utterance u's controls>)`` bit for bit.
+        """N independent utterances at once.  ``n_samples`` an int: ``uniforms`` is (N, >= n_samples) float64, utterance u draws
+        with ``uniforms[u]``, and (N, n_samples) int32 tokens on the device come back.  ``n_samples`` a sequence of N positive
+        ints -- a length per utterance: ``uniforms`` is an (N, >= max) array or a list of N 1-D arrays, and a LIST of N 1-D int32
+        device tensors comes back, tensor u of length ``n_samples[u]``.  Either way row u equals ``generate(<u's length>,
+        <u's uniforms>, initial_tokens=<u's window>, <u's controls, class, features, phase>)`` bit for bit.
+
+        ``initial_tokens``: None (silence), one 1-D window for every utterance, or an (N, W) integer array -- a prompt per
+        utterance.  ``temperature`` / ``top_k`` / ``top_p``: as for ``generate``, each a scalar or one value per utterance.
+        ``condition`` (globally conditioned models): one class id for all utterances or one each -- a voice per utterance.
+        ``local`` / ``local_phase`` (locally conditioned models): one (F, n) array for all utterances or a list of one per
+        utterance, each covering its utterance from its first sample on, prompt included; the phases likewise.  Whatever is
+        wrong with the arguments -- the features not covering an utterance's own length included -- raises before any device
+        work; with a length per utterance the message names the first such utterance.
 
         A single utterance is a strict sample-to-sample chain (generate.py:9-60, batch 1: wavenet.py:286,290,354); the
-        batched launch (``wn_decoder_run_batch``) runs such chains side by side, each with a decoder state of its own: nine
+        batched launch (``wn_decoder_run_batch``) runs such chains side by side, each with a decoder handle of its own: nine
         workgroups per utterance and up to ``wn_decoder_batch_max()`` = 28 utterances per launch for config 4's shape, one
         workgroup per utterance and up to ``WN_DECODER_BATCH_MAX_ANY`` for every other model (any channels, filter widths,
-        causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``).  More utterances run as several launches, one after
-        another.  Step 1 -- the full forward over the window, at batch 1 exactly as ``generate`` runs it -- runs once per
-        DISTINCT window.  What still runs as a loop over ``generate()``, decided before any work: ``WN_DECODER_ONE_WORKGROUP``,
-        ``n_samples == 2`` on the nine-workgroup form, and a device the nine-workgroup launch does not fit.
+        causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``; a conditioned model of config 4's shape too: its
+        handles hold gate biases or a frame table).  More utterances run as several launches, one after another, dealt
+        longest first (``deal_launches``): a launch's step count is its longest utterance's, and with a length per utterance
+        every handle carries ``step_limit`` = its own ``n_samples[u] - 1`` and its workgroups end there.  An utterance of
+        length 1 decodes nothing and joins no launch.  Step 1 -- the full forward over the window, at batch 1 exactly as
+        ``generate`` runs it -- runs once per distinct (window, class, features, phase).  What still runs as a loop over
+        ``generate()``: ``WN_DECODER_ONE_WORKGROUP``, any utterance of length 2 on the nine-workgroup form, and a device the
+        nine-workgroup launch does not fit."""
+        ragged = not isinstance(n_samples, (int, np.integer))
+        recs, feats = self._batch_plan(n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase)
+        N, Q, lib = len(recs), self.params.quantization_steps, _lib.lib()
+        # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
+        # decided BEFORE any work is done
+        flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        nine = self._nine_workgroup_shape(flags)
+        if nine and (any(r.n == 2 for r in recs) or flags & _lib.WN_DECODER_ONE_WORKGROUP):
+            return self._generate_batch_loop(recs, ragged)
+        limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
+        live = [i for i in range(N) if recs[i].n > 1]                  # the utterances that decode at all
+        # a result is a 1-D tensor per utterance, its uniforms likewise: rows of one (N, n) tensor and of one upload for
+        # equal lengths, tensors and uploads of their own otherwise.  (Every upload here, ahead of the device work: one
+        # behind the prefills would have the host wait for them.)
+        if ragged:
+            u_dev = [torch.as_tensor(r.u).to(self.device) for r in recs]
+            u0 = torch.as_tensor(np.array([r.u[0] for r in recs], dtype=np.float64)).to(self.device)
+            res = [torch.empty((r.n,), device=self.device, dtype=torch.int32) for r in recs]
+        else:
+            u = torch.as_tensor(np.stack([r.u for r in recs])).to(self.device)
+            u_dev, u0 = list(u), u[:, 0].contiguous()
+            out = torch.empty((N, recs[0].n), device=self.device, dtype=torch.int32)
+            res = list(out)
+        if live:
+            self._batch_handles(recs, feats, ragged)
+        # one prefill per group, at batch 1 as generate() runs it; the decoder states of its utterances are seeded from it,
+        # and its first row (one per distinct temperature) is what generate() draws the first token from
+        self.prev_causal_outputs = None
+        rows = {}
+        for g in sorted({r.group for r in recs}, key=lambda g: (g[0], -1 if g[1] is None else g[1], g[2], g[3])):
+            mine = [i for i in range(N) if recs[i].group == g]
+            r = recs[mine[0]]
+            tok = torch.as_tensor(r.window.reshape(1, -1)).to(self.device)
+            p0, sum_skip = self._seed(tok, r.class_id, feats[g][0], r.phase, [self._handles[i].h for i in mine] if live else [])
+            for t in sorted({recs[i].temperature for i in mine}):
+                rows[g + (t,)] = self._first_row(sum_skip, p0, t)
+        first_rows = [rows[r.group + (r.temperature,)] for r in recs]
+        first = torch.empty((N,), device=self.device, dtype=torch.int32)
+        if all(sampling.controls_off(r.temperature, r.top_k, r.top_p, Q) for r in recs):
+            first_prob = torch.cat(first_rows, dim=0).contiguous()
+            check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
+        else:
+            for i, r in enumerate(recs):                             # the truncation per utterance, as generate() draws
+                check(lib.wn_sample_categorical_filtered(ptr(first_rows[i]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1, Q,
+                                                         r.top_k, r.top_p, stream_ptr()), "wn_sample_categorical_filtered")
+        if ragged:
+            for i in range(N):
+                res[i][:1] = first[i:i + 1]
+        else:
+            out[:, 0] = first                                        # (one copy: a copy per row costs 20 us a row)
+        if live:
+            firsts = [int(v) for v in first.cpu().tolist()]
+            # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
+            outs = [torch.empty((r.n - 1,), device=self.device, dtype=torch.int32) if nine else res[i][1:] for i, r in enumerate(recs)]
+            same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
+            if len({r.class_id for r in recs}) > 1:
+                same = 0                                              # ... but hold different classes' biases
+            if self.local_channels and len({r.group[:1] + r.group[2:] for r in recs}) > 1:
+                same = 0                                              # ... or different frame tables
+            # launches of at most `limit` utterances, one after another; a launch's handles go longest first: on the any-shape
+            # form that is roughly the order workgroups are dispatched in when they outnumber what the device holds
+            for n_launch, idx in deal_launches([recs[i].n - 1 for i in live], limit, self.batch_longest_first):
+                sel = [live[j] for j in idx]
+                rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._handles[i].h.value for i in sel]), len(sel),
+                                              (C.c_int32 * len(sel))(*[firsts[i] for i in sel]), ptr_array([u_dev[i][1:] for i in sel]),
+                                              n_launch, ptr_array([outs[i] for i in sel]), None, same, stream_ptr())
+                if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
+                    return self._generate_batch_loop(recs, ragged)
+                check(rc, "wn_decoder_run_batch")
+            for i in (live if nine else live[:1]):                    # any-shape: nothing can give up; one synchronise
+                check(lib.wn_decoder_status(self._handles[i].h, stream_ptr()), "wn_decoder_status")
+            if nine:
+                for i in live:
+                    res[i][1:] = outs[i]
+        return res if ragged else out
 
-        ``condition`` (globally conditioned models): one class id for all utterances or one each -- a voice per utterance.
-        Every handle owns its packed weights, so utterance u's handle simply holds ``condition_biases(condition[u])``; such
-        handles are any-shape ones (one workgroup per utterance, up to 1,024 per launch -- a conditioned model of config 4's
-        shape does not get the nine-workgroup kernel), one prefill runs per distinct (window, class) pair, and
-        ``same_weights`` is 0 when the ids differ.
-
-        ``local`` / ``local_phase`` (locally conditioned models): one (F, n) array for all utterances or a list of one per
-        utterance, each covering its utterance from its first sample on, prompt included; the phases likewise.  Every
-        handle copies its utterance's table, one prefill runs per distinct (window, class, features, phase), and
-        ``same_weights`` is 0 when the tables differ.
-
-        A length per utterance: ``n_samples`` a sequence of N positive ints, ``uniforms`` an (N, >= max) array or a list of N
-        1-D arrays (utterance u needs ``n_samples[u]`` values).  Returns a LIST of N 1-D int32 device tensors, tensor u of length
-        ``n_samples[u]`` and equal, bit for bit, to ``generate(n_samples[u], uniforms[u][:n_samples[u]], initial_tokens=<u's
-        window>, <u's controls, class, features, phase>)``; the features are checked per utterance against its own length.
-        A wrong number of lengths, a non-integer or non-positive one, too few uniforms or features that do not cover an
-        utterance raise before any device work, naming the first such utterance.  The utterances are dealt to launches longest
-        first (``deal_launches``): a launch's step count is its longest utterance's, every handle carries ``step_limit`` =
-        its own ``n_samples[u] - 1`` and its workgroups end there.  An utterance of length 1 decodes nothing and joins no
-        launch; on the nine-workgroup form any utterance of length 2 sends the whole call to the loop over ``generate()``,
-        as ``n_samples == 2`` does.  An int ``n_samples`` is the call it always was (no limit on any handle)."""
-        p = self.params
-        Q = p.quantization_steps
+    def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase):
+        """``generate_batch``'s arguments -> (one ``_Utterance`` per utterance, {group: (features on the device or None,
+        phase)}), every check that needs no decoder made, in the order the messages always came in."""
         ragged = not isinstance(n_samples, (int, np.integer))
         if ragged:
             ns, u_rows = _ragged_lengths(n_samples, uniforms)
-            N = len(ns)
-            u_np = None
         else:
-            u_np = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
-            if u_np.ndim != 2 or u_np.shape[1] < n_samples:
+            u_rows = np.ascontiguousarray(np.asarray(uniforms, dtype=np.float64))
+            if u_rows.ndim != 2 or u_rows.shape[1] < n_samples:
                 raise Exception("uniforms must be (N, >= n_samples)")
-            N = u_np.shape[0]
-            ns, u_rows = [int(n_samples)] * N, u_np
-            n_samples = int(n_samples)
-        lib = _lib.lib()
+            ns = [int(n_samples)] * u_rows.shape[0]
+        N = len(ns)
         temps = [float(t) for t in sampling.per_utterance(temperature, N, "temperature")]
         top_ks = [int(k) for k in sampling.per_utterance(top_k, N, "top_k")]
         top_ps = [float(v) for v in sampling.per_utterance(top_p, N, "top_p")]
@@ -521,7 +630,6 @@ class FasterWaveNet(WaveNet):
         else:
             self._condition_ids(condition, N)                                     # raises when ids were given
             cids = [None] * N
-        # local conditioning: utterance i's features are locs[lid[i]] (distinct arrays, by identity) at phase phs[i]
         if isinstance(local, (list, tuple)):
             if len(local) != N:
                 raise Exception("generate_batch: local= holds %d feature arrays for %d utterances" % (len(local), N))
@@ -529,151 +637,48 @@ class FasterWaveNet(WaveNet):
         else:
             per = [local] * N
         phs = [int(v) for v in sampling.per_utterance(local_phase, N, "local_phase")]
-        locs, lid, seen_l = [], [], {}
-        for i in range(N):
-            if id(per[i]) not in seen_l:
-                seen_l[id(per[i])] = len(locs)
-                locs.append(per[i])
-            lid.append(seen_l[id(per[i])])
-        W_of = [int(prompts[k].shape[0]) for k in which]
-        lfeats, covered = {}, {}
-        for i in range(N):                                                    # every check before any work
-            key = (which[i], lid[i], phs[i])
-            # (the features are checked against each utterance's own length: again only for a longer utterance than the
-            # key's longest so far, so the first utterance they do not cover is the one that raises)
-            if key not in lfeats or ns[i] > covered[key]:
+        seen = {}                                                                 # the distinct feature arrays, by identity
+        recs = [_Utterance(ns[i], u_rows[i], temps[i], top_ks[i], top_ps[i], cids[i], per[i], phs[i], prompts[which[i]],
+                           (which[i], cids[i], seen.setdefault(id(per[i]), len(seen)), phs[i])) for i in range(N)]
+        # the features are checked against each utterance's own length: again only for a longer utterance than the longest so
+        # far of the same (window, features, phase), so the first utterance they do not cover is the one that raises
+        checked, covered = {}, {}
+        for i, r in enumerate(recs):
+            key = r.group[:1] + r.group[2:]
+            if key not in checked or r.n > covered[key]:
                 try:
-                    lfeats[key] = self._utterance_local(locs[lid[i]], phs[i], W_of[i], ns[i], "generate_batch")
+                    checked[key] = self._utterance_local(r.local, r.phase, len(r.window), r.n, "generate_batch")
                 except Exception as e:
                     if not ragged:
                         raise
                     raise Exception("generate_batch: utterance %d: %s" % (i, e))
-                covered[key] = ns[i]
-        # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
-        # decided BEFORE any work is done
-        flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
-        nine = self._nine_workgroup_shape(flags)
-        loop_args = (ns if ragged else n_samples, u_rows, prompts, which, temps, top_ks, top_ps, cids, per, phs)
-        if nine and (any(n == 2 for n in ns) or flags & _lib.WN_DECODER_ONE_WORKGROUP):
-            return self._generate_batch_loop(*loop_args)
-        limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
-        if ragged:
-            u_dev = [torch.as_tensor(r).to(self.device) for r in u_rows]
-        else:
-            u = torch.as_tensor(u_np).to(self.device)
-        run = max(ns) > 1
-        # a ragged call: every handle ends after its own utterance's decode steps (the first sample comes from the prefill)
-        limits = [n - 1 if ragged else 0 for n in ns]
-        biases = {c: self.condition_biases(c) for c in sorted(set(cids))} if run and self.condition_classes else {None: None}
-        fresh = set()                                     # handles created in this call hold their weights and table already
-        while run and len(self._batch_decs) < N:
-            i = len(self._batch_decs)
-            fresh.add(i)
-            c = cids[i]
-            ft, ph = lfeats[(which[i], lid[i], phs[i])]       # (a handle is created WITH its table: that selects the any-shape decoder)
-            d, keep = self._desc(biases[c], None if ft is None else self._decoder_table(ft, ph, W_of[i]), limits[i])
-            h = C.c_void_p()
-            check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
-            self._batch_decs.append(h)
-            self._batch_stale.append(False)
-            self._batch_class.append(c)
-        for i in range(N if run else 0):
-            # (a locally conditioned model's other handles are updated in every call: the table and its step count belong to the
-            # utterance, and the library's one way to set them is wn_decoder_update_weights, which also re-packs the weights)
-            # (a ragged call updates them all as well: the update is the library's one way to set a step limit and to start its
-            # count again.  A handle that holds a limit stays marked stale, so that a later int call takes the limit off.)
-            if i not in fresh and (self._batch_stale[i] or self._batch_class[i] != cids[i] or self.local_channels or ragged):
-                ft, ph = lfeats[(which[i], lid[i], phs[i])]
-                d, keep = self._desc(biases[cids[i]], None if ft is None else self._decoder_table(ft, ph, W_of[i]), limits[i])
-                check(lib.wn_decoder_update_weights(self._batch_decs[i], C.byref(d), stream_ptr()), "wn_decoder_update_weights")
-                self._batch_stale[i], self._batch_class[i] = False, cids[i]
-            if limits[i]:
-                self._batch_stale[i] = True
-            check(lib.wn_decoder_set_sampling(self._batch_decs[i], temps[i], top_ks[i], top_ps[i]), "wn_decoder_set_sampling")
-        # one prefill per distinct window, at batch 1 as generate() runs it; the decoder states of its utterances are seeded
-        # from it, and its first row (one per distinct temperature) is what generate() draws the first token from
-        self.prev_causal_outputs = None
-        rows = {}
-        for k, cid, li, ph in sorted({(which[i], cids[i], lid[i], phs[i]) for i in range(N)},
-                                     key=lambda kc: (kc[0], -1 if kc[1] is None else kc[1], kc[2], kc[3])):
-            prompt = prompts[k]
-            ft = lfeats[(k, li, ph)][0]
-            tok = torch.as_tensor(prompt.reshape(1, -1)).to(self.device)
-            storage, self.storage = self.storage, "fp32"
-            try:
-                with torch.no_grad():
-                    causal_output = self.forward_causal_block(tok)
-                    _, sum_skip = self.forward_residual_block(causal_output, condition=None if cid is None else [cid],
-                                                              local=ft, local_phase=ph)
-                    p0 = self.forward_softmax_block(sum_skip, apply_softmax=True)
-            finally:
-                self.storage = storage
-            tokens = tok.to(torch.int32).contiguous()
-            mine = [i for i in range(N) if which[i] == k and cids[i] == cid and lid[i] == li and phs[i] == ph]
-            if run:
-                causal_outs = ptr_array([t.contiguous() for t in self._last_causal_outputs])
-                layer_ins = ptr_array(self._last_layer_inputs)
-                for i in mine:
-                    check(lib.wn_decoder_load_state(self._batch_decs[i], ptr(tokens), tokens.shape[1], causal_outs, layer_ins,
-                                                    stream_ptr()), "wn_decoder_load_state")
-            for t in sorted({temps[i] for i in mine}):
-                rows[(k, cid, li, ph, t)] = self._first_row(sum_skip, p0, t)
-        if ragged:
-            res = [torch.empty((ns[i],), device=self.device, dtype=torch.int32) for i in range(N)]
-            u0 = torch.as_tensor(np.array([r[0] for r in u_rows], dtype=np.float64)).to(self.device)
-        else:
-            out = torch.empty((N, n_samples), device=self.device, dtype=torch.int32)
-            u0 = u[:, 0].contiguous()
-        first = torch.empty((N,), device=self.device, dtype=torch.int32)
-        if all(sampling.controls_off(temps[i], top_ks[i], top_ps[i], Q) for i in range(N)):
-            first_prob = torch.cat([rows[(which[i], cids[i], lid[i], phs[i], temps[i])] for i in range(N)], dim=0).contiguous()
-            check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
-        else:
-            for i in range(N):                                       # the truncation per utterance, as generate() draws
-                check(lib.wn_sample_categorical_filtered(ptr(rows[(which[i], cids[i], lid[i], phs[i], temps[i])]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1,
-                                                         Q, top_ks[i], top_ps[i], stream_ptr()), "wn_sample_categorical_filtered")
-        if ragged:
-            for i in range(N):
-                res[i][:1] = first[i:i + 1]
-        else:
-            out[:, 0] = first
-        if run:
-            firsts = [int(v) for v in first.cpu().tolist()]
-            rest = [u_dev[i][1:] if ragged else u[i, 1:].contiguous() for i in range(N)]
-            # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
-            outs = [torch.empty((ns[i] - 1,), device=self.device, dtype=torch.int32) if nine else
-                    (res[i][1:] if ragged else out[i, 1:]) for i in range(N)]
-            same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
-            if len(set(cids)) > 1:
-                same = 0                                              # ... but hold different classes' biases
-            if self.local_channels and len({(which[i], lid[i], phs[i]) for i in range(N)}) > 1:
-                same = 0                                              # ... or different frame tables
-            # launches of at most `limit` utterances, one after another: the utterances that decode at all (length 1 is the
-            # prefill's sample alone), dealt longest first -- equal lengths: the caller's order, cut into runs of `limit`.
-            # Inside a launch the handles go longest first too: on the any-shape form that is roughly the order workgroups are
-            # dispatched in when they outnumber what the device holds, so the longest start first.
-            live = [i for i in range(N) if ns[i] > 1]
-            for n_launch, idx in deal_launches([ns[i] - 1 for i in live], limit, self.batch_longest_first):
-                sel = [live[j] for j in idx]
-                rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._batch_decs[i].value for i in sel]), len(sel),
-                                              (C.c_int32 * len(sel))(*[firsts[i] for i in sel]), ptr_array([rest[i] for i in sel]),
-                                              n_launch, ptr_array([outs[i] for i in sel]), None, same, stream_ptr())
-                if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
-                    return self._generate_batch_loop(*loop_args)
-                check(rc, "wn_decoder_run_batch")
-            for i in (live if nine else live[:1]):                    # any-shape: nothing can give up; one synchronise
-                check(lib.wn_decoder_status(self._batch_decs[i], stream_ptr()), "wn_decoder_status")
-            if nine:
-                for i in live:
-                    (res[i] if ragged else out[i])[1:] = outs[i]
-        return res if ragged else out
+                covered[key] = r.n
+        return recs, {r.group: checked[r.group[:1] + r.group[2:]] for r in recs}
 
-    def _generate_batch_loop(self, n_samples, u_rows, prompts, which, temperature, top_k, top_p, cids, locals_, phases):
+    def _batch_handles(self, recs, feats, ragged):
+        """A handle per utterance with its sampling controls, holding its class's biases, its frame table and, in a ragged
+        call, its step limit (its decode steps: the first sample comes from the prefill).  Tables and limits belong to the
+        utterance, so such handles are updated in every call; a handle created here holds all of it already."""
+        lib = _lib.lib()
+        biases = {c: self.condition_biases(c) for c in sorted({r.class_id for r in recs})} if self.condition_classes else {None: None}
+
+        def bring(h, r):
+            ft, ph = feats[r.group]       # (a handle is created WITH its table: that selects the any-shape decoder)
+            h.bring(self, r.class_id, biases.get, None if ft is None else self._decoder_table(ft, ph, len(r.window)),
+                    r.n - 1 if ragged else None)
+        held = len(self._handles)
+        for r in recs[held:]:
+            self._handles.append(_Handle())
+            bring(self._handles[-1], r)
+        for i, r in enumerate(recs):
+            if i < held:
+                bring(self._handles[i], r)
+            check(lib.wn_decoder_set_sampling(self._handles[i].h, r.temperature, r.top_k, r.top_p), "wn_decoder_set_sampling")
+
+    def _generate_batch_loop(self, recs, ragged):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
-        ``generate(n_samples, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls by
-        definition).  ``n_samples`` a list: a length per utterance, and a list of rows comes back."""
-        ragged = isinstance(n_samples, list)
-        rows = [self.generate(n_samples[i] if ragged else n_samples, u_rows[i], initial_tokens=prompts[which[i]],
-                              temperature=temperature[i], top_k=top_k[i], top_p=top_p[i], condition=cids[i], local=locals_[i],
-                              local_phase=phases[i]) for i in range(len(u_rows))]
+        ``generate(<utterance u's length>, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls
+        by definition); ``ragged``: a list of rows comes back."""
+        rows = [self.generate(r.n, r.u, initial_tokens=r.window, temperature=r.temperature, top_k=r.top_k, top_p=r.top_p,
+                              condition=r.class_id, local=r.local, local_phase=r.phase) for r in recs]
         return rows if ragged else torch.stack(rows)

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import data, sampling
+from ..faster_wavenet import silence_window
 from . import args as _args
 from . import local as _local
 from . import model as _model
@@ -55,13 +56,23 @@ def _host_loop(net, window, n, sampling_rate, generate_sec, temperature, top_k, 
     return buf[iw:]
 
 
+def _save(start_time, output_dir, Q, sampling_rate, named):
+    """Report the time since ``start_time``, make the directory and write ``<output_dir>/<name>.wav`` for every (name, tokens)
+    pair; returns the file names."""
+    print("\ndone in {:.3f} sec".format(time.time() - start_time))
+    os.makedirs(output_dir, exist_ok=True)
+    filenames = ["{}/{}.wav".format(output_dir, name) for name, _ in named]
+    for filename, (_, tokens) in zip(filenames, named):
+        data.save_audio_file(filename, tokens, Q, format="16bit_pcm", sampling_rate=sampling_rate)
+    return filenames
+
+
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
                    temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None):
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
-    iw = input_width_of(params)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
-    silence = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)
+    silence = silence_window(Q, input_width_of(params))
     start_time = time.time()
     if n <= 0:
         tokens = np.zeros((0,), np.int32)
@@ -73,11 +84,7 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
                               condition=condition, **lkw).cpu().numpy()
     else:
         tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition, local)
-    print("\ndone in {:.3f} sec".format(time.time() - start_time))
-    os.makedirs(output_dir, exist_ok=True)
-    filename = "{}/generated.wav".format(output_dir)
-    data.save_audio_file(filename, tokens, Q, format="16bit_pcm", sampling_rate=sampling_rate)
-    return filename, tokens
+    return _save(start_time, output_dir, Q, sampling_rate, [("generated", tokens)])[0], tokens
 
 
 def read_prompt(path, params):
@@ -87,8 +94,7 @@ def read_prompt(path, params):
     iw = input_width_of(params)
     tokens, _ = data.load_audio_file(path, quantization_steps=Q)
     tokens = np.asarray(tokens, dtype=np.int32)[-iw:]
-    silence = 127 if Q > 127 else Q // 2
-    return np.concatenate([np.full((iw - tokens.size,), silence, dtype=np.int32), tokens])
+    return np.concatenate([silence_window(Q, iw - tokens.size), tokens])
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
@@ -97,10 +103,9 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
-    iw = input_width_of(params)
     N = len(prompt_files)
     n = int(sampling_rate * generate_sec) - 1
-    silence = np.full((iw,), 127 if Q > 127 else Q // 2, dtype=np.int32)
+    silence = silence_window(Q, input_width_of(params))
     read = {f: read_prompt(f, params) for f in set(prompt_files) if f is not None}
     prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
     start_time = time.time()
@@ -115,13 +120,7 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
         tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p,
                                       None if conditions is None else conditions[i],
                                       None if locals_ is None else locals_[i]) for i in range(N)])
-    print("\ndone in {:.3f} sec".format(time.time() - start_time))
-    os.makedirs(output_dir, exist_ok=True)
-    filenames = []
-    for i in range(N):
-        filenames.append("{}/generated_{:03d}.wav".format(output_dir, i))
-        data.save_audio_file(filenames[-1], tokens[i], Q, format="16bit_pcm", sampling_rate=sampling_rate)
-    return filenames, tokens
+    return _save(start_time, output_dir, Q, sampling_rate, [("generated_{:03d}".format(i), tokens[i]) for i in range(N)]), tokens
 
 
 def directory_job(args, seconds_given):
@@ -164,7 +163,7 @@ def generate_directory(net, params, names, feats, lengths, cids, seed=None, outp
     each at its own length.  With a seed every file draws what its own ``generate --fast --local NAME.npy`` run draws."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
-    silence = np.full((input_width_of(params),), 127 if Q > 127 else Q // 2, dtype=np.int32)
+    silence = silence_window(Q, input_width_of(params))
     uniforms = []
     for n in lengths:
         if seed is not None:
@@ -174,13 +173,7 @@ def generate_directory(net, params, names, feats, lengths, cids, seed=None, outp
     rows = net.generate_batch(list(lengths), uniforms, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
                               condition=cids, local=list(feats))
     tokens = [r.cpu().numpy() for r in rows]
-    print("\ndone in {:.3f} sec".format(time.time() - start_time))
-    os.makedirs(output_dir, exist_ok=True)
-    filenames = []
-    for name, t in zip(names, tokens):
-        filenames.append("{}/{}.wav".format(output_dir, name))
-        data.save_audio_file(filenames[-1], t, Q, format="16bit_pcm", sampling_rate=params.sampling_rate)
-    return filenames, tokens
+    return _save(start_time, output_dir, Q, params.sampling_rate, list(zip(names, tokens))), tokens
 
 
 def _seconds_given(argv) -> bool:
