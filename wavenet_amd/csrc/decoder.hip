@@ -13,6 +13,7 @@
 // Weights are re-packed once per handle into transposed form (consecutive threads read consecutive
 // addresses): gate  WfgT[k*Cr+c][o2]  (o2 < 2Cd: filter then gate),  projections  WpsT[cd][o]
 // (o < Cr+Cs: residual rows then skip rows), head  WhT[ci][co], first causal layer W0t[q][k][c].
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -24,12 +25,14 @@ namespace wn {
 
 static constexpr int kDecThreads = 512;
 
+// local conditioning: the handle's own compact copy of the table -- n rows (room for cap) of `row` floats --, hop, phase, mode
+struct FrameTable { float* tab; int cap, n, hop, phase, row, interp; };
+
 struct Decoder {
     DecMeta meta{};
     std::vector<DecCausal> causal;
     std::vector<DecLayer> layers;
     std::vector<DecHead> heads;
-    std::vector<int> causal_ch, cd, head_ch;
     float* arena = nullptr;       // packed weights + rings
     long long arena_floats = 0;
     int* tok_ring = nullptr;      // fwc-1 previous tokens
@@ -50,10 +53,7 @@ struct Decoder {
     void* batch_img = nullptr;
     int batch_cap = 0;
     hipEvent_t batch_copied = nullptr;
-    // local conditioning (WnDecoderDesc.frame_bias): the handle's own compact copy of the table -- n_frames rows of frame_row
-    // floats (sum_l 2 cd_l) --, its hop and phase
-    float* frame_tab = nullptr;
-    int frame_cap = 0, n_frames = 0, frame_hop = 0, frame_phase = 0, frame_row = 0, frame_interp = 0;
+    FrameTable frames{};          // local conditioning (WnDecoderDesc.frame_bias); n == 0: none
     // steps run since the last create / update call -- the call that sets the frame table AND the step limit, so one counter
     // serves both: the table row of a step and the steps left under WnDecoderDesc.step_limit (0: no limit)
     long long since_set = 0;
@@ -84,16 +84,6 @@ static SampleCtl launch_ctl(const Decoder* D) {
     SampleCtl c = D->ctl;
     if (c.top_k >= D->meta.Q) c.top_k = 0;
     return c;
-}
-
-// one utterance's launch arguments of the specialised kernels (decoder_fast.hip), from its handle
-static DecUtt fast_utt(const Decoder* D, int first_token, const double* uniforms, int32_t* out_tokens, float* prob_out,
-                       const SampleCtl& sc) {
-    DecUtt q{};
-    q.P = D->fastP; q.hbias = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
-    q.E = D->arena + D->causal[0].w; q.layers = D->d_layers; q.arena = D->arena; q.tok_ring = D->tok_ring; q.n0 = D->step;
-    q.uniforms = uniforms; q.out_tokens = out_tokens; q.prob_out = prob_out; q.first_token = first_token; q.sc = sc;
-    return q;
 }
 
 // ---- packing ---------------------------------------------------------------------------------
@@ -141,11 +131,20 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 
 // ---- the step loop ---------------------------------------------------------------------------
 // Local conditioning: the frame table of one utterance as the step loop takes it.  tab == NULL: no table, and the loop
-// executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the handle's
-// frame_phase + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
+// executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the table's
+// phase (FrameTable) + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
 // interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
 // float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
 struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
+// One utterance as the any-shape kernels take it, from its own handle (any_utt): k_decode's arguments, and an entry of the
+// table k_decode_batch reads from device memory (Decoder::batch_tab of handle 0).
+struct DecAnyUtt {
+    const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
+    float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
+    int first_token; int nsteps;       // nsteps: the utterance's own step count (batched: min(n, steps left under its step_limit))
+    SampleCtl sc;
+    DecFrames fr;
+};
 __device__ __forceinline__ int pmod(long long a, int D) {
     long long r = a % D;
     return (int)(r < 0 ? r + D : r);
@@ -342,16 +341,6 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
                  apply_softmax, do_sample, sc, fr);
 }
 
-// One utterance of the batched any-shape launch: what k_decode takes as arguments, from the utterance's own handle.  The
-// table of them lives in device memory (Decoder::batch_tab of handle 0).
-struct DecAnyUtt {
-    const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
-    float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
-    int first_token; int nsteps;       // nsteps: the utterance's own step count, min(n, steps left under its step_limit)
-    SampleCtl sc;
-    DecFrames fr;
-};
-
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
 // never wait for each other, so any number of them may be queued behind the CUs -- and each runs its utterance's own step
 // count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.
@@ -385,42 +374,31 @@ static inline long long align64(long long x) { return (x + 63) & ~63ll; }
 
 // ---- local conditioning: the handle's frame table ----------------------------------------------
 static DecFrames launch_frames(const Decoder* D) {
+    const FrameTable& F = D->frames;
     DecFrames f{};
-    if (D->n_frames > 0) {
-        f.tab = D->frame_tab; f.hop = D->frame_hop; f.row = D->frame_row; f.pos0 = D->frame_phase + D->since_set;
-        f.interp = D->frame_interp;
-    }
+    if (F.n > 0) { f.tab = F.tab; f.hop = F.hop; f.row = F.row; f.pos0 = F.phase + D->since_set; f.interp = F.interp; }
     return f;
 }
-static bool lerp_table(const Decoder* D) { return D->n_frames > 0 && D->frame_interp != 0; }   // the LERP kernels
-// n more steps must not read past row n_frames - 1 (refused before any device work; no clamping)
+static bool lerp_table(const Decoder* D) { return D->frames.n > 0 && D->frames.interp != 0; }   // the LERP kernels
+static int row_width(const Decoder* D) {           // floats of one table row: the sum of 2 cd over the layers
+    int row = 0;
+    for (const DecLayer& L : D->layers) row += 2 * L.cd;
+    return row;
+}
+// n more steps must not read past row frames.n - 1 (refused before any device work; no clamping)
 static int check_frames(const char* fn, const Decoder* D, long long n) {
-    if (D->n_frames <= 0) return WN_OK;
+    const FrameTable& F = D->frames;
+    if (F.n <= 0) return WN_OK;
     // (linear interpolation: the last step reads row j + 1 as well)
-    const long long last = (D->frame_phase + D->since_set + n - 1) / D->frame_hop + (D->frame_interp ? 1 : 0);
-    WN_CHECK_ARG(last < D->n_frames, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
-                                     "run on it%s)", fn, n, last, D->n_frames, D->frame_hop, D->frame_phase, D->since_set,
-                 D->frame_interp ? "; linear interpolation reads the row after the step's own" : "");
+    const long long last = (F.phase + D->since_set + n - 1) / F.hop + (F.interp ? 1 : 0);
+    WN_CHECK_ARG(last < F.n, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
+                             "run on it%s)", fn, n, last, F.n, F.hop, F.phase, D->since_set,
+                 F.interp ? "; linear interpolation reads the row after the step's own" : "");
     return WN_OK;
-}
-// WnDecoderDesc.step_limit: n more steps must not pass it.  The single-utterance entry points refuse before any device work
-// and never clamp -- the rule of a frame-table overrun; wn_decoder_run_batch clamps per utterance instead (steps_left).
-static int check_limit(const char* fn, const Decoder* D, long long n) {
-    WN_CHECK_ARG(D->step_limit <= 0 || D->since_set + n <= D->step_limit,
-                 "%s: n = %lld more steps would pass step_limit = %d (%lld steps run since it was set)", fn, n, D->step_limit,
-                 D->since_set);
-    return WN_OK;
-}
-// how many of n steps the handle may still run: all of them without a limit
-static long long steps_left(const Decoder* D, long long n) {
-    if (D->step_limit <= 0) return n;
-    const long long left = D->step_limit - D->since_set;
-    return left < n ? left : n;
 }
 static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
     if (!d->frame_bias) return WN_OK;
-    int row = 0;
-    for (const DecLayer& L : D->layers) row += 2 * L.cd;
+    const int row = row_width(D);
     WN_CHECK_ARG(d->n_frames > 0 && d->frame_hop > 0, "decoder: a frame table needs n_frames > 0 and frame_hop > 0 (got %d, %d)",
                  d->n_frames, d->frame_hop);
     WN_CHECK_ARG(d->frame_phase >= 0 && d->frame_phase < d->frame_hop, "decoder: frame_phase = %d outside [0, frame_hop = %d)",
@@ -438,18 +416,45 @@ static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
 static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     D->since_set = 0;
     D->step_limit = d->step_limit;
-    if (!d->frame_bias) { D->n_frames = 0; return WN_OK; }
-    int row = 0;
-    for (const DecLayer& L : D->layers) row += 2 * L.cd;
-    if (d->n_frames > D->frame_cap || row != D->frame_row) {
-        if (D->frame_tab) { WN_HIP(hipFree(D->frame_tab)); D->frame_tab = nullptr; D->frame_cap = 0; }
-        WN_HIP(hipMalloc(&D->frame_tab, (size_t)d->n_frames * row * sizeof(float)));
-        D->frame_cap = d->n_frames;
+    FrameTable& F = D->frames;
+    if (!d->frame_bias) { F.n = 0; return WN_OK; }
+    const int row = row_width(D);
+    if (d->n_frames > F.cap || row != F.row) {
+        if (F.tab) { WN_HIP(hipFree(F.tab)); F.tab = nullptr; F.cap = 0; }
+        WN_HIP(hipMalloc(&F.tab, (size_t)d->n_frames * row * sizeof(float)));
+        F.cap = d->n_frames;
     }
-    WN_HIP(hipMemcpy2DAsync(D->frame_tab, (size_t)row * sizeof(float), d->frame_bias, (size_t)d->frame_stride * sizeof(float),
+    WN_HIP(hipMemcpy2DAsync(F.tab, (size_t)row * sizeof(float), d->frame_bias, (size_t)d->frame_stride * sizeof(float),
                             (size_t)row * sizeof(float), (size_t)d->n_frames, hipMemcpyDeviceToDevice, s));
-    D->n_frames = d->n_frames; D->frame_hop = d->frame_hop; D->frame_phase = d->frame_phase; D->frame_row = row;
-    D->frame_interp = d->frame_interp;
+    F.n = d->n_frames; F.hop = d->frame_hop; F.phase = d->frame_phase; F.row = row; F.interp = d->frame_interp;
+    return WN_OK;
+}
+
+// one utterance's launch arguments of the specialised kernels (decoder_fast.hip), from its handle
+static DecUtt fast_utt(const Decoder* D, int first_token, const double* uniforms, int32_t* out_tokens, float* prob_out,
+                       const SampleCtl& sc) {
+    DecUtt q{};
+    q.P = D->fastP; q.hbias = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
+    q.E = D->arena + D->causal[0].w; q.layers = D->d_layers; q.arena = D->arena; q.tok_ring = D->tok_ring; q.n0 = D->step;
+    q.uniforms = uniforms; q.out_tokens = out_tokens; q.prob_out = prob_out; q.first_token = first_token; q.sc = sc;
+    return q;
+}
+// ... and of the any-shape kernels
+static DecAnyUtt any_utt(const Decoder* D, int first_token, const double* uniforms, int32_t* out_tokens, float* prob_out,
+                         int nsteps, const SampleCtl& sc) {
+    DecAnyUtt q{};
+    q.causal = D->d_causal; q.layers = D->d_layers; q.heads = D->d_heads; q.arena = D->arena; q.tok_ring = D->tok_ring;
+    q.n0 = D->step; q.uniforms = uniforms; q.out_tokens = out_tokens; q.prob_out = prob_out;
+    q.first_token = first_token; q.nsteps = nsteps; q.sc = sc; q.fr = launch_frames(D);
+    return q;
+}
+
+// before the first pack launch: a refused wn_decoder_update_weights leaves the handle as it was
+static int check_weight_ptrs(const Decoder* D, const WnDecoderDesc* d) {
+    for (int i = 0; i < d->n_causal; ++i) WN_CHECK_ARG(d->causal_W[i], "decoder: causal_W[%d] NULL", i);
+    for (int j = 0; j < (int)D->layers.size(); ++j)
+        WN_CHECK_ARG(d->Wf[j] && d->Wg[j] && d->Wp[j] && d->Ws[j], "decoder: layer %d has a NULL weight", j);
+    for (int i = 0; i < d->n_head; ++i) WN_CHECK_ARG(d->head_W[i], "decoder: head_W[%d] NULL", i);
     return WN_OK;
 }
 
@@ -469,7 +474,6 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     for (int i = 0; i < d->n_causal; ++i) {
         const DecCausal& L = D->causal[i];
         int n = L.cout * L.cin * d->fw_causal;
-        WN_CHECK_ARG(d->causal_W[i], "decoder: causal_W[%d] NULL", i);
         if (i == 0)
             hipLaunchKernelGGL(k_pack_embed, dim3(cdiv(n, T)), dim3(T), 0, s, d->causal_W[i], D->arena + L.w, L.cout,
                                L.cin, d->fw_causal);
@@ -483,7 +487,6 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     for (int j = 0; j < (int)D->layers.size(); ++j) {
         const DecLayer& L = D->layers[j];
         int cd = L.cd, Cr = d->Cr, Cs = d->Cs;
-        WN_CHECK_ARG(d->Wf[j] && d->Wg[j] && d->Wp[j] && d->Ws[j], "decoder: layer %d has a NULL weight", j);
         int n = cd * Cr * d->fw;
         hipLaunchKernelGGL(k_pack_conv_T, dim3(cdiv(n, T)), dim3(T), 0, s, d->Wf[j], D->arena + L.wfg, cd, Cr, d->fw,
                            2 * cd, 0);
@@ -504,7 +507,6 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     }
     for (int i = 0; i < d->n_head; ++i) {
         const DecHead& H = D->heads[i];
-        WN_CHECK_ARG(d->head_W[i], "decoder: head_W[%d] NULL", i);
         hipLaunchKernelGGL(k_pack_conv_T, dim3(cdiv(H.cin * H.cout, T)), dim3(T), 0, s, d->head_W[i], D->arena + H.w,
                            H.cout, H.cin, 1, H.cout, 0);
         if (H.b >= 0)
@@ -515,18 +517,8 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     return WN_OK;
 }
 
-}  // namespace wn
-
-using namespace wn;
-
-extern "C" {
-
-int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
-    WN_CHECK_ARG(handle, "wn_decoder_create: handle is NULL");
-    int rc = validate(d);
-    if (rc) return rc;
-    Decoder* D = new (std::nothrow) Decoder();
-    WN_CHECK_ARG(D, "wn_decoder_create: out of host memory");
+// wn_decoder_create, first half: meta, the three host tables, arena_floats and lds_bytes.  Host arithmetic only.
+static int lay_out(Decoder* D, const WnDecoderDesc* d) {
     DecMeta& M = D->meta;
     M.Q = d->Q; M.fwc = d->fw_causal; M.ncausal = d->n_causal; M.fw = d->fw;
     M.nlayers = d->n_blocks * d->n_layers; M.Cr = d->Cr; M.Cs = d->Cs; M.nhead = d->n_head;
@@ -534,7 +526,6 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
     long long off = 0;
     int maxc = d->Q > d->Cs ? d->Q : d->Cs;
     if (d->Cr > maxc) maxc = d->Cr;
-    // layout of the arena
     int cin = d->Q;
     for (int i = 0; i < d->n_causal; ++i) {
         DecCausal L{};
@@ -554,7 +545,7 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
             int j = b * d->n_layers + l;
             DecLayer L{};
             L.cd = d->cd[l]; L.d = dil;
-            if (2 * L.cd > 2 * maxc) maxc = L.cd;
+            if (L.cd > maxc) maxc = L.cd;
             L.wfg = (int)off; off = align64(off + (long long)d->fw * d->Cr * 2 * L.cd);
             bool hb = d->bf && d->bf[j];
             WN_CHECK_ARG(hb == (d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
@@ -577,39 +568,55 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
         H.b = hb ? (int)off : -1; if (hb) off = align64(off + H.cout);
         D->heads.push_back(H);
     }
-    if (off >= (1ll << 31)) { delete D; wn::set_error("decoder: arena too large"); return WN_ESHAPE; }
+    WN_CHECK_SHAPE(off < (1ll << 31), "decoder: arena too large");
     M.maxc = maxc;
     D->arena_floats = off;
     D->lds_bytes = (size_t)(7 * maxc + 16) * sizeof(float);
-    if (D->lds_bytes > 150 * 1024) { delete D; wn::set_error("decoder: channel width %d too large", maxc); return WN_ESHAPE; }
+    WN_CHECK_SHAPE(D->lds_bytes <= 150 * 1024, "decoder: channel width %d too large", maxc);
+    return WN_OK;
+}
+
+}  // namespace wn
+
+using namespace wn;
+
+extern "C" {
+
+int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
+    WN_CHECK_ARG(handle, "wn_decoder_create: handle is NULL");
+    int rc = validate(d);
+    if (rc) return rc;
+    // a handle that is not handed out is destroyed, with whatever it holds by then
+    std::unique_ptr<Decoder, int (*)(void*)> built(new (std::nothrow) Decoder(), wn_decoder_destroy);
+    Decoder* D = built.get();
+    WN_CHECK_ARG(D, "wn_decoder_create: out of host memory");
+    if ((rc = lay_out(D, d))) return rc;
+    if ((rc = check_frame_desc(D, d))) return rc;
+    if ((rc = check_weight_ptrs(D, d))) return rc;
+    // second half: the device memory, zeroed, and the device copies of the three tables
     hipStream_t s = as_stream(stream);
-    size_t tab = D->causal.size() * sizeof(DecCausal) + D->layers.size() * sizeof(DecLayer) +
-                 D->heads.size() * sizeof(DecHead);
-#define DEC_HIP(e) do { hipError_t e__ = (e); if (e__ != hipSuccess) { wn::set_error("%s: %s", #e, hipGetErrorString(e__)); wn_decoder_destroy(D); return WN_EHIP; } } while (0)
-    DEC_HIP(hipMalloc(&D->arena, (size_t)off * sizeof(float)));
-    DEC_HIP(hipMemsetAsync(D->arena, 0, (size_t)off * sizeof(float), s));
-    DEC_HIP(hipMalloc(&D->tok_ring, sizeof(int) * (d->fw_causal > 1 ? d->fw_causal - 1 : 1)));
-    DEC_HIP(hipMemsetAsync(D->tok_ring, 0, sizeof(int) * (d->fw_causal > 1 ? d->fw_causal - 1 : 1), s));
-    DEC_HIP(hipMalloc(&D->dmeta, tab));
-    char* p = (char*)D->dmeta;
-    D->d_causal = (DecCausal*)p; p += D->causal.size() * sizeof(DecCausal);
-    D->d_layers = (DecLayer*)p; p += D->layers.size() * sizeof(DecLayer);
-    D->d_heads = (DecHead*)p;
-    DEC_HIP(hipMemcpyAsync(D->d_causal, D->causal.data(), D->causal.size() * sizeof(DecCausal), hipMemcpyHostToDevice, s));
-    DEC_HIP(hipMemcpyAsync(D->d_layers, D->layers.data(), D->layers.size() * sizeof(DecLayer), hipMemcpyHostToDevice, s));
-    DEC_HIP(hipMemcpyAsync(D->d_heads, D->heads.data(), D->heads.size() * sizeof(DecHead), hipMemcpyHostToDevice, s));
-    DEC_HIP(hipStreamSynchronize(s));      // the host vectors above must outlive the copies
+    const size_t ring = sizeof(int) * (d->fw_causal > 1 ? d->fw_causal - 1 : 1);
+    const size_t nc = D->causal.size() * sizeof(DecCausal), nl = D->layers.size() * sizeof(DecLayer), nh = D->heads.size() * sizeof(DecHead);
+    WN_HIP(hipMalloc(&D->arena, (size_t)D->arena_floats * sizeof(float)));
+    WN_HIP(hipMemsetAsync(D->arena, 0, (size_t)D->arena_floats * sizeof(float), s));
+    WN_HIP(hipMalloc(&D->tok_ring, ring));
+    WN_HIP(hipMemsetAsync(D->tok_ring, 0, ring, s));
+    WN_HIP(hipMalloc(&D->dmeta, nc + nl + nh));
+    D->d_causal = (DecCausal*)D->dmeta;
+    D->d_layers = (DecLayer*)((char*)D->dmeta + nc);
+    D->d_heads = (DecHead*)((char*)D->dmeta + nc + nl);
+    WN_HIP(hipMemcpyAsync(D->d_causal, D->causal.data(), nc, hipMemcpyHostToDevice, s));
+    WN_HIP(hipMemcpyAsync(D->d_layers, D->layers.data(), nl, hipMemcpyHostToDevice, s));
+    WN_HIP(hipMemcpyAsync(D->d_heads, D->heads.data(), nh, hipMemcpyHostToDevice, s));
+    WN_HIP(hipStreamSynchronize(s));      // the host vectors above must outlive the copies
     if (fast_shape(d)) {
-        DEC_HIP(hipMalloc(&D->fastP, decode_fast_pack_floats(M.nlayers) * sizeof(float)));
+        WN_HIP(hipMalloc(&D->fastP, decode_fast_pack_floats(D->meta.nlayers) * sizeof(float)));
         D->head_bias_off = D->heads[0].b;
         D->three_wgs = !(d->flags & WN_DECODER_ONE_WORKGROUP);
     }
-#undef DEC_HIP
-    rc = check_frame_desc(D, d);
-    if (!rc) rc = pack_weights(D, d, s);
-    if (!rc) rc = take_frames(D, d, s);
-    if (rc) { wn_decoder_destroy(D); return rc; }
-    *handle = D;
+    if ((rc = pack_weights(D, d, s))) return rc;
+    if ((rc = take_frames(D, d, s))) return rc;
+    *handle = built.release();
     return WN_OK;
 }
 
@@ -620,7 +627,7 @@ int wn_decoder_destroy(void* handle) {
     if (D->fastP) (void)hipFree(D->fastP);
     if (D->tok_ring) (void)hipFree(D->tok_ring);
     if (D->dmeta) (void)hipFree(D->dmeta);
-    if (D->frame_tab) (void)hipFree(D->frame_tab);
+    if (D->frames.tab) (void)hipFree(D->frames.tab);
     if (D->batch_tab) (void)hipFree(D->batch_tab);
     if (D->batch_img) (void)hipHostFree(D->batch_img);
     if (D->batch_copied) (void)hipEventDestroy(D->batch_copied);
@@ -637,6 +644,7 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
                      d->Q == D->meta.Q && d->n_causal == D->meta.ncausal && d->n_head == D->meta.nhead,
                  "wn_decoder_update_weights: topology differs from the handle's");
     if ((rc = check_frame_desc(D, d))) return rc;
+    if ((rc = check_weight_ptrs(D, d))) return rc;
     if ((rc = pack_weights(D, d, as_stream(stream)))) return rc;
     return take_frames(D, d, as_stream(stream));
 }
@@ -667,29 +675,42 @@ int wn_decoder_load_state(void* handle, const int32_t* tokens, int W, const floa
     return WN_OK;
 }
 
+// n steps were launched: the one writer of both counters after create / update / load_state
+static void advance(Decoder* D, long long n) { D->step += n; D->since_set += n; }
+
+// wn_decoder_step / wn_decoder_run behind their own argument checks: n steps of one handle.  A run that would read past
+// the frame table or pass WnDecoderDesc.step_limit is refused before any device work, never clamped
+static int run_one(const char* fn, Decoder* D, int token, const double* uniforms, int n, int32_t* out_tokens, float* prob,
+                   int apply_softmax, int do_sample, const SampleCtl& sc, bool three_wgs, hipStream_t s) {
+    WN_CHECK_ARG(D->step + n < (1ll << 31), "%s: step counter overflow", fn);
+    if (int rc = check_frames(fn, D, n)) return rc;
+    WN_CHECK_ARG(D->step_limit <= 0 || D->since_set + n <= D->step_limit,
+                 "%s: n = %lld more steps would pass step_limit = %d (%lld steps run since it was set)", fn, (long long)n,
+                 D->step_limit, D->since_set);
+    if (D->fastP) {
+        if (int rc = decode_fast_launch(fast_utt(D, token, uniforms, out_tokens, prob, sc), D->meta.nlayers, n, D->meta.Q,
+                                        apply_softmax, do_sample, D->meta.head_act, three_wgs, s))
+            return rc;
+        if (three_wgs) D->ran_multi = n > 1;       // (a single step is on one workgroup: an earlier run's entry stays readable)
+    } else {
+        // (k_decode takes the record's members as loose arguments: DESIGN.md, "The library's host side, tidied likewise")
+        const DecAnyUtt q = any_utt(D, token, uniforms, out_tokens, prob, n, sc);
+        const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, s, D->meta, q.causal, q.layers, q.heads, q.arena, q.tok_ring,
+                           q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out, D->meta.Q, apply_softmax, do_sample,
+                           q.sc, q.fr);
+        WN_LAUNCH_CHECK();
+    }
+    advance(D, n);
+    return WN_OK;
+}
+
 int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax, void* stream) {
     Decoder* D = (Decoder*)handle;
     WN_CHECK_ARG(D && prob, "wn_decoder_step: bad argument");
     WN_CHECK_ARG(token >= 0 && token < D->meta.Q, "wn_decoder_step: token %d outside [0,%d)", token, D->meta.Q);
-    WN_CHECK_ARG(D->step + 1 < (1ll << 31), "wn_decoder_step: step counter overflow");
-    if (int rc = check_frames("wn_decoder_step", D, 1)) return rc;
-    if (int rc = check_limit("wn_decoder_step", D, 1)) return rc;
-    if (D->fastP) {
-        int rc = decode_fast_launch(fast_utt(D, (int)token, nullptr, nullptr, prob, SampleCtl()), D->meta.nlayers, 1, D->meta.Q,
-                                    apply_softmax, 0, D->meta.head_act, false, as_stream(stream));
-        if (rc) return rc;
-        D->step += 1;
-        D->since_set += 1;
-        return WN_OK;
-    }
-    const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
-                       D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, 1, (int)token,
-                       (const double*)nullptr, (int32_t*)nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl(), launch_frames(D));
-    WN_LAUNCH_CHECK();
-    D->step += 1;
-    D->since_set += 1;
-    return WN_OK;
+    return run_one("wn_decoder_step", D, (int)token, nullptr, 1, nullptr, prob, apply_softmax, 0, SampleCtl(), false,
+                   as_stream(stream));
 }
 
 int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, int n, int32_t* out_tokens,
@@ -697,26 +718,8 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     Decoder* D = (Decoder*)handle;
     WN_CHECK_ARG(D && uniforms && out_tokens && n > 0, "wn_decoder_run: bad argument");
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
-    WN_CHECK_ARG(D->step + n < (1ll << 31), "wn_decoder_run: step counter overflow");
-    if (int rc = check_frames("wn_decoder_run", D, n)) return rc;
-    if (int rc = check_limit("wn_decoder_run", D, n)) return rc;
-    if (D->fastP) {
-        int rc = decode_fast_launch(fast_utt(D, (int)first_token, uniforms, out_tokens, prob_trace, launch_ctl(D)),
-                                    D->meta.nlayers, n, D->meta.Q, 1, 1, D->meta.head_act, D->three_wgs, as_stream(stream));
-        if (rc) return rc;
-        D->ran_multi = D->three_wgs && n > 1;
-        D->step += n;
-        D->since_set += n;
-        return WN_OK;
-    }
-    const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, as_stream(stream), D->meta, D->d_causal,
-                       D->d_layers, D->d_heads, D->arena, D->tok_ring, D->step, n, (int)first_token, uniforms,
-                       out_tokens, prob_trace, D->meta.Q, 1, 1, launch_ctl(D), launch_frames(D));
-    WN_LAUNCH_CHECK();
-    D->step += n;
-    D->since_set += n;
-    return WN_OK;
+    return run_one("wn_decoder_run", D, (int)first_token, uniforms, n, out_tokens, prob_trace, 1, 1, launch_ctl(D), D->three_wgs,
+                   as_stream(stream));
 }
 
 int wn_decoder_set_sampling(void* handle, float temperature, int top_k, double top_p) {
@@ -755,11 +758,8 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     DecAnyUtt* img = (DecAnyUtt*)D0->batch_img;
     for (int u = 0; u < n_handles; ++u) {
         const Decoder* D = (const Decoder*)handles[u];
-        DecAnyUtt q{};
-        q.causal = D->d_causal; q.layers = D->d_layers; q.heads = D->d_heads; q.arena = D->arena; q.tok_ring = D->tok_ring;
-        q.n0 = D->step; q.uniforms = uniforms[u]; q.out_tokens = out_tokens[u]; q.prob_out = prob_traces ? prob_traces[u] : nullptr;
-        q.first_token = (int)first_tokens[u]; q.nsteps = nsteps[u]; q.sc = launch_ctl(D); q.fr = launch_frames(D);
-        img[u] = q;
+        img[u] = any_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, nsteps[u],
+                         launch_ctl(D));
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
@@ -767,7 +767,48 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
                        n_handles);
     WN_LAUNCH_CHECK();
-    for (int u = 0; u < n_handles; ++u) { ((Decoder*)handles[u])->step += nsteps[u]; ((Decoder*)handles[u])->since_set += nsteps[u]; }
+    return WN_OK;
+}
+
+// wn_decoder_run_batch: utterance u's handle holds utterance 0's model
+static int same_model(const Decoder* D, const Decoder* D0, int u, int same_weights) {
+    WN_CHECK_SHAPE(!D->fastP == !D0->fastP, "wn_decoder_run_batch: utterance %d is %s decoder, utterance 0 is not: one launch takes one form", u,
+                   D->fastP ? "a nine-workgroup (config 4's shape)" : "an any-shape");
+    const DecMeta &A = D->meta, &B = D0->meta;
+    WN_CHECK_SHAPE(A.nlayers == B.nlayers && A.head_act == B.head_act && A.Q == B.Q && A.Cr == B.Cr && A.Cs == B.Cs && A.fw == B.fw &&
+                       A.fwc == B.fwc && A.ncausal == B.ncausal && A.nhead == B.nhead && A.maxc == B.maxc &&
+                       D->layers.size() == D0->layers.size(),
+                   "wn_decoder_run_batch: utterance %d's model differs from utterance 0's (layers, channels, filter widths, Q or head "
+                   "activation)", u);
+    for (size_t l = 0; l < D->layers.size(); ++l)
+        WN_CHECK_SHAPE(D->layers[l].d == D0->layers[l].d && D->layers[l].cd == D0->layers[l].cd,
+                       "wn_decoder_run_batch: layer %d of utterance %d has another dilation / width than utterance 0's", (int)l, u);
+    for (size_t i = 0; i < D->causal.size(); ++i)
+        WN_CHECK_SHAPE(D->causal[i].cin == D0->causal[i].cin && D->causal[i].cout == D0->causal[i].cout,
+                       "wn_decoder_run_batch: causal layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
+    for (size_t i = 0; i < D->heads.size(); ++i)
+        WN_CHECK_SHAPE(D->heads[i].cin == D0->heads[i].cin && D->heads[i].cout == D0->heads[i].cout,
+                       "wn_decoder_run_batch: head layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
+    // same_weights = 1 reads ONE copy of the packed weights (handle 0's) for every utterance: only sound when every
+    // handle was packed from the same model -- the same weight pointers at its last create / update_weights.  (The
+    // any-shape form checks the claim and then reads each utterance's own copy all the same.)
+    WN_CHECK_ARG(!same_weights || D->src_key == D0->src_key,
+                 "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
+    return WN_OK;
+}
+
+// wn_decoder_run_batch clamps where run_one refuses: utterance u runs *nu = min(n, steps left under its handle's step_limit)
+// steps, n without a limit
+static int steps_left(const Decoder* D, int u, int n, bool any, int* nu) {
+    const long long left = D->step_limit > 0 && D->step_limit - D->since_set < n ? D->step_limit - D->since_set : n;
+    WN_CHECK_ARG(left > 0, "wn_decoder_run_batch: utterance %d has run all %d steps of its step_limit: leave a finished utterance "
+                           "out of the launch", u, D->step_limit);
+    // the nine-workgroup form runs two steps at least: its existing rule, here per utterance (a launch whose own n is below
+    // 2 is refused as ever, by decode_fast_batch_ok)
+    WN_CHECK_ARG(any || left == n || left >= 2, "wn_decoder_run_batch: utterance %d has %lld step left under its step_limit = %d: "
+                                                "the nine-workgroup form runs 2 at least", u, left, D->step_limit);
+    *nu = (int)left;
+    WN_CHECK_ARG(D->step + left < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
     return WN_OK;
 }
 
@@ -782,67 +823,37 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     WN_CHECK_SHAPE(n_handles <= limit, "wn_decoder_run_batch: at most %d utterances per launch of %s decoders", limit,
                    any ? "any-shape" : "nine-workgroup");
     DecUtt utt[kDecMaxBatch];
-    // utterance u runs nu[u] = min(n, steps left under its handle's step_limit) steps: n without a limit
-    int nu[WN_DECODER_BATCH_MAX_ANY];
-    for (int u = 0; u < n_handles; ++u) {
-        Decoder* D = (Decoder*)handles[u];
+    int nu[WN_DECODER_BATCH_MAX_ANY];              // the utterances' own step counts
+    for (int u = 0; u < n_handles; ++u) {          // per utterance: arguments, same model, steps, frames, record
+        const Decoder* D = (const Decoder*)handles[u];
         WN_CHECK_ARG(D && uniforms[u] && out_tokens[u], "wn_decoder_run_batch: NULL handle / uniforms / out_tokens of utterance %d", u);
         for (int v = 0; v < u; ++v) WN_CHECK_ARG(handles[v] != handles[u], "wn_decoder_run_batch: handle %d given twice", u);
         WN_CHECK_SHAPE(!D->fastP || D->three_wgs, "wn_decoder_run_batch: utterance %d's decoder was created with WN_DECODER_ONE_WORKGROUP: "
                                                   "the one-workgroup specialised kernel has no batched form", u);
-        WN_CHECK_SHAPE(!D->fastP == any, "wn_decoder_run_batch: utterance %d is %s decoder, utterance 0 is not: one launch takes one form", u,
-                       D->fastP ? "a nine-workgroup (config 4's shape)" : "an any-shape");
-        const DecMeta &A = D->meta, &B = D0->meta;
-        WN_CHECK_SHAPE(A.nlayers == B.nlayers && A.head_act == B.head_act && A.Q == B.Q && A.Cr == B.Cr && A.Cs == B.Cs && A.fw == B.fw &&
-                           A.fwc == B.fwc && A.ncausal == B.ncausal && A.nhead == B.nhead && A.maxc == B.maxc &&
-                           D->layers.size() == D0->layers.size(),
-                       "wn_decoder_run_batch: utterance %d's model differs from utterance 0's (layers, channels, filter widths, Q or head "
-                       "activation)", u);
-        for (size_t l = 0; l < D->layers.size(); ++l)
-            WN_CHECK_SHAPE(D->layers[l].d == D0->layers[l].d && D->layers[l].cd == D0->layers[l].cd,
-                           "wn_decoder_run_batch: layer %d of utterance %d has another dilation / width than utterance 0's", (int)l, u);
-        for (size_t i = 0; i < D->causal.size(); ++i)
-            WN_CHECK_SHAPE(D->causal[i].cin == D0->causal[i].cin && D->causal[i].cout == D0->causal[i].cout,
-                           "wn_decoder_run_batch: causal layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
-        for (size_t i = 0; i < D->heads.size(); ++i)
-            WN_CHECK_SHAPE(D->heads[i].cin == D0->heads[i].cin && D->heads[i].cout == D0->heads[i].cout,
-                           "wn_decoder_run_batch: head layer %d of utterance %d has other channels than utterance 0's", (int)i, u);
-        // same_weights = 1 reads ONE copy of the packed weights (handle 0's) for every utterance: only sound when every
-        // handle was packed from the same model -- the same weight pointers at its last create / update_weights.  (The
-        // any-shape form checks the claim and then reads each utterance's own copy all the same.)
-        WN_CHECK_ARG(!same_weights || D->src_key == D0->src_key,
-                     "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
+        if (int rc = same_model(D, D0, u, same_weights)) return rc;
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
-        const long long left = steps_left(D, n);
-        WN_CHECK_ARG(left > 0, "wn_decoder_run_batch: utterance %d has run all %d steps of its step_limit: leave a finished utterance "
-                               "out of the launch", u, D->step_limit);
-        // the nine-workgroup form runs two steps at least: its existing rule, here per utterance (a launch whose own n is below
-        // 2 is refused as ever, below)
-        WN_CHECK_ARG(any || left == n || left >= 2, "wn_decoder_run_batch: utterance %d has %lld step left under its step_limit = %d: "
-                                                    "the nine-workgroup form runs 2 at least", u, left, D->step_limit);
-        nu[u] = (int)left;
-        WN_CHECK_ARG(D->step + nu[u] < (1ll << 31), "wn_decoder_run_batch: step counter overflow");
-        WN_CHECK_ARG((D->n_frames > 0) == (D0->n_frames > 0) && (D->n_frames <= 0 || D->frame_hop == D0->frame_hop),
+        if (int rc = steps_left(D, u, n, any, &nu[u])) return rc;
+        const FrameTable &F = D->frames, &F0 = D0->frames;
+        WN_CHECK_ARG((F.n > 0) == (F0.n > 0) && (F.n <= 0 || F.hop == F0.hop),
                      "wn_decoder_run_batch: utterance %d and utterance 0 disagree on having a frame table or on its hop", u);
-        WN_CHECK_ARG(D->n_frames <= 0 || D->frame_interp == D0->frame_interp,
+        WN_CHECK_ARG(F.n <= 0 || F.interp == F0.interp,
                      "wn_decoder_run_batch: utterance %d and utterance 0 disagree on frame_interp (repeat / linear)", u);
-        if (int rcf = check_frames("wn_decoder_run_batch", D, nu[u])) return rcf;
+        if (int rc = check_frames("wn_decoder_run_batch", D, nu[u])) return rc;
         if (!any) {
             utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
             utt[u].nsteps = nu[u];
         }
     }
-    if (any) return run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream));
-    WN_CHECK_SHAPE(decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
+    WN_CHECK_SHAPE(any || decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
-    const int rc = decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
-                                            as_stream(stream));
+    const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream))
+                       : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
+                                                  as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];
-        D->ran_multi = true;
-        D->step += nu[u];
-        D->since_set += nu[u];
+        if (!any) D->ran_multi = true;
+        advance(D, nu[u]);
     }
     return WN_OK;
 }
