@@ -356,6 +356,29 @@ int wn_btc_to_nchw(const float* src, float* dst, int B, int C, int T, void* stre
  * per extra causal layer) instead of the reference's full-window caches that are rolled every
  * step; the head runs on the newest column only.                                               */
 #define WN_DECODER_ONE_WORKGROUP 64u
+/* WnDecoderDesc.flags: on a description that is otherwise of the specialised decoder's shape (config 4's: Q = 256, one causal
+ * layer of filter width 2, 32 / 32 / 256 channels, filter width 2, head 256 -> 256, at most 128 layers), gate biases (bf[j] /
+ * bg[j], both or neither per layer; a layer without them adds 0) and / or a frame table do NOT deselect that decoder: the
+ * handle runs k_decode_fast / k_decode_fast3 / k_decode_fast3_batch, and only wave 1 of the chain workgroup changes -- the
+ * wave that runs ahead of the layer chain and forms the x[n-d] half of every gate row.  For step k of a launch, p = pos0 + k,
+ * j = p / frame_hop, alpha = float32(p % frame_hop) / float32(frame_hop), lane `lane` of flat layer l starts its accumulator at
+ * (static bias or 0) + y with y = r[j][64 l + lane] (repeat) or r[j] + alpha * (r[j + 1] - r[j]) (linear: three separately
+ * rounded fp32 operations, WnStackDesc.bias_interp's rule); the row is fetched one layer ahead like the weights, nothing is
+ * added to the chain wave, the skip workgroups or the exchange between workgroups, and a table of zeros changes no bit.
+ * Without the flag every call does what it did before the flag existed (such a description gives an any-shape handle); bp, bs,
+ * a causal bias and WN_EXEC_FORCE_GENERIC deselect the specialised decoder with or without it, and on a description of any
+ * other shape the flag is ignored.  A handle's form is fixed at create: wn_decoder_update_weights on a flagged handle takes new
+ * gate biases (or none), a new table, another one or none, and a description whose flag differs from the handle's is WN_EARG
+ * before any device work.  The frame-table rules (refusals, messages, the step counter shared with step_limit, "nothing
+ * clamps") are the any-shape decoder's.  wn_decoder_run_batch on flagged handles is the nine-workgroup form with its rules
+ * (28 utterances, n >= 2, n_u >= 2) and the any-shape form's agreement on having a table, frame_hop and frame_interp; under
+ * same_weights != 0 the utterances share handle 0's packed weights, while every utterance's static gate biases and table
+ * rows come from its OWN handle -- they are not part of the shared weights, and the same_weights check does not look at a
+ * flagged handle's bf / bg pointers, so utterances of different classes (speakers) and different tables share one copy.
+ * The specialised kernels sum a gate row in another order than the any-shape decoder: probabilities agree to rounding, and
+ * a conditioned model's sampled tokens can differ from the any-shape decoder's at a near-tie of the cumulative distribution
+ * (as for WN_DECODER_ONE_WORKGROUP); each form is deterministic. */
+#define WN_DECODER_GATE_ROWS 128u
 typedef struct WnDecoderDesc {
     int Q, fw_causal, n_causal, fw, n_blocks, n_layers;  /* n_layers per block; dilation fw^l */
     int Cr, Cs, n_head;
@@ -371,6 +394,8 @@ typedef struct WnDecoderDesc {
     const float* const* head_W; const float* const* head_b;                     /* n_head      */
     int head_act;                     /* WN_ACT_ELU for FasterWaveNet, WN_ACT_RELU for WaveNet  */
     unsigned flags;                   /* WN_EXEC_FORCE_GENERIC: never the specialised 32/256-channel decode kernel;
+                                         WN_DECODER_GATE_ROWS (see the define): gate biases and a frame table do not
+                                         deselect that kernel;
                                          WN_DECODER_ONE_WORKGROUP: wn_decoder_run of that kernel on ONE workgroup instead of
                                          nine (the chain | eight workgroups of skip rows and their share of the logits):
                                          same products, another summation order for the skip rows and the logits --
@@ -393,9 +418,10 @@ typedef struct WnDecoderDesc {
      * wn_decoder_run_batch runs it -- adds row (frame_phase + k) / frame_hop to every layer's gate pre-activations, in fp32, on
      * top of the static bf / bg where those exist: per output (static bias or 0) + frame value, then the taps, so a table of
      * zeros changes no bit.  A run that would read past row n_frames - 1 is refused with WN_EARG before any device work (no
-     * clamping).  A handle with a table is an any-shape one, as with biased layers (a handle created WITHOUT one on config 4's
-     * shape runs the specialised kernels and refuses a table in wn_decoder_update_weights); an update without a table drops
-     * it.  wn_decoder_run_batch: the handles must agree on having a table and on frame_hop; phase, row count and contents are
+     * clamping).  Without WN_DECODER_GATE_ROWS a handle with a table is an any-shape one, as with biased layers (a handle created
+     * WITHOUT one on config 4's shape runs the specialised kernels and refuses a table in wn_decoder_update_weights); with the
+     * flag a description of config 4's shape gives a handle of the specialised kernels that takes tables (see the define).  An
+     * update without a table drops it.  wn_decoder_run_batch: the handles must agree on having a table and on frame_hop; phase, row count and contents are
      * per utterance.
      * frame_interp = 1 (0, the default: the above, unchanged; read only with a table): linear interpolation, the rule of
      * WnStackDesc.bias_interp with rows anchored at the first step of their frame -- step k, p = frame_phase + k, j = p /
@@ -434,7 +460,9 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
  * in HOST arrays, first_tokens is a host array.  The utterances share nothing: an utterance's tokens and probability trace are
  * those of its own wn_decoder_run on the same handle with the same uniforms, bit for bit, and every handle's step counter
  * advances by n.  Handle 0 chooses between two forms, and all handles must be of its form (WN_ESHAPE otherwise):
- *   - nine workgroups per utterance: handles of the specialised decoder (config 4's shape, no WN_EXEC_FORCE_GENERIC).  At most
+ *   - nine workgroups per utterance: handles of the specialised decoder (config 4's shape, no WN_EXEC_FORCE_GENERIC; with
+ *     WN_DECODER_GATE_ROWS also such handles with gate biases and / or a frame table, which must agree on having a table, on
+ *     frame_hop and on frame_interp, and whose gate biases and rows stay per utterance under same_weights).  At most
  *     wn_decoder_batch_max() (28) utterances, 9 * n_handles workgroups must fit the device's CUs (WN_ESHAPE otherwise), and
  *     n >= 2.  same_weights != 0 is the caller's word that every handle was created from (and updated with) the SAME weights:
  *     all utterances then read handle 0's packed weights (one copy through the L2s instead of n_handles; each keeps its own

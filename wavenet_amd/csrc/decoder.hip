@@ -45,6 +45,9 @@ struct Decoder {
     float* fastP = nullptr;       // packed weights of the specialised kernel (decoder_fast.hip), or NULL
     int head_bias_off = -1;
     bool three_wgs = true;        // wn_decoder_run on nine workgroups (decoder_fast.hip); WN_DECODER_ONE_WORKGROUP clears it
+    bool gate_bias = false;       // ... and the last create / update gave it static gate biases (else its 64 floats per layer hold 0)
+    bool gate_rows = false;       // created with WN_DECODER_GATE_ROWS (the handle's form is fixed at create): a fast handle that
+                                  // takes static gate biases and a frame table -- wave 1 of the chain workgroup adds them
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
     SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
     // wn_decoder_run_batch on any-shape handles, as handle 0 of the call: the per-utterance table (DecAnyUtt) in device
@@ -62,19 +65,22 @@ struct Decoder {
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
 };
 
-// the shape decoder_fast.hip is written for (BASELINE.json config 4 with the reference's default biases)
+// the shape decoder_fast.hip is written for (BASELINE.json config 4 with the reference's default biases).  Gate biases
+// (bf / bg) and a frame table deselect it unless the description carries WN_DECODER_GATE_ROWS; bp / bs, a causal bias and
+// WN_EXEC_FORCE_GENERIC always do
 static bool fast_shape(const WnDecoderDesc* d) {
+    const bool rows = (d->flags & WN_DECODER_GATE_ROWS) != 0;
     if (d->flags & WN_EXEC_FORCE_GENERIC) return false;
     if (!(d->Q == 256 && d->n_causal == 1 && d->fw_causal == 2 && d->fw == 2 && d->Cr == 32 && d->Cs == 256 &&
           d->n_head == 1 && d->head_channels[0] == 256 && d->head_channels[1] == 256 &&
           d->n_blocks * d->n_layers <= 128))
         return false;
     if (d->causal_b && d->causal_b[0]) return false;
-    if (d->frame_bias) return false;               // a frame table selects the any-shape decoder, as biased layers do
+    if (d->frame_bias && !rows) return false;      // a frame table selects the any-shape decoder, as biased layers do
     for (int l = 0; l < d->n_layers; ++l)
         if (d->cd[l] != 32) return false;
     for (int j = 0; j < d->n_blocks * d->n_layers; ++j)
-        if ((d->bf && d->bf[j]) || (d->bg && d->bg[j]) || (d->bp && d->bp[j]) || (d->bs && d->bs[j])) return false;
+        if ((!rows && ((d->bf && d->bf[j]) || (d->bg && d->bg[j]))) || (d->bp && d->bp[j]) || (d->bs && d->bs[j])) return false;
     return true;
 }
 
@@ -130,12 +136,7 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 }
 
 // ---- the step loop ---------------------------------------------------------------------------
-// Local conditioning: the frame table of one utterance as the step loop takes it.  tab == NULL: no table, and the loop
-// executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the table's
-// phase (FrameTable) + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
-// interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
-// float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
-struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
+// (DecFrames, the frame table of one utterance as a step loop takes it: decoder_types.hpp)
 // One utterance as the any-shape kernels take it, from its own handle (any_utt): k_decode's arguments, and an entry of the
 // table k_decode_batch reads from device memory (Decoder::batch_tab of handle 0).
 struct DecAnyUtt {
@@ -407,7 +408,7 @@ static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
                  d->frame_interp);
     WN_CHECK_ARG(d->frame_stride >= row, "decoder: frame_stride = %d below the row width %d (sum of 2 cd over the layers)",
                  d->frame_stride, row);
-    WN_CHECK_ARG(!D->fastP, "decoder: this handle runs the specialised 32/256-channel kernels, which take no frame table: create the "
+    WN_CHECK_ARG(!D->fastP || D->gate_rows, "decoder: this handle runs the specialised 32/256-channel kernels, which take no frame table: create the "
                             "handle with the table");
     return WN_OK;
 }
@@ -431,12 +432,18 @@ static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
 }
 
 // one utterance's launch arguments of the specialised kernels (decoder_fast.hip), from its handle
+// a WN_DECODER_GATE_ROWS handle that holds something to add: static gate biases or a table (else the launch is the plain one)
+static bool gate_launch(const Decoder* D) {
+    if (!D->gate_rows) return false;
+    return D->frames.n > 0 || D->gate_bias;
+}
 static DecUtt fast_utt(const Decoder* D, int first_token, const double* uniforms, int32_t* out_tokens, float* prob_out,
                        const SampleCtl& sc) {
     DecUtt q{};
     q.P = D->fastP; q.hbias = D->head_bias_off >= 0 ? D->arena + D->head_bias_off : nullptr;
     q.E = D->arena + D->causal[0].w; q.layers = D->d_layers; q.arena = D->arena; q.tok_ring = D->tok_ring; q.n0 = D->step;
     q.uniforms = uniforms; q.out_tokens = out_tokens; q.prob_out = prob_out; q.first_token = first_token; q.sc = sc;
+    if (D->gate_rows) q.fr = launch_frames(D);
     return q;
 }
 // ... and of the any-shape kernels
@@ -466,7 +473,10 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
         for (int i = 0; i < d->n_causal; ++i) { mix(d->causal_W[i]); mix(d->causal_b ? d->causal_b[i] : nullptr); }
         for (int j = 0; j < (int)D->layers.size(); ++j) {
             mix(d->Wf[j]); mix(d->Wg[j]); mix(d->Wp[j]); mix(d->Ws[j]);
-            mix(d->bf ? d->bf[j] : nullptr); mix(d->bg ? d->bg[j] : nullptr); mix(d->bp ? d->bp[j] : nullptr); mix(d->bs ? d->bs[j] : nullptr);
+            // (a WN_DECODER_GATE_ROWS handle keeps its gate biases out of the packed weights that same_weights shares: handles of
+            // one model holding different classes' biases still carry one key)
+            if (!D->gate_rows) { mix(d->bf ? d->bf[j] : nullptr); mix(d->bg ? d->bg[j] : nullptr); }
+            mix(d->bp ? d->bp[j] : nullptr); mix(d->bs ? d->bs[j] : nullptr);
         }
         for (int i = 0; i < d->n_head; ++i) { mix(d->head_W[i]); mix(d->head_b ? d->head_b[i] : nullptr); }
         D->src_key = h;
@@ -484,6 +494,7 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
             hipLaunchKernelGGL(k_copy_off, dim3(cdiv(L.cout, T)), dim3(T), 0, s, d->causal_b[i], D->arena + L.b,
                                L.cout);
     }
+    D->gate_bias = false;
     for (int j = 0; j < (int)D->layers.size(); ++j) {
         const DecLayer& L = D->layers[j];
         int cd = L.cd, Cr = d->Cr, Cs = d->Cs;
@@ -496,9 +507,12 @@ static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
                            Cr + Cs, 0);
         hipLaunchKernelGGL(k_pack_conv_T, dim3(cdiv(Cs * cd, T)), dim3(T), 0, s, d->Ws[j], D->arena + L.wps, Cs, cd, 1,
                            Cr + Cs, Cr);
-        if (L.bfg >= 0) {
+        if (L.bfg >= 0 && d->bf && d->bf[j]) {
             hipLaunchKernelGGL(k_copy_off, dim3(cdiv(cd, T)), dim3(T), 0, s, d->bf[j], D->arena + L.bfg, cd);
             hipLaunchKernelGGL(k_copy_off, dim3(cdiv(cd, T)), dim3(T), 0, s, d->bg[j], D->arena + L.bfg + cd, cd);
+            D->gate_bias = true;
+        } else if (L.bfg >= 0) {           // a WN_DECODER_GATE_ROWS handle (every layer has room) given no bias for this layer: 0
+            WN_HIP(hipMemsetAsync(D->arena + L.bfg, 0, 2 * (size_t)cd * sizeof(float), s));
         }
         if (L.bps >= 0) {
             hipLaunchKernelGGL(k_copy_off, dim3(cdiv(Cr, T)), dim3(T), 0, s, d->bp[j], D->arena + L.bps, Cr);
@@ -524,6 +538,9 @@ static int lay_out(Decoder* D, const WnDecoderDesc* d) {
     M.nlayers = d->n_blocks * d->n_layers; M.Cr = d->Cr; M.Cs = d->Cs; M.nhead = d->n_head;
     M.head_act = d->head_act;
     long long off = 0;
+    // a WN_DECODER_GATE_ROWS handle of the specialised shape keeps room for every layer's gate biases, given or not: an update
+    // may bring biases to a handle created without them (and the other way round)
+    const bool rows = (d->flags & WN_DECODER_GATE_ROWS) && fast_shape(d);
     int maxc = d->Q > d->Cs ? d->Q : d->Cs;
     if (d->Cr > maxc) maxc = d->Cr;
     int cin = d->Q;
@@ -549,7 +566,7 @@ static int lay_out(Decoder* D, const WnDecoderDesc* d) {
             L.wfg = (int)off; off = align64(off + (long long)d->fw * d->Cr * 2 * L.cd);
             bool hb = d->bf && d->bf[j];
             WN_CHECK_ARG(hb == (d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
-            L.bfg = hb ? (int)off : -1; if (hb) off = align64(off + 2 * L.cd);
+            L.bfg = hb || rows ? (int)off : -1; if (hb || rows) off = align64(off + 2 * L.cd);
             L.wps = (int)off; off = align64(off + (long long)L.cd * (d->Cr + d->Cs));
             bool hp = d->bp && d->bp[j];
             WN_CHECK_ARG(hp == (d->bs && d->bs[j]), "decoder: bp/bs must both be present or absent");
@@ -613,6 +630,7 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
         WN_HIP(hipMalloc(&D->fastP, decode_fast_pack_floats(D->meta.nlayers) * sizeof(float)));
         D->head_bias_off = D->heads[0].b;
         D->three_wgs = !(d->flags & WN_DECODER_ONE_WORKGROUP);
+        D->gate_rows = (d->flags & WN_DECODER_GATE_ROWS) != 0;
     }
     if ((rc = pack_weights(D, d, s))) return rc;
     if ((rc = take_frames(D, d, s))) return rc;
@@ -643,6 +661,12 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
     WN_CHECK_ARG(d->n_blocks * d->n_layers == D->meta.nlayers && d->Cr == D->meta.Cr && d->Cs == D->meta.Cs &&
                      d->Q == D->meta.Q && d->n_causal == D->meta.ncausal && d->n_head == D->meta.nhead,
                  "wn_decoder_update_weights: topology differs from the handle's");
+    // a handle's form is fixed at create (the flag is ignored on other shapes, at create and here)
+    WN_CHECK_ARG(!D->fastP || ((d->flags & WN_DECODER_GATE_ROWS) != 0) == D->gate_rows,
+                 "wn_decoder_update_weights: the description %s WN_DECODER_GATE_ROWS, the handle was created %s it: a handle's form "
+                 "is fixed at create", d->flags & WN_DECODER_GATE_ROWS ? "carries" : "lacks", D->gate_rows ? "with" : "without");
+    for (int j = 0; D->gate_rows && j < D->meta.nlayers; ++j)
+        WN_CHECK_ARG(!(d->bf && d->bf[j]) == !(d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
     if ((rc = check_frame_desc(D, d))) return rc;
     if ((rc = check_weight_ptrs(D, d))) return rc;
     if ((rc = pack_weights(D, d, as_stream(stream)))) return rc;
@@ -689,7 +713,7 @@ static int run_one(const char* fn, Decoder* D, int token, const double* uniforms
                  D->step_limit, D->since_set);
     if (D->fastP) {
         if (int rc = decode_fast_launch(fast_utt(D, token, uniforms, out_tokens, prob, sc), D->meta.nlayers, n, D->meta.Q,
-                                        apply_softmax, do_sample, D->meta.head_act, three_wgs, s))
+                                        apply_softmax, do_sample, D->meta.head_act, three_wgs, gate_launch(D), s))
             return rc;
         if (three_wgs) D->ran_multi = n > 1;       // (a single step is on one workgroup: an earlier run's entry stays readable)
     } else {
@@ -824,6 +848,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
                    any ? "any-shape" : "nine-workgroup");
     DecUtt utt[kDecMaxBatch];
     int nu[WN_DECODER_BATCH_MAX_ANY];              // the utterances' own step counts
+    bool gate = false;                             // nine-workgroup form: some utterance has gate rows to add
     for (int u = 0; u < n_handles; ++u) {          // per utterance: arguments, same model, steps, frames, record
         const Decoder* D = (const Decoder*)handles[u];
         WN_CHECK_ARG(D && uniforms[u] && out_tokens[u], "wn_decoder_run_batch: NULL handle / uniforms / out_tokens of utterance %d", u);
@@ -842,13 +867,14 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         if (!any) {
             utt[u] = fast_utt(D, (int)first_tokens[u], uniforms[u], out_tokens[u], prob_traces ? prob_traces[u] : nullptr, launch_ctl(D));
             utt[u].nsteps = nu[u];
+            gate = gate || gate_launch(D);
         }
     }
     WN_CHECK_SHAPE(any || decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream))
                        : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
-                                                  as_stream(stream));
+                                                  gate, as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {
         Decoder* D = (Decoder*)handles[u];

@@ -1,6 +1,7 @@
 // Specialised persistent decode kernel for the shape of BASELINE.json config 4:
 //   Q = 256, one causal layer (fw 2), Cr = Cd = 32, Cs = 256, residual fw 2, one head conv 256 -> 256,
-//   no biases except the head's (the reference's defaults, wavenet.py:108,116-117,138).
+//   no biases except the head's (the reference's defaults, wavenet.py:108,116-117,138) -- and, on WN_DECODER_GATE_ROWS handles,
+//   gate biases and a frame table (global / local conditioning): "Gate rows" below, wave 1 only, the GATE instantiations.
 // Same algorithm and state as k_decode in decoder.hip (FasterWaveNet._forward_one_step restated with
 // rings instead of rolled windows); what changes is how ONE workgroup is used so that a step is not
 // a chain of L2 round trips and wide barriers:
@@ -235,10 +236,63 @@ __device__ __forceinline__ void wait_count(const int* c, int v) {               
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// wave 1: the x[n-d] half of gate row `lane` of layer l -> aold[l][lane]
-__device__ __forceinline__ void old_layer(const ChainLds& S, const OldW& w, int l, int lane) {
+// Gate rows (WN_DECODER_GATE_ROWS handles; the GATE instantiations of the three kernels): what wave 1 adds to gate row `lane` of
+// every layer besides the x[n-d] half -- the handle's static gate bias and the step's frame-table value, both known when the
+// step starts.  A table row is laid out as wave 1's lanes are: flat layer l's 32 filter values at 64 l, its 32 gate values at
+// 64 l + 32, so lane `lane` of layer l reads float 64 l + lane of the row -- one coalesced 256-byte read per layer --, and the
+// static biases of a layer are 64 floats (bf | bg) at DecLayer.bfg of the utterance's OWN arena (never utterance 0's packed
+// weights: under same_weights the utterances still differ in class and table).
+// GateStep: one step's view, wave-uniform except the two offsets.
+struct GateStep {
+    const float* r0;          // row j of the step (NULL: no table)
+    const float* r1;          // row j + 1 (NULL: repeat mode, or no table)
+    float alpha;              // float(p % hop) / float(hop)
+    const float* arena;
+    int b_lo, b_hi;           // lane k holds DecLayer.bfg of layers k and 64 + k (< 0: the layer has no static bias)
+};
+struct GateB { float s, y0, y1; };                 // static bias | row j | row j + 1 of one layer, this lane's
+__device__ __forceinline__ void load_gate(GateB& b, const GateStep& g, int l, int lane) {
+    const int off = __builtin_amdgcn_readlane(l < 64 ? g.b_lo : g.b_hi, l & 63);      // uniform
+    b.s = off >= 0 ? g.arena[off + lane] : 0.f;
+    b.y0 = g.r0 ? g.r0[64 * l + lane] : 0.f;
+    b.y1 = g.r1 ? g.r1[64 * l + lane] : 0.f;
+}
+// the step's view of utterance q's rows: `frow` = the table row of this step (walked by the step loop, gate_walk), `rem` = p % hop
+__device__ __forceinline__ GateStep gate_step(const DecUtt& q, const float* frow, int rem, int nlayers, int lane) {
+    GateStep g;
+    g.r0 = frow;
+    g.r1 = frow && q.fr.interp ? frow + q.fr.row : nullptr;
+    g.alpha = g.r1 ? __fdiv_rn((float)rem, (float)q.fr.hop) : 0.f;
+    g.arena = q.arena;
+    g.b_lo = lane < nlayers ? q.layers[lane].bfg : -1;
+    g.b_hi = 64 + lane < nlayers ? q.layers[64 + lane].bfg : -1;
+    return g;
+}
+// The table row of a launch's steps without a division per step: row and remainder of the first step once (pos0 / hop, a 64-bit
+// division), then one increment per step.  Wave-uniform; every thread of the chain workgroup keeps it (scalar registers).
+struct GateWalk { const float* frow; int rem; };
+__device__ __forceinline__ GateWalk gate_walk_open(const DecFrames& fr) {
+    GateWalk w{nullptr, 0};
+    if (fr.tab) {
+        const long long j = fr.pos0 / fr.hop;
+        w.frow = fr.tab + j * (long long)fr.row;
+        w.rem = (int)(fr.pos0 - j * fr.hop);
+    }
+    return w;
+}
+__device__ __forceinline__ void gate_walk_next(GateWalk& w, const DecFrames& fr) {
+    if (w.frow && ++w.rem == fr.hop) { w.rem = 0; w.frow += fr.row; }
+}
+// (static bias or 0) + frame value: the any-shape decoder's rule (decode_steps), bias_lerp never contracted -- a table of
+// zeros gives +0, the seed the unconditioned kernels start from
+__device__ __forceinline__ float gate_seed_of(const GateB& b, const GateStep& g) {
+    const float y = g.r1 ? bias_lerp(b.y0, b.y1, g.alpha) : b.y0;
+    return __fadd_rn(b.s, y);
+}
+// wave 1: the x[n-d] half of gate row `lane` of layer l -> aold[l][lane]; `seed`: the row's bias (GATE), else 0
+__device__ __forceinline__ void old_layer(const ChainLds& S, const OldW& w, int l, int lane, float seed) {
     const float* xo = S.xold + l * 32;                 // same address in every lane: broadcast reads
-    f2 A0 = {0.f, 0.f}, A1 = {0.f, 0.f};
+    f2 A0 = {seed, 0.f}, A1 = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float4 x4 = *reinterpret_cast<const float4*>(xo + 4 * j);
@@ -414,9 +468,19 @@ __device__ __forceinline__ void chain_wave(const ChainLds& S, const float* __res
     if (nlayers % kUnroll == 0) chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
     else chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
 }
-__device__ __forceinline__ void old_wave(const ChainLds& S, const float* __restrict__ P, int nlayers, int lane) {
+// GATE: every row starts from its bias (gate rows above), fetched like the weights -- one layer ahead, off the chain.  The
+// hand-off to the chain wave (aold, ready_old) is the same with and without: nothing is waited for that was not before.
+template <bool GATE>
+__device__ __forceinline__ void old_wave(const ChainLds& S, const float* __restrict__ P, int nlayers, int lane, const DecUtt& q,
+                                         const GateWalk& gw) {
     OldW wo[2];
+    GateB gb[2] = {};
+    GateStep g{};
     load_old(wo[0], P, 0, 4u * lane);
+    if (GATE) {
+        g = gate_step(q, gw.frow, gw.rem, nlayers, lane);
+        load_gate(gb[0], g, 0, lane);
+    }
     __syncthreads();
     for (int l0 = 0; l0 < nlayers; l0 += kUnroll) {
 #pragma unroll
@@ -424,8 +488,11 @@ __device__ __forceinline__ void old_wave(const ChainLds& S, const float* __restr
             const int l = l0 + u;
             if (l < nlayers) {
                 __builtin_amdgcn_s_waitcnt(0x0F70);          // as in the chain wave: exact counters
-                if (l + 1 < nlayers) load_old(wo[(u + 1) & 1], P, l + 1, 4u * lane);
-                old_layer(S, wo[u & 1], l, lane);
+                if (l + 1 < nlayers) {
+                    load_old(wo[(u + 1) & 1], P, l + 1, 4u * lane);
+                    if (GATE) load_gate(gb[(u + 1) & 1], g, l + 1, lane);
+                }
+                old_layer(S, wo[u & 1], l, lane, GATE ? gate_seed_of(gb[u & 1], g) : 0.f);
             }
         }
     }
@@ -504,6 +571,7 @@ __device__ __forceinline__ void draw_token(const ChainLds& S, const SampleCtl& s
     }
 }
 
+template <bool GATE>          // GATE: wave 1 seeds the gate rows with the handle's biases and table rows (gate rows, above)
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                         int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -514,6 +582,8 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float hb = chain_prologue(S, q, nlayers, tid);
     const unsigned t4 = 4u * (tid & 127);
+    GateWalk gw{nullptr, 0};
+    if (GATE) gw = gate_walk_open(q.fr);
 
     for (int it = 0; it < nsteps; ++it) {
         const unsigned n = (unsigned)(q.n0 + it);
@@ -524,7 +594,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
         if (wv == 0) {
             chain_wave(S, P, nlayers, lane);
         } else if (wv == 1) {
-            old_wave(S, P, nlayers, lane);
+            old_wave<GATE>(S, P, nlayers, lane, q, gw);
         } else {
             float skip0 = 0.f, skip1 = 0.f;
             SkipW w[2];
@@ -593,6 +663,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
         if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
+        if (GATE) gate_walk_next(gw, q.fr);
     }
     if (tid == 0) q.tok_ring[0] = S.s_tok[1];      // the token before the next one to be consumed
 }
@@ -629,6 +700,7 @@ static u64* x_area(const float* P, int nlayers) {
 
 // `wg`: this workgroup's role in its utterance's group of nine (0 = chain, 1..8 = skip rows): blockIdx.x for one utterance,
 // blockIdx.x % 9 in the batched launch (k_decode_fast3_batch)
+template <bool GATE>
 __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q, int nlayers, int nsteps, int prob_stride,
                                                   int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -688,6 +760,8 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
     const ChainLds S(sm);
     const float hb = chain_prologue(S, q, nlayers, tid);
     bool dead0 = false;                                   // this thread's wait for the logit shares gave up: wait for nothing any more
+    GateWalk gw{nullptr, 0};
+    if (GATE) gw = gate_walk_open(q.fr);
 
     for (int it = 0; it < nsteps; ++it) {
         const unsigned n = (unsigned)(q.n0 + it);
@@ -699,7 +773,7 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
         if (wv == 0) {
             chain_wave(S, P, nlayers, lane);
         } else if (wv == 1) {
-            old_wave(S, P, nlayers, lane);
+            old_wave<GATE>(S, P, nlayers, lane, q, gw);
         } else if (wv == 2) {
             __syncthreads();
             // the publisher: follows the chain through the layer counter in LDS and hands every layer's z to the other CUs
@@ -755,13 +829,15 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
         if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
+        if (GATE) gate_walk_next(gw, q.fr);
     }
     if (tid == 0) q.tok_ring[0] = S.s_tok[1];
 }
 
+template <bool GATE>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                          int apply_softmax, int do_sample, int head_act) {
-    decode_fast3_body((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
+    decode_fast3_body<GATE>((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
 }
 
 // N independent utterances in ONE launch: nine workgroups each (the single-GPU form of "replicas only", SURVEY 8(e): batch 1
@@ -774,9 +850,10 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nla
 // partners do not, so no wait is left without its entry, and a group that ends early simply ends.
 struct DecBatchArgs { DecUtt it[kDecMaxBatch]; };
 static_assert(sizeof(DecBatchArgs) + 4 * sizeof(int) <= 4096, "kernel arguments are passed by value: 4 KB at most");
+template <bool GATE>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int prob_stride, int head_act) {
     const int u = blockIdx.x / (kD10Skip + 1);
-    decode_fast3_body((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
+    decode_fast3_body<GATE>((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
@@ -804,8 +881,8 @@ int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
 }
 
 int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int apply_softmax, int do_sample, int head_act,
-                       bool three_wgs, hipStream_t s) {
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast, k_decode_fast3);
+                       bool three_wgs, bool gate_rows, hipStream_t s) {
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast<false>, k_decode_fast3<false>, k_decode_fast<true>, k_decode_fast3<true>);
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
         // per device, per call: cheap, and a process may drive several devices).  What the count cannot see -- other work
@@ -815,13 +892,13 @@ int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int a
             hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu >= kD10Skip + 1) {
             q.X = x_area(q.P, nlayers);
             zero_x(q.X, nlayers, s);
-            hipLaunchKernelGGL(k_decode_fast3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
+            hipLaunchKernelGGL(gate_rows ? k_decode_fast3<true> : k_decode_fast3<false>, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
                                prob_stride, apply_softmax, do_sample, head_act);
             WN_LAUNCH_CHECK();
             return WN_OK;
         }
     }
-    hipLaunchKernelGGL(k_decode_fast, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
+    hipLaunchKernelGGL(gate_rows ? k_decode_fast<true> : k_decode_fast<false>, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
                        apply_softmax, do_sample, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -836,7 +913,7 @@ int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps) {
 }
 
 int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
-                             bool same_weights, hipStream_t s) {
+                             bool same_weights, bool gate_rows, hipStream_t s) {
     if (!decode_fast_batch_ok(nlayers, n_utt, nsteps)) {
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
         return WN_ESHAPE;
@@ -846,7 +923,7 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
             wn::set_error("decode batch: utterance %d's step count %d outside [2, %d]", u, utt[u].nsteps, nsteps);
             return WN_EARG;
         }
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch);
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch<false>, k_decode_fast3_batch<true>);
     DecBatchArgs a{};
     for (int u = 0; u < n_utt; ++u) {
         DecUtt& q = a.it[u];
@@ -857,10 +934,11 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
         // 0's packed weights, embedding table and head bias -- the 28 chain workgroups then stream ONE 0.96 MB copy per step
         // through the XCDs' L2s instead of 28; the state (rings, token ring, exchange entries) stays per utterance.  An
         // utterance 0 that ends before the others leaves its packed weights in place -- a launch frees and rewrites nothing of
-        // a handle's weights -- and the others keep reading them.
+        // a handle's weights -- and the others keep reading them.  Gate rows are not part of P: an utterance's static gate
+        // biases (its arena) and frame table (DecUtt.fr) stay its own, so utterances of one model may differ in class and table.
         if (same_weights) { q.P = utt[0].P; q.hbias = utt[0].hbias; q.E = utt[0].E; }
     }
-    hipLaunchKernelGGL(k_decode_fast3_batch, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
+    hipLaunchKernelGGL(gate_rows ? k_decode_fast3_batch<true> : k_decode_fast3_batch<false>, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
                        prob_stride, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;

@@ -9,6 +9,12 @@ struct DecMeta {
     int Q, fwc, ncausal, fw, nlayers, Cr, Cs, nhead, head_act;
     int maxc;          // widest vector that has to sit in LDS
 };
+// Local conditioning: the frame table of one utterance as a step loop takes it.  tab == NULL: no table, and the loop
+// executes what it executed before tables existed.  Step `it` of the launch adds row (pos0 + it) / hop -- pos0 = the table's
+// phase (FrameTable) + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
+// interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
+// float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
+struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
 // One utterance's launch arguments of the specialised decode kernels (decoder_fast.hip): filled from its handle by
 // decoder.hip, passed to the kernels by value (the batched launch passes an array of them)
 struct DecUtt {
@@ -19,15 +25,19 @@ struct DecUtt {
     int nsteps;                        // batched launch: the utterance's own step count, the ONE word all nine of its workgroups
                                        // read (single runs pass theirs as a kernel argument and leave this 0)
     SampleCtl sc;                      // per utterance: its handle's wn_decoder_set_sampling
+    DecFrames fr;                      // WN_DECODER_GATE_ROWS handles: the utterance's own frame table (tab == NULL: none)
 };
 size_t decode_fast_pack_floats(int nlayers);
 int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s);
+// gate_rows (both launches): a WN_DECODER_GATE_ROWS handle that holds static gate biases (its own arena, DecLayer.bfg) or a frame
+// table (DecUtt.fr) -- the launch takes the instantiations whose wave 1 seeds every gate row with them; without it the launch
+// is the one it was before the flag existed
 int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int apply_softmax, int do_sample, int head_act,
-                       bool three_wgs, hipStream_t s);
+                       bool three_wgs, bool gate_rows, hipStream_t s);
 static constexpr int kDecMaxBatch = 28;                    // utterances per batched launch: 28 x 9 workgroups on 256 CUs
 int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps);
 // (nsteps: the launch's n, an upper bound of the utterances' counts, for the checks only: the kernel reads DecUtt.nsteps)
 int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
-                             bool same_weights, hipStream_t s);
+                             bool same_weights, bool gate_rows, hipStream_t s);
 int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up);
 }  // namespace wn

@@ -179,11 +179,12 @@ class FasterWaveNet(WaveNet):
         """``step_limit``: ``WnDecoderDesc.step_limit`` -- a handle of a ragged ``generate_batch`` call ends after its own
         utterance's steps (0: no limit).
         ``table``: (rows (n, sum 2 cd) float32 on the device, hop, phase) -- a locally conditioned model's handle copies one
-        utterance's frame table (``WnDecoderDesc.frame_bias``) at create / update time and counts its steps from there; such
-        handles are any-shape ones too.
+        utterance's frame table (``WnDecoderDesc.frame_bias``) at create / update time and counts its steps from there.
         ``cond``: [(bf, bg)] per residual layer (``condition_biases``) -- a globally conditioned model's handle holds ONE
-        class's folded gate biases, copied like any bias at create / update time.  Biased layers select the any-shape decoder
-        (one workgroup per utterance): a conditioned model of config 4's shape does not get the nine-workgroup kernel."""
+        class's folded gate biases, copied like any bias at create / update time.
+        A conditioned model (either kind) sets ``WN_DECODER_GATE_ROWS``: on config 4's shape its handles are then the
+        specialised decoder's -- wave 1 of the chain workgroup adds the biases and the table rows -- and on every other
+        shape the flag changes nothing.  An ordinary model with bias tensors sets no flag and keeps the any-shape decoder."""
         p = self.params
         L = self._flat_layers
         keep = dict(
@@ -208,6 +209,8 @@ class FasterWaveNet(WaveNet):
             setattr(d, k, C.cast(keep[k], C.POINTER(C.c_void_p)))
         d.head_act = ACT[self.fast_head_activation]
         d.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        if self.condition_classes or self.local_channels:
+            d.flags |= _lib.WN_DECODER_GATE_ROWS
         d.step_limit = int(step_limit)
         if table is not None:
             rows, hop, phase = table
@@ -455,7 +458,8 @@ class FasterWaveNet(WaveNet):
     # -- N utterances at once (new capability: the reference generates one utterance per process) ------------------------
     def _nine_workgroup_shape(self, flags) -> bool:
         """Whether ``wn_decoder_create`` gives this model the specialised decoder (csrc/decoder.hip ``fast_shape``: BASELINE
-        config 4's shape with the reference's default biases).  Only a forecast -- it picks the batch limit and the
+        config 4's shape with the reference's default biases; global and local conditioning do not change the answer, their
+        handles carry ``WN_DECODER_GATE_ROWS``).  Only a forecast -- it picks the batch limit and the
         ``n_samples == 2`` rule before any work; the library decides, and refuses a launch it does not take."""
         p = self.params
         L = self._flat_layers
@@ -463,9 +467,7 @@ class FasterWaveNet(WaveNet):
                 len(p.causal_conv_channels) == 1 and p.causal_conv_filter_width == 2 and p.residual_conv_filter_width == 2 and
                 self._Cr == 32 and self._Cs == 256 and list(p.softmax_conv_channels) == [256, 256] and len(L) <= 128 and
                 all(int(c) == 32 for c in p.residual_conv_channels) and self.causal_conv_layers[0].bshape is None and
-                all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)) and
-                not self.condition_classes and      # a conditioned model's handles hold gate biases: the any-shape decoder
-                not self.local_channels)             # ... and a locally conditioned model's a frame table
+                all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)))
 
     def _batch_prompts(self, initial_tokens, N):
         """``generate_batch``'s ``initial_tokens`` -> (the distinct windows, 1-D int32 each; the window index of every
@@ -517,8 +519,9 @@ class FasterWaveNet(WaveNet):
         batched launch (``wn_decoder_run_batch``) runs such chains side by side, each with a decoder handle of its own: nine
         workgroups per utterance and up to ``wn_decoder_batch_max()`` = 28 utterances per launch for config 4's shape, one
         workgroup per utterance and up to ``WN_DECODER_BATCH_MAX_ANY`` for every other model (any channels, filter widths,
-        causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``; a conditioned model of config 4's shape too: its
-        handles hold gate biases or a frame table).  More utterances run as several launches, one after another, dealt
+        causal layers, Q; ``WN_EXEC_FORCE_GENERIC``; ``storage="bf16"``).  A conditioned model of config 4's shape is on the
+        nine-workgroup form too: a class, a table and a phase per utterance, all reading one copy of the weights.
+        More utterances run as several launches, one after another, dealt
         longest first (``deal_launches``): a launch's step count is its longest utterance's, and with a length per utterance
         every handle carries ``step_limit`` = its own ``n_samples[u] - 1`` and its workgroups end there.  An utterance of
         length 1 decodes nothing and joins no launch.  Step 1 -- the full forward over the window, at batch 1 exactly as
@@ -580,9 +583,10 @@ class FasterWaveNet(WaveNet):
             # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
             outs = [torch.empty((r.n - 1,), device=self.device, dtype=torch.int32) if nine else res[i][1:] for i, r in enumerate(recs)]
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
-            if len({r.class_id for r in recs}) > 1:
+            # (nine-workgroup form: gate biases and frame tables are not part of the shared weights -- every utterance reads its own)
+            if not nine and len({r.class_id for r in recs}) > 1:
                 same = 0                                              # ... but hold different classes' biases
-            if self.local_channels and len({r.group[:1] + r.group[2:] for r in recs}) > 1:
+            if not nine and self.local_channels and len({r.group[:1] + r.group[2:] for r in recs}) > 1:
                 same = 0                                              # ... or different frame tables
             # launches of at most `limit` utterances, one after another; a launch's handles go longest first: on the any-shape
             # form that is roughly the order workgroups are dispatched in when they outnumber what the device holds
@@ -663,7 +667,7 @@ class FasterWaveNet(WaveNet):
         biases = {c: self.condition_biases(c) for c in sorted({r.class_id for r in recs})} if self.condition_classes else {None: None}
 
         def bring(h, r):
-            ft, ph = feats[r.group]       # (a handle is created WITH its table: that selects the any-shape decoder)
+            ft, ph = feats[r.group]       # (a handle is created WITH its table)
             h.bring(self, r.class_id, biases.get, None if ft is None else self._decoder_table(ft, ph, len(r.window)),
                     r.n - 1 if ragged else None)
         held = len(self._handles)
