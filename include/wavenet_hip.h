@@ -379,6 +379,20 @@ int wn_btc_to_nchw(const float* src, float* dst, int B, int C, int T, void* stre
  * a conditioned model's sampled tokens can differ from the any-shape decoder's at a near-tie of the cumulative distribution
  * (as for WN_DECODER_ONE_WORKGROUP); each form is deterministic. */
 #define WN_DECODER_GATE_ROWS 128u
+/* WnDecoderDesc.flags, on every shape: the handle's probability trace is the probability of each token it emits -- ONE float per
+ * step instead of a row of Q.  wn_decoder_run: prob_trace, when not NULL, points at n floats; element i receives the fp32
+ * probability of out_tokens[i] exactly as the row the draw consumed held it (post-temperature; top-k / top-p leave a kept
+ * entry's value untouched and the drawn token is a kept entry) -- the very float an unflagged handle in the same state writes to
+ * prob_trace[i * Q + out_tokens[i]].  The fallback at the end of the cumulative distribution (token Q - 1) reports whatever that
+ * entry holds then, 0.0f included; nothing is clamped.  wn_decoder_run_batch: prob_traces[u] is n_u floats (elements n_u .. n are
+ * not written), and all handles of a launch must agree on the flag (WN_EARG naming the first utterance that differs, before any
+ * device work).  The flag never changes which decoder a description selects, nor a token: a flagged and an unflagged handle in
+ * the same state, given the same uniforms, emit the same tokens bit for bit.  wn_decoder_step is not affected.  A handle's
+ * form is fixed at create: wn_decoder_update_weights with a description whose bit differs from the handle's is WN_EARG before
+ * any device work (the WN_DECODER_GATE_ROWS rule; the two bits and WN_DECODER_ONE_WORKGROUP combine freely).  In the kernels the
+ * thread that owns the drawn token stores its entry with one ordinary store per step; the full-row write and this one exclude
+ * each other per launch.  Without the flag every call does what it did before the flag existed. */
+#define WN_DECODER_TRACE_CHOSEN 256u
 typedef struct WnDecoderDesc {
     int Q, fw_causal, n_causal, fw, n_blocks, n_layers;  /* n_layers per block; dilation fw^l */
     int Cr, Cs, n_head;
@@ -396,6 +410,8 @@ typedef struct WnDecoderDesc {
     unsigned flags;                   /* WN_EXEC_FORCE_GENERIC: never the specialised 32/256-channel decode kernel;
                                          WN_DECODER_GATE_ROWS (see the define): gate biases and a frame table do not
                                          deselect that kernel;
+                                         WN_DECODER_TRACE_CHOSEN (see the define): prob_trace is one float per step, the
+                                         emitted token's probability, on every shape;
                                          WN_DECODER_ONE_WORKGROUP: wn_decoder_run of that kernel on ONE workgroup instead of
                                          nine (the chain | eight workgroups of skip rows and their share of the logits):
                                          same products, another summation order for the skip rows and the logits --
@@ -449,7 +465,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
  * previous token, computes p, draws with numpy's algorithm from uniforms[i] (float64 cumsum,
  * normalise, searchsorted right) and appends.  first_token is the newest token of the window the
  * state was loaded from plus one draw, i.e. the token emitted by the prefill step.  out_tokens (n)
- * receives the n emitted tokens; prob_trace (n*Q) is optional.                                  */
+ * receives the n emitted tokens; prob_trace (n*Q; n on a WN_DECODER_TRACE_CHOSEN handle) is optional. */
 int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, int n,
                    int32_t* out_tokens, float* prob_trace, void* stream);
 /* ABI 4.  n_handles independent utterances in ONE launch (generate.py:9-60 is batch 1 with a strict sample-to-sample
@@ -476,6 +492,9 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
  *     previous call's table copy (not its launch) before it rewrites the pinned image of the table.
  * A handle created with WN_DECODER_ONE_WORKGROUP is refused (WN_ESHAPE): that kernel has no batched form.  Every refusal
  * comes before any device work.
+ * WN_DECODER_TRACE_CHOSEN: the trace's form is the launch's, so the handles must all carry the flag or all lack it (WN_EARG
+ * naming the first utterance that differs from utterance 0, every handle's state left alone); with it prob_traces[u] is n_u
+ * floats -- the probability of each token utterance u emitted -- instead of n_u rows of Q.
  * A length per utterance (WnDecoderDesc.step_limit).  Utterance u runs n_u = min(n, left_u) steps, left_u = its handle's
  * step_limit minus the steps run since the create / update call that set it (the counter the frame table shares), or n without a
  * limit; handles with and without a limit may share a launch.  Everything per utterance uses n_u: the frame-table check, the

@@ -48,6 +48,8 @@ struct Decoder {
     bool gate_bias = false;       // ... and the last create / update gave it static gate biases (else its 64 floats per layer hold 0)
     bool gate_rows = false;       // created with WN_DECODER_GATE_ROWS (the handle's form is fixed at create): a fast handle that
                                   // takes static gate biases and a frame table -- wave 1 of the chain workgroup adds them
+    bool trace_chosen = false;    // created with WN_DECODER_TRACE_CHOSEN (fixed at create, on every shape): a run's prob_trace is one
+                                  // float per step, the drawn token's probability, not a row of Q
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
     SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
     // wn_decoder_run_batch on any-shape handles, as handle 0 of the call: the per-utterance table (DecAnyUtt) in device
@@ -308,7 +310,7 @@ __device__ __forceinline__ void decode_steps(
             for (int q = tid; q < M.Q; q += NT) hin[q] = expf(hin[q] - m) * inv;
             __syncthreads();
         }
-        if (prob_out)
+        if (prob_out && prob_stride)          // the full row; prob_stride == 0 (kProbChosen): one float per step, at the draw below
             for (int q = tid; q < M.Q; q += NT) prob_out[(long long)it * prob_stride + q] = hin[q];
         if (do_sample) {
             if (filt)                    // top-k / top-p: the trace above holds the row as the filter receives it
@@ -326,6 +328,9 @@ __device__ __forceinline__ void decode_steps(
                 if (idx >= M.Q) idx = M.Q - 1;
                 s_token = idx;
                 out_tokens[it] = idx;
+                // WN_DECODER_TRACE_CHOSEN: the drawn token's entry of the row the draw consumed (the filter leaves a kept entry
+                // as it was, and a drawn token is a kept one); nothing clamped
+                if (prob_out && !prob_stride) prob_out[it] = hin[idx];
             }
         }
         __syncthreads();
@@ -344,13 +349,14 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
 
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
 // never wait for each other, so any number of them may be queued behind the CUs -- and each runs its utterance's own step
-// count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.
+// count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.  prob_stride is the
+// launch's (M.Q, or kProbChosen when the handles were created with WN_DECODER_TRACE_CHOSEN: they must agree).
 template <bool LERP>
-__global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt) {
+__global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int prob_stride) {
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
     decode_steps<LERP>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
-                 q.prob_out, M.Q, 1, 1, q.sc, q.fr);
+                 q.prob_out, prob_stride, 1, 1, q.sc, q.fr);
 }
 
 // ---- host side -------------------------------------------------------------------------------
@@ -632,6 +638,7 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
         D->three_wgs = !(d->flags & WN_DECODER_ONE_WORKGROUP);
         D->gate_rows = (d->flags & WN_DECODER_GATE_ROWS) != 0;
     }
+    D->trace_chosen = (d->flags & WN_DECODER_TRACE_CHOSEN) != 0;
     if ((rc = pack_weights(D, d, s))) return rc;
     if ((rc = take_frames(D, d, s))) return rc;
     *handle = built.release();
@@ -665,6 +672,9 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
     WN_CHECK_ARG(!D->fastP || ((d->flags & WN_DECODER_GATE_ROWS) != 0) == D->gate_rows,
                  "wn_decoder_update_weights: the description %s WN_DECODER_GATE_ROWS, the handle was created %s it: a handle's form "
                  "is fixed at create", d->flags & WN_DECODER_GATE_ROWS ? "carries" : "lacks", D->gate_rows ? "with" : "without");
+    WN_CHECK_ARG(((d->flags & WN_DECODER_TRACE_CHOSEN) != 0) == D->trace_chosen,
+                 "wn_decoder_update_weights: the description %s WN_DECODER_TRACE_CHOSEN, the handle was created %s it: a handle's form "
+                 "is fixed at create", d->flags & WN_DECODER_TRACE_CHOSEN ? "carries" : "lacks", D->trace_chosen ? "with" : "without");
     for (int j = 0; D->gate_rows && j < D->meta.nlayers; ++j)
         WN_CHECK_ARG(!(d->bf && d->bf[j]) == !(d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
     if ((rc = check_frame_desc(D, d))) return rc;
@@ -699,20 +709,23 @@ int wn_decoder_load_state(void* handle, const int32_t* tokens, int W, const floa
     return WN_OK;
 }
 
+// floats between the rows of a run's prob_trace: Q, or kProbChosen on a WN_DECODER_TRACE_CHOSEN handle
+static int trace_stride(const Decoder* D) { return D->trace_chosen ? kProbChosen : D->meta.Q; }
+
 // n steps were launched: the one writer of both counters after create / update / load_state
 static void advance(Decoder* D, long long n) { D->step += n; D->since_set += n; }
 
 // wn_decoder_step / wn_decoder_run behind their own argument checks: n steps of one handle.  A run that would read past
 // the frame table or pass WnDecoderDesc.step_limit is refused before any device work, never clamped
 static int run_one(const char* fn, Decoder* D, int token, const double* uniforms, int n, int32_t* out_tokens, float* prob,
-                   int apply_softmax, int do_sample, const SampleCtl& sc, bool three_wgs, hipStream_t s) {
+                   int prob_stride, int apply_softmax, int do_sample, const SampleCtl& sc, bool three_wgs, hipStream_t s) {
     WN_CHECK_ARG(D->step + n < (1ll << 31), "%s: step counter overflow", fn);
     if (int rc = check_frames(fn, D, n)) return rc;
     WN_CHECK_ARG(D->step_limit <= 0 || D->since_set + n <= D->step_limit,
                  "%s: n = %lld more steps would pass step_limit = %d (%lld steps run since it was set)", fn, (long long)n,
                  D->step_limit, D->since_set);
     if (D->fastP) {
-        if (int rc = decode_fast_launch(fast_utt(D, token, uniforms, out_tokens, prob, sc), D->meta.nlayers, n, D->meta.Q,
+        if (int rc = decode_fast_launch(fast_utt(D, token, uniforms, out_tokens, prob, sc), D->meta.nlayers, n, prob_stride,
                                         apply_softmax, do_sample, D->meta.head_act, three_wgs, gate_launch(D), s))
             return rc;
         if (three_wgs) D->ran_multi = n > 1;       // (a single step is on one workgroup: an earlier run's entry stays readable)
@@ -721,7 +734,7 @@ static int run_one(const char* fn, Decoder* D, int token, const double* uniforms
         const DecAnyUtt q = any_utt(D, token, uniforms, out_tokens, prob, n, sc);
         const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
         hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, s, D->meta, q.causal, q.layers, q.heads, q.arena, q.tok_ring,
-                           q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out, D->meta.Q, apply_softmax, do_sample,
+                           q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out, prob_stride, apply_softmax, do_sample,
                            q.sc, q.fr);
         WN_LAUNCH_CHECK();
     }
@@ -733,7 +746,7 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
     Decoder* D = (Decoder*)handle;
     WN_CHECK_ARG(D && prob, "wn_decoder_step: bad argument");
     WN_CHECK_ARG(token >= 0 && token < D->meta.Q, "wn_decoder_step: token %d outside [0,%d)", token, D->meta.Q);
-    return run_one("wn_decoder_step", D, (int)token, nullptr, 1, nullptr, prob, apply_softmax, 0, SampleCtl(), false,
+    return run_one("wn_decoder_step", D, (int)token, nullptr, 1, nullptr, prob, D->meta.Q, apply_softmax, 0, SampleCtl(), false,
                    as_stream(stream));
 }
 
@@ -742,7 +755,7 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     Decoder* D = (Decoder*)handle;
     WN_CHECK_ARG(D && uniforms && out_tokens && n > 0, "wn_decoder_run: bad argument");
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
-    return run_one("wn_decoder_run", D, (int)first_token, uniforms, n, out_tokens, prob_trace, 1, 1, launch_ctl(D), D->three_wgs,
+    return run_one("wn_decoder_run", D, (int)first_token, uniforms, n, out_tokens, prob_trace, trace_stride(D), 1, 1, launch_ctl(D), D->three_wgs,
                    as_stream(stream));
 }
 
@@ -789,7 +802,7 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     WN_HIP(hipEventRecord(D0->batch_copied, s));
     const auto kern = lerp_table(D0) ? k_decode_batch<true> : k_decode_batch<false>;     // (the handles agree on the mode)
     hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
-                       n_handles);
+                       n_handles, trace_stride(D0));
     WN_LAUNCH_CHECK();
     return WN_OK;
 }
@@ -856,6 +869,10 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_SHAPE(!D->fastP || D->three_wgs, "wn_decoder_run_batch: utterance %d's decoder was created with WN_DECODER_ONE_WORKGROUP: "
                                                   "the one-workgroup specialised kernel has no batched form", u);
         if (int rc = same_model(D, D0, u, same_weights)) return rc;
+        // the trace's form is the launch's (one stride for every workgroup)
+        WN_CHECK_ARG(D->trace_chosen == D0->trace_chosen, "wn_decoder_run_batch: utterance %d was created %s WN_DECODER_TRACE_CHOSEN, "
+                     "utterance 0 %s it: the handles of a launch agree on the flag", u, D->trace_chosen ? "with" : "without",
+                     D0->trace_chosen ? "with" : "without");
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         if (int rc = steps_left(D, u, n, any, &nu[u])) return rc;
         const FrameTable &F = D->frames, &F0 = D0->frames;
@@ -873,7 +890,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     WN_CHECK_SHAPE(any || decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream))
-                       : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, D0->meta.Q, D0->meta.head_act, same_weights != 0,
+                       : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, trace_stride(D0), D0->meta.head_act, same_weights != 0,
                                                   gate, as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {

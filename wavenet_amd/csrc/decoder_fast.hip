@@ -465,8 +465,17 @@ __device__ __forceinline__ void chain_wave(const ChainLds& S, const float* __res
     const float xc0 = S.xcur[lane & 31];
     wait_count(S.ready_old, 1);
     const float a0 = S.aold[lane];
-    if (nlayers % kUnroll == 0) chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
-    else chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
+    // The partial-trip walk (a stack that is no whole number of ten-layer trips) is entered with layer 0's weights LANDED: on the
+    // way into chain_run<false> hipcc copied all 64 registers of w[0] to others, between the request above and the wait at the
+    // top of the walk -- a copy of registers a load still in flight had not written (stale weights for layer 0 whenever the load
+    // was slow: the first launch on cold caches, then intermittently; a six-layer stack's tokens differed from run to run).
+    // The wait costs nothing: the walk begins with the same one.  The whole-trip walk is entered as ever.
+    if (nlayers % kUnroll == 0) {
+        chain_run<true>(S, P, nlayers, lane, xc0, a0, w, co);
+    } else {
+        chain_landed(w[0]);
+        chain_run<false>(S, P, nlayers, lane, xc0, a0, w, co);
+    }
 }
 // GATE: every row starts from its bias (gate rows above), fetched like the weights -- one layer ahead, off the chain.  The
 // hand-off to the chain wave (aold, ready_old) is the same with and without: nothing is waited for that was not before.
@@ -571,7 +580,17 @@ __device__ __forceinline__ void draw_token(const ChainLds& S, const SampleCtl& s
     }
 }
 
-template <bool GATE>          // GATE: wave 1 seeds the gate rows with the handle's biases and table rows (gate rows, above)
+// WN_DECODER_TRACE_CHOSEN (the CHOSEN instantiations of the three kernels: the host takes them when prob_stride == kProbChosen,
+// and the others execute what they executed before the flag existed): step `it`'s trace is one float, the drawn token's
+// entry of the row the draw consumed.  Behind the step's closing barrier the token is in s_tok[0] and the row still in lg
+// (thread `tid` rewrites lg[tid] itself, next step); the filter left a kept entry as it was and the drawn token is a kept
+// one, so the thread that owns it stores the float the full-row form writes at [it * Q + token].  One ordinary per-lane
+// store per step; the full-row write and this one exclude each other (an instantiation has one or the other).
+__device__ __forceinline__ void store_chosen(const ChainLds& S, float* __restrict__ prob_out, int it, int tid) {
+    if (prob_out && tid == S.s_tok[0]) prob_out[it] = S.lg[tid];
+}
+
+template <bool GATE, bool CHOSEN>          // GATE: wave 1 seeds the gate rows with the handle's biases and table rows (gate rows, above)
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                         int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -658,11 +677,12 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
         }
         if (apply_softmax) v = softmax_row(S, v, q.sc.inv_temp, tid);
         S.lg[tid] = v;
-        if (q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
+        if (!CHOSEN && q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
         if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
+        if (CHOSEN) store_chosen(S, q.prob_out, it, tid);
         if (GATE) gate_walk_next(gw, q.fr);
     }
     if (tid == 0) q.tok_ring[0] = S.s_tok[1];      // the token before the next one to be consumed
@@ -700,7 +720,7 @@ static u64* x_area(const float* P, int nlayers) {
 
 // `wg`: this workgroup's role in its utterance's group of nine (0 = chain, 1..8 = skip rows): blockIdx.x for one utterance,
 // blockIdx.x % 9 in the batched launch (k_decode_fast3_batch)
-template <bool GATE>
+template <bool GATE, bool CHOSEN>
 __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q, int nlayers, int nsteps, int prob_stride,
                                                   int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -824,20 +844,21 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
         }
         if (apply_softmax) v = softmax_row(S, v, q.sc.inv_temp, tid);
         S.lg[tid] = v;
-        if (q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
+        if (!CHOSEN && q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
         if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
+        if (CHOSEN) store_chosen(S, q.prob_out, it, tid);
         if (GATE) gate_walk_next(gw, q.fr);
     }
     if (tid == 0) q.tok_ring[0] = S.s_tok[1];
 }
 
-template <bool GATE>
+template <bool GATE, bool CHOSEN>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                          int apply_softmax, int do_sample, int head_act) {
-    decode_fast3_body<GATE>((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
+    decode_fast3_body<GATE, CHOSEN>((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
 }
 
 // N independent utterances in ONE launch: nine workgroups each (the single-GPU form of "replicas only", SURVEY 8(e): batch 1
@@ -850,10 +871,10 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nla
 // partners do not, so no wait is left without its entry, and a group that ends early simply ends.
 struct DecBatchArgs { DecUtt it[kDecMaxBatch]; };
 static_assert(sizeof(DecBatchArgs) + 4 * sizeof(int) <= 4096, "kernel arguments are passed by value: 4 KB at most");
-template <bool GATE>
+template <bool GATE, bool CHOSEN>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int prob_stride, int head_act) {
     const int u = blockIdx.x / (kD10Skip + 1);
-    decode_fast3_body<GATE>((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
+    decode_fast3_body<GATE, CHOSEN>((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
@@ -882,7 +903,10 @@ int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
 
 int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int apply_softmax, int do_sample, int head_act,
                        bool three_wgs, bool gate_rows, hipStream_t s) {
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast<false>, k_decode_fast3<false>, k_decode_fast<true>, k_decode_fast3<true>);
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast<false, false>, k_decode_fast3<false, false>, k_decode_fast<true, false>,
+                    k_decode_fast3<true, false>, k_decode_fast<false, true>, k_decode_fast3<false, true>, k_decode_fast<true, true>,
+                    k_decode_fast3<true, true>);
+    const bool chosen = prob_stride == kProbChosen;          // (a sampling launch: wn_decoder_step passes Q)
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
         // per device, per call: cheap, and a process may drive several devices).  What the count cannot see -- other work
@@ -892,13 +916,17 @@ int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int a
             hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu >= kD10Skip + 1) {
             q.X = x_area(q.P, nlayers);
             zero_x(q.X, nlayers, s);
-            hipLaunchKernelGGL(gate_rows ? k_decode_fast3<true> : k_decode_fast3<false>, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
+            const auto k3 = chosen ? (gate_rows ? k_decode_fast3<true, true> : k_decode_fast3<false, true>)
+                                   : (gate_rows ? k_decode_fast3<true, false> : k_decode_fast3<false, false>);
+            hipLaunchKernelGGL(k3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
                                prob_stride, apply_softmax, do_sample, head_act);
             WN_LAUNCH_CHECK();
             return WN_OK;
         }
     }
-    hipLaunchKernelGGL(gate_rows ? k_decode_fast<true> : k_decode_fast<false>, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
+    const auto k1 = chosen ? (gate_rows ? k_decode_fast<true, true> : k_decode_fast<false, true>)
+                           : (gate_rows ? k_decode_fast<true, false> : k_decode_fast<false, false>);
+    hipLaunchKernelGGL(k1, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
                        apply_softmax, do_sample, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;
@@ -923,7 +951,9 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
             wn::set_error("decode batch: utterance %d's step count %d outside [2, %d]", u, utt[u].nsteps, nsteps);
             return WN_EARG;
         }
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch<false>, k_decode_fast3_batch<true>);
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch<false, false>, k_decode_fast3_batch<true, false>,
+                    k_decode_fast3_batch<false, true>, k_decode_fast3_batch<true, true>);
+    const bool chosen = prob_stride == kProbChosen;
     DecBatchArgs a{};
     for (int u = 0; u < n_utt; ++u) {
         DecUtt& q = a.it[u];
@@ -938,7 +968,9 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
         // biases (its arena) and frame table (DecUtt.fr) stay its own, so utterances of one model may differ in class and table.
         if (same_weights) { q.P = utt[0].P; q.hbias = utt[0].hbias; q.E = utt[0].E; }
     }
-    hipLaunchKernelGGL(gate_rows ? k_decode_fast3_batch<true> : k_decode_fast3_batch<false>, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
+    const auto kb = chosen ? (gate_rows ? k_decode_fast3_batch<true, true> : k_decode_fast3_batch<false, true>)
+                           : (gate_rows ? k_decode_fast3_batch<true, false> : k_decode_fast3_batch<false, false>);
+    hipLaunchKernelGGL(kb, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
                        prob_stride, head_act);
     WN_LAUNCH_CHECK();
     return WN_OK;

@@ -14,6 +14,9 @@ struct DecMeta {
 // phase (FrameTable) + the steps run since the table was set (Decoder::since_set) -- to every layer's gate pre-activations.
 // interp != 0 (WnDecoderDesc.frame_interp, linear interpolation): with p = pos0 + it, j = p / hop and alpha = float(p % hop) /
 // float(hop) the step adds r[j] + alpha (r[j + 1] - r[j]) (bias_lerp, as the layer kernels form it).
+// prob_stride of the step loops (both files): the floats between two rows of the probability trace, Q -- or kProbChosen: the
+// trace is ONE float per step, the probability of the token drawn (WN_DECODER_TRACE_CHOSEN).  One or the other per launch.
+static constexpr int kProbChosen = 0;
 struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
 // One utterance's launch arguments of the specialised decode kernels (decoder_fast.hip): filled from its handle by
 // decoder.hip, passed to the kernels by value (the batched launch passes an array of them)

@@ -93,18 +93,25 @@ def silence_window(params_or_Q, width):
 class _Handle(object):
     """A decoder handle of the library and what the host knows about it: whether the weights changed since it was packed
     (``stale``; a handle that holds a step limit stays stale, so that the next call takes the limit off), the class whose
-    folded gate biases it holds, and whether it holds a frame table."""
+    folded gate biases it holds, whether it holds a frame table, and its form -- ``chosen``: created with
+    ``WN_DECODER_TRACE_CHOSEN``, its probability trace is one float per step."""
 
     def __init__(self):
-        self.h, self.stale, self.class_id, self.has_table = None, True, None, False
+        self.h, self.stale, self.class_id, self.has_table, self.chosen = None, True, None, False, False
 
-    def bring(self, net, class_id, cond_of, table=None, step_limit=None):
+    def bring(self, net, class_id, cond_of, table=None, step_limit=None, chosen=False):
         """Create the handle, or update it when it is stale, holds another class, or is given a table or a limit (the
         update is the library's one way to set either and to start their step count again; it also re-packs the weights);
-        otherwise nothing.  ``cond_of(class_id)``: the class's folded biases, asked for only when they are packed."""
+        otherwise nothing.  ``cond_of(class_id)``: the class's folded biases, asked for only when they are packed.
+        ``chosen``: the form asked for; a handle of the other form is destroyed and created anew (a handle's form is fixed
+        at create)."""
+        if self.h is not None and self.chosen != bool(chosen):
+            self.destroy()
+            self.stale, self.class_id, self.has_table = True, None, False
         if self.h is not None and not (self.stale or self.class_id != class_id or table is not None or step_limit is not None):
             return
-        d, keep = net._desc(cond_of(class_id), table, step_limit or 0)
+        d, keep = net._desc(cond_of(class_id), table, step_limit or 0, chosen)
+        self.chosen = bool(chosen)
         if self.h is None:
             h = C.c_void_p()
             check(_lib.lib().wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
@@ -134,6 +141,7 @@ class FasterWaveNet(WaveNet):
                  local_interp: str = "repeat"):
         self._dec = _Handle()              # the batch-1 handle
         self._handles = []                 # generate_batch's handles (one per utterance), created on demand
+        self._trace_chosen = False         # the form of the batch-1 handle: generate(..., return_chosen=True) alone sets it
         self.prev_causal_outputs = None
         self.prev_residual_outputs = None
         self.keep_window = True            # keep the logits of the whole window on the device: _forward_one_step's reference shape
@@ -175,8 +183,10 @@ class FasterWaveNet(WaveNet):
             self.storage = storage
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self, cond=None, table=None, step_limit=0):
-        """``step_limit``: ``WnDecoderDesc.step_limit`` -- a handle of a ragged ``generate_batch`` call ends after its own
+    def _desc(self, cond=None, table=None, step_limit=0, chosen=False):
+        """``chosen``: ``WN_DECODER_TRACE_CHOSEN`` -- the handle's probability trace is the probability of each token it emits,
+        one float per step (``return_chosen``); it selects no other decoder and changes no token.
+        ``step_limit``: ``WnDecoderDesc.step_limit`` -- a handle of a ragged ``generate_batch`` call ends after its own
         utterance's steps (0: no limit).
         ``table``: (rows (n, sum 2 cd) float32 on the device, hop, phase) -- a locally conditioned model's handle copies one
         utterance's frame table (``WnDecoderDesc.frame_bias``) at create / update time and counts its steps from there.
@@ -211,6 +221,8 @@ class FasterWaveNet(WaveNet):
         d.flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         if self.condition_classes or self.local_channels:
             d.flags |= _lib.WN_DECODER_GATE_ROWS
+        if chosen:
+            d.flags |= _lib.WN_DECODER_TRACE_CHOSEN
         d.step_limit = int(step_limit)
         if table is not None:
             rows, hop, phase = table
@@ -274,7 +286,10 @@ class FasterWaveNet(WaveNet):
                 raise Exception("this model is globally conditioned: prefill with condition= first")
         if self.local_channels and table is None and dec.stale:
             raise Exception("the weights changed since the last prefill: prefill with local= again")
-        dec.bring(self, class_id, self.condition_biases if self.condition_classes else lambda c: None, table)
+        if dec.h is not None and dec.chosen != self._trace_chosen and self.local_channels and table is None:
+            raise Exception("the batch-1 handle changes its form (return_chosen): prefill with local= again")
+        dec.bring(self, class_id, self.condition_biases if self.condition_classes else lambda c: None, table,
+                  chosen=self._trace_chosen)
         return dec.h
 
     # -- the reference's face -------------------------------------------------------------------
@@ -399,7 +414,7 @@ class FasterWaveNet(WaveNet):
         return out
 
     def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False,
-                 temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, local_phase=0):
+                 temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, local_phase=0, return_chosen: bool = False):
         """Emit ``n_samples`` tokens.  Step 1 is the full forward over the initial window (ReLU head,
         like the reference's first ``_forward_one_step`` call); steps 2.. run inside one persistent
         kernel with the ELU head.  ``uniforms[i]`` is the float64 draw numpy's ``choice`` would make
@@ -414,9 +429,17 @@ class FasterWaveNet(WaveNet):
 
         ``local`` (locally conditioned models): the utterance's (F, n) features from its first sample on, prompt included;
         ``local_phase``: where that sample lies inside column 0.  Generating more samples than the features cover raises
-        before anything runs."""
+        before anything runs.
+
+        ``return_chosen``: also return ``chosen``, (n_samples,) float32 on the device -- the probability the model gave each
+        token it emitted, ``chosen[i] == probs[i, tokens[i]]`` of a ``return_probs`` run bit for bit (element 0 from the
+        prefill row the first draw consumed, the rest written by the decoder, one float per step:
+        ``WN_DECODER_TRACE_CHOSEN``).  ``sampling.chosen_nll(chosen)`` is the utterance's nats per sample.  The tokens are
+        those of a run without it.  Returns ``(tokens, chosen)``; with ``return_probs`` as well ``(tokens, probs, chosen)``,
+        on the full-row handle, ``chosen`` gathered from ``probs``."""
         Q = self.params.quantization_steps
         class_id = self._class_id(condition)
+        self._trace_chosen = bool(return_chosen) and not return_probs
         sampling.check_controls(temperature, top_k, top_p)
         top_k, top_p = int(top_k), float(top_p)
         if initial_tokens is None:
@@ -441,11 +464,15 @@ class FasterWaveNet(WaveNet):
         probs = torch.empty((n_samples, Q), device=self.device, dtype=torch.float32) if return_probs else None
         if return_probs:
             probs[0] = first_prob[0]
+        chosen = torch.empty((n_samples,), device=self.device, dtype=torch.float32) if self._trace_chosen else None
+        if chosen is not None:
+            chosen[:1] = first_prob[0].gather(0, out[:1].long())
         if n_samples > 1:
             first = int(out[0].item())
             check(lib.wn_decoder_set_sampling(self._decoder(), float(temperature), top_k, top_p), "wn_decoder_set_sampling")
             check(lib.wn_decoder_run(self._decoder(), first, ptr(u[1:]), n_samples - 1, ptr(out[1:]),
-                                     ptr(probs[1:]) if return_probs else None, stream_ptr()), "wn_decoder_run")
+                                     ptr(probs[1:]) if return_probs else ptr(chosen[1:]) if chosen is not None else None,
+                                     stream_ptr()), "wn_decoder_run")
             # the nine-workgroup run reports a wait that gave up (workgroups not all resident) instead of trapping: its
             # tokens would be void.  One 8-byte read-back; generate() hands tokens to the host anyway.
             check(lib.wn_decoder_status(self._decoder(), stream_ptr()), "wn_decoder_status")
@@ -453,7 +480,10 @@ class FasterWaveNet(WaveNet):
             # on from here), but the host-side window history -- what _forward_one_step(..., full_window=True) returns
             # the older columns from -- still holds the prefill state: drop it rather than answer with a stale window
             self._hist = None
-        return (out, probs) if return_probs else out
+        if return_chosen and return_probs:
+            chosen = probs.gather(1, out.long()[:, None])[:, 0].contiguous()
+        res = (out,) + ((probs,) if return_probs else ()) + ((chosen,) if return_chosen else ())
+        return res if len(res) > 1 else out
 
     # -- N utterances at once (new capability: the reference generates one utterance per process) ------------------------
     def _nine_workgroup_shape(self, flags) -> bool:
@@ -500,7 +530,7 @@ class FasterWaveNet(WaveNet):
         return prompts, which
 
     def generate_batch(self, n_samples, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
-                       condition=None, local=None, local_phase=0):
+                       condition=None, local=None, local_phase=0, return_chosen: bool = False):
         """N independent utterances at once.  ``n_samples`` an int: ``uniforms`` is (N, >= n_samples) float64, utterance u draws
         with ``uniforms[u]``, and (N, n_samples) int32 tokens on the device come back.  ``n_samples`` a sequence of N positive
         ints -- a length per utterance: ``uniforms`` is an (N, >= max) array or a list of N 1-D arrays, and a LIST of N 1-D int32
@@ -527,7 +557,12 @@ class FasterWaveNet(WaveNet):
         length 1 decodes nothing and joins no launch.  Step 1 -- the full forward over the window, at batch 1 exactly as
         ``generate`` runs it -- runs once per distinct (window, class, features, phase).  What still runs as a loop over
         ``generate()``: ``WN_DECODER_ONE_WORKGROUP``, any utterance of length 2 on the nine-workgroup form, and a device the
-        nine-workgroup launch does not fit."""
+        nine-workgroup launch does not fit.
+
+        ``return_chosen``: ``(tokens, chosen)`` comes back, ``chosen`` float32 on the device in the shape of the tokens --
+        (N, n_samples), or a list of N 1-D tensors -- row u the probabilities ``generate(..., return_chosen=True)`` gives for
+        utterance u, bit for bit.  The handles of such a call are ``WN_DECODER_TRACE_CHOSEN`` ones (a trace of one float per
+        step and utterance, not a row of Q); handles of the other form are created anew, and a launch never mixes the two."""
         ragged = not isinstance(n_samples, (int, np.integer))
         recs, feats = self._batch_plan(n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase)
         N, Q, lib = len(recs), self.params.quantization_steps, _lib.lib()
@@ -536,7 +571,7 @@ class FasterWaveNet(WaveNet):
         flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
         nine = self._nine_workgroup_shape(flags)
         if nine and (any(r.n == 2 for r in recs) or flags & _lib.WN_DECODER_ONE_WORKGROUP):
-            return self._generate_batch_loop(recs, ragged)
+            return self._generate_batch_loop(recs, ragged, return_chosen)
         limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
         live = [i for i in range(N) if recs[i].n > 1]                  # the utterances that decode at all
         # a result is a 1-D tensor per utterance, its uniforms likewise: rows of one (N, n) tensor and of one upload for
@@ -546,13 +581,16 @@ class FasterWaveNet(WaveNet):
             u_dev = [torch.as_tensor(r.u).to(self.device) for r in recs]
             u0 = torch.as_tensor(np.array([r.u[0] for r in recs], dtype=np.float64)).to(self.device)
             res = [torch.empty((r.n,), device=self.device, dtype=torch.int32) for r in recs]
+            ch = [torch.empty((r.n,), device=self.device, dtype=torch.float32) for r in recs] if return_chosen else None
         else:
             u = torch.as_tensor(np.stack([r.u for r in recs])).to(self.device)
             u_dev, u0 = list(u), u[:, 0].contiguous()
             out = torch.empty((N, recs[0].n), device=self.device, dtype=torch.int32)
             res = list(out)
+            ch_all = torch.empty((N, recs[0].n), device=self.device, dtype=torch.float32) if return_chosen else None
+            ch = list(ch_all) if return_chosen else None
         if live:
-            self._batch_handles(recs, feats, ragged)
+            self._batch_handles(recs, feats, ragged, return_chosen)
         # one prefill per group, at batch 1 as generate() runs it; the decoder states of its utterances are seeded from it,
         # and its first row (one per distinct temperature) is what generate() draws the first token from
         self.prev_causal_outputs = None
@@ -578,6 +616,13 @@ class FasterWaveNet(WaveNet):
                 res[i][:1] = first[i:i + 1]
         else:
             out[:, 0] = first                                        # (one copy: a copy per row costs 20 us a row)
+        if return_chosen:                                            # element 0: the prefill row the first draw consumed
+            ch0 = torch.cat(first_rows, dim=0).gather(1, first.long()[:, None])[:, 0]
+            if ragged:
+                for i in range(N):
+                    ch[i][:1] = ch0[i:i + 1]
+            else:
+                ch_all[:, 0] = ch0
         if live:
             firsts = [int(v) for v in first.cpu().tolist()]
             # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
@@ -594,15 +639,18 @@ class FasterWaveNet(WaveNet):
                 sel = [live[j] for j in idx]
                 rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._handles[i].h.value for i in sel]), len(sel),
                                               (C.c_int32 * len(sel))(*[firsts[i] for i in sel]), ptr_array([u_dev[i][1:] for i in sel]),
-                                              n_launch, ptr_array([outs[i] for i in sel]), None, same, stream_ptr())
+                                              n_launch, ptr_array([outs[i] for i in sel]),
+                                              ptr_array([ch[i][1:] for i in sel]) if return_chosen else None, same, stream_ptr())
                 if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
-                    return self._generate_batch_loop(recs, ragged)
+                    return self._generate_batch_loop(recs, ragged, return_chosen)
                 check(rc, "wn_decoder_run_batch")
             for i in (live if nine else live[:1]):                    # any-shape: nothing can give up; one synchronise
                 check(lib.wn_decoder_status(self._handles[i].h, stream_ptr()), "wn_decoder_status")
             if nine:
                 for i in live:
                     res[i][1:] = outs[i]
+        if return_chosen:
+            return (res, ch) if ragged else (out, ch_all)
         return res if ragged else out
 
     def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase):
@@ -659,8 +707,9 @@ class FasterWaveNet(WaveNet):
                 covered[key] = r.n
         return recs, {r.group: checked[r.group[:1] + r.group[2:]] for r in recs}
 
-    def _batch_handles(self, recs, feats, ragged):
-        """A handle per utterance with its sampling controls, holding its class's biases, its frame table and, in a ragged
+    def _batch_handles(self, recs, feats, ragged, chosen=False):
+        """``chosen``: the form of every handle of the call (``_Handle.bring`` creates a handle of the other form anew).
+        A handle per utterance with its sampling controls, holding its class's biases, its frame table and, in a ragged
         call, its step limit (its decode steps: the first sample comes from the prefill).  Tables and limits belong to the
         utterance, so such handles are updated in every call; a handle created here holds all of it already."""
         lib = _lib.lib()
@@ -669,7 +718,7 @@ class FasterWaveNet(WaveNet):
         def bring(h, r):
             ft, ph = feats[r.group]       # (a handle is created WITH its table)
             h.bring(self, r.class_id, biases.get, None if ft is None else self._decoder_table(ft, ph, len(r.window)),
-                    r.n - 1 if ragged else None)
+                    r.n - 1 if ragged else None, chosen)
         held = len(self._handles)
         for r in recs[held:]:
             self._handles.append(_Handle())
@@ -679,10 +728,13 @@ class FasterWaveNet(WaveNet):
                 bring(self._handles[i], r)
             check(lib.wn_decoder_set_sampling(self._handles[i].h, r.temperature, r.top_k, r.top_p), "wn_decoder_set_sampling")
 
-    def _generate_batch_loop(self, recs, ragged):
+    def _generate_batch_loop(self, recs, ragged, return_chosen=False):
         """generate_batch for what ``wn_decoder_run_batch`` does not cover: ``generate()`` per utterance (row u is
         ``generate(<utterance u's length>, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls
         by definition); ``ragged``: a list of rows comes back."""
         rows = [self.generate(r.n, r.u, initial_tokens=r.window, temperature=r.temperature, top_k=r.top_k, top_p=r.top_p,
-                              condition=r.class_id, local=r.local, local_phase=r.phase) for r in recs]
+                              condition=r.class_id, local=r.local, local_phase=r.phase, return_chosen=return_chosen) for r in recs]
+        if return_chosen:
+            toks, ch = [t for t, _ in rows], [c for _, c in rows]
+            return (toks, ch) if ragged else (torch.stack(toks), torch.stack(ch))
         return rows if ragged else torch.stack(rows)

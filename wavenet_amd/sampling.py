@@ -110,3 +110,28 @@ def per_utterance(value, n, name="control"):
     if len(vals) != n:
         raise ValueError("%s: expected a scalar or %d values, got %d" % (name, n, len(vals)))
     return vals
+
+
+def chosen_nll(chosen) -> float:
+    """Nats per sample of one utterance from the probabilities of the tokens it emitted (``generate(..., return_chosen=True)``:
+    a 1-D array or tensor): the float64 mean of ``-log(float64(p))`` -- the number ``evaluate`` prints for held-out audio,
+    here for generated audio.  ``inf`` when a token of probability 0.0 was drawn (the fallback at the end of the cumulative
+    distribution); 0.0 for no samples."""
+    p = np.asarray(chosen.detach().cpu() if hasattr(chosen, "detach") else chosen, dtype=np.float64).reshape(-1)
+    if p.size == 0:
+        return 0.0
+    with np.errstate(divide="ignore"):
+        return float(np.mean(-np.log(p)))
+
+
+def pick_best(nlls) -> int:
+    """The index of the smallest of ``nlls`` (the candidate the model found most likely), the lowest index on ties.  NaN never
+    wins: it is passed over, and index 0 comes back only when every value is NaN."""
+    vals = [float(v) for v in nlls]
+    if not vals:
+        raise ValueError("pick_best: no candidate")
+    best = 0
+    for i, v in enumerate(vals):
+        if not math.isnan(v) and (math.isnan(vals[best]) or v < vals[best]):
+            best = i
+    return best

@@ -65,6 +65,16 @@ _LOCAL_FLAGS = (
                                    "'sample' (anywhere, as without features: one --seed selects the same crops; every crop "
                                    "carries its own phase).  A property of the run, not of the checkpoint"),
 )
+# likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
+# attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
+_LIKELIHOOD_FLAGS = (
+    (("--report",), str, None, "generate --fast: write FILE.json with the negative log-likelihood the model gave every written "
+                               ".wav -- samples, nats and bits per emitted sample (prompt and window excluded) -- and the total "
+                               "weighted by samples, as evaluate --json does for held-out audio"),
+    (("--best-of",), int, 1, "generate --fast: draw every utterance K times, all candidates in the same batched run, and write "
+                             "the one the model found most likely (lowest nats per sample).  Likelihood rewards quiet, "
+                             "predictable audio: a ranking tool, most useful when vocoding from features, not a quality score"),
+)
 _LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
                "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
 _SPEAKER_HELP = ("generate: the speaker label to generate as (a conditioned checkpoint needs one); repeatable: one label for all "
@@ -78,6 +88,7 @@ class Args(argparse.Namespace):
     ema_decay, valid_wav_dir, ema = 0.0, None, False
     speaker_prefix, condition_channels, speaker = False, None, None
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
+    report, best_of = None, 1
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -87,7 +98,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _LIKELIHOOD_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

@@ -4,9 +4,15 @@
 Beyond the reference: ``--utterances N`` and ``--prompt FILE.wav`` write ``generated_000.wav`` ... ``generated_{N-1:03d}.wav``,
 each continuing its prompt (or silence); with ``--fast`` all of them in one ``FasterWaveNet.generate_batch`` run.
 ``--fast --local-dir FEAT_DIR`` vocodes a directory: ``<output_dir>/NAME.wav`` for every ``FEAT_DIR/NAME.npy``, each at the
-length its own features cover, all in one ragged ``generate_batch`` run."""
+length its own features cover, all in one ragged ``generate_batch`` run.
+``--fast --report FILE.json`` writes the negative log-likelihood the model gave every written file (nats and bits per emitted
+sample, as ``evaluate`` prints for held-out audio); ``--fast --best-of K`` draws every utterance K times in the same batched
+run and keeps the candidate the model found most likely.  Likelihood rewards quiet, predictable audio: it ranks candidates
+(most usefully when vocoding from features), it does not measure quality."""
 from __future__ import annotations
 
+import json
+import math
 import os
 import sys
 import time
@@ -67,14 +73,67 @@ def _save(start_time, output_dir, Q, sampling_rate, named):
     return filenames
 
 
+def likelihood_job(args):
+    """``generate --report FILE.json / --best-of K``: the checks, made before a model is built.  Returns (K, FILE or None)."""
+    K, report = int(args.best_of), args.report
+    if K < 1:
+        raise SystemExit("generate: --best-of K needs K >= 1, got {}".format(K))
+    if (K > 1 or report) and not args.fast:
+        raise SystemExit("generate: --report and --best-of read the probability of every emitted sample from the decoder on "
+                         "the device: give --fast")
+    return K, report
+
+
+def _keep_best(tokens, chosen, K):
+    """``tokens`` / ``chosen``: N * K rows, row ``u * K + c`` candidate c of utterance u (1-D arrays or device tensors) ->
+    (the kept candidate's tokens per utterance as numpy, [(kept index, [nats per sample of every candidate])])."""
+    nlls = [sampling.chosen_nll(c) for c in chosen]
+    ranked = [(sampling.pick_best(nlls[u * K:(u + 1) * K]), nlls[u * K:(u + 1) * K]) for u in range(len(nlls) // K)]
+    kept = [tokens[u * K + k] for u, (k, _) in enumerate(ranked)]
+    return [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in kept], ranked
+
+
+def write_report(path, filenames, tokens, ranked, K):
+    """``--report``: per written file {"file", "samples", "nats_per_sample", "bits_per_sample"} (the emitted samples only: no
+    prompt, no window) and, with ``--best-of K`` > 1, "candidates" (every candidate's nats per sample) and "kept"; then the
+    total weighted by samples, in the layout of ``evaluate --json``.  Returns the table."""
+    rows, nats, samples = [], 0.0, 0
+    for fn, t, (k, cand) in zip(filenames, tokens, ranked):
+        row = {"file": os.path.basename(fn), "samples": int(len(t)), "nats_per_sample": cand[k],
+               "bits_per_sample": cand[k] / math.log(2.0)}
+        if K > 1:
+            row["candidates"], row["kept"] = list(cand), int(k)
+        rows.append(row)
+        nats += cand[k] * len(t) if len(t) else 0.0
+        samples += int(len(t))
+    mean = nats / samples if samples else 0.0
+    table = {"files": rows, "total": {"samples": samples, "nats_per_sample": mean, "bits_per_sample": mean / math.log(2.0)}}
+    with open(path, "w") as f:
+        json.dump(table, f, indent=2)
+    return table
+
+
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None):
+                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, best_of=1, report=None):
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
     silence = silence_window(Q, input_width_of(params))
     start_time = time.time()
-    if n <= 0:
+    ranked = None
+    if fast and (best_of > 1 or report):
+        lkw = {} if local is None else {"local": local}
+        kw = dict(initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p, condition=condition,
+                  return_chosen=True, **lkw)
+        if n <= 0:
+            rows, chosen = [np.zeros((0,), np.int32)] * best_of, [np.zeros((0,), np.float32)] * best_of
+        elif best_of == 1:
+            rows, chosen = [[v] for v in net.generate(n, np.random.random_sample(n), **kw)]
+        else:
+            # K candidates of the one utterance are K utterances of a batched run: same prompt, speaker, features, controls
+            rows, chosen = net.generate_batch(n, np.random.random_sample((best_of, n)), **kw)
+        (tokens,), ranked = _keep_best(list(rows), list(chosen), best_of)
+    elif n <= 0:
         tokens = np.zeros((0,), np.int32)
     elif fast:
         # one uniform per sample, the draw numpy's choice() makes (generate.py:40); the whole loop runs on the device
@@ -84,7 +143,10 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
                               condition=condition, **lkw).cpu().numpy()
     else:
         tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition, local)
-    return _save(start_time, output_dir, Q, sampling_rate, [("generated", tokens)])[0], tokens
+    filename = _save(start_time, output_dir, Q, sampling_rate, [("generated", tokens)])[0]
+    if report:
+        write_report(report, [filename], [tokens], ranked, best_of)
+    return filename, tokens
 
 
 def read_prompt(path, params):
@@ -98,9 +160,11 @@ def read_prompt(path, params):
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None):
+                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
-    ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance."""
+    ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance.
+    ``best_of`` = K > 1 (``fast`` only): N * K candidates in that run, row ``u * K + c`` candidate c of utterance u, the
+    most likely one of every utterance written under the utterance's name; ``report``: ``write_report``'s file."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     N = len(prompt_files)
@@ -109,7 +173,21 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     read = {f: read_prompt(f, params) for f in set(prompt_files) if f is not None}
     prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
     start_time = time.time()
-    if n <= 0:
+    ranked = None
+    if fast and (best_of > 1 or report):
+        K = best_of
+        if n <= 0:
+            rows, chosen = [np.zeros((0,), np.int32)] * (N * K), [np.zeros((0,), np.float32)] * (N * K)
+        else:
+            u = np.random.random_sample((N * K, n))
+            lkw = {} if locals_ is None else {"local": [f for f in locals_ for _ in range(K)]}
+            rows, chosen = net.generate_batch(n, u, initial_tokens=np.repeat(prompts, K, axis=0), temperature=temperature,
+                                              top_k=top_k, top_p=top_p, return_chosen=True,
+                                              condition=None if conditions is None else [c for c in conditions for _ in range(K)],
+                                              **lkw)
+        tokens, ranked = _keep_best(list(rows), list(chosen), K)
+        tokens = np.stack(tokens)
+    elif n <= 0:
         tokens = np.zeros((N, 0), np.int32)
     elif fast:
         u = np.random.random_sample((N, n))
@@ -120,7 +198,10 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
         tokens = np.stack([_host_loop(net, prompts[i], n, sampling_rate, generate_sec, temperature, top_k, top_p,
                                       None if conditions is None else conditions[i],
                                       None if locals_ is None else locals_[i]) for i in range(N)])
-    return _save(start_time, output_dir, Q, sampling_rate, [("generated_{:03d}".format(i), tokens[i]) for i in range(N)]), tokens
+    filenames = _save(start_time, output_dir, Q, sampling_rate, [("generated_{:03d}".format(i), tokens[i]) for i in range(N)])
+    if report:
+        write_report(report, filenames, list(tokens), ranked, best_of)
+    return filenames, tokens
 
 
 def directory_job(args, seconds_given):
@@ -158,9 +239,11 @@ def directory_job(args, seconds_given):
 
 
 def generate_directory(net, params, names, feats, lengths, cids, seed=None, output_dir="generated_audio", temperature=1.0,
-                       top_k=0, top_p=1.0):
+                       top_k=0, top_p=1.0, best_of=1, report=None):
     """One ragged ``generate_batch`` run over the whole directory, from silence; ``<output_dir>/NAME.wav`` per feature file,
-    each at its own length.  With a seed every file draws what its own ``generate --fast --local NAME.npy`` run draws."""
+    each at its own length.  With a seed every file draws what its own ``generate --fast --local NAME.npy`` run draws.
+    ``best_of`` = K > 1: K candidates per file in that run (``random_sample((K, n_file))`` behind the file's seed), the most
+    likely one written; ``report``: ``write_report``'s file."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     silence = silence_window(Q, input_width_of(params))
@@ -168,12 +251,23 @@ def generate_directory(net, params, names, feats, lengths, cids, seed=None, outp
     for n in lengths:
         if seed is not None:
             np.random.seed(seed)
-        uniforms.append(np.random.random_sample(n))
+        uniforms.append(np.random.random_sample(n) if best_of == 1 else np.random.random_sample((best_of, n)))
     start_time = time.time()
-    rows = net.generate_batch(list(lengths), uniforms, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
-                              condition=cids, local=list(feats))
-    tokens = [r.cpu().numpy() for r in rows]
-    return _save(start_time, output_dir, Q, params.sampling_rate, list(zip(names, tokens))), tokens
+    if best_of == 1 and not report:
+        rows = net.generate_batch(list(lengths), uniforms, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  condition=cids, local=list(feats))
+        tokens = [r.cpu().numpy() for r in rows]
+        return _save(start_time, output_dir, Q, params.sampling_rate, list(zip(names, tokens))), tokens
+    K = best_of
+    rows, chosen = net.generate_batch([n for n in lengths for _ in range(K)], [r for u in uniforms for r in np.reshape(u, (K, -1))],
+                                      initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
+                                      condition=None if cids is None else [c for c in cids for _ in range(K)],
+                                      local=[f for f in feats for _ in range(K)], return_chosen=True)
+    tokens, ranked = _keep_best(rows, chosen, K)
+    filenames = _save(start_time, output_dir, Q, params.sampling_rate, list(zip(names, tokens)))
+    if report:
+        write_report(report, filenames, tokens, ranked, K)
+    return filenames, tokens
 
 
 def _seconds_given(argv) -> bool:
@@ -187,12 +281,13 @@ def _seconds_given(argv) -> bool:
 
 def main(argv=None):
     args = _args.parse(argv)
+    best_of, report = likelihood_job(args)
     seconds_given = _seconds_given(argv)
     if args.local_dir is not None:
         names, feats, lengths, cids = directory_job(args, seconds_given)
         params, net = _model.build(args)
         return generate_directory(net, params, names, feats, lengths, cids, seed=args.seed, output_dir=args.output_dir,
-                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p)
+                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, best_of=best_of, report=report)
     n_utt, prompt_files = _args.utterance_prompts(args)
     # the speaker of every utterance, checked against the checkpoint's table before the model is built: an unknown label,
     # --speaker on an unconditioned checkpoint and its absence on a conditioned one all stop here with a clear message
@@ -226,10 +321,11 @@ def main(argv=None):
     if n_utt is not None:
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
-                                   top_p=args.top_p, conditions=cids if table else None, locals_=feats)
+                                   top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of,
+                                   report=report)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                          condition=cids[0], local=None if feats is None else feats[0])
+                          condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report)
 
 
 if __name__ == "__main__":
