@@ -393,6 +393,27 @@ int wn_btc_to_nchw(const float* src, float* dst, int B, int C, int T, void* stre
  * thread that owns the drawn token stores its entry with one ordinary store per step; the full-row write and this one exclude
  * each other per launch.  Without the flag every call does what it did before the flag existed. */
 #define WN_DECODER_TRACE_CHOSEN 256u
+/* WnDecoderDesc.flags, on every shape: the handle keeps the samples it is given and draws the rest.  out_tokens of wn_decoder_run
+ * (out_tokens[u] of wn_decoder_run_batch) is READ BEFORE IT IS WRITTEN: with f = out_tokens[i] on entry,
+ *   - 0 <= f < Q: step i emits f.  No truncation and no draw run; uniforms[i] has no effect (the array is still n doubles, and a
+ *     NaN there is harmless); out_tokens[i] stays f; the token enters the rings and the next step exactly as a drawn one does;
+ *   - any other value (-1 by convention): step i draws exactly as an unflagged handle does -- the row, the controls, uniforms[i],
+ *     the token and the trace are the same, bit for bit.
+ * The kernels decide with (unsigned)f < (unsigned)Q: a fence, so that a garbage buffer cannot index outside the embedding, not
+ * a feature -- callers write -1 or a token.  There is no separate input buffer because no export, field or signature was free
+ * to carry one; the buffer the run writes anyway is the one it reads.  The full-row trace is what it was: row i is the
+ * post-temperature, pre-truncation row.  On a WN_DECODER_TRACE_CHOSEN handle element i of a given step is row_i[f] -- post-
+ * temperature and never truncated, because the filter did not run; nothing is clamped, 0.0f is reported as 0.0f -- so a run
+ * with every sample given is the decoder's own likelihood of those samples.  wn_decoder_run_batch: only elements [0, n_u) of
+ * out_tokens[u] are read (and, as ever, written), and all handles of a launch must agree on the flag (WN_EARG naming the first
+ * utterance that differs from utterance 0, before any device work, every handle's state and every buffer left alone).  A handle's
+ * form is fixed at create: wn_decoder_update_weights with a description whose bit differs from the handle's is WN_EARG before
+ * any device work.  The bit combines freely with WN_DECODER_GATE_ROWS, WN_DECODER_TRACE_CHOSEN and WN_DECODER_ONE_WORKGROUP
+ * and never changes which decoder a description selects; wn_decoder_step is not affected.  In the kernels the entry is fetched
+ * at the top of its step, off the layer chain, and a given step skips the sampler behind the network; the mode sits in
+ * template instantiations of its own, so without the flag every call does what it did before the flag existed, and out_tokens
+ * is write-only again. */
+#define WN_DECODER_FORCED_TOKENS 512u
 typedef struct WnDecoderDesc {
     int Q, fw_causal, n_causal, fw, n_blocks, n_layers;  /* n_layers per block; dilation fw^l */
     int Cr, Cs, n_head;
@@ -412,6 +433,8 @@ typedef struct WnDecoderDesc {
                                          deselect that kernel;
                                          WN_DECODER_TRACE_CHOSEN (see the define): prob_trace is one float per step, the
                                          emitted token's probability, on every shape;
+                                         WN_DECODER_FORCED_TOKENS (see the define): out_tokens is read before it is written, and
+                                         a step whose entry is a token emits it instead of drawing, on every shape;
                                          WN_DECODER_ONE_WORKGROUP: wn_decoder_run of that kernel on ONE workgroup instead of
                                          nine (the chain | eight workgroups of skip rows and their share of the logits):
                                          same products, another summation order for the skip rows and the logits --
@@ -465,7 +488,8 @@ int wn_decoder_step(void* handle, int32_t token, float* prob, int apply_softmax,
  * previous token, computes p, draws with numpy's algorithm from uniforms[i] (float64 cumsum,
  * normalise, searchsorted right) and appends.  first_token is the newest token of the window the
  * state was loaded from plus one draw, i.e. the token emitted by the prefill step.  out_tokens (n)
- * receives the n emitted tokens; prob_trace (n*Q; n on a WN_DECODER_TRACE_CHOSEN handle) is optional. */
+ * receives the n emitted tokens; prob_trace (n*Q; n on a WN_DECODER_TRACE_CHOSEN handle) is optional.
+ * On a WN_DECODER_FORCED_TOKENS handle out_tokens is an input as well: see the define. */
 int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, int n,
                    int32_t* out_tokens, float* prob_trace, void* stream);
 /* ABI 4.  n_handles independent utterances in ONE launch (generate.py:9-60 is batch 1 with a strict sample-to-sample

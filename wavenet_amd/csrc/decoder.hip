@@ -50,6 +50,8 @@ struct Decoder {
                                   // takes static gate biases and a frame table -- wave 1 of the chain workgroup adds them
     bool trace_chosen = false;    // created with WN_DECODER_TRACE_CHOSEN (fixed at create, on every shape): a run's prob_trace is one
                                   // float per step, the drawn token's probability, not a row of Q
+    bool forced = false;          // created with WN_DECODER_FORCED_TOKENS (fixed at create, on every shape): a run reads out_tokens[i] before
+                                  // it writes it, and a step whose entry is a token of [0, Q) emits that token instead of drawing
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
     SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
     // wn_decoder_run_batch on any-shape handles, as handle 0 of the call: the per-utterance table (DecAnyUtt) in device
@@ -168,7 +170,9 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
 // The step loop of one utterance on one workgroup: k_decode runs it for its handle, workgroup u of k_decode_batch for
 // utterance u.  Everything it touches -- arena, token ring, uniforms, outputs -- is the utterance's own; `sc` and the flags
 // are the same for every thread of the workgroup.
-template <bool LERP>         // LERP: the table is interpolated (DecFrames.interp); without it the loop is what it was
+// FORCED (WN_DECODER_FORCED_TOKENS handles): a step may emit the token out_tokens[it] holds instead of drawing; without it the
+// loop is what it was
+template <bool LERP, bool FORCED>         // LERP: the table is interpolated (DecFrames.interp); without it the loop is what it was
 __device__ __forceinline__ void decode_steps(
     const DecMeta& M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
@@ -191,6 +195,10 @@ __device__ __forceinline__ void decode_steps(
     for (int it = 0; it < nsteps; ++it) {
         const long long n = n0 + it;
         const int token = s_token;
+        // FORCED: the entry this step may have to emit, read by every thread ahead of the network (one address for all: uniform) --
+        // thread 0 writes out_tokens[it] only at the draw below; unsigned compare: a garbage entry is no index
+        const int f_tok = FORCED && do_sample ? __builtin_amdgcn_readfirstlane(out_tokens[it]) : -1;
+        const bool given = FORCED && (unsigned)f_tok < (unsigned)M.Q;
         // ---- causal layer 0: two (fwc) gathered rows of the packed table ---------------------
         {
             const DecCausal L = causal[0];
@@ -312,7 +320,13 @@ __device__ __forceinline__ void decode_steps(
         }
         if (prob_out && prob_stride)          // the full row; prob_stride == 0 (kProbChosen): one float per step, at the draw below
             for (int q = tid; q < M.Q; q += NT) prob_out[(long long)it * prob_stride + q] = hin[q];
-        if (do_sample) {
+        if (do_sample && given) {
+            // a given step: no filter, no draw; out_tokens[it] holds the token already, and it enters the next step as a drawn one
+            if (tid == 0) {
+                s_token = f_tok;
+                if (prob_out && !prob_stride) prob_out[it] = hin[f_tok];     // the untruncated row's entry, nothing clamped
+            }
+        } else if (do_sample) {
             if (filt)                    // top-k / top-p: the trace above holds the row as the filter receives it
                 sample_filter<false>(hin, M.Q, tid, NT, sc.top_k, sc.top_p);
             if (tid == 0) {
@@ -337,25 +351,26 @@ __device__ __forceinline__ void decode_steps(
     }
 }
 
-template <bool LERP>
+template <bool LERP, bool FORCED>
 __global__ __launch_bounds__(kDecThreads) void k_decode(
     DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
     float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc, const DecFrames fr) {
-    decode_steps<LERP>(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
+    decode_steps<LERP, FORCED>(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
                  apply_softmax, do_sample, sc, fr);
 }
 
 // wn_decoder_run_batch on any-shape handles: workgroup u is utterance u's k_decode.  The workgroups share nothing and
 // never wait for each other, so any number of them may be queued behind the CUs -- and each runs its utterance's own step
 // count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.  prob_stride is the
-// launch's (M.Q, or kProbChosen when the handles were created with WN_DECODER_TRACE_CHOSEN: they must agree).
-template <bool LERP>
+// launch's (M.Q, or kProbChosen when the handles were created with WN_DECODER_TRACE_CHOSEN: they must agree), and so is FORCED
+// (the handles agree on WN_DECODER_FORCED_TOKENS).
+template <bool LERP, bool FORCED>
 __global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int prob_stride) {
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
-    decode_steps<LERP>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
+    decode_steps<LERP, FORCED>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
                  q.prob_out, prob_stride, 1, 1, q.sc, q.fr);
 }
 
@@ -639,6 +654,7 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
         D->gate_rows = (d->flags & WN_DECODER_GATE_ROWS) != 0;
     }
     D->trace_chosen = (d->flags & WN_DECODER_TRACE_CHOSEN) != 0;
+    D->forced = (d->flags & WN_DECODER_FORCED_TOKENS) != 0;
     if ((rc = pack_weights(D, d, s))) return rc;
     if ((rc = take_frames(D, d, s))) return rc;
     *handle = built.release();
@@ -675,6 +691,9 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
     WN_CHECK_ARG(((d->flags & WN_DECODER_TRACE_CHOSEN) != 0) == D->trace_chosen,
                  "wn_decoder_update_weights: the description %s WN_DECODER_TRACE_CHOSEN, the handle was created %s it: a handle's form "
                  "is fixed at create", d->flags & WN_DECODER_TRACE_CHOSEN ? "carries" : "lacks", D->trace_chosen ? "with" : "without");
+    WN_CHECK_ARG(((d->flags & WN_DECODER_FORCED_TOKENS) != 0) == D->forced,
+                 "wn_decoder_update_weights: the description %s WN_DECODER_FORCED_TOKENS, the handle was created %s it: a handle's form "
+                 "is fixed at create", d->flags & WN_DECODER_FORCED_TOKENS ? "carries" : "lacks", D->forced ? "with" : "without");
     for (int j = 0; D->gate_rows && j < D->meta.nlayers; ++j)
         WN_CHECK_ARG(!(d->bf && d->bf[j]) == !(d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
     if ((rc = check_frame_desc(D, d))) return rc;
@@ -712,6 +731,9 @@ int wn_decoder_load_state(void* handle, const int32_t* tokens, int W, const floa
 // floats between the rows of a run's prob_trace: Q, or kProbChosen on a WN_DECODER_TRACE_CHOSEN handle
 static int trace_stride(const Decoder* D) { return D->trace_chosen ? kProbChosen : D->meta.Q; }
 
+// do_sample of a run's launch: kSampleGiven on a WN_DECODER_FORCED_TOKENS handle (out_tokens is read before it is written)
+static int sample_mode(const Decoder* D) { return D->forced ? kSampleGiven : kSampleDraw; }
+
 // n steps were launched: the one writer of both counters after create / update / load_state
 static void advance(Decoder* D, long long n) { D->step += n; D->since_set += n; }
 
@@ -732,7 +754,9 @@ static int run_one(const char* fn, Decoder* D, int token, const double* uniforms
     } else {
         // (k_decode takes the record's members as loose arguments: DESIGN.md, "The library's host side, tidied likewise")
         const DecAnyUtt q = any_utt(D, token, uniforms, out_tokens, prob, n, sc);
-        const auto kern = lerp_table(D) ? k_decode<true> : k_decode<false>;
+        const bool forced = do_sample == kSampleGiven;      // (the kernel itself only asks whether do_sample != 0)
+        const auto kern = forced ? (lerp_table(D) ? k_decode<true, true> : k_decode<false, true>)
+                                 : (lerp_table(D) ? k_decode<true, false> : k_decode<false, false>);
         hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, s, D->meta, q.causal, q.layers, q.heads, q.arena, q.tok_ring,
                            q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out, prob_stride, apply_softmax, do_sample,
                            q.sc, q.fr);
@@ -755,7 +779,7 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
     Decoder* D = (Decoder*)handle;
     WN_CHECK_ARG(D && uniforms && out_tokens && n > 0, "wn_decoder_run: bad argument");
     WN_CHECK_ARG(first_token >= 0 && first_token < D->meta.Q, "wn_decoder_run: token outside [0,Q)");
-    return run_one("wn_decoder_run", D, (int)first_token, uniforms, n, out_tokens, prob_trace, trace_stride(D), 1, 1, launch_ctl(D), D->three_wgs,
+    return run_one("wn_decoder_run", D, (int)first_token, uniforms, n, out_tokens, prob_trace, trace_stride(D), 1, sample_mode(D), launch_ctl(D), D->three_wgs,
                    as_stream(stream));
 }
 
@@ -800,7 +824,8 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
-    const auto kern = lerp_table(D0) ? k_decode_batch<true> : k_decode_batch<false>;     // (the handles agree on the mode)
+    const auto kern = D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true> : k_decode_batch<false, true>)       // (the handles agree
+                                 : (lerp_table(D0) ? k_decode_batch<true, false> : k_decode_batch<false, false>);    // on both modes)
     hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
                        n_handles, trace_stride(D0));
     WN_LAUNCH_CHECK();
@@ -873,6 +898,10 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_ARG(D->trace_chosen == D0->trace_chosen, "wn_decoder_run_batch: utterance %d was created %s WN_DECODER_TRACE_CHOSEN, "
                      "utterance 0 %s it: the handles of a launch agree on the flag", u, D->trace_chosen ? "with" : "without",
                      D0->trace_chosen ? "with" : "without");
+        // ... and so is whether out_tokens is read (one mode for every workgroup)
+        WN_CHECK_ARG(D->forced == D0->forced, "wn_decoder_run_batch: utterance %d was created %s WN_DECODER_FORCED_TOKENS, "
+                     "utterance 0 %s it: the handles of a launch agree on the flag", u, D->forced ? "with" : "without",
+                     D0->forced ? "with" : "without");
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         if (int rc = steps_left(D, u, n, any, &nu[u])) return rc;
         const FrameTable &F = D->frames, &F0 = D0->frames;
@@ -890,7 +919,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     WN_CHECK_SHAPE(any || decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
     const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream))
-                       : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, trace_stride(D0), D0->meta.head_act, same_weights != 0,
+                       : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, trace_stride(D0), sample_mode(D0), D0->meta.head_act, same_weights != 0,
                                                   gate, as_stream(stream));
     if (rc) return rc;
     for (int u = 0; u < n_handles; ++u) {

@@ -523,9 +523,21 @@ __device__ __forceinline__ float softmax_row(const ChainLds& S, float v, float i
     return e * (1.f / s);
 }
 // The draw from the row in S.lg with the uniform u_draw: the token to *out_token and into the token pair.
+// `given` (WN_DECODER_FORCED_TOKENS launches, the FORCED instantiations; the constant -1 in every other one, where the test folds
+// away and the draw is the code it was): what *out_token held when the step began, the same value in every thread.  A token of [0, 256) is emitted as it is -- no filter, no scan, no exact fallback;
+// *out_token holds it already; it enters the token pair as a drawn one does -- and anything else draws.  The compare is unsigned:
+// a garbage entry cannot index outside the embedding table.  The branch is uniform over the workgroup and the given path meets
+// no barrier, so the callers' closing barrier stays matched; the row in S.lg is left as the softmax wrote it (store_chosen).
 __device__ __forceinline__ void draw_token(const ChainLds& S, const SampleCtl& sc, double u_draw, int token,
-                                           int32_t* __restrict__ out_token, int tid) {
+                                           int32_t* __restrict__ out_token, int tid, int given) {
     const int lane = tid & 63, wv = tid >> 6;
+    if ((unsigned)given < 256u) {
+        if (tid == 0) {
+            S.s_tok[1] = token;
+            S.s_tok[0] = given;
+        }
+        return;
+    }
     float* lg = S.lg;
     double* cdf = S.cdf;
     int* red = reinterpret_cast<int*>(S.red);
@@ -590,7 +602,11 @@ __device__ __forceinline__ void store_chosen(const ChainLds& S, float* __restric
     if (prob_out && tid == S.s_tok[0]) prob_out[it] = S.lg[tid];
 }
 
-template <bool GATE, bool CHOSEN>          // GATE: wave 1 seeds the gate rows with the handle's biases and table rows (gate rows, above)
+// FORCED (WN_DECODER_FORCED_TOKENS handles; the host takes these instantiations for do_sample == kSampleGiven): out_tokens[it] is
+// read at the top of step `it`, off the chain, and handed to draw_token.  A template parameter like CHOSEN, not a run-time test: as
+// a value of do_sample it cost every existing instantiation of k_decode_fast and most of k_decode_fast3 a register (DESIGN.md,
+// "Given samples in the decode loop"); so the other instantiations are, instruction for instruction, what they were.
+template <bool GATE, bool CHOSEN, bool FORCED>   // GATE: wave 1 seeds the gate rows with the handle's biases and table rows (gate rows, above)
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                         int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -608,6 +624,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
         const unsigned n = (unsigned)(q.n0 + it);
         const int token = S.s_tok[0], tprev = S.s_tok[1];
         const double u_draw = do_sample ? q.uniforms[it] : 0.0;      // fetched here, used after the network
+        const int f_tok = FORCED && do_sample ? q.out_tokens[it] : -1;           // ... and the entry a given step emits (draw_token)
         fetch_xold(S, q.arena, nlayers, n, tid);
         open_step(S, token, tprev, tid);
         if (wv == 0) {
@@ -679,7 +696,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
         S.lg[tid] = v;
         if (!CHOSEN && q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
-        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
+        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid, FORCED ? __builtin_amdgcn_readfirstlane(f_tok) : -1);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
         if (CHOSEN) store_chosen(S, q.prob_out, it, tid);
@@ -720,7 +737,7 @@ static u64* x_area(const float* P, int nlayers) {
 
 // `wg`: this workgroup's role in its utterance's group of nine (0 = chain, 1..8 = skip rows): blockIdx.x for one utterance,
 // blockIdx.x % 9 in the batched launch (k_decode_fast3_batch)
-template <bool GATE, bool CHOSEN>
+template <bool GATE, bool CHOSEN, bool FORCED>
 __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q, int nlayers, int nsteps, int prob_stride,
                                                   int apply_softmax, int do_sample, int head_act) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -788,6 +805,7 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
         const unsigned seq = (unsigned)(it + 1);
         const int token = S.s_tok[0], tprev = S.s_tok[1];
         const double u_draw = do_sample ? q.uniforms[it] : 0.0;
+        const int f_tok = FORCED && do_sample ? q.out_tokens[it] : -1;           // the entry a given step emits (draw_token)
         if (it == 0) fetch_xold(S, q.arena, nlayers, n, tid);   // later steps: fetched during the previous step's wait (below)
         open_step(S, token, tprev, tid);
         if (wv == 0) {
@@ -846,7 +864,7 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
         S.lg[tid] = v;
         if (!CHOSEN && q.prob_out) q.prob_out[(long long)it * prob_stride + tid] = v;
         lds_barrier();
-        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid);
+        if (do_sample) draw_token(S, q.sc, u_draw, token, q.out_tokens + it, tid, FORCED ? __builtin_amdgcn_readfirstlane(f_tok) : -1);
         else if (tid == 0) S.s_tok[1] = token;
         __syncthreads();                           // full barrier: orders this step's ring stores before the next step's loads
         if (CHOSEN) store_chosen(S, q.prob_out, it, tid);
@@ -855,10 +873,10 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
     if (tid == 0) q.tok_ring[0] = S.s_tok[1];
 }
 
-template <bool GATE, bool CHOSEN>
+template <bool GATE, bool CHOSEN, bool FORCED>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nlayers, int nsteps, int prob_stride,
                                                          int apply_softmax, int do_sample, int head_act) {
-    decode_fast3_body<GATE, CHOSEN>((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
+    decode_fast3_body<GATE, CHOSEN, FORCED>((int)blockIdx.x, q, nlayers, nsteps, prob_stride, apply_softmax, do_sample, head_act);
 }
 
 // N independent utterances in ONE launch: nine workgroups each (the single-GPU form of "replicas only", SURVEY 8(e): batch 1
@@ -871,10 +889,11 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast3(const DecUtt q, int nla
 // partners do not, so no wait is left without its entry, and a group that ends early simply ends.
 struct DecBatchArgs { DecUtt it[kDecMaxBatch]; };
 static_assert(sizeof(DecBatchArgs) + 4 * sizeof(int) <= 4096, "kernel arguments are passed by value: 4 KB at most");
-template <bool GATE, bool CHOSEN>
+template <bool GATE, bool CHOSEN, bool FORCED>
 __global__ __launch_bounds__(kFT, 1) void k_decode_fast3_batch(const DecBatchArgs a, int nlayers, int prob_stride, int head_act) {
     const int u = blockIdx.x / (kD10Skip + 1);
-    decode_fast3_body<GATE, CHOSEN>((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1, head_act);
+    decode_fast3_body<GATE, CHOSEN, FORCED>((int)blockIdx.x - u * (kD10Skip + 1), a.it[u], nlayers, a.it[u].nsteps, prob_stride, 1, 1,
+                                            head_act);
 }
 
 __global__ void k_decode_zero_x(u64* X, int n) {
@@ -885,6 +904,12 @@ static void zero_x(u64* X, int nlayers, hipStream_t s) {
     const int nx = x_entries(nlayers);
     hipLaunchKernelGGL(k_decode_zero_x, dim3(cdiv(nx, 256)), dim3(256), 0, s, X, nx);
 }
+
+// the instantiation of kernel template K for a launch: gate rows | chosen trace | given tokens
+#define WN_DEC_ALL(K) K<false, false, false>, K<true, false, false>, K<false, true, false>, K<true, true, false>, \
+                      K<false, false, true>, K<true, false, true>, K<false, true, true>, K<true, true, true>
+#define WN_DEC_PICK2(K, g, c, F) ((c) ? ((g) ? K<true, true, F> : K<false, true, F>) : ((g) ? K<true, false, F> : K<false, false, F>))
+#define WN_DEC_PICK(K, g, c, f) ((f) ? WN_DEC_PICK2(K, g, c, true) : WN_DEC_PICK2(K, g, c, false))
 
 size_t decode_fast_lds_bytes() { return ChainLds::kBytes; }
 size_t decode_fast_pack_floats(int nlayers) {            // weights, then the exchange entries of the nine-workgroup form (8 bytes each)
@@ -903,10 +928,9 @@ int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s) {
 
 int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int apply_softmax, int do_sample, int head_act,
                        bool three_wgs, bool gate_rows, hipStream_t s) {
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast<false, false>, k_decode_fast3<false, false>, k_decode_fast<true, false>,
-                    k_decode_fast3<true, false>, k_decode_fast<false, true>, k_decode_fast3<false, true>, k_decode_fast<true, true>,
-                    k_decode_fast3<true, true>);
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), WN_DEC_ALL(k_decode_fast), WN_DEC_ALL(k_decode_fast3));
     const bool chosen = prob_stride == kProbChosen;          // (a sampling launch: wn_decoder_step passes Q)
+    const bool forced = do_sample == kSampleGiven;           // (the kernels themselves only ask whether do_sample != 0)
     if (three_wgs && nsteps > 1 && nsteps < (1 << 30) && nlayers <= kD10MaxL) {
         // nine workgroups that wait for each other: the device the stream belongs to must be able to hold them at once (asked
         // per device, per call: cheap, and a process may drive several devices).  What the count cannot see -- other work
@@ -916,16 +940,14 @@ int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int a
             hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu >= kD10Skip + 1) {
             q.X = x_area(q.P, nlayers);
             zero_x(q.X, nlayers, s);
-            const auto k3 = chosen ? (gate_rows ? k_decode_fast3<true, true> : k_decode_fast3<false, true>)
-                                   : (gate_rows ? k_decode_fast3<true, false> : k_decode_fast3<false, false>);
+            const auto k3 = WN_DEC_PICK(k_decode_fast3, gate_rows, chosen, forced);
             hipLaunchKernelGGL(k3, dim3(kD10Skip + 1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps,
                                prob_stride, apply_softmax, do_sample, head_act);
             WN_LAUNCH_CHECK();
             return WN_OK;
         }
     }
-    const auto k1 = chosen ? (gate_rows ? k_decode_fast<true, true> : k_decode_fast<false, true>)
-                           : (gate_rows ? k_decode_fast<true, false> : k_decode_fast<false, false>);
+    const auto k1 = WN_DEC_PICK(k_decode_fast, gate_rows, chosen, forced);
     hipLaunchKernelGGL(k1, dim3(1), dim3(kFT), decode_fast_lds_bytes(), s, q, nlayers, nsteps, prob_stride,
                        apply_softmax, do_sample, head_act);
     WN_LAUNCH_CHECK();
@@ -940,7 +962,7 @@ int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps) {
     return n_utt * (kD10Skip + 1) <= n_cu ? 1 : 0;             // every workgroup resident (one per CU by LDS footprint)
 }
 
-int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
+int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int do_sample, int head_act,
                              bool same_weights, bool gate_rows, hipStream_t s) {
     if (!decode_fast_batch_ok(nlayers, n_utt, nsteps)) {
         wn::set_error("decode batch: %d utterances x 9 workgroups do not fit the device (or fewer than 2 steps)", n_utt);
@@ -951,8 +973,7 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
             wn::set_error("decode batch: utterance %d's step count %d outside [2, %d]", u, utt[u].nsteps, nsteps);
             return WN_EARG;
         }
-    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), k_decode_fast3_batch<false, false>, k_decode_fast3_batch<true, false>,
-                    k_decode_fast3_batch<false, true>, k_decode_fast3_batch<true, true>);
+    WN_MAX_LDS_ONCE((int)decode_fast_lds_bytes(), WN_DEC_ALL(k_decode_fast3_batch));
     const bool chosen = prob_stride == kProbChosen;
     DecBatchArgs a{};
     for (int u = 0; u < n_utt; ++u) {
@@ -968,8 +989,7 @@ int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nste
         // biases (its arena) and frame table (DecUtt.fr) stay its own, so utterances of one model may differ in class and table.
         if (same_weights) { q.P = utt[0].P; q.hbias = utt[0].hbias; q.E = utt[0].E; }
     }
-    const auto kb = chosen ? (gate_rows ? k_decode_fast3_batch<true, true> : k_decode_fast3_batch<false, true>)
-                           : (gate_rows ? k_decode_fast3_batch<true, false> : k_decode_fast3_batch<false, false>);
+    const auto kb = WN_DEC_PICK(k_decode_fast3_batch, gate_rows, chosen, do_sample == kSampleGiven);
     hipLaunchKernelGGL(kb, dim3(n_utt * (kD10Skip + 1)), dim3(kFT), decode_fast_lds_bytes(), s, a, nlayers,
                        prob_stride, head_act);
     WN_LAUNCH_CHECK();

@@ -17,6 +17,11 @@ struct DecMeta {
 // prob_stride of the step loops (both files): the floats between two rows of the probability trace, Q -- or kProbChosen: the
 // trace is ONE float per step, the probability of the token drawn (WN_DECODER_TRACE_CHOSEN).  One or the other per launch.
 static constexpr int kProbChosen = 0;
+// do_sample of the launchers (both files): 0 = no draw (wn_decoder_step), kSampleDraw = every step draws, kSampleGiven
+// (WN_DECODER_FORCED_TOKENS handles) = step `it` reads f = out_tokens[it] first and emits f when (unsigned)f < (unsigned)Q -- no
+// filter, no draw, uniforms[it] unused -- and draws as kSampleDraw does otherwise.  One value per launch.  The launchers turn
+// kSampleGiven into the FORCED instantiations of the kernels; a kernel only asks whether its do_sample is 0.
+static constexpr int kSampleDraw = 1, kSampleGiven = 2;
 struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
 // One utterance's launch arguments of the specialised decode kernels (decoder_fast.hip): filled from its handle by
 // decoder.hip, passed to the kernels by value (the batched launch passes an array of them)
@@ -39,8 +44,9 @@ int decode_fast_launch(DecUtt q, int nlayers, int nsteps, int prob_stride, int a
                        bool three_wgs, bool gate_rows, hipStream_t s);
 static constexpr int kDecMaxBatch = 28;                    // utterances per batched launch: 28 x 9 workgroups on 256 CUs
 int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps);
-// (nsteps: the launch's n, an upper bound of the utterances' counts, for the checks only: the kernel reads DecUtt.nsteps)
-int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int head_act,
+// (nsteps: the launch's n, an upper bound of the utterances' counts, for the checks only: the kernel reads DecUtt.nsteps;
+// do_sample: kSampleDraw or kSampleGiven, the launch's)
+int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int do_sample, int head_act,
                              bool same_weights, bool gate_rows, hipStream_t s);
 int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up);
 }  // namespace wn

@@ -93,25 +93,30 @@ def silence_window(params_or_Q, width):
 class _Handle(object):
     """A decoder handle of the library and what the host knows about it: whether the weights changed since it was packed
     (``stale``; a handle that holds a step limit stays stale, so that the next call takes the limit off), the class whose
-    folded gate biases it holds, whether it holds a frame table, and its form -- ``chosen``: created with
-    ``WN_DECODER_TRACE_CHOSEN``, its probability trace is one float per step."""
+    folded gate biases it holds, whether it holds a frame table, and its form ``(chosen, forced)`` -- ``chosen``: created with
+    ``WN_DECODER_TRACE_CHOSEN``, its probability trace is one float per step; ``forced``: created with
+    ``WN_DECODER_FORCED_TOKENS``, its runs read the token buffer before they write it."""
 
     def __init__(self):
-        self.h, self.stale, self.class_id, self.has_table, self.chosen = None, True, None, False, False
+        self.h, self.stale, self.class_id, self.has_table, self.chosen, self.forced = None, True, None, False, False, False
 
-    def bring(self, net, class_id, cond_of, table=None, step_limit=None, chosen=False):
+    @property
+    def form(self):
+        return (self.chosen, self.forced)
+
+    def bring(self, net, class_id, cond_of, table=None, step_limit=None, chosen=False, forced=False):
         """Create the handle, or update it when it is stale, holds another class, or is given a table or a limit (the
         update is the library's one way to set either and to start their step count again; it also re-packs the weights);
         otherwise nothing.  ``cond_of(class_id)``: the class's folded biases, asked for only when they are packed.
-        ``chosen``: the form asked for; a handle of the other form is destroyed and created anew (a handle's form is fixed
-        at create)."""
-        if self.h is not None and self.chosen != bool(chosen):
+        ``chosen`` / ``forced``: the form asked for; a handle of another form is destroyed and created anew (a handle's form
+        is fixed at create)."""
+        if self.h is not None and self.form != (bool(chosen), bool(forced)):
             self.destroy()
             self.stale, self.class_id, self.has_table = True, None, False
         if self.h is not None and not (self.stale or self.class_id != class_id or table is not None or step_limit is not None):
             return
-        d, keep = net._desc(cond_of(class_id), table, step_limit or 0, chosen)
-        self.chosen = bool(chosen)
+        d, keep = net._desc(cond_of(class_id), table, step_limit or 0, chosen, forced=forced)
+        self.chosen, self.forced = bool(chosen), bool(forced)
         if self.h is None:
             h = C.c_void_p()
             check(_lib.lib().wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
@@ -129,7 +134,9 @@ class _Handle(object):
 # one utterance of a generate_batch call: its length, uniforms, controls, class id, features as the caller gave them and their
 # phase, its window, and ``group`` -- (index of the distinct window, class, index of the distinct feature array by identity,
 # phase): utterances of one group share a prefill
-_Utterance = collections.namedtuple("_Utterance", "n u temperature top_k top_p class_id local phase window group")
+# ``forced``: its given samples (int32, -1: draw; ``sampling.check_forced``'s answer), or None
+_Utterance = collections.namedtuple("_Utterance", "n u temperature top_k top_p class_id local phase window group forced")
+_Utterance.__new__.__defaults__ = (None,)
 
 
 class FasterWaveNet(WaveNet):
@@ -142,6 +149,7 @@ class FasterWaveNet(WaveNet):
         self._dec = _Handle()              # the batch-1 handle
         self._handles = []                 # generate_batch's handles (one per utterance), created on demand
         self._trace_chosen = False         # the form of the batch-1 handle: generate(..., return_chosen=True) alone sets it
+        self._forced = False               # ... and generate(..., forced=...)
         self.prev_causal_outputs = None
         self.prev_residual_outputs = None
         self.keep_window = True            # keep the logits of the whole window on the device: _forward_one_step's reference shape
@@ -183,8 +191,10 @@ class FasterWaveNet(WaveNet):
             self.storage = storage
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self, cond=None, table=None, step_limit=0, chosen=False):
-        """``chosen``: ``WN_DECODER_TRACE_CHOSEN`` -- the handle's probability trace is the probability of each token it emits,
+    def _desc(self, cond=None, table=None, step_limit=0, chosen=False, forced=False):
+        """``forced``: ``WN_DECODER_FORCED_TOKENS`` -- a run of the handle reads its token buffer before it writes it and emits
+        the tokens it finds there instead of drawing (``forced=`` of ``generate``); it selects no other decoder.
+        ``chosen``: ``WN_DECODER_TRACE_CHOSEN`` -- the handle's probability trace is the probability of each token it emits,
         one float per step (``return_chosen``); it selects no other decoder and changes no token.
         ``step_limit``: ``WnDecoderDesc.step_limit`` -- a handle of a ragged ``generate_batch`` call ends after its own
         utterance's steps (0: no limit).
@@ -223,6 +233,8 @@ class FasterWaveNet(WaveNet):
             d.flags |= _lib.WN_DECODER_GATE_ROWS
         if chosen:
             d.flags |= _lib.WN_DECODER_TRACE_CHOSEN
+        if forced:
+            d.flags |= _lib.WN_DECODER_FORCED_TOKENS
         d.step_limit = int(step_limit)
         if table is not None:
             rows, hop, phase = table
@@ -286,10 +298,10 @@ class FasterWaveNet(WaveNet):
                 raise Exception("this model is globally conditioned: prefill with condition= first")
         if self.local_channels and table is None and dec.stale:
             raise Exception("the weights changed since the last prefill: prefill with local= again")
-        if dec.h is not None and dec.chosen != self._trace_chosen and self.local_channels and table is None:
-            raise Exception("the batch-1 handle changes its form (return_chosen): prefill with local= again")
+        if dec.h is not None and dec.form != (self._trace_chosen, self._forced) and self.local_channels and table is None:
+            raise Exception("the batch-1 handle changes its form (return_chosen / forced): prefill with local= again")
         dec.bring(self, class_id, self.condition_biases if self.condition_classes else lambda c: None, table,
-                  chosen=self._trace_chosen)
+                  chosen=self._trace_chosen, forced=self._forced)
         return dec.h
 
     # -- the reference's face -------------------------------------------------------------------
@@ -414,7 +426,8 @@ class FasterWaveNet(WaveNet):
         return out
 
     def generate(self, n_samples: int, uniforms, initial_tokens=None, return_probs: bool = False,
-                 temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, local_phase=0, return_chosen: bool = False):
+                 temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, local_phase=0, return_chosen: bool = False,
+                 forced=None):
         """Emit ``n_samples`` tokens.  Step 1 is the full forward over the initial window (ReLU head,
         like the reference's first ``_forward_one_step`` call); steps 2.. run inside one persistent
         kernel with the ELU head.  ``uniforms[i]`` is the float64 draw numpy's ``choice`` would make
@@ -436,10 +449,21 @@ class FasterWaveNet(WaveNet):
         prefill row the first draw consumed, the rest written by the decoder, one float per step:
         ``WN_DECODER_TRACE_CHOSEN``).  ``sampling.chosen_nll(chosen)`` is the utterance's nats per sample.  The tokens are
         those of a run without it.  Returns ``(tokens, chosen)``; with ``return_probs`` as well ``(tokens, probs, chosen)``,
-        on the full-row handle, ``chosen`` gathered from ``probs``."""
+        on the full-row handle, ``chosen`` gathered from ``probs``.
+
+        ``forced``: a 1-D integer array of ``n_samples`` entries -- sample i is emitted as given where ``forced[i]`` is a token
+        of ``[0, Q)`` and drawn where it is -1 (``sampling.check_forced``; anything else raises before any device work).  A
+        given sample enters the next step as a drawn one does; its uniform is not looked at; a drawn sample is drawn exactly as
+        without ``forced``.  ``probs`` rows are the post-temperature, pre-truncation rows as ever, and ``chosen[i]`` of a given
+        sample is ``probs[i, forced[i]]``: with every sample given, ``sampling.chosen_nll(chosen)`` is the decoder's own
+        likelihood of that audio.  Element 0 is the prefill's.  The handle is a ``WN_DECODER_FORCED_TOKENS`` one, created
+        anew when the last call's was not; ``forced=None`` is every call as it was."""
         Q = self.params.quantization_steps
         class_id = self._class_id(condition)
+        if forced is not None:
+            forced = sampling.check_forced(forced, n_samples, Q)
         self._trace_chosen = bool(return_chosen) and not return_probs
+        self._forced = forced is not None
         sampling.check_controls(temperature, top_k, top_p)
         top_k, top_p = int(top_k), float(top_p)
         if initial_tokens is None:
@@ -458,9 +482,11 @@ class FasterWaveNet(WaveNet):
         finally:
             self.keep_window = keep
         first_prob = self._first_row(self._last_sum_skip, p0, temperature)
-        out = torch.empty((n_samples,), device=self.device, dtype=torch.int32)
-        check(lib.wn_sample_categorical_filtered(ptr(first_prob), ptr(u), ptr(out), 1, Q, top_k, top_p, stream_ptr()),
-              "wn_sample_categorical_filtered")
+        # (given samples: the token buffer holds them before the run, element 0 -- the prefill's -- included)
+        out = torch.empty((n_samples,), device=self.device, dtype=torch.int32) if forced is None else torch.as_tensor(forced).to(self.device)
+        if forced is None or forced[0] < 0:
+            check(lib.wn_sample_categorical_filtered(ptr(first_prob), ptr(u), ptr(out), 1, Q, top_k, top_p, stream_ptr()),
+                  "wn_sample_categorical_filtered")
         probs = torch.empty((n_samples, Q), device=self.device, dtype=torch.float32) if return_probs else None
         if return_probs:
             probs[0] = first_prob[0]
@@ -530,7 +556,7 @@ class FasterWaveNet(WaveNet):
         return prompts, which
 
     def generate_batch(self, n_samples, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
-                       condition=None, local=None, local_phase=0, return_chosen: bool = False):
+                       condition=None, local=None, local_phase=0, return_chosen: bool = False, forced=None):
         """N independent utterances at once.  ``n_samples`` an int: ``uniforms`` is (N, >= n_samples) float64, utterance u draws
         with ``uniforms[u]``, and (N, n_samples) int32 tokens on the device come back.  ``n_samples`` a sequence of N positive
         ints -- a length per utterance: ``uniforms`` is an (N, >= max) array or a list of N 1-D arrays, and a LIST of N 1-D int32
@@ -562,9 +588,16 @@ class FasterWaveNet(WaveNet):
         ``return_chosen``: ``(tokens, chosen)`` comes back, ``chosen`` float32 on the device in the shape of the tokens --
         (N, n_samples), or a list of N 1-D tensors -- row u the probabilities ``generate(..., return_chosen=True)`` gives for
         utterance u, bit for bit.  The handles of such a call are ``WN_DECODER_TRACE_CHOSEN`` ones (a trace of one float per
-        step and utterance, not a row of Q); handles of the other form are created anew, and a launch never mixes the two."""
+        step and utterance, not a row of Q); handles of the other form are created anew, and a launch never mixes the two.
+
+        ``forced``: None, one 1-D integer array for all utterances (at least as long as the longest; utterance u takes its first
+        ``n_u`` entries), or a list of N entries, each such an array of the utterance's own length or None (= all -1).  Row u is
+        ``generate(..., forced=<u's entries>)`` bit for bit, tokens and ``chosen``; the handles of such a call are
+        ``WN_DECODER_FORCED_TOKENS`` ones, all of them."""
         ragged = not isinstance(n_samples, (int, np.integer))
-        recs, feats = self._batch_plan(n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase)
+        recs, feats = self._batch_plan(n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase,
+                                       forced)
+        given = forced is not None                                 # the form of every handle of the call
         N, Q, lib = len(recs), self.params.quantization_steps, _lib.lib()
         # what the batched launch does not cover runs as a loop over generate() -- same tokens, one utterance at a time --
         # decided BEFORE any work is done
@@ -572,6 +605,8 @@ class FasterWaveNet(WaveNet):
         nine = self._nine_workgroup_shape(flags)
         if nine and (any(r.n == 2 for r in recs) or flags & _lib.WN_DECODER_ONE_WORKGROUP):
             return self._generate_batch_loop(recs, ragged, return_chosen)
+        # given samples: the token buffers hold them before the launch (an utterance without any: -1 throughout)
+        held = [r.forced if r.forced is not None else np.full((r.n,), -1, np.int32) for r in recs] if given else None
         limit = int(lib.wn_decoder_batch_max()) if nine else _lib.WN_DECODER_BATCH_MAX_ANY
         live = [i for i in range(N) if recs[i].n > 1]                  # the utterances that decode at all
         # a result is a 1-D tensor per utterance, its uniforms likewise: rows of one (N, n) tensor and of one upload for
@@ -580,17 +615,19 @@ class FasterWaveNet(WaveNet):
         if ragged:
             u_dev = [torch.as_tensor(r.u).to(self.device) for r in recs]
             u0 = torch.as_tensor(np.array([r.u[0] for r in recs], dtype=np.float64)).to(self.device)
-            res = [torch.empty((r.n,), device=self.device, dtype=torch.int32) for r in recs]
+            res = [torch.empty((r.n,), device=self.device, dtype=torch.int32) if not given else
+                   torch.as_tensor(held[i]).to(self.device) for i, r in enumerate(recs)]
             ch = [torch.empty((r.n,), device=self.device, dtype=torch.float32) for r in recs] if return_chosen else None
         else:
             u = torch.as_tensor(np.stack([r.u for r in recs])).to(self.device)
             u_dev, u0 = list(u), u[:, 0].contiguous()
-            out = torch.empty((N, recs[0].n), device=self.device, dtype=torch.int32)
+            out = torch.empty((N, recs[0].n), device=self.device, dtype=torch.int32) if not given else \
+                torch.as_tensor(np.stack(held)).to(self.device)
             res = list(out)
             ch_all = torch.empty((N, recs[0].n), device=self.device, dtype=torch.float32) if return_chosen else None
             ch = list(ch_all) if return_chosen else None
         if live:
-            self._batch_handles(recs, feats, ragged, return_chosen)
+            self._batch_handles(recs, feats, ragged, return_chosen, given)
         # one prefill per group, at batch 1 as generate() runs it; the decoder states of its utterances are seeded from it,
         # and its first row (one per distinct temperature) is what generate() draws the first token from
         self.prev_causal_outputs = None
@@ -611,6 +648,9 @@ class FasterWaveNet(WaveNet):
             for i, r in enumerate(recs):                             # the truncation per utterance, as generate() draws
                 check(lib.wn_sample_categorical_filtered(ptr(first_rows[i]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1, Q,
                                                          r.top_k, r.top_p, stream_ptr()), "wn_sample_categorical_filtered")
+        if given:                                                    # a given first sample replaces the draw
+            f0 = torch.as_tensor(np.array([h[0] for h in held], dtype=np.int32)).to(self.device)
+            first = torch.where(f0 >= 0, f0, first)
         if ragged:
             for i in range(N):
                 res[i][:1] = first[i:i + 1]
@@ -626,7 +666,8 @@ class FasterWaveNet(WaveNet):
         if live:
             firsts = [int(v) for v in first.cpu().tolist()]
             # the any-shape kernel writes each utterance's tokens where they belong; the nine-workgroup form keeps its buffers
-            outs = [torch.empty((r.n - 1,), device=self.device, dtype=torch.int32) if nine else res[i][1:] for i, r in enumerate(recs)]
+            outs = [(res[i][1:].clone() if given else torch.empty((r.n - 1,), device=self.device, dtype=torch.int32)) if nine else
+                    res[i][1:] for i, r in enumerate(recs)]
             same = 0 if os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1" else 1      # the handles ARE copies of this model's weights
             # (nine-workgroup form: gate biases and frame tables are not part of the shared weights -- every utterance reads its own)
             if not nine and len({r.class_id for r in recs}) > 1:
@@ -653,7 +694,8 @@ class FasterWaveNet(WaveNet):
             return (res, ch) if ragged else (out, ch_all)
         return res if ragged else out
 
-    def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase):
+    def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase,
+                    forced=None):
         """``generate_batch``'s arguments -> (one ``_Utterance`` per utterance, {group: (features on the device or None,
         phase)}), every check that needs no decoder made, in the order the messages always came in."""
         ragged = not isinstance(n_samples, (int, np.integer))
@@ -689,9 +731,10 @@ class FasterWaveNet(WaveNet):
         else:
             per = [local] * N
         phs = [int(v) for v in sampling.per_utterance(local_phase, N, "local_phase")]
+        given = self._batch_forced(forced, ns)
         seen = {}                                                                 # the distinct feature arrays, by identity
         recs = [_Utterance(ns[i], u_rows[i], temps[i], top_ks[i], top_ps[i], cids[i], per[i], phs[i], prompts[which[i]],
-                           (which[i], cids[i], seen.setdefault(id(per[i]), len(seen)), phs[i])) for i in range(N)]
+                           (which[i], cids[i], seen.setdefault(id(per[i]), len(seen)), phs[i]), given[i]) for i in range(N)]
         # the features are checked against each utterance's own length: again only for a longer utterance than the longest so
         # far of the same (window, features, phase), so the first utterance they do not cover is the one that raises
         checked, covered = {}, {}
@@ -707,8 +750,32 @@ class FasterWaveNet(WaveNet):
                 covered[key] = r.n
         return recs, {r.group: checked[r.group[:1] + r.group[2:]] for r in recs}
 
-    def _batch_handles(self, recs, feats, ragged, chosen=False):
-        """``chosen``: the form of every handle of the call (``_Handle.bring`` creates a handle of the other form anew).
+    def _batch_forced(self, forced, ns):
+        """``generate_batch``'s ``forced`` -> one checked int32 array or None per utterance (``ns``: their lengths); the message
+        of whatever is wrong names the utterance."""
+        N, Q = len(ns), self.params.quantization_steps
+        if forced is None:
+            return [None] * N
+        if isinstance(forced, (list, tuple)) and any(e is None or np.ndim(e) > 0 for e in forced):
+            if len(forced) != N:
+                raise ValueError("generate_batch: forced= holds %d entries for %d utterances" % (len(forced), N))
+            per = list(forced)
+        else:
+            one = np.asarray(forced.detach().cpu() if hasattr(forced, "detach") else forced)
+            if one.ndim != 1 or one.shape[0] < max(ns):
+                raise ValueError("generate_batch: one forced= array for all utterances must be 1-D and hold the longest "
+                                 "utterance's %d entries, got shape %s" % (max(ns), one.shape))
+            per = [one[:n] for n in ns]
+        out = []
+        for i, (e, n) in enumerate(zip(per, ns)):
+            try:
+                out.append(None if e is None else sampling.check_forced(e, n, Q))
+            except ValueError as err:
+                raise ValueError("generate_batch: utterance %d: %s" % (i, err))
+        return out
+
+    def _batch_handles(self, recs, feats, ragged, chosen=False, forced=False):
+        """``chosen`` / ``forced``: the form of every handle of the call (``_Handle.bring`` creates a handle of another form anew).
         A handle per utterance with its sampling controls, holding its class's biases, its frame table and, in a ragged
         call, its step limit (its decode steps: the first sample comes from the prefill).  Tables and limits belong to the
         utterance, so such handles are updated in every call; a handle created here holds all of it already."""
@@ -718,7 +785,7 @@ class FasterWaveNet(WaveNet):
         def bring(h, r):
             ft, ph = feats[r.group]       # (a handle is created WITH its table)
             h.bring(self, r.class_id, biases.get, None if ft is None else self._decoder_table(ft, ph, len(r.window)),
-                    r.n - 1 if ragged else None, chosen)
+                    r.n - 1 if ragged else None, chosen, forced)
         held = len(self._handles)
         for r in recs[held:]:
             self._handles.append(_Handle())
@@ -733,7 +800,8 @@ class FasterWaveNet(WaveNet):
         ``generate(<utterance u's length>, uniforms[u], initial_tokens=<utterance u's window>)`` with utterance u's controls
         by definition); ``ragged``: a list of rows comes back."""
         rows = [self.generate(r.n, r.u, initial_tokens=r.window, temperature=r.temperature, top_k=r.top_k, top_p=r.top_p,
-                              condition=r.class_id, local=r.local, local_phase=r.phase, return_chosen=return_chosen) for r in recs]
+                              condition=r.class_id, local=r.local, local_phase=r.phase, return_chosen=return_chosen,
+                              forced=r.forced) for r in recs]
         if return_chosen:
             toks, ch = [t for t, _ in rows], [c for _, c in rows]
             return (toks, ch) if ragged else (torch.stack(toks), torch.stack(ch))

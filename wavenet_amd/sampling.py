@@ -14,6 +14,11 @@ and as the statement of the contract.  Given a row ``p`` of float32 probabilitie
 4. draw: excluded entries become 0.0f, kept entries keep their float32 value (no renormalisation in float32), and numpy's
    legacy ``choice`` runs on that row: float64 running sum, divide by the last entry, first index with ``cdf > u``.
 
+5. given samples (``forced=`` of ``FasterWaveNet.generate`` / ``generate_batch``, ``WN_DECODER_FORCED_TOKENS`` in the library): a
+   step whose entry of ``forced`` is a token of ``[0, Q)`` emits that token -- steps 1-4 do not run, the step's uniform is not
+   looked at, and the probability reported for it is the untruncated ``p[token]``; a step whose entry is -1 runs steps 1-4 as
+   ever.  ``draw_or_keep`` is the rule for one step, ``check_forced`` what a caller may pass.
+
 Everything is integer and float64 arithmetic in a fixed order (``np.cumsum`` adds sequentially), so the token equals the
 device's bit for bit when the probabilities do.  Temperature acts on the logits (``logits * (1.0f / temperature)`` in
 float32, then the softmax): ``inv_temperature`` gives that factor.
@@ -90,6 +95,34 @@ def choice_from_uniform(p, u) -> int:
 def sample(p, u, top_k=0, top_p=1.0) -> int:
     """Steps 1-4: the token drawn from the row ``p`` with the uniform ``u``."""
     return choice_from_uniform(filter_probs(p, top_k, top_p), u)
+
+
+def check_forced(forced, n_samples, Q) -> np.ndarray:
+    """``forced=`` of one utterance -> a 1-D int32 array of ``n_samples`` entries, each -1 (draw) or a token of ``[0, Q)``
+    (emit as given).  Raises ValueError for anything else -- a wrong length, a non-integer dtype, a value outside
+    ``{-1} | [0, Q)`` -- and names the first offending index.  Pure numpy: it runs before any device work."""
+    a = np.asarray(forced.detach().cpu() if hasattr(forced, "detach") else forced)
+    if a.dtype == bool or a.dtype.kind not in "iu":
+        raise ValueError("forced must hold integers (-1: draw, a token of [0, %d): emit as given), got dtype %s" % (Q, a.dtype))
+    if a.ndim != 1 or a.shape[0] != int(n_samples):
+        raise ValueError("forced must be a 1-D array of n_samples = %d entries, got shape %s" % (int(n_samples), a.shape))
+    wide = a.astype(np.int64)
+    bad = np.flatnonzero((wide < -1) | (wide >= int(Q)))
+    if bad.size:
+        raise ValueError("forced[%d] = %d is neither -1 (draw) nor a token of [0, %d)" % (bad[0], wide[bad[0]], Q))
+    return np.ascontiguousarray(wide.astype(np.int32))
+
+
+def draw_or_keep(prob, u, forced_i, temperature=1.0, top_k=0, top_p=1.0) -> int:
+    """Step 5 for one step: the given token when ``forced_i`` is one, else the draw of steps 1-4 from the row ``prob`` with
+    the uniform ``u``.  ``prob`` is the post-temperature row (``temperature`` acts on the logits, before this function: it is
+    taken for the argument check only)."""
+    check_controls(temperature, top_k, top_p)
+    if int(forced_i) != -1:
+        if not 0 <= int(forced_i) < len(prob):
+            raise ValueError("forced entry %d is neither -1 nor a token of [0, %d)" % (int(forced_i), len(prob)))
+        return int(forced_i)
+    return sample(prob, u, top_k, top_p)
 
 
 def apply_temperature(logits, temperature) -> np.ndarray:

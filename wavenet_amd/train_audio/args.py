@@ -73,8 +73,19 @@ _LIKELIHOOD_FLAGS = (
                                "weighted by samples, as evaluate --json does for held-out audio"),
     (("--best-of",), int, 1, "generate --fast: draw every utterance K times, all candidates in the same batched run, and write "
                              "the one the model found most likely (lowest nats per sample).  Likelihood rewards quiet, "
-                             "predictable audio: a ranking tool, most useful when vocoding from features, not a quality score"),
+                             "predictable audio: a ranking tool, most useful when vocoding from features, not a quality score.  "
+                             "With --keep the figure covers the kept samples too: a candidate is judged by how the real audio "
+                             "continues from what was drawn into it"),
 )
+# regenerating stretches of a recording (FasterWaveNet.generate(..., forced=...); train_audio/generate.py keep_job / keep_mask): off,
+# attributes of the namespace only when given, checked by generate before the model is built
+_KEEP_HELP = ("generate --fast: keep this recording and draw only the --redraw stretches: the file's first input_width samples are "
+              "the window, every later sample is emitted as the file has it unless a --redraw range covers it, and the output is "
+              "the file with those ranges regenerated.  Without --redraw everything is kept: with --report the run is the "
+              "decoder's own likelihood of the file.  Repeatable: one file for all utterances, or one per utterance; excludes "
+              "--prompt, -s and --local-dir")
+_REDRAW_HELP = ("generate --keep: a stretch A:B, in seconds of the kept file, to draw instead of keeping; repeatable, applies to "
+                "every utterance; it cannot start inside the window (the first input_width samples)")
 _LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
                "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
 _SPEAKER_HELP = ("generate: the speaker label to generate as (a conditioned checkpoint needs one); repeatable: one label for all "
@@ -89,6 +100,7 @@ class Args(argparse.Namespace):
     speaker_prefix, condition_channels, speaker = False, None, None
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
     report, best_of = None, 1
+    keep, redraw = None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -107,6 +119,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prompt", action="append", default=None, metavar="FILE.wav", help=_PROMPT_HELP)
     ap.add_argument("--speaker", action="append", default=argparse.SUPPRESS, metavar="LABEL", help=_SPEAKER_HELP)
     ap.add_argument("--local", action="append", default=argparse.SUPPRESS, metavar="FILE.npy", help=_LOCAL_HELP)
+    ap.add_argument("--keep", action="append", default=argparse.SUPPRESS, metavar="FILE.wav", help=_KEEP_HELP)
+    ap.add_argument("--redraw", action="append", default=argparse.SUPPRESS, metavar="A:B", help=_REDRAW_HELP)
     return ap
 
 
@@ -124,11 +138,30 @@ def utterance_prompts(args):
     return n, (files * n if len(files) == 1 else files or [None] * n)
 
 
+def kept_files(args):
+    """(number of utterances, kept file of each utterance) of a command line with --keep, or (None, None) without."""
+    if not args.keep:
+        return None, None
+    files = list(args.keep)
+    n = args.utterances if args.utterances is not None else len(files)
+    if n < 1:
+        raise ValueError("--utterances must be at least 1, got %d" % n)
+    if len(files) not in (1, n):
+        raise ValueError("%d --keep files for %d utterances: give one for all of them, or one each" % (len(files), n))
+    return n, (files * n if len(files) == 1 else files)
+
+
+def utterance_count(args):
+    """The utterances a command line asks for: --keep's, else --utterances / --prompt's, else one."""
+    return kept_files(args)[0] or utterance_prompts(args)[0] or 1
+
+
 def parse(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv, namespace=Args())
     try:
         utterance_prompts(args)
+        kept_files(args)
     except ValueError as e:
         ap.error(str(e))
     if not (0.0 <= args.ema_decay < 1.0):
@@ -146,13 +179,13 @@ def parse(argv=None):
     if args.local and args.local_dir is not None:
         ap.error("--local-dir FEAT_DIR (every feature file of a directory) and --local FILE.npy exclude each other")
     if args.local:
-        n = utterance_prompts(args)[0] or 1
+        n = utterance_count(args)
         if len(args.local) not in (1, n):
             ap.error("%d --local files for %d utterances: give one for all of them, or one each" % (len(args.local), n))
     if args.speaker:
         from .speakers import utterance_speakers
         try:
-            utterance_speakers(args.speaker, utterance_prompts(args)[0] or 1)
+            utterance_speakers(args.speaker, utterance_count(args))
         except ValueError as e:
             ap.error(str(e))
     return args

@@ -8,7 +8,12 @@ length its own features cover, all in one ragged ``generate_batch`` run.
 ``--fast --report FILE.json`` writes the negative log-likelihood the model gave every written file (nats and bits per emitted
 sample, as ``evaluate`` prints for held-out audio); ``--fast --best-of K`` draws every utterance K times in the same batched
 run and keeps the candidate the model found most likely.  Likelihood rewards quiet, predictable audio: it ranks candidates
-(most usefully when vocoding from features), it does not measure quality."""
+(most usefully when vocoding from features), it does not measure quality.
+``--fast --keep FILE.wav [--redraw A:B ...]`` regenerates stretches of a recording: the file's first ``input_width`` samples are
+the window, every later sample is emitted as the file has it (``FasterWaveNet.generate(..., forced=...)``) unless a ``--redraw``
+range, in seconds of the file, covers it, and the output is the file with those ranges drawn anew.  Without ``--redraw`` the
+run keeps everything and ``--report`` is the decoder's own likelihood of the file; ``--best-of K`` ranks on the figure over all
+emitted samples, kept ones included -- a candidate is judged by how the real audio continues from what was drawn into it."""
 from __future__ import annotations
 
 import json
@@ -270,6 +275,96 @@ def generate_directory(net, params, names, feats, lengths, cids, seed=None, outp
     return filenames, tokens
 
 
+def parse_redraw(text):
+    """``--redraw A:B`` -> (A, B) in seconds; SystemExit for anything malformed, empty or with A >= B."""
+    parts = str(text).split(":")
+    try:
+        a, b = (float(v) for v in parts) if len(parts) == 2 else (None, None)
+    except ValueError:
+        a = b = None
+    if a is None or not (math.isfinite(a) and math.isfinite(b)) or a < 0.0:
+        raise SystemExit("generate: --redraw takes A:B, two times in seconds of the kept file, got {!r}".format(text))
+    if a >= b:
+        raise SystemExit("generate: --redraw {} is empty: A:B needs A < B".format(text))
+    return a, b
+
+
+def keep_mask(M, W, ranges, sr):
+    """The forced template of a kept file of ``M`` samples behind a window of ``W``: an int32 array over the ``M - W`` emitted
+    positions (position i is file sample ``W + i``), 0 where the file's sample is kept and -1 where a range redraws it.
+    ``ranges``: (A, B) pairs in seconds; each covers samples ``[round(A sr), round(B sr))``, cut off at M; ranges may touch or
+    overlap.  A range that starts inside the window stops with the earliest time that can be redrawn."""
+    template = np.zeros((max(int(M) - int(W), 0),), dtype=np.int32)
+    for a, b in ranges:
+        lo, hi = int(round(a * sr)), min(int(round(b * sr)), int(M))
+        if lo < W:
+            raise SystemExit("generate: --redraw {:g}:{:g} starts at sample {} of the file, inside the window of {} samples that "
+                             "seeds the run: the earliest time that can be redrawn is {:.6f} s".format(a, b, lo, W, W / float(sr)))
+        if hi > lo:
+            template[lo - W:hi - W] = -1
+    return template
+
+
+def keep_job(args, seconds_given):
+    """``generate --keep FILE.wav [--redraw A:B ...]``: every check, made before a model is built.  Returns None without
+    ``--keep``, else (kept file of each utterance, its tokens, its forced array over the emitted positions, single) --
+    ``single``: one utterance written as ``generated.wav``."""
+    if args.redraw and not args.keep:
+        raise SystemExit("generate: --redraw A:B says what to draw anew of a kept recording: give --keep FILE.wav")
+    if not args.keep:
+        return None
+    if not args.fast:
+        raise SystemExit("generate: --keep hands the kept samples to the decoder on the device: give --fast")
+    if args.prompt or seconds_given or args.local_dir is not None:
+        raise SystemExit("generate: --keep takes the window, the length and the samples from the kept file: --prompt, -s and "
+                         "--local-dir do not go with it")
+    ranges = [parse_redraw(r) for r in (args.redraw or [])]
+    n_utt, files = _args.kept_files(args)
+    params = _model.load_params(args.model_dir)
+    Q, W, sr = params.quantization_steps, input_width_of(params), params.sampling_rate
+    read = {}
+    for f in files:
+        if f not in read:
+            t = np.asarray(data.load_audio_file(f, quantization_steps=Q)[0], dtype=np.int32)
+            if t.size < W + 2:
+                raise SystemExit("generate: --keep {} holds {} samples as training reads it; the window takes {} and the decoder "
+                                 "runs two more at least: {} are needed".format(f, t.size, W, W + 2))
+            template = keep_mask(t.size, W, ranges, sr)
+            read[f] = (t, np.where(template < 0, -1, t[W:]).astype(np.int32))
+    return files, [read[f][0] for f in files], [read[f][1] for f in files], args.utterances is None and len(files) == 1
+
+
+def generate_kept(net, params, files, tokens, forced, single, output_dir="generated_audio", temperature=1.0, top_k=0, top_p=1.0,
+                  conditions=None, locals_=None, best_of=1, report=None):
+    """One ``generate_batch`` run over the kept files: utterance u starts from its file's first ``input_width`` samples, emits
+    ``forced[u]`` where that is a token and draws where it is -1, and is written as those samples followed by what was emitted --
+    the file, with the ``--redraw`` ranges regenerated.  Uniforms: utterance after utterance, ``random_sample((K, n_u))``, row c
+    candidate c's.  ``best_of`` = K > 1: rows ``u * K + c`` of the run; the figure ranked on (and reported) is over all ``n_u``
+    emitted samples, kept ones included."""
+    Q, W, K = params.quantization_steps, input_width_of(params), best_of
+    sampling.check_controls(temperature, top_k, top_p)
+    lengths = [len(f) for f in forced]
+    uniforms = [row for n in lengths for row in np.random.random_sample((K, n))]
+    start_time = time.time()
+    rep_k = lambda xs: [x for x in xs for _ in range(K)]
+    lkw = {} if locals_ is None else {"local": rep_k(locals_)}
+    want = K > 1 or bool(report)
+    got = net.generate_batch(rep_k(lengths), uniforms, initial_tokens=np.stack(rep_k([t[:W] for t in tokens])),
+                             temperature=temperature, top_k=top_k, top_p=top_p, condition=None if conditions is None else rep_k(conditions),
+                             return_chosen=want, forced=rep_k(forced), **lkw)
+    ranked = None
+    if want:
+        emitted, ranked = _keep_best(list(got[0]), list(got[1]), K)
+    else:
+        emitted = [r.cpu().numpy() for r in got]
+    whole = [np.concatenate([t[:W], e.astype(np.int32)]) for t, e in zip(tokens, emitted)]
+    names = ["generated"] if single else ["generated_{:03d}".format(i) for i in range(len(files))]
+    filenames = _save(start_time, output_dir, Q, params.sampling_rate, list(zip(names, whole)))
+    if report:
+        write_report(report, filenames, emitted, ranked, K)
+    return (filenames[0], whole[0]) if single else (filenames, whole)
+
+
 def _seconds_given(argv) -> bool:
     """Whether the command line names -s / --seconds (its default, 1.0, is a length like any other when it is given)."""
     import argparse
@@ -283,12 +378,15 @@ def main(argv=None):
     args = _args.parse(argv)
     best_of, report = likelihood_job(args)
     seconds_given = _seconds_given(argv)
+    kept = keep_job(args, seconds_given)
     if args.local_dir is not None:
         names, feats, lengths, cids = directory_job(args, seconds_given)
         params, net = _model.build(args)
         return generate_directory(net, params, names, feats, lengths, cids, seed=args.seed, output_dir=args.output_dir,
                                   temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, best_of=best_of, report=report)
     n_utt, prompt_files = _args.utterance_prompts(args)
+    if kept is not None:
+        n_utt = len(kept[0])
     # the speaker of every utterance, checked against the checkpoint's table before the model is built: an unknown label,
     # --speaker on an unconditioned checkpoint and its absence on a conditioned one all stop here with a clear message
     table = _speakers.load_table(args.model_dir)
@@ -313,11 +411,19 @@ def main(argv=None):
         feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir)) for f in feats]
         if cover < 1:
             raise SystemExit("generate: the features cover {} samples, fewer than the {} of the window".format(cover + iw - 1, iw))
-        if not seconds_given:
+        if kept is not None:
+            short = [f for f, fd in zip(kept[0], kept[2]) if len(fd) > cover]
+            if short:
+                raise SystemExit("generate: --keep {} emits {} samples behind its window, the features cover {}".format(
+                    short[0], max(len(fd) for fd in kept[2]), cover))
+        elif not seconds_given:
             args.seconds = (cover + 1.5) / float(params.sampling_rate)            # int(rate * seconds) - 1 == cover
         elif int(params.sampling_rate * args.seconds) - 1 > cover:
             raise SystemExit("generate: -s {} asks for {} samples, the features cover {}".format(
                 args.seconds, int(params.sampling_rate * args.seconds) - 1, cover))
+    if kept is not None:
+        return generate_kept(net, params, *kept, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
+                             top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of, report=report)
     if n_utt is not None:
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
