@@ -145,7 +145,7 @@ class FasterWaveNet(WaveNet):
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
                  condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
-                 local_interp: str = "repeat"):
+                 local_interp: str = "repeat", local_upsample: int = 1):
         self._dec = _Handle()              # the batch-1 handle
         self._handles = []                 # generate_batch's handles (one per utterance), created on demand
         self._trace_chosen = False         # the form of the batch-1 handle: generate(..., return_chosen=True) alone sets it
@@ -157,7 +157,8 @@ class FasterWaveNet(WaveNet):
         self._hist_pos = 0
         super().__init__(params, compat_zero_prefix=compat_zero_prefix, seed=seed, storage=storage,
                          condition_classes=condition_classes, condition_channels=condition_channels,
-                         local_channels=local_channels, local_hop=local_hop, local_interp=local_interp)
+                         local_channels=local_channels, local_hop=local_hop, local_interp=local_interp,
+                         local_upsample=local_upsample)
 
     def close(self):
         """Destroy every decoder handle (under the library that is loaded now) and forget them."""
@@ -269,11 +270,14 @@ class FasterWaveNet(WaveNet):
         """The decoder's table after a prefill over W positions: the step that consumes the sample at absolute position
         p = phase + W + k reads column p // hop, so the handle gets the rows from column (phase + W) // hop on and the phase
         (phase + W) % hop.  With linear interpolation a step also reads the column after its own; the rows go on to the last
-        column given, so the one after the last that is needed is there (``_utterance_local`` has checked it)."""
-        col, ph = divmod(int(phase) + int(W), self.local_hop)
+        column given, so the one after the last that is needed is there (``_utterance_local`` has checked it).  With a learned
+        upsampling layer (``local_upsample`` > 1) the utterance's features go through it once, ``hop`` is the fine hop
+        H' = local_hop / local_upsample and the table holds the fine columns' rows: the decoders run at hop H'."""
+        hop = self.local_fine_hop
+        col, ph = divmod(int(phase) + int(W), hop)
         rows = self.local_biases(feats[0], phase)
         col = min(col, int(rows.shape[0]) - 1)            # (n_samples == 1: nothing is decoded, any row will do)
-        return rows[col:].contiguous(), self.local_hop, ph
+        return rows[col:].contiguous(), hop, ph
 
     def _class_id(self, condition):
         """``condition=`` of the batch-1 methods (an id, or a sequence holding one) -> int, or None for an unconditioned model."""

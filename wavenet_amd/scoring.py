@@ -70,7 +70,8 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
     the first sample reads column 0.  The pieces of one launch share one phase, so ``chunk_width`` must be a multiple of H
     (raises otherwise); the result still does not depend on ``chunk_width`` or ``batch_size`` beyond arithmetic.  With
     ``local_interp="linear"`` every sample also reads the column after its own, so ``local`` needs ceil(n / H) + 1 columns
-    and neighbouring pieces overlap by one column."""
+    and neighbouring pieces overlap by one column.  With a learned upsampling layer (``local_upsample`` = U > 1) ``local``
+    needs ``coarse_frames_needed(n, H, U, 0, interp)`` columns -- the layer reads pairs of neighbouring columns."""
     import torch
     t = net.to_variable(np.asarray(tokens) if not isinstance(tokens, torch.Tensor) else tokens)
     if t.dim() != 1 or t.is_floating_point():
@@ -112,6 +113,9 @@ def score(net, tokens, chunk_width: int = 16384, batch_size: int = 8, condition=
         if ext is not None:
             ph = (launch[0][0] + shift) % H
             need = (C - 1 + w + ph + H - 1) // H + (1 if getattr(net, "local_interp", "repeat") == "linear" else 0)
+            if getattr(net, "local_upsample", 1) > 1:                            # a learned upsampling layer reads pairs of columns
+                from .wavenet import coarse_frames_needed
+                need = coarse_frames_needed(C - 1 + w, H, net.local_upsample, ph, net.local_interp)
             kw = dict(local=torch.stack([ext[:, (a + shift) // H:(a + shift) // H + need] for a, _ in launch]).contiguous(),
                       local_phase=ph)
         out[launch[0][0]:launch[-1][0] + w] = net.token_nll(x, tgt, condition=cond, **kw).reshape(-1)

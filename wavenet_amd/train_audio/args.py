@@ -64,6 +64,9 @@ _LOCAL_FLAGS = (
     (("--local-crop",), str, None, "train --local-dir: where crops start, 'frame' (on a feature column border, the default) or "
                                    "'sample' (anywhere, as without features: one --seed selects the same crops; every crop "
                                    "carries its own phase).  A property of the run, not of the checkpoint"),
+    (("--local-upsample",), int, None, "train --local-dir: a learned upsampling layer of factor U ahead of the projection (U "
+                                       "divides the hop; the network then runs at hop / U); stored in local.json when U > 1, "
+                                       "which generate and evaluate follow"),
 )
 # likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
 # attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
@@ -99,6 +102,7 @@ class Args(argparse.Namespace):
     ema_decay, valid_wav_dir, ema = 0.0, None, False
     speaker_prefix, condition_channels, speaker = False, None, None
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
+    local_upsample = None
     report, best_of = None, 1
     keep, redraw = None, None
 
@@ -176,6 +180,8 @@ def parse(argv=None):
         ap.error("--local-interp {repeat,linear} goes with --local-dir")
     if args.local_crop is not None and (args.local_dir is None or args.local_crop not in ("frame", "sample")):
         ap.error("--local-crop {frame,sample} goes with --local-dir")
+    if args.local_upsample is not None and (args.local_dir is None or args.local_upsample < 1):
+        ap.error("--local-upsample U goes with --local-dir and needs U >= 1")
     if args.local and args.local_dir is not None:
         ap.error("--local-dir FEAT_DIR (every feature file of a directory) and --local FILE.npy exclude each other")
     if args.local:

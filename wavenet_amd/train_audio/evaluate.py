@@ -55,7 +55,8 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     for fn in files:
         tokens, _ = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
         lkw = {} if local is None else {"local": _local.with_extra_column(
-            _local.file_features(local_dir, fn, tokens.size, local[0], local[1]), getattr(net, "local_interp", "repeat"))}
+            _local.file_features(local_dir, fn, tokens.size, local[0], local[1]), getattr(net, "local_interp", "repeat"),
+            getattr(net, "local_upsample", 1))}
         row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn], **lkw))
         rows.append(dict(file=fn, **row))
         nats += row["nats_per_sample"] * row["samples"]

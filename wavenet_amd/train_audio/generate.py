@@ -229,7 +229,7 @@ def directory_job(args, seconds_given):
     cap = int(params.sampling_rate * args.seconds) - 1 if seconds_given else None
     if cap is not None and cap < 1:
         raise SystemExit("{}: -s {} asks for {} samples".format(what, args.seconds, cap))
-    interp = _local.load_interp(args.model_dir)
+    interp, upsample = _local.load_interp(args.model_dir), _local.load_upsample(args.model_dir)
     feats, lengths = [], []
     for name in names:
         f = _local.read_features(os.path.join(args.local_dir, name + ".npy"), config[0])
@@ -239,7 +239,7 @@ def directory_job(args, seconds_given):
             raise SystemExit("generate: the features of {}.npy cover {} samples, fewer than the {} of the window".format(
                 name, cover + iw - 1, iw))
         lengths.append(cover if cap is None else min(cover, cap))
-        feats.append(_local.with_extra_column(f, interp))
+        feats.append(_local.with_extra_column(f, interp, upsample))
     return names, feats, lengths, cids
 
 
@@ -408,7 +408,8 @@ def main(argv=None):
         cover = min(f.shape[1] for f in feats) * config[1] - iw + 1          # samples that can be emitted
         # (linear interpolation: the column behind the last is the driver's to supply -- the file's last one again -- so n
         # columns still give n * hop samples)
-        feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir)) for f in feats]
+        # (a learned upsampling layer reads pairs of columns: one more copy of the last, likewise)
+        feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir), _local.load_upsample(args.model_dir)) for f in feats]
         if cover < 1:
             raise SystemExit("generate: the features cover {} samples, fewer than the {} of the window".format(cover + iw - 1, iw))
         if kept is not None:

@@ -7,7 +7,8 @@ tokens k * hop .. (k + 1) * hop - 1.  ``python -m wavenet_amd.train_audio.featur
 ``local.json`` holds ``{"channels": F, "hop": H}``: whenever it exists the network is built locally conditioned
 (``wavenet.json`` is unchanged), and a resumed run must find the same values.  ``train --local-interp linear`` adds
 ``"interp": "linear"`` -- the key is written ONLY then, so a repeat-mode file is byte for byte what it always was; a file
-without it means "repeat" (``load_interp``).
+without it means "repeat" (``load_interp``).  ``train --local-upsample U`` adds ``"upsample": U`` the same way, ONLY for U > 1
+(``load_upsample``): the network is then built with a learned upsampling layer of that factor ahead of the projection.
 
 Linear interpolation reads, at every position, the column after the position's own, so a window needs one more column than it
 spans.  The library never clamps: the drivers supply that column by repeating the file's last one (``with_extra_column``);
@@ -54,28 +55,55 @@ def load_interp(model_dir: str) -> Optional[str]:
     return interp
 
 
-def with_extra_column(features: np.ndarray, interp: Optional[str]) -> np.ndarray:
+def load_upsample(model_dir: str) -> Optional[int]:
+    """U of ``<model_dir>/local.json``: the factor of the learned upsampling layer (no "upsample" key: 1, none); None when
+    the checkpoint is not locally conditioned."""
+    have = load_config(model_dir)
+    if have is None:
+        return None
+    filename = os.path.join(model_dir, FILE)
+    with open(filename) as f:
+        u = json.load(f).get("upsample", 1)
+    if not isinstance(u, int) or u < 1 or have[1] % u:
+        raise Exception("{}: \"upsample\" must be an integer >= 1 that divides the hop {}, got {!r}".format(filename, have[1], u))
+    return u
+
+
+def with_extra_column(features: np.ndarray, interp: Optional[str], upsample: int = 1) -> np.ndarray:
     """The features as the network takes them: with ``interp == "linear"`` the last column once more behind the others (the
-    column that the last position's interpolation reads); unchanged otherwise."""
-    if interp != "linear":
+    column that the last position's interpolation reads); with a learned upsampling layer (``upsample`` > 1) once more
+    again (the layer reads pairs of neighbouring columns: n columns make (n - 1) * upsample fine ones) -- what
+    ``coarse_frames_needed`` asks for at the file's end; unchanged otherwise."""
+    extra = (1 if interp == "linear" else 0) + (1 if int(upsample) > 1 else 0)
+    if not extra:
         return features
-    return np.ascontiguousarray(np.concatenate([features, features[:, -1:]], axis=1))
+    return np.ascontiguousarray(np.concatenate([features] + [features[:, -1:]] * extra, axis=1))
 
 
-def ensure_config(model_dir: str, channels: int, hop: int, interp: Optional[str] = None) -> Tuple[int, int]:
+def ensure_config(model_dir: str, channels: int, hop: int, interp: Optional[str] = None,
+                  upsample: Optional[int] = None) -> Tuple[int, int]:
     """train --local-dir: write the file on the first run; a resumed run must find the SAME values or it stops.  ``interp``:
-    what --local-interp gave (None: not given -- a first run then trains "repeat", a resumed one keeps the file's mode)."""
+    what --local-interp gave (None: not given -- a first run then trains "repeat", a resumed one keeps the file's mode).
+    ``upsample``: what --local-upsample gave, likewise (None: a first run trains without the layer, a resumed one keeps the
+    file's factor); ``"upsample": U`` is written ONLY for U > 1."""
     have = load_config(model_dir)
     if interp is not None and interp not in INTERP:
         raise SystemExit("--local-interp must be one of {}, got {!r}".format(list(INTERP), interp))
+    if upsample is not None and (int(upsample) < 1 or int(hop) % int(upsample)):
+        raise SystemExit("--local-upsample must be >= 1 and divide the hop {}, got {}".format(int(hop), upsample))
     if have is None:
         os.makedirs(model_dir, exist_ok=True)
         d = {"channels": int(channels), "hop": int(hop)}
         if interp == "linear":
             d["interp"] = "linear"
+        if upsample is not None and int(upsample) > 1:
+            d["upsample"] = int(upsample)
         with open(os.path.join(model_dir, FILE), "w") as f:
             json.dump(d, f)
         return int(channels), int(hop)
+    if upsample is not None and int(upsample) != load_upsample(model_dir):
+        raise SystemExit("{}: this checkpoint was trained with --local-upsample {}, the command line gives {}: a resumed run "
+                         "must find the same value".format(os.path.join(model_dir, FILE), load_upsample(model_dir), int(upsample)))
     if interp is not None and interp != load_interp(model_dir):
         raise SystemExit("{}: this checkpoint was trained with --local-interp {}, the command line gives {}: a resumed run must "
                          "find the same mode".format(os.path.join(model_dir, FILE), load_interp(model_dir), interp))

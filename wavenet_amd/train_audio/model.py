@@ -65,7 +65,8 @@ def build(args, train: bool = False):
     Features: ``args.local_dir`` with ``train`` (the training driver) reads the channel count F from the feature file of the first .wav file and writes it,
     with the hop, to ``local.json`` -- or checks both against the one already there.  Whenever that file exists the network
     is built locally conditioned, and ``net.local`` is (F, hop) (None otherwise); ``args.local_interp`` (train) goes into the
-    file the same way and ``net.local_interp`` is the file's mode."""
+    file the same way and ``net.local_interp`` is the file's mode; so does ``args.local_upsample`` (``"upsample"``, written
+    for U > 1 only), and ``net.local_upsample`` is the file's factor."""
     params = load_params(args.model_dir)
     local_dir = getattr(args, "local_dir", None)
     if local_dir is not None and train:                                     # (evaluate and generate read the config only)
@@ -73,7 +74,7 @@ def build(args, train: bool = False):
         have = _local.load_config(args.model_dir)
         hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
         local = _local.ensure_config(args.model_dir, _local.directory_channels(local_dir, wavs), hop,
-                                     getattr(args, "local_interp", None))
+                                     getattr(args, "local_interp", None), getattr(args, "local_upsample", None))
     else:
         local = _local.load_config(args.model_dir)
     if bool(getattr(args, "speaker_prefix", False)):
@@ -84,6 +85,8 @@ def build(args, train: bool = False):
     cond = dict(condition_classes=len(table[0]), condition_channels=table[1]) if table else {}
     if local:
         cond.update(local_channels=local[0], local_hop=local[1], local_interp=_local.load_interp(args.model_dir))
+        if _local.load_upsample(args.model_dir) > 1:                            # a learned upsampling layer ahead of the projection
+            cond.update(local_upsample=_local.load_upsample(args.model_dir))
     net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed, **cond)
     net.speakers = table[0] if table else None
     net.local = local

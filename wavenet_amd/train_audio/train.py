@@ -11,6 +11,7 @@ import torch
 
 from .. import TrainStepGraph, data
 from ..graph import default_loss
+from ..wavenet import coarse_frames_needed
 from . import args as _args
 from . import model as _model
 from .evaluate import evaluate_dir
@@ -32,7 +33,7 @@ class _Crops(object):
     global generator (the draw the reference makes, so ``--seed`` selects the same crops), the gather runs on the GPU."""
 
     def __init__(self, signal: np.ndarray, input_width: int, target_width: int, device, features=None, hop=0, shift=0,
-                 extra_column=False, crop="frame"):
+                 extra_column=False, crop="frame", columns=None):
         """``features`` (F, columns) on the grid ``local.padded`` describes (index into ``signal`` + ``shift`` = position,
         position // hop = column): starts are then drawn so that every crop begins on a column border (phase 0), and ``draw``
         also returns the crops' (B, F, ceil((input_width + target_width) / hop)) columns -- one more with ``extra_column``
@@ -41,7 +42,8 @@ class _Crops(object):
         ``np.random.randint`` call, so one ``--seed`` selects the same crops with and without features -- and ``draw`` also
         returns every crop's phase (start + shift) % hop; the columns run from (start + shift) // hop on and there are as
         many as the worst phase needs, ceil((input_width + target_width + hop - 1) / hop) (one more with ``extra_column``),
-        the file's last column repeated where that runs past the file."""
+        the file's last column repeated where that runs past the file.  ``columns``: the column count itself, when another
+        rule gives it (a learned upsampling layer: ``coarse_frames_needed``)."""
         if crop not in ("frame", "sample"):
             raise Exception("crop must be 'frame' or 'sample', got %r" % (crop,))
         self.hop, self.shift, self.crop = int(hop), int(shift), crop
@@ -49,7 +51,8 @@ class _Crops(object):
         if features is not None:
             self.features = torch.as_tensor(features).to(device)
             worst = hop - 1 if crop == "sample" else 0
-            self.fcol = torch.arange((input_width + target_width + worst + hop - 1) // hop + int(extra_column), device=device)
+            ncol = (input_width + target_width + worst + hop - 1) // hop + int(extra_column)
+            self.fcol = torch.arange(ncol if columns is None else int(columns), device=device)
         self.n = int(signal.size)
         self.iw, self.tw = input_width, target_width
         if self.n - target_width - input_width - 1 <= 0:
@@ -102,8 +105,11 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     if local is not None:
         feats = _local.file_features(local_dir, path_to_file, signals.size, local[0], local[1])
         interp = getattr(net, "local_interp", "repeat")
-        ext, shift = _local.padded(_local.with_extra_column(feats, interp), iw, local[1])
+        U = getattr(net, "local_upsample", 1)
+        ext, shift = _local.padded(_local.with_extra_column(feats, interp, U), iw, local[1])
         fkw = dict(features=ext, hop=local[1], shift=shift, extra_column=interp == "linear", crop=local_crop)
+        if U > 1:                                                  # the learned layer reads pairs of neighbouring columns
+            fkw["columns"] = coarse_frames_needed(iw + train_width, local[1], U, None if local_crop == "sample" else 0, interp)
     signals = np.concatenate([np.full((iw,), silence, dtype=np.int32), signals.astype(np.int32)])   # train.py:53
     crops = _Crops(signals, iw, train_width, net.device, **fkw)
     # a conditioned model: every crop carries the label of the file it came from

@@ -466,6 +466,23 @@ def frames_needed(T: int, hop: int, phase: int = 0, interp: str = "repeat") -> i
     return (int(T) + int(phase) + int(hop) - 1) // int(hop) + (1 if interp == "linear" else 0)
 
 
+def coarse_frames_needed(T: int, hop: int, upsample: int = 1, phase=0, interp: str = "repeat") -> int:
+    """Feature columns at hop ``hop`` that a window of ``T`` positions reads through a learned upsampling layer of factor
+    ``upsample`` (``local_upsample``): the layer makes (n - 1) * upsample fine columns at hop' = hop / upsample out of n
+    coarse ones, the window starts ``phase`` positions into coarse column 0 -- that is, at fine column c0 = phase // hop',
+    phase' = phase % hop' -- and reads nf = ``frames_needed(T, hop', phase', interp)`` fine columns from there:
+    ceil((c0 + nf) / upsample) + 1.  ``phase`` None: a phase per clip, sized for the worst case c0 = upsample - 1 and
+    phase' = hop' - 1.  ``upsample`` = 1 is ``frames_needed`` itself (no layer, no column more)."""
+    T, hop, upsample = int(T), int(hop), int(upsample)
+    if upsample < 1 or hop % upsample:
+        raise Exception("coarse_frames_needed: upsample must be >= 1 and divide hop = %d, got %d" % (hop, upsample))
+    if upsample == 1:
+        return frames_needed(T, hop, hop - 1 if phase is None else phase, interp)
+    fine = hop // upsample
+    c0, ph = (upsample - 1, fine - 1) if phase is None else divmod(int(phase), fine)
+    return (c0 + frames_needed(T, fine, ph, interp) + upsample - 1) // upsample + 1
+
+
 def local_alignment(s0: int, hop: int):
     """THE alignment rule of local conditioning, in one place: network input position t of a clip whose first input sample is
     sample ``s0`` of its file reads feature column (s0 + t) // hop.  Returns (first column, phase) = (s0 // hop, s0 % hop): the
@@ -507,6 +524,47 @@ class _LocalFn(_Fn):
         check(_lib.lib().wn_pointwise_bwd(ptr(h), ptr(V), ptr(dout), ptr(dh), ptr(V.grad), None, B * n, F, V.shape[0],
                                           ACT["none"], ctx.net._exec(), stream_ptr()), "wn_pointwise_bwd")
         return (None if dh is None else dh.view(B, n, F).permute(0, 2, 1)), None, None
+
+
+class _UpsampleFn(_Fn):
+    """Learned upsampling ahead of the projection (van den Oord et al. 2016, section 2.5: "a transposed convolutional network
+    (learned upsampling)"): features (B, F, n) at hop H -> fine features (B, (n - 1) U, F) at hop H / U, time-major.  A
+    transposed convolution of stride U and kernel 2 U over the frame axis, written as ONE channel GEMM (``wn_pointwise_*``,
+    the entry point ``_LocalFn`` uses): the input is the (B (n - 1), 2 F) matrix of neighbouring column pairs (h_k ; h_k+1),
+    the weight W is (U F, 2 F), and the output (B (n - 1), U F) viewed as (B, (n - 1) U, F) IS the fine sequence -- row
+    q F + c of W makes channel c of fine column k U + q.  No bias, no activation.  The weight's gradient goes straight into
+    the gradient arena; the coarse features receive theirs when they require grad: the two halves of the pair matrix's
+    gradient, added back onto columns k and k + 1."""
+
+    @staticmethod
+    def forward(ctx, feats, W, net):
+        B, F, n = feats.shape
+        U = W.shape[0] // F
+        h = feats.permute(0, 2, 1)
+        pairs = torch.cat([h[:, :-1], h[:, 1:]], dim=2).contiguous().view(B * (n - 1), 2 * F)
+        out = torch.empty((B, (n - 1) * U, F), device=pairs.device, dtype=torch.float32)
+        check(_lib.lib().wn_pointwise_fwd(ptr(pairs), ptr(W), None, ptr(out), B * (n - 1), 2 * F, U * F, ACT["none"],
+                                          net._exec(), stream_ptr()), "wn_pointwise_fwd")
+        ctx.save_for_backward(pairs)
+        ctx.W, ctx.net, ctx.shape = W, net, (B, F, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (pairs,) = ctx.saved_tensors
+        W = ctx.W
+        B, F, n = ctx.shape
+        dout = dout.contiguous()
+        dp = torch.empty_like(pairs) if ctx.needs_input_grad[0] else None
+        check(_lib.lib().wn_pointwise_bwd(ptr(pairs), ptr(W), ptr(dout), ptr(dp), ptr(W.grad), None, B * (n - 1), 2 * F,
+                                          W.shape[0], ACT["none"], ctx.net._exec(), stream_ptr()), "wn_pointwise_bwd")
+        if dp is None:
+            return None, None, None
+        dp = dp.view(B, n - 1, 2 * F)
+        dh = torch.zeros((B, n, F), device=dp.device, dtype=torch.float32)
+        dh[:, :-1] += dp[:, :, :F]
+        dh[:, 1:] += dp[:, :, F:]
+        return dh.permute(0, 2, 1), None, None
 
 
 class _CondFn(_Fn):
@@ -809,7 +867,7 @@ class WaveNet(object):
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
                  condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
-                 local_interp: str = "repeat"):
+                 local_interp: str = "repeat", local_upsample: int = 1):
         """``storage="bf16"`` (BASELINE config 5; not in the reference): activations in bfloat16, fp32 accumulation, fp32
         master weights; for 128 residual / dilation channels, filter width 2, a multiple of 256 skip channels.
 
@@ -847,10 +905,35 @@ class WaveNet(object):
         per clip, each in [0, H) (anything else raises before any device work and names the first offending clip).  The
         phases then live in device memory (``WnStackDesc.bias_phase_tab``) and are read when the kernels run, so one batch --
         and one captured step -- holds clips that start at any sample.  Every clip then needs
-        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase."""
+        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase.
+
+        ``local_upsample`` = U (1, the default: none, and the model is byte for byte what it was; U > 1 must divide H): a
+        LEARNED upsampling layer ahead of the projection (section 2.5 of the paper).  It takes the features from hop H to hop
+        H' = H / U; the projection, the layer kernels and the decoders then run at hop H' in the model's ``local_interp``
+        mode.  One more link, last of all in the arena: ``local_condition_upsample/W`` (U F, 2 F, 1, 1).  For coarse columns
+        h_k, rows q F .. (q + 1) F of W make fine column m = k U + q, q in [0, U):
+        y[:, k U + q] = W[qF:(q+1)F, :F] h_k + W[qF:(q+1)F, F:] h_k+1 -- a transposed convolution of stride U and kernel 2 U over
+        the frame axis, one channel GEMM over the (B (n - 1), 2 F) matrix of neighbouring column pairs (``_UpsampleFn``), no
+        bias, no activation.  n coarse columns make (n - 1) U fine ones; fine column m is anchored at position m H'.  The
+        weight starts, without a draw from the RNG, at linear interpolation between the coarse columns
+        (W[qF + c, c] = 1 - float32(q) / float32(U), W[qF + c, F + c] = float32(q) / float32(U), 0 elsewhere), so every other
+        tensor equals the same-seed U = 1 model's and a "linear" model starts, in exact arithmetic, as the U = 1 linear
+        model at hop H.  The caller's contract does not change: coarse columns from s0 // H on and ``local_phase`` = s0 % H
+        in [0, H), an int or one per clip.  The fine sequence is cut at fine column phase // H' (per clip: gathered on the
+        device) and the stack runs at phase % H'.  A window needs ``coarse_frames_needed(T, H, U, phase, interp)`` columns
+        (a phase per clip: ``phase=None``, the worst case); surplus ones are ignored.  ``upsampled_features`` returns the
+        layer's output; ``local_biases`` then holds one row per FINE column."""
         params.check()
         if storage not in ("fp32", "bf16"):
             raise Exception("storage must be 'fp32' or 'bf16'")
+        self.local_upsample = int(local_upsample)
+        if self.local_upsample < 1:
+            raise Exception("local_upsample must be >= 1 (1: no learned upsampling), got %d" % self.local_upsample)
+        if self.local_upsample > 1 and not (int(local_channels) > 0 and int(local_hop) > 0):
+            raise Exception("local_upsample = %d needs local conditioning (local_channels / local_hop)" % self.local_upsample)
+        if self.local_upsample > 1 and int(local_hop) % self.local_upsample:
+            raise Exception("local_upsample = %d does not divide local_hop = %d (the fine hop is local_hop / local_upsample)"
+                            % (self.local_upsample, int(local_hop)))
         self.condition_classes, self.condition_channels = int(condition_classes), int(condition_channels)
         if (self.condition_classes > 0) != (self.condition_channels > 0) or self.condition_classes < 0 or self.condition_channels < 0:
             raise Exception("global conditioning needs condition_classes > 0 and condition_channels > 0 (or both 0: off), got "
@@ -945,6 +1028,10 @@ class WaveNet(object):
         self.local_condition_projection = None
         if self.local_channels:
             self.local_condition_projection = _Link("local_condition_projection", (self._cond_rows, self.local_channels, 1, 1), None)
+        self.local_condition_upsample = None
+        if self.local_upsample > 1:
+            self.local_condition_upsample = _Link("local_condition_upsample", (self.local_upsample * self.local_channels,
+                                                                               2 * self.local_channels, 1, 1), None)
         if self.condition_classes:
             self.global_condition_embed = _Link("global_condition_embed",
                                                 (self.condition_classes, self.condition_channels, 1, 1), None)
@@ -961,7 +1048,25 @@ class WaveNet(object):
             out += [self.global_condition_embed, self.global_condition_projection]
         if self.local_channels:                                      # last of all, with or without global conditioning
             out.append(self.local_condition_projection)
+        if self.local_upsample > 1:                                  # ... and the learned upsampling layer behind it
+            out.append(self.local_condition_upsample)
         return out
+
+    @property
+    def local_fine_hop(self) -> int:
+        """The hop the projection, the layer kernels and the decoders run at: local_hop / local_upsample."""
+        return self.local_hop // self.local_upsample
+
+    def _upsample_init(self) -> np.ndarray:
+        """The learned upsampling layer's starting weight (U F, 2 F): linear interpolation between the coarse columns."""
+        U, F = self.local_upsample, self.local_channels
+        w = np.zeros((U * F, 2 * F), dtype=np.float32)
+        c = np.arange(F)
+        for q in range(U):
+            a = np.float32(q) / np.float32(U)
+            w[q * F + c, c] = np.float32(1) - a
+            w[q * F + c, F + c] = a
+        return w
 
     # -- parameters: one flat arena (what the DP all-reduce and the optimiser kernel see) -----
     def _allocate(self, seed):
@@ -978,7 +1083,9 @@ class WaveNet(object):
         self._spans = spans
         host = np.zeros((off,), dtype=np.float32)
         for ln, kind, o, n, shape in spans:
-            if kind == "W":                                         # LeCunNormal like Chainer's default
+            if ln is self.local_condition_upsample:                # no draw: every other tensor is the U = 1 model's
+                host[o:o + n] = self._upsample_init().reshape(-1)
+            elif kind == "W":                                       # LeCunNormal like Chainer's default
                 fan_in = shape[1] * shape[2] * shape[3]
                 host[o:o + n] = (rs.standard_normal(n) / math.sqrt(fan_in)).astype(np.float32)
         self._arena = torch.from_numpy(host)
@@ -1029,6 +1136,13 @@ class WaveNet(object):
         if self.local_channels and not has_local:
             raise Exception("this model is locally conditioned and the checkpoint is not (it holds no "
                             "local_condition_projection/W)")
+        up = sd.get("local_condition_upsample/W")
+        have = 1 if up is None else (2 * int(np.shape(up)[0])) // max(int(np.shape(up)[1]), 1)
+        if have != self.local_upsample:
+            raise Exception("this checkpoint was trained with local_upsample = %d%s and the model is built with local_upsample "
+                            "= %d%s: construct the model with the checkpoint's value"
+                            % (have, "" if have > 1 else " (it holds no local_condition_upsample/W)", self.local_upsample,
+                               "" if self.local_upsample > 1 else " (no learned upsampling)"))
 
     def load_state_dict(self, sd: Dict[str, np.ndarray]):
         self._check_condition_keys(sd)
@@ -1237,8 +1351,17 @@ class WaveNet(object):
             raise Exception("local= must be float32 of shape (%d, %d, frames), got %s %s"
                             % (B, self.local_channels, f.dtype, tuple(f.shape)))
         worst = phase if tab is None else self.local_hop - 1
+        if self.local_upsample > 1:
+            U, fine = self.local_upsample, self.local_fine_hop
+            need = coarse_frames_needed(T, self.local_hop, U, None if tab is not None else phase, self.local_interp)
+            if f.shape[2] < need:
+                c0, ph = (U - 1, fine - 1) if tab is not None else divmod(phase, fine)
+                raise Exception("local= holds %d feature columns at hop %d, but %d positions at phase %d read %d fine columns at "
+                                "hop %d from fine column %d on (local_upsample = %d), which takes %d%s"
+                                % (f.shape[2], self.local_hop, T, worst, frames_needed(T, fine, ph, self.local_interp), fine, c0,
+                                   U, need, "" if tab is None else " (a phase per clip is sized for the worst phase)"))
         need = frames_needed(T, self.local_hop, worst, self.local_interp)
-        if f.shape[2] < need:
+        if self.local_upsample == 1 and f.shape[2] < need:
             raise Exception("local= holds %d feature columns, but %d positions at hop %d and phase %d read %d%s%s"
                             % (f.shape[2], T, self.local_hop, worst, need,
                                " (linear interpolation reads the column after the last position's own)"
@@ -1256,16 +1379,67 @@ class WaveNet(object):
         blk = _LocalFn.apply(feats, self.local_condition_projection.W, self)
         return blk if glob is None else blk + glob.unsqueeze(1)
 
+    def _upsample(self, feats):
+        """(B, F, n) coarse features on the device -> the learned layer's (B, (n - 1) U, F) fine sequence, time-major."""
+        _need_gpu(feats)
+        return _UpsampleFn.apply(feats, self.local_condition_upsample.W, self)
+
+    def upsampled_features(self, features):
+        """The fine features of a batch, on the device: (B, F, n) float32 features at hop ``local_hop`` -> (B, F, (n - 1) U) at
+        hop ``local_hop / local_upsample``, fine column m anchored at position m H' of coarse column 0's frame -- a view of the
+        learned layer's time-major output, what the projection then reads (cut at fine column phase // H').  An autograd node
+        when grad is enabled.  With ``local_upsample`` = 1 there is no layer: the features come back as they are."""
+        if not self.local_channels:
+            raise Exception("upsampled_features: this model has no local conditioning (local_channels = 0)")
+        f = features if isinstance(features, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(features, dtype=np.float32)))
+        f = self.to_variable(f)
+        if f.dim() != 3 or f.shape[1] != self.local_channels or f.dtype != torch.float32:
+            raise Exception("upsampled_features: features must be float32 of shape (clips, %d, frames), got %s %s"
+                            % (self.local_channels, f.dtype, tuple(f.shape)))
+        if self.local_upsample == 1:
+            _need_gpu(f)
+            return f
+        if f.shape[2] < 2:
+            raise Exception("upsampled_features: the layer reads pairs of neighbouring columns, got %d column" % f.shape[2])
+        return self._upsample(f).permute(0, 2, 1)
+
+    def _stack_features(self, feats, phase, T):
+        """What the projection and the stack take, from what ``_local_features`` checked: (features (B, F, n'), hop, phase).
+        Without a learned layer: the arguments and ``local_hop``.  With one (``local_upsample`` = U, H' = H / U): the first
+        ``coarse_frames_needed`` columns go through the layer, and the fine sequence is cut where the window starts -- an int
+        phase: at fine column phase // H', the stack running at phase % H'; a phase per clip: clip b's
+        ``frames_needed(T, H', H' - 1)`` columns are gathered from fine column tab[b] // H' on (torch ops on the device
+        buffer: capturable) and the stack gets the derived ``LocalPhases(tab % H', H')``."""
+        if self.local_upsample == 1:
+            return feats, self.local_hop, phase
+        U, fine = self.local_upsample, self.local_fine_hop
+        per_clip = isinstance(phase, LocalPhases)
+        need = coarse_frames_needed(T, self.local_hop, U, None if per_clip else phase, self.local_interp)
+        y = self._upsample(feats[:, :, :need])                                   # (B, (need - 1) U, F)
+        if not per_clip:
+            c0, ph = divmod(int(phase), fine)
+            nf = frames_needed(T, fine, ph, self.local_interp)
+            return y[:, c0:c0 + nf].permute(0, 2, 1), fine, ph
+        nf = frames_needed(T, fine, fine - 1, self.local_interp)
+        c0 = torch.div(phase.tab, fine, rounding_mode="floor").to(torch.int64)
+        idx = c0.unsqueeze(1) + torch.arange(nf, device=y.device, dtype=torch.int64).unsqueeze(0)        # (B, nf)
+        y = torch.gather(y, 1, idx.unsqueeze(2).expand(-1, -1, y.shape[2]))
+        return y.permute(0, 2, 1), fine, LocalPhases(torch.remainder(phase.tab, fine).to(torch.int32).contiguous(), fine)
+
     def local_biases(self, features, phase: int = 0):
         """(n, sum 2 cd) float32 on the device: the table of one utterance -- row f holds, for flat layer l, its cd filter
         biases at offset sum_{i<l} 2 cd_i and then its cd gate biases, the values V h[:, f] that feature column f adds to
         every layer.  ``features``: (F, n).  Computed on the device by the node the forward uses; ``phase`` is only checked
-        (it travels next to the table)."""
+        (it travels next to the table).  With a learned upsampling layer (``local_upsample`` = U > 1) the table holds one row
+        per FINE column -- ((n - 1) U, sum 2 cd), row m the values V y[:, m] of ``upsampled_features`` -- and ``features`` needs
+        at least ``coarse_frames_needed(1, H, U, phase, interp)`` columns."""
         f = np.asarray(features, dtype=np.float32) if not isinstance(features, torch.Tensor) else features
         if len(f.shape) != 2:
             raise Exception("local_biases: features must be (F, frames), got %s" % (tuple(f.shape),))
         feats, _ = self._local_features(f[None], 1, 1, phase)
         with torch.no_grad():
+            if self.local_upsample > 1:
+                feats = self._upsample(feats).permute(0, 2, 1)
             return self._local_block(feats)[0].contiguous()
 
     def condition_biases(self, class_id: int):
@@ -1553,15 +1727,18 @@ class WaveNet(object):
         locally conditioned model (and only for one); see ``local_alignment``.  ``local_phase`` is an int (every clip at that
         phase) or one phase per clip -- a 1-D sequence, numpy array or integer tensor, each entry in [0, local_hop): the
         phases then travel in device memory (``WnStackDesc.bias_phase_tab``) and every clip needs
-        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase."""
+        ``frames_needed(T, H, H - 1, interp)`` columns, whatever its phase.  With a learned upsampling layer
+        (``local_upsample`` = U > 1) ``local`` and ``local_phase`` mean the same -- coarse columns at hop H, phases in [0, H) --
+        and the call needs ``coarse_frames_needed(T, H, U, phase, interp)`` columns (``phase=None`` for a phase per clip)."""
         x = self.to_variable(x_batch)
         _need_gpu(x)
         cond = self._condition_block(condition, int(x.shape[0]))
         feats, phase = self._local_features(local, int(x.shape[0]), int(x.shape[3]), local_phase)
         rows = None
         if feats is not None:
+            feats, hop, phase = self._stack_features(feats, phase, int(x.shape[3]))
             cond = self._local_block(feats, cond).contiguous()
-            rows = GateBiasRows(self, cond, self.local_hop, phase, LOCAL_INTERP.index(self.local_interp))
+            rows = GateBiasRows(self, cond, hop, phase, LOCAL_INTERP.index(self.local_interp))
         elif cond is not None:
             cond = cond.contiguous()
             rows = GateBiasRows(self, cond)
