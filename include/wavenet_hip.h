@@ -414,6 +414,30 @@ int wn_btc_to_nchw(const float* src, float* dst, int B, int C, int T, void* stre
  * template instantiations of its own, so without the flag every call does what it did before the flag existed, and out_tokens
  * is write-only again. */
 #define WN_DECODER_FORCED_TOKENS 512u
+/* WnDecoderDesc.flags, on every shape: the frame table is a RING of R = n_frames rows in the caller's memory, read in place --
+ * streaming synthesis: the caller keeps writing rows ahead of the decoder and runs the handle in pieces.
+ *   - By reference.  frame_bias is NOT copied: the handle keeps the pointer, frame_stride and n_frames, and the kernels read the
+ *     caller's memory when they run.  The caller keeps it alive until the handle is destroyed or updated with another ring, and
+ *     writes rows only in the stream it runs the handle on: stream order is the only synchronisation.
+ *   - Ring addressing.  Frame J (J = p / frame_hop, p = frame_phase + the steps run since the create / update call, as for the
+ *     flat table) lives in row J mod R; with frame_interp = 1 the second row is (J + 1) mod R.  Everything else is the flat
+ *     table's rule, bit for bit: (static bias or 0) + y, the interpolation, alpha, the layout of a row.
+ *   - Which frames ARE in the ring is the caller's business: the flat table's refusal for reading past row n_frames - 1 does not
+ *     apply, and no call can tell a row that was not refilled in time from one that was.  What is refused (WN_EARG, before any
+ *     device work, the handle's state left alone) is a run of n steps that reads more than R frames -- frames p0 / hop ...
+ *     (p0 + n - 1) / hop, one more with frame_interp = 1: a launch cannot be refilled while it runs.
+ *   - The flag without frame_bias is WN_EARG.  The kernels read a row one float per lane, so frame_bias must be a multiple of
+ *     4 bytes (sizeof(float)); frame_stride counts floats, and any stride >= the row width keeps every row so aligned.  A
+ *     pointer that is not is WN_EARG at create / update, naming the 4 bytes.
+ *   - A handle's form is fixed at create: wn_decoder_update_weights with the bit flipped is WN_EARG; with the bit kept it may
+ *     bring another ring, R, phase or step limit, and restarts the step count as ever.
+ *   - wn_decoder_run_batch: the handles of a launch agree on the flag (WN_EARG naming the first utterance that differs from
+ *     utterance 0); pointer, R, position and phase are per utterance.
+ * The bit combines freely with WN_DECODER_GATE_ROWS, WN_DECODER_TRACE_CHOSEN, WN_DECODER_FORCED_TOKENS and
+ * WN_DECODER_ONE_WORKGROUP and never changes which decoder a description selects.  In the kernels the wrap is a wave-uniform
+ * compare on the walked row (specialised decoder: wave 1 of the chain workgroup, inside the gate-row instantiations) or
+ * instantiations of its own (any-shape decoder); a handle created without the flag does exactly what it did before. */
+#define WN_DECODER_FRAME_RING 1024u
 typedef struct WnDecoderDesc {
     int Q, fw_causal, n_causal, fw, n_blocks, n_layers;  /* n_layers per block; dilation fw^l */
     int Cr, Cs, n_head;
@@ -435,6 +459,8 @@ typedef struct WnDecoderDesc {
                                          emitted token's probability, on every shape;
                                          WN_DECODER_FORCED_TOKENS (see the define): out_tokens is read before it is written, and
                                          a step whose entry is a token emits it instead of drawing, on every shape;
+                                         WN_DECODER_FRAME_RING (see the define): frame_bias is a ring of n_frames rows read in
+                                         place, not a table the handle copies, on every shape;
                                          WN_DECODER_ONE_WORKGROUP: wn_decoder_run of that kernel on ONE workgroup instead of
                                          nine (the chain | eight workgroups of skip rows and their share of the logits):
                                          same products, another summation order for the skip rows and the logits --

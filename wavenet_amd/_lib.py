@@ -225,7 +225,8 @@ WN_DECODER_ONE_WORKGROUP = 64          # WnDecoderDesc.flags: wn_decoder_run on 
 WN_DECODER_GATE_ROWS = 128             # WnDecoderDesc.flags: gate biases / a frame table do not deselect the specialised 32/256-channel decoder
 WN_DECODER_TRACE_CHOSEN = 256          # WnDecoderDesc.flags: prob_trace is one float per step -- the emitted token's probability -- not a row of Q
 WN_DECODER_FORCED_TOKENS = 512         # WnDecoderDesc.flags: out_tokens is read before it is written -- an entry in [0, Q) is emitted as given, anything else draws
-WN_DECODER_BATCH_MAX_ANY = 1024     # wn_decoder_run_batch on any-shape handles: utterances per launch (wn_decoder_batch_max(): the nine-workgroup form's)
+WN_DECODER_FRAME_RING = 1024           # WnDecoderDesc.flags: frame_bias is a ring of n_frames rows in the caller's memory, read in place (streaming)
+WN_DECODER_BATCH_MAX_ANY = 1024    # wn_decoder_run_batch on any-shape handles: utterances per launch (wn_decoder_batch_max(): the nine-workgroup form's)
 
 
 def default_exec_flags() -> int:

@@ -26,7 +26,9 @@ namespace wn {
 static constexpr int kDecThreads = 512;
 
 // local conditioning: the handle's own compact copy of the table -- n rows (room for cap) of `row` floats --, hop, phase, mode
-struct FrameTable { float* tab; int cap, n, hop, phase, row, interp; };
+// A WN_DECODER_FRAME_RING handle copies nothing: `ring` is the caller's memory, n its capacity R and row the caller's stride (tab
+// stays NULL).
+struct FrameTable { float* tab; int cap, n, hop, phase, row, interp; const float* ring; };
 
 struct Decoder {
     DecMeta meta{};
@@ -52,6 +54,8 @@ struct Decoder {
                                   // float per step, the drawn token's probability, not a row of Q
     bool forced = false;          // created with WN_DECODER_FORCED_TOKENS (fixed at create, on every shape): a run reads out_tokens[i] before
                                   // it writes it, and a step whose entry is a token of [0, Q) emits that token instead of drawing
+    bool frame_ring = false;      // created with WN_DECODER_FRAME_RING (fixed at create, on every shape): the frame table is a ring in the
+                                  // caller's memory, read in place (FrameTable.ring)
     bool ran_multi = false;       // a nine-workgroup run has been launched (its error entry is meaningful)
     SampleCtl ctl;                // wn_decoder_set_sampling: temperature / top-k / top-p of wn_decoder_run (off at create)
     // wn_decoder_run_batch on any-shape handles, as handle 0 of the call: the per-utterance table (DecAnyUtt) in device
@@ -172,7 +176,9 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
 // are the same for every thread of the workgroup.
 // FORCED (WN_DECODER_FORCED_TOKENS handles): a step may emit the token out_tokens[it] holds instead of drawing; without it the
 // loop is what it was
-template <bool LERP, bool FORCED>         // LERP: the table is interpolated (DecFrames.interp); without it the loop is what it was
+// RING (WN_DECODER_FRAME_RING handles): the table is a ring of fr.ring rows -- the step's row is a walked slot that wraps, not a
+// quotient per step; without it the loop is what it was
+template <bool LERP, bool FORCED, bool RING>         // LERP: the table is interpolated (DecFrames.interp); without it the loop is what it was
 __device__ __forceinline__ void decode_steps(
     const DecMeta& M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
@@ -191,6 +197,13 @@ __device__ __forceinline__ void decode_steps(
     __shared__ int s_token;
     if (tid == 0) s_token = first_token;
     __syncthreads();
+    // RING: slot = (pos0 / hop) mod ring and p % hop of the first step once, then one increment per step (workgroup-uniform)
+    int rslot = 0, rrem = 0;
+    if (RING && fr.tab) {
+        const long long j = fr.pos0 / fr.hop;
+        rslot = (int)(j % fr.ring);
+        rrem = (int)(fr.pos0 - j * fr.hop);
+    }
 
     for (int it = 0; it < nsteps; ++it) {
         const long long n = n0 + it;
@@ -240,10 +253,16 @@ __device__ __forceinline__ void decode_steps(
         }
         for (int o = tid; o < M.Cs; o += NT) skip[o] = 0.f;
         // the step's frame row, computed once per step (workgroup-uniform); layer j's 2 cd values lie at the running offset
-        const float* __restrict__ frow = fr.tab ? fr.tab + ((fr.pos0 + it) / fr.hop) * (long long)fr.row : nullptr;
-        // linear interpolation: the next row and its weight, likewise once per step
-        const float* __restrict__ fnext = LERP && frow ? frow + fr.row : nullptr;
-        const float falpha = fnext ? __fdiv_rn((float)(int)((fr.pos0 + it) % fr.hop), (float)fr.hop) : 0.f;
+        const float* __restrict__ frow = !fr.tab ? nullptr
+                                         : RING ? fr.tab + rslot * (long long)fr.row
+                                                : fr.tab + ((fr.pos0 + it) / fr.hop) * (long long)fr.row;
+        // linear interpolation: the next row and its weight, likewise once per step (ring: the row after slot ring - 1 is slot 0)
+        const float* __restrict__ fnext = !(LERP && frow) ? nullptr : RING && rslot + 1 == fr.ring ? fr.tab : frow + fr.row;
+        const float falpha = fnext ? __fdiv_rn(RING ? (float)rrem : (float)(int)((fr.pos0 + it) % fr.hop), (float)fr.hop) : 0.f;
+        if (RING && ++rrem == fr.hop) {          // the walk, for the next step
+            rrem = 0;
+            if (++rslot == fr.ring) rslot = 0;
+        }
         // ---- residual layers ------------------------------------------------------------------
         for (int j = 0; j < M.nlayers; ++j) {
             const DecLayer L = layers[j];
@@ -351,13 +370,13 @@ __device__ __forceinline__ void decode_steps(
     }
 }
 
-template <bool LERP, bool FORCED>
+template <bool LERP, bool FORCED, bool RING>
 __global__ __launch_bounds__(kDecThreads) void k_decode(
     DecMeta M, const DecCausal* __restrict__ causal, const DecLayer* __restrict__ layers,
     const DecHead* __restrict__ heads, float* __restrict__ arena, int* __restrict__ tok_ring, long long n0,
     int nsteps, int first_token, const double* __restrict__ uniforms, int32_t* __restrict__ out_tokens,
     float* __restrict__ prob_out, int prob_stride, int apply_softmax, int do_sample, const SampleCtl sc, const DecFrames fr) {
-    decode_steps<LERP, FORCED>(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
+    decode_steps<LERP, FORCED, RING>(M, causal, layers, heads, arena, tok_ring, n0, nsteps, first_token, uniforms, out_tokens, prob_out, prob_stride,
                  apply_softmax, do_sample, sc, fr);
 }
 
@@ -365,12 +384,12 @@ __global__ __launch_bounds__(kDecThreads) void k_decode(
 // never wait for each other, so any number of them may be queued behind the CUs -- and each runs its utterance's own step
 // count (DecAnyUtt.nsteps; the launch has no count of its own): an utterance that ends early simply ends.  prob_stride is the
 // launch's (M.Q, or kProbChosen when the handles were created with WN_DECODER_TRACE_CHOSEN: they must agree), and so is FORCED
-// (the handles agree on WN_DECODER_FORCED_TOKENS).
-template <bool LERP, bool FORCED>
+// (the handles agree on WN_DECODER_FORCED_TOKENS), and RING (they agree on WN_DECODER_FRAME_RING).
+template <bool LERP, bool FORCED, bool RING>
 __global__ __launch_bounds__(kDecThreads) void k_decode_batch(DecMeta M, const DecAnyUtt* __restrict__ tab, int n_utt, int prob_stride) {
     if ((int)blockIdx.x >= n_utt) return;
     const DecAnyUtt q = tab[blockIdx.x];
-    decode_steps<LERP, FORCED>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
+    decode_steps<LERP, FORCED, RING>(M, q.causal, q.layers, q.heads, q.arena, q.tok_ring, q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens,
                  q.prob_out, prob_stride, 1, 1, q.sc, q.fr);
 }
 
@@ -399,6 +418,7 @@ static DecFrames launch_frames(const Decoder* D) {
     const FrameTable& F = D->frames;
     DecFrames f{};
     if (F.n > 0) { f.tab = F.tab; f.hop = F.hop; f.row = F.row; f.pos0 = F.phase + D->since_set; f.interp = F.interp; }
+    if (F.n > 0 && D->frame_ring) { f.tab = F.ring; f.ring = F.n; }       // (F.row is the caller's stride)
     return f;
 }
 static bool lerp_table(const Decoder* D) { return D->frames.n > 0 && D->frames.interp != 0; }   // the LERP kernels
@@ -411,6 +431,16 @@ static int row_width(const Decoder* D) {           // floats of one table row: t
 static int check_frames(const char* fn, const Decoder* D, long long n) {
     const FrameTable& F = D->frames;
     if (F.n <= 0) return WN_OK;
+    if (D->frame_ring) {
+        // a ring: which frames it holds is the caller's business; a launch cannot be refilled while it runs, so the frames of
+        // its steps -- the first step's to the last step's, one more under linear interpolation -- must fit the ring at once
+        const long long p0 = F.phase + D->since_set;
+        const long long reads = (p0 + n - 1) / F.hop - p0 / F.hop + 1 + (F.interp ? 1 : 0);
+        WN_CHECK_ARG(reads <= F.n, "%s: %lld more steps read %lld frames of a ring of %d rows (WN_DECODER_FRAME_RING; hop %d, phase %d, "
+                                   "%lld steps run on it%s): a launch cannot be refilled while it runs", fn, n, reads, F.n, F.hop,
+                     F.phase, D->since_set, F.interp ? "; linear interpolation reads the frame after the step's own" : "");
+        return WN_OK;
+    }
     // (linear interpolation: the last step reads row j + 1 as well)
     const long long last = (F.phase + D->since_set + n - 1) / F.hop + (F.interp ? 1 : 0);
     WN_CHECK_ARG(last < F.n, "%s: %lld more steps would read row %lld of a frame table of %d rows (hop %d, phase %d, %lld steps "
@@ -419,6 +449,13 @@ static int check_frames(const char* fn, const Decoder* D, long long n) {
     return WN_OK;
 }
 static int check_frame_desc(const Decoder* D, const WnDecoderDesc* d) {
+    const bool ring = (d->flags & WN_DECODER_FRAME_RING) != 0;
+    WN_CHECK_ARG(!ring || d->frame_bias, "decoder: WN_DECODER_FRAME_RING without frame_bias: the flag makes frame_bias a ring of "
+                                         "n_frames rows read in place");
+    // the kernels read a row one float per lane / thread: 4-byte reads.  frame_stride counts floats, so every row of an aligned
+    // ring is aligned
+    WN_CHECK_ARG(!ring || (uintptr_t)d->frame_bias % sizeof(float) == 0, "decoder: WN_DECODER_FRAME_RING: frame_bias = %p is not a "
+                 "multiple of 4 bytes (sizeof(float)), the alignment the kernels' row reads need", (const void*)d->frame_bias);
     if (!d->frame_bias) return WN_OK;
     const int row = row_width(D);
     WN_CHECK_ARG(d->n_frames > 0 && d->frame_hop > 0, "decoder: a frame table needs n_frames > 0 and frame_hop > 0 (got %d, %d)",
@@ -440,6 +477,11 @@ static int take_frames(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     D->step_limit = d->step_limit;
     FrameTable& F = D->frames;
     if (!d->frame_bias) { F.n = 0; return WN_OK; }
+    if (D->frame_ring) {                  // by reference: the pointer, the stride and R; nothing is copied, nothing launched
+        F.ring = d->frame_bias;
+        F.n = d->n_frames; F.hop = d->frame_hop; F.phase = d->frame_phase; F.row = d->frame_stride; F.interp = d->frame_interp;
+        return WN_OK;
+    }
     const int row = row_width(D);
     if (d->n_frames > F.cap || row != F.row) {
         if (F.tab) { WN_HIP(hipFree(F.tab)); F.tab = nullptr; F.cap = 0; }
@@ -655,6 +697,7 @@ int wn_decoder_create(void** handle, const WnDecoderDesc* d, void* stream) {
     }
     D->trace_chosen = (d->flags & WN_DECODER_TRACE_CHOSEN) != 0;
     D->forced = (d->flags & WN_DECODER_FORCED_TOKENS) != 0;
+    D->frame_ring = (d->flags & WN_DECODER_FRAME_RING) != 0;
     if ((rc = pack_weights(D, d, s))) return rc;
     if ((rc = take_frames(D, d, s))) return rc;
     *handle = built.release();
@@ -694,6 +737,9 @@ int wn_decoder_update_weights(void* handle, const WnDecoderDesc* d, void* stream
     WN_CHECK_ARG(((d->flags & WN_DECODER_FORCED_TOKENS) != 0) == D->forced,
                  "wn_decoder_update_weights: the description %s WN_DECODER_FORCED_TOKENS, the handle was created %s it: a handle's form "
                  "is fixed at create", d->flags & WN_DECODER_FORCED_TOKENS ? "carries" : "lacks", D->forced ? "with" : "without");
+    WN_CHECK_ARG(((d->flags & WN_DECODER_FRAME_RING) != 0) == D->frame_ring,
+                 "wn_decoder_update_weights: the description %s WN_DECODER_FRAME_RING, the handle was created %s it: a handle's form "
+                 "is fixed at create", d->flags & WN_DECODER_FRAME_RING ? "carries" : "lacks", D->frame_ring ? "with" : "without");
     for (int j = 0; D->gate_rows && j < D->meta.nlayers; ++j)
         WN_CHECK_ARG(!(d->bf && d->bf[j]) == !(d->bg && d->bg[j]), "decoder: bf/bg must both be present or absent");
     if ((rc = check_frame_desc(D, d))) return rc;
@@ -755,8 +801,11 @@ static int run_one(const char* fn, Decoder* D, int token, const double* uniforms
         // (k_decode takes the record's members as loose arguments: DESIGN.md, "The library's host side, tidied likewise")
         const DecAnyUtt q = any_utt(D, token, uniforms, out_tokens, prob, n, sc);
         const bool forced = do_sample == kSampleGiven;      // (the kernel itself only asks whether do_sample != 0)
-        const auto kern = forced ? (lerp_table(D) ? k_decode<true, true> : k_decode<false, true>)
-                                 : (lerp_table(D) ? k_decode<true, false> : k_decode<false, false>);
+        const bool ring = q.fr.ring != 0;
+        const auto kern = ring ? (forced ? (lerp_table(D) ? k_decode<true, true, true> : k_decode<false, true, true>)
+                                         : (lerp_table(D) ? k_decode<true, false, true> : k_decode<false, false, true>))
+                               : (forced ? (lerp_table(D) ? k_decode<true, true, false> : k_decode<false, true, false>)
+                                         : (lerp_table(D) ? k_decode<true, false, false> : k_decode<false, false, false>));
         hipLaunchKernelGGL(kern, dim3(1), dim3(kDecThreads), D->lds_bytes, s, D->meta, q.causal, q.layers, q.heads, q.arena, q.tok_ring,
                            q.n0, q.nsteps, q.first_token, q.uniforms, q.out_tokens, q.prob_out, prob_stride, apply_softmax, do_sample,
                            q.sc, q.fr);
@@ -824,8 +873,11 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     }
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
-    const auto kern = D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true> : k_decode_batch<false, true>)       // (the handles agree
-                                 : (lerp_table(D0) ? k_decode_batch<true, false> : k_decode_batch<false, false>);    // on both modes)
+    const bool ring = D0->frame_ring && D0->frames.n > 0;                         // (the handles agree on all three modes)
+    const auto kern = ring ? (D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true, true> : k_decode_batch<false, true, true>)
+                                         : (lerp_table(D0) ? k_decode_batch<true, false, true> : k_decode_batch<false, false, true>))
+                           : (D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true, false> : k_decode_batch<false, true, false>)
+                                         : (lerp_table(D0) ? k_decode_batch<true, false, false> : k_decode_batch<false, false, false>));
     hipLaunchKernelGGL(kern, dim3(n_handles), dim3(kDecThreads), D0->lds_bytes, s, D0->meta, (const DecAnyUtt*)D0->batch_tab,
                        n_handles, trace_stride(D0));
     WN_LAUNCH_CHECK();
@@ -902,6 +954,10 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
         WN_CHECK_ARG(D->forced == D0->forced, "wn_decoder_run_batch: utterance %d was created %s WN_DECODER_FORCED_TOKENS, "
                      "utterance 0 %s it: the handles of a launch agree on the flag", u, D->forced ? "with" : "without",
                      D0->forced ? "with" : "without");
+        // ... and whether the table is a ring (one walk for every workgroup)
+        WN_CHECK_ARG(D->frame_ring == D0->frame_ring, "wn_decoder_run_batch: utterance %d was created %s WN_DECODER_FRAME_RING, "
+                     "utterance 0 %s it: the handles of a launch agree on the flag", u, D->frame_ring ? "with" : "without",
+                     D0->frame_ring ? "with" : "without");
         WN_CHECK_ARG(first_tokens[u] >= 0 && first_tokens[u] < D->meta.Q, "wn_decoder_run_batch: token outside [0,Q)");
         if (int rc = steps_left(D, u, n, any, &nu[u])) return rc;
         const FrameTable &F = D->frames, &F0 = D0->frames;

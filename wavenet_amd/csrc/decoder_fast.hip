@@ -257,11 +257,13 @@ __device__ __forceinline__ void load_gate(GateB& b, const GateStep& g, int l, in
     b.y0 = g.r0 ? g.r0[64 * l + lane] : 0.f;
     b.y1 = g.r1 ? g.r1[64 * l + lane] : 0.f;
 }
-// the step's view of utterance q's rows: `frow` = the table row of this step (walked by the step loop, gate_walk), `rem` = p % hop
-__device__ __forceinline__ GateStep gate_step(const DecUtt& q, const float* frow, int rem, int nlayers, int lane) {
+// the step's view of utterance q's rows: `frow` = the table row of this step (walked by the step loop, gate_walk), `rem` = p % hop,
+// `end` = one past the ring's last row (GateWalk.end; NULL: a flat table)
+__device__ __forceinline__ GateStep gate_step(const DecUtt& q, const float* frow, const float* end, int rem, int nlayers, int lane) {
     GateStep g;
     g.r0 = frow;
     g.r1 = frow && q.fr.interp ? frow + q.fr.row : nullptr;
+    if (end && g.r1 == end) g.r1 = q.fr.tab;           // ring: the row after the ring's last row is row 0 (flat: end is NULL)
     g.alpha = g.r1 ? __fdiv_rn((float)rem, (float)q.fr.hop) : 0.f;
     g.arena = q.arena;
     g.b_lo = lane < nlayers ? q.layers[lane].bfg : -1;
@@ -270,18 +272,26 @@ __device__ __forceinline__ GateStep gate_step(const DecUtt& q, const float* frow
 }
 // The table row of a launch's steps without a division per step: row and remainder of the first step once (pos0 / hop, a 64-bit
 // division), then one increment per step.  Wave-uniform; every thread of the chain workgroup keeps it (scalar registers).
-struct GateWalk { const float* frow; int rem; };
+// A ring (DecFrames.ring, WN_DECODER_FRAME_RING): the walk starts at row j mod ring and returns to the ring's base when it
+// reaches `end`, one past its last row -- one more uniform compare where the row moves on; a flat table has end == NULL, which
+// no row pointer equals.
+struct GateWalk { const float* frow; int rem; const float* end; };
 __device__ __forceinline__ GateWalk gate_walk_open(const DecFrames& fr) {
-    GateWalk w{nullptr, 0};
+    GateWalk w{nullptr, 0, nullptr};
     if (fr.tab) {
         const long long j = fr.pos0 / fr.hop;
-        w.frow = fr.tab + j * (long long)fr.row;
+        w.frow = fr.tab + (fr.ring ? j % fr.ring : j) * (long long)fr.row;
         w.rem = (int)(fr.pos0 - j * fr.hop);
+        if (fr.ring) w.end = fr.tab + (long long)fr.ring * fr.row;
     }
     return w;
 }
 __device__ __forceinline__ void gate_walk_next(GateWalk& w, const DecFrames& fr) {
-    if (w.frow && ++w.rem == fr.hop) { w.rem = 0; w.frow += fr.row; }
+    if (w.frow && ++w.rem == fr.hop) {
+        w.rem = 0;
+        w.frow += fr.row;
+        if (w.frow == w.end) w.frow = fr.tab;
+    }
 }
 // (static bias or 0) + frame value: the any-shape decoder's rule (decode_steps), bias_lerp never contracted -- a table of
 // zeros gives +0, the seed the unconditioned kernels start from
@@ -487,7 +497,7 @@ __device__ __forceinline__ void old_wave(const ChainLds& S, const float* __restr
     GateStep g{};
     load_old(wo[0], P, 0, 4u * lane);
     if (GATE) {
-        g = gate_step(q, gw.frow, gw.rem, nlayers, lane);
+        g = gate_step(q, gw.frow, gw.end, gw.rem, nlayers, lane);
         load_gate(gb[0], g, 0, lane);
     }
     __syncthreads();
@@ -617,7 +627,7 @@ __global__ __launch_bounds__(kFT, 1) void k_decode_fast(const DecUtt q, int nlay
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float hb = chain_prologue(S, q, nlayers, tid);
     const unsigned t4 = 4u * (tid & 127);
-    GateWalk gw{nullptr, 0};
+    GateWalk gw{nullptr, 0, nullptr};
     if (GATE) gw = gate_walk_open(q.fr);
 
     for (int it = 0; it < nsteps; ++it) {
@@ -797,7 +807,7 @@ __device__ __forceinline__ void decode_fast3_body(const int wg, const DecUtt& q,
     const ChainLds S(sm);
     const float hb = chain_prologue(S, q, nlayers, tid);
     bool dead0 = false;                                   // this thread's wait for the logit shares gave up: wait for nothing any more
-    GateWalk gw{nullptr, 0};
+    GateWalk gw{nullptr, 0, nullptr};
     if (GATE) gw = gate_walk_open(q.fr);
 
     for (int it = 0; it < nsteps; ++it) {

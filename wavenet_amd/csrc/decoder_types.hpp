@@ -22,7 +22,9 @@ static constexpr int kProbChosen = 0;
 // filter, no draw, uniforms[it] unused -- and draws as kSampleDraw does otherwise.  One value per launch.  The launchers turn
 // kSampleGiven into the FORCED instantiations of the kernels; a kernel only asks whether its do_sample is 0.
 static constexpr int kSampleDraw = 1, kSampleGiven = 2;
-struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; };
+// ring != 0 (WN_DECODER_FRAME_RING handles): tab is the caller's ring of `ring` rows, `row` floats apart, read in place -- frame j
+// lives in row j mod ring, and row j + 1 of the ring's last row is row 0.  ring == 0: the flat table, addressed as ever.
+struct DecFrames { const float* tab; int hop; int row; long long pos0; int interp; int ring; };
 // One utterance's launch arguments of the specialised decode kernels (decoder_fast.hip): filled from its handle by
 // decoder.hip, passed to the kernels by value (the batched launch passes an array of them)
 struct DecUtt {

@@ -55,6 +55,31 @@ def deal_launches(lengths, limit, longest_first=True):
     return launches if longest_first else [(n, sorted(idx)) for n, idx in launches]
 
 
+StreamFrames = collections.namedtuple("StreamFrames", "steps current reads min_ring")
+
+
+def stream_frames(hop, linear, phase, fed=0, done=0, pull=0):
+    """THE arithmetic of a frame ring (``WN_DECODER_FRAME_RING``, ``DecodeStream``), in one place.  A decoder whose table was set
+    with phase ``phase`` in [0, hop) reads, at its k-th step (k = 0, 1, ...), frame (phase + k) // hop -- and, with ``linear``
+    interpolation, the frame after it.  With frames 0 .. ``fed`` - 1 fed so far and ``done`` steps run:
+
+    * ``steps``: how many more steps the frames fed allow -- max(0, (fed - linear) * hop - phase - done);
+    * ``current``: the frame of the next step, (phase + done) // hop -- every frame before it is consumed, and a ring of R rows
+      may be fed up to frame ``current`` + R - 1 without overwriting a row that is still to be read;
+    * ``reads``: the frames a run of ``pull`` more steps reads at once (0 for ``pull`` = 0) -- the library refuses a run that
+      reads more than R, because a launch cannot be refilled while it runs;
+    * ``min_ring``: the smallest R that takes a run of ``pull`` steps wherever it starts: ceil((pull - 1) / hop) + 1 + linear
+      (0 for ``pull`` = 0)."""
+    hop, lin, phase, fed, done, pull = int(hop), 1 if linear else 0, int(phase), int(fed), int(done), int(pull)
+    if hop < 1 or not 0 <= phase < hop or fed < 0 or done < 0 or pull < 0:
+        raise ValueError("stream_frames: needs hop >= 1, 0 <= phase < hop and non-negative counts, got hop %d, phase %d, fed %d, "
+                         "done %d, pull %d" % (hop, phase, fed, done, pull))
+    p0 = phase + done
+    return StreamFrames(steps=max(0, (fed - lin) * hop - p0), current=p0 // hop,
+                        reads=(p0 + pull - 1) // hop - p0 // hop + 1 + lin if pull else 0,
+                        min_ring=(pull - 1 + hop - 1) // hop + 1 + lin if pull else 0)
+
+
 def _ragged_lengths(n_samples, uniforms):
     """``generate_batch``'s sequence form: (lengths, one 1-D float64 array of uniforms per utterance), every check made and
     every message naming the first offending utterance."""
@@ -192,8 +217,10 @@ class FasterWaveNet(WaveNet):
             self.storage = storage
 
     # -- decoder handle -------------------------------------------------------------------------
-    def _desc(self, cond=None, table=None, step_limit=0, chosen=False, forced=False):
-        """``forced``: ``WN_DECODER_FORCED_TOKENS`` -- a run of the handle reads its token buffer before it writes it and emits
+    def _desc(self, cond=None, table=None, step_limit=0, chosen=False, forced=False, ring=False):
+        """``ring``: ``WN_DECODER_FRAME_RING`` -- ``table``'s rows are a ring the handle reads in place and the caller keeps
+        refilling (``open_stream``), not a table it copies; it selects no other decoder.
+        ``forced``: ``WN_DECODER_FORCED_TOKENS`` -- a run of the handle reads its token buffer before it writes it and emits
         the tokens it finds there instead of drawing (``forced=`` of ``generate``); it selects no other decoder.
         ``chosen``: ``WN_DECODER_TRACE_CHOSEN`` -- the handle's probability trace is the probability of each token it emits,
         one float per step (``return_chosen``); it selects no other decoder and changes no token.
@@ -236,6 +263,8 @@ class FasterWaveNet(WaveNet):
             d.flags |= _lib.WN_DECODER_TRACE_CHOSEN
         if forced:
             d.flags |= _lib.WN_DECODER_FORCED_TOKENS
+        if ring:
+            d.flags |= _lib.WN_DECODER_FRAME_RING
         d.step_limit = int(step_limit)
         if table is not None:
             rows, hop, phase = table
@@ -698,6 +727,30 @@ class FasterWaveNet(WaveNet):
             return (res, ch) if ragged else (out, ch_all)
         return res if ragged else out
 
+    def open_stream(self, utterances=1, initial_tokens=None, condition=None, local=None, local_phase=0, temperature=1.0,
+                    top_k=0, top_p=1.0, return_chosen: bool = False, ring_frames=None, max_pull=4096):
+        """Streaming synthesis: a ``DecodeStream`` over ``utterances`` utterances -- features go in by ``push``, samples come out
+        by ``pull``, in pieces of any size, and the concatenation of everything pulled equals row for row, bit for bit, what ONE
+        ``generate_batch`` call with the same arguments and a table of the same rows returns (tokens, and ``chosen`` with
+        ``return_chosen``, element 0 from the prefill row included).
+
+        The call runs the prefill ``generate_batch`` runs -- the same rules per utterance for ``initial_tokens``, ``condition``,
+        ``local`` / ``local_phase`` and the controls, the same refusals and messages -- and creates one decoder handle per
+        utterance, which the stream keeps until ``close()``.  For a locally conditioned model ``local=`` is required: one
+        (F, n) array or one per utterance, covering at least the window; columns beyond the window go into the ring.  Every
+        utterance owns a ring of ``ring_frames`` = R rows on the device that its handle reads in place
+        (``WN_DECODER_FRAME_RING``); R defaults to the smallest ring that serves pulls of ``max_pull`` samples with one pull's
+        worth of rows fed ahead, and an R too small for ``max_pull`` raises, naming the minimum (``stream_frames``).
+        Unconditioned and globally conditioned models take the same interface without a ring: ``pull`` only.  Given samples
+        (``forced=``) are not part of a stream.
+
+        Rows fed with ``push_rows`` are the table's rows by construction.  Rows made by ``push(features)`` come from a projection
+        GEMM over fewer columns per call than the whole utterance's: in the default fp16 x 2 arithmetic the per-tile scales
+        depend on a row's tile mates, so such rows agree with the whole-utterance rows to that GEMM's product error only, and a
+        token can differ at a near-tie of the cumulative distribution -- the caveat of ``WN_DECODER_ONE_WORKGROUP``."""
+        return DecodeStream(self, utterances, initial_tokens, condition, local, local_phase, temperature, top_k, top_p,
+                            return_chosen, ring_frames, max_pull)
+
     def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase,
                     forced=None):
         """``generate_batch``'s arguments -> (one ``_Utterance`` per utterance, {group: (features on the device or None,
@@ -810,3 +863,321 @@ class FasterWaveNet(WaveNet):
             toks, ch = [t for t, _ in rows], [c for _, c in rows]
             return (toks, ch) if ragged else (torch.stack(toks), torch.stack(ch))
         return rows if ragged else torch.stack(rows)
+
+
+class StreamBook(object):
+    """The host's books of a ``DecodeStream``: per utterance the frames fed and the decoder steps run, and every refusal of
+    ``push`` and ``pull`` -- plain integers, no device (``stream_frames`` is the arithmetic).  ``ring``: R, or 0 for a stream
+    without a ring (a model without local conditioning); ``phases``: the decoders' ``frame_phase`` per utterance; ``two_steps``:
+    the launches are the nine-workgroup decoder's, which runs two steps at least."""
+
+    def __init__(self, phases, hop=0, linear=False, ring=0, two_steps=False):
+        self.phases, self.hop, self.linear, self.ring, self.two_steps = [int(p) for p in phases], int(hop), bool(linear), int(ring), bool(two_steps)
+        self.n = len(self.phases)
+        self.fed, self.done, self.started = [0] * self.n, [0] * self.n, False
+
+    def frames(self, u, pull=0):
+        return stream_frames(self.hop, self.linear, self.phases[u], self.fed[u], self.done[u], pull)
+
+    def available(self):
+        """Samples that can be pulled per utterance from the rows present (None: no ring, no bound): the steps the frames fed
+        allow, and before the first pull one more -- the prefill's sample, which takes no step."""
+        if not self.ring:
+            return [None] * self.n
+        return [self.frames(u).steps + (0 if self.started else 1) for u in range(self.n)]
+
+    def check_push(self, counts):
+        """``counts[u]`` more frames for utterance u: refused when they would overwrite a row that is still to be read."""
+        if not self.ring:
+            raise Exception("push: this stream has no ring (the model has no local conditioning): pull only")
+        if len(counts) != self.n:
+            raise Exception("push: %d arrays for %d utterances" % (len(counts), self.n))
+        for u, k in enumerate(counts):
+            cur = self.frames(u).current
+            if self.fed[u] + int(k) > cur + self.ring:
+                raise Exception("push: utterance %d: %d more rows on top of the %d fed would overwrite a row not yet consumed: the "
+                                "ring holds %d rows and the decoder has consumed %d (pull first, or open the stream with a larger "
+                                "ring_frames)" % (u, int(k), self.fed[u], self.ring, cur))
+
+    def pushed(self, counts):
+        for u, k in enumerate(counts):
+            self.fed[u] += int(k)
+
+    def steps_of(self, n):
+        """A pull of ``n`` samples runs n decoder steps -- n - 1 when it is the first: its element 0 is the prefill's."""
+        return int(n) - (0 if self.started else 1)
+
+    def check_pull(self, n):
+        n = int(n)
+        if n < 1:
+            raise Exception("pull: n must be positive, got %d" % n)
+        steps = self.steps_of(n)
+        if self.two_steps and steps == 1:
+            raise Exception("pull: %d sample%s here is ONE decoder step, and the nine-workgroup decoder of this model's shape runs two "
+                            "at least (n >= 2 per launch): pull %s" % (n, "" if n == 1 else "s (the first is the prefill's)",
+                                                                      "1, or 3 and more" if not self.started else "2 and more"))
+        for u in range(self.n if self.ring else 0):
+            f = self.frames(u, steps)
+            if steps > f.steps:
+                raise Exception("pull: utterance %d: %d samples asked for, the rows present allow %d (%d frames fed, %d steps run, "
+                                "hop %d, phase %d%s): push more first"
+                                % (u, n, f.steps + (0 if self.started else 1), self.fed[u], self.done[u], self.hop, self.phases[u],
+                                   "; linear interpolation reads the frame after a step's own" if self.linear else ""))
+            if f.reads > self.ring:
+                raise Exception("pull: utterance %d: %d samples read %d frames at once, the ring holds %d: pull less, or open the "
+                                "stream with a larger ring_frames" % (u, n, f.reads, self.ring))
+        return steps
+
+    def pulled(self, steps):
+        self.started = True
+        for u in range(self.n):
+            self.done[u] += int(steps)
+
+
+class DecodeStream(object):
+    """What ``FasterWaveNet.open_stream`` returns (see there): ``push`` / ``push_rows`` feed frames, ``available`` says how many
+    samples they allow, ``pull`` draws them, ``close`` destroys the handles and then drops the rings.  Also a context manager.
+    The stream holds the weights as they were when it was opened."""
+
+    def __init__(self, net, utterances, initial_tokens, condition, local, local_phase, temperature, top_k, top_p, return_chosen,
+                 ring_frames, max_pull):
+        self.net, self._hs, self._rings, self.closed = net, [], [], False
+        N = int(utterances)
+        if N < 1:
+            raise Exception("open_stream: utterances must be positive, got %d" % N)
+        # generate_batch's own plan over one sample per utterance: its rules, refusals and messages (the features must cover
+        # the window), and the groups that share a prefill
+        recs, feats = net._batch_plan(1, np.zeros((N, 1)), initial_tokens, temperature, top_k, top_p, condition, local, local_phase)
+        self._recs, self.return_chosen = recs, bool(return_chosen)
+        flags = _lib.default_exec_flags() if net.exec_flags is None else int(net.exec_flags)
+        nine = net._nine_workgroup_shape(flags)
+        self._nine, self._one_wg = nine, bool(nine and flags & _lib.WN_DECODER_ONE_WORKGROUP)
+        self.max_pull = int(max_pull)
+        if self.max_pull < 1:
+            raise Exception("open_stream: max_pull must be positive, got %d" % self.max_pull)
+        hop, linear, R = 0, False, 0
+        if net.local_channels:
+            hop, linear = net.local_fine_hop, net.local_interp == "linear"
+            least = stream_frames(hop, linear, 0, pull=self.max_pull).min_ring
+            R = least + (self.max_pull + hop - 1) // hop if ring_frames is None else int(ring_frames)
+            if R < least:
+                raise Exception("open_stream: ring_frames = %d is too small for max_pull = %d: a pull of %d samples at hop %d reads up "
+                                "to %d frames at once%s, the minimum" % (R, self.max_pull, self.max_pull, hop, least,
+                                                                          " (linear interpolation: one more)" if linear else ""))
+        elif ring_frames is not None:
+            raise Exception("open_stream: ring_frames= was given, but this model has no local conditioning: its streams have no ring")
+        W = [len(r.window) for r in recs]
+        starts = [divmod(r.phase + W[i], hop) if R else (0, 0) for i, r in enumerate(recs)]      # (first frame of the ring, frame_phase)
+        self.book = StreamBook([ph for _, ph in starts], hop, linear, R, nine and not self._one_wg)
+        self.ring_frames = R
+        lib, dev = _lib.lib(), net.device
+        # ---- device work from here on -----------------------------------------------------------------------------------------
+        first_rows_of = {}
+        if R:
+            # the rows the features given here make -- the table generate_batch would build --, from the decoder's first frame on
+            rows_of = {g: net.local_biases(feats[g][0][0], feats[g][1]) for g in sorted({r.group for r in recs}, key=self._group_key)}
+            width = int(next(iter(rows_of.values())).shape[1])
+            self._last_col = [feats[r.group][0][0][:, -1:].clone() for r in recs]      # the learned layer reads neighbouring pairs
+            for i, r in enumerate(recs):
+                self._rings.append(torch.zeros((R, width), device=dev, dtype=torch.float32))
+            head = [rows_of[r.group][starts[i][0]:] for i, r in enumerate(recs)]
+            self.book.check_push([int(h.shape[0]) for h in head])
+        biases = {c: net.condition_biases(c) for c in sorted({r.class_id for r in recs})} if net.condition_classes else {None: None}
+        for i, r in enumerate(recs):
+            d, _keep = net._desc(biases[r.class_id], (self._rings[i], hop, starts[i][1]) if R else None, 0, self.return_chosen,
+                                 ring=bool(R))
+            h = C.c_void_p()
+            check(lib.wn_decoder_create(C.byref(h), C.byref(d), stream_ptr()), "wn_decoder_create")
+            self._hs.append(h)
+            check(lib.wn_decoder_set_sampling(h, r.temperature, r.top_k, r.top_p), "wn_decoder_set_sampling")
+        if R:
+            self._write(head)
+        net.prev_causal_outputs = None
+        for g in sorted({r.group for r in recs}, key=self._group_key):
+            mine = [i for i in range(N) if recs[i].group == g]
+            r = recs[mine[0]]
+            tok = torch.as_tensor(r.window.reshape(1, -1)).to(dev)
+            p0, sum_skip = net._seed(tok, r.class_id, feats[g][0], r.phase, [self._hs[i] for i in mine])
+            for t in sorted({recs[i].temperature for i in mine}):
+                first_rows_of[g + (t,)] = net._first_row(sum_skip, p0, t)
+        self._first_rows = [first_rows_of[r.group + (r.temperature,)] for r in recs]
+        self._last = None                  # the newest token of every utterance, on the host
+
+    @staticmethod
+    def _group_key(g):
+        return (g[0], -1 if g[1] is None else g[1], g[2], g[3])
+
+    # -- feeding ------------------------------------------------------------------------------------------------------------------
+    def _write(self, rows):
+        """rows[u] (k_u, width) on the device -> ring slots (fed + i) mod R of utterance u, in stream order; the books follow."""
+        R = self.ring_frames
+        for u, x in enumerate(rows):
+            k, at = int(x.shape[0]), self.book.fed[u] % R
+            first = min(k, R - at)
+            if first:
+                self._rings[u][at:at + first].copy_(x[:first])
+            if k > first:
+                self._rings[u][:k - first].copy_(x[first:])
+        self.book.pushed([int(x.shape[0]) for x in rows])
+
+    def _per_utterance(self, what, x, ndim):
+        per = list(x) if isinstance(x, (list, tuple)) else [x]
+        if not isinstance(x, (list, tuple)) and self.book.n != 1:
+            raise Exception("%s: one array serves a stream of one utterance; this one has %d: pass a list of one per utterance"
+                            % (what, self.book.n))
+        if len(per) != self.book.n:
+            raise Exception("%s: %d arrays for %d utterances" % (what, len(per), self.book.n))
+        out = []
+        for u, a in enumerate(per):
+            a = a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32)
+            if len(a.shape) != ndim:
+                raise Exception("%s: utterance %d: a %d-D array is needed, got shape %s" % (what, u, ndim, tuple(a.shape)))
+            out.append(a)
+        return out
+
+    def push_rows(self, rows):
+        """Projected fine rows, what ``net.local_biases`` returns: (k, row width) for a stream of one utterance, else a list of
+        one array per utterance; k may differ between utterances and may be 0.  They become frames fed .. fed + k - 1 of their
+        utterance, written to ring slots J mod R.  A push that would overwrite a row not yet consumed raises before any device
+        work, naming the utterance and both counts."""
+        self._open()
+        per = self._per_utterance("push_rows", rows, 2)
+        self.book.check_push([int(a.shape[0]) for a in per])      # (also: a stream without a ring takes no rows)
+        width = int(self._rings[0].shape[1])
+        for u, a in enumerate(per):
+            if int(a.shape[1]) != width:
+                raise Exception("push_rows: utterance %d: rows of %d floats, the model's rows hold %d (sum of 2 cd over the layers)"
+                                % (u, int(a.shape[1]), width))
+        dev = self.net.device
+        self._write([(a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, torch.float32) for a in per])
+
+    def push(self, features):
+        """The next coarse feature columns: (F, k) for a stream of one utterance, else a list of one array per utterance; k may
+        differ between utterances and may be 0.  They go through the learned upsampling layer when ``local_upsample`` > 1 (the
+        stream keeps every utterance's last coarse column: the layer reads neighbouring pairs, so k columns make k U fine ones)
+        and through the projection -- the path of ``net.local_biases`` --, and the rows are fed as ``push_rows`` feeds them."""
+        self._open()
+        net = self.net
+        per = self._per_utterance("push", features, 2)
+        for u, a in enumerate(per):
+            if self.book.ring and int(a.shape[0]) != net.local_channels:
+                raise Exception("push: utterance %d: features of %d channels, the model takes %d" % (u, int(a.shape[0]), net.local_channels))
+        U = net.local_upsample if self.book.ring else 1
+        self.book.check_push([int(a.shape[1]) * U for a in per])
+        rows, dev = [], net.device
+        width = int(self._rings[0].shape[1])
+        made = {}                                  # utterances given the same array (behind the same last column) share a projection
+        for u, a in enumerate(per):
+            if int(a.shape[1]) == 0:
+                rows.append(torch.empty((0, width), device=dev, dtype=torch.float32))
+                continue
+            key = (id(a), id(self._last_col[u]) if U > 1 else None)
+            if key not in made:
+                x = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev, torch.float32)
+                # net.local_biases' own path, without its check that the columns cover a window: these are columns in the middle
+                with torch.no_grad():
+                    f = (torch.cat([self._last_col[u], x], dim=1) if U > 1 else x)[None]
+                    if U > 1:
+                        f = net._upsample(f).permute(0, 2, 1)
+                    made[key] = (net._local_block(f)[0].contiguous(), x[:, -1:].clone())
+            rows.append(made[key][0])
+            self._last_col[u] = made[key][1]
+        self._write(rows)
+
+    def available(self):
+        """Per utterance: how many samples can be pulled from the rows present (``stream_frames``; linear interpolation needs
+        the row after a step's own).  None per utterance on a stream without a ring."""
+        return self.book.available()
+
+    # -- drawing ------------------------------------------------------------------------------------------------------------------
+    def pull(self, n, uniforms):
+        """``n`` more samples of every utterance: (utterances, n) int32 on the device -- with ``return_chosen`` ``(tokens,
+        chosen)``, chosen float32 of the same shape.  ``uniforms``: (utterances, n) float64, one per emitted sample, as in
+        ``generate_batch``.  Raises before any device work, naming the utterance, when n exceeds what ``available()`` allows.
+        One utterance runs ``wn_decoder_run``, several ``wn_decoder_run_batch`` -- over several launches when there are more
+        than a launch takes (``deal_launches``).  The nine-workgroup decoder (config 4's shape) runs two steps at least per
+        launch: there a pull must not come to exactly one decoder step (n >= 2; the first pull, whose element 0 is the
+        prefill's, n = 1 or n >= 3)."""
+        self._open()
+        net, book, recs = self.net, self.book, self._recs
+        N, Q, lib, dev = book.n, net.params.quantization_steps, _lib.lib(), net.device
+        u_host = np.ascontiguousarray(np.asarray(uniforms.cpu() if isinstance(uniforms, torch.Tensor) else uniforms, dtype=np.float64))
+        if u_host.shape != (N, int(n)):
+            raise Exception("pull: uniforms must be (%d, %d) float64, one per emitted sample, got %s" % (N, int(n), u_host.shape))
+        steps = book.check_pull(n)
+        n = int(n)
+        u = torch.as_tensor(u_host).to(dev)
+        out = torch.empty((N, n), device=dev, dtype=torch.int32)
+        ch = torch.empty((N, n), device=dev, dtype=torch.float32) if self.return_chosen else None
+        off = n - steps                                            # 1 on the first pull: element 0 is the prefill's
+        if off:
+            first = torch.empty((N,), device=dev, dtype=torch.int32)
+            u0 = u[:, 0].contiguous()
+            if all(sampling.controls_off(r.temperature, r.top_k, r.top_p, Q) for r in recs):
+                first_prob = torch.cat(self._first_rows, dim=0).contiguous()
+                check(lib.wn_sample_categorical(ptr(first_prob), ptr(u0), ptr(first), N, Q, stream_ptr()), "wn_sample_categorical")
+            else:
+                for i, r in enumerate(recs):
+                    check(lib.wn_sample_categorical_filtered(ptr(self._first_rows[i]), ptr(u0[i:i + 1]), ptr(first[i:i + 1]), 1, Q,
+                                                             r.top_k, r.top_p, stream_ptr()), "wn_sample_categorical_filtered")
+            out[:, 0] = first
+            if ch is not None:
+                ch[:, 0] = torch.cat(self._first_rows, dim=0).gather(1, first.long()[:, None])[:, 0]
+            self._last = [int(v) for v in first.cpu().tolist()]
+        if steps:
+            # (the nine-workgroup form keeps its token buffers, as in generate_batch)
+            outs = [torch.empty((steps,), device=dev, dtype=torch.int32) if self._nine else out[i][off:] for i in range(N)]
+            us = [u[i][off:] for i in range(N)]
+            chs = [ch[i][off:] for i in range(N)] if ch is not None else None
+            batched = N > 1 and not self._one_wg
+            if batched:
+                limit = int(lib.wn_decoder_batch_max()) if self._nine else _lib.WN_DECODER_BATCH_MAX_ANY
+                same = 1 if self._nine and os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") != "1" else 0
+                launched = 0
+                for n_launch, sel in deal_launches([steps] * N, limit):
+                    rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._hs[i].value for i in sel]), len(sel),
+                                                  (C.c_int32 * len(sel))(*[self._last[i] for i in sel]), ptr_array([us[i] for i in sel]),
+                                                  n_launch, ptr_array([outs[i] for i in sel]),
+                                                  ptr_array([chs[i] for i in sel]) if chs is not None else None, same, stream_ptr())
+                    if rc == _lib.WN_ESHAPE and self._nine and not launched:
+                        batched = False            # refused before any device work: nine workgroups per utterance do not fit the device
+                        break
+                    check(rc, "wn_decoder_run_batch")
+                    launched += 1
+            if not batched:
+                for i in range(N):
+                    check(lib.wn_decoder_run(self._hs[i], self._last[i], ptr(us[i]), steps, ptr(outs[i]),
+                                             ptr(chs[i]) if chs is not None else None, stream_ptr()), "wn_decoder_run")
+            for i in (range(N) if self._nine else range(1)):
+                check(lib.wn_decoder_status(self._hs[i], stream_ptr()), "wn_decoder_status")
+            if self._nine:
+                for i in range(N):
+                    out[i][off:] = outs[i]
+            self._last = [int(v) for v in out[:, -1].cpu().tolist()]
+        book.pulled(steps)
+        return (out, ch) if self.return_chosen else out
+
+    # -- the end ------------------------------------------------------------------------------------------------------------------
+    def _open(self):
+        if self.closed:
+            raise Exception("this stream is closed")
+
+    def close(self):
+        """Destroy the handles, then drop the rings they read (in that order: a handle reads its ring in place)."""
+        hs, self._hs = self._hs, []
+        for h in hs:
+            _lib.lib().wn_decoder_destroy(h)
+        self._rings, self.closed = [], True
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -80,6 +80,18 @@ _LIKELIHOOD_FLAGS = (
                              "With --keep the figure covers the kept samples too: a candidate is judged by how the real audio "
                              "continues from what was drawn into it"),
 )
+# streaming synthesis (FasterWaveNet.open_stream; train_audio/generate.py stream_job / generate_streamed): off, attributes of the
+# namespace only when given, checked by generate before the model is built
+_STREAM_FLAGS = (
+    (("--chunk-frames",), int, None, "generate --fast --local FILE.npy: vocode as a stream -- hand the decoder C feature columns at a "
+                                     "time, draw what they allow and append it to generated.wav as it goes; prints the time to the "
+                                     "first written chunk.  With C >= the file's columns the output is byte for byte that of the "
+                                     "command without the flag (with --best-of K > 1 the file is written at the end, when the "
+                                     "ranking is known).  One utterance, from silence: excludes --utterances, --prompt, --keep and "
+                                     "--local-dir"),
+    (("--ring-frames",), int, None, "generate --chunk-frames: rows of the ring of projected feature rows the decoder reads in place "
+                                    "(default: what one chunk and the largest pull need)"),
+)
 # regenerating stretches of a recording (FasterWaveNet.generate(..., forced=...); train_audio/generate.py keep_job / keep_mask): off,
 # attributes of the namespace only when given, checked by generate before the model is built
 _KEEP_HELP = ("generate --fast: keep this recording and draw only the --redraw stretches: the file's first input_width samples are "
@@ -105,6 +117,7 @@ class Args(argparse.Namespace):
     local_upsample = None
     report, best_of = None, 1
     keep, redraw = None, None
+    chunk_frames, ring_frames = None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -114,7 +127,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _LIKELIHOOD_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

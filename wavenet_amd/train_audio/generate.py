@@ -13,7 +13,10 @@ run and keeps the candidate the model found most likely.  Likelihood rewards qui
 the window, every later sample is emitted as the file has it (``FasterWaveNet.generate(..., forced=...)``) unless a ``--redraw``
 range, in seconds of the file, covers it, and the output is the file with those ranges drawn anew.  Without ``--redraw`` the
 run keeps everything and ``--report`` is the decoder's own likelihood of the file; ``--best-of K`` ranks on the figure over all
-emitted samples, kept ones included -- a candidate is judged by how the real audio continues from what was drawn into it."""
+emitted samples, kept ones included -- a candidate is judged by how the real audio continues from what was drawn into it.
+``--fast --local FILE.npy --chunk-frames C [--ring-frames R]`` vocodes as a stream (``FasterWaveNet.open_stream``): C feature
+columns at a time go to the decoder, which draws what they allow; ``generated.wav`` grows as it goes, and the time to its first
+chunk is printed."""
 from __future__ import annotations
 
 import json
@@ -152,6 +155,128 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
     if report:
         write_report(report, [filename], [tokens], ranked, best_of)
     return filename, tokens
+
+
+def stream_job(args):
+    """``generate --chunk-frames C [--ring-frames R]``: the checks, made before a model is built.  Returns (C or None, R or
+    None)."""
+    C, R = args.chunk_frames, args.ring_frames
+    if C is None:
+        if R is not None:
+            raise SystemExit("generate: --ring-frames sizes the ring of a streamed run: give --chunk-frames C")
+        return None, None
+    if C < 1:
+        raise SystemExit("generate: --chunk-frames C needs C >= 1, got {}".format(C))
+    if R is not None and R < 1:
+        raise SystemExit("generate: --ring-frames R needs R >= 1, got {}".format(R))
+    if not args.fast:
+        raise SystemExit("generate: --chunk-frames streams features to the decoder on the device: give --fast")
+    if not args.local:
+        raise SystemExit("generate: --chunk-frames streams the columns of a feature file: give --local FILE.npy")
+    if args.utterances is not None or args.prompt or args.keep or args.local_dir is not None:
+        raise SystemExit("generate: --chunk-frames vocodes one utterance from silence: --utterances, --prompt, --keep and "
+                         "--local-dir do not go with it")
+    return int(C), None if R is None else int(R)
+
+
+class _GrowingWav(object):
+    """``generated.wav`` written chunk by chunk: the bytes ``data.save_audio_file`` writes for the same tokens (16-bit PCM, the
+    mono signal in two channels), the header kept current after every chunk."""
+
+    def __init__(self, filename, Q, sampling_rate):
+        import wave
+        self.Q = Q
+        self.f = wave.open(filename, "wb")
+        self.f.setnchannels(2)
+        self.f.setsampwidth(2)
+        self.f.setframerate(int(sampling_rate))
+
+    def append(self, tokens):
+        scale, dtype = data._pcm_format("16bit_pcm", True)
+        s = data.mulaw_decode(np.asarray(tokens), self.Q, True) * scale
+        self.f.writeframes(np.repeat(s.reshape((-1, 1)).astype(dtype), 2, axis=1).astype("<i2").tobytes())
+
+    def close(self):
+        self.f.close()
+
+
+def generate_streamed(net, params, local, chunk_frames, ring_frames=None, generate_sec=1.0, output_dir="generated_audio",
+                      temperature=1.0, top_k=0, top_p=1.0, condition=None, best_of=1, report=None, max_pull=4096):
+    """``generate --chunk-frames C``: one utterance from silence through ``FasterWaveNet.open_stream``.  The stream is opened with
+    the first max(C, columns of the window) columns of ``local`` and fed C more at a time; after every feed everything
+    ``available()`` is pulled, ``max_pull`` samples at a time at most, and appended to ``generated.wav``.  Uniforms: the
+    ``random_sample`` draws of the command without the flag, so with C >= the columns -- one projection over the same array --
+    the file is the same, byte for byte.  ``best_of`` = K > 1: the K candidates are K utterances of the stream, ``chosen`` is
+    collected per pull, and the file is written at the end, when the ranking is known."""
+    from ..faster_wavenet import stream_frames
+    from ..wavenet import coarse_frames_needed
+    Q, sr = params.quantization_steps, params.sampling_rate
+    sampling.check_controls(temperature, top_k, top_p)
+    n = int(sr * generate_sec) - 1
+    K, want = int(best_of), best_of > 1 or bool(report)
+    if n <= 0:
+        return generate_audio(net, params, sr, generate_sec, True, output_dir, temperature, top_k, top_p, condition, local, best_of, report)
+    silence = silence_window(Q, input_width_of(params))
+    start_time = time.time()
+    os.makedirs(output_dir, exist_ok=True)
+    filename = "{}/generated.wav".format(output_dir)
+    u = np.reshape(np.random.random_sample(n) if K == 1 else np.random.random_sample((K, n)), (K, n))
+    local = np.asarray(local, dtype=np.float32)
+    cols, C, U = int(local.shape[1]), int(chunk_frames), net.local_upsample
+    # the window's own columns come with the call that opens the stream: the prefill reads them
+    first = min(cols, max(C, coarse_frames_needed(len(silence), net.local_hop, U, 0, net.local_interp)))
+    if ring_frames is None:            # one feed, and what the largest pull reads at once
+        ring_frames = max(first, C) * U + stream_frames(net.local_fine_hop, net.local_interp == "linear", 0, pull=max_pull).min_ring
+    wav = _GrowingWav(filename, Q, sr) if K == 1 else None
+    toks, chosen, done, at = [], [], 0, first
+    try:
+        with net.open_stream(utterances=K, initial_tokens=silence, condition=condition, local=local[:, :first],
+                             temperature=temperature, top_k=top_k, top_p=top_p, return_chosen=want, ring_frames=ring_frames,
+                             max_pull=max_pull) as st:
+            while True:
+                while done < n:
+                    m = min(min(st.available()), n - done, max_pull)
+                    if st.book.two_steps:                              # the nine-workgroup decoder runs two steps at least per launch:
+                        if n - done - m == 1:                          # ... leave no single step for the end,
+                            m -= 1
+                        if st.book.steps_of(m) == 1:                   # ... and run none now (more rows are coming)
+                            m -= 1
+                    if m < 1:
+                        break
+                    got = st.pull(m, u[:, done:done + m])
+                    t, c = got if want else (got, None)
+                    t = t.cpu().numpy()
+                    toks.append(t)
+                    if c is not None:
+                        chosen.append(c.cpu().numpy())
+                    if wav is not None:
+                        wav.append(t[0])
+                    if not done:
+                        print("first chunk ({} samples) after {:.3f} sec".format(m, time.time() - start_time))
+                    done += m
+                if done >= n or at >= cols:
+                    break
+                k = min(C, cols - at)
+                st.push(local[:, at:at + k] if K == 1 else [local[:, at:at + k]] * K)
+                at += k
+    finally:
+        if wav is not None:
+            wav.close()
+    if done < n:
+        raise SystemExit("generate: the stream ended after {} of {} samples: what is left is a single decoder step, and the "
+                         "nine-workgroup decoder runs two at least".format(done, n))
+    tokens = np.concatenate(toks, axis=1)
+    ranked = None
+    if want:
+        (kept,), ranked = _keep_best(list(tokens), list(np.concatenate(chosen, axis=1)), K)
+    else:
+        kept = tokens[0]
+    print("\ndone in {:.3f} sec".format(time.time() - start_time))
+    if wav is None:
+        data.save_audio_file(filename, kept, Q, format="16bit_pcm", sampling_rate=sr)
+    if report:
+        write_report(report, [filename], [kept], ranked, K)
+    return filename, kept
 
 
 def read_prompt(path, params):
@@ -377,6 +502,7 @@ def _seconds_given(argv) -> bool:
 def main(argv=None):
     args = _args.parse(argv)
     best_of, report = likelihood_job(args)
+    chunk_frames, ring_frames = stream_job(args)
     seconds_given = _seconds_given(argv)
     kept = keep_job(args, seconds_given)
     if args.local_dir is not None:
@@ -425,6 +551,10 @@ def main(argv=None):
     if kept is not None:
         return generate_kept(net, params, *kept, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
                              top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of, report=report)
+    if chunk_frames is not None:
+        return generate_streamed(net, params, feats[0], chunk_frames, ring_frames, generate_sec=args.seconds, output_dir=args.output_dir,
+                                 temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, condition=cids[0],
+                                 best_of=best_of, report=report)
     if n_utt is not None:
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
