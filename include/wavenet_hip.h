@@ -108,7 +108,8 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                       rescaled -- they never pass through the power-of-two tile scale -- and runs every layer as
                                       its own launch, as under WN_EXEC_NO_FWD_GROUPS.  The stack backward takes the per-layer
                                       path (bias-gradient tables always do), so wn_stack_saves_tanh is 1.  wn16_* (bf16 storage)
-                                      keeps refusing biases.  A step plan holds weight images only, never a bias pointer.
+                                      takes rows through the descriptor alone (WN16_BWD_ROW_GRADS).  A step plan holds
+                                      weight images only, never a bias pointer.
                                       Local conditioning (eq. 4 with y = the features repeated over time): wn_stack_fwd /
                                       wn_stack_bwd read three trailing WnStackDesc fields under this flag.  bias_hop = h > 0
                                       turns clip b's row into a block of n = ceil((T + bias_phase) / h) rows: bf[l] / bg[l]
@@ -129,7 +130,7 @@ enum { WN_GEMM_FP32 = 0, WN_GEMM_BF16X3 = 1, WN_GEMM_BF16 = 2, WN_GEMM_FP16X2 = 
                                       reserved < n * bias_frame_stride; bias_hop > 0 without the flag; on the fp16 x 2 path rows that are not 16-byte aligned or a clip /
                                       frame stride that is no multiple of 4 floats (refused, never sent down another path).
                                       bias_hop == 0: the other two fields are ignored.  wn_layer_fwd / wn_layer_bwd take no
-                                      descriptor and keep per-clip rows only; wn16_* keeps refusing biases.
+                                      descriptor and keep per-clip rows only; wn16_*: see WN16_BWD_ROW_GRADS.
                                       Linear interpolation between frames (WnStackDesc.bias_interp = 1; 0, the default, is
                                       the above, unchanged): row k is ANCHORED at the first position of its frame, k * h --
                                       the alignment rule above is untouched, a value is reached exactly at its frame's first
@@ -678,12 +679,37 @@ int wn16_embed_bwd(const int32_t* idx, const uint16_t* dout, float* dW, float* d
                    void* ws, size_t ws_bytes, void* stream);
 int wn16_cvt_to_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);     /* n % 8 == 0 */
 int wn16_cvt_to_f32(const uint16_t* src, float* dst, int64_t n, void* stream);
+/* Gate-bias rows in bf16 storage (conditioning).  wn16_* calls take no WnExec: the descriptor alone decides.  It has rows when
+ * bf[l] and bg[l] are non-NULL for every layer AND bias_frame_stride > 0 (all NULL: unconditioned; non-NULL entries with
+ * bias_frame_stride == 0 are static biases and refused; a mixture of NULL and non-NULL is WN_EARG; wn16_pack_stack ignores
+ * rows).  bf[l] / bg[l] point at layer l's filter / gate row -- 128 floats, 16-byte aligned -- of (clip 0, frame 0);
+ * bias_frame_stride (>= 128, a multiple of 4) is the number of floats between consecutive rows of a block.  bias_hop == 0: one
+ * row per clip, clip b's row b * bias_frame_stride floats on.  bias_hop = H > 0: a row per (clip, frame); bias_phase,
+ * bias_interp and bias_phase_tab mean what they mean under WN_EXEC_BIAS_PER_CLIP, and the value position t reads is formed by
+ * the same arithmetic (the frame's row, or r[j] + alpha (r[j + 1] - r[j]) in three separately rounded fp32 operations; a table
+ * value is fenced with (unsigned) v % H).  Clip blocks are DENSE: clip b's block starts b * n * bias_frame_stride floats on, n
+ * the rows the call itself needs -- ceil((T + worst phase) / H), one more with bias_interp = 1; the worst phase is bias_phase,
+ * or H - 1 with a table.  For t < Z neither the convolution nor the row counts.  The row value is the start of the fp32
+ * accumulator the convolution is added to.  WN_EARG before any device work, each naming its field: what the fp32 path refuses
+ * (bias_hop < 0, bias_phase outside [0, bias_hop), bias_interp outside {0, 1} or without a hop, a table without a hop, with
+ * bias_phase != 0 or misaligned, T + worst phase beyond 32 bits, bias_frame_stride < 128), rows that are not 16-byte aligned
+ * and a stride that is no multiple of 4.
+ * Backward: a descriptor with rows needs WN16_BWD_ROW_GRADS in flags, and dWf / dWg then hold 2 n_layers entries: entry
+ * n_layers + l is layer l's filter / gate GRADIENT row of (clip 0, frame 0), in a block of the forward block's strides and
+ * alignment.  Row j of clip b receives (+=, one addition per element) the fp32 sum over max(Z, first written row) <= t < T of
+ * w_t v_t, v_t the STORED bf16 [da | dg] of position t: w = 1 over the t of frame j (over all t with one row per clip); with
+ * bias_interp = 1, 1 - alpha_t over the t of frame j and alpha_t over those of frame j - 1.  One launch for all layers
+ * (k16_row_grads; rows of more than 512 positions leave per-chunk sums in the workspace, added in chunk order by a second):
+ * ascending t, no float atomics, bit-reproducible.  Every row of the block is written; one no live position reaches receives
+ * + 0.  WN_EARG: the bit without rows, rows without the bit, any other bit. */
+#define WN16_BWD_ROW_GRADS 1u
 /* A11: xs (L,B,T,128) every layer's output, z (L,B,T,128), skip (B,T-t_off,Cs) or NULL */
 int wn16_stack_fwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x, uint16_t* xs, uint16_t* z,
                    uint16_t* skip, int B, int T, int t_off, int compat_zero_prefix, void* stream);
 size_t wn16_stack_bwd_workspace_bytes(const WnStackDesc* d, int B, int T, int t_off);
 /* A15: dout must be NULL (train_audio/train.py:72 discards the stack's residual output), dskip (B,T-t_off,Cs),
- * dx (B,T,128) or NULL; fp32 gradients accumulated.  flags: unused (kept for the ABI), pass 0. */
+ * dx (B,T,128) or NULL; fp32 gradients accumulated.  flags: 0, or WN16_BWD_ROW_GRADS for a descriptor with gate-bias
+ * rows (above: dWf / dWg then hold 2 n_layers entries). */
 int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x, const uint16_t* xs, const uint16_t* z,
                    const uint16_t* dout, const uint16_t* dskip, uint16_t* dx, float* const* dWf, float* const* dWg,
                    float* const* dWp, float* const* dWs, void* ws, size_t ws_bytes, int B, int T, int t_off,

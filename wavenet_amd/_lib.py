@@ -220,6 +220,7 @@ GEMM_PRECISIONS = ("fp32", "bf16x3", "bf16", "fp16x2")
 WN_EXEC_FORCE_GENERIC, WN_EXEC_NO_FWD_GROUPS, WN_EXEC_NO_PIPELINED_GEMM = 1, 4, 8
 WN_EXEC_NO_MULTI_LAYER_BWD = 16
 WN_EXEC_BIAS_PER_CLIP = 2              # wn_layer_* / wn_stack_*: one row of gate biases per clip, WnExec.reserved floats apart (global conditioning)
+WN16_BWD_ROW_GRADS = 1           # wn16_stack_bwd flags: dWf / dWg hold 2 L entries, the gate-row gradient tables behind the weights'
 WN_EXEC_HEAD_ROW_NLL = 32              # wn_head_xent only: N per-row negative log-likelihoods instead of the (N, Q) gradient
 WN_DECODER_ONE_WORKGROUP = 64          # WnDecoderDesc.flags: wn_decoder_run on one workgroup instead of nine (other summation order: ~1e-7)
 WN_DECODER_GATE_ROWS = 128             # WnDecoderDesc.flags: gate biases / a frame table do not deselect the specialised 32/256-channel decoder

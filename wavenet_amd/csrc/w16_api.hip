@@ -27,10 +27,57 @@ const char* unsupported(const WnStackDesc* d) {
     if (d->n_layers > kMaxProb16 || (d->n_layers & 1)) return "needs an even number of layers, at most 48";
     for (int l = 0; l < d->n_layers; ++l) {
         if (d->cd[l] != 128) return "needs 128 dilation channels in every layer";
-        if ((d->bf && d->bf[l]) || (d->bg && d->bg[l]) || (d->bp && d->bp[l]) || (d->bs && d->bs[l]))
+        // (bf / bg with a row stride are gate-bias rows -- conditioning, take_rows below --, without one static biases)
+        if ((d->bias_frame_stride <= 0 && ((d->bf && d->bf[l]) || (d->bg && d->bg[l]))) || (d->bp && d->bp[l]) || (d->bs && d->bs[l]))
             return "convolution / projection biases are not supported (the reference's default has none)";
     }
     return nullptr;
+}
+
+// Gate-bias rows (conditioning).  A wn16_* call takes no WnExec, so the descriptor alone decides: it has rows when bf[l] and
+// bg[l] are non-NULL for every layer and bias_frame_stride > 0 (all NULL: unconditioned; unsupported() has refused non-NULL
+// entries without a stride).  Clip blocks are dense: with frames, clip b's block starts b * rows(T) * bias_frame_stride floats
+// on (BiasFrames::rows: the frames at the worst phase, one more with interpolation); with one row per clip, b *
+// bias_frame_stride.  Checked before any device work; R.bf / R.bg are left for the caller to fill per layer.
+int take_rows(const char* fn, const WnStackDesc* d, int T, LayerRows& R) {
+    R = LayerRows{nullptr, nullptr, 0, {0, 0, 0, 0, nullptr}, wn::kCondNone};
+    const int L = d->n_layers;
+    int have = 0;
+    for (int l = 0; l < L; ++l) have += (d->bf && d->bf[l] ? 1 : 0) + (d->bg && d->bg[l] ? 1 : 0);
+    if (have == 0) return WN_OK;
+    WN_CHECK_ARG(have == 2 * L, "%s: WnStackDesc.bf / bg hold NULL and non-NULL entries (gate-bias rows are given for every layer "
+                                "or for none)", fn);
+    const int stride = d->bias_frame_stride;
+    WN_CHECK_ARG(stride >= 128, "%s: WnStackDesc.bias_frame_stride = %d below cd = 128", fn, stride);
+    WN_CHECK_ARG(stride % 4 == 0, "%s: WnStackDesc.bias_frame_stride = %d is no multiple of 4 floats (rows are read 16 bytes at a "
+                                  "time)", fn, stride);
+    for (int l = 0; l < L; ++l)
+        WN_CHECK_ARG(((reinterpret_cast<uintptr_t>(d->bf[l]) | reinterpret_cast<uintptr_t>(d->bg[l])) & 15) == 0,
+                     "%s: WnStackDesc.bf / bg rows of layer %d are not 16-byte aligned", fn, l);
+    WN_CHECK_ARG(d->bias_hop >= 0, "%s: WnStackDesc.bias_hop = %d is negative", fn, d->bias_hop);
+    WN_CHECK_ARG(d->bias_interp == 0 || d->bias_interp == 1, "%s: WnStackDesc.bias_interp = %d is neither 0 (repeat) nor 1 (linear)",
+                 fn, d->bias_interp);
+    WN_CHECK_ARG(d->bias_interp == 0 || d->bias_hop > 0, "%s: WnStackDesc.bias_interp = %d without frames (bias_hop = 0)", fn,
+                 d->bias_interp);
+    const int* tab = d->bias_phase_tab;
+    WN_CHECK_ARG(!tab || d->bias_hop > 0, "%s: WnStackDesc.bias_phase_tab without frames (bias_hop = 0)", fn);
+    R.clip_stride = stride;
+    R.fr.stride = stride;
+    R.mode = wn::kCondClip;
+    if (d->bias_hop == 0) return WN_OK;
+    WN_CHECK_ARG(d->bias_phase >= 0 && d->bias_phase < d->bias_hop, "%s: WnStackDesc.bias_phase = %d outside [0, bias_hop = %d)", fn,
+                 d->bias_phase, d->bias_hop);
+    WN_CHECK_ARG(!tab || d->bias_phase == 0, "%s: WnStackDesc.bias_phase_tab together with bias_phase = %d is ambiguous (a table "
+                                             "goes with bias_phase = 0)", fn, d->bias_phase);
+    WN_CHECK_ARG((reinterpret_cast<uintptr_t>(tab) & 3) == 0, "%s: WnStackDesc.bias_phase_tab is not 4-byte aligned", fn);
+    R.fr = wn::BiasFrames{d->bias_hop, d->bias_phase, (long long)stride, d->bias_interp, tab};
+    const long long last = (long long)T + R.fr.worst_phase();
+    WN_CHECK_ARG(last <= 2147483647ll,
+                 tab ? "%s: T + WnStackDesc.bias_hop - 1 = %lld does not fit 32 bits (a bias_phase_tab entry may be bias_hop - 1)"
+                     : "%s: T + WnStackDesc.bias_phase = %lld does not fit 32 bits", fn, last);
+    R.clip_stride = R.fr.rows(T) * stride;
+    R.mode = d->bias_interp ? wn::kCondLinear : wn::kCondFrame;
+    return WN_OK;
 }
 
 size_t pack_elems(const WnStackDesc* d) {
@@ -38,8 +85,10 @@ size_t pack_elems(const WnStackDesc* d) {
     return L * kLayerImg + 2 * (size_t)d->Cs * L * 128;     // layer images, skip matrix [Cs][128 L], dz matrix [128 L][Cs]
 }
 
-struct BwdWs { bf16* dzs; bf16* dadg; bf16* dxb[2]; float* parts; float* wgparts; size_t bytes; };
-BwdWs carve(const WnStackDesc* d, int B, int T, int t_off, char* ws) {
+struct BwdWs { bf16* dzs; bf16* dadg; bf16* dxb[2]; float* parts; float* wgparts; float* rowparts; size_t bytes; };
+// (R: the call's gate-bias rows.  Their partial sums lie BEHIND everything else: a descriptor without rows gets the layout and
+// the byte count it always got)
+BwdWs carve(const WnStackDesc* d, int B, int T, int t_off, char* ws, const LayerRows& R) {
     const size_t L = d->n_layers, n = (size_t)B * T, nw = (size_t)B * (T - t_off);
     BwdWs r{};
     size_t o = 0;
@@ -50,6 +99,7 @@ BwdWs carve(const WnStackDesc* d, int B, int T, int t_off, char* ws) {
     r.dxb[1] = reinterpret_cast<bf16*>(take(n * 128 * 2));
     r.parts = reinterpret_cast<float*>(take(L * (size_t)dx_grid(B, T) * 128 * 128 * 4));
     r.wgparts = reinterpret_cast<float*>(take(kWgPartBytes));        // per-workgroup blocks of the time contractions
+    if (const size_t rb = row_grad_ws_bytes(R, (int)L, B, T)) r.rowparts = reinterpret_cast<float*>(take(rb));
     r.bytes = o;
     return r;
 }
@@ -113,6 +163,8 @@ int wn16_stack_fwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
                    uint16_t* skip, int B, int T, int t_off, int compat_zero_prefix, void* stream) {
     W16_CHECK_DESC(d);
     WN_CHECK_ARG(pack && x && xs && z && B > 0 && T > 0 && t_off >= 0 && t_off < T, "wn16_stack_fwd: bad argument");
+    LayerRows R;
+    if (int rc = take_rows(__func__, d, T, R)) return rc;
     hipStream_t s = wn::as_stream(stream);
     const int L = d->n_layers;
     const size_t n = (size_t)B * T;
@@ -126,7 +178,8 @@ int wn16_stack_fwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
         for (int l = 0; l < L; ++l) {
             const int Z = compat_zero_prefix ? zero_prefix(T, d->dilation[l], 2) : 0;
             bf16* out = xsb + (size_t)l * n * 128;
-            if ((rc = fwd_layer(in, img + (size_t)l * kLayerImg, out, zb + (size_t)l * n * 128, B, T, d->dilation[l], Z, s)))
+            if (R.mode != wn::kCondNone) { R.bf = d->bf[l]; R.bg = d->bg[l]; }
+            if ((rc = fwd_layer(in, img + (size_t)l * kLayerImg, out, zb + (size_t)l * n * 128, B, T, d->dilation[l], Z, R, s)))
                 return rc;
             in = out;
         }
@@ -143,15 +196,32 @@ int wn16_stack_fwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
 
 size_t wn16_stack_bwd_workspace_bytes(const WnStackDesc* d, int B, int T, int t_off) {
     if (unsupported(d) || B <= 0 || T <= 0 || t_off < 0 || t_off >= T) return 0;
-    return carve(d, B, T, t_off, nullptr).bytes;
+    LayerRows R;
+    if (take_rows(__func__, d, T, R)) return 0;
+    return carve(d, B, T, t_off, nullptr, R).bytes;
 }
 
 int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x, const uint16_t* xs, const uint16_t* z,
                    const uint16_t* dout, const uint16_t* dskip, uint16_t* dx, float* const* dWf, float* const* dWg,
                    float* const* dWp, float* const* dWs, void* ws, size_t ws_bytes, int B, int T, int t_off,
-                   int compat_zero_prefix, unsigned /* flags: unused */, void* stream) {
+                   int compat_zero_prefix, unsigned flags, void* stream) {
     W16_CHECK_DESC(d);
     WN_CHECK_ARG(pack && x && xs && z && dWf && dWg && dWp && ws && B > 0 && T > 0, "wn16_stack_bwd: bad argument");
+    WN_CHECK_ARG((flags & ~WN16_BWD_ROW_GRADS) == 0, "wn16_stack_bwd: unknown bits in flags (0x%x)", flags);
+    LayerRows R;
+    if (int rc0 = take_rows(__func__, d, T, R)) return rc0;
+    const bool row_grads_wanted = (flags & WN16_BWD_ROW_GRADS) != 0;
+    WN_CHECK_ARG(!row_grads_wanted || R.mode != wn::kCondNone, "wn16_stack_bwd: flags has WN16_BWD_ROW_GRADS but the descriptor holds no "
+                                                               "gate-bias rows (bf / bg)");
+    WN_CHECK_ARG(row_grads_wanted || R.mode == wn::kCondNone, "wn16_stack_bwd: the descriptor holds gate-bias rows (bf / bg): flags "
+                                                              "must have WN16_BWD_ROW_GRADS and dWf / dWg 2 n_layers entries");
+    if (row_grads_wanted)
+        for (int l = 0; l < d->n_layers; ++l) {
+            WN_CHECK_ARG(dWf[d->n_layers + l] && dWg[d->n_layers + l], "wn16_stack_bwd: WN16_BWD_ROW_GRADS: dWf / dWg entry n_layers + %d "
+                                                                       "(the gradient rows of layer %d) is NULL", l, l);
+            WN_CHECK_ARG(((reinterpret_cast<uintptr_t>(dWf[d->n_layers + l]) | reinterpret_cast<uintptr_t>(dWg[d->n_layers + l])) & 15) == 0,
+                         "wn16_stack_bwd: the gradient rows of layer %d (dWf / dWg entry n_layers + %d) are not 16-byte aligned", l, l);
+        }
     WN_CHECK_ARG(dskip, "wn16_stack_bwd: dskip is NULL (the loss reaches the stack through the skip sum)");
     WN_CHECK_ARG(t_off >= 0 && t_off < T, "wn16_stack_bwd: t_off outside [0,T)");
     WN_CHECK_ARG(ws_bytes >= wn16_stack_bwd_workspace_bytes(d, B, T, t_off), "wn16_stack_bwd: workspace too small");
@@ -163,7 +233,7 @@ int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
     const bf16* xsb = reinterpret_cast<const bf16*>(xs);
     const bf16* zb = reinterpret_cast<const bf16*>(z);
     const bf16* dsk = reinterpret_cast<const bf16*>(dskip);
-    BwdWs w = carve(d, B, T, t_off, reinterpret_cast<char*>(ws));
+    BwdWs w = carve(d, B, T, t_off, reinterpret_cast<char*>(ws), R);
     int rc;
     if (dsk) {
         {   // dz_skip of every layer: one GEMM, M = 128 L, each 128-row block is a layer's (B, Tw, 128) slab
@@ -224,8 +294,9 @@ int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
             const bf16* in = l == 0 ? xb : xsb + (size_t)(l - 1) * n * 128;
             const int dl = d->dilation[l];
             bf16* dadg = w.dadg + (size_t)l * n * 256;
+            if (R.mode != wn::kCondNone) { R.bf = d->bf[l]; R.bg = d->bg[l]; }
             if ((rc = gate_bwd_layer(in, img + (size_t)l * kLayerImg, gout, dsk ? w.dzs + (size_t)l * nw * 128 : nullptr,
-                                     t_off, dadg, B, T, dl, Zl[l], live_g[l], zero_g[l], s)))
+                                     t_off, dadg, B, T, dl, Zl[l], live_g[l], zero_g[l], R, s)))
                 return rc;
             bf16* gin = l == 0 ? reinterpret_cast<bf16*>(dx) : w.dxb[l & 1];
             if (!gin) break;                               // l == 0 and the caller does not want dx
@@ -257,6 +328,12 @@ int wn16_stack_bwd(const WnStackDesc* d, const uint16_t* pack, const uint16_t* x
             }
         }
         if ((rc = launch_wgrad16(a, L, s))) return rc;
+    }
+    if (row_grads_wanted) {   // the gate-row gradients of every layer in one launch, from the [da | dg] retained above
+        wn::ProfScope prof__("wn16_row_grads", stream);
+        std::vector<int> lo(L);
+        for (int l = 0; l < L; ++l) lo[l] = Zl[l] > zero_g[l] ? Zl[l] : zero_g[l];   // below: the zero prefix, unwritten rows
+        if ((rc = row_grads(w.dadg, R, dWf + L, dWg + L, lo.data(), L, B, T, w.rowparts, s))) return rc;
     }
     return reduce_parts(w.parts, part_stride, nwg, 128 * 128, dWp_eff.data(), L, s);
 }

@@ -1,6 +1,7 @@
 // Host-side descriptors and launchers of the bf16-storage path (w16_*.hip).
 #pragma once
 #include "w16.hpp"
+#include "wn_kernels.hpp"
 
 namespace w16 {
 
@@ -66,11 +67,29 @@ int embed_bwd16(const int32_t* idx, const bf16* dx, float* dW, float* dbias, int
 int embed_fwd16(const int32_t* idx, const float* W, const float* bias, bf16* out, int B, int T, int Q, int C, hipStream_t s);
 
 // w16_layer.hip
-int fwd_layer(const bf16* x, const bf16* img, bf16* out, bf16* z, int B, int T, int d, int Z, hipStream_t s);
+// One layer's gate-bias rows (conditioning): bf / bg point at the filter / gate row (128 floats, 16-byte aligned) of (clip 0,
+// frame 0); clip b's block starts b * clip_stride floats on, frame f lies f * fr.stride floats on inside it (wn::BiasFrames and
+// the helpers around it, wn_kernels.hpp: the arithmetic of a row value is the fp32 path's).  mode: wn::kCond*; kCondNone = no rows.
+struct LayerRows {
+    const float* bf; const float* bg;
+    long long clip_stride;
+    wn::BiasFrames fr;
+    int mode;
+};
+int fwd_layer(const bf16* x, const bf16* img, bf16* out, bf16* z, int B, int T, int d, int Z, const LayerRows& R, hipStream_t s);
+// The gate-row gradients of every layer in one launch (two when a row sums more than kRowChunk positions: partials, then a
+// fixed-order reduce), from the retained [da | dg] (L, B, T, 256): row j of clip b of layer l receives (+=, one addition per
+// element) the sum over lo[l] <= t < T of w_t v_t, v_t the stored bf16 row of position t, w_t = 1 for the t of frame j (every t
+// with one row per clip), with interpolation 1 - alpha_t for the t of frame j and alpha_t for those of frame j - 1.  fp32, ascending t,
+// no atomics.  dbf / dbg: per layer, the gradient rows of (clip 0, frame 0), blocks of the forward's geometry (R.bf / R.bg unused).
+static constexpr int kRowChunk = 512;
+size_t row_grad_ws_bytes(const LayerRows& R, int L, int B, int T);
+int row_grads(const bf16* dadg, const LayerRows& R, float* const* dbf, float* const* dbg, const int* lo, int L, int B, int T,
+              float* part, hipStream_t s);
 // live ranges (multiples of 32; GateP / DxP in w16_layer.hip): columns below t_live receive no gradient; gate tiles below t_zero
 // and (unless zero_dead) dx tiles below t_live are not touched at all; [da | dg](t) and dout(t) read as zero below t_gate
 int gate_bwd_layer(const bf16* x, const bf16* img, const bf16* dout, const bf16* dzs, int dz_t0, bf16* dadg, int B, int T,
-                   int d, int Z, int t_live, int t_zero, hipStream_t s);
+                   int d, int Z, int t_live, int t_zero, const LayerRows& R, hipStream_t s);
 int dx_grid(int B, int T);
 int dx_layer(const bf16* dadg, const bf16* img, const bf16* dout, const bf16* zprev, bf16* dx, float* dwp_part, int B,
              int T, int d, int t_live, int t_gate, int zero_dead, hipStream_t s);

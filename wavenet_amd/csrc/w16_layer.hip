@@ -54,16 +54,94 @@ static constexpr int kLT = 32;                          // time columns per tile
 static constexpr int kLTileB = kLT * 256;               // 8 KB
 
 // ---------------------------------------------------------------------------------------------
+// gate-bias rows (conditioning; LayerRows in w16_gemm.hpp, the modes are wn::kCond*).  A lane owns one time column of a tile,
+// so it reads ITS column's row values: fp32, 16 bytes at a time, straight into registers (LDS is full).  The reads are
+// inline asm like every other request of these loops -- a load hipcc knows of gets an s_waitcnt vmcnt(0) at its first use,
+// which drains the LDS-DMA prefetch of the next tile -- and they are issued AHEAD of issue(next): the counted waits of the
+// tile loops then say what they said (the reads are gone before the tile's stores are issued), and the reads themselves are
+// waited for with "as many requests as issue(next) made may stay in flight".
+// ---------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+using wn::kCondNone; using wn::kCondClip; using wn::kCondFrame; using wn::kCondLinear;
+
+template <int OFF>
+__device__ __forceinline__ f32x4 row_ld16(const float* p) {
+    f32x4 v;
+    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(v) : "v"(p), "n"(OFF) : "memory");
+    return v;
+}
+// behind a counted wait that covers them: the values of row_ld16 may be used from here on (the tie keeps every use behind
+// the wait, which is volatile asm like it)
+template <int K>
+__device__ __forceinline__ void rows_tie(f32x4 (&r)[K]) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) asm volatile("" : "+v"(r[i]));
+}
+template <int N, int K>
+__device__ __forceinline__ void rows_wait(f32x4 (&r)[K]) {
+    wait_vm<N>();
+    rows_tie(r);
+}
+// frame and position inside it of tile column jj (< 32) of the tile at t0, phase ph: (t0 + jj + ph) / hop and % hop, with
+// the division on the scalar unit alone when a frame is at least a tile long
+__device__ __forceinline__ void tile_frame(int hop, int ph, int t0, int jj, int& fi, int& rem) {
+    const int p0 = t0 + ph, f0 = p0 / hop, r0 = p0 - f0 * hop;
+    if (hop >= kLT) {
+        const bool over = r0 + jj >= hop;
+        fi = f0 + (over ? 1 : 0);
+        rem = r0 + jj - (over ? hop : 0);
+    } else {
+        const int q = (r0 + jj) / hop;
+        fi = f0 + q;
+        rem = r0 + jj - q * hop;
+    }
+}
+// THE phase of clip b by wn::frame_phase's rule (the fence included), for a tile loop: b is uniform there, and the table entry
+// is read by an explicit scalar load -- left to hipcc it becomes a vector load with an s_waitcnt vmcnt(0) behind it, inside
+// the loop (tests/test_isa_cpu.py)
+__device__ __forceinline__ int tile_phase(const wn::BiasFrames& fr, int b) {
+    if (!fr.tab) return fr.phase;
+    const int* p = fr.tab + b;
+    int v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
+    return wn::bias_phase_fence(v, fr.hop);
+}
+// what a lane needs to read its column's rows of one tile: the address of its first float of the filter row and of the gate
+// row (frame J(t) of clip b; lane_off = the lane's first channel), the next frame's rows `next` floats on, and alpha
+struct RowAt { const float* pf; const float* pg; float alpha; };
+template <int MODE>
+__device__ __forceinline__ RowAt row_at(const LayerRows& R, int b, int t0, int jj, int lane_off) {
+    RowAt a;
+    long long o = (long long)b * R.clip_stride + lane_off;
+    a.alpha = 0.f;
+    if constexpr (MODE >= kCondFrame) {
+        const int ph = tile_phase(R.fr, b);
+        int fi, rem;
+        tile_frame(R.fr.hop, ph, t0, jj, fi, rem);
+        o += (long long)fi * R.fr.stride;
+        if constexpr (MODE == kCondLinear) a.alpha = wn::bias_alpha(rem, R.fr.hop);            // wn::bias_frame_alpha's value
+    }
+    a.pf = R.bf + o;
+    a.pg = R.bg + o;
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------------
 // forward.  256 threads; LDS: (xold, xcur) x 2 buffers + z tile + out tile = 48 KB, + the projection's operand image
 // (32 KB, read at each use: keeping it in registers left none to prefetch the column operands with, and every
 // ds_read_b128 -> s_waitcnt -> MFMA pair ran back to back: 16 exposed LDS latencies per tile)
 // ---------------------------------------------------------------------------------------------
 static constexpr int kFwdLds = 6 * kLTileB + kProjA * 2;
 
+// MODE (wn::kCond*): the gate-bias rows.  kCondNone is the kernel without them; in the others the lane of column t0 + j starts
+// its accumulators from its column's 16 filter and 16 gate values (channels 32 w + 8 q + 4 h + e = accumulator register
+// 4 q + e; interpolated in fp32 first with kCondLinear), so the matrix pipe adds the convolution to them: no add, no register
+// beside the accumulators while the convolution runs.  The reads of a tile are requested one tile ahead (rows_issue).
+template <int MODE>
 __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void k16_fwd(const bf16* __restrict__ x, const bf16* __restrict__ convA,
                                                    const bf16* __restrict__ projA, bf16* __restrict__ out,
                                                    bf16* __restrict__ z, int B, int T, int d, int Z, int tiles_per_b,
-                                                   int ntiles) {
+                                                   int ntiles, const LayerRows R) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     auto xold = [&](int buf) { return lds + buf * kLTileB; };
     auto xcur = [&](int buf) { return lds + (2 + buf) * kLTileB; };
@@ -136,7 +214,43 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         });
     };
 
+    // the rows of a tile's columns: filter and gate row of each column's frame (ya, yb) and, with interpolation, of the next
+    // (yc, yd).  A column beyond the clip reads the last one's -- its result is never stored.
+    f32x4 ya[4], yb[4], yc[4], yd[4];
+    float alpha = 0.f;
+    const float* pg_next = nullptr;                    // (linear) the gate row of the tile whose filter pair is in flight
+    auto rows_issue = [&](int tile) {                  // linear: the filter pair only, rows_issue_gate asks for the rest
+        const int b = tile / tiles_per_b;
+        const int t0 = (tile - b * tiles_per_b) * kLT;
+        const RowAt ra = row_at<MODE>(R, b, t0, t0 + j < T ? j : T - 1 - t0, 32 * w + 4 * h);
+        alpha = ra.alpha;
+        ya[0] = row_ld16<0>(ra.pf); ya[1] = row_ld16<32>(ra.pf); ya[2] = row_ld16<64>(ra.pf); ya[3] = row_ld16<96>(ra.pf);
+        if constexpr (MODE == kCondLinear) {
+            const float* pf1 = ra.pf + R.fr.stride;
+            yc[0] = row_ld16<0>(pf1); yc[1] = row_ld16<32>(pf1); yc[2] = row_ld16<64>(pf1); yc[3] = row_ld16<96>(pf1);
+            pg_next = ra.pg;
+        } else {
+            yb[0] = row_ld16<0>(ra.pg); yb[1] = row_ld16<32>(ra.pg); yb[2] = row_ld16<64>(ra.pg); yb[3] = row_ld16<96>(ra.pg);
+        }
+    };
+    // (linear) two rows per gate are 64 registers, which do not fit beside the weights.  The filter pair travels like a frame's
+    // rows (requested behind the gate, 32 registers through the projection); BEHIND the tile's stores it is waited for and
+    // folded into 16 values and the gate pair is requested: 48 registers cross the loop's head, where there is room (the
+    // accumulators are not live yet) -- and the wait there is then for everything, the previous tile's stores included.
+    auto rows_issue_gate = [&]() {
+        rows_wait<0>(ya); rows_wait<0>(yc);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ya[q][e] = wn::bias_lerp(ya[q][e], yc[q][e], alpha);
+        const float* pg1 = pg_next + R.fr.stride;
+        yb[0] = row_ld16<0>(pg_next); yb[1] = row_ld16<32>(pg_next); yb[2] = row_ld16<64>(pg_next); yb[3] = row_ld16<96>(pg_next);
+        yd[0] = row_ld16<0>(pg1); yd[1] = row_ld16<32>(pg1); yd[2] = row_ld16<64>(pg1); yd[3] = row_ld16<96>(pg1);
+    };
+
     issue(first, 0);
+    if constexpr (MODE != kCondNone) rows_issue(first);
+    if constexpr (MODE == kCondLinear) rows_issue_gate();
     bool full_prev = false;                            // the previous tile's 4 stores were issued unconditionally
     int it = 0;
     for (int tile = first; tile < last; tile += stride, ++it) {
@@ -144,7 +258,8 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         const int b = tile / tiles_per_b;
         const int t0 = (tile - b * tiles_per_b) * kLT;
         // this tile's 4 DMA pieces are older than the previous tile's 4 stores: those stay in flight
-        if (full_prev) wait_vm<4>(); else wait_vm<0>();
+        // (and so are its row reads, requested between the previous tile's gate and its stores: this wait is theirs too)
+        if (full_prev && MODE != kCondLinear) wait_vm<4>(); else wait_vm<0>();
         barrier();
         if (tile + stride < last) issue(tile + stride, buf ^ 1);
         if (t0 < d) {
@@ -155,8 +270,23 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
         }
         // ---- both dilated convolutions for this wave's 32 channels; column operands fetched four k-steps ahead ----
         f32x16 af, ag;
+        if constexpr (MODE == kCondNone) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { af[r] = 0.f; ag[r] = 0.f; }
+            for (int r = 0; r < 16; ++r) { af[r] = 0.f; ag[r] = 0.f; }
+        } else {                                       // the accumulators start from the column's row values
+            rows_tie(ya); rows_tie(yb);
+            if constexpr (MODE == kCondLinear) {
+                rows_tie(yd);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) yb[q][e] = wn::bias_lerp(yb[q][e], yd[q][e], alpha);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { af[4 * q + e] = ya[q][e]; ag[4 * q + e] = yb[q][e]; }
+        }
         {
             const char* t0p = xold(buf);
             const char* t1p = xcur(buf);
@@ -190,6 +320,11 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                     zz[e] = live ? gate_z(af[4 * q + e], ag[4 * q + e]) : 0.f;
                 *reinterpret_cast<bf16x4*>(zt + qoff[q]) = pack4(zz[0], zz[1], zz[2], zz[3]);
             }
+        }
+        if constexpr (MODE != kCondNone) {
+            // the next tile's rows: the accumulators' registers are free from here on; the requests are older than this tile's
+            // stores, so the wait at the loop's head covers them
+            if (tile + stride < last) rows_issue(tile + stride);
         }
         barrier();
         // ---- residual projection: out rows 32 w .. of all 32 columns, + x ----
@@ -225,6 +360,9 @@ __global__ __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) 
                 st16_wt_s(ob, loff[pp], vo);
             }
         }
+        if constexpr (MODE == kCondLinear) {
+            if (tile + stride < last) rows_issue_gate();
+        }
         full_prev = full;
     }
 }
@@ -249,6 +387,7 @@ static constexpr int kGateLds = 10 * kLTileB;
 struct GateP {
     const bf16* x; const bf16* convA; const bf16* dzA; const bf16* dout; const bf16* dzs; int dz_t0; bf16* dadg;
     int B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero;
+    LayerRows R;                                         // the gate-bias rows the forward added (MODE of gate_phase)
 };
 struct DxP {
     const bf16* dadg; const bf16* dxA; const bf16* dout; const bf16* zprev; bf16* dx; float* dwp_part;
@@ -377,8 +516,10 @@ __device__ __forceinline__ void dx_issue(char* lds, const DxP& P, const WaveC& c
     }
 }
 
-// One layer's gate backward over this workgroup's tiles.
-template <bool HAS_DO, bool HAS_DZ>
+// One layer's gate backward over this workgroup's tiles.  MODE (wn::kCond*) as in k16_fwd: the recomputed pre-activations get
+// the rows the forward added -- a lane's 8 filter and 8 gate values (channels 16 w + 8 q + 4 h + e = accumulator registers
+// 4 q + e and 8 + 4 q + e), read ahead of issue(next) and waited for where the elementwise phase starts.
+template <bool HAS_DO, bool HAS_DZ, int MODE>
 __device__ __forceinline__ void gate_phase(char* lds, const GateP& P) {
     using M = GateMap;
     const bf16* __restrict__ convA = P.convA; const bf16* __restrict__ dzA = P.dzA; bf16* __restrict__ dadg = P.dadg;
@@ -399,6 +540,7 @@ __device__ __forceinline__ void gate_phase(char* lds, const GateP& P) {
     const int n = first < last ? (last - first + stride - 1) / stride : 0;     // this workgroup's tiles
     auto issue = [&](int tile, int buf) { gate_issue<HAS_DO, HAS_DZ>(lds, P, c, tile, buf); };
     constexpr int kStores = 2;                          // da and dg pieces per wave and tile
+    constexpr int kReqs = 2 + (HAS_DO ? 1 : 0) + (HAS_DZ ? 1 : 0);   // requests per wave of one gate_issue (none for a dead tile)
 
     // the first tile's operands are requested BEFORE this wave's weights (register-resident A operands) so that the two
     // round trips overlap; the weights are waited for here (left pending, the compiler's s_waitcnt vmcnt(0) would sit at their
@@ -425,6 +567,29 @@ __device__ __forceinline__ void gate_phase(char* lds, const GateP& P) {
         const int t0 = (tile - b * tiles_per_b) * kLT;
         if (full_prev) wait_vm<kStores>(); else wait_vm<0>();
         barrier();
+        f32x4 ya[2], yb[2], yc[2], yd[2];                  // filter, gate rows of the column's frame; linear: and of the next
+        float alpha = 0.f;
+        bool next_reqs = false;                            // issue(next) makes requests (there is a next tile and it is live)
+        if constexpr (MODE != kCondNone) {
+            // (a dead tile reads its rows too: no branch between a request and the tie behind its wait -- a value that meets
+            // another at a join is COPIED there, and a copy ahead of the wait reads a register the load has not written yet)
+            {
+                const RowAt ra = row_at<MODE>(P.R, b, t0, t0 + j < T ? j : T - 1 - t0, 16 * w + 4 * h);
+                alpha = ra.alpha;
+                ya[0] = row_ld16<0>(ra.pf); ya[1] = row_ld16<32>(ra.pf);
+                yb[0] = row_ld16<0>(ra.pg); yb[1] = row_ld16<32>(ra.pg);
+                if constexpr (MODE == kCondLinear) {
+                    const float* pf1 = ra.pf + P.R.fr.stride;
+                    const float* pg1 = ra.pg + P.R.fr.stride;
+                    yc[0] = row_ld16<0>(pf1); yc[1] = row_ld16<32>(pf1);
+                    yd[0] = row_ld16<0>(pg1); yd[1] = row_ld16<32>(pg1);
+                }
+            }
+            if (tile + stride < last) {
+                const int nt = tile + stride;
+                next_reqs = (nt - (nt / tiles_per_b) * tiles_per_b) * kLT + kLT > t_live;
+            }
+        }
         if (tile + stride < last) issue(tile + stride, buf ^ 1);
         if (t0 + kLT <= t_live) {                          // dead tile (workgroup-uniform)
             if (t0 + kLT <= P.t_zero) {                    // ... that nobody reads: not touched
@@ -489,6 +654,24 @@ __device__ __forceinline__ void gate_phase(char* lds, const GateP& P) {
         }
         // ---- gate forward + backward, elementwise ----
         const bool live = t >= Z && t < T;
+        if constexpr (MODE != kCondNone) {
+            if (next_reqs) wait_vm<kReqs>(); else wait_vm<0>();      // issue(next)'s requests may stay in flight: the rows are older
+            rows_tie(ya); rows_tie(yb);
+            if constexpr (MODE == kCondLinear) {
+                rows_tie(yc); rows_tie(yd);
+#pragma unroll
+                for (int q = 0; q < 2; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        ya[q][e] = wn::bias_lerp(ya[q][e], yc[q][e], alpha);
+                        yb[q][e] = wn::bias_lerp(yb[q][e], yd[q][e], alpha);
+                    }
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { acc[4 * q + e] += ya[q][e]; acc[8 + 4 * q + e] += yb[q][e]; }
+        }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             float da[4], dg[4];
@@ -522,14 +705,14 @@ __device__ __forceinline__ void gate_phase(char* lds, const GateP& P) {
     }
 }
 
-template <bool HAS_DO, bool HAS_DZ>
+template <bool HAS_DO, bool HAS_DZ, int MODE>
 __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void k16_gate_bwd(
     const bf16* __restrict__ x, const bf16* __restrict__ convA, const bf16* __restrict__ dzA,
     const bf16* __restrict__ dout, const bf16* __restrict__ dzs, int dz_t0, bf16* __restrict__ dadg, int B, int T, int d,
-    int Z, int tiles_per_b, int ntiles, int t_live, int t_zero) {
+    int Z, int tiles_per_b, int ntiles, int t_live, int t_zero, const LayerRows R) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
-    const GateP P{x, convA, dzA, dout, dzs, dz_t0, dadg, B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero};
-    gate_phase<HAS_DO, HAS_DZ>(lds, P);
+    const GateP P{x, convA, dzA, dout, dzs, dz_t0, dadg, B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero, R};
+    gate_phase<HAS_DO, HAS_DZ, MODE>(lds, P);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -716,6 +899,83 @@ __global__ void k16_reduce_parts(const float* __restrict__ part, long long layer
 }
 
 // ---------------------------------------------------------------------------------------------
+// gate-row gradients (conditioning): the column sums of the retained [da | dg] of EVERY layer in one launch, a gather per
+// output row.  Workgroup (row j, chunk c; layer; clip), 128 threads, two of the 256 columns each: the positions of the row's
+// range -- [0, T) with one row per clip, frame j, or frames j - 1 and j with interpolation -- are cut into chunks of kRowChunk from
+// the range's first position on, a thread adds its chunk in ascending t (fp32, fma with the weight).  One chunk per row: the
+// sum is added to the gradient row at once.  More: the chunks' sums go to the workspace and k16_row_grads_reduce adds them in
+// chunk order.  Rows below lo[l] (unwritten memory below the layer's zero bound, the zero prefix) are not read.
+// ---------------------------------------------------------------------------------------------
+struct RowGradArgs { float* dbf[kMaxProb16]; float* dbg[kMaxProb16]; int lo[kMaxProb16]; };
+
+__device__ __forceinline__ float* row_grad_out(const LayerRows& R, const RowGradArgs& A, int l, int b, int row, int col) {
+    float* o = col < 128 ? A.dbf[l] : A.dbg[l];
+    return o + (long long)b * R.clip_stride + (long long)row * R.fr.stride + (col & 127);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(128) void k16_row_grads(const bf16* __restrict__ dadg, const LayerRows R, const RowGradArgs A,
+                                                     int B, int T, int nrows, int nch, float* __restrict__ part) {
+    const int l = blockIdx.y, b = blockIdx.z;
+    const int row = blockIdx.x / nch, c = blockIdx.x - row * nch;
+    const long long hop = R.fr.hop;
+    const int ph = MODE >= kCondFrame ? wn::frame_phase(R.fr, b) : 0;
+    long long a = 0, e = T, mid = 0;                    // the row's range [a, e); linear: frame j - 1 below mid, frame j from it on
+    if (MODE == kCondFrame) { a = row * hop - ph; e = a + hop; }
+    if (MODE == kCondLinear) { mid = row * hop - ph; a = mid - hop; e = mid + hop; }
+    if (a < 0) a = 0;
+    if (e > T) e = T;
+    long long t = a + (long long)c * kRowChunk;
+    const long long hi = t + kRowChunk < e ? t + kRowChunk : e;
+    if (t < A.lo[l]) t = A.lo[l];
+    const bf16x2* src = reinterpret_cast<const bf16x2*>(dadg) + ((long long)l * B + b) * T * 128 + threadIdx.x;
+    auto weight = [&](long long tt) {                  // 1 - alpha_t in frame j, alpha_t in frame j - 1 (wn::bias_frame_alpha's value)
+        if (MODE != kCondLinear) return 1.f;
+        const float al = wn::bias_alpha((int)(tt < mid ? tt - (mid - hop) : tt - mid), R.fr.hop);
+        return tt < mid ? al : __fsub_rn(1.f, al);
+    };
+    float s0 = 0.f, s1 = 0.f;
+    for (; t + 8 <= hi; t += 8) {
+        bf16x2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(t + u) * 128];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float wt = weight(t + u);
+            s0 = __fmaf_rn(wt, (float)v[u][0], s0);
+            s1 = __fmaf_rn(wt, (float)v[u][1], s1);
+        }
+    }
+    for (; t < hi; ++t) {
+        const bf16x2 v = src[t * 128];
+        const float wt = weight(t);
+        s0 = __fmaf_rn(wt, (float)v[0], s0);
+        s1 = __fmaf_rn(wt, (float)v[1], s1);
+    }
+    const int col = 2 * threadIdx.x;
+    if (nch == 1) {
+        float* o = row_grad_out(R, A, l, b, row, col);
+        o[0] += s0;
+        o[1] += s1;
+    } else {
+        float* o = part + ((((long long)l * B + b) * nrows + row) * nch + c) * 256 + col;
+        o[0] = s0;
+        o[1] = s1;
+    }
+}
+
+__global__ __launch_bounds__(128) void k16_row_grads_reduce(const float* __restrict__ part, const LayerRows R, const RowGradArgs A,
+                                                            int B, int nrows, int nch) {
+    const int l = blockIdx.y, b = blockIdx.z, row = blockIdx.x, col = 2 * threadIdx.x;
+    const float* p = part + (((long long)l * B + b) * nrows + row) * nch * 256 + col;
+    float s0 = p[0], s1 = p[1];
+    for (int c = 1; c < nch; ++c) { s0 += p[(long long)c * 256]; s1 += p[(long long)c * 256 + 1]; }
+    float* o = row_grad_out(R, A, l, b, row, col);
+    o[0] += s0;
+    o[1] += s1;
+}
+
+// ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
 static int grid_for(int ntiles, int per_cu) {
@@ -724,33 +984,92 @@ static int grid_for(int ntiles, int per_cu) {
     return g;
 }
 
-int fwd_layer(const bf16* x, const bf16* img, bf16* out, bf16* z, int B, int T, int d, int Z, hipStream_t s) {
+int fwd_layer(const bf16* x, const bf16* img, bf16* out, bf16* z, int B, int T, int d, int Z, const LayerRows& R,
+              hipStream_t s) {
     const int tiles_per_b = (T + kLT - 1) / kLT;
     const int ntiles = B * tiles_per_b;
-    WN_MAX_LDS_ONCE(kFwdLds, k16_fwd);
-    hipLaunchKernelGGL(k16_fwd, dim3(grid_for(ntiles, 2)), dim3(256), kFwdLds, s, x, img, img + kConvA, out, z, B, T, d, Z,
-                       tiles_per_b, ntiles);
+#define FWD_LAUNCH(MODE)                                                                                               \
+    do {                                                                                                               \
+        WN_MAX_LDS_ONCE(kFwdLds, k16_fwd<MODE>);                                                                       \
+        hipLaunchKernelGGL(k16_fwd<MODE>, dim3(grid_for(ntiles, 2)), dim3(256), kFwdLds, s, x, img, img + kConvA, out, \
+                           z, B, T, d, Z, tiles_per_b, ntiles, R);                                                     \
+    } while (0)
+    switch (R.mode) {
+        case kCondNone: FWD_LAUNCH(kCondNone); break;
+        case kCondClip: FWD_LAUNCH(kCondClip); break;
+        case kCondFrame: FWD_LAUNCH(kCondFrame); break;
+        case kCondLinear: FWD_LAUNCH(kCondLinear); break;
+        default: wn::set_error("fwd_layer: unknown row mode %d", R.mode); return WN_EARG;
+    }
+#undef FWD_LAUNCH
     WN_LAUNCH_CHECK();
     return WN_OK;
 }
 
 int gate_bwd_layer(const bf16* x, const bf16* img, const bf16* dout, const bf16* dzs, int dz_t0, bf16* dadg, int B, int T,
-                   int d, int Z, int t_live, int t_zero, hipStream_t s) {
+                   int d, int Z, int t_live, int t_zero, const LayerRows& R, hipStream_t s) {
     const int tiles_per_b = (T + kLT - 1) / kLT;
     const int ntiles = B * tiles_per_b;
     const int grid = grid_for(ntiles, 1);
-#define GB_LAUNCH(DO, DZ)                                                                                              \
+#define GB_LAUNCH_M(DO, DZ, MODE)                                                                                      \
     do {                                                                                                               \
-        WN_MAX_LDS_ONCE(kGateLds, k16_gate_bwd<DO, DZ>);                                                               \
-        hipLaunchKernelGGL((k16_gate_bwd<DO, DZ>), dim3(grid), dim3(512), kGateLds, s, x, img + kOffConvA8,           \
-                           img + kOffDzA8, dout, dzs, dz_t0, dadg, B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero);  \
+        WN_MAX_LDS_ONCE(kGateLds, k16_gate_bwd<DO, DZ, MODE>);                                                         \
+        hipLaunchKernelGGL((k16_gate_bwd<DO, DZ, MODE>), dim3(grid), dim3(512), kGateLds, s, x, img + kOffConvA8,     \
+                           img + kOffDzA8, dout, dzs, dz_t0, dadg, B, T, d, Z, tiles_per_b, ntiles, t_live, t_zero, R); \
     } while (0)
-    if (dout && dzs) GB_LAUNCH(true, true);
-    else if (dout) GB_LAUNCH(true, false);
-    else if (dzs) GB_LAUNCH(false, true);
+#define GB_LAUNCH(DO, DZ)                                                                                              \
+    switch (R.mode) {                                                                                                  \
+        case kCondNone: GB_LAUNCH_M(DO, DZ, kCondNone); break;                                                         \
+        case kCondClip: GB_LAUNCH_M(DO, DZ, kCondClip); break;                                                         \
+        case kCondFrame: GB_LAUNCH_M(DO, DZ, kCondFrame); break;                                                       \
+        case kCondLinear: GB_LAUNCH_M(DO, DZ, kCondLinear); break;                                                     \
+        default: wn::set_error("gate_bwd_layer: unknown row mode %d", R.mode); return WN_EARG;                         \
+    }
+    if (dout && dzs) { GB_LAUNCH(true, true); }
+    else if (dout) { GB_LAUNCH(true, false); }
+    else if (dzs) { GB_LAUNCH(false, true); }
     else { wn::set_error("gate_bwd_layer: no incoming gradient"); return WN_EARG; }
 #undef GB_LAUNCH
+#undef GB_LAUNCH_M
     WN_LAUNCH_CHECK();
+    return WN_OK;
+}
+
+// rows of a clip's block and chunks per row of the row-gradient launch
+static void row_grad_geometry(const LayerRows& R, int T, long long& nrows, long long& nch) {
+    nrows = R.mode >= kCondFrame ? R.fr.rows(T) : 1;
+    long long span = R.mode == kCondFrame ? R.fr.hop : R.mode == kCondLinear ? 2ll * R.fr.hop : T;
+    if (span > T) span = T;
+    nch = (span + kRowChunk - 1) / kRowChunk;
+}
+
+size_t row_grad_ws_bytes(const LayerRows& R, int L, int B, int T) {
+    if (R.mode == kCondNone) return 0;
+    long long nrows, nch;
+    row_grad_geometry(R, T, nrows, nch);
+    return nch > 1 ? (size_t)L * B * nrows * nch * 256 * sizeof(float) : 0;
+}
+
+int row_grads(const bf16* dadg, const LayerRows& R, float* const* dbf, float* const* dbg, const int* lo, int L, int B, int T,
+              float* part, hipStream_t s) {
+    if (L > kMaxProb16) { wn::set_error("w16: more than %d layers", kMaxProb16); return WN_ESHAPE; }
+    long long nrows, nch;
+    row_grad_geometry(R, T, nrows, nch);
+    if (nrows * nch > 2147483647ll || B > 65535) { wn::set_error("w16 row gradients: too many rows or clips for one launch"); return WN_ESHAPE; }
+    RowGradArgs a{};
+    for (int l = 0; l < L; ++l) { a.dbf[l] = dbf[l]; a.dbg[l] = dbg[l]; a.lo[l] = lo[l]; }
+    const dim3 grid((unsigned)(nrows * nch), L, B);
+    switch (R.mode) {
+        case kCondClip: hipLaunchKernelGGL(k16_row_grads<kCondClip>, grid, dim3(128), 0, s, dadg, R, a, B, T, (int)nrows, (int)nch, part); break;
+        case kCondFrame: hipLaunchKernelGGL(k16_row_grads<kCondFrame>, grid, dim3(128), 0, s, dadg, R, a, B, T, (int)nrows, (int)nch, part); break;
+        case kCondLinear: hipLaunchKernelGGL(k16_row_grads<kCondLinear>, grid, dim3(128), 0, s, dadg, R, a, B, T, (int)nrows, (int)nch, part); break;
+        default: wn::set_error("row_grads: unknown row mode %d", R.mode); return WN_EARG;
+    }
+    WN_LAUNCH_CHECK();
+    if (nch > 1) {
+        hipLaunchKernelGGL(k16_row_grads_reduce, dim3((unsigned)nrows, L, B), dim3(128), 0, s, part, R, a, B, (int)nrows, (int)nch);
+        WN_LAUNCH_CHECK();
+    }
     return WN_OK;
 }
 

@@ -34,9 +34,13 @@ enum { kCondNone = 0, kCondClip = 1, kCondFrame = 2, kCondLinear = 3 };
 // uniform over a wave (a tile, a workgroup) this is one scalar load.
 // frame_phase_as<TAB>: "has a table" as a compile-time mode, for a kernel whose scalar-phase instantiation must stay
 // the code it was (k_layer_fwd_h2_t1, which sits near its register limit); frame_phase decides at run time.
+// (the fence and alpha's formula stand alone as well: the bf16-storage tile loops, w16_layer.hip, read the table entry by an
+// explicit scalar load and have the position inside the frame at hand already -- they call these two, nothing is restated)
+__device__ __forceinline__ int bias_phase_fence(int v, int hop) { return (int)((unsigned)v % (unsigned)hop); }
+__device__ __forceinline__ float bias_alpha(int rem, int hop) { return __fdiv_rn((float)rem, (float)hop); }   // rem = p % hop
 template <bool TAB>
 __device__ __forceinline__ int frame_phase_as(const BiasFrames& fr, int b) {
-    return TAB ? (int)((unsigned)fr.tab[b] % (unsigned)fr.hop) : fr.phase;
+    return TAB ? bias_phase_fence(fr.tab[b], fr.hop) : fr.phase;
 }
 __device__ __forceinline__ int frame_phase(const BiasFrames& fr, int b) {
     return fr.tab ? frame_phase_as<true>(fr, b) : frame_phase_as<false>(fr, b);
@@ -48,7 +52,7 @@ __device__ __forceinline__ long long bias_frame_off(const BiasFrames& fr, int ph
 // the weight of row j + 1 at position t (fr.hop > 0): float(p % hop) / float(hop), an IEEE fp32 division
 __device__ __forceinline__ float bias_frame_alpha(const BiasFrames& fr, int ph, int t) {
     const int p = t + ph;
-    return __fdiv_rn((float)(p - (p / fr.hop) * fr.hop), (float)fr.hop);
+    return bias_alpha(p - (p / fr.hop) * fr.hop, fr.hop);
 }
 __device__ __forceinline__ float bias_lerp(float a, float b, float alpha) {      // a + alpha (b - a), never contracted
     return __fadd_rn(a, __fmul_rn(alpha, __fsub_rn(b, a)));

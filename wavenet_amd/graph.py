@@ -140,7 +140,8 @@ class TrainStepGraph(object):
         opt, p = self.net.optimizer, self.net.params
         return tuple(getattr(opt, k, None) for k in ("beta1", "beta2", "beta3", "eps", "hyper")) + \
             (p.gradient_clipping, p.weight_decay, self.net.gemm_precision or _lib.get_gemm_precision(),
-             self.net.ema_enabled)              # ... and whether the averaging launch is among the captured nodes
+             self.net.ema_enabled,              # ... and whether the averaging launch is among the captured nodes
+             self.net.storage)                  # ... and which kernels were captured at all (WaveNet.set_storage)
 
     def _fwd_bwd(self):
         if getattr(self, "_use_plan", False) and self._planned:

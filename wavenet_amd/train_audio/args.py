@@ -68,6 +68,12 @@ _LOCAL_FLAGS = (
                                        "divides the hop; the network then runs at hop / U); stored in local.json when U > 1, "
                                        "which generate and evaluate follow"),
 )
+# activation storage of the run (WaveNet.set_storage): fp32, and an attribute of the namespace only when given
+_STORAGE_FLAGS = (
+    (("--storage",), str, "fp32", "train, evaluate: activation storage, 'fp32' or 'bf16' (bfloat16 activations with fp32 accumulation "
+                                  "on the 128-channel kernels; conditioned models included).  A property of the run, not of the "
+                                  "checkpoint: weights, optimiser state and checkpoints are fp32 either way"),
+)
 # likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
 # attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
 _LIKELIHOOD_FLAGS = (
@@ -115,6 +121,7 @@ class Args(argparse.Namespace):
     speaker_prefix, condition_channels, speaker = False, None, None
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
     local_upsample = None
+    storage = "fp32"
     report, best_of = None, 1
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
@@ -127,7 +134,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
@@ -195,6 +202,8 @@ def parse(argv=None):
         ap.error("--local-crop {frame,sample} goes with --local-dir")
     if args.local_upsample is not None and (args.local_dir is None or args.local_upsample < 1):
         ap.error("--local-upsample U goes with --local-dir and needs U >= 1")
+    if args.storage not in ("fp32", "bf16"):
+        ap.error("--storage {fp32,bf16}, got %r" % (args.storage,))
     if args.local and args.local_dir is not None:
         ap.error("--local-dir FEAT_DIR (every feature file of a directory) and --local FILE.npy exclude each other")
     if args.local:

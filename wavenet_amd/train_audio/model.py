@@ -110,4 +110,5 @@ def build(args, train: bool = False):
         raise Exception("--gpu_device -1 (CPU) is not supported: this engine runs on a HIP device only")
     torch.cuda.set_device(args.gpu_device)
     net.to_gpu(args.gpu_device)
+    net.set_storage(getattr(args, "storage", "fp32"))      # --storage: how the model runs, nothing of it is in the checkpoint
     return params, net

@@ -410,9 +410,9 @@ class GateBiasRows(object):
         bg = (C.c_void_p * len(offsets))(*[p0 + 4 * og for _, og in offsets])
         return bf, bg
 
-    def call(self, B, T):
-        """(descriptor, WnExec, what must stay alive) of a forward or backward call on these rows: a copy of the model's stack
-        descriptor whose bf / bg tables point into the block, and the call's WN_EXEC_BIAS_PER_CLIP context."""
+    def _descriptor(self):
+        """(d, bf, bg): a copy of the model's stack descriptor whose bf / bg tables point into the block, with the frames'
+        geometry filled in."""
         net = self.net
         net._stack_desc()
         d = _lib.WnStackDesc()
@@ -429,8 +429,29 @@ class GateBiasRows(object):
             d.bias_hop, d.bias_frame_stride, d.bias_interp = self.hop, net._cond_rows, self.interp
             d.bias_phase = 0 if tab is not None else int(self.phase)
             d.bias_phase_tab = None if tab is None else tab.tab.data_ptr()
-        ex = net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=self.clip_stride)
+        return d, bf, bg
+
+    def call(self, B, T):
+        """(descriptor, WnExec, what must stay alive) of a forward or backward call on these rows: the descriptor of
+        ``_descriptor`` and the call's WN_EXEC_BIAS_PER_CLIP context."""
+        d, bf, bg = self._descriptor()
+        ex = self.net._exec(B, T, _lib.WN_EXEC_BIAS_PER_CLIP, bias_stride=self.clip_stride)
         return C.byref(d), ex, (d, bf, bg)
+
+    def call16(self, B, T):
+        """(descriptor, what must stay alive) of a bf16-storage call on these rows.  The wn16_* calls take no WnExec: the
+        descriptor alone says that there are rows (bf / bg and a row stride, also with one row per clip) and how they are
+        addressed, and there is no field for a clip stride -- clip blocks are dense, so a block of frames holds exactly the
+        rows the call needs (``forward_residual_block`` trims)."""
+        keep = self._descriptor()
+        d = keep[0]
+        d.bias_frame_stride = self.net._cond_rows
+        if self.hop:
+            need = frames_needed(T, self.hop, self.worst_phase, LOCAL_INTERP[self.interp])
+            if int(self.block.shape[1]) != need:
+                raise _lib.WaveNetHipError("bf16 storage takes dense clip blocks: the local conditioning block holds %d rows per "
+                                           "clip, the call reads %d" % (int(self.block.shape[1]), need))
+        return C.byref(d), keep
 
 
 def _one_phase(phase) -> bool:
@@ -639,14 +660,20 @@ class _Embed16Fn(_Fn):
 
 class _Stack16Fn(_Fn):
     """forward_residual_block in bf16 storage: one library call each way (wn16_stack_fwd / wn16_stack_bwd).  The forward
-    keeps every layer's output and z only; the backward recomputes tanh / sigmoid."""
+    keeps every layer's output and z only; the backward recomputes tanh / sigmoid.  ``cond`` / ``rows`` as in ``_StackFn``:
+    the conditioning block and its ``GateBiasRows``, handed to the library through the descriptor alone (the wn16_* calls
+    take no WnExec); the backward returns the block's gradient (``WN16_BWD_ROW_GRADS``)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, net, t_off, train):
+    def forward(ctx, x, anchor, net, t_off, train, cond=None, rows=None):
         ctx.set_materialize_grads(False)
         B, T, Cr = x.shape
         x = x.contiguous()
-        desc = net._stack_desc()
+        if rows is None:
+            desc = net._stack_desc()
+        else:
+            rows.check(B, T)
+            desc, ckeep = rows.call16(B, T)
         L = len(net._flat_layers)
         dev_ = x.device
         xs = torch.empty((L, B, T, Cr), device=dev_, dtype=torch.bfloat16)
@@ -656,6 +683,8 @@ class _Stack16Fn(_Fn):
                                         1 if net.compat_zero_prefix else 0, stream_ptr()), "wn16_stack_fwd")
         ctx.net, ctx.t_off, ctx.shape = net, t_off, (B, T, Cr)
         ctx.saved = (x, xs, z) if train else None
+        ctx.cond = cond if train else None
+        ctx.rows = rows
         net._last16 = (x, xs, z, skip)                               # (tests look at the intermediates)
         return xs[L - 1], skip
 
@@ -669,17 +698,28 @@ class _Stack16Fn(_Fn):
         lib = _lib.lib()
         desc = net._stack_desc()
         gt = net._grad_tables()
+        dcond, flags, dwf, dwg = None, 0, gt["wf"], gt["wg"]
+        if ctx.cond is not None:
+            # the gate-row gradients accumulate (+=) into a zeroed block: the gradient of the conditioning block.  dWf / dWg
+            # grow to 2 L entries: the weight gradients, then every layer's gradient row of (clip 0, frame 0)
+            dcond = torch.zeros_like(ctx.cond)
+            desc, ckeep = ctx.rows.call16(B, T)
+            dbf, dbg = ctx.rows.grad_tables(dcond)
+            nl = len(net._flat_layers)
+            dwf = (C.c_void_p * (2 * nl))(*([gt["wf"][l] for l in range(nl)] + [dbf[l] for l in range(nl)]))
+            dwg = (C.c_void_p * (2 * nl))(*([gt["wg"][l] for l in range(nl)] + [dbg[l] for l in range(nl)]))
+            flags = _lib.WN16_BWD_ROW_GRADS
         nbytes = lib.wn16_stack_bwd_workspace_bytes(desc, B, T, t_off)
         ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
         dout = None if dout is None else dout.contiguous()
         dskip = None if dskip is None else dskip.contiguous()
         dx = torch.empty((B, T, Cr), device=x.device, dtype=torch.bfloat16) if ctx.needs_input_grad[0] else None
         check(lib.wn16_stack_bwd(desc, ptr(net._pack16), ptr(x), ptr(xs), ptr(z), ptr(dout), ptr(dskip), ptr(dx),
-                                 gt["wf"], gt["wg"], gt["wp"], gt["ws"], ptr(ws), nbytes, B, T, t_off,
-                                 1 if net.compat_zero_prefix else 0, 0, stream_ptr()), "wn16_stack_bwd")
+                                 dwf, dwg, gt["wp"], gt["ws"], ptr(ws), nbytes, B, T, t_off,
+                                 1 if net.compat_zero_prefix else 0, flags, stream_ptr()), "wn16_stack_bwd")
         net._last16_ws = ws
-        ctx.saved = None
-        return dx, None, None, None, None
+        ctx.saved = ctx.cond = None
+        return dx, None, None, None, None, dcond, None
 
 
 class _Pointwise16Fn(_Fn):
@@ -939,7 +979,9 @@ class WaveNet(object):
             raise Exception("global conditioning needs condition_classes > 0 and condition_channels > 0 (or both 0: off), got "
                             "%d and %d" % (self.condition_classes, self.condition_channels))
         if self.condition_classes and storage == "bf16":
-            raise Exception("global conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases)")
+            raise Exception("global conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases) "
+                            "in the constructor: build the conditioned model at storage='fp32' and switch it with "
+                            "set_storage('bf16')")
         if self.condition_classes and not params.residual_conv_dilation_no_bias:
             raise Exception("global conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
                             "convolutions' bias; a second, shared one is not supported)")
@@ -948,7 +990,9 @@ class WaveNet(object):
             raise Exception("local conditioning needs local_channels > 0 and local_hop > 0 (or both 0: off), got %d and %d"
                             % (self.local_channels, self.local_hop))
         if self.local_channels and storage == "bf16":
-            raise Exception("local conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases)")
+            raise Exception("local conditioning is not available with storage='bf16' (the bf16-storage kernels take no gate biases) "
+                            "in the constructor: build the conditioned model at storage='fp32' and switch it with "
+                            "set_storage('bf16')")
         if self.local_channels and not params.residual_conv_dilation_no_bias:
             raise Exception("local conditioning needs residual_conv_dilation_no_bias = True (the conditioning term is the gate "
                             "convolutions' bias; a second, shared one is not supported)")
@@ -1225,6 +1269,18 @@ class WaveNet(object):
         check(_lib.lib().wn_plan_stats(self._plan, out), "wn_plan_stats")
         return dict(zip(("state", "weight_images", "layer_images", "plan_words", "device_bytes", "prepare_calls", "served", "not_served"),
                         [int(v) for v in out]))
+
+    def set_storage(self, storage: str):
+        """The activation storage of every later call: "fp32", or "bf16" (BASELINE config 5's kernels: bfloat16 activations,
+        fp32 accumulation).  A property of how the model RUNS, like ``set_gemm_precision``: weights, gradients, optimiser
+        state and checkpoints are fp32 either way, so it may be switched at any time, in both directions, and it is the way a
+        conditioned model (global, local, both) gets onto the bf16 kernels -- the constructor builds those at fp32 storage.  A
+        shape the bf16 kernels do not take fails at the first call, with the library's text.  The bf16 operand images are
+        repacked at the next call; a ``TrainStepGraph`` captured before the switch refuses to step."""
+        if storage not in ("fp32", "bf16"):
+            raise Exception("storage must be 'fp32' or 'bf16'")
+        self.storage = storage
+        self._w16_stale = True
 
     def _pack16_if_stale(self):
         """bf16 operand images of the current weights (one pack per optimiser step; captured with the step in a graph)."""
@@ -1737,14 +1793,20 @@ class WaveNet(object):
         rows = None
         if feats is not None:
             feats, hop, phase = self._stack_features(feats, phase, int(x.shape[3]))
-            cond = self._local_block(feats, cond).contiguous()
+            cond = self._local_block(feats, cond)
+            if self.storage == "bf16":
+                # the bf16 calls carry no clip stride: clip blocks are dense, surplus columns are trimmed (a slice autograd
+                # sees, so the gradient finds its way back)
+                worst = hop - 1 if isinstance(phase, LocalPhases) else int(phase)
+                cond = cond[:, :frames_needed(int(x.shape[3]), hop, worst, self.local_interp)]
+            cond = cond.contiguous()
             rows = GateBiasRows(self, cond, hop, phase, LOCAL_INTERP.index(self.local_interp))
         elif cond is not None:
             cond = cond.contiguous()
             rows = GateBiasRows(self, cond)
         if self.storage == "bf16":
             self._pack16_if_stale()
-            out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled())
+            out, skip = _Stack16Fn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled(), cond, rows)
             return _as_view(out), _as_view(skip)
         out, skip = _StackFn.apply(_to_btc(x), self._anchor, self, int(t_off), torch.is_grad_enabled(),
                                    bool(window_only), cond, rows)
