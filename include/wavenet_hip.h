@@ -556,8 +556,24 @@ int wn_decoder_run(void* handle, int32_t first_token, const double* uniforms, in
  * In the kernels the count is a word of the utterance's entry (read by all nine workgroups of its group; by its one workgroup
  * in the any-shape form); the batched kernels take NO launch-wide step count any more -- n remains the host-side bound of the
  * checks.  With every n_u == n a launch computes what it computed before.  same_weights != 0: an utterance 0 that ends first
- * leaves its packed weights in place, and the others keep reading them.  wn_decoder_status is unchanged. */
+ * leaves its packed weights in place, and the others keep reading them.  wn_decoder_status is unchanged.
+ * Utterance tiles.  The tile size is a property of a launch and travels in same_weights:
+ *   same_weights | any-shape handles                                          | nine-workgroup handles
+ *   0            | every utterance reads its own copy                         | every utterance reads its own copy
+ *   1            | the claim is checked, own copies are read                  | one copy (handle 0's)
+ *   2, 4, 8, 16  | workgroup g decodes utterances [gU, gU + U) of the launch  | treated as 1
+ *                | (the last tile may be short), all reading handle 0's copy  |
+ * Any other value is WN_EARG.  A tile shares handle 0's embedding, causal weights and biases, every layer's filter / gate and
+ * projection weights and projection biases, and the head; an utterance keeps its own rings, token ring, static gate biases
+ * (bf / bg: a class per utterance), frame table or ring with its phase, sampling controls, counters, uniforms and outputs --
+ * so utterances of different speakers, features, phases, controls, prompts and lengths share a tile, and each one's tokens and
+ * trace stay those of its own wn_decoder_run, bit for bit.  The claim is checked on a key of the weight pointers that leaves
+ * bf / bg out, and every handle's arena layout (which biases exist included) must equal handle 0's: WN_EARG naming the
+ * utterance.  A tile keeps U x (7 maxc + 16) floats in LDS, maxc the widest channel count of the model; a U beyond 150 KiB is
+ * WN_ESHAPE, the message naming the largest U that fits (never clamped).  The limit of WN_DECODER_BATCH_MAX_ANY utterances per
+ * launch and the agreement rules above are unchanged. */
 #define WN_DECODER_BATCH_MAX_ANY 1024      /* utterances per launch of the one-workgroup-per-utterance form */
+#define WN_DECODER_TILE_MAX 16             /* the largest tile: utterances per workgroup under same_weights = 2, 4, 8, 16 */
 /* the limit of the nine-workgroup form (28) */
 int wn_decoder_batch_max(void);
 int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms, int n,

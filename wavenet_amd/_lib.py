@@ -228,6 +228,7 @@ WN_DECODER_TRACE_CHOSEN = 256          # WnDecoderDesc.flags: prob_trace is one 
 WN_DECODER_FORCED_TOKENS = 512         # WnDecoderDesc.flags: out_tokens is read before it is written -- an entry in [0, Q) is emitted as given, anything else draws
 WN_DECODER_FRAME_RING = 1024           # WnDecoderDesc.flags: frame_bias is a ring of n_frames rows in the caller's memory, read in place (streaming)
 WN_DECODER_BATCH_MAX_ANY = 1024    # wn_decoder_run_batch on any-shape handles: utterances per launch (wn_decoder_batch_max(): the nine-workgroup form's)
+WN_DECODER_TILE_MAX = 16           # ... and the largest utterance tile: same_weights = 2, 4, 8, 16 utterances per workgroup, one copy of the weights
 
 
 def default_exec_flags() -> int:

@@ -71,6 +71,8 @@ struct Decoder {
     int step_limit = 0;
     unsigned long long src_key = 0;   // hash of the caller's weight POINTERS at the last pack: two handles packed from the same
                                       // model carry the same key (wn_decoder_run_batch's same_weights check)
+    unsigned long long tile_key = 0;  // ... the same hash without the gate-bias pointers: what a tile shares (same_weights >= 2 on
+                                      // any-shape handles; the static gate biases stay an utterance's own)
 };
 
 // the shape decoder_fast.hip is written for (BASELINE.json config 4 with the reference's default biases).  Gate biases
@@ -145,15 +147,7 @@ __global__ void k_load_tok_ring(const int32_t* __restrict__ tokens, int* __restr
 
 // ---- the step loop ---------------------------------------------------------------------------
 // (DecFrames, the frame table of one utterance as a step loop takes it: decoder_types.hpp)
-// One utterance as the any-shape kernels take it, from its own handle (any_utt): k_decode's arguments, and an entry of the
-// table k_decode_batch reads from device memory (Decoder::batch_tab of handle 0).
-struct DecAnyUtt {
-    const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
-    float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
-    int first_token; int nsteps;       // nsteps: the utterance's own step count (batched: min(n, steps left under its step_limit))
-    SampleCtl sc;
-    DecFrames fr;
-};
+// (DecAnyUtt, one utterance as the any-shape kernels take it: decoder_types.hpp)
 __device__ __forceinline__ int pmod(long long a, int D) {
     long long r = a % D;
     return (int)(r < 0 ? r + D : r);
@@ -170,7 +164,6 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
     return r;
 }
-
 // The step loop of one utterance on one workgroup: k_decode runs it for its handle, workgroup u of k_decode_batch for
 // utterance u.  Everything it touches -- arena, token ring, uniforms, outputs -- is the utterance's own; `sc` and the flags
 // are the same for every thread of the workgroup.
@@ -531,18 +524,21 @@ static int check_weight_ptrs(const Decoder* D, const WnDecoderDesc* d) {
 static int pack_weights(Decoder* D, const WnDecoderDesc* d, hipStream_t s) {
     const int T = 256;
     {   // FNV-1a over every weight / bias pointer of the description, in a fixed order
-        unsigned long long h = 1469598103934665603ull;
-        auto mix = [&](const void* p) { h = (h ^ (unsigned long long)(uintptr_t)p) * 1099511628211ull; };
+        // (h: src_key; t: tile_key, the same walk without the gate-bias pointers)
+        unsigned long long h = 1469598103934665603ull, t = h;
+        auto mix1 = [](unsigned long long& k, const void* p) { k = (k ^ (unsigned long long)(uintptr_t)p) * 1099511628211ull; };
+        auto mix = [&](const void* p) { mix1(h, p); mix1(t, p); };
         for (int i = 0; i < d->n_causal; ++i) { mix(d->causal_W[i]); mix(d->causal_b ? d->causal_b[i] : nullptr); }
         for (int j = 0; j < (int)D->layers.size(); ++j) {
             mix(d->Wf[j]); mix(d->Wg[j]); mix(d->Wp[j]); mix(d->Ws[j]);
             // (a WN_DECODER_GATE_ROWS handle keeps its gate biases out of the packed weights that same_weights shares: handles of
             // one model holding different classes' biases still carry one key)
-            if (!D->gate_rows) { mix(d->bf ? d->bf[j] : nullptr); mix(d->bg ? d->bg[j] : nullptr); }
+            if (!D->gate_rows) { mix1(h, d->bf ? d->bf[j] : nullptr); mix1(h, d->bg ? d->bg[j] : nullptr); }
             mix(d->bp ? d->bp[j] : nullptr); mix(d->bs ? d->bs[j] : nullptr);
         }
         for (int i = 0; i < d->n_head; ++i) { mix(d->head_W[i]); mix(d->head_b ? d->head_b[i] : nullptr); }
         D->src_key = h;
+        D->tile_key = t;
     }
     for (int i = 0; i < d->n_causal; ++i) {
         const DecCausal& L = D->causal[i];
@@ -655,6 +651,11 @@ static int lay_out(Decoder* D, const WnDecoderDesc* d) {
     WN_CHECK_SHAPE(D->lds_bytes <= 150 * 1024, "decoder: channel width %d too large", maxc);
     return WN_OK;
 }
+
+// dynamic LDS of a tile of U utterances: U x decode_steps' (7 maxc + 16) floats.  (k_decode_tile's own U slot records are
+// static LDS on top: 2.2 KB at U = 16, inside what the 150 KiB bound leaves of a CU's 160 KiB.)
+static size_t tile_lds(const Decoder* D, int U) { return (size_t)U * (7 * (size_t)D->meta.maxc + 16) * sizeof(float); }
+static constexpr size_t kDecLdsMax = 150 * 1024;
 
 }  // namespace wn
 
@@ -848,8 +849,9 @@ int wn_decoder_batch_max(void) { return kDecMaxBatch; }
 
 // the any-shape form of wn_decoder_run_batch, after every check: the utterances' table into handle 0's device buffer (one
 // async copy from its pinned image), then one launch of n_handles workgroups.  nsteps[u]: utterance u's own step count
+// tile = 0: one workgroup of k_decode_batch per utterance.  tile = U >= 2 (checked): ceil(n_handles / U) workgroups of k_decode_tile<U>
 static int run_batch_any(void* const* handles, int n_handles, const int32_t* first_tokens, const double* const* uniforms,
-                         const int* nsteps, int32_t* const* out_tokens, float* const* prob_traces, hipStream_t s) {
+                         const int* nsteps, int32_t* const* out_tokens, float* const* prob_traces, int tile, hipStream_t s) {
     Decoder* D0 = (Decoder*)handles[0];
     if (n_handles > D0->batch_cap) {                   // first use, or a larger batch than ever before
         if (D0->batch_tab) { WN_HIP(hipFree(D0->batch_tab)); D0->batch_tab = nullptr; }      // hipFree waits for its readers
@@ -874,6 +876,9 @@ static int run_batch_any(void* const* handles, int n_handles, const int32_t* fir
     WN_HIP(hipMemcpyAsync(D0->batch_tab, img, (size_t)n_handles * sizeof(DecAnyUtt), hipMemcpyHostToDevice, s));
     WN_HIP(hipEventRecord(D0->batch_copied, s));
     const bool ring = D0->frame_ring && D0->frames.n > 0;                         // (the handles agree on all three modes)
+    if (tile)
+        return decode_tile_launch(tile, lerp_table(D0), D0->forced, ring, D0->meta, (const DecAnyUtt*)D0->batch_tab, n_handles,
+                                  trace_stride(D0), tile_lds(D0, tile), s);
     const auto kern = ring ? (D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true, true> : k_decode_batch<false, true, true>)
                                          : (lerp_table(D0) ? k_decode_batch<true, false, true> : k_decode_batch<false, false, true>))
                            : (D0->forced ? (lerp_table(D0) ? k_decode_batch<true, true, false> : k_decode_batch<false, true, false>)
@@ -906,8 +911,25 @@ static int same_model(const Decoder* D, const Decoder* D0, int u, int same_weigh
     // same_weights = 1 reads ONE copy of the packed weights (handle 0's) for every utterance: only sound when every
     // handle was packed from the same model -- the same weight pointers at its last create / update_weights.  (The
     // any-shape form checks the claim and then reads each utterance's own copy all the same.)
-    WN_CHECK_ARG(!same_weights || D->src_key == D0->src_key,
+    const bool tile = same_weights >= 2 && !D0->fastP;
+    WN_CHECK_ARG(!same_weights || tile || D->src_key == D0->src_key,
                  "wn_decoder_run_batch: same_weights = 1 but utterance %d's handle was packed from other weights than utterance 0's", u);
+    if (!tile) return WN_OK;
+    // a tile really reads handle 0's copy for every utterance but the static gate biases: the key without the gate-bias
+    // pointers, and handle 0's arena layout offset for offset (whether a bias exists is part of the layout)
+    WN_CHECK_ARG(D->tile_key == D0->tile_key, "wn_decoder_run_batch: same_weights = %d (a tile size) but utterance %d's handle was packed "
+                 "from other weights than utterance 0's (gate biases apart)", same_weights, u);
+    bool eq = true;
+    for (size_t i = 0; i < D->causal.size(); ++i)
+        eq = eq && D->causal[i].w == D0->causal[i].w && D->causal[i].b == D0->causal[i].b && D->causal[i].ring == D0->causal[i].ring;
+    for (size_t l = 0; l < D->layers.size(); ++l) {
+        const DecLayer &a = D->layers[l], &b = D0->layers[l];
+        eq = eq && a.wfg == b.wfg && a.bfg == b.bfg && a.wps == b.wps && a.bps == b.bps && a.ring == b.ring;
+    }
+    for (size_t i = 0; i < D->heads.size(); ++i) eq = eq && D->heads[i].w == D0->heads[i].w && D->heads[i].b == D0->heads[i].b;
+    WN_CHECK_ARG(eq, "wn_decoder_run_batch: same_weights = %d (a tile size) but the arena layout of utterance %d's handle differs from "
+                 "utterance 0's (a bias one was created with and the other without): a tile reads every utterance at handle 0's offsets",
+                 same_weights, u);
     return WN_OK;
 }
 
@@ -936,6 +958,18 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     const int limit = any ? WN_DECODER_BATCH_MAX_ANY : kDecMaxBatch;
     WN_CHECK_SHAPE(n_handles <= limit, "wn_decoder_run_batch: at most %d utterances per launch of %s decoders", limit,
                    any ? "any-shape" : "nine-workgroup");
+    WN_CHECK_ARG(same_weights == 0 || same_weights == 1 || same_weights == 2 || same_weights == 4 || same_weights == 8 ||
+                     same_weights == WN_DECODER_TILE_MAX,
+                 "wn_decoder_run_batch: same_weights = %d is neither 0, 1 nor a tile size (2, 4, 8, %d)", same_weights, WN_DECODER_TILE_MAX);
+    // a tile size on any-shape handles: U utterances per workgroup, one copy of the weights (nine-workgroup handles: as 1)
+    const int tile = any && same_weights >= 2 ? same_weights : 0;
+    if (tile && tile_lds(D0, tile) > kDecLdsMax) {
+        int fit = 1;
+        for (int U = 2; U <= WN_DECODER_TILE_MAX; U *= 2)
+            if (tile_lds(D0, U) <= kDecLdsMax) fit = U;
+        WN_CHECK_SHAPE(false, "wn_decoder_run_batch: a tile of %d utterances needs %zu bytes of LDS (%d x (7 x %d + 16) floats), more than "
+                       "%zu: the largest tile that fits this model is %d", tile, tile_lds(D0, tile), tile, D0->meta.maxc, kDecLdsMax, fit);
+    }
     DecUtt utt[kDecMaxBatch];
     int nu[WN_DECODER_BATCH_MAX_ANY];              // the utterances' own step counts
     bool gate = false;                             // nine-workgroup form: some utterance has gate rows to add
@@ -974,7 +1008,7 @@ int wn_decoder_run_batch(void* const* handles, int n_handles, const int32_t* fir
     }
     WN_CHECK_SHAPE(any || decode_fast_batch_ok(D0->meta.nlayers, n_handles, n),
                    "wn_decoder_run_batch: %d utterances x 9 workgroups must all be resident on the device, and n >= 2", n_handles);
-    const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, as_stream(stream))
+    const int rc = any ? run_batch_any(handles, n_handles, first_tokens, uniforms, nu, out_tokens, prob_traces, tile, as_stream(stream))
                        : decode_fast_launch_batch(n_handles, utt, D0->meta.nlayers, n, trace_stride(D0), sample_mode(D0), D0->meta.head_act, same_weights != 0,
                                                   gate, as_stream(stream));
     if (rc) return rc;

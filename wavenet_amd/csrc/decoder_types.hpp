@@ -37,6 +37,15 @@ struct DecUtt {
     SampleCtl sc;                      // per utterance: its handle's wn_decoder_set_sampling
     DecFrames fr;                      // WN_DECODER_GATE_ROWS handles: the utterance's own frame table (tab == NULL: none)
 };
+// One utterance as the any-shape kernels take it, from its own handle (any_utt): k_decode's arguments, and an entry of the
+// table k_decode_batch and k_decode_tile (decoder_tile.hip) read from device memory (Decoder::batch_tab of handle 0).
+struct DecAnyUtt {
+    const DecCausal* causal; const DecLayer* layers; const DecHead* heads;
+    float* arena; int* tok_ring; long long n0; const double* uniforms; int32_t* out_tokens; float* prob_out;
+    int first_token; int nsteps;       // nsteps: the utterance's own step count (batched: min(n, steps left under its step_limit))
+    SampleCtl sc;
+    DecFrames fr;
+};
 size_t decode_fast_pack_floats(int nlayers);
 int decode_fast_pack(const WnDecoderDesc* d, float* dst, hipStream_t s);
 // gate_rows (both launches): a WN_DECODER_GATE_ROWS handle that holds static gate biases (its own arena, DecLayer.bfg) or a frame
@@ -51,4 +60,8 @@ int decode_fast_batch_ok(int nlayers, int n_utt, int nsteps);
 int decode_fast_launch_batch(int n_utt, const DecUtt* utt, int nlayers, int nsteps, int prob_stride, int do_sample, int head_act,
                              bool same_weights, bool gate_rows, hipStream_t s);
 int decode_fast_status(const float* P, int nlayers, hipStream_t s, int* gave_up);
+// decoder_tile.hip: one launch of k_decode_tile<U, LERP, FORCED, RING> over the n_utt entries of `tab` (device memory), ceil(n_utt / U)
+// workgroups with `lds` bytes of dynamic LDS each; U in {2, 4, 8, 16} (checked by the caller)
+int decode_tile_launch(int U, bool lerp, bool forced, bool ring, const DecMeta& M, const DecAnyUtt* tab, int n_utt, int prob_stride,
+                       size_t lds, hipStream_t s);
 }  // namespace wn

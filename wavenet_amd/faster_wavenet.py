@@ -55,6 +55,52 @@ def deal_launches(lengths, limit, longest_first=True):
     return launches if longest_first else [(n, sorted(idx)) for n, idx in launches]
 
 
+TILE_SIZES = (2, 4, 8, 16)             # wn_decoder_run_batch's same_weights values that are tile sizes (up to WN_DECODER_TILE_MAX)
+_TILE_LDS_BYTES = 150 * 1024           # the library's bound on a decode workgroup's LDS (csrc/decoder.hip)
+
+
+def tile_lds_bytes(params, U):
+    """LDS of a tile of ``U`` utterances, as the library counts it: U x (7 maxc + 16) floats, maxc the widest channel count
+    of the model (Q, causal, dilated and head channels)."""
+    maxc = max([int(params.quantization_steps)] + [int(c) for c in params.causal_conv_channels] +
+               [int(c) for c in params.residual_conv_channels] + [int(c) for c in params.softmax_conv_channels])
+    return int(U) * (7 * maxc + 16) * 4
+
+
+def tile_fit(params):
+    """The largest U in {1, 2, 4, 8, 16} whose tile fits the LDS bound: the host's restatement of the rule
+    ``wn_decoder_run_batch`` refuses a tile by (``WN_ESHAPE``).  1: this model decodes one utterance per workgroup only."""
+    return max([1] + [U for U in TILE_SIZES if tile_lds_bytes(params, U) <= _TILE_LDS_BYTES])
+
+
+def pick_tile(n_utterances, n_cu, fit):
+    """``tile="auto"``: the tile size of a launch of ``n_utterances`` on a device of ``n_cu`` compute units for a model whose
+    ``tile_fit`` is ``fit``; 0 = off.  A pure function.  The rule is read off profiles/tiled_decode.json (DESIGN "Decoding in
+    utterance tiles"): on both measured shapes and at every measured N from 16 to 1,024 -- 8 to 512 workgroups on 256 CUs --
+    U = 2 was the fastest by far and every larger U slower than it, because a step of ``k_decode_tile`` costs more the more slots
+    a workgroup holds while a launch of at most 1,024 utterances never runs out of CUs.  So: 2 wherever a tile applies.  The
+    starting rule -- the largest fitting U with ceil(N / U) >= n_cu -- picked off or 4 where 2 was 2 to 15 times faster.
+    ``n_cu`` stays an argument: a rule for launches that outnumber what the device holds would need it."""
+    return 2 if int(n_utterances) >= 2 and int(fit) >= 2 and int(n_cu) >= 1 else 0
+
+
+def check_tile(tile, params=None, what="generate_batch"):
+    """``tile=`` as ``generate_batch`` / ``open_stream`` take it -> 0 (off), a tile size or ``"auto"``.  Raises ``ValueError`` for
+    anything else and, given ``params``, for a U that does not fit the model -- naming ``tile_fit``'s value --, all without a
+    device."""
+    if isinstance(tile, str):
+        if tile != "auto":
+            raise ValueError("%s: tile= takes 0 / 1 (off), 2, 4, 8, 16 or \"auto\", got %r" % (what, tile))
+        return "auto"
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or int(tile) not in (0, 1) + TILE_SIZES:
+        raise ValueError("%s: tile= takes 0 / 1 (off), 2, 4, 8, 16 or \"auto\", got %r" % (what, tile))
+    U = 0 if int(tile) < 2 else int(tile)
+    if U and params is not None and U > tile_fit(params):
+        raise ValueError("%s: tile=%d does not fit this model: a tile keeps %d bytes in LDS, the bound is %d; the largest tile that "
+                         "fits (tile_fit) is %d" % (what, U, tile_lds_bytes(params, U), _TILE_LDS_BYTES, tile_fit(params)))
+    return U
+
+
 StreamFrames = collections.namedtuple("StreamFrames", "steps current reads min_ring")
 
 
@@ -167,6 +213,7 @@ _Utterance.__new__.__defaults__ = (None,)
 class FasterWaveNet(WaveNet):
     fast_head_activation = "elu"       # faster_wavenet.py:108 (the normal head is ReLU, wavenet.py:588)
     batch_longest_first = True         # generate_batch: a launch's handles longest first (deal_launches; False: caller's order)
+    batch_tile = 0                     # generate_batch / open_stream without tile=: 0 (off), 2, 4, 8, 16 or "auto" (pick_tile)
 
     def __init__(self, params, compat_zero_prefix: bool = True, seed: Optional[int] = None, storage: str = "fp32",
                  condition_classes: int = 0, condition_channels: int = 0, local_channels: int = 0, local_hop: int = 0,
@@ -558,6 +605,17 @@ class FasterWaveNet(WaveNet):
                 all(int(c) == 32 for c in p.residual_conv_channels) and self.causal_conv_layers[0].bshape is None and
                 all(k.bshape is None for l in L for k in (l.wf, l.wg, l.projection_block, l.projection_softmax)))
 
+    def _launch_tile(self, tile, n_launch_utterances, nine):
+        """``same_weights`` of one any-shape launch from a checked ``tile`` (``check_tile``), or None where tiles do not apply --
+        config 4's shape, ``WAVENET_HIP_BATCH_OWN_WEIGHTS=1``, a single utterance, tile off -- and the call passes what it
+        always passed."""
+        if nine or not tile or n_launch_utterances < 2 or os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") == "1":
+            return None
+        if tile == "auto":
+            n_cu = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
+            tile = pick_tile(n_launch_utterances, n_cu, tile_fit(self.params))
+        return tile or None
+
     def _batch_prompts(self, initial_tokens, N):
         """``generate_batch``'s ``initial_tokens`` -> (the distinct windows, 1-D int32 each; the window index of every
         utterance).  Raises on anything but None, one 1-D window or an (N, W) integer array."""
@@ -589,7 +647,7 @@ class FasterWaveNet(WaveNet):
         return prompts, which
 
     def generate_batch(self, n_samples, uniforms, initial_tokens=None, temperature=1.0, top_k=0, top_p=1.0,
-                       condition=None, local=None, local_phase=0, return_chosen: bool = False, forced=None):
+                       condition=None, local=None, local_phase=0, return_chosen: bool = False, forced=None, tile=None):
         """N independent utterances at once.  ``n_samples`` an int: ``uniforms`` is (N, >= n_samples) float64, utterance u draws
         with ``uniforms[u]``, and (N, n_samples) int32 tokens on the device come back.  ``n_samples`` a sequence of N positive
         ints -- a length per utterance: ``uniforms`` is an (N, >= max) array or a list of N 1-D arrays, and a LIST of N 1-D int32
@@ -626,7 +684,15 @@ class FasterWaveNet(WaveNet):
         ``forced``: None, one 1-D integer array for all utterances (at least as long as the longest; utterance u takes its first
         ``n_u`` entries), or a list of N entries, each such an array of the utterance's own length or None (= all -1).  Row u is
         ``generate(..., forced=<u's entries>)`` bit for bit, tokens and ``chosen``; the handles of such a call are
-        ``WN_DECODER_FORCED_TOKENS`` ones, all of them."""
+        ``WN_DECODER_FORCED_TOKENS`` ones, all of them.
+
+        ``tile``: None (= ``self.batch_tile``, 0 by default), 0 / 1 (off), 2, 4, 8, 16 or ``"auto"`` (``pick_tile`` per launch).  With
+        U >= 2 a workgroup of the any-shape decoder takes U utterances of a launch and reads ONE copy of the weights for them
+        (``same_weights = U``) -- also when classes, tables, phases, controls, prompts or lengths differ within the call, which
+        stay per utterance.  The result is the same, bit for bit.  A U that does not fit the model's LDS (``tile_fit``) raises
+        before any device work.  On config 4's shape, under ``WAVENET_HIP_BATCH_OWN_WEIGHTS=1`` and for a single live utterance
+        ``tile`` changes nothing."""
+        tile = check_tile(self.batch_tile if tile is None else tile, self.params)
         ragged = not isinstance(n_samples, (int, np.integer))
         recs, feats = self._batch_plan(n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase,
                                        forced)
@@ -711,10 +777,12 @@ class FasterWaveNet(WaveNet):
             # form that is roughly the order workgroups are dispatched in when they outnumber what the device holds
             for n_launch, idx in deal_launches([recs[i].n - 1 for i in live], limit, self.batch_longest_first):
                 sel = [live[j] for j in idx]
+                U = self._launch_tile(tile, len(sel), nine) if len(live) > 1 else None      # a tile size, or None: `same` as ever
                 rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._handles[i].h.value for i in sel]), len(sel),
                                               (C.c_int32 * len(sel))(*[firsts[i] for i in sel]), ptr_array([u_dev[i][1:] for i in sel]),
                                               n_launch, ptr_array([outs[i] for i in sel]),
-                                              ptr_array([ch[i][1:] for i in sel]) if return_chosen else None, same, stream_ptr())
+                                              ptr_array([ch[i][1:] for i in sel]) if return_chosen else None,
+                                              same if U is None else U, stream_ptr())
                 if rc == _lib.WN_ESHAPE and nine:     # refused before any device work: the nine workgroups per utterance do not fit the device
                     return self._generate_batch_loop(recs, ragged, return_chosen)
                 check(rc, "wn_decoder_run_batch")
@@ -728,7 +796,7 @@ class FasterWaveNet(WaveNet):
         return res if ragged else out
 
     def open_stream(self, utterances=1, initial_tokens=None, condition=None, local=None, local_phase=0, temperature=1.0,
-                    top_k=0, top_p=1.0, return_chosen: bool = False, ring_frames=None, max_pull=4096):
+                    top_k=0, top_p=1.0, return_chosen: bool = False, ring_frames=None, max_pull=4096, tile=None):
         """Streaming synthesis: a ``DecodeStream`` over ``utterances`` utterances -- features go in by ``push``, samples come out
         by ``pull``, in pieces of any size, and the concatenation of everything pulled equals row for row, bit for bit, what ONE
         ``generate_batch`` call with the same arguments and a table of the same rows returns (tokens, and ``chosen`` with
@@ -747,9 +815,11 @@ class FasterWaveNet(WaveNet):
         Rows fed with ``push_rows`` are the table's rows by construction.  Rows made by ``push(features)`` come from a projection
         GEMM over fewer columns per call than the whole utterance's: in the default fp16 x 2 arithmetic the per-tile scales
         depend on a row's tile mates, so such rows agree with the whole-utterance rows to that GEMM's product error only, and a
-        token can differ at a near-tie of the cumulative distribution -- the caveat of ``WN_DECODER_ONE_WORKGROUP``."""
+        token can differ at a near-tie of the cumulative distribution -- the caveat of ``WN_DECODER_ONE_WORKGROUP``.
+
+        ``tile``: as for ``generate_batch``; the stream keeps its tile size for every ``pull``."""
         return DecodeStream(self, utterances, initial_tokens, condition, local, local_phase, temperature, top_k, top_p,
-                            return_chosen, ring_frames, max_pull)
+                            return_chosen, ring_frames, max_pull, tile)
 
     def _batch_plan(self, n_samples, uniforms, initial_tokens, temperature, top_k, top_p, condition, local, local_phase,
                     forced=None):
@@ -940,8 +1010,9 @@ class DecodeStream(object):
     The stream holds the weights as they were when it was opened."""
 
     def __init__(self, net, utterances, initial_tokens, condition, local, local_phase, temperature, top_k, top_p, return_chosen,
-                 ring_frames, max_pull):
+                 ring_frames, max_pull, tile=None):
         self.net, self._hs, self._rings, self.closed = net, [], [], False
+        self.tile = check_tile(net.batch_tile if tile is None else tile, net.params, "open_stream")      # kept for every pull
         N = int(utterances)
         if N < 1:
             raise Exception("open_stream: utterances must be positive, got %d" % N)
@@ -1135,10 +1206,12 @@ class DecodeStream(object):
                 same = 1 if self._nine and os.environ.get("WAVENET_HIP_BATCH_OWN_WEIGHTS") != "1" else 0
                 launched = 0
                 for n_launch, sel in deal_launches([steps] * N, limit):
+                    U = net._launch_tile(self.tile, len(sel), self._nine)      # a tile size, or None: `same` as ever
                     rc = lib.wn_decoder_run_batch((C.c_void_p * len(sel))(*[self._hs[i].value for i in sel]), len(sel),
                                                   (C.c_int32 * len(sel))(*[self._last[i] for i in sel]), ptr_array([us[i] for i in sel]),
                                                   n_launch, ptr_array([outs[i] for i in sel]),
-                                                  ptr_array([chs[i] for i in sel]) if chs is not None else None, same, stream_ptr())
+                                                  ptr_array([chs[i] for i in sel]) if chs is not None else None,
+                                                  same if U is None else U, stream_ptr())
                     if rc == _lib.WN_ESHAPE and self._nine and not launched:
                         batched = False            # refused before any device work: nine workgroups per utterance do not fit the device
                         break

@@ -98,6 +98,13 @@ _STREAM_FLAGS = (
     (("--ring-frames",), int, None, "generate --chunk-frames: rows of the ring of projected feature rows the decoder reads in place "
                                     "(default: what one chunk and the largest pull need)"),
 )
+# decoding in utterance tiles (FasterWaveNet.batch_tile; train_audio/generate.py tile_job): off, an attribute of the namespace only
+# when given, checked by generate before the model is built
+_TILE_FLAGS = (
+    (("--tile",), str, None, "generate --fast: decode the utterances of a batched run in tiles of U that share one read of the "
+                             "weights -- auto, 2, 4, 8 or 16 (models of any shape but the specialised 32/256-channel one, which "
+                             "ignores it); the samples are the same, bit for bit"),
+)
 # regenerating stretches of a recording (FasterWaveNet.generate(..., forced=...); train_audio/generate.py keep_job / keep_mask): off,
 # attributes of the namespace only when given, checked by generate before the model is built
 _KEEP_HELP = ("generate --fast: keep this recording and draw only the --redraw stretches: the file's first input_width samples are "
@@ -125,6 +132,7 @@ class Args(argparse.Namespace):
     report, best_of = None, 1
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
+    tile = None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -134,7 +142,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

@@ -92,6 +92,18 @@ def likelihood_job(args):
     return K, report
 
 
+def tile_job(args):
+    """``generate --tile auto|2|4|8|16``: the check, made before a model is built.  Returns None without the flag, else what
+    ``FasterWaveNet.batch_tile`` takes: ``"auto"`` or the tile size."""
+    if args.tile is None:
+        return None
+    if not args.fast:
+        raise SystemExit("generate: --tile sizes the utterance tiles of the decoder on the device: give --fast")
+    if args.tile != "auto" and args.tile not in ("2", "4", "8", "16"):
+        raise SystemExit("generate: --tile takes auto, 2, 4, 8 or 16, got {!r}".format(args.tile))
+    return "auto" if args.tile == "auto" else int(args.tile)
+
+
 def _keep_best(tokens, chosen, K):
     """``tokens`` / ``chosen``: N * K rows, row ``u * K + c`` candidate c of utterance u (1-D arrays or device tensors) ->
     (the kept candidate's tokens per utterance as numpy, [(kept index, [nats per sample of every candidate])])."""
@@ -503,11 +515,14 @@ def main(argv=None):
     args = _args.parse(argv)
     best_of, report = likelihood_job(args)
     chunk_frames, ring_frames = stream_job(args)
+    tile = tile_job(args)
     seconds_given = _seconds_given(argv)
     kept = keep_job(args, seconds_given)
     if args.local_dir is not None:
         names, feats, lengths, cids = directory_job(args, seconds_given)
         params, net = _model.build(args)
+        if tile is not None:
+            net.batch_tile = tile
         return generate_directory(net, params, names, feats, lengths, cids, seed=args.seed, output_dir=args.output_dir,
                                   temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, best_of=best_of, report=report)
     n_utt, prompt_files = _args.utterance_prompts(args)
@@ -526,6 +541,8 @@ def main(argv=None):
         distinct = {f: _local.read_features(f, config[0]) for f in set(args.local)}
         feats = [distinct[f] for f in (args.local * (n_utt or 1) if len(args.local) == 1 else args.local)]
     params, net = _model.build(args)
+    if tile is not None:               # every generate_batch / open_stream call of this run decodes in tiles
+        net.batch_tile = tile
     np.random.seed(args.seed)
     if feats is not None:
         # the features cover an utterance from its first sample, the window of input_width samples included; the length
