@@ -1,4 +1,5 @@
-"""Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950.
+"""Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950 -- all but logmel.hip, which becomes
+wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h: a library of its own, the first one's exports are pinned).
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the .so then travels
 in-tree to the GPU box.  Usage: ``python -m wavenet_amd.build [--force]``.
@@ -15,6 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libwavenet_hip.so")
+LOGMEL_LIB = os.path.join(HERE, "libwavenet_logmel.so")
+LOGMEL_SRC = "logmel.hip"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"] + \
@@ -39,21 +42,28 @@ def _compile(src: str, force: bool, hdr_mtime: float) -> str:
     return obj
 
 
+def _link(lib: str, objs, version_script: str, force: bool) -> None:
+    if force or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
+        # the version script drops what hipcc itself adds to the dynamic table (one __hip_cuid_* marker per translation unit)
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden",
+               "-Wl,--version-script=" + os.path.join(CSRC, version_script), "-o", lib] + list(objs)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdr = _newest_header()
     with ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, hdr), srcs))
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
-        # the version script drops what hipcc itself adds to the dynamic table (one __hip_cuid_* marker per translation unit)
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fvisibility=hidden",
-               "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", LIB] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed:\n%s\n%s" % (r.stdout, r.stderr))
+    logmel = [o for s, o in zip(srcs, objs) if os.path.basename(s) == LOGMEL_SRC]
+    _link(LIB, [o for o in objs if o not in logmel], "exports.map", force)
+    _link(LOGMEL_LIB, logmel, "logmel_exports.map", force)
     if verbose:
         print("built", LIB)
+        print("built", LOGMEL_LIB)
     return LIB
 
 

@@ -817,6 +817,9 @@ class FasterWaveNet(WaveNet):
         depend on a row's tile mates, so such rows agree with the whole-utterance rows to that GEMM's product error only, and a
         token can differ at a near-tie of the cumulative distribution -- the caveat of ``WN_DECODER_ONE_WORKGROUP``.
 
+        Audio in: ``st.push(an.feed(chunk))`` with ``an = features.LogMel(...).stream()`` makes the next columns on the device, where
+        the ring lives, and feeds them; column k needs the samples up to k hop + win / 2, a look-ahead of win / 2 samples.
+
         ``tile``: as for ``generate_batch``; the stream keeps its tile size for every ``pull``."""
         return DecodeStream(self, utterances, initial_tokens, condition, local, local_phase, temperature, top_k, top_p,
                             return_chosen, ring_frames, max_pull, tile)

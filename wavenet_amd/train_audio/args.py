@@ -57,16 +57,25 @@ _LOCAL_FLAGS = (
                                   "writes log-mel ones); F and the hop go to <model-dir>/local.json.  generate --fast: vocode "
                                   "every NAME.npy of the directory into <output_dir>/NAME.wav, each at the length its features "
                                   "cover (-s caps them), in one batched run; excludes --local"),
-    (("--local-hop",), int, None, "train --local-dir: samples per feature column (256 unless local.json says otherwise)"),
-    (("--local-interp",), str, None, "train --local-dir: how the features reach the sample rate, 'repeat' (a column holds for "
+    (("--local-hop",), int, None, "train --local-dir / --local-mel: samples per feature column (256 unless local.json says otherwise)"),
+    (("--local-interp",), str, None, "train --local-dir / --local-mel: how the features reach the sample rate, 'repeat' (a column holds for "
                                      "its hop samples) or 'linear' (interpolated between neighbouring columns, a column anchored "
                                      "at the first sample of its frame); stored in local.json, which generate and evaluate follow"),
-    (("--local-crop",), str, None, "train --local-dir: where crops start, 'frame' (on a feature column border, the default) or "
+    (("--local-crop",), str, None, "train --local-dir / --local-mel: where crops start, 'frame' (on a feature column border, the default) or "
                                    "'sample' (anywhere, as without features: one --seed selects the same crops; every crop "
                                    "carries its own phase).  A property of the run, not of the checkpoint"),
-    (("--local-upsample",), int, None, "train --local-dir: a learned upsampling layer of factor U ahead of the projection (U "
+    (("--local-upsample",), int, None, "train --local-dir / --local-mel: a learned upsampling layer of factor U ahead of the projection (U "
                                        "divides the hop; the network then runs at hop / U); stored in local.json when U > 1, "
                                        "which generate and evaluate follow"),
+)
+# log-mel features made from the audio on the device (features.LogMel; train_audio/local.py "mel"): off, attributes of the
+# namespace only when given
+_MEL_FLAGS = (
+    (("--local-mel",), None, False, "train: condition on the log-mel spectrogram of every .wav file itself, made on the device when "
+                                    "the file is loaded (--mels F channels, one column per --local-hop samples, a window of --win); "
+                                    "F, the hop and the window go to <model-dir>/local.json.  Excludes --local-dir"),
+    (("--mels",), int, None, "train --local-mel: mel channels F (80 unless local.json says otherwise)"),
+    (("--win",), int, None, "train --local-mel: analysis window in samples (1024 unless local.json says otherwise)"),
 )
 # activation storage of the run (WaveNet.set_storage): fp32, and an attribute of the namespace only when given
 _STORAGE_FLAGS = (
@@ -116,6 +125,10 @@ _REDRAW_HELP = ("generate --keep: a stretch A:B, in seconds of the kept file, to
                 "every utterance; it cannot start inside the window (the first input_width samples)")
 _LOCAL_HELP = ("generate: the (F, frames) .npy features to generate from (a locally conditioned checkpoint needs them); repeatable: "
                "one file for all utterances, or one per utterance.  Without -s the length is what the features cover")
+_FROM_WAV_HELP = ("generate --fast: copy synthesis -- read this recording as training reads it, make its log-mel features on the "
+                  "device with the checkpoint's \"mel\" settings (a train --local-mel checkpoint) and generate as --local would from "
+                  "those columns; with --chunk-frames C the analyser is fed C hops of audio at a time.  Repeatable: one file for all "
+                  "utterances, or one per utterance; excludes --local, --local-dir and --keep")
 _SPEAKER_HELP = ("generate: the speaker label to generate as (a conditioned checkpoint needs one); repeatable: one label for all "
                  "utterances, or one per utterance")
 _PROMPT_HELP = ("a .wav file whose last input_width samples seed the generation instead of silence; repeatable: one file for "
@@ -128,6 +141,7 @@ class Args(argparse.Namespace):
     speaker_prefix, condition_channels, speaker = False, None, None
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
     local_upsample = None
+    local_mel, mels, win, from_wav = False, None, None, None
     storage = "fp32"
     report, best_of = None, 1
     keep, redraw = None, None
@@ -142,7 +156,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
@@ -152,6 +166,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--speaker", action="append", default=argparse.SUPPRESS, metavar="LABEL", help=_SPEAKER_HELP)
     ap.add_argument("--local", action="append", default=argparse.SUPPRESS, metavar="FILE.npy", help=_LOCAL_HELP)
     ap.add_argument("--keep", action="append", default=argparse.SUPPRESS, metavar="FILE.wav", help=_KEEP_HELP)
+    ap.add_argument("--from-wav", action="append", default=argparse.SUPPRESS, metavar="FILE.wav", help=_FROM_WAV_HELP)
     ap.add_argument("--redraw", action="append", default=argparse.SUPPRESS, metavar="A:B", help=_REDRAW_HELP)
     return ap
 
@@ -202,14 +217,34 @@ def parse(argv=None):
         ap.error("--speaker-prefix needs --condition-channels H with H >= 1")
     if args.condition_channels is not None and not args.speaker_prefix:
         ap.error("--condition-channels goes with --speaker-prefix")
-    if args.local_hop is not None and (args.local_dir is None or args.local_hop < 1):
-        ap.error("--local-hop H goes with --local-dir and needs H >= 1")
-    if args.local_interp is not None and (args.local_dir is None or args.local_interp not in ("repeat", "linear")):
-        ap.error("--local-interp {repeat,linear} goes with --local-dir")
-    if args.local_crop is not None and (args.local_dir is None or args.local_crop not in ("frame", "sample")):
-        ap.error("--local-crop {frame,sample} goes with --local-dir")
-    if args.local_upsample is not None and (args.local_dir is None or args.local_upsample < 1):
-        ap.error("--local-upsample U goes with --local-dir and needs U >= 1")
+    has_local = args.local_dir is not None or args.local_mel
+    if args.local_mel and args.local_dir is not None:
+        ap.error("--local-mel (features made from the audio) and --local-dir FEAT_DIR (feature files) exclude each other")
+    if (args.mels is not None or args.win is not None) and not args.local_mel:
+        ap.error("--mels F and --win W go with --local-mel")
+    if args.local_mel:
+        from .. import features
+        try:
+            features._check_logmel_shape(args.mels, args.local_hop, args.win)      # what is given; model.build checks what is used
+        except ValueError as e:
+            ap.error("--local-mel: %s" % e)
+    if args.from_wav:
+        bad = [f for f, on in (("--local", args.local), ("--local-dir", args.local_dir is not None), ("--keep", args.keep)) if on]
+        if bad:
+            ap.error("--from-wav FILE.wav (features made from a recording) excludes %s" % ", ".join(bad))
+        if not args.fast:
+            ap.error("--from-wav needs --fast")
+        n = utterance_count(args)
+        if len(args.from_wav) not in (1, n):
+            ap.error("%d --from-wav files for %d utterances: give one for all of them, or one each" % (len(args.from_wav), n))
+    if args.local_hop is not None and (not has_local or args.local_hop < 1):
+        ap.error("--local-hop H goes with --local-dir or --local-mel and needs H >= 1")
+    if args.local_interp is not None and (not has_local or args.local_interp not in ("repeat", "linear")):
+        ap.error("--local-interp {repeat,linear} goes with --local-dir or --local-mel")
+    if args.local_crop is not None and (not has_local or args.local_crop not in ("frame", "sample")):
+        ap.error("--local-crop {frame,sample} goes with --local-dir or --local-mel")
+    if args.local_upsample is not None and (not has_local or args.local_upsample < 1):
+        ap.error("--local-upsample U goes with --local-dir or --local-mel and needs U >= 1")
     if args.storage not in ("fp32", "bf16"):
         ap.error("--storage {fp32,bf16}, got %r" % (args.storage,))
     if args.local and args.local_dir is not None:

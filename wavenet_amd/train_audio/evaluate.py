@@ -31,19 +31,24 @@ def build_parser() -> argparse.ArgumentParser:
                     help="score the checkpoint's averaged weights (wavenet.ema.npz, written by train --ema-decay)")
     ap.add_argument("--local-dir", type=str, default=argparse.SUPPRESS, metavar="FEAT_DIR",
                     help="the files' features, NAME.npy per NAME.wav (a locally conditioned checkpoint needs them)")
+    ap.add_argument("--local-mel", action="store_true", default=argparse.SUPPRESS,
+                    help="score every file under the log-mel features of the file itself, made on the device (a checkpoint trained "
+                         "with train --local-mel); --local-dir, when given too, wins")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
     return ap
 
 
-def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None):
+def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None,
+                 local_mel=None):
     """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
     "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
     samples, and prints one line per file and one for the total unless ``verbose`` is off.  A checkpoint conditioned on
     speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run.
     A locally conditioned checkpoint scores every file under its feature file in ``local_dir`` (train_audio/local.py); the
-    pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop."""
+    pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop.  ``local_mel`` ({"win": W}, the
+    checkpoint's "mel" entry): without ``local_dir``, every file is scored under the log-mel features of its own tokens."""
     local = getattr(net, "local", None)
-    _local.require_match(local, local_dir is not None, "evaluate", "--local-dir FEAT_DIR")
+    _local.require_match(local, local_dir is not None or local_mel is not None, "evaluate", "--local-dir FEAT_DIR or --local-mel")
     if local is not None:
         chunk_width = -(-int(chunk_width) // local[1]) * local[1]
     files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
@@ -53,10 +58,10 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     labels = getattr(net, "speakers", None)
     cids = {fn: None if labels is None else _speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files}
     for fn in files:
-        tokens, _ = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
+        tokens, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
         lkw = {} if local is None else {"local": _local.with_extra_column(
-            _local.file_features(local_dir, fn, tokens.size, local[0], local[1]), getattr(net, "local_interp", "repeat"),
-            getattr(net, "local_upsample", 1))}
+            _local.file_or_mel_features(local_dir, local_mel, fn, tokens, rate, local[0], local[1], params.quantization_steps),
+            getattr(net, "local_interp", "repeat"), getattr(net, "local_upsample", 1))}
         row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn], **lkw))
         rows.append(dict(file=fn, **row))
         nats += row["nats_per_sample"] * row["samples"]
@@ -75,9 +80,13 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
 def main(argv=None):
     args = build_parser().parse_args(argv)
     args.fast, args.seed = False, None                       # what train_audio.model.build reads beyond the shared flags
+    want_mel = bool(getattr(args, "local_mel", False))
+    if want_mel and _local.load_mel(args.model_dir) is None:                 # before a model is built
+        raise SystemExit("evaluate: --local-mel needs a checkpoint trained with train --local-mel ({} has no \"mel\")".format(
+            os.path.join(args.model_dir, _local.FILE)))
     params, net = _model.build(args)
     table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
-                         local_dir=getattr(args, "local_dir", None))
+                         local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(table, f, indent=2)

@@ -1,10 +1,11 @@
 """Write log-mel feature files for local conditioning: ``FEAT_DIR/NAME.npy`` per ``WAV_DIR/NAME.wav``.
 
-    python -m wavenet_amd.train_audio.features -w WAV_DIR -o FEAT_DIR [--hop 256 --mels 80 --win 1024]
+    python -m wavenet_amd.train_audio.features -w WAV_DIR -o FEAT_DIR [--hop 256 --mels 80 --win 1024] [--device]
 
 A file is read as training reads it (``data.load_audio_file``: mu-law tokens, silence trimmed) and the spectrogram is taken
 of those tokens decoded back to a waveform, so column k belongs to tokens k * hop .. (k + 1) * hop - 1 of what the network
-sees.  See wavenet_amd/features.py for the definition."""
+sees.  See wavenet_amd/features.py for the definition.  ``--device`` writes the same files from the kernel
+(``features.LogMel.batch`` over the tokens, at most 64 files per launch): float32 sums in place of float64 ones."""
 from __future__ import annotations
 
 import argparse
@@ -24,7 +25,23 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--mels", type=int, default=80, help="mel channels F")
     ap.add_argument("--win", type=int, default=1024, help="analysis window in samples")
     ap.add_argument("--quantization-steps", type=int, default=256, help="the model's quantization_steps")
+    ap.add_argument("--device", action="store_true",
+                    help="compute on the GPU (features.LogMel): the values that train --local-mel and generate --from-wav see")
     return ap
+
+
+def device_features(paths, quantization_steps, mels, hop, win):
+    """[(tokens, (F, frames) float32 array)] of wav files, LogMel.batch over each run of files that share a sampling rate."""
+    loaded = [data.load_audio_file(p, quantization_steps=quantization_steps) for p in paths]
+    feats = [None] * len(paths)
+    for rate in sorted({r for _, r in loaded}):
+        mel = features.LogMel(rate, n_mels=mels, hop=hop, win=win)
+        idx = [i for i, (_, r) in enumerate(loaded) if r == rate]
+        for at in range(0, len(idx), features.LOGMEL_MAX_CLIPS):
+            part = idx[at:at + features.LOGMEL_MAX_CLIPS]
+            for i, out in zip(part, mel.batch([loaded[i][0] for i in part], quantization_steps)):
+                feats[i] = out.cpu().numpy()
+    return [(tok, f) for (tok, _), f in zip(loaded, feats)]
 
 
 def main(argv=None):
@@ -34,6 +51,16 @@ def main(argv=None):
         raise SystemExit("no .wav file in {}".format(args.wav_dir))
     os.makedirs(args.output_dir, exist_ok=True)
     written = []
+    if args.device:
+        features._check_logmel_shape(args.mels, args.hop, args.win)      # before any file is read
+        got = device_features([os.path.join(args.wav_dir, fn) for fn in files], args.quantization_steps, args.mels, args.hop,
+                              args.win)
+        for fn, (tokens, feats) in zip(files, got):
+            out = feature_path(args.output_dir, fn)
+            np.save(out, feats)
+            print("{}: {} samples -> {} {}".format(fn, tokens.size, out, feats.shape))
+            written.append(out)
+        return written
     for fn in files:
         tokens, rate = data.load_audio_file(os.path.join(args.wav_dir, fn), quantization_steps=args.quantization_steps)
         signal = data.mulaw_decode(tokens, args.quantization_steps)

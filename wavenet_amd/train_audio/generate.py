@@ -28,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from .. import data, sampling
+from .. import data, features, sampling
 from ..faster_wavenet import silence_window
 from . import args as _args
 from . import local as _local
@@ -183,12 +183,62 @@ def stream_job(args):
         raise SystemExit("generate: --ring-frames R needs R >= 1, got {}".format(R))
     if not args.fast:
         raise SystemExit("generate: --chunk-frames streams features to the decoder on the device: give --fast")
-    if not args.local:
+    if not args.local and not args.from_wav:
         raise SystemExit("generate: --chunk-frames streams the columns of a feature file: give --local FILE.npy")
     if args.utterances is not None or args.prompt or args.keep or args.local_dir is not None:
         raise SystemExit("generate: --chunk-frames vocodes one utterance from silence: --utterances, --prompt, --keep and "
                          "--local-dir do not go with it")
     return int(C), None if R is None else int(R)
+
+
+class _ArrayColumns(object):
+    """The columns of a feature array, handed out in order (``generate_streamed``'s source)."""
+
+    def __init__(self, local):
+        self.a = np.asarray(local, dtype=np.float32)
+        self.total = int(self.a.shape[1])
+        self.at = 0
+
+    def take(self, k, host=False):
+        out = self.a[:, self.at:self.at + k]
+        self.at += int(out.shape[1])
+        return out
+
+
+class MelColumns(object):
+    """The same interface over a recording: its tokens are fed to a streaming analyser (``features.LogMel.stream``) ``chunk_frames``
+    hops at a time -- the look-ahead of win / 2 samples means a feed may complete fewer columns than it carries samples for --
+    until ``take`` has its columns or the recording ends (``flush``); ``extra`` copies of the last column follow it, what
+    ``local.with_extra_column`` appends to a file's array.  The columns are the one-shot call's, bit for bit."""
+
+    def __init__(self, mel, tokens, quantization_steps, chunk_frames, extra=0):
+        self.an = mel.stream(quantization_steps)
+        self.tokens = np.asarray(tokens, dtype=np.int32)
+        self.step = int(chunk_frames) * mel.hop
+        self.fed, self.extra, self.flushed = 0, int(extra), False
+        self.total = features.frame_count(self.tokens.size, mel.hop) + self.extra
+        self.have, self._last = [], None                # (F, k) device tensors not handed out yet; the last column made
+
+    def _more(self):
+        if self.fed < self.tokens.size:
+            part = self.tokens[self.fed:self.fed + self.step]
+            self.fed += part.size
+            return self.an.feed(part)
+        self.flushed = True
+        out = self.an.flush()
+        last = out[:, -1:] if out.shape[1] else self._last
+        return torch.cat([out] + [last] * self.extra, dim=1) if self.extra else out
+
+    def take(self, k, host=False):
+        while sum(int(c.shape[1]) for c in self.have) < k and not self.flushed:
+            got = self._more()
+            if got.shape[1]:
+                self._last = got[:, -1:]
+                self.have.append(got)
+        allc = torch.cat(self.have, dim=1) if self.have else self.an._empty()
+        out, rest = allc[:, :k].contiguous(), allc[:, k:]
+        self.have = [rest] if rest.shape[1] else []
+        return out.cpu().numpy() if host else out
 
 
 class _GrowingWav(object):
@@ -219,7 +269,8 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
     ``available()`` is pulled, ``max_pull`` samples at a time at most, and appended to ``generated.wav``.  Uniforms: the
     ``random_sample`` draws of the command without the flag, so with C >= the columns -- one projection over the same array --
     the file is the same, byte for byte.  ``best_of`` = K > 1: the K candidates are K utterances of the stream, ``chosen`` is
-    collected per pull, and the file is written at the end, when the ranking is known."""
+    collected per pull, and the file is written at the end, when the ranking is known.  ``local`` may be a ``MelColumns``
+    (``--from-wav``): the columns are then made from the recording as the loop asks for them."""
     from ..faster_wavenet import stream_frames
     from ..wavenet import coarse_frames_needed
     Q, sr = params.quantization_steps, params.sampling_rate
@@ -227,14 +278,16 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
     n = int(sr * generate_sec) - 1
     K, want = int(best_of), best_of > 1 or bool(report)
     if n <= 0:
+        if isinstance(local, MelColumns):
+            local = local.take(local.total, host=True)
         return generate_audio(net, params, sr, generate_sec, True, output_dir, temperature, top_k, top_p, condition, local, best_of, report)
     silence = silence_window(Q, input_width_of(params))
     start_time = time.time()
     os.makedirs(output_dir, exist_ok=True)
     filename = "{}/generated.wav".format(output_dir)
     u = np.reshape(np.random.random_sample(n) if K == 1 else np.random.random_sample((K, n)), (K, n))
-    local = np.asarray(local, dtype=np.float32)
-    cols, C, U = int(local.shape[1]), int(chunk_frames), net.local_upsample
+    src = local if isinstance(local, MelColumns) else _ArrayColumns(local)       # a feature array, or columns made as the audio arrives
+    cols, C, U = src.total, int(chunk_frames), net.local_upsample
     # the window's own columns come with the call that opens the stream: the prefill reads them
     first = min(cols, max(C, coarse_frames_needed(len(silence), net.local_hop, U, 0, net.local_interp)))
     if ring_frames is None:            # one feed, and what the largest pull reads at once
@@ -242,7 +295,7 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
     wav = _GrowingWav(filename, Q, sr) if K == 1 else None
     toks, chosen, done, at = [], [], 0, first
     try:
-        with net.open_stream(utterances=K, initial_tokens=silence, condition=condition, local=local[:, :first],
+        with net.open_stream(utterances=K, initial_tokens=silence, condition=condition, local=src.take(first, host=True),
                              temperature=temperature, top_k=top_k, top_p=top_p, return_chosen=want, ring_frames=ring_frames,
                              max_pull=max_pull) as st:
             while True:
@@ -269,7 +322,8 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
                 if done >= n or at >= cols:
                     break
                 k = min(C, cols - at)
-                st.push(local[:, at:at + k] if K == 1 else [local[:, at:at + k]] * K)
+                part = src.take(k)
+                st.push(part if K == 1 else [part] * K)
                 at += k
     finally:
         if wav is not None:
@@ -289,6 +343,30 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
     if report:
         write_report(report, [filename], [kept], ranked, K)
     return filename, kept
+
+
+def from_wav_job(args, config, n_utt, chunk_frames):
+    """``generate --fast --from-wav FILE.wav``: every file read as training reads it and its log-mel features made on the device with
+    the checkpoint's "mel" settings -> (one (F, frames) array per utterance, None), or with ``--chunk-frames`` (None, the streamed
+    run's ``MelColumns``: nothing is computed yet, the column count follows from the file's length).  Stops
+    before a model is built when the checkpoint was not trained with ``train --local-mel``."""
+    mel = _local.load_mel(args.model_dir)
+    if mel is None:
+        raise SystemExit("generate: --from-wav makes the features from the recording and needs a checkpoint trained with "
+                         "train --local-mel ({} has no \"mel\")".format(os.path.join(args.model_dir, _local.FILE)))
+    Q = _model.load_params(args.model_dir).quantization_steps
+    distinct = {}
+    with torch.cuda.device(args.gpu_device):
+        for f in sorted(set(args.from_wav)):
+            if not os.path.isfile(f):
+                raise SystemExit("generate: --from-wav {} is missing".format(f))
+            tokens, rate = data.load_audio_file(f, quantization_steps=Q)
+            if chunk_frames is not None:                 # streamed (one file): the analyser makes the columns as they are asked for
+                extra = (1 if _local.load_interp(args.model_dir) == "linear" else 0) + (1 if _local.load_upsample(args.model_dir) > 1 else 0)
+                return None, MelColumns(_local.mel_analyser(rate, config[0], config[1], mel["win"]), tokens, Q, chunk_frames, extra)
+            distinct[f] = _local.mel_features(tokens, rate, config[0], config[1], mel["win"], Q)
+    files = args.from_wav * n_utt if len(args.from_wav) == 1 else args.from_wav
+    return [distinct[f] for f in files], None
 
 
 def read_prompt(path, params):
@@ -535,24 +613,29 @@ def main(argv=None):
     cids = [_speakers.class_id(table[0] if table else None, s, "generate") for s in names]
     # features: checked against the checkpoint's local.json before the model is built, like the speakers
     config = _local.load_config(args.model_dir)
-    _local.require_match(config, bool(args.local), "generate", "--local FILE.npy")
-    feats = None
-    if config is not None:
+    _local.require_match(config, bool(args.local) or bool(args.from_wav), "generate",
+                         "--from-wav FILE.wav" if args.from_wav else "--local FILE.npy")
+    feats, mel_src = None, None
+    if args.from_wav:
+        feats, mel_src = from_wav_job(args, config, n_utt or 1, chunk_frames)
+    elif config is not None:
         distinct = {f: _local.read_features(f, config[0]) for f in set(args.local)}
         feats = [distinct[f] for f in (args.local * (n_utt or 1) if len(args.local) == 1 else args.local)]
     params, net = _model.build(args)
     if tile is not None:               # every generate_batch / open_stream call of this run decodes in tiles
         net.batch_tile = tile
     np.random.seed(args.seed)
-    if feats is not None:
+    if feats is not None or mel_src is not None:
         # the features cover an utterance from its first sample, the window of input_width samples included; the length
         # generated defaults to what they cover (-s left at its default), and more than that is refused before anything runs
         iw = input_width_of(params)
-        cover = min(f.shape[1] for f in feats) * config[1] - iw + 1          # samples that can be emitted
+        columns = [f.shape[1] for f in feats] if mel_src is None else [mel_src.total - mel_src.extra]
+        cover = min(columns) * config[1] - iw + 1                            # samples that can be emitted
         # (linear interpolation: the column behind the last is the driver's to supply -- the file's last one again -- so n
         # columns still give n * hop samples)
         # (a learned upsampling layer reads pairs of columns: one more copy of the last, likewise)
-        feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir), _local.load_upsample(args.model_dir)) for f in feats]
+        if feats is not None:
+            feats = [_local.with_extra_column(f, _local.load_interp(args.model_dir), _local.load_upsample(args.model_dir)) for f in feats]
         if cover < 1:
             raise SystemExit("generate: the features cover {} samples, fewer than the {} of the window".format(cover + iw - 1, iw))
         if kept is not None:
@@ -569,7 +652,7 @@ def main(argv=None):
         return generate_kept(net, params, *kept, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
                              top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of, report=report)
     if chunk_frames is not None:
-        return generate_streamed(net, params, feats[0], chunk_frames, ring_frames, generate_sec=args.seconds, output_dir=args.output_dir,
+        return generate_streamed(net, params, mel_src if mel_src is not None else feats[0], chunk_frames, ring_frames, generate_sec=args.seconds, output_dir=args.output_dir,
                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, condition=cids[0],
                                  best_of=best_of, report=report)
     if n_utt is not None:

@@ -9,6 +9,9 @@ tokens k * hop .. (k + 1) * hop - 1.  ``python -m wavenet_amd.train_audio.featur
 ``"interp": "linear"`` -- the key is written ONLY then, so a repeat-mode file is byte for byte what it always was; a file
 without it means "repeat" (``load_interp``).  ``train --local-upsample U`` adds ``"upsample": U`` the same way, ONLY for U > 1
 (``load_upsample``): the network is then built with a learned upsampling layer of that factor ahead of the projection.
+``train --local-mel`` adds ``"mel": {"win": W}``, again ONLY with that flag (``load_mel``): the features are then the log-mel
+spectrogram of the audio itself, made on the device (``features.LogMel``: F channels, the hop, that window), and evaluate
+and generate can make them from a .wav file with no feature file at all.
 
 Linear interpolation reads, at every position, the column after the position's own, so a window needs one more column than it
 spans.  The library never clamps: the drivers supply that column by repeating the file's last one (``with_extra_column``);
@@ -23,6 +26,7 @@ import numpy as np
 
 FILE = "local.json"
 DEFAULT_HOP = 256
+DEFAULT_MELS, DEFAULT_WIN = 80, 1024          # train --local-mel without --mels / --win
 INTERP = ("repeat", "linear")
 
 
@@ -69,6 +73,41 @@ def load_upsample(model_dir: str) -> Optional[int]:
     return u
 
 
+def load_mel(model_dir: str) -> Optional[dict]:
+    """{"win": W} of ``<model_dir>/local.json`` when the checkpoint was trained on log-mel features of the audio itself
+    (``train --local-mel``); None otherwise."""
+    if load_config(model_dir) is None:
+        return None
+    filename = os.path.join(model_dir, FILE)
+    with open(filename) as f:
+        mel = json.load(f).get("mel")
+    if mel is None:
+        return None
+    if not isinstance(mel, dict) or not isinstance(mel.get("win"), int):
+        raise Exception("{}: \"mel\" must be {{\"win\": W}}, got {!r}".format(filename, mel))
+    return {"win": int(mel["win"])}
+
+
+def mel_features(tokens, rate, channels: int, hop: int, win: int, quantization_steps: int) -> np.ndarray:
+    """The (F, ceil(samples / hop)) float32 log-mel features of a file's tokens as training reads them, made on the device in
+    one launch (``features.LogMel``) and brought back: the array ``features --device`` writes for that file, bit for bit."""
+    return mel_analyser(rate, channels, hop, win)(np.asarray(tokens, dtype=np.int32), quantization_steps).cpu().numpy()
+
+
+def mel_analyser(rate, channels: int, hop: int, win: int):
+    """The ``features.LogMel`` of these settings on the current device (the last one is kept: a run uses one)."""
+    import torch
+    from .. import features
+    key = (float(rate), int(channels), int(hop), int(win), torch.cuda.current_device())
+    if key not in _MEL:
+        _MEL.clear()
+        _MEL[key] = features.LogMel(rate, n_mels=channels, hop=hop, win=win, device="cuda:%d" % key[-1])
+    return _MEL[key]
+
+
+_MEL = {}
+
+
 def with_extra_column(features: np.ndarray, interp: Optional[str], upsample: int = 1) -> np.ndarray:
     """The features as the network takes them: with ``interp == "linear"`` the last column once more behind the others (the
     column that the last position's interpolation reads); with a learned upsampling layer (``upsample`` > 1) once more
@@ -81,11 +120,12 @@ def with_extra_column(features: np.ndarray, interp: Optional[str], upsample: int
 
 
 def ensure_config(model_dir: str, channels: int, hop: int, interp: Optional[str] = None,
-                  upsample: Optional[int] = None) -> Tuple[int, int]:
+                  upsample: Optional[int] = None, mel: Optional[dict] = None) -> Tuple[int, int]:
     """train --local-dir: write the file on the first run; a resumed run must find the SAME values or it stops.  ``interp``:
     what --local-interp gave (None: not given -- a first run then trains "repeat", a resumed one keeps the file's mode).
     ``upsample``: what --local-upsample gave, likewise (None: a first run trains without the layer, a resumed one keeps the
-    file's factor); ``"upsample": U`` is written ONLY for U > 1."""
+    file's factor); ``"upsample": U`` is written ONLY for U > 1.  ``mel``: {"win": W} of train --local-mel (None: not given);
+    ``"mel"`` is written ONLY then, and a resumed --local-mel run must find the same window."""
     have = load_config(model_dir)
     if interp is not None and interp not in INTERP:
         raise SystemExit("--local-interp must be one of {}, got {!r}".format(list(INTERP), interp))
@@ -98,9 +138,17 @@ def ensure_config(model_dir: str, channels: int, hop: int, interp: Optional[str]
             d["interp"] = "linear"
         if upsample is not None and int(upsample) > 1:
             d["upsample"] = int(upsample)
+        if mel is not None:
+            d["mel"] = {"win": int(mel["win"])}
         with open(os.path.join(model_dir, FILE), "w") as f:
             json.dump(d, f)
         return int(channels), int(hop)
+    if mel is not None and load_mel(model_dir) != {"win": int(mel["win"])}:
+        was = load_mel(model_dir)
+        raise SystemExit("{}: this checkpoint was trained {}, the command line gives --local-mel --win {}: a resumed run must "
+                         "find the same value".format(os.path.join(model_dir, FILE),
+                                                      "on feature files (no \"mel\")" if was is None else
+                                                      "with --local-mel --win {}".format(was["win"]), int(mel["win"])))
     if upsample is not None and int(upsample) != load_upsample(model_dir):
         raise SystemExit("{}: this checkpoint was trained with --local-upsample {}, the command line gives {}: a resumed run "
                          "must find the same value".format(os.path.join(model_dir, FILE), load_upsample(model_dir), int(upsample)))
@@ -172,6 +220,14 @@ def padded(features: np.ndarray, pad_samples: int, hop: int) -> Tuple[np.ndarray
     cols = (int(pad_samples) + hop - 1) // hop
     ext = np.concatenate([np.repeat(features[:, :1], cols, axis=1), features], axis=1)
     return np.ascontiguousarray(ext), cols * hop - int(pad_samples)
+
+
+def file_or_mel_features(local_dir, mel, wav_name: str, tokens, rate, channels: int, hop: int, quantization_steps: int):
+    """One file's features from either source: its feature file in ``local_dir`` when a directory is given (it wins), else the
+    log-mel of its own tokens (``mel`` = {"win": W}).  Both hand back the same kind of array."""
+    if local_dir is not None:
+        return file_features(local_dir, wav_name, np.asarray(tokens).size, channels, hop)
+    return mel_features(tokens, rate, channels, hop, mel["win"], quantization_steps)
 
 
 def require_match(config, given: bool, what: str, flag: str):

@@ -66,7 +66,9 @@ def build(args, train: bool = False):
     with the hop, to ``local.json`` -- or checks both against the one already there.  Whenever that file exists the network
     is built locally conditioned, and ``net.local`` is (F, hop) (None otherwise); ``args.local_interp`` (train) goes into the
     file the same way and ``net.local_interp`` is the file's mode; so does ``args.local_upsample`` (``"upsample"``, written
-    for U > 1 only), and ``net.local_upsample`` is the file's factor."""
+    for U > 1 only), and ``net.local_upsample`` is the file's factor.  ``args.local_mel`` (train) takes F, the hop and the
+    window from --mels / --local-hop / --win instead of a feature file and adds ``"mel": {"win": W}``; ``net.local_mel`` is that
+    entry of the file (None without it)."""
     params = load_params(args.model_dir)
     local_dir = getattr(args, "local_dir", None)
     if local_dir is not None and train:                                     # (evaluate and generate read the config only)
@@ -75,6 +77,19 @@ def build(args, train: bool = False):
         hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
         local = _local.ensure_config(args.model_dir, _local.directory_channels(local_dir, wavs), hop,
                                      getattr(args, "local_interp", None), getattr(args, "local_upsample", None))
+    elif bool(getattr(args, "local_mel", False)) and train:                  # the features are made from the audio: F is a flag
+        have = _local.load_config(args.model_dir)
+        hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
+        was = _local.load_mel(args.model_dir) if have else None
+        win = getattr(args, "win", None) or (was["win"] if was else _local.DEFAULT_WIN)
+        mels = getattr(args, "mels", None) or (have[0] if have else _local.DEFAULT_MELS)
+        from .. import features
+        try:
+            features._check_logmel_shape(mels, hop, win)
+        except ValueError as e:
+            raise SystemExit("--local-mel: {}".format(e))
+        local = _local.ensure_config(args.model_dir, mels, hop, getattr(args, "local_interp", None),
+                                     getattr(args, "local_upsample", None), mel={"win": win})
     else:
         local = _local.load_config(args.model_dir)
     if bool(getattr(args, "speaker_prefix", False)):
@@ -90,6 +105,7 @@ def build(args, train: bool = False):
     net = (FasterWaveNet if args.fast else WaveNet)(params, seed=args.seed, **cond)
     net.speakers = table[0] if table else None
     net.local = local
+    net.local_mel = _local.load_mel(args.model_dir) if local else None
     params.dump()
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     use_ema = bool(getattr(args, "ema", False))

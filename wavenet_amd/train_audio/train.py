@@ -92,18 +92,21 @@ class _Crops(object):
 
 
 def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None,
-                local_dir=None, local_crop="frame"):
+                local_dir=None, local_crop="frame", local_mel=None):
     """One file: returns the summed loss of its ``repeat`` updates (train.py:24-90).  ``local_dir``: where the file's feature
     file lies (a locally conditioned model); crops then start on a feature column border (``local_crop="frame"``) or at any
-    sample, each with its own phase (``"sample"``: the crops a run without features draws)."""
-    signals, _ = data.load_audio_file(path_to_file, quantization_steps=params.quantization_steps)
+    sample, each with its own phase (``"sample"``: the crops a run without features draws).  ``local_mel`` ({"win": W},
+    ``--local-mel``): no feature file -- the log-mel features of the file's tokens, made on the device here, once per call;
+    from there on the array takes the feature file's path."""
+    signals, rate = data.load_audio_file(path_to_file, quantization_steps=params.quantization_steps)
     iw = input_width_of(params)
     silence = 127 if params.quantization_steps > 127 else params.quantization_steps // 2
     local = getattr(net, "local", None)
-    _local.require_match(local, local_dir is not None, "train", "--local-dir FEAT_DIR")
+    _local.require_match(local, local_dir is not None or local_mel is not None, "train", "--local-dir FEAT_DIR or --local-mel")
     fkw = {}
     if local is not None:
-        feats = _local.file_features(local_dir, path_to_file, signals.size, local[0], local[1])
+        feats = _local.file_or_mel_features(local_dir, local_mel, path_to_file, signals, rate, local[0], local[1],
+                                            params.quantization_steps)
         interp = getattr(net, "local_interp", "repeat")
         U = getattr(net, "local_upsample", 1)
         ext, shift = _local.padded(_local.with_extra_column(feats, interp, U), iw, local[1])
@@ -160,16 +163,16 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     return float(sum_loss.item())
 
 
-def validate(net, params, wav_dir, epoch, local_dir=None):
+def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None):
     """The held-out negative log-likelihood after an epoch: one line for the weights being trained and, when a weight
     average is kept, one for the averaged weights."""
     def line(what, total):
         sys.stdout.write("epoch: {} - held-out {}: {:.6f} nats/sample  {:.6f} bits/sample  ({} samples)\n".format(
             epoch, what, total["nats_per_sample"], total["bits_per_sample"], total["samples"]))
-    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir)["total"])
+    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel)["total"])
     if net.ema_enabled:
         with net.ema_weights():
-            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir)["total"])
+            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel)["total"])
     sys.stdout.flush()
 
 
@@ -178,7 +181,8 @@ def main(argv=None):
     if args.ema:
         raise Exception("--ema belongs to generate and evaluate; train keeps an average with --ema-decay")
     params, net = _model.build(args, train=True)
-    _local.require_match(net.local, args.local_dir is not None, "train", "--local-dir FEAT_DIR")
+    _local.require_match(net.local, args.local_dir is not None or args.local_mel, "train", "--local-dir FEAT_DIR or --local-mel")
+    local_mel = net.local_mel if args.local_mel else None      # (--local-dir on such a checkpoint: the feature files win)
     np.random.seed(args.seed)
     net.update_laerning_rate(args.lr)
     files = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
@@ -200,7 +204,7 @@ def main(argv=None):
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
                                         use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir,
-                                        local_crop=args.local_crop or "frame")
+                                        local_crop=args.local_crop or "frame", local_mel=local_mel)
             net.save(args.model_dir)
         average_loss /= len(files)
         sys.stdout.write("\033[2K\repoch: {} - {:.4e} loss - {} min\n".format(
@@ -208,7 +212,7 @@ def main(argv=None):
         sys.stdout.flush()
         net.save(args.model_dir)
         if args.valid_wav_dir:
-            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir)
+            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir, local_mel=local_mel)
     return average_loss
 
 
