@@ -8,4 +8,5 @@ from .faster_wavenet import FasterWaveNet              # noqa: F401
 from . import data                                     # noqa: F401
 from . import scoring                                  # noqa: F401
 from .graph import TrainStepGraph                      # noqa: F401
+from .corpus import Corpus                             # noqa: F401
 from ._lib import WaveNetHipError, set_gemm_precision, get_gemm_precision   # noqa: F401

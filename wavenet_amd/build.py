@@ -1,5 +1,6 @@
-"""Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950 -- all but logmel.hip, which becomes
-wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h: a library of its own, the first one's exports are pinned).
+"""Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950 -- all but the sources of ``SIDE_LIBS``:
+logmel.hip becomes wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h) and corpus.hip wavenet_amd/libwavenet_corpus.so
+(include/wavenet_corpus.h), libraries of their own: the first one's exports are pinned.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the .so then travels
 in-tree to the GPU box.  Usage: ``python -m wavenet_amd.build [--force]``.
@@ -17,7 +18,12 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libwavenet_hip.so")
 LOGMEL_LIB = os.path.join(HERE, "libwavenet_logmel.so")
-LOGMEL_SRC = "logmel.hip"
+CORPUS_LIB = os.path.join(HERE, "libwavenet_corpus.so")
+# source -> (library, version script): a source that is a library of its own; every other source goes into LIB
+SIDE_LIBS = {
+    "logmel.hip": (LOGMEL_LIB, "logmel_exports.map"),
+    "corpus.hip": (CORPUS_LIB, "corpus_exports.map"),
+}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"] + \
@@ -58,12 +64,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdr = _newest_header()
     with ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, hdr), srcs))
-    logmel = [o for s, o in zip(srcs, objs) if os.path.basename(s) == LOGMEL_SRC]
-    _link(LIB, [o for o in objs if o not in logmel], "exports.map", force)
-    _link(LOGMEL_LIB, logmel, "logmel_exports.map", force)
+    side = {os.path.basename(s): o for s, o in zip(srcs, objs) if os.path.basename(s) in SIDE_LIBS}
+    _link(LIB, [o for o in objs if o not in side.values()], "exports.map", force)
+    for src, (lib, version_script) in SIDE_LIBS.items():
+        _link(lib, [side[src]], version_script, force)
     if verbose:
-        print("built", LIB)
-        print("built", LOGMEL_LIB)
+        for lib in [LIB] + [lib for lib, _ in SIDE_LIBS.values()]:
+            print("built", lib)
     return LIB
 
 

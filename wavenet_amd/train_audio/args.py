@@ -83,6 +83,15 @@ _STORAGE_FLAGS = (
                                   "on the 128-channel kernels; conditioned models included).  A property of the run, not of the "
                                   "checkpoint: weights, optimiser state and checkpoints are fp32 either way"),
 )
+# crops drawn across the whole corpus (wavenet_amd/corpus.py; train_audio/train.py train_corpus): off, an attribute of the
+# namespace only when given, checked by train before the model is built
+_CORPUS_FLAGS = (
+    (("--corpus",), None, False, "train: keep every .wav file of --wav-dir on the device and draw each batch uniformly over all "
+                                 "training windows of all files -- a batch then mixes files and speakers, each crop with its own "
+                                 "file's speaker, features and phase, gathered in one launch -- instead of --repeat updates on "
+                                 "one file after the other.  An epoch stays files x --repeat updates, with a checkpoint every "
+                                 "--repeat.  A property of the run, not of the checkpoint"),
+)
 # likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
 # attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
 _LIKELIHOOD_FLAGS = (
@@ -143,6 +152,7 @@ class Args(argparse.Namespace):
     local_upsample = None
     local_mel, mels, win, from_wav = False, None, None, None
     storage = "fp32"
+    corpus = False
     report, best_of = None, 1
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
@@ -156,7 +166,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

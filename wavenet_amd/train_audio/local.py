@@ -94,6 +94,22 @@ def mel_features(tokens, rate, channels: int, hop: int, win: int, quantization_s
     return mel_analyser(rate, channels, hop, win)(np.asarray(tokens, dtype=np.int32), quantization_steps).cpu().numpy()
 
 
+def mel_features_of_files(tokens_per_file, rates, channels: int, hop: int, win: int, quantization_steps: int):
+    """``mel_features`` of every file of a corpus, up to 64 files (one launch) at a time: by the log-mel contract -- a column's
+    bits depend on its own samples only -- the arrays of the single calls, bit for bit."""
+    from ..features import LOGMEL_MAX_CLIPS
+    out, at = [], 0
+    while at < len(tokens_per_file):
+        end = at + 1
+        while end < len(tokens_per_file) and end - at < LOGMEL_MAX_CLIPS and rates[end] == rates[at]:
+            end += 1
+        cols = mel_analyser(rates[at], channels, hop, win).batch(
+            [np.asarray(t, dtype=np.int32) for t in tokens_per_file[at:end]], quantization_steps)
+        out.extend(c.cpu().numpy() for c in cols)
+        at = end
+    return out
+
+
 def mel_analyser(rate, channels: int, hop: int, win: int):
     """The ``features.LogMel`` of these settings on the current device (the last one is kept: a run uses one)."""
     import torch

@@ -1,5 +1,9 @@
 """Training driver (train_audio/train.py:24-135): for every epoch, for every .wav file, ``repeat`` updates on random crops
-of ``input_width + train_width`` samples with next-sample targets; checkpoint after every file and every epoch."""
+of ``input_width + train_width`` samples with next-sample targets; checkpoint after every file and every epoch.
+
+``--corpus`` (new): the files stay on the device (``wavenet_amd.corpus.Corpus``) and every batch is drawn uniformly over all
+training windows of all files, so a batch mixes files and speakers; an epoch keeps its ``len(files) * repeat`` updates and its
+checkpoints.  Both paths run the one update loop, ``run_updates``."""
 from __future__ import annotations
 
 import os
@@ -10,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import TrainStepGraph, data
+from ..corpus import Corpus, columns_per_crop
 from ..graph import default_loss
 from ..wavenet import coarse_frames_needed
 from . import args as _args
@@ -121,18 +126,29 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     if labels is not None:
         cid = _speakers.class_id(labels, _speakers.speaker_label(path_to_file), os.path.basename(path_to_file))
         cond = torch.full((batch_size,), cid, device=net.device, dtype=torch.int64)
-    sum_loss = torch.zeros((), device=net.device, dtype=torch.float64)
-    graph = None
-    skipped = 0
-    name = os.path.basename(path_to_file)
-    for batch_index in range(repeat):
+
+    def draw():
         drawn = crops.draw(batch_size)
-        x, tgt = drawn[0], drawn[1]
         lkw = {} if local is None else {"local": drawn[2]}
         if len(drawn) > 3:
             lkw["local_phase"] = drawn[3]                           # a phase per crop (--local-crop sample)
+        return drawn[0], drawn[1], cond, lkw
+
+    return run_updates(net, params, draw, repeat, (batch_size, iw + train_width), use_graph, state,
+                       os.path.basename(path_to_file), signals.size)
+
+
+def run_updates(net, params, draw, repeat, key, use_graph, state, name, width):
+    """``repeat`` updates, each on the batch ``draw()`` hands back -- (x, tgt, condition or None, the ``local=`` /
+    ``local_phase=`` keywords of the step) -- through the replayed graph of shape ``key`` (kept in ``state``) or op by op;
+    returns their summed loss.  ``name`` and ``width`` are what the progress line says of the source.  The one update loop of
+    the per-file path (``train_audio``) and of the corpus path (``train_corpus``)."""
+    sum_loss = torch.zeros((), device=net.device, dtype=torch.float64)
+    graph = None
+    skipped = 0
+    for batch_index in range(repeat):
+        x, tgt, cond, lkw = draw()
         if use_graph and str(params.optimizer).lower() != "eve":     # Eve needs the loss on the host every update
-            key = (batch_size, iw + train_width)
             graph = None if state is None else state.get(key)
             if graph is None:
                 graph = TrainStepGraph(net, x, tgt, condition=cond, **lkw)
@@ -158,9 +174,53 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
         elif batch_index % HEALTH_EVERY == HEALTH_EVERY - 1:
             skipped = 0
         if batch_index % 10 == 0:
-            sys.stdout.write("\r\t{} - {} width; {}/{}".format(name, signals.size, batch_index, repeat))
+            sys.stdout.write("\r\t{} - {} width; {}/{}".format(name, width, batch_index, repeat))
             sys.stdout.flush()
     return float(sum_loss.item())
+
+
+def load_corpus(net, params, wav_dir, files, local_dir=None, local_mel=None):
+    """``--corpus``: every .wav file of ``files`` loaded once -- its tokens, its features (the feature file of ``local_dir``, or
+    the log-mel of its own tokens made on the device, up to 64 files per launch: the bits of the single calls) and its
+    speaker's class id -- packed into a ``Corpus`` on the network's device."""
+    local = getattr(net, "local", None)
+    _local.require_match(local, local_dir is not None or local_mel is not None, "train", "--local-dir FEAT_DIR or --local-mel")
+    tokens, rates = [], []
+    for fn in files:
+        signals, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
+        tokens.append(signals.astype(np.int32))
+        rates.append(rate)
+    feats = None
+    if local is not None and local_dir is not None:
+        feats = [_local.file_features(local_dir, fn, t.size, local[0], local[1]) for fn, t in zip(files, tokens)]
+    elif local is not None:
+        feats = _local.mel_features_of_files(tokens, rates, local[0], local[1], local_mel["win"], params.quantization_steps)
+    labels = getattr(net, "speakers", None)
+    classes = None if labels is None else [_speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files]
+    return Corpus(tokens, input_width_of(params), params.quantization_steps, net.device, features=feats,
+                  hop=local[1] if local is not None else 0, classes=classes)
+
+
+def train_corpus(net, params, corpus, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None,
+                 local_crop="frame"):
+    """``repeat`` updates on batches drawn uniformly over all training windows of the corpus, every crop with its own file's
+    class id, feature columns and phase; returns their summed loss.  The rules are ``train_audio``'s: the column count per
+    crop, the int phase 0 of ``local_crop="frame"`` against one phase per crop (``"sample"``), the graph kept by shape."""
+    iw = corpus.input_width
+    n_cols = None
+    if corpus.features is not None:
+        n_cols = columns_per_crop(iw, train_width, corpus.hop, local_crop, getattr(net, "local_interp", "repeat"),
+                                  getattr(net, "local_upsample", 1))
+
+    def draw():
+        x, tgt, feats, cond, phases = corpus.draw(batch_size, train_width, local_crop, n_cols)
+        lkw = {} if feats is None else {"local": feats}
+        if feats is not None and local_crop == "sample":
+            lkw["local_phase"] = phases
+        return x, tgt, cond, lkw
+
+    return run_updates(net, params, draw, repeat, (batch_size, iw + train_width), use_graph, state, "corpus",
+                       int(corpus.tokens.size))
 
 
 def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None):
@@ -180,6 +240,12 @@ def main(argv=None):
     args = _args.parse(argv)
     if args.ema:
         raise Exception("--ema belongs to generate and evaluate; train keeps an average with --ema-decay")
+    if args.corpus:
+        if args.batch_size < 1 or args.train_width < 1 or args.repeat < 1:
+            raise SystemExit("train --corpus: --batch-size, --train-width and --repeat must be at least 1, got {}, {} and {}".format(
+                args.batch_size, args.train_width, args.repeat))
+        if not os.path.isdir(args.wav_dir) or not any(fn.endswith(".wav") for fn in os.listdir(args.wav_dir)):
+            raise SystemExit("train --corpus: no .wav file in {}".format(args.wav_dir))
     params, net = _model.build(args, train=True)
     _local.require_match(net.local, args.local_dir is not None or args.local_mel, "train", "--local-dir FEAT_DIR or --local-mel")
     local_mel = net.local_mel if args.local_mel else None      # (--local-dir on such a checkpoint: the feature files win)
@@ -195,12 +261,29 @@ def main(argv=None):
     print("files: {} batch_size: {} train_width: {}".format(len(files), args.batch_size, args.train_width))
     if not files:
         raise Exception("no .wav file in {}".format(args.wav_dir))
+    corpus = None
+    if args.corpus:
+        corpus = load_corpus(net, params, args.wav_dir, files, local_dir=args.local_dir, local_mel=local_mel)
+        counts = corpus.windows(args.train_width, args.local_crop or "frame")
+        for fn, n, c in zip(files, corpus.file_len, counts):
+            if c == 0:
+                print("leaving out {}: its {} samples hold no crop of input_width + train_width".format(fn, int(n)))
+        if int(counts.sum()) == 0:
+            raise Exception("signal too short for input_width + train_width: no file of {} holds a crop".format(args.wav_dir))
+        print("corpus: {} samples and {} training windows in {} files, {} bytes on the device".format(
+            int(corpus.tokens.size), int(counts.sum()), int((counts > 0).sum()), corpus.device_bytes()))
     start_time = time.time()
     graphs = {}
     average_loss = None
     for epoch in range(1, args.max_epoch):                          # train.py:118: epochs 1 .. max_epoch - 1
         average_loss = 0.0
         for fn in files:
+            if corpus is not None:                                  # as many updates, and checkpoints, as the per-file loop makes
+                average_loss += train_corpus(net, params, corpus, batch_size=args.batch_size, train_width=args.train_width,
+                                             repeat=args.repeat, use_graph=not args.no_graph, state=graphs,
+                                             local_crop=args.local_crop or "frame")
+                net.save(args.model_dir)
+                continue
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
                                         use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir,
