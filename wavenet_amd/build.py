@@ -1,6 +1,8 @@
 """Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950 -- all but the sources of ``SIDE_LIBS``:
 logmel.hip becomes wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h) and corpus.hip wavenet_amd/libwavenet_corpus.so
-(include/wavenet_corpus.h), libraries of their own: the first one's exports are pinned.
+(include/wavenet_corpus.h), libraries of their own: the first one's exports are pinned.  ``FRONT_LIBS`` does the same for the
+sources of wavenet_amd/csrc/front/, which the ``csrc/*.hip`` glob does not see: front/resample.hip becomes
+wavenet_amd/libwavenet_resample.so (include/wavenet_resample.h).
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the .so then travels
 in-tree to the GPU box.  Usage: ``python -m wavenet_amd.build [--force]``.
@@ -23,6 +25,11 @@ CORPUS_LIB = os.path.join(HERE, "libwavenet_corpus.so")
 SIDE_LIBS = {
     "logmel.hip": (LOGMEL_LIB, "logmel_exports.map"),
     "corpus.hip": (CORPUS_LIB, "corpus_exports.map"),
+}
+RESAMPLE_LIB = os.path.join(HERE, "libwavenet_resample.so")
+# source below csrc/ -> (library, version script): front ends in a directory of their own, one library each
+FRONT_LIBS = {
+    "front/resample.hip": (RESAMPLE_LIB, "front/resample_exports.map"),
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
@@ -68,8 +75,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _link(LIB, [o for o in objs if o not in side.values()], "exports.map", force)
     for src, (lib, version_script) in SIDE_LIBS.items():
         _link(lib, [side[src]], version_script, force)
+    for src, (lib, version_script) in FRONT_LIBS.items():
+        _link(lib, [_compile(os.path.join(CSRC, src), force, hdr)], version_script, force)
     if verbose:
-        for lib in [LIB] + [lib for lib, _ in SIDE_LIBS.values()]:
+        for lib in [LIB] + [lib for lib, _ in list(SIDE_LIBS.values()) + list(FRONT_LIBS.values())]:
             print("built", lib)
     return LIB
 

@@ -98,11 +98,33 @@ def trim_silence(quantized_signal, silence_threshold: int = 1, compat: bool = Tr
     return q[start:q.size - end + 1]
 
 
+def _convertible(filename, signal) -> np.ndarray:
+    """The left channel of a wav file as the rate converter takes it: int16 PCM as it is, float samples as float32; any
+    other format is refused, the file named."""
+    if signal.ndim > 1:
+        signal = signal[:, 0]
+    if signal.dtype == np.int16:
+        return np.ascontiguousarray(signal)
+    if signal.dtype.kind == "f":
+        return np.ascontiguousarray(signal, dtype=np.float32)
+    raise Exception("%s holds %s samples: only 16-bit PCM and float wav files are converted to another rate" % (filename, signal.dtype))
+
+
 def load_audio_file(filename, quantization_steps: int = 256, format: str = "16bit_pcm", compat: bool = True,
-                    compat_mono_int_division: bool = False):
-    """wav file -> (mu-law tokens int32 with silence trimmed, sampling rate)   (data.py:5-35)."""
+                    compat_mono_int_division: bool = False, rate=None, device=None):
+    """wav file -> (mu-law tokens int32 with silence trimmed, sampling rate)   (data.py:5-35).
+
+    ``rate=R`` (new): a file at another rate is brought to R first -- its left channel through ``resample.Resampler`` to 16-bit
+    PCM and the tokens of that (on ``device``; ``device=None``: the numpy definition), then the silence trim -- and R is the
+    rate returned; a file already at R takes the path below.  Only 16-bit PCM and float files are converted."""
     from scipy.io import wavfile
     sampling_rate, signal = wavfile.read(filename)
+    if rate is not None and int(rate) != int(sampling_rate):
+        from . import resample
+        tokens = resample.resampler(sampling_rate, rate, device)(_convertible(filename, signal), out="tokens",
+                                                                 quantization_steps=quantization_steps)
+        tokens = np.asarray(tokens.cpu() if hasattr(tokens, "cpu") else tokens, dtype=np.int32)
+        return trim_silence(tokens, 1, compat), int(rate)
     scale, _ = _pcm_format(format, compat)
     if signal.ndim > 1:
         signal = signal[:, 0].astype(float)            # left channel only
@@ -112,6 +134,29 @@ def load_audio_file(filename, quantization_steps: int = 256, format: str = "16bi
     else:
         signal = signal.astype(float) / scale
     return trim_silence(mulaw_encode(signal, quantization_steps), 1, compat), sampling_rate
+
+
+def load_audio_files(paths, rate, quantization_steps: int = 256, device=None, compat: bool = True):
+    """``load_audio_file(p, quantization_steps, rate=rate, device=device)[0]`` for every path, the files that need converting
+    grouped by their own rate: one cached ``resample.Resampler`` per rate pair, 64 files per launch (``Resampler.batch``: the
+    bits of the single calls).  Returns the token arrays in the order of ``paths``; every one is at ``rate``."""
+    from scipy.io import wavfile
+    from . import resample
+    out, groups = [None] * len(paths), {}
+    for i, p in enumerate(paths):
+        file_rate, signal = wavfile.read(p)
+        if int(file_rate) == int(rate):
+            out[i] = load_audio_file(p, quantization_steps, compat=compat)[0]
+        else:
+            groups.setdefault((int(file_rate), signal.dtype == np.int16), []).append((i, _convertible(p, signal)))
+    for (file_rate, _), members in sorted(groups.items()):           # a launch reads one kind of samples
+        rs = resample.resampler(file_rate, rate, device)
+        for at in range(0, len(members), resample.RESAMPLE_MAX_CLIPS):
+            part = members[at:at + resample.RESAMPLE_MAX_CLIPS]
+            for (i, _), tok in zip(part, rs.batch([x for _, x in part], out="tokens", quantization_steps=quantization_steps)):
+                tok = np.asarray(tok.cpu() if hasattr(tok, "cpu") else tok, dtype=np.int32)
+                out[i] = trim_silence(tok, 1, compat)
+    return out
 
 
 def mulaw_decode(quantized_signal, quantization_steps: int = 256, compat: bool = True) -> np.ndarray:

@@ -92,6 +92,14 @@ _CORPUS_FLAGS = (
                                  "one file after the other.  An epoch stays files x --repeat updates, with a checkpoint every "
                                  "--repeat.  A property of the run, not of the checkpoint"),
 )
+# files at any rate (wavenet_amd/resample.py; data.load_audio_file(..., rate=)): off, an attribute of the namespace only when given
+_RESAMPLE_FLAGS = (
+    (("--resample",), None, False, "train, generate: bring every .wav file that is read (the training files, --valid-wav-dir, "
+                                   "--prompt, --keep, --from-wav) to the model's sampling_rate on the device before it is "
+                                   "encoded, and make --local-mel features at that rate; a file already at that rate is read as "
+                                   "without the flag.  Without it a file's samples are taken as they are, whatever its rate.  "
+                                   "A property of the run, not of the checkpoint"),
+)
 # likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
 # attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
 _LIKELIHOOD_FLAGS = (
@@ -153,6 +161,7 @@ class Args(argparse.Namespace):
     local_mel, mels, win, from_wav = False, None, None, None
     storage = "fp32"
     corpus = False
+    resample = False
     report, best_of = None, 1
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
@@ -166,7 +175,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

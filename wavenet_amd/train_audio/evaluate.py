@@ -34,19 +34,23 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--local-mel", action="store_true", default=argparse.SUPPRESS,
                     help="score every file under the log-mel features of the file itself, made on the device (a checkpoint trained "
                          "with train --local-mel); --local-dir, when given too, wins")
+    ap.add_argument("--resample", action="store_true", default=argparse.SUPPRESS,
+                    help="bring every file to the model's sampling_rate on the device before it is encoded (and make --local-mel "
+                         "features at that rate); without it a file's samples are taken as they are, whatever its rate")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
     return ap
 
 
 def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None,
-                 local_mel=None):
+                 local_mel=None, resample=False):
     """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
     "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
     samples, and prints one line per file and one for the total unless ``verbose`` is off.  A checkpoint conditioned on
     speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run.
     A locally conditioned checkpoint scores every file under its feature file in ``local_dir`` (train_audio/local.py); the
     pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop.  ``local_mel`` ({"win": W}, the
-    checkpoint's "mel" entry): without ``local_dir``, every file is scored under the log-mel features of its own tokens."""
+    checkpoint's "mel" entry): without ``local_dir``, every file is scored under the log-mel features of its own tokens.
+    ``resample``: every file is read at the model's sampling_rate (``data.load_audio_file(..., rate=)``, on the network's device)."""
     local = getattr(net, "local", None)
     _local.require_match(local, local_dir is not None or local_mel is not None, "evaluate", "--local-dir FEAT_DIR or --local-mel")
     if local is not None:
@@ -58,7 +62,8 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     labels = getattr(net, "speakers", None)
     cids = {fn: None if labels is None else _speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files}
     for fn in files:
-        tokens, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
+        rkw = dict(rate=int(params.sampling_rate), device=net.device) if resample else {}
+        tokens, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps, **rkw)
         lkw = {} if local is None else {"local": _local.with_extra_column(
             _local.file_or_mel_features(local_dir, local_mel, fn, tokens, rate, local[0], local[1], params.quantization_steps),
             getattr(net, "local_interp", "repeat"), getattr(net, "local_upsample", 1))}
@@ -86,7 +91,8 @@ def main(argv=None):
             os.path.join(args.model_dir, _local.FILE)))
     params, net = _model.build(args)
     table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
-                         local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None)
+                         local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None,
+                         resample=bool(getattr(args, "resample", False)))
     if args.json:
         with open(args.json, "w") as f:
             json.dump(table, f, indent=2)

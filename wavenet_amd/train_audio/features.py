@@ -5,7 +5,9 @@
 A file is read as training reads it (``data.load_audio_file``: mu-law tokens, silence trimmed) and the spectrogram is taken
 of those tokens decoded back to a waveform, so column k belongs to tokens k * hop .. (k + 1) * hop - 1 of what the network
 sees.  See wavenet_amd/features.py for the definition.  ``--device`` writes the same files from the kernel
-(``features.LogMel.batch`` over the tokens, at most 64 files per launch): float32 sums in place of float64 ones."""
+(``features.LogMel.batch`` over the tokens, at most 64 files per launch): float32 sums in place of float64 ones.
+``--resample -m MODEL_DIR`` (or ``--rate R``) reads every file at the model's sampling_rate, as ``train --resample`` does (on the
+GPU with ``--device``, else by the numpy definition), and the filterbank is that rate's."""
 from __future__ import annotations
 
 import argparse
@@ -27,12 +29,36 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--quantization-steps", type=int, default=256, help="the model's quantization_steps")
     ap.add_argument("--device", action="store_true",
                     help="compute on the GPU (features.LogMel): the values that train --local-mel and generate --from-wav see")
+    ap.add_argument("--resample", action="store_true", default=argparse.SUPPRESS,
+                    help="bring every file to the rate of -m MODEL_DIR's wavenet.json (or --rate R) before it is encoded")
+    ap.add_argument("-m", "--model-dir", type=str, default=argparse.SUPPRESS, help="--resample: where wavenet.json lies")
+    ap.add_argument("--rate", type=int, default=argparse.SUPPRESS, help="--resample: the rate itself")
     return ap
 
 
-def device_features(paths, quantization_steps, mels, hop, win):
-    """[(tokens, (F, frames) float32 array)] of wav files, LogMel.batch over each run of files that share a sampling rate."""
-    loaded = [data.load_audio_file(p, quantization_steps=quantization_steps) for p in paths]
+def target_rate(args):
+    """None without --resample, else the rate it converts to: --rate R, or sampling_rate of -m MODEL_DIR's wavenet.json."""
+    if not getattr(args, "resample", False):
+        if hasattr(args, "rate") or hasattr(args, "model_dir"):
+            raise SystemExit("features: --rate R and -m MODEL_DIR go with --resample")
+        return None
+    if hasattr(args, "rate"):
+        if args.rate < 1:
+            raise SystemExit("features: --rate R needs R >= 1, got {}".format(args.rate))
+        return int(args.rate)
+    if not hasattr(args, "model_dir"):
+        raise SystemExit("features: --resample needs the rate to convert to: give -m MODEL_DIR or --rate R")
+    from . import model as _model
+    return int(_model.load_params(args.model_dir).sampling_rate)
+
+
+def device_features(paths, quantization_steps, mels, hop, win, rate=None):
+    """[(tokens, (F, frames) float32 array)] of wav files, LogMel.batch over each run of files that share a sampling rate.
+    ``rate``: every file is read at that rate (converted on the device)."""
+    if rate is None:
+        loaded = [data.load_audio_file(p, quantization_steps=quantization_steps) for p in paths]
+    else:
+        loaded = [(t, rate) for t in data.load_audio_files(paths, rate, quantization_steps, "cuda")]
     feats = [None] * len(paths)
     for rate in sorted({r for _, r in loaded}):
         mel = features.LogMel(rate, n_mels=mels, hop=hop, win=win)
@@ -46,6 +72,7 @@ def device_features(paths, quantization_steps, mels, hop, win):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    to_rate = target_rate(args)
     files = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
     if not files:
         raise SystemExit("no .wav file in {}".format(args.wav_dir))
@@ -54,7 +81,7 @@ def main(argv=None):
     if args.device:
         features._check_logmel_shape(args.mels, args.hop, args.win)      # before any file is read
         got = device_features([os.path.join(args.wav_dir, fn) for fn in files], args.quantization_steps, args.mels, args.hop,
-                              args.win)
+                              args.win, to_rate)
         for fn, (tokens, feats) in zip(files, got):
             out = feature_path(args.output_dir, fn)
             np.save(out, feats)
@@ -62,7 +89,8 @@ def main(argv=None):
             written.append(out)
         return written
     for fn in files:
-        tokens, rate = data.load_audio_file(os.path.join(args.wav_dir, fn), quantization_steps=args.quantization_steps)
+        tokens, rate = data.load_audio_file(os.path.join(args.wav_dir, fn), quantization_steps=args.quantization_steps,
+                                            rate=to_rate)
         signal = data.mulaw_decode(tokens, args.quantization_steps)
         feats = features.log_mel(signal, rate, n_mels=args.mels, hop=args.hop, win=args.win)
         out = feature_path(args.output_dir, fn)

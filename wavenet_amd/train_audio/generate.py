@@ -348,7 +348,8 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
 def from_wav_job(args, config, n_utt, chunk_frames):
     """``generate --fast --from-wav FILE.wav``: every file read as training reads it and its log-mel features made on the device with
     the checkpoint's "mel" settings -> (one (F, frames) array per utterance, None), or with ``--chunk-frames`` (None, the streamed
-    run's ``MelColumns``: nothing is computed yet, the column count follows from the file's length).  Stops
+    run's ``MelColumns``: nothing is computed yet, the column count follows from the file's length).  ``--resample``: the file is
+    brought to the model's rate first, in one call also for a streamed run -- the silence trim needs the file's end.  Stops
     before a model is built when the checkpoint was not trained with ``train --local-mel``."""
     mel = _local.load_mel(args.model_dir)
     if mel is None:
@@ -360,7 +361,7 @@ def from_wav_job(args, config, n_utt, chunk_frames):
         for f in sorted(set(args.from_wav)):
             if not os.path.isfile(f):
                 raise SystemExit("generate: --from-wav {} is missing".format(f))
-            tokens, rate = data.load_audio_file(f, quantization_steps=Q)
+            tokens, rate = data.load_audio_file(f, quantization_steps=Q, **read_kw(args, _model.load_params(args.model_dir)))
             if chunk_frames is not None:                 # streamed (one file): the analyser makes the columns as they are asked for
                 extra = (1 if _local.load_interp(args.model_dir) == "linear" else 0) + (1 if _local.load_upsample(args.model_dir) > 1 else 0)
                 return None, MelColumns(_local.mel_analyser(rate, config[0], config[1], mel["win"]), tokens, Q, chunk_frames, extra)
@@ -369,18 +370,26 @@ def from_wav_job(args, config, n_utt, chunk_frames):
     return [distinct[f] for f in files], None
 
 
-def read_prompt(path, params):
+def read_kw(args, params):
+    """The keywords of ``data.load_audio_file`` that ``--resample`` adds: the model's rate, and the device that converts."""
+    if not args.resample:
+        return {}
+    return dict(rate=int(params.sampling_rate), device="cuda:%d" % args.gpu_device)
+
+
+def read_prompt(path, params, rkw={}):
     """The window a generation continues from: the file's tokens as training reads them (``data.load_audio_file``: mu-law,
-    silence trimmed), their last ``input_width``, left-padded with the silence token when the file is shorter."""
+    silence trimmed; ``rkw``, the keywords of ``read_kw``: at the model's rate), their last ``input_width``, left-padded with
+    the silence token when the file is shorter."""
     Q = params.quantization_steps
     iw = input_width_of(params)
-    tokens, _ = data.load_audio_file(path, quantization_steps=Q)
+    tokens, _ = data.load_audio_file(path, quantization_steps=Q, **rkw)
     tokens = np.asarray(tokens, dtype=np.int32)[-iw:]
     return np.concatenate([silence_window(Q, iw - tokens.size), tokens])
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None):
+                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None, rkw={}):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance.
     ``best_of`` = K > 1 (``fast`` only): N * K candidates in that run, row ``u * K + c`` candidate c of utterance u, the
@@ -390,7 +399,7 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     N = len(prompt_files)
     n = int(sampling_rate * generate_sec) - 1
     silence = silence_window(Q, input_width_of(params))
-    read = {f: read_prompt(f, params) for f in set(prompt_files) if f is not None}
+    read = {f: read_prompt(f, params, rkw) for f in set(prompt_files) if f is not None}
     prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
     start_time = time.time()
     ranked = None
@@ -540,7 +549,7 @@ def keep_job(args, seconds_given):
     read = {}
     for f in files:
         if f not in read:
-            t = np.asarray(data.load_audio_file(f, quantization_steps=Q)[0], dtype=np.int32)
+            t = np.asarray(data.load_audio_file(f, quantization_steps=Q, **read_kw(args, params))[0], dtype=np.int32)
             if t.size < W + 2:
                 raise SystemExit("generate: --keep {} holds {} samples as training reads it; the window takes {} and the decoder "
                                  "runs two more at least: {} are needed".format(f, t.size, W, W + 2))
@@ -659,7 +668,7 @@ def main(argv=None):
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
                                    top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of,
-                                   report=report)
+                                   report=report, rkw=read_kw(args, params))
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                           condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report)

@@ -96,14 +96,22 @@ class _Crops(object):
         return (x, tgt) if self.features is None else (x, tgt, feats)
 
 
+def read_file(path, params, device=None, resample=False):
+    """(tokens, rate) of a .wav file as training reads it; ``resample``: brought to the model's sampling_rate on ``device``
+    first (``--resample``), and that rate is the one returned."""
+    if not resample:
+        return data.load_audio_file(path, quantization_steps=params.quantization_steps)
+    return data.load_audio_file(path, quantization_steps=params.quantization_steps, rate=int(params.sampling_rate), device=device)
+
+
 def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat=1000, use_graph=True, state=None,
-                local_dir=None, local_crop="frame", local_mel=None):
+                local_dir=None, local_crop="frame", local_mel=None, resample=False):
     """One file: returns the summed loss of its ``repeat`` updates (train.py:24-90).  ``local_dir``: where the file's feature
     file lies (a locally conditioned model); crops then start on a feature column border (``local_crop="frame"``) or at any
     sample, each with its own phase (``"sample"``: the crops a run without features draws).  ``local_mel`` ({"win": W},
     ``--local-mel``): no feature file -- the log-mel features of the file's tokens, made on the device here, once per call;
-    from there on the array takes the feature file's path."""
-    signals, rate = data.load_audio_file(path_to_file, quantization_steps=params.quantization_steps)
+    from there on the array takes the feature file's path.  ``resample``: the file is read at the model's rate (``read_file``)."""
+    signals, rate = read_file(path_to_file, params, net.device, resample)
     iw = input_width_of(params)
     silence = 127 if params.quantization_steps > 127 else params.quantization_steps // 2
     local = getattr(net, "local", None)
@@ -179,17 +187,20 @@ def run_updates(net, params, draw, repeat, key, use_graph, state, name, width):
     return float(sum_loss.item())
 
 
-def load_corpus(net, params, wav_dir, files, local_dir=None, local_mel=None):
+def load_corpus(net, params, wav_dir, files, local_dir=None, local_mel=None, resample=False):
     """``--corpus``: every .wav file of ``files`` loaded once -- its tokens, its features (the feature file of ``local_dir``, or
     the log-mel of its own tokens made on the device, up to 64 files per launch: the bits of the single calls) and its
-    speaker's class id -- packed into a ``Corpus`` on the network's device."""
+    speaker's class id -- packed into a ``Corpus`` on the network's device.  ``resample``: the files are read at the model's rate,
+    converted on the device 64 per launch (``data.load_audio_files``)."""
     local = getattr(net, "local", None)
     _local.require_match(local, local_dir is not None or local_mel is not None, "train", "--local-dir FEAT_DIR or --local-mel")
-    tokens, rates = [], []
-    for fn in files:
-        signals, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps)
-        tokens.append(signals.astype(np.int32))
-        rates.append(rate)
+    paths = [os.path.join(wav_dir, fn) for fn in files]
+    if resample:
+        rate = int(params.sampling_rate)
+        loaded = [(t, rate) for t in data.load_audio_files(paths, rate, params.quantization_steps, net.device)]
+    else:
+        loaded = [data.load_audio_file(p, quantization_steps=params.quantization_steps) for p in paths]
+    tokens, rates = [t.astype(np.int32) for t, _ in loaded], [r for _, r in loaded]
     feats = None
     if local is not None and local_dir is not None:
         feats = [_local.file_features(local_dir, fn, t.size, local[0], local[1]) for fn, t in zip(files, tokens)]
@@ -223,16 +234,16 @@ def train_corpus(net, params, corpus, batch_size=16, train_width=16, repeat=1000
                        int(corpus.tokens.size))
 
 
-def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None):
+def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None, resample=False):
     """The held-out negative log-likelihood after an epoch: one line for the weights being trained and, when a weight
     average is kept, one for the averaged weights."""
     def line(what, total):
         sys.stdout.write("epoch: {} - held-out {}: {:.6f} nats/sample  {:.6f} bits/sample  ({} samples)\n".format(
             epoch, what, total["nats_per_sample"], total["bits_per_sample"], total["samples"]))
-    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel)["total"])
+    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample)["total"])
     if net.ema_enabled:
         with net.ema_weights():
-            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel)["total"])
+            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample)["total"])
     sys.stdout.flush()
 
 
@@ -263,7 +274,8 @@ def main(argv=None):
         raise Exception("no .wav file in {}".format(args.wav_dir))
     corpus = None
     if args.corpus:
-        corpus = load_corpus(net, params, args.wav_dir, files, local_dir=args.local_dir, local_mel=local_mel)
+        corpus = load_corpus(net, params, args.wav_dir, files, local_dir=args.local_dir, local_mel=local_mel,
+                             resample=args.resample)
         counts = corpus.windows(args.train_width, args.local_crop or "frame")
         for fn, n, c in zip(files, corpus.file_len, counts):
             if c == 0:
@@ -287,7 +299,7 @@ def main(argv=None):
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
                                         use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir,
-                                        local_crop=args.local_crop or "frame", local_mel=local_mel)
+                                        local_crop=args.local_crop or "frame", local_mel=local_mel, resample=args.resample)
             net.save(args.model_dir)
         average_loss /= len(files)
         sys.stdout.write("\033[2K\repoch: {} - {:.4e} loss - {} min\n".format(
@@ -295,7 +307,7 @@ def main(argv=None):
         sys.stdout.flush()
         net.save(args.model_dir)
         if args.valid_wav_dir:
-            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir, local_mel=local_mel)
+            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir, local_mel=local_mel, resample=args.resample)
     return average_loss
 
 
