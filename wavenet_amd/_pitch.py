@@ -1,0 +1,53 @@
+"""ctypes binding of libwavenet_pitch.so (include/wavenet_pitch.h): the pitch tracker, a library of its own next to
+libwavenet_hip.so.  No fallback: a missing library or a failing call raises."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+from ._lib import WaveNetHipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libwavenet_pitch.so")
+ABI_VERSION = 1
+WNP_OK, WNP_EARG, WNP_EHIP = 0, -1, -3
+WN_PITCH_MAX_CLIPS = 64                       # clips per launch
+WN_PITCH_START, WN_PITCH_END = 1, 2           # WnPitchClip.flags: that edge of the buffer is the signal's, zero beyond it
+
+
+class WnPitchClip(C.Structure):
+    """One clip of a wn_pitch launch."""
+    _fields_ = [("x", C.c_void_p), ("n", C.c_int64), ("origin", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64),
+                ("curve", C.c_void_p), ("first", C.c_int32), ("count", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+_SIGS = {
+    "wn_pitch_abi_version": (C.c_int, []),
+    "wn_pitch_last_error": (C.c_char_p, []),
+    "wn_pitch": (C.c_int, [C.POINTER(WnPitchClip), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                           C.c_float, C.c_void_p]),
+}
+EXPORTS = tuple(_SIGS)
+_lib: Optional[C.CDLL] = None
+
+
+def lib() -> C.CDLL:
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise WaveNetHipError("%s not found: build it with `python -m wavenet_amd.build` (hipcc, gfx950)" % LIB_PATH)
+        l = C.CDLL(LIB_PATH)
+        for name, (res, args) in _SIGS.items():
+            fn = getattr(l, name)
+            fn.restype = res
+            fn.argtypes = args
+        if l.wn_pitch_abi_version() != ABI_VERSION:
+            raise WaveNetHipError("ABI mismatch: %s is version %d, the binding %d" % (LIB_PATH, l.wn_pitch_abi_version(), ABI_VERSION))
+        _lib = l
+    return _lib
+
+
+def check(rc: int, what: str = "wn_pitch") -> None:
+    if rc != 0:
+        raise WaveNetHipError("%s failed (%d): %s" % (what, rc, lib().wn_pitch_last_error().decode("utf-8", "replace")))

@@ -2,7 +2,8 @@
 logmel.hip becomes wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h) and corpus.hip wavenet_amd/libwavenet_corpus.so
 (include/wavenet_corpus.h), libraries of their own: the first one's exports are pinned.  ``FRONT_LIBS`` does the same for the
 sources of wavenet_amd/csrc/front/, which the ``csrc/*.hip`` glob does not see: front/resample.hip becomes
-wavenet_amd/libwavenet_resample.so (include/wavenet_resample.h).
+wavenet_amd/libwavenet_resample.so (include/wavenet_resample.h).  ``ANALYSIS_LIBS`` is the same table for wavenet_amd/csrc/analysis/:
+analysis/pitch.hip becomes wavenet_amd/libwavenet_pitch.so (include/wavenet_pitch.h).
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the .so then travels
 in-tree to the GPU box.  Usage: ``python -m wavenet_amd.build [--force]``.
@@ -30,6 +31,11 @@ RESAMPLE_LIB = os.path.join(HERE, "libwavenet_resample.so")
 # source below csrc/ -> (library, version script): front ends in a directory of their own, one library each
 FRONT_LIBS = {
     "front/resample.hip": (RESAMPLE_LIB, "front/resample_exports.map"),
+}
+PITCH_LIB = os.path.join(HERE, "libwavenet_pitch.so")
+# source below csrc/ -> (library, version script): analysers of audio, handled like the front ends
+ANALYSIS_LIBS = {
+    "analysis/pitch.hip": (PITCH_LIB, "analysis/pitch_exports.map"),
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
@@ -75,10 +81,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _link(LIB, [o for o in objs if o not in side.values()], "exports.map", force)
     for src, (lib, version_script) in SIDE_LIBS.items():
         _link(lib, [side[src]], version_script, force)
-    for src, (lib, version_script) in FRONT_LIBS.items():
+    for src, (lib, version_script) in list(FRONT_LIBS.items()) + list(ANALYSIS_LIBS.items()):
         _link(lib, [_compile(os.path.join(CSRC, src), force, hdr)], version_script, force)
     if verbose:
-        for lib in [LIB] + [lib for lib, _ in list(SIDE_LIBS.values()) + list(FRONT_LIBS.values())]:
+        for lib in [LIB] + [lib for lib, _ in list(SIDE_LIBS.values()) + list(FRONT_LIBS.values()) + list(ANALYSIS_LIBS.values())]:
             print("built", lib)
     return LIB
 

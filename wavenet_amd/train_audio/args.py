@@ -112,6 +112,15 @@ _LIKELIHOOD_FLAGS = (
                              "With --keep the figure covers the kept samples too: a candidate is judged by how the real audio "
                              "continues from what was drawn into it"),
 )
+# what --best-of ranks on (wavenet_amd/metrics.py; train_audio/generate.py rank_job / MelRank): likelihood, an attribute of the
+# namespace only when given, checked by generate before the model is built
+_RANK_FLAGS = (
+    (("--rank",), str, "likelihood", "generate --fast --from-wav FILE.wav --best-of K: what the K candidates are ranked on, 'likelihood' "
+                                     "(lowest nats per sample) or 'mel' (the smallest log-spectral distance on the mel scale to the "
+                                     "recording's own columns, the candidates analysed on the device in one batch; --report then "
+                                     "carries each kept file's log_mel_distance_db).  'mel' goes with --from-wav only, not with "
+                                     "--chunk-frames"),
+)
 # streaming synthesis (FasterWaveNet.open_stream; train_audio/generate.py stream_job / generate_streamed): off, attributes of the
 # namespace only when given, checked by generate before the model is built
 _STREAM_FLAGS = (
@@ -163,6 +172,7 @@ class Args(argparse.Namespace):
     corpus = False
     resample = False
     report, best_of = None, 1
+    rank = "likelihood"
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
     tile = None
@@ -175,7 +185,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _LIKELIHOOD_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

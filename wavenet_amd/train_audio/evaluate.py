@@ -2,6 +2,7 @@
 teacher-forced, in nats and bits per sample -- the held-out number that tells overfitting from learning.
 
     python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model [--ema] [--json scores.json]
+    python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model --copy-synthesis [--seconds S] [--seed N] [--json FILE]
 
 Files are read as training reads them (mu-law tokens, silence trimmed) and scored by ``WaveNet.score``.  The command has
 its own parser: it shares ``-g / -w / -m`` with train and generate and takes none of their other flags."""
@@ -38,7 +39,110 @@ def build_parser() -> argparse.ArgumentParser:
                     help="bring every file to the model's sampling_rate on the device before it is encoded (and make --local-mel "
                          "features at that rate); without it a file's samples are taken as they are, whatever its rate")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
+    # copy synthesis (wavenet_amd/metrics.py; copy_synthesis_dir below): present in the namespace only when given
+    ap.add_argument("--copy-synthesis", action="store_true", default=argparse.SUPPRESS,
+                    help="instead of scoring, resynthesise every file from its own features (a checkpoint trained with train "
+                         "--local-mel; the fast decoder, all files in one batched run) and print how close the result is: the "
+                         "log-spectral distance on the mel scale in dB, the F0 error in cents, gross F0 errors and the voiced / "
+                         "unvoiced error, against the file itself")
+    ap.add_argument("--seconds", type=float, default=argparse.SUPPRESS, metavar="S", help="--copy-synthesis: at most S seconds of every file")
+    ap.add_argument("--seed", type=int, default=argparse.SUPPRESS, metavar="N", help="--copy-synthesis: numpy seed of the draws")
+    ap.add_argument("--temperature", type=float, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
+    ap.add_argument("--top-k", type=int, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
+    ap.add_argument("--top-p", type=float, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
     return ap
+
+
+COPY_FLAGS = ("seconds", "seed", "temperature", "top_k", "top_p")
+COPY_KEYS = ("log_mel_distance_db", "f0_rmse_cents", "f0_gross_error", "vuv_error", "voiced_frames", "nats_per_sample")
+
+
+def copy_synthesis_job(args):
+    """``evaluate --copy-synthesis``: the checks, made before a model is built.  Returns None without the flag, else the keywords
+    of ``copy_synthesis_dir`` that the command line gives."""
+    given = [f for f in COPY_FLAGS if hasattr(args, f)]
+    if not getattr(args, "copy_synthesis", False):
+        if given:
+            raise SystemExit("evaluate: {} go{} with --copy-synthesis".format(
+                ", ".join("--" + f.replace("_", "-") for f in given), "es" if len(given) == 1 else ""))
+        return None
+    if _local.load_mel(args.model_dir) is None:
+        raise SystemExit("evaluate: --copy-synthesis compares mel columns and needs the mel parameters of a checkpoint trained with "
+                         "train --local-mel ({} has no \"mel\")".format(os.path.join(args.model_dir, _local.FILE)))
+    kw = {f: getattr(args, f) for f in given}
+    if "seconds" in kw and not kw["seconds"] > 0:
+        raise SystemExit("evaluate: --seconds S needs S > 0, got {}".format(kw["seconds"]))
+    from .. import sampling
+    try:
+        sampling.check_controls(kw.get("temperature", 1.0), kw.get("top_k", 0), kw.get("top_p", 1.0))
+    except ValueError as e:
+        raise SystemExit("evaluate: {}".format(e))
+    return kw
+
+
+def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=None, resample=False, verbose: bool = True,
+                       **controls):
+    """Resynthesise every .wav file of ``wav_dir`` (sorted by name) from its own features and compare the result with the file:
+    ``metrics.copy_synthesis`` over all files, one ``generate_batch`` run (``net``: a ``FasterWaveNet`` whose checkpoint has
+    "mel" in local.json).  A file is read as training reads it (``resample``: at the model's rate) and cut to ``seconds``; its
+    features are its feature file in ``local_dir`` or, without one, its log-mel columns made on the device; its speaker is the
+    label its name carries.  ``seed``: numpy's, set once before the files' uniforms are drawn in order.  ``controls``:
+    temperature, top_k, top_p.  Returns ``{"files": [{"file", "samples", "log_mel_distance_db", "f0_rmse_cents",
+    "f0_gross_error", "vuv_error", "voiced_frames", "nats_per_sample"}, ...], "total": {...}}`` -- the total weighted by what each
+    figure was averaged over (``metrics.total``: compared columns, frames voiced in both, emitted samples) -- and prints one line
+    per file and one for the total unless ``verbose`` is off."""
+    import numpy as np
+    import torch
+    from .. import metrics
+    from ..pitch import Pitch
+    local, mel = getattr(net, "local", None), getattr(net, "local_mel", None)
+    if local is None or mel is None:
+        raise SystemExit("evaluate: --copy-synthesis needs a checkpoint trained with train --local-mel")
+    files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
+    if not files:
+        raise Exception("no .wav file in {}".format(wav_dir))
+    Q, W = params.quantization_steps, int(net.input_width)
+    labels = getattr(net, "speakers", None)
+    cids = None if labels is None else [_speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files]
+    tokens, feats, rates = [], [], []
+    rkw = dict(rate=int(params.sampling_rate), device=net.device) if resample else {}
+    with torch.cuda.device(net.device):
+        for fn in files:
+            t, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=Q, **rkw)
+            t = np.asarray(t, dtype=np.int32)
+            if seconds is not None:
+                t = t[:int(rate * seconds)]
+            if t.size < W + 2:
+                raise SystemExit("evaluate: --copy-synthesis: {} holds {} samples{}; the window takes {} and the decoder runs two more "
+                                 "at least".format(fn, t.size, "" if seconds is None else " within --seconds {}".format(seconds), W))
+            tokens.append(t)
+            rates.append(int(rate))
+            feats.append(_local.with_extra_column(
+                _local.file_or_mel_features(local_dir, mel, fn, t, rate, local[0], local[1], Q),
+                getattr(net, "local_interp", "repeat"), getattr(net, "local_upsample", 1)))
+        if len(set(rates)) > 1:
+            raise SystemExit("evaluate: --copy-synthesis analyses all files on one column grid, and {} holds files at {} Hz: give "
+                             "--resample".format(wav_dir, ", ".join(str(r) for r in sorted(set(rates)))))
+        try:
+            pitch = Pitch(rates[0], hop=local[1], win=mel["win"], device=net.device)
+        except ValueError as e:
+            raise SystemExit("evaluate: --copy-synthesis: {}".format(e))
+        if seed is not None:
+            np.random.seed(seed)
+        uniforms = [np.random.random_sample(t.size - W) for t in tokens]
+        got = metrics.copy_synthesis(net, tokens, feats, cids, uniforms, _local.mel_analyser(rates[0], local[0], local[1], mel["win"]),
+                                     pitch, **controls)
+    table = {"files": [dict([("file", fn), ("samples", r["samples"])] + [(k, r[k]) for k in COPY_KEYS]) for fn, r in zip(files, got)]}
+    whole = metrics.total(got)
+    table["total"] = dict([("samples", whole["samples"])] + [(k, whole[k]) for k in COPY_KEYS])
+    if verbose:
+        fmt = lambda v, spec: "-" if v is None else format(v, spec)
+        for r in table["files"] + [dict(file="total", **table["total"])]:
+            sys.stdout.write("{:<32} {:>10d} samples  {} dB log-mel  {} cents F0 ({} gross, {} voiced frames)  {} V/UV  {} nats/sample\n".format(
+                r["file"], r["samples"], fmt(r["log_mel_distance_db"], ".4f"), fmt(r["f0_rmse_cents"], ".2f"),
+                fmt(r["f0_gross_error"], ".4f"), r["voiced_frames"], fmt(r["vuv_error"], ".4f"), fmt(r["nats_per_sample"], ".6f")))
+        sys.stdout.flush()
+    return table
 
 
 def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None,
@@ -84,7 +188,16 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    args.fast, args.seed = False, None                       # what train_audio.model.build reads beyond the shared flags
+    copy = copy_synthesis_job(args)                          # before a model is built
+    args.fast, args.seed = copy is not None, None            # what train_audio.model.build reads beyond the shared flags
+    if copy is not None:
+        params, net = _model.build(args)
+        table = copy_synthesis_dir(net, params, args.wav_dir, local_dir=getattr(args, "local_dir", None),
+                                   resample=bool(getattr(args, "resample", False)), **copy)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(table, f, indent=2)
+        return table
     want_mel = bool(getattr(args, "local_mel", False))
     if want_mel and _local.load_mel(args.model_dir) is None:                 # before a model is built
         raise SystemExit("evaluate: --local-mel needs a checkpoint trained with train --local-mel ({} has no \"mel\")".format(

@@ -8,7 +8,8 @@ length its own features cover, all in one ragged ``generate_batch`` run.
 ``--fast --report FILE.json`` writes the negative log-likelihood the model gave every written file (nats and bits per emitted
 sample, as ``evaluate`` prints for held-out audio); ``--fast --best-of K`` draws every utterance K times in the same batched
 run and keeps the candidate the model found most likely.  Likelihood rewards quiet, predictable audio: it ranks candidates
-(most usefully when vocoding from features), it does not measure quality.
+(most usefully when vocoding from features), it does not measure quality.  ``--fast --from-wav FILE.wav --best-of K --rank mel``
+keeps the candidate whose log-mel columns are closest to the recording's own instead (``wavenet_amd/metrics.py``).
 ``--fast --keep FILE.wav [--redraw A:B ...]`` regenerates stretches of a recording: the file's first ``input_width`` samples are
 the window, every later sample is emitted as the file has it (``FasterWaveNet.generate(..., forced=...)``) unless a ``--redraw``
 range, in seconds of the file, covers it, and the output is the file with those ranges drawn anew.  Without ``--redraw`` the
@@ -92,6 +93,66 @@ def likelihood_job(args):
     return K, report
 
 
+def rank_job(args):
+    """``generate --rank likelihood|mel``: the checks, made before a model is built.  Returns whether the candidates are ranked
+    on their distance to the recording's mel columns."""
+    if args.rank not in ("likelihood", "mel"):
+        raise SystemExit("generate: --rank takes likelihood or mel, got {!r}".format(args.rank))
+    if args.rank == "likelihood":
+        return False
+    if not args.from_wav:
+        bad = [f for f, on in (("--local", args.local), ("--local-dir", args.local_dir is not None), ("--keep", args.keep)) if on]
+        raise SystemExit("generate: --rank mel compares every candidate with the columns of the recording it was made from: give "
+                         "--from-wav FILE.wav{}".format(" (it does not go with {})".format(", ".join(bad)) if bad else ""))
+    if args.chunk_frames is not None:
+        raise SystemExit("generate: --rank mel analyses whole candidates and does not go with --chunk-frames")
+    return True
+
+
+class MelRank(object):
+    """``--rank mel``: the candidates of a run against the columns of the recordings they were made from.  A candidate is the
+    window followed by its emitted samples, on the recording's column grid (``metrics.copy_synthesis`` states the rule): its
+    columns come from one ``LogMel.batch`` call over all candidates, and those whose window touches the generation's window
+    are left out, as are those past the shorter of the two.  The window that is put in front is always silence, also where a
+    run continues a ``--prompt``: no compared column reads a sample of the window, so what it holds does not matter."""
+
+    def __init__(self, analyser_of, rates, targets, quantization_steps, window):
+        """``analyser_of(rate)``: the ``features.LogMel`` of the checkpoint's settings at that rate; ``rates[u]`` / ``targets[u]``:
+        the rate recording u was analysed at and its (F, columns) array."""
+        self.analyser_of, self.rates, self.targets, self.Q = analyser_of, list(rates), list(targets), int(quantization_steps)
+        self.window = np.asarray(window, dtype=np.int32)
+
+    def distances(self, rows, K):
+        """The log-mel distance in dB of every row, row ``u * K + c`` against target u (None where no column is compared).  The
+        rows of recordings at one rate -- as a rule all of them -- are analysed in one ``LogMel.batch`` call."""
+        from .. import metrics
+        win = torch.as_tensor(self.window)
+        sig = [torch.cat([win, torch.as_tensor(np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r, dtype=np.int32))]) for r in rows]
+        out = [None] * len(sig)
+        for rate in sorted(set(self.rates)):
+            an = self.analyser_of(rate)
+            mine = [i for i in range(len(sig)) if self.rates[i // K] == rate and sig[i].numel() > an.win // 2]
+            if not mine:
+                continue
+            k0 = metrics.first_free_column(self.window.size, an.win, an.hop)
+            for i, c in zip(mine, an.batch([sig[i] for i in mine], self.Q)):
+                t = self.targets[i // K]
+                n = min(int(c.shape[1]), int(t.shape[1]))
+                out[i] = metrics.log_mel_distance(t[:, k0:n], c[:, k0:n])[0] if n > k0 else None
+        return out
+
+    def keep_best(self, tokens, chosen, K):
+        """``_keep_best`` with the ranking on the distances: (kept tokens, [(kept index, nats of every candidate)], the kept
+        candidates' distances)."""
+        from .. import metrics
+        nlls = [sampling.chosen_nll(c) for c in chosen]
+        dist = self.distances(tokens, K)
+        ranked = [(metrics.pick_closest(dist[u * K:(u + 1) * K]), nlls[u * K:(u + 1) * K]) for u in range(len(nlls) // K)]
+        kept = [tokens[u * K + k] for u, (k, _) in enumerate(ranked)]
+        return ([np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in kept], ranked,
+                [dist[u * K + k] for u, (k, _) in enumerate(ranked)])
+
+
 def tile_job(args):
     """``generate --tile auto|2|4|8|16``: the check, made before a model is built.  Returns None without the flag, else what
     ``FasterWaveNet.batch_tile`` takes: ``"auto"`` or the tile size."""
@@ -113,35 +174,41 @@ def _keep_best(tokens, chosen, K):
     return [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in kept], ranked
 
 
-def write_report(path, filenames, tokens, ranked, K):
+def write_report(path, filenames, tokens, ranked, K, distances=None):
     """``--report``: per written file {"file", "samples", "nats_per_sample", "bits_per_sample"} (the emitted samples only: no
     prompt, no window) and, with ``--best-of K`` > 1, "candidates" (every candidate's nats per sample) and "kept"; then the
-    total weighted by samples, in the layout of ``evaluate --json``.  Returns the table."""
+    total weighted by samples, in the layout of ``evaluate --json``.  ``distances`` (``--rank mel``: the kept candidates'): every
+    row gains "log_mel_distance_db" and the table "rank": "mel".  Returns the table."""
     rows, nats, samples = [], 0.0, 0
-    for fn, t, (k, cand) in zip(filenames, tokens, ranked):
+    for i, (fn, t, (k, cand)) in enumerate(zip(filenames, tokens, ranked)):
         row = {"file": os.path.basename(fn), "samples": int(len(t)), "nats_per_sample": cand[k],
                "bits_per_sample": cand[k] / math.log(2.0)}
         if K > 1:
             row["candidates"], row["kept"] = list(cand), int(k)
+        if distances is not None:
+            row["log_mel_distance_db"] = distances[i]
         rows.append(row)
         nats += cand[k] * len(t) if len(t) else 0.0
         samples += int(len(t))
     mean = nats / samples if samples else 0.0
     table = {"files": rows, "total": {"samples": samples, "nats_per_sample": mean, "bits_per_sample": mean / math.log(2.0)}}
+    if distances is not None:
+        table["rank"] = "mel"
     with open(path, "w") as f:
         json.dump(table, f, indent=2)
     return table
 
 
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, best_of=1, report=None):
+                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, best_of=1, report=None, rank=None):
+    """``rank``: None (the candidates of ``best_of`` are ranked on their likelihood) or a ``MelRank``."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
     silence = silence_window(Q, input_width_of(params))
     start_time = time.time()
-    ranked = None
-    if fast and (best_of > 1 or report):
+    ranked = dists = None
+    if fast and (best_of > 1 or report or rank is not None):
         lkw = {} if local is None else {"local": local}
         kw = dict(initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p, condition=condition,
                   return_chosen=True, **lkw)
@@ -152,7 +219,10 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
         else:
             # K candidates of the one utterance are K utterances of a batched run: same prompt, speaker, features, controls
             rows, chosen = net.generate_batch(n, np.random.random_sample((best_of, n)), **kw)
-        (tokens,), ranked = _keep_best(list(rows), list(chosen), best_of)
+        if rank is None:
+            (tokens,), ranked = _keep_best(list(rows), list(chosen), best_of)
+        else:
+            (tokens,), ranked, dists = rank.keep_best(list(rows), list(chosen), best_of)
     elif n <= 0:
         tokens = np.zeros((0,), np.int32)
     elif fast:
@@ -165,7 +235,7 @@ def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=Fals
         tokens = _host_loop(net, silence, n, sampling_rate, generate_sec, temperature, top_k, top_p, condition, local)
     filename = _save(start_time, output_dir, Q, sampling_rate, [("generated", tokens)])[0]
     if report:
-        write_report(report, [filename], [tokens], ranked, best_of)
+        write_report(report, [filename], [tokens], ranked, best_of, dists)
     return filename, tokens
 
 
@@ -370,6 +440,12 @@ def from_wav_job(args, config, n_utt, chunk_frames):
     return [distinct[f] for f in files], None
 
 
+def _wav_rate(path) -> int:
+    """The sampling rate a .wav file's header states."""
+    from scipy.io import wavfile
+    return int(wavfile.read(path, mmap=True)[0])
+
+
 def read_kw(args, params):
     """The keywords of ``data.load_audio_file`` that ``--resample`` adds: the model's rate, and the device that converts."""
     if not args.resample:
@@ -389,11 +465,13 @@ def read_prompt(path, params, rkw={}):
 
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None, rkw={}):
+                        temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None, rkw={},
+                        rank=None):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance.
     ``best_of`` = K > 1 (``fast`` only): N * K candidates in that run, row ``u * K + c`` candidate c of utterance u, the
-    most likely one of every utterance written under the utterance's name; ``report``: ``write_report``'s file."""
+    most likely one of every utterance written under the utterance's name; ``report``: ``write_report``'s file; ``rank``: None or a
+    ``MelRank`` (the candidate closest to its recording's columns is written instead)."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     N = len(prompt_files)
@@ -402,8 +480,8 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     read = {f: read_prompt(f, params, rkw) for f in set(prompt_files) if f is not None}
     prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
     start_time = time.time()
-    ranked = None
-    if fast and (best_of > 1 or report):
+    ranked = dists = None
+    if fast and (best_of > 1 or report or rank is not None):
         K = best_of
         if n <= 0:
             rows, chosen = [np.zeros((0,), np.int32)] * (N * K), [np.zeros((0,), np.float32)] * (N * K)
@@ -414,7 +492,10 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
                                               top_k=top_k, top_p=top_p, return_chosen=True,
                                               condition=None if conditions is None else [c for c in conditions for _ in range(K)],
                                               **lkw)
-        tokens, ranked = _keep_best(list(rows), list(chosen), K)
+        if rank is None:
+            tokens, ranked = _keep_best(list(rows), list(chosen), K)
+        else:
+            tokens, ranked, dists = rank.keep_best(list(rows), list(chosen), K)
         tokens = np.stack(tokens)
     elif n <= 0:
         tokens = np.zeros((N, 0), np.int32)
@@ -429,7 +510,7 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
                                       None if locals_ is None else locals_[i]) for i in range(N)])
     filenames = _save(start_time, output_dir, Q, sampling_rate, [("generated_{:03d}".format(i), tokens[i]) for i in range(N)])
     if report:
-        write_report(report, filenames, list(tokens), ranked, best_of)
+        write_report(report, filenames, list(tokens), ranked, best_of, dists)
     return filenames, tokens
 
 
@@ -603,6 +684,7 @@ def main(argv=None):
     best_of, report = likelihood_job(args)
     chunk_frames, ring_frames = stream_job(args)
     tile = tile_job(args)
+    rank_mel = rank_job(args)
     seconds_given = _seconds_given(argv)
     kept = keep_job(args, seconds_given)
     if args.local_dir is not None:
@@ -630,9 +712,21 @@ def main(argv=None):
     elif config is not None:
         distinct = {f: _local.read_features(f, config[0]) for f in set(args.local)}
         feats = [distinct[f] for f in (args.local * (n_utt or 1) if len(args.local) == 1 else args.local)]
+    targets = list(feats) if rank_mel else None         # the recordings' own columns, one array per utterance
     params, net = _model.build(args)
     if tile is not None:               # every generate_batch / open_stream call of this run decodes in tiles
         net.batch_tile = tile
+    rank = None
+    if rank_mel:
+        win = _local.load_mel(args.model_dir)["win"]
+        files = args.from_wav * len(targets) if len(args.from_wav) == 1 else args.from_wav
+
+        def analyser_of(rate):
+            with torch.cuda.device(args.gpu_device):
+                return _local.mel_analyser(rate, config[0], config[1], win)
+
+        rank = MelRank(analyser_of, [int(params.sampling_rate) if args.resample else _wav_rate(f) for f in files], targets,
+                       params.quantization_steps, silence_window(params, input_width_of(params)))
     np.random.seed(args.seed)
     if feats is not None or mel_src is not None:
         # the features cover an utterance from its first sample, the window of input_width samples included; the length
@@ -668,10 +762,10 @@ def main(argv=None):
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
                                    top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of,
-                                   report=report, rkw=read_kw(args, params))
+                                   report=report, rkw=read_kw(args, params), rank=rank)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                          condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report)
+                          condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report, rank=rank)
 
 
 if __name__ == "__main__":
