@@ -181,20 +181,7 @@ def test_header_map_and_binding_name_the_same_three_functions():
     fields = [re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
     assert fields == [f[0] for f in _corpus.WnCorpusDesc._fields_]
     assert C.sizeof(_corpus.WnCorpusDesc) == 7 * 8 + 8 + 8 * 4
-    # the other two libraries keep their exports: nothing of this one leaked into them
-    from wavenet_amd import _logmel
-    for path, n in ((_lib.LIB_PATH, 69), (_logmel.LIB_PATH, 3)):
-        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = [ln.split()[-1] for ln in nm.splitlines() if ln.strip()]
-        assert len(names) == n and not [s for s in names if "corpus" in s]
     assert "getenv" not in open(os.path.join(ROOT, "wavenet_amd", "csrc", "corpus.hip")).read()
-
-
-def test_the_build_table_sends_each_side_source_to_its_own_library():
-    from wavenet_amd import build
-    assert build.SIDE_LIBS == {"logmel.hip": (build.LOGMEL_LIB, "logmel_exports.map"),
-                               "corpus.hip": (build.CORPUS_LIB, "corpus_exports.map")}
-    assert build.CORPUS_LIB == _corpus.LIB_PATH
 
 
 def test_parse_accepts_corpus_with_the_flags_it_works_with_and_is_unchanged_without():

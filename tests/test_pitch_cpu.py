@@ -1,6 +1,6 @@
 """The host side of the pitch tracker: the numpy definition against truth, the float32 restatement's decisions against the
-definition's on every frame of every test signal, selection in both precisions, the ABI's names and refusals (no GPU needed)
-and the build table."""
+definition's on every frame of every test signal, selection in both precisions, and the ABI's names and refusals (no GPU
+needed)."""
 import ctypes as C
 import os
 import re
@@ -132,19 +132,7 @@ def test_header_map_and_binding_name_the_same_three_functions():
     fields = [re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
     assert fields == [f[0] for f in _pitch.WnPitchClip._fields_]
     assert C.sizeof(_pitch.WnPitchClip) == 6 * 8 + 4 * 4
-    # the other four libraries keep their exports: nothing of this one leaked into them
-    from wavenet_amd import _corpus, _lib, _logmel, _resample
-    for path, n in ((_lib.LIB_PATH, 69), (_logmel.LIB_PATH, 3), (_corpus.LIB_PATH, 3), (_resample.LIB_PATH, 3)):
-        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = [ln.split()[-1] for ln in nm.splitlines() if ln.strip()]
-        assert len(names) == n and not [s for s in names if "pitch" in s]
     assert "getenv" not in open(os.path.join(ROOT, "wavenet_amd", "csrc", "analysis", "pitch.hip")).read()
-
-
-def test_the_build_table_sends_the_analyser_to_its_own_library():
-    from wavenet_amd import build
-    assert build.ANALYSIS_LIBS == {"analysis/pitch.hip": (build.PITCH_LIB, "analysis/pitch_exports.map")}
-    assert build.PITCH_LIB == _pitch.LIB_PATH
 
 
 def test_wn_pitch_refuses_every_bad_argument_by_name_without_a_gpu():

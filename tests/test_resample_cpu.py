@@ -173,21 +173,7 @@ def test_header_map_and_binding_name_the_same_three_functions():
     fields = [re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
     assert fields == [f[0] for f in _resample.WnResampleClip._fields_]
     assert C.sizeof(_resample.WnResampleClip) == 6 * 8 + 2 * 4
-    # the other three libraries keep their exports: nothing of this one leaked into them
-    from wavenet_amd import _corpus, _lib, _logmel
-    for path, n in ((_lib.LIB_PATH, 69), (_logmel.LIB_PATH, 3), (_corpus.LIB_PATH, 3)):
-        nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-        names = [ln.split()[-1] for ln in nm.splitlines() if ln.strip()]
-        assert len(names) == n and not [s for s in names if "resample" in s]
     assert "getenv" not in open(os.path.join(ROOT, "wavenet_amd", "csrc", "front", "resample.hip")).read()
-
-
-def test_the_build_tables_send_the_front_end_to_its_own_library():
-    from wavenet_amd import build
-    assert build.SIDE_LIBS == {"logmel.hip": (build.LOGMEL_LIB, "logmel_exports.map"),
-                               "corpus.hip": (build.CORPUS_LIB, "corpus_exports.map")}
-    assert build.FRONT_LIBS == {"front/resample.hip": (build.RESAMPLE_LIB, "front/resample_exports.map")}
-    assert build.RESAMPLE_LIB == _resample.LIB_PATH
 
 
 def test_wn_resample_refuses_every_bad_argument_by_name_without_a_gpu():

@@ -141,21 +141,33 @@ class WaveNetHipError(RuntimeError):
     pass
 
 
+def load(path: str, sigs: dict, abi_export: str, abi_version: int) -> C.CDLL:
+    """What every binding's ``lib()`` does on its first call: load ``path``, type the entries of ``sigs`` and compare the
+    library's ``abi_export()`` with the binding's ``abi_version``.  No fallback: a missing library raises."""
+    if not os.path.exists(path):
+        raise WaveNetHipError("%s not found: build it with `python -m wavenet_amd.build` (hipcc, gfx950)" % path)
+    l = C.CDLL(path)
+    for name, (res, args) in sigs.items():
+        fn = getattr(l, name)          # AttributeError if the .so does not export it
+        fn.restype = res
+        fn.argtypes = args
+    found = getattr(l, abi_export)()
+    if found != abi_version:
+        raise WaveNetHipError("ABI mismatch: %s is version %d, the binding %d" % (path, found, abi_version))
+    return l
+
+
+def raise_on(rc: int, what: str, last_error) -> None:
+    """``check()`` of every binding: a nonzero return code raises with the text of the library's ``*_last_error``."""
+    if rc != 0:
+        raise WaveNetHipError("%s failed (%d): %s" % (what, rc, last_error().decode("utf-8", "replace")))
+
+
 def lib() -> C.CDLL:
     """Load the library once; raise if it is absent (there is deliberately no fallback)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise WaveNetHipError(
-                "%s not found: build it with `python -m wavenet_amd.build` (hipcc, gfx950)" % LIB_PATH)
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)          # AttributeError if the .so does not export it
-            fn.restype = res
-            fn.argtypes = args
-        if l.wn_abi_version() != ABI_VERSION:
-            raise WaveNetHipError("ABI mismatch: library %d, binding %d" % (l.wn_abi_version(), ABI_VERSION))
-        _lib = l
+        _lib = load(LIB_PATH, _SIGS, "wn_abi_version", ABI_VERSION)
     return _lib
 
 

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 from typing import Optional
 
-from ._lib import WaveNetHipError
+from ._lib import load, raise_on
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libwavenet_pitch.so")
@@ -35,19 +35,9 @@ _lib: Optional[C.CDLL] = None
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise WaveNetHipError("%s not found: build it with `python -m wavenet_amd.build` (hipcc, gfx950)" % LIB_PATH)
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(l, name)
-            fn.restype = res
-            fn.argtypes = args
-        if l.wn_pitch_abi_version() != ABI_VERSION:
-            raise WaveNetHipError("ABI mismatch: %s is version %d, the binding %d" % (LIB_PATH, l.wn_pitch_abi_version(), ABI_VERSION))
-        _lib = l
+        _lib = load(LIB_PATH, _SIGS, "wn_pitch_abi_version", ABI_VERSION)
     return _lib
 
 
 def check(rc: int, what: str = "wn_pitch") -> None:
-    if rc != 0:
-        raise WaveNetHipError("%s failed (%d): %s" % (what, rc, lib().wn_pitch_last_error().decode("utf-8", "replace")))
+    raise_on(rc, what, lib().wn_pitch_last_error)

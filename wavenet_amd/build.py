@@ -1,9 +1,7 @@
-"""Compile wavenet_amd/csrc/*.hip into wavenet_amd/libwavenet_hip.so for gfx950 -- all but the sources of ``SIDE_LIBS``:
-logmel.hip becomes wavenet_amd/libwavenet_logmel.so (include/wavenet_logmel.h) and corpus.hip wavenet_amd/libwavenet_corpus.so
-(include/wavenet_corpus.h), libraries of their own: the first one's exports are pinned.  ``FRONT_LIBS`` does the same for the
-sources of wavenet_amd/csrc/front/, which the ``csrc/*.hip`` glob does not see: front/resample.hip becomes
-wavenet_amd/libwavenet_resample.so (include/wavenet_resample.h).  ``ANALYSIS_LIBS`` is the same table for wavenet_amd/csrc/analysis/:
-analysis/pitch.hip becomes wavenet_amd/libwavenet_pitch.so (include/wavenet_pitch.h).
+"""Compile wavenet_amd/csrc into shared libraries for gfx950.
+
+``SIDE_LIBS`` maps a source, by its path below csrc/, to (library, version script): that source becomes a library of its own
+in wavenet_amd/, linked with that version script of csrc/.  Every other csrc/*.hip goes into libwavenet_hip.so.
 
 hipcc cross-compiles without a GPU, so this runs in the build container; the .so then travels
 in-tree to the GPU box.  Usage: ``python -m wavenet_amd.build [--force]``.
@@ -20,22 +18,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libwavenet_hip.so")
-LOGMEL_LIB = os.path.join(HERE, "libwavenet_logmel.so")
-CORPUS_LIB = os.path.join(HERE, "libwavenet_corpus.so")
-# source -> (library, version script): a source that is a library of its own; every other source goes into LIB
+# source below csrc/ -> (library in wavenet_amd/, version script below csrc/)
 SIDE_LIBS = {
-    "logmel.hip": (LOGMEL_LIB, "logmel_exports.map"),
-    "corpus.hip": (CORPUS_LIB, "corpus_exports.map"),
-}
-RESAMPLE_LIB = os.path.join(HERE, "libwavenet_resample.so")
-# source below csrc/ -> (library, version script): front ends in a directory of their own, one library each
-FRONT_LIBS = {
-    "front/resample.hip": (RESAMPLE_LIB, "front/resample_exports.map"),
-}
-PITCH_LIB = os.path.join(HERE, "libwavenet_pitch.so")
-# source below csrc/ -> (library, version script): analysers of audio, handled like the front ends
-ANALYSIS_LIBS = {
-    "analysis/pitch.hip": (PITCH_LIB, "analysis/pitch_exports.map"),
+    "logmel.hip": ("libwavenet_logmel.so", "logmel_exports.map"),
+    "corpus.hip": ("libwavenet_corpus.so", "corpus_exports.map"),
+    "front/resample.hip": ("libwavenet_resample.so", "front/resample_exports.map"),
+    "analysis/pitch.hip": ("libwavenet_pitch.so", "analysis/pitch_exports.map"),
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fvisibility=hidden: only what include/wavenet_hip.h declares (inside its `#pragma GCC visibility push(default)`) is exported
@@ -73,18 +61,16 @@ def _link(lib: str, objs, version_script: str, force: bool) -> None:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    side = [os.path.join(CSRC, src) for src in SIDE_LIBS]
+    main = sorted(set(glob.glob(os.path.join(CSRC, "*.hip"))) - set(side))
     hdr = _newest_header()
-    with ThreadPoolExecutor(max_workers=min(6, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, force, hdr), srcs))
-    side = {os.path.basename(s): o for s, o in zip(srcs, objs) if os.path.basename(s) in SIDE_LIBS}
-    _link(LIB, [o for o in objs if o not in side.values()], "exports.map", force)
-    for src, (lib, version_script) in SIDE_LIBS.items():
-        _link(lib, [side[src]], version_script, force)
-    for src, (lib, version_script) in list(FRONT_LIBS.items()) + list(ANALYSIS_LIBS.items()):
-        _link(lib, [_compile(os.path.join(CSRC, src), force, hdr)], version_script, force)
-    if verbose:
-        for lib in [LIB] + [lib for lib, _ in list(SIDE_LIBS.values()) + list(FRONT_LIBS.values()) + list(ANALYSIS_LIBS.values())]:
+    with ThreadPoolExecutor(max_workers=6) as ex:
+        objs = dict(zip(main + side, ex.map(lambda s: _compile(s, force, hdr), main + side)))
+    libs = [(LIB, [objs[s] for s in main], "exports.map")]
+    libs += [(os.path.join(HERE, name), [objs[s]], script) for s, (name, script) in zip(side, SIDE_LIBS.values())]
+    for lib, lib_objs, version_script in libs:
+        _link(lib, lib_objs, version_script, force)
+        if verbose:
             print("built", lib)
     return LIB
 

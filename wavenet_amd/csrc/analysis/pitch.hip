@@ -17,27 +17,16 @@
 //
 // Built into libwavenet_pitch.so (include/wavenet_pitch.h), not into libwavenet_hip.so: it shares no code with that library.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../../include/wavenet_pitch.h"
 
+#define WN_SIDE_EARG WNP_EARG
+#define WN_SIDE_EHIP WNP_EHIP
+#include "../side_host.hpp"
+
 namespace wn {
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int rc, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return rc;
-}
-#define WN_CHECK_ARG(cond, ...)                        \
-    do {                                               \
-        if (!(cond)) return fail(WNP_EARG, __VA_ARGS__); \
-    } while (0)
 
 // consecutive lags per lane.  Odd: neighbouring lanes read their windows kLags LDS words apart, and ds_read_b32 banks by the word
 // address mod 32 over 32 lanes, so an odd step is conflict-free where a step of 4 is 4-way
@@ -267,18 +256,8 @@ int wn_pitch(const WnPitchClip* clips, int n_clips, const float* table, int Q, i
     args.n_clips = n_clips;
     const int items = ft * lag_groups(tau_max);
     const int threads = items >= kThreads ? kThreads : (items + 63) / 64 * 64;
-    // A launch may ask for 48 KB of dynamic LDS without more ado; above that the kernel's limit is raised first, by the call
-    // that needs it (a host-side call on the current device, nothing is enqueued).
-    if (lds_bytes > 48 * 1024) {
-        const hipError_t lds_e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pitch), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)lds_bytes);
-        if (lds_e != hipSuccess)
-            return fail(WNP_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %lld) failed for k_pitch: %s", lds_bytes,
-                        hipGetErrorString(lds_e));
-    }
+    if (const int rc = raise_lds_limit(k_pitch, "k_pitch", lds_bytes)) return rc;
     hipLaunchKernelGGL(k_pitch, dim3((unsigned)tiles), dim3(threads), (size_t)lds_bytes, reinterpret_cast<hipStream_t>(stream), args,
                        table, Q, win, hop, tau_min, tau_max, threshold, rate, ft);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WNP_EHIP, "wn_pitch: kernel launch failed: %s", hipGetErrorString(e));
-    return WNP_OK;
+    return launch_status("wn_pitch");
 }

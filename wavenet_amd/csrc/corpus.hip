@@ -11,27 +11,16 @@
 //
 // Built into libwavenet_corpus.so (include/wavenet_corpus.h), not into libwavenet_hip.so: it shares no code with that library.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/wavenet_corpus.h"
 
+#define WN_SIDE_EARG WNC_EARG
+#define WN_SIDE_EHIP WNC_EHIP
+#include "side_host.hpp"
+
 namespace wn {
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int rc, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return rc;
-}
-#define WN_CHECK_ARG(cond, ...)                          \
-    do {                                                 \
-        if (!(cond)) return fail(WNC_EARG, __VA_ARGS__); \
-    } while (0)
 
 constexpr int kThreads = 256;
 constexpr int kPerThread = 4;
@@ -124,7 +113,5 @@ int wn_corpus_gather(const WnCorpusDesc* desc, const int32_t* draws, int B, int 
         hipLaunchKernelGGL(k_corpus_gather<uint8_t>, grid, block, 0, st, d, draws, target_width, n_cols, (int)chunks, x, tgt, local, cond);
     else
         hipLaunchKernelGGL(k_corpus_gather<int32_t>, grid, block, 0, st, d, draws, target_width, n_cols, (int)chunks, x, tgt, local, cond);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WNC_EHIP, "wn_corpus_gather: kernel launch failed: %s", hipGetErrorString(e));
-    return WNC_OK;
+    return launch_status("wn_corpus_gather");
 }

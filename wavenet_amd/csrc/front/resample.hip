@@ -14,27 +14,16 @@
 //
 // Built into libwavenet_resample.so (include/wavenet_resample.h): it shares no code with the other libraries.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../../include/wavenet_resample.h"
 
+#define WN_SIDE_EARG WNR_EARG
+#define WN_SIDE_EHIP WNR_EHIP
+#include "../side_host.hpp"
+
 namespace wn {
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int rc, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return rc;
-}
-#define WN_CHECK_ARG(cond, ...)                        \
-    do {                                               \
-        if (!(cond)) return fail(WNR_EARG, __VA_ARGS__); \
-    } while (0)
 
 constexpr int kTile = WN_RESAMPLE_TILE;   // outputs per workgroup, one per lane
 constexpr int kLdsLimit = 160 * 1024;     // gfx950
@@ -161,18 +150,8 @@ int wn_resample(const WnResampleClip* clips, int n_clips, int in_kind, int out_k
     WN_CHECK_ARG(tiles < (1ll << 31), "wn_resample: %lld output tiles in one launch", tiles);
     if (tiles == 0) return WNR_OK;
     args.n_clips = n_clips;
-    // A launch may ask for 48 KB of dynamic LDS without more ado; above that the kernel's limit is raised first.  The attribute
-    // belongs to the device that is current, so it is set by the call that needs it (a host-side call, nothing is enqueued).
-    if (lds_bytes > 48 * 1024) {
-        const hipError_t lds_e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_resample),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (lds_e != hipSuccess)
-            return fail(WNR_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %lld) failed for k_resample: %s", lds_bytes,
-                        hipGetErrorString(lds_e));
-    }
+    if (const int rc = raise_lds_limit(k_resample, "k_resample", lds_bytes)) return rc;
     hipLaunchKernelGGL(k_resample, dim3((unsigned)tiles), dim3(kTile), (size_t)lds_bytes, reinterpret_cast<hipStream_t>(stream),
                        args, in_kind, out_kind, taps, L, M, T, lut);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WNR_EHIP, "wn_resample: kernel launch failed: %s", hipGetErrorString(e));
-    return WNR_OK;
+    return launch_status("wn_resample");
 }

@@ -14,27 +14,16 @@
 //
 // Built into libwavenet_logmel.so (include/wavenet_logmel.h), not into libwavenet_hip.so: it shares no code with that library.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/wavenet_logmel.h"
 
+#define WN_SIDE_EARG WNL_EARG
+#define WN_SIDE_EHIP WNL_EHIP
+#include "side_host.hpp"
+
 namespace wn {
 namespace {
-
-thread_local char g_err[512] = "";
-int fail(int rc, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return rc;
-}
-#define WN_CHECK_ARG(cond, ...)                        \
-    do {                                               \
-        if (!(cond)) return fail(WNL_EARG, __VA_ARGS__); \
-    } while (0)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -231,19 +220,8 @@ int wn_logmel(const WnLogmelClip* clips, int n_clips, const float* table, int Q,
     }
     WN_CHECK_ARG(tiles < (1ll << 31), "wn_logmel: %lld frame tiles in one launch", tiles);
     args.n_clips = n_clips;
-    // A launch may ask for 48 KB of dynamic LDS without more ado; above that the kernel's limit is raised first.  The attribute
-    // belongs to the device that is current, so it is set by the call that needs it (a host-side call, nothing is enqueued),
-    // not once per process: another device, or a call after a failed one, is served like the first.
-    if (lds_bytes > 48 * 1024) {
-        const hipError_t lds_e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_logmel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (lds_e != hipSuccess)
-            return fail(WNL_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize, %lld) failed for k_logmel: %s", lds_bytes,
-                        hipGetErrorString(lds_e));
-    }
+    if (const int rc = raise_lds_limit(k_logmel, "k_logmel", lds_bytes)) return rc;
     hipLaunchKernelGGL(k_logmel, dim3((unsigned)tiles), dim3(256), (size_t)lds_bytes, reinterpret_cast<hipStream_t>(stream), args,
                        table, Q, basis, fbT, win, hop, n_mels);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WNL_EHIP, "wn_logmel: kernel launch failed: %s", hipGetErrorString(e));
-    return WNL_OK;
+    return launch_status("wn_logmel");
 }

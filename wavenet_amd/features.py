@@ -118,39 +118,32 @@ def _check_logmel_shape(n_mels, hop, win) -> None:
                          % (hop, win, seg, need, LOGMEL_LDS_BYTES))
 
 
-class LogMel(object):
-    """``log_mel`` on the device: ``LogMel(rate)(x)`` -> (n_mels, ceil(N / hop)) float32 device tensor.
+class ClipAnalyser(object):
+    """What the per-clip analysers share (``LogMel`` here, ``pitch.Pitch``): how a clip is taken in and which columns are asked
+    for.  A subclass has ``hop`` and ``_launch(jobs, quantization_steps)`` -> one tensor per job, where a job is
+    (samples, origin, first, count, left, right) and left / right say that this end of the buffer is the signal's.  Its name
+    opens the messages."""
 
-    ``x`` is a float32 signal, or int32 mu-law tokens together with ``quantization_steps`` (decoded inside the kernel with
-    ``data.mulaw_decode``'s table); a numpy array or a tensor on any device is moved.  A column's bits depend on its own
-    ``win`` samples only -- not on the call, the batch or the chunking that produced it, nor on tokens versus floats."""
-
-    def __init__(self, rate, n_mels: int = 80, hop: int = 256, win: int = 1024, device=None):
+    def __init__(self, device):
         import torch
-        n_mels, hop, win = int(n_mels), int(hop), int(win)
-        _check_logmel_shape(n_mels, hop, win)
-        self.rate, self.n_mels, self.hop, self.win = rate, n_mels, hop, win
-        self.device = torch.device("cuda" if device is None else device)
-        basis, fbT = logmel_tables(rate, win, n_mels)
-        self.basis = torch.as_tensor(basis).to(self.device)
-        self.fbT = torch.as_tensor(fbT).to(self.device)
+        self.device = torch.device(device)
         self._decode = {}
         self.launches = 0
 
-    # -- inputs ---------------------------------------------------------------------------------------------------------------
     def _signal(self, x, quantization_steps):
         import torch
+        name = type(self).__name__
         t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
         t = t.reshape(-1)
         if quantization_steps is None:
             if t.dtype != torch.float32:
                 if not t.dtype.is_floating_point:
-                    raise ValueError("LogMel: integer input (%s) is tokens and needs quantization_steps" % t.dtype)
+                    raise ValueError("%s: integer input (%s) is tokens and needs quantization_steps" % (name, t.dtype))
                 t = t.to(torch.float32)
         else:
             if t.dtype.is_floating_point:
-                raise ValueError("LogMel: quantization_steps = %d given with a %s signal; tokens are integers"
-                                 % (quantization_steps, t.dtype))
+                raise ValueError("%s: quantization_steps = %d given with a %s signal; tokens are integers"
+                                 % (name, quantization_steps, t.dtype))
             t = t.to(torch.int32)
         return t.to(self.device).contiguous()
 
@@ -163,6 +156,49 @@ class LogMel(object):
         if q not in self._decode:
             self._decode[q] = torch.as_tensor(data.mulaw_decode(np.arange(q), q).astype(np.float32)).to(self.device)
         return self._decode[q]
+
+    def _check_length(self, n: int) -> None:
+        """Refuse a clip of n samples that the analyser cannot take; any length by default."""
+
+    def batch(self, clips, quantization_steps=None):
+        """A list of clips of any lengths -> a list of (rows, ceil(N_i / hop)) tensors, at most 64 clips per launch."""
+        xs = [self._signal(x, quantization_steps) for x in clips]
+        for x in xs:
+            self._check_length(x.numel())
+        if not xs:
+            return []
+        return self._launch([(x, 0, 0, frame_count(x.numel(), self.hop), True, True) for x in xs], quantization_steps)
+
+    def __call__(self, x, quantization_steps=None):
+        return self.batch([x], quantization_steps)[0]
+
+    def frames(self, x, first: int, count: int, quantization_steps=None):
+        """Columns [first, first + count) of ``self(x)``."""
+        x = self._signal(x, quantization_steps)
+        self._check_length(x.numel())
+        total = frame_count(x.numel(), self.hop)
+        if first < 0 or count < 1 or first + count > total:
+            raise ValueError("%s.frames: columns %d .. %d of a clip that has %d"
+                             % (type(self).__name__, first, first + count - 1, total))
+        return self._launch([(x, 0, first, count, True, True)], quantization_steps)[0]
+
+
+class LogMel(ClipAnalyser):
+    """``log_mel`` on the device: ``LogMel(rate)(x)`` -> (n_mels, ceil(N / hop)) float32 device tensor.
+
+    ``x`` is a float32 signal, or int32 mu-law tokens together with ``quantization_steps`` (decoded inside the kernel with
+    ``data.mulaw_decode``'s table); a numpy array or a tensor on any device is moved.  A column's bits depend on its own
+    ``win`` samples only -- not on the call, the batch or the chunking that produced it, nor on tokens versus floats."""
+
+    def __init__(self, rate, n_mels: int = 80, hop: int = 256, win: int = 1024, device=None):
+        import torch
+        n_mels, hop, win = int(n_mels), int(hop), int(win)
+        _check_logmel_shape(n_mels, hop, win)
+        self.rate, self.n_mels, self.hop, self.win = rate, n_mels, hop, win
+        ClipAnalyser.__init__(self, "cuda" if device is None else device)
+        basis, fbT = logmel_tables(rate, win, n_mels)
+        self.basis = torch.as_tensor(basis).to(self.device)
+        self.fbT = torch.as_tensor(fbT).to(self.device)
 
     def _check_length(self, n: int) -> None:
         if n <= self.win // 2:
@@ -191,27 +227,6 @@ class LogMel(object):
                                                       _lib.stream_ptr()))
                 self.launches += 1
         return outs
-
-    def batch(self, clips, quantization_steps=None):
-        """A list of clips of any lengths -> a list of (n_mels, ceil(N_i / hop)) tensors, LOGMEL_MAX_CLIPS clips per launch."""
-        xs = [self._signal(x, quantization_steps) for x in clips]
-        for x in xs:
-            self._check_length(x.numel())
-        if not xs:
-            return []
-        return self._launch([(x, 0, 0, frame_count(x.numel(), self.hop), True, True) for x in xs], quantization_steps)
-
-    def __call__(self, x, quantization_steps=None):
-        return self.batch([x], quantization_steps)[0]
-
-    def frames(self, x, first: int, count: int, quantization_steps=None):
-        """Columns [first, first + count) of ``self(x)``."""
-        x = self._signal(x, quantization_steps)
-        self._check_length(x.numel())
-        total = frame_count(x.numel(), self.hop)
-        if first < 0 or count < 1 or first + count > total:
-            raise ValueError("LogMel.frames: columns %d .. %d of a clip that has %d" % (first, first + count - 1, total))
-        return self._launch([(x, 0, first, count, True, True)], quantization_steps)[0]
 
     def stream(self, quantization_steps=None):
         return MelStream(self, quantization_steps)

@@ -21,7 +21,7 @@ import math
 
 import numpy as np
 
-from .features import frame_count
+from .features import ClipAnalyser, frame_count
 
 
 def pitch_lags(rate, fmin: float = 60.0, fmax: float = 500.0):
@@ -145,7 +145,7 @@ def _device_refusal(win, hop, tau_min, tau_max):
     return None
 
 
-class Pitch(object):
+class Pitch(ClipAnalyser):
     """``yin`` on the device: ``Pitch(rate)(x)`` -> (2, ceil(N / hop)) float32 device tensor (F0 with 0 for unvoiced;
     aperiodicity).
 
@@ -155,7 +155,6 @@ class Pitch(object):
 
     def __init__(self, rate, hop: int = 256, win: int = 1024, fmin: float = 60.0, fmax: float = 500.0, threshold: float = 0.15,
                  device="cuda"):
-        import torch
         hop, win = int(hop), int(win)
         self.tau_min, self.tau_max = pitch_lags(rate, fmin, fmax)
         why = _device_refusal(win, hop, self.tau_min, self.tau_max)
@@ -163,36 +162,7 @@ class Pitch(object):
             raise ValueError(why)
         self.rate, self.hop, self.win, self.fmin, self.fmax, self.threshold = rate, hop, win, fmin, fmax, float(threshold)
         self.span = win + self.tau_max                                # S: the samples a column reads
-        self.device = torch.device(device)
-        self._decode = {}
-        self.launches = 0
-
-    # -- inputs ---------------------------------------------------------------------------------------------------------------
-    def _signal(self, x, quantization_steps):
-        import torch
-        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
-        t = t.reshape(-1)
-        if quantization_steps is None:
-            if t.dtype != torch.float32:
-                if not t.dtype.is_floating_point:
-                    raise ValueError("Pitch: integer input (%s) is tokens and needs quantization_steps" % t.dtype)
-                t = t.to(torch.float32)
-        else:
-            if t.dtype.is_floating_point:
-                raise ValueError("Pitch: quantization_steps = %d given with a %s signal; tokens are integers"
-                                 % (quantization_steps, t.dtype))
-            t = t.to(torch.int32)
-        return t.to(self.device).contiguous()
-
-    def _table(self, quantization_steps):
-        import torch
-        from . import data
-        if quantization_steps is None:
-            return None
-        q = int(quantization_steps)
-        if q not in self._decode:
-            self._decode[q] = torch.as_tensor(data.mulaw_decode(np.arange(q), q).astype(np.float32)).to(self.device)
-        return self._decode[q]
+        ClipAnalyser.__init__(self, device)
 
     def reach(self, origin: int, first: int, count: int):
         """Buffer indices (lo, hi) of the first and last sample that columns first .. first + count - 1 read."""
@@ -231,24 +201,6 @@ class Pitch(object):
                                                    self.tau_min, self.tau_max, self.threshold, float(self.rate), _lib.stream_ptr()))
                 self.launches += 1
         return (outs, curves) if curve else outs
-
-    def batch(self, clips, quantization_steps=None):
-        """A list of clips of any lengths -> a list of (2, ceil(N_i / hop)) tensors, PITCH_MAX_CLIPS clips per launch."""
-        xs = [self._signal(x, quantization_steps) for x in clips]
-        if not xs:
-            return []
-        return self._launch([(x, 0, 0, frame_count(x.numel(), self.hop), True, True) for x in xs], quantization_steps)
-
-    def __call__(self, x, quantization_steps=None):
-        return self.batch([x], quantization_steps)[0]
-
-    def frames(self, x, first: int, count: int, quantization_steps=None):
-        """Columns [first, first + count) of ``self(x)``."""
-        x = self._signal(x, quantization_steps)
-        total = frame_count(x.numel(), self.hop)
-        if first < 0 or count < 1 or first + count > total:
-            raise ValueError("Pitch.frames: columns %d .. %d of a clip that has %d" % (first, first + count - 1, total))
-        return self._launch([(x, 0, first, count, True, True)], quantization_steps)[0]
 
     def block(self, x, origin: int, first: int, count: int, start: bool = False, end: bool = False, quantization_steps=None):
         """``count`` columns from a buffer that is part of a longer signal: column ``first + j`` is centred on buffer sample
