@@ -41,6 +41,14 @@ def columns_per_crop(input_width: int, target_width: int, hop: int, crop: str = 
     return (input_width + target_width + worst + hop - 1) // hop + int(interp == "linear")
 
 
+def check_shard(shard, batch_size: int):
+    """(lo, hi) with 0 <= lo < hi <= batch_size, as ints: the crops of a global draw that one rank gathers."""
+    lo, hi = int(shard[0]), int(shard[1])
+    if not (0 <= lo < hi <= int(batch_size)):
+        raise ValueError("shard = (%d, %d) is no range of crops of a batch of %d" % (lo, hi, int(batch_size)))
+    return lo, hi
+
+
 class Corpus(object):
     """``Corpus(tokens_per_file, input_width, quantization_steps, device, features=None, hop=0, classes=None)``.
 
@@ -207,10 +215,16 @@ class Corpus(object):
         self.launches += 1
         return x, tgt, local, cond, self.phases(starts)
 
-    def draw(self, batch_size: int, target_width: int, crop: str = "sample", n_cols: Optional[int] = None, rng=np.random):
-        """``gather(*draw_indices(...))``; the (files, starts) drawn stay in ``last_draw``."""
+    def draw(self, batch_size: int, target_width: int, crop: str = "sample", n_cols: Optional[int] = None, rng=np.random,
+             shard=None):
+        """``gather(*draw_indices(...))``; the (files, starts) drawn stay in ``last_draw``.  ``shard`` = (lo, hi), a rank of a
+        data-parallel run: the draw is the global one all the same -- ``batch_size`` pairs from the one ``randint`` call, all of
+        them kept in ``last_draw`` -- and crops lo .. hi - 1 of it are gathered, so equally seeded ranks cover one global batch."""
         files, starts = self.draw_indices(batch_size, target_width, crop, rng)
         self.last_draw = (files, starts)
+        if shard is not None:
+            lo, hi = check_shard(shard, batch_size)
+            files, starts = files[lo:hi], starts[lo:hi]
         return self.gather(files, starts, target_width, n_cols)
 
     def device_bytes(self) -> int:

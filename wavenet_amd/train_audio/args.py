@@ -4,6 +4,8 @@ from __future__ import annotations
 
 import argparse
 
+from . import launch
+
 # (flags, type, default, help); a bool default makes a store_true switch
 _REFERENCE_FLAGS = (
     (("-g", "--gpu_device"), int, 0, "HIP device index"),
@@ -100,6 +102,14 @@ _RESAMPLE_FLAGS = (
                                    "without the flag.  Without it a file's samples are taken as they are, whatever its rate.  "
                                    "A property of the run, not of the checkpoint"),
 )
+# data parallelism over the GPUs of the node (wavenet_amd/dp.py; train_audio/launch.py): off, an attribute of the namespace only
+# when given, checked by parse (the range) and by train (the batch) before anything is launched
+_GPUS_FLAGS = (
+    (("--gpus",), int, 1, "train: N ranks, one per GPU from --gpu_device on, each training its equal share of every batch, with one "
+                          "all-reduce of the gradients per update; 1 .. 8.  --batch-size stays the GLOBAL batch and must divide "
+                          "by N, so the flag changes the speed, not the optimisation problem; rank 0 prints and writes the "
+                          "checkpoints.  A property of the run, not of the checkpoint"),
+)
 # likelihood of what was generated (FasterWaveNet.generate(..., return_chosen=True); sampling.chosen_nll / pick_best): off, and
 # attributes of the namespace only when given.  generate checks them (both need --fast) before the model is built
 _LIKELIHOOD_FLAGS = (
@@ -171,6 +181,7 @@ class Args(argparse.Namespace):
     storage = "fp32"
     corpus = False
     resample = False
+    gpus = 1
     report, best_of = None, 1
     rank = "likelihood"
     keep, redraw = None, None
@@ -185,7 +196,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _GPUS_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
@@ -276,6 +287,10 @@ def parse(argv=None):
         ap.error("--local-upsample U goes with --local-dir or --local-mel and needs U >= 1")
     if args.storage not in ("fp32", "bf16"):
         ap.error("--storage {fp32,bf16}, got %r" % (args.storage,))
+    try:
+        launch.check_gpus(args.gpus)
+    except ValueError as e:
+        ap.error(str(e))
     if args.local and args.local_dir is not None:
         ap.error("--local-dir FEAT_DIR (every feature file of a directory) and --local FILE.npy exclude each other")
     if args.local:

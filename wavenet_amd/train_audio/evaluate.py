@@ -15,6 +15,7 @@ import os
 import sys
 
 from .. import data, scoring
+from . import launch as _launch
 from . import local as _local
 from . import model as _model
 from . import speakers as _speakers
@@ -39,6 +40,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="bring every file to the model's sampling_rate on the device before it is encoded (and make --local-mel "
                          "features at that rate); without it a file's samples are taken as they are, whatever its rate")
     ap.add_argument("--json", type=str, default=None, metavar="FILE", help="also write the table to FILE")
+    ap.add_argument("--gpus", type=int, default=argparse.SUPPRESS, metavar="N",
+                    help="score the files on N ranks, one per GPU from --gpu_device on (1 .. 8): rank r takes every N-th file from "
+                         "the r-th on, rank 0 prints and writes the table, which is the single-process one value for value; not "
+                         "with --copy-synthesis")
     # copy synthesis (wavenet_amd/metrics.py; copy_synthesis_dir below): present in the namespace only when given
     ap.add_argument("--copy-synthesis", action="store_true", default=argparse.SUPPRESS,
                     help="instead of scoring, resynthesise every file from its own features (a checkpoint trained with train "
@@ -145,8 +150,23 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
     return table
 
 
+def table_of(rows):
+    """``{"files": rows, "total": {...}}`` of scored rows, the total weighted by samples and summed in the rows' order."""
+    nats, samples = 0.0, 0
+    for row in rows:
+        nats += row["nats_per_sample"] * row["samples"]
+        samples += row["samples"]
+    mean = nats / samples if samples else 0.0
+    return {"files": rows, "total": {"samples": samples, "nats_per_sample": mean, "bits_per_sample": mean / math.log(2.0)}}
+
+
+def merge_rows(rows_per_rank):
+    """The rows that the ranks scored (rank r holds those of ``files[r::world]``, possibly none), back in sorted file order."""
+    return sorted((row for rows in rows_per_rank for row in rows), key=lambda row: row["file"])
+
+
 def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int = 8, verbose: bool = True, local_dir=None,
-                 local_mel=None, resample=False):
+                 local_mel=None, resample=False, shard=None):
     """Score every .wav file of ``wav_dir`` (sorted by name).  Returns ``{"files": [{"file", "samples", "nats_per_sample",
     "bits_per_sample"}, ...], "total": {"samples", "nats_per_sample", "bits_per_sample"}}``, the total weighted by
     samples, and prints one line per file and one for the total unless ``verbose`` is off.  A checkpoint conditioned on
@@ -154,7 +174,10 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     A locally conditioned checkpoint scores every file under its feature file in ``local_dir`` (train_audio/local.py); the
     pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop.  ``local_mel`` ({"win": W}, the
     checkpoint's "mel" entry): without ``local_dir``, every file is scored under the log-mel features of its own tokens.
-    ``resample``: every file is read at the model's sampling_rate (``data.load_audio_file(..., rate=)``, on the network's device)."""
+    ``resample``: every file is read at the model's sampling_rate (``data.load_audio_file(..., rate=)``, on the network's device).
+    ``shard`` = (rank, world), inside a process group of that size: this process scores ``files[rank::world]`` -- possibly no
+    file --, the rows are exchanged (``all_gather_object``) and every rank returns the whole table.  A file's row does not depend
+    on the other files and the total is summed in sorted order, so the table is the single-process one, value for value."""
     local = getattr(net, "local", None)
     _local.require_match(local, local_dir is not None or local_mel is not None, "evaluate", "--local-dir FEAT_DIR or --local-mel")
     if local is not None:
@@ -162,10 +185,10 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
     if not files:
         raise Exception("no .wav file in {}".format(wav_dir))
-    rows, nats, samples = [], 0.0, 0
+    rows = []
     labels = getattr(net, "speakers", None)
     cids = {fn: None if labels is None else _speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files}
-    for fn in files:
+    for fn in files if shard is None else files[int(shard[0])::int(shard[1])]:
         rkw = dict(rate=int(params.sampling_rate), device=net.device) if resample else {}
         tokens, rate = data.load_audio_file(os.path.join(wav_dir, fn), quantization_steps=params.quantization_steps, **rkw)
         lkw = {} if local is None else {"local": _local.with_extra_column(
@@ -173,11 +196,12 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
             getattr(net, "local_interp", "repeat"), getattr(net, "local_upsample", 1))}
         row = scoring.summarize(net.score(tokens, chunk_width=chunk_width, batch_size=batch_size, condition=cids[fn], **lkw))
         rows.append(dict(file=fn, **row))
-        nats += row["nats_per_sample"] * row["samples"]
-        samples += row["samples"]
-    mean = nats / samples if samples else 0.0
-    table = {"files": rows, "total": {"samples": samples, "nats_per_sample": mean,
-                                      "bits_per_sample": mean / math.log(2.0)}}
+    if shard is not None:
+        import torch.distributed as dist
+        per_rank = [None] * int(shard[1])
+        dist.all_gather_object(per_rank, rows)
+        rows = merge_rows(per_rank)
+    table = table_of(rows)
     if verbose:
         for r in rows + [dict(file="total", **table["total"])]:
             sys.stdout.write("{:<32} {:>10d} samples  {:.6f} nats/sample  {:.6f} bits/sample\n".format(
@@ -187,8 +211,24 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
     copy = copy_synthesis_job(args)                          # before a model is built
+    gpus = getattr(args, "gpus", 1)
+    try:
+        _launch.check_gpus(gpus)
+    except ValueError as e:
+        ap.error(str(e))
+    if gpus > 1:
+        # --gpus N: this process starts the N ranks of this very command line as a child (train_audio/launch.py) and hands their
+        # exit code on; it builds no model and touches no device.  A rank finds WORLD_SIZE set and scores its files
+        if copy is not None:
+            raise SystemExit("evaluate: --gpus {} covers the likelihood table; --copy-synthesis runs on one device".format(gpus))
+        if not _launch.in_rank():
+            code = _launch.run("wavenet_amd.train_audio.evaluate", sys.argv[1:] if argv is None else list(argv), gpus)
+            if code:
+                raise SystemExit(code)
+            return None
     args.fast, args.seed = copy is not None, None            # what train_audio.model.build reads beyond the shared flags
     if copy is not None:
         params, net = _model.build(args)
@@ -202,13 +242,17 @@ def main(argv=None):
     if want_mel and _local.load_mel(args.model_dir) is None:                 # before a model is built
         raise SystemExit("evaluate: --local-mel needs a checkpoint trained with train --local-mel ({} has no \"mel\")".format(
             os.path.join(args.model_dir, _local.FILE)))
-    params, net = _model.build(args)
-    table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
-                         local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None,
-                         resample=bool(getattr(args, "resample", False)))
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(table, f, indent=2)
+    rank, world = _launch.join(args)                         # before a model is built; (0, 1) without --gpus
+    with _launch.rank_stdout(rank):                          # rank 0 alone prints, and writes --json
+        params, net = _launch.build_in_turn(lambda: _model.build(args), rank, world)
+        skw = {} if world == 1 else {"shard": (rank, world)}
+        table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
+                             local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None,
+                             resample=bool(getattr(args, "resample", False)), **skw)
+        if args.json and rank == 0:
+            with open(args.json, "w") as f:
+                json.dump(table, f, indent=2)
+    _launch.leave(world)                                     # a barrier precedes exit
     return table
 
 

@@ -681,6 +681,8 @@ def _seconds_given(argv) -> bool:
 
 def main(argv=None):
     args = _args.parse(argv)
+    if args.gpus != 1:
+        raise SystemExit("generate: --gpus {} belongs to train and evaluate; generation runs on one device".format(args.gpus))
     best_of, report = likelihood_job(args)
     chunk_frames, ring_frames = stream_job(args)
     tile = tile_job(args)

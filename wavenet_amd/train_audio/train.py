@@ -14,12 +14,13 @@ import numpy as np
 import torch
 
 from .. import TrainStepGraph, data
-from ..corpus import Corpus, columns_per_crop
+from ..corpus import Corpus, check_shard, columns_per_crop
 from ..graph import default_loss
 from ..wavenet import coarse_frames_needed
 from . import args as _args
 from . import model as _model
 from .evaluate import evaluate_dir
+from . import launch as _launch
 from . import local as _local
 from . import speakers as _speakers
 
@@ -64,15 +65,25 @@ class _Crops(object):
             raise Exception("signal too short for input_width + train_width")
         self.signal = torch.as_tensor(signal.astype(np.int32)).to(device)
         self.col = torch.arange(input_width + target_width + 1, device=device)
+        self.last_draw = None
 
-    def draw(self, batch_size: int):
+    def draw(self, batch_size: int, shard=None):
+        """``shard`` = (lo, hi), a rank of a data-parallel run: the ``randint`` call is the global one all the same --
+        ``batch_size`` starts, all of them kept in ``last_draw`` -- and crops lo .. hi - 1 of it are gathered."""
         hi = self.n - self.tw - self.iw - 1
         feats = None
         phases = None
+
+        def mine(drawn):
+            self.last_draw = drawn
+            if shard is None:
+                return drawn
+            lo, up = check_shard(shard, batch_size)
+            return drawn[lo:up]
         if self.features is None:
-            starts = np.random.randint(0, hi, size=batch_size)
+            starts = mine(np.random.randint(0, hi, size=batch_size))
         elif self.crop == "sample":
-            starts = np.random.randint(0, hi, size=batch_size)        # the feature-less draw: same seed, same crops
+            starts = mine(np.random.randint(0, hi, size=batch_size))  # the feature-less draw: same seed, same crops
             pos = starts + self.shift
             phases = (pos % self.hop).astype(np.int32)
             first = torch.as_tensor(pos // self.hop).to(self.col.device)
@@ -85,7 +96,7 @@ class _Crops(object):
             r = (-self.shift) % self.hop
             if hi - r <= 0:
                 raise Exception("signal too short for a crop that starts on a feature column")
-            starts = r + self.hop * np.random.randint(0, (hi - r + self.hop - 1) // self.hop, size=batch_size)
+            starts = mine(r + self.hop * np.random.randint(0, (hi - r + self.hop - 1) // self.hop, size=batch_size))
             first = torch.as_tensor((starts + self.shift) // self.hop).to(self.col.device)
             feats = self.features[:, first[:, None] + self.fcol[None, :]].permute(1, 0, 2).contiguous()
         idx = torch.as_tensor(starts).to(self.col.device)[:, None] + self.col[None, :]
@@ -131,12 +142,14 @@ def train_audio(net, params, path_to_file, batch_size=16, train_width=16, repeat
     # a conditioned model: every crop carries the label of the file it came from
     labels = getattr(net, "speakers", None)
     cond = None
+    shard = rank_shard(net, batch_size)
+    skw = {} if shard is None else {"shard": shard}
     if labels is not None:
         cid = _speakers.class_id(labels, _speakers.speaker_label(path_to_file), os.path.basename(path_to_file))
-        cond = torch.full((batch_size,), cid, device=net.device, dtype=torch.int64)
+        cond = torch.full((batch_size if shard is None else shard[1] - shard[0],), cid, device=net.device, dtype=torch.int64)
 
     def draw():
-        drawn = crops.draw(batch_size)
+        drawn = crops.draw(batch_size, **skw)
         lkw = {} if local is None else {"local": drawn[2]}
         if len(drawn) > 3:
             lkw["local_phase"] = drawn[3]                           # a phase per crop (--local-crop sample)
@@ -150,7 +163,8 @@ def run_updates(net, params, draw, repeat, key, use_graph, state, name, width):
     """``repeat`` updates, each on the batch ``draw()`` hands back -- (x, tgt, condition or None, the ``local=`` /
     ``local_phase=`` keywords of the step) -- through the replayed graph of shape ``key`` (kept in ``state``) or op by op;
     returns their summed loss.  ``name`` and ``width`` are what the progress line says of the source.  The one update loop of
-    the per-file path (``train_audio``) and of the corpus path (``train_corpus``)."""
+    the per-file path (``train_audio``) and of the corpus path (``train_corpus``).  On a data-parallel network ``draw()`` hands
+    back this rank's shard of each global batch, and the sum returned is the global batch's, the same on every rank."""
     sum_loss = torch.zeros((), device=net.device, dtype=torch.float64)
     graph = None
     skipped = 0
@@ -184,7 +198,15 @@ def run_updates(net, params, draw, repeat, key, use_graph, state, name, width):
         if batch_index % 10 == 0:
             sys.stdout.write("\r\t{} - {} width; {}/{}".format(name, width, batch_index, repeat))
             sys.stdout.flush()
-    return float(sum_loss.item())
+    total = float(sum_loss.item())
+    # data parallel: every rank summed the losses of its own shards; one mean over ranks per call, none per update
+    return total if net._dp_group is None else net._dp_group.mean_loss(total)
+
+
+def rank_shard(net, batch_size):
+    """The crops [lo, hi) of a global batch that this process trains on: None without data parallelism
+    (``WaveNet.enable_data_parallel``), else ``dp.shard``'s equal share -- a batch that does not divide by the ranks stops."""
+    return None if net._dp_group is None else net._dp_group.shard(batch_size)
 
 
 def load_corpus(net, params, wav_dir, files, local_dir=None, local_mel=None, resample=False):
@@ -223,8 +245,11 @@ def train_corpus(net, params, corpus, batch_size=16, train_width=16, repeat=1000
         n_cols = columns_per_crop(iw, train_width, corpus.hop, local_crop, getattr(net, "local_interp", "repeat"),
                                   getattr(net, "local_upsample", 1))
 
+    shard = rank_shard(net, batch_size)
+    skw = {} if shard is None else {"shard": shard}
+
     def draw():
-        x, tgt, feats, cond, phases = corpus.draw(batch_size, train_width, local_crop, n_cols)
+        x, tgt, feats, cond, phases = corpus.draw(batch_size, train_width, local_crop, n_cols, **skw)
         lkw = {} if feats is None else {"local": feats}
         if feats is not None and local_crop == "sample":
             lkw["local_phase"] = phases
@@ -234,16 +259,19 @@ def train_corpus(net, params, corpus, batch_size=16, train_width=16, repeat=1000
                        int(corpus.tokens.size))
 
 
-def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None, resample=False):
+def validate(net, params, wav_dir, epoch, local_dir=None, local_mel=None, resample=False, shard=None):
     """The held-out negative log-likelihood after an epoch: one line for the weights being trained and, when a weight
-    average is kept, one for the averaged weights."""
+    average is kept, one for the averaged weights.  ``shard`` = (rank, world): the held-out files are scored by the ranks in
+    turn (``evaluate_dir``); every rank forms both lines."""
+    skw = {} if shard is None else {"shard": shard}
+
     def line(what, total):
         sys.stdout.write("epoch: {} - held-out {}: {:.6f} nats/sample  {:.6f} bits/sample  ({} samples)\n".format(
             epoch, what, total["nats_per_sample"], total["bits_per_sample"], total["samples"]))
-    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample)["total"])
+    line("weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample, **skw)["total"])
     if net.ema_enabled:
         with net.ema_weights():
-            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample)["total"])
+            line("ema weights", evaluate_dir(net, params, wav_dir, verbose=False, local_dir=local_dir, local_mel=local_mel, resample=resample, **skw)["total"])
     sys.stdout.flush()
 
 
@@ -257,7 +285,32 @@ def main(argv=None):
                 args.batch_size, args.train_width, args.repeat))
         if not os.path.isdir(args.wav_dir) or not any(fn.endswith(".wav") for fn in os.listdir(args.wav_dir)):
             raise SystemExit("train --corpus: no .wav file in {}".format(args.wav_dir))
-    params, net = _model.build(args, train=True)
+    if args.gpus > 1:
+        # --gpus N: this process checks, starts the N ranks of this very command line as a child (train_audio/launch.py) and
+        # hands their exit code on; it builds no model and touches no device.  A rank finds WORLD_SIZE set and trains
+        try:
+            _launch.check_batch(args.batch_size, args.gpus)
+        except ValueError as e:
+            raise SystemExit("train: {}".format(e))
+        if not _launch.in_rank():
+            code = _launch.run("wavenet_amd.train_audio.train", sys.argv[1:] if argv is None else list(argv), args.gpus)
+            if code:
+                raise SystemExit(code)
+            return None
+    rank, world = _launch.join(args)                                # before a model is built; (0, 1) without --gpus
+    with _launch.rank_stdout(rank):                                 # rank 0 alone prints
+        average_loss = train(args, rank, world)
+    _launch.leave(world)                                            # a barrier precedes exit
+    return average_loss
+
+
+def train(args, rank=0, world=1):
+    """The run of one process: all of it without ``--gpus``, one rank of ``world`` with it (``launch.join`` has been called).  The
+    ranks make the same draws from one seed and each gathers its shard (``rank_shard``); rank 0 alone writes files."""
+    args.seed = _launch.shared_seed(args.seed, rank, world)
+    params, net = _launch.build_in_turn(lambda: _model.build(args, train=True), rank, world)
+    if world > 1:
+        net.enable_data_parallel()                                  # rank 0's weights, optimiser state and weight average
     _local.require_match(net.local, args.local_dir is not None or args.local_mel, "train", "--local-dir FEAT_DIR or --local-mel")
     local_mel = net.local_mel if args.local_mel else None      # (--local-dir on such a checkpoint: the feature files win)
     np.random.seed(args.seed)
@@ -284,6 +337,11 @@ def main(argv=None):
             raise Exception("signal too short for input_width + train_width: no file of {} holds a crop".format(args.wav_dir))
         print("corpus: {} samples and {} training windows in {} files, {} bytes on the device".format(
             int(corpus.tokens.size), int(counts.sum()), int((counts > 0).sum()), corpus.device_bytes()))
+
+    def save():
+        if rank == 0:
+            net.save(args.model_dir)
+    vkw = {} if world == 1 else {"shard": (rank, world)}
     start_time = time.time()
     graphs = {}
     average_loss = None
@@ -294,20 +352,21 @@ def main(argv=None):
                 average_loss += train_corpus(net, params, corpus, batch_size=args.batch_size, train_width=args.train_width,
                                              repeat=args.repeat, use_graph=not args.no_graph, state=graphs,
                                              local_crop=args.local_crop or "frame")
-                net.save(args.model_dir)
+                save()
                 continue
             average_loss += train_audio(net, params, os.path.join(args.wav_dir, fn), batch_size=args.batch_size,
                                         train_width=args.train_width, repeat=args.repeat,
                                         use_graph=not args.no_graph, state=graphs, local_dir=args.local_dir,
                                         local_crop=args.local_crop or "frame", local_mel=local_mel, resample=args.resample)
-            net.save(args.model_dir)
+            save()
         average_loss /= len(files)
         sys.stdout.write("\033[2K\repoch: {} - {:.4e} loss - {} min\n".format(
             epoch, average_loss, int((time.time() - start_time) / 60)))
         sys.stdout.flush()
-        net.save(args.model_dir)
+        save()
         if args.valid_wav_dir:
-            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir, local_mel=local_mel, resample=args.resample)
+            validate(net, params, args.valid_wav_dir, epoch, local_dir=args.local_dir, local_mel=local_mel, resample=args.resample,
+                     **vkw)
     return average_loss
 
 
