@@ -14,7 +14,12 @@ exactly when row 1 < threshold.  Column k sits on ``features.log_mel``'s column 
     f0        a, b, g = c[tau* - 1], c[tau*], c[tau* + 1]; den = a - 2 b + g; shift = 0.5 (a - g) / den if den > 0 else 0, clamped
               to [-1, 1]; f0 = rate / (tau* + shift)
 
-``Pitch`` computes the same on the device (libwavenet_pitch.so: wn_pitch), one launch per batch of clips."""
+``Pitch`` computes the same on the device (libwavenet_pitch.so: wn_pitch), one launch per batch of clips.
+
+``pitch_channels(rows, fmin, fmax)`` -> (3, n): what a network is conditioned on -- voiced (1 / 0), log-F0 on a scale where fmin is 0
+and fmax is 1 (0 where unvoiced; never clamped: the refinement may leave [fmin, fmax] by a fraction of a lag, and the value follows
+it) and the aperiodicity min(c[tau*], 1).  ``Pitch.channels`` is the same map in float32 on the device, ``scale_f0`` moves the
+pitch of such channels, ``Pitch.stream`` makes the rows as the audio arrives (``pitch_stream_frames`` says how many)."""
 from __future__ import annotations
 
 import math
@@ -103,6 +108,75 @@ def yin_select(curve, tau_min: int, threshold: float, rate, dtype=np.float64):
 def yin(signal, rate, hop: int = 256, win: int = 1024, fmin: float = 60.0, fmax: float = 500.0, threshold: float = 0.15):
     tau_min, tau_max = pitch_lags(rate, fmin, fmax)
     return yin_select(yin_curve_lags(signal, hop, win, tau_max), tau_min, threshold, rate, np.float64)[1]
+
+
+# ---- pitch as conditioning channels -------------------------------------------------------------------------------------------------
+PITCH_CHANNELS = 3             # voiced, log-F0, aperiodicity
+
+
+def _check_band(who, fmin, fmax):
+    if not fmin > 0:
+        raise ValueError("%s: fmin = %r; it takes fmin > 0" % (who, fmin))
+    if not fmax > fmin:
+        raise ValueError("%s: fmax = %r; it takes fmax > fmin = %r" % (who, fmax, fmin))
+
+
+def pitch_channels(rows, fmin: float = 60.0, fmax: float = 500.0) -> np.ndarray:
+    """(2, n) pitch rows (F0 with 0 for unvoiced; c[tau*]) -> (3, n) float64 conditioning channels:
+
+        row 0   1 where f0 > 0, else 0
+        row 1   (log2(f0) - log2(fmin)) / log2(fmax / fmin) where voiced, else 0 -- fmin is 0, fmax is 1, nothing is clamped
+        row 2   min(c[tau*], 1)"""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[0] != 2:
+        raise ValueError("pitch_channels: rows of shape %s; it takes (2, n)" % (rows.shape,))
+    _check_band("pitch_channels", fmin, fmax)
+    voiced = rows[0] > 0
+    out = np.zeros((PITCH_CHANNELS, rows.shape[1]), dtype=np.float64)
+    out[0, voiced] = 1.0
+    out[1, voiced] = (np.log2(rows[0, voiced]) - math.log2(fmin)) / math.log2(fmax / fmin)
+    out[2] = np.minimum(rows[1], 1.0)
+    return out
+
+
+def channel_constants(fmin, fmax):
+    """(lo, k) of the float32 map: lo = float32(log2(fmin)), k = float32(1 / log2(fmax / fmin)); lf = (log2(f0) - lo) * k."""
+    _check_band("pitch_channels", fmin, fmax)
+    return np.float32(math.log2(fmin)), np.float32(1.0 / math.log2(fmax / fmin))
+
+
+def scale_f0(channels, scale, fmin: float = 60.0, fmax: float = 500.0):
+    """Pitch channels (3, n) -- a numpy array or a tensor -- with the pitch of the voiced columns multiplied by ``scale``:
+    log2(scale) / log2(fmax / fmin), rounded to the array's type, is added to row 1 where row 0 is 1.  Everything else keeps its
+    bits, and ``scale`` = 1 hands the input back."""
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("scale_f0: scale = %r; it takes a finite scale > 0" % (scale,))
+    _check_band("scale_f0", fmin, fmax)
+    if len(channels.shape) != 2 or channels.shape[0] != PITCH_CHANNELS:
+        raise ValueError("scale_f0: channels of shape %s; it takes (3, n)" % (tuple(channels.shape),))
+    if scale == 1.0:
+        return channels
+    delta = math.log2(scale) / math.log2(fmax / fmin)
+    if isinstance(channels, np.ndarray):
+        out = channels.copy()
+        out[1] = np.where(channels[0] == 1, channels[1] + channels.dtype.type(delta), channels[1])
+        return out
+    import torch
+    out = channels.clone()
+    out[1] = torch.where(channels[0] == 1, channels[1] + delta, channels[1])
+    return out
+
+
+def pitch_stream_frames(total_fed: int, hop: int, span: int, final: bool = False) -> int:
+    """Columns a streaming pitch analyser has emitted once ``total_fed`` samples have arrived.  Column k reads the ``span``
+    samples from k hop - span // 2 on, the last of them sample k hop - span // 2 + span - 1, so it is out as soon as
+    total_fed >= k hop + span - span // 2: a look-ahead of span - span // 2 samples.  ``final`` (after ``flush``): every column of
+    the signal, ``frame_count(total_fed, hop)``."""
+    total_fed, hop, ahead = int(total_fed), int(hop), int(span) - int(span) // 2
+    if final:
+        return frame_count(total_fed, hop)
+    return 0 if total_fed < ahead else (total_fed - ahead) // hop + 1
 
 
 # ---- the same on the device (libwavenet_pitch.so: wn_pitch) -----------------------------------------------------------------------
@@ -218,3 +292,68 @@ class Pitch(ClipAnalyser):
         x = self._signal(x, quantization_steps)
         outs, curves = self._launch([(x, 0, 0, frame_count(x.numel(), self.hop), True, True)], quantization_steps, curve=True)
         return outs[0], curves[0]
+
+    def channels(self, rows):
+        """``pitch_channels`` of (2, n) device rows, in float32 with elementwise torch operations: lo = float32(log2(fmin)),
+        k = float32(1 / log2(fmax / fmin)), lf = (log2(f0) - lo) * k.  A column's bits depend on its own column of ``rows``."""
+        import torch
+        if rows.dim() != 2 or rows.shape[0] != 2:
+            raise ValueError("Pitch.channels: rows of shape %s; it takes (2, n)" % (tuple(rows.shape),))
+        lo, k = (float(v) for v in channel_constants(self.fmin, self.fmax))
+        rows = rows.to(torch.float32)
+        f0, voiced = rows[0], rows[0] > 0
+        lf = (torch.log2(torch.where(voiced, f0, torch.ones_like(f0))) - lo) * k
+        return torch.stack([voiced.to(torch.float32), torch.where(voiced, lf, torch.zeros_like(lf)), torch.clamp(rows[1], max=1.0)])
+
+    def stream(self, quantization_steps=None):
+        return PitchStream(self, quantization_steps)
+
+
+class PitchStream(object):
+    """``Pitch.stream()``: ``feed(samples)`` returns the (2, k) columns whose spans the samples fed so far cover (k may be 0),
+    ``flush()`` the remaining ones, with zeros beyond the signal's end.  Whatever the chunking, the columns concatenated are
+    ``Pitch(...)(signal)`` bit for bit; ``pitch_stream_frames`` says how many there are after each call.  Only the samples that a
+    later column still reads are kept: from next_column * hop - span // 2 on."""
+
+    def __init__(self, pitch: Pitch, quantization_steps=None):
+        self.pitch, self.q = pitch, quantization_steps
+        self.total = 0           # samples fed
+        self.emitted = 0         # columns returned
+        self.start = 0           # signal index of tail[0]
+        self.tail = None
+        self.closed = False
+
+    def _empty(self):
+        import torch
+        return torch.empty((2, 0), dtype=torch.float32, device=self.pitch.device)
+
+    def _emit(self, upto: int, final: bool):
+        count = upto - self.emitted
+        if count <= 0:
+            return self._empty()
+        p = self.pitch
+        # frame 0 of the launch is column `emitted`; its centre sits at tail index emitted * hop - start
+        out = p._launch([(self.tail, self.emitted * p.hop - self.start, 0, count, self.start == 0, final)], self.q)[0]
+        self.emitted = upto
+        keep_from = min(max(self.start, self.emitted * p.hop - p.span // 2), self.total)
+        if keep_from > self.start:
+            self.tail = self.tail[keep_from - self.start:].clone()
+            self.start = keep_from
+        return out
+
+    def feed(self, samples):
+        import torch
+        if self.closed:
+            raise ValueError("Pitch.stream: feed after flush")
+        x = self.pitch._signal(samples, self.q)
+        self.tail = x if self.tail is None else torch.cat([self.tail, x])
+        self.total += x.numel()
+        return self._emit(pitch_stream_frames(self.total, self.pitch.hop, self.pitch.span), False)
+
+    def flush(self):
+        if self.closed:
+            raise ValueError("Pitch.stream: flush twice")
+        self.closed = True
+        if self.tail is None:
+            return self._empty()
+        return self._emit(pitch_stream_frames(self.total, self.pitch.hop, self.pitch.span, True), True)

@@ -79,6 +79,20 @@ _MEL_FLAGS = (
     (("--mels",), int, None, "train --local-mel: mel channels F (80 unless local.json says otherwise)"),
     (("--win",), int, None, "train --local-mel: analysis window in samples (1024 unless local.json says otherwise)"),
 )
+# pitch channels behind the mel rows (acoustic.MelPitch; train_audio/local.py "pitch"): off, attributes of the namespace only
+# when given
+_PITCH_FLAGS = (
+    (("--local-pitch",), None, False, "train --local-mel: add three pitch channels behind the mel rows -- voiced, log-F0 between --f0-min "
+                                      "(0) and --f0-max (1), aperiodicity -- tracked on the device from the same audio "
+                                      "(pitch.Pitch); the three settings go to <model-dir>/local.json, whose channels are then "
+                                      "--mels + 3, and evaluate and generate follow it"),
+    (("--f0-min",), float, None, "train --local-pitch: lowest F0 in Hz (60 unless local.json says otherwise)"),
+    (("--f0-max",), float, None, "train --local-pitch: highest F0 in Hz (500 unless local.json says otherwise)"),
+    (("--f0-threshold",), float, None, "train --local-pitch: YIN's voicing threshold (0.15 unless local.json says otherwise)"),
+    (("--f0-scale",), float, 1.0, "generate, on a checkpoint trained with --local-pitch: multiply the pitch of every voiced column of "
+                                  "the features by S before the network sees them (--from-wav, --local, --local-dir; streamed "
+                                  "chunks included); excludes --rank mel and --keep"),
+)
 # activation storage of the run (WaveNet.set_storage): fp32, and an attribute of the namespace only when given
 _STORAGE_FLAGS = (
     (("--storage",), str, "fp32", "train, evaluate: activation storage, 'fp32' or 'bf16' (bfloat16 activations with fp32 accumulation "
@@ -178,6 +192,7 @@ class Args(argparse.Namespace):
     local_dir, local_hop, local, local_interp, local_crop = None, None, None, None, None
     local_upsample = None
     local_mel, mels, win, from_wav = False, None, None, None
+    local_pitch, f0_min, f0_max, f0_threshold, f0_scale = False, None, None, None, 1.0
     storage = "fp32"
     corpus = False
     resample = False
@@ -196,7 +211,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _GPUS_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _PITCH_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _GPUS_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)
@@ -268,6 +283,10 @@ def parse(argv=None):
             features._check_logmel_shape(args.mels, args.local_hop, args.win)      # what is given; model.build checks what is used
         except ValueError as e:
             ap.error("--local-mel: %s" % e)
+    if args.local_pitch and (not args.local_mel or args.local_dir is not None):
+        ap.error("--local-pitch (pitch channels made from the audio) goes with --local-mel, not with --local-dir FEAT_DIR")
+    if (args.f0_min is not None or args.f0_max is not None or args.f0_threshold is not None) and not args.local_pitch:
+        ap.error("--f0-min, --f0-max and --f0-threshold go with --local-pitch")
     if args.from_wav:
         bad = [f for f, on in (("--local", args.local), ("--local-dir", args.local_dir is not None), ("--keep", args.keep)) if on]
         if bad:

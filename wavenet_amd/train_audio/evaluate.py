@@ -86,13 +86,16 @@ def copy_synthesis_job(args):
 
 
 def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=None, resample=False, verbose: bool = True,
-                       **controls):
+                       forced: bool = False, **controls):
     """Resynthesise every .wav file of ``wav_dir`` (sorted by name) from its own features and compare the result with the file:
     ``metrics.copy_synthesis`` over all files, one ``generate_batch`` run (``net``: a ``FasterWaveNet`` whose checkpoint has
     "mel" in local.json).  A file is read as training reads it (``resample``: at the model's rate) and cut to ``seconds``; its
     features are its feature file in ``local_dir`` or, without one, its log-mel columns made on the device; its speaker is the
     label its name carries.  ``seed``: numpy's, set once before the files' uniforms are drawn in order.  ``controls``:
-    temperature, top_k, top_p.  Returns ``{"files": [{"file", "samples", "log_mel_distance_db", "f0_rmse_cents",
+    temperature, top_k, top_p.  A checkpoint with "pitch" in local.json: the network's features are ``acoustic.MelPitch``'s (mel
+    rows, then pitch channels), while the figures keep comparing pure ``LogMel`` columns (the mel count) and ``Pitch`` rows of file
+    and resynthesis.  ``forced``: every sample behind the window is given instead of drawn (the resynthesis is then the file and every
+    distance 0: features and metrics sit on one grid).  Returns ``{"files": [{"file", "samples", "log_mel_distance_db", "f0_rmse_cents",
     "f0_gross_error", "vuv_error", "voiced_frames", "nats_per_sample"}, ...], "total": {...}}`` -- the total weighted by what each
     figure was averaged over (``metrics.total``: compared columns, frames voiced in both, emitted samples) -- and prints one line
     per file and one for the total unless ``verbose`` is off."""
@@ -101,6 +104,9 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
     from .. import metrics
     from ..pitch import Pitch
     local, mel = getattr(net, "local", None), getattr(net, "local_mel", None)
+    with_pitch = getattr(net, "local_pitch", None)
+    settings = _local.analysis_settings(mel, with_pitch)
+    mels = None if local is None else local[0] - (_local.PITCH_CHANNELS if with_pitch else 0)
     if local is None or mel is None:
         raise SystemExit("evaluate: --copy-synthesis needs a checkpoint trained with train --local-mel")
     files = sorted(fn for fn in os.listdir(wav_dir) if fn.endswith(".wav"))
@@ -123,7 +129,7 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
             tokens.append(t)
             rates.append(int(rate))
             feats.append(_local.with_extra_column(
-                _local.file_or_mel_features(local_dir, mel, fn, t, rate, local[0], local[1], Q),
+                _local.file_or_mel_features(local_dir, settings, fn, t, rate, local[0], local[1], Q),
                 getattr(net, "local_interp", "repeat"), getattr(net, "local_upsample", 1)))
         if len(set(rates)) > 1:
             raise SystemExit("evaluate: --copy-synthesis analyses all files on one column grid, and {} holds files at {} Hz: give "
@@ -135,8 +141,9 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
         if seed is not None:
             np.random.seed(seed)
         uniforms = [np.random.random_sample(t.size - W) for t in tokens]
-        got = metrics.copy_synthesis(net, tokens, feats, cids, uniforms, _local.mel_analyser(rates[0], local[0], local[1], mel["win"]),
-                                     pitch, **controls)
+        fkw = {"forced": [t[W:] for t in tokens]} if forced else {}
+        got = metrics.copy_synthesis(net, tokens, feats, cids, uniforms, _local.mel_analyser(rates[0], mels, local[1], mel["win"]),
+                                     pitch, **fkw, **controls)
     table = {"files": [dict([("file", fn), ("samples", r["samples"])] + [(k, r[k]) for k in COPY_KEYS]) for fn, r in zip(files, got)]}
     whole = metrics.total(got)
     table["total"] = dict([("samples", whole["samples"])] + [(k, whole[k]) for k in COPY_KEYS])
@@ -173,7 +180,8 @@ def evaluate_dir(net, params, wav_dir, chunk_width: int = 16384, batch_size: int
     speakers scores every file under the label its name carries (train_audio/speakers.py); an unknown label stops the run.
     A locally conditioned checkpoint scores every file under its feature file in ``local_dir`` (train_audio/local.py); the
     pieces of a launch share a phase, so ``chunk_width`` is rounded up to a multiple of the hop.  ``local_mel`` ({"win": W}, the
-    checkpoint's "mel" entry): without ``local_dir``, every file is scored under the log-mel features of its own tokens.
+    checkpoint's "mel" entry; with its "pitch" entry inside, ``local.analysis_settings``, the pitch channels follow the mel rows):
+    without ``local_dir``, every file is scored under the log-mel features of its own tokens.
     ``resample``: every file is read at the model's sampling_rate (``data.load_audio_file(..., rate=)``, on the network's device).
     ``shard`` = (rank, world), inside a process group of that size: this process scores ``files[rank::world]`` -- possibly no
     file --, the rows are exchanged (``all_gather_object``) and every rank returns the whole table.  A file's row does not depend
@@ -247,7 +255,8 @@ def main(argv=None):
         params, net = _launch.build_in_turn(lambda: _model.build(args), rank, world)
         skw = {} if world == 1 else {"shard": (rank, world)}
         table = evaluate_dir(net, params, args.wav_dir, chunk_width=args.chunk_width, batch_size=args.batch_size,
-                             local_dir=getattr(args, "local_dir", None), local_mel=net.local_mel if want_mel else None,
+                             local_dir=getattr(args, "local_dir", None),
+                             local_mel=_local.analysis_settings(net.local_mel, getattr(net, "local_pitch", None)) if want_mel else None,
                              resample=bool(getattr(args, "resample", False)), **skw)
         if args.json and rank == 0:
             with open(args.json, "w") as f:

@@ -17,7 +17,10 @@ run keeps everything and ``--report`` is the decoder's own likelihood of the fil
 emitted samples, kept ones included -- a candidate is judged by how the real audio continues from what was drawn into it.
 ``--fast --local FILE.npy --chunk-frames C [--ring-frames R]`` vocodes as a stream (``FasterWaveNet.open_stream``): C feature
 columns at a time go to the decoder, which draws what they allow; ``generated.wav`` grows as it goes, and the time to its first
-chunk is printed."""
+chunk is printed.
+On a checkpoint trained with ``train --local-mel --local-pitch`` the features carry three pitch channels behind the mel rows
+(``acoustic.MelPitch`` makes them from a ``--from-wav`` recording, streamed or not), and ``--f0-scale S`` multiplies the pitch of
+every voiced column by S before the network sees it (``pitch.scale_f0``)."""
 from __future__ import annotations
 
 import json
@@ -153,6 +156,37 @@ class MelRank(object):
                 [dist[u * K + k] for u, (k, _) in enumerate(ranked)])
 
 
+def f0_scale_job(args):
+    """``generate --f0-scale S``: the checks, made before a model is built.  Returns None without the flag, else (S, fmin, fmax,
+    F): the scale, the checkpoint's pitch band and its mel count -- rows F .. F + 2 of a feature array are the pitch channels."""
+    if "f0_scale" not in vars(args):
+        return None
+    S = float(args.f0_scale)
+    pitch = _local.load_pitch(args.model_dir)
+    if pitch is None:
+        raise SystemExit("generate: --f0-scale moves the pitch channels of a checkpoint trained with train --local-mel --local-pitch "
+                         "({} has no \"pitch\")".format(os.path.join(args.model_dir, _local.FILE)))
+    if not (math.isfinite(S) and S > 0):
+        raise SystemExit("generate: --f0-scale S needs a finite S > 0, got {}".format(args.f0_scale))
+    if args.rank == "mel":
+        raise SystemExit("generate: --f0-scale does not go with --rank mel: the recording is no target for a shifted voice")
+    if args.keep:
+        raise SystemExit("generate: --f0-scale does not go with --keep: the kept samples carry the recording's own pitch")
+    return S, pitch["fmin"], pitch["fmax"], _local.mel_count(args.model_dir)
+
+
+def scaled_f0(feats, f0):
+    """A (F + 3, columns) feature array (numpy or tensor) as the network is to see it under ``--f0-scale``: ``pitch.scale_f0`` on
+    rows F .. F + 2, the other rows' bits kept; the array itself without the flag or at S = 1."""
+    if f0 is None or f0[0] == 1.0:
+        return feats
+    from ..pitch import scale_f0
+    S, fmin, fmax, F = f0
+    out = feats.copy() if isinstance(feats, np.ndarray) else feats.clone()
+    out[F:] = scale_f0(feats[F:], S, fmin, fmax)
+    return out
+
+
 def tile_job(args):
     """``generate --tile auto|2|4|8|16``: the check, made before a model is built.  Returns None without the flag, else what
     ``FasterWaveNet.batch_tile`` takes: ``"auto"`` or the tile size."""
@@ -281,7 +315,10 @@ class MelColumns(object):
     until ``take`` has its columns or the recording ends (``flush``); ``extra`` copies of the last column follow it, what
     ``local.with_extra_column`` appends to a file's array.  The columns are the one-shot call's, bit for bit."""
 
-    def __init__(self, mel, tokens, quantization_steps, chunk_frames, extra=0):
+    def __init__(self, mel, tokens, quantization_steps, chunk_frames, extra=0, f0=None):
+        """``mel``: a ``features.LogMel`` or an ``acoustic.MelPitch`` (``stream``, ``hop`` and the stream's ``_empty`` are all that is
+        used); ``f0``: what ``f0_scale_job`` returned -- every chunk handed out goes through ``scaled_f0``."""
+        self.f0 = f0
         self.an = mel.stream(quantization_steps)
         self.tokens = np.asarray(tokens, dtype=np.int32)
         self.step = int(chunk_frames) * mel.hop
@@ -308,6 +345,7 @@ class MelColumns(object):
         allc = torch.cat(self.have, dim=1) if self.have else self.an._empty()
         out, rest = allc[:, :k].contiguous(), allc[:, k:]
         self.have = [rest] if rest.shape[1] else []
+        out = scaled_f0(out, self.f0)
         return out.cpu().numpy() if host else out
 
 
@@ -415,13 +453,16 @@ def generate_streamed(net, params, local, chunk_frames, ring_frames=None, genera
     return filename, kept
 
 
-def from_wav_job(args, config, n_utt, chunk_frames):
+def from_wav_job(args, config, n_utt, chunk_frames, f0=None):
     """``generate --fast --from-wav FILE.wav``: every file read as training reads it and its log-mel features made on the device with
     the checkpoint's "mel" settings -> (one (F, frames) array per utterance, None), or with ``--chunk-frames`` (None, the streamed
     run's ``MelColumns``: nothing is computed yet, the column count follows from the file's length).  ``--resample``: the file is
     brought to the model's rate first, in one call also for a streamed run -- the silence trim needs the file's end.  Stops
-    before a model is built when the checkpoint was not trained with ``train --local-mel``."""
+    before a model is built when the checkpoint was not trained with ``train --local-mel``.  A checkpoint with "pitch": the
+    analyser is ``acoustic.MelPitch`` (mel rows, then pitch channels); ``f0`` (``f0_scale_job``) is handed to the streamed source,
+    the arrays of the one-shot path are scaled by the caller."""
     mel = _local.load_mel(args.model_dir)
+    pitch = _local.load_pitch(args.model_dir)
     if mel is None:
         raise SystemExit("generate: --from-wav makes the features from the recording and needs a checkpoint trained with "
                          "train --local-mel ({} has no \"mel\")".format(os.path.join(args.model_dir, _local.FILE)))
@@ -434,8 +475,9 @@ def from_wav_job(args, config, n_utt, chunk_frames):
             tokens, rate = data.load_audio_file(f, quantization_steps=Q, **read_kw(args, _model.load_params(args.model_dir)))
             if chunk_frames is not None:                 # streamed (one file): the analyser makes the columns as they are asked for
                 extra = (1 if _local.load_interp(args.model_dir) == "linear" else 0) + (1 if _local.load_upsample(args.model_dir) > 1 else 0)
-                return None, MelColumns(_local.mel_analyser(rate, config[0], config[1], mel["win"]), tokens, Q, chunk_frames, extra)
-            distinct[f] = _local.mel_features(tokens, rate, config[0], config[1], mel["win"], Q)
+                return None, MelColumns(_local.feature_analyser(rate, config[0], config[1], mel["win"], pitch), tokens, Q, chunk_frames,
+                                        extra, f0)
+            distinct[f] = _local.mel_features(tokens, rate, config[0], config[1], mel["win"], Q, pitch=pitch)
     files = args.from_wav * n_utt if len(args.from_wav) == 1 else args.from_wav
     return [distinct[f] for f in files], None
 
@@ -514,7 +556,7 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     return filenames, tokens
 
 
-def directory_job(args, seconds_given):
+def directory_job(args, seconds_given, f0=None):
     """``generate --fast --local-dir FEAT_DIR``: every check that needs no model, made before one is built.  Returns
     (names, features as the network takes them, samples to emit per file, class id per file or None)."""
     what = "generate --local-dir"
@@ -544,7 +586,7 @@ def directory_job(args, seconds_given):
             raise SystemExit("generate: the features of {}.npy cover {} samples, fewer than the {} of the window".format(
                 name, cover + iw - 1, iw))
         lengths.append(cover if cap is None else min(cover, cap))
-        feats.append(_local.with_extra_column(f, interp, upsample))
+        feats.append(_local.with_extra_column(scaled_f0(f, f0), interp, upsample))
     return names, feats, lengths, cids
 
 
@@ -687,10 +729,11 @@ def main(argv=None):
     chunk_frames, ring_frames = stream_job(args)
     tile = tile_job(args)
     rank_mel = rank_job(args)
+    f0 = f0_scale_job(args)
     seconds_given = _seconds_given(argv)
     kept = keep_job(args, seconds_given)
     if args.local_dir is not None:
-        names, feats, lengths, cids = directory_job(args, seconds_given)
+        names, feats, lengths, cids = directory_job(args, seconds_given, f0)
         params, net = _model.build(args)
         if tile is not None:
             net.batch_tile = tile
@@ -710,11 +753,14 @@ def main(argv=None):
                          "--from-wav FILE.wav" if args.from_wav else "--local FILE.npy")
     feats, mel_src = None, None
     if args.from_wav:
-        feats, mel_src = from_wav_job(args, config, n_utt or 1, chunk_frames)
+        feats, mel_src = from_wav_job(args, config, n_utt or 1, chunk_frames, f0)
     elif config is not None:
         distinct = {f: _local.read_features(f, config[0]) for f in set(args.local)}
         feats = [distinct[f] for f in (args.local * (n_utt or 1) if len(args.local) == 1 else args.local)]
-    targets = list(feats) if rank_mel else None         # the recordings' own columns, one array per utterance
+    mels = _local.mel_count(args.model_dir)              # (pitch channels behind the mel rows are no part of a mel distance)
+    targets = [f[:mels] for f in feats] if rank_mel else None         # the recordings' own columns, one array per utterance
+    if feats is not None:
+        feats = [scaled_f0(f, f0) for f in feats]
     params, net = _model.build(args)
     if tile is not None:               # every generate_batch / open_stream call of this run decodes in tiles
         net.batch_tile = tile
@@ -725,7 +771,7 @@ def main(argv=None):
 
         def analyser_of(rate):
             with torch.cuda.device(args.gpu_device):
-                return _local.mel_analyser(rate, config[0], config[1], win)
+                return _local.mel_analyser(rate, mels, config[1], win)
 
         rank = MelRank(analyser_of, [int(params.sampling_rate) if args.resample else _wav_rate(f) for f in files], targets,
                        params.quantization_steps, silence_window(params, input_width_of(params)))

@@ -50,6 +50,32 @@ def load_params(model_dir: str) -> Params:
     return params
 
 
+def local_pitch_settings(args, params, hop=None, win=None, had=None):
+    """``train --local-mel --local-pitch``: {"fmin", "fmax", "threshold"} from --f0-min / --f0-max / --f0-threshold, else from the
+    checkpoint's local.json, else the defaults -- after ``pitch.pitch_lags`` and ``pitch.Pitch``'s device refusal were tried with
+    the model's rate and the run's hop and window; a refusal stops the command.  None without --local-pitch.  ``hop``, ``win``,
+    ``had``: what ``build`` has resolved already; a caller without them (the driver, before a model is built) gets them resolved
+    the same way."""
+    if not bool(getattr(args, "local_pitch", False)):
+        return None
+    have = _local.load_config(args.model_dir)
+    if hop is None:
+        hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
+    if win is None:
+        was = _local.load_mel(args.model_dir) if have else None
+        win = getattr(args, "win", None) or (was["win"] if was else _local.DEFAULT_WIN)
+    if had is None:
+        had = _local.load_pitch(args.model_dir) if have else None
+    given = {"fmin": getattr(args, "f0_min", None), "fmax": getattr(args, "f0_max", None),
+             "threshold": getattr(args, "f0_threshold", None)}
+    pitch = {k: float(given[k] if given[k] is not None else (had or _local.DEFAULT_PITCH)[k]) for k in _local.PITCH_KEYS}
+    try:
+        _local.check_pitch(params.sampling_rate, hop, win, pitch)
+    except ValueError as e:
+        raise SystemExit("--local-pitch: {}".format(e))
+    return pitch
+
+
 def build(args, train: bool = False):
     """-> (params, wavenet) on ``cuda:<args.gpu_device>``.  There is no CPU mode (``-g -1`` in the reference): the product
     path is the HIP library and fails loudly without a device.
@@ -68,7 +94,9 @@ def build(args, train: bool = False):
     file the same way and ``net.local_interp`` is the file's mode; so does ``args.local_upsample`` (``"upsample"``, written
     for U > 1 only), and ``net.local_upsample`` is the file's factor.  ``args.local_mel`` (train) takes F, the hop and the
     window from --mels / --local-hop / --win instead of a feature file and adds ``"mel": {"win": W}``; ``net.local_mel`` is that
-    entry of the file (None without it)."""
+    entry of the file (None without it).  ``args.local_pitch`` (train, with ``args.local_mel``) adds 3 pitch channels behind the
+    mel rows: ``"pitch": {"fmin", "fmax", "threshold"}`` from --f0-min / --f0-max / --f0-threshold, ``"channels"`` = mels + 3, after
+    ``pitch.Pitch``'s refusals were tried at the model's rate; ``net.local_pitch`` is that entry of the file (None without it)."""
     params = load_params(args.model_dir)
     local_dir = getattr(args, "local_dir", None)
     if local_dir is not None and train:                                     # (evaluate and generate read the config only)
@@ -82,14 +110,17 @@ def build(args, train: bool = False):
         hop = getattr(args, "local_hop", None) or (have[1] if have else _local.DEFAULT_HOP)
         was = _local.load_mel(args.model_dir) if have else None
         win = getattr(args, "win", None) or (was["win"] if was else _local.DEFAULT_WIN)
-        mels = getattr(args, "mels", None) or (have[0] if have else _local.DEFAULT_MELS)
+        had = _local.load_pitch(args.model_dir) if have else None
+        mels = getattr(args, "mels", None) or (_local.mel_count(args.model_dir) if have else _local.DEFAULT_MELS)
         from .. import features
         try:
             features._check_logmel_shape(mels, hop, win)
         except ValueError as e:
             raise SystemExit("--local-mel: {}".format(e))
-        local = _local.ensure_config(args.model_dir, mels, hop, getattr(args, "local_interp", None),
-                                     getattr(args, "local_upsample", None), mel={"win": win})
+        pitch = local_pitch_settings(args, params, hop, win, had)           # three pitch channels behind the mel rows, or None
+        local = _local.ensure_config(args.model_dir, mels + (_local.PITCH_CHANNELS if pitch else 0), hop,
+                                     getattr(args, "local_interp", None), getattr(args, "local_upsample", None), mel={"win": win},
+                                     pitch=pitch)
     else:
         local = _local.load_config(args.model_dir)
     if bool(getattr(args, "speaker_prefix", False)):
@@ -106,6 +137,7 @@ def build(args, train: bool = False):
     net.speakers = table[0] if table else None
     net.local = local
     net.local_mel = _local.load_mel(args.model_dir) if local else None
+    net.local_pitch = _local.load_pitch(args.model_dir) if local else None
     params.dump()
     ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
     use_ema = bool(getattr(args, "ema", False))

@@ -227,7 +227,8 @@ def load_corpus(net, params, wav_dir, files, local_dir=None, local_mel=None, res
     if local is not None and local_dir is not None:
         feats = [_local.file_features(local_dir, fn, t.size, local[0], local[1]) for fn, t in zip(files, tokens)]
     elif local is not None:
-        feats = _local.mel_features_of_files(tokens, rates, local[0], local[1], local_mel["win"], params.quantization_steps)
+        feats = _local.mel_features_of_files(tokens, rates, local[0], local[1], local_mel["win"], params.quantization_steps,
+                                             pitch=local_mel.get("pitch"))
     labels = getattr(net, "speakers", None)
     classes = None if labels is None else [_speakers.class_id(labels, _speakers.speaker_label(fn), fn) for fn in files]
     return Corpus(tokens, input_width_of(params), params.quantization_steps, net.device, features=feats,
@@ -285,6 +286,10 @@ def main(argv=None):
                 args.batch_size, args.train_width, args.repeat))
         if not os.path.isdir(args.wav_dir) or not any(fn.endswith(".wav") for fn in os.listdir(args.wav_dir)):
             raise SystemExit("train --corpus: no .wav file in {}".format(args.wav_dir))
+    if args.f0_scale != 1.0:
+        raise SystemExit("train: --f0-scale belongs to generate")
+    if args.local_pitch:                                            # Pitch's refusals at the run's rate, hop and window, before a model is built
+        _model.local_pitch_settings(args, _model.load_params(args.model_dir))
     if args.gpus > 1:
         # --gpus N: this process checks, starts the N ranks of this very command line as a child (train_audio/launch.py) and
         # hands their exit code on; it builds no model and touches no device.  A rank finds WORLD_SIZE set and trains
@@ -312,7 +317,8 @@ def train(args, rank=0, world=1):
     if world > 1:
         net.enable_data_parallel()                                  # rank 0's weights, optimiser state and weight average
     _local.require_match(net.local, args.local_dir is not None or args.local_mel, "train", "--local-dir FEAT_DIR or --local-mel")
-    local_mel = net.local_mel if args.local_mel else None      # (--local-dir on such a checkpoint: the feature files win)
+    # (--local-dir on such a checkpoint: the feature files win); a "pitch" entry rides inside: mel rows, then pitch channels
+    local_mel = _local.analysis_settings(net.local_mel, getattr(net, "local_pitch", None)) if args.local_mel else None
     np.random.seed(args.seed)
     net.update_laerning_rate(args.lr)
     files = sorted(fn for fn in os.listdir(args.wav_dir) if fn.endswith(".wav"))
