@@ -185,6 +185,43 @@ def save_audio_file(filename, quantized_signal, quantization_steps: int = 256, f
     wavfile.write(filename, sampling_rate, audio)
 
 
+def pcm_table(quantization_steps: int = 256, format: str = "16bit_pcm", compat: bool = True) -> np.ndarray:
+    """(Q,) integers: per token the value :func:`save_audio_file` writes for it, ``(mulaw_decode(q) * scale).astype(dtype)`` --
+    ``pcm_table(Q)[tokens]`` is the signal of the file (``fold.unfold`` joins segments on these values)."""
+    scale, dtype = _pcm_format(format, compat)
+    s = mulaw_decode(np.arange(quantization_steps), quantization_steps, compat) * scale
+    if not compat:
+        info = np.iinfo(dtype)
+        s = np.clip(s, info.min, info.max)
+    return s.astype(dtype)
+
+
+def pcm_lookup_device(tokens, table):
+    """int32 token device tensor -> float32 device tensor of ``table[token]`` (``wn_mulaw_decode`` with ``table``, e.g.
+    :func:`pcm_table`'s integers, as its float32 table: 16-bit values are exact in float32)."""
+    import torch
+    from . import _lib
+    if not (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dtype == torch.int32):
+        raise _lib.WaveNetHipError("pcm_lookup_device needs an int32 tensor on a HIP device")
+    tab = torch.as_tensor(np.asarray(table).astype(np.float32)).to(tokens.device)
+    tokens = tokens.contiguous()
+    out = torch.empty(tokens.shape, dtype=torch.float32, device=tokens.device)
+    if tokens.numel():
+        _lib.check(_lib.lib().wn_mulaw_decode(_lib.ptr(tokens), _lib.ptr(tab), _lib.ptr(out), tokens.numel(), int(tab.numel()),
+                                             _lib.stream_ptr()), "wn_mulaw_decode")
+    return out
+
+
+def save_pcm_file(filename, pcm, sampling_rate: int = 48000):
+    """Integer PCM values (``pcm_table(Q)[tokens]``, or a cross-faded signal of such values) -> wav file, the mono signal
+    duplicated into two channels as :func:`save_audio_file` writes it."""
+    from scipy.io import wavfile
+    pcm = np.asarray(pcm)
+    if pcm.dtype.kind not in "iu":
+        raise Exception("save_pcm_file takes integer PCM values, got %s" % pcm.dtype)
+    wavfile.write(filename, sampling_rate, np.repeat(pcm.reshape((-1, 1)), 2, axis=1))
+
+
 def onehot_pixel_image(quantized_signal_batch, quantization_steps: int = 256) -> np.ndarray:
     """(B, T) tokens -> (B, Q, 1, T) float32 one-hot image (data.py:61-68).  The engine also takes
     the tokens directly (WaveNet.forward_causal_block), which skips this 134 MB tensor at B=8,T=16k."""

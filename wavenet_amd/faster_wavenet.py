@@ -795,6 +795,183 @@ class FasterWaveNet(WaveNet):
             return (res, ch) if ragged else (out, ch_all)
         return res if ragged else out
 
+    # -- one long utterance as overlapping segments of ONE batched call (wavenet_amd/fold.py states the rule) -----------------
+    def fold_capacity(self, tile=None, utterances=1):
+        """The segments per utterance that ``body="auto"`` aims at: what one launch decodes side by side -- ``wn_decoder_batch_max()``
+        on config 4's shape, else the device's compute units times the tile size (1 with tiles off) -- divided by
+        ``utterances``; at least 1."""
+        flags = _lib.default_exec_flags() if self.exec_flags is None else int(self.exec_flags)
+        if self._nine_workgroup_shape(flags):
+            cap = int(_lib.lib().wn_decoder_batch_max())
+        else:
+            n_cu = int(torch.cuda.get_device_properties(self.device).multi_processor_count)
+            tile = check_tile(self.batch_tile if tile is None else tile, self.params, "generate_folded")
+            cap = n_cu * max(1, pick_tile(2 * n_cu, n_cu, tile_fit(self.params)) if tile == "auto" else tile)
+        return max(1, cap // max(1, int(utterances)))
+
+    def generate_folded(self, n_samples, uniforms, body, overlap=None, warmup=None, initial_tokens=None, condition=None,
+                        local=None, local_phase=0, temperature=1.0, top_k=0, top_p=1.0, return_chosen: bool = False,
+                        return_segments: bool = False, tile=None, **other):
+        """One long utterance of a locally conditioned model, decoded as overlapping segments side by side and cross-faded:
+        ``fold.fold_plan(n_samples, body, overlap, warmup)`` cuts it, every segment is an utterance of ONE ragged
+        ``generate_batch`` call, and ``fold.unfold`` joins them -- here on the device, bit for bit.  Returns the (n_samples,)
+        int16 signal on the device: the values ``data.save_audio_file`` writes for tokens (``data.pcm_table``), cross-faded inside
+        the seams; ``data.save_pcm_file`` writes it.
+
+        ``n_samples`` an int and ``uniforms`` one row of >= n_samples float64: one utterance.  ``n_samples`` a sequence of N
+        lengths and ``uniforms`` a list of N rows (or an (N, >= max) array): N utterances, folded in the same call, and lists come
+        back.  ``initial_tokens``, ``condition``, ``local`` / ``local_phase`` and the sampling controls are ``generate_batch``'s,
+        per utterance; a segment repeats its utterance's speaker and controls.
+
+        ``body``: samples per segment, or ``"auto"`` = ``fold.auto_body(n, fold_capacity(tile, N), overlap, warmup)`` per
+        utterance.  ``overlap`` (default ``local_hop`` samples: one feature column) and ``warmup`` (default ``input_width``:
+        after that many generated samples no token of the silent window is inside the receptive field) are design defaults,
+        not tuned values; ``metrics.copy_synthesis(..., fold=)`` reads what a choice costs on a trained model.
+
+        The contract: segment u's row equals its own ``generate(e_u - s_u, U[s_u:e_u], initial_tokens=<the utterance's window
+        where s_u = 0, else silence>, local=<its columns>, local_phase=<its phase>, ...)`` call, tokens and ``chosen``, bit
+        for bit (``generate_batch``'s contract; the prefill runs once per segment at batch 1).  The uniforms are keyed by
+        position, so segment 0 draws what the sequential chain draws, a plan of one segment (``body >= n_samples``) is
+        ``pcm_table[generate(n_samples, uniforms, ...)]``, and both sides of a seam see the same draw at the same position.
+        (Segment 0's tokens ARE the chain's first ones where a projected feature row does not depend on the columns projected
+        with it -- ``open_stream``'s caveat about ``push``.)
+
+        ``return_chosen``: also the (n_samples,) float32 probability the owning segment gave each position's token.
+        ``return_segments``: also ``(plan, token rows, chosen rows)`` -- lists of those for N utterances.
+        ``tile``: ``generate_batch``'s.
+
+        Refused before any device work, naming the value: a model without local conditioning (nothing makes segments agree);
+        overlap > body, body < 1, warmup < 0; ``forced=`` (given samples are not part of a folded run); features that do not
+        cover a segment (the segment and both column counts are named).  Streams, ``--best-of`` and several GPUs are left out."""
+        from . import data, fold
+        what = "generate_folded"
+        if "forced" in other:
+            raise ValueError("%s: forced= is not an argument of this method (got %r): given samples would have to be cut and "
+                             "joined like drawn ones; use generate / generate_batch" % (what, other["forced"]))
+        if other:
+            raise TypeError("%s: unexpected argument %s" % (what, ", ".join(sorted(other))))
+        if not self.local_channels:
+            raise ValueError("%s: this model has no local conditioning (local_channels = 0): nothing makes segments of one "
+                             "utterance agree; use generate" % what)
+        single = isinstance(n_samples, (int, np.integer)) and not isinstance(n_samples, (bool, np.bool_))
+        if single:
+            ns, u_rows = _ragged_lengths([n_samples], [np.asarray(uniforms, dtype=np.float64).reshape(-1)])
+        else:
+            ns, u_rows = _ragged_lengths(n_samples, uniforms)
+        N, Q = len(ns), self.params.quantization_steps
+        if N < 1:
+            raise ValueError("%s: no utterance" % what)
+        O = self.local_hop if overlap is None else overlap
+        Wm = self.input_width if warmup is None else warmup
+        tile = check_tile(self.batch_tile if tile is None else tile, self.params, what)
+        if isinstance(body, str):
+            if body != "auto":
+                raise ValueError("%s: body= takes samples per segment or \"auto\", got %r" % (what, body))
+            fold.check_fold(max(1, O), O, Wm)                                     # (the body is not known yet)
+            cap = self.fold_capacity(tile, N)
+            bodies = [fold.auto_body(n, cap, O, Wm) for n in ns]
+        else:
+            bodies = [body] * N
+        plans = [fold.fold_plan(ns[i], bodies[i], O, Wm) for i in range(N)]
+        temps = sampling.per_utterance(temperature, N, "temperature")
+        top_ks = sampling.per_utterance(top_k, N, "top_k")
+        top_ps = sampling.per_utterance(top_p, N, "top_p")
+        for i in range(N):
+            sampling.check_controls(temps[i], top_ks[i], top_ps[i])
+        cids = None if condition is None else list(sampling.per_utterance(condition, N, "condition"))
+        prompts, which = self._batch_prompts(initial_tokens if not single or initial_tokens is None else
+                                             np.asarray(initial_tokens).reshape(-1), N)
+        Wd = len(prompts[0])
+        silence = silence_window(Q, Wd)
+        if isinstance(local, (list, tuple)):
+            if len(local) != N:
+                raise ValueError("%s: local= holds %d feature arrays for %d utterances" % (what, len(local), N))
+            per = list(local)
+        else:
+            per = [local] * N
+        phs = [int(v) for v in sampling.per_utterance(local_phase, N, "local_phase")]
+        seg_of, lengths, us, wins, feats, phases = [], [], [], [], [], []
+        for i in range(N):
+            f = per[i]
+            if f is None:
+                self._local_features(None, 1, 1, 0)                                   # raises: the model needs features
+            if not isinstance(f, torch.Tensor):
+                f = np.asarray(f, dtype=np.float32)
+            if len(f.shape) == 3 and f.shape[0] == 1:
+                f = f[0]
+            if len(f.shape) != 2 or int(f.shape[0]) != self.local_channels:
+                raise ValueError("%s: utterance %d: local= must be (%d, frames), got %s" % (what, i, self.local_channels, tuple(f.shape)))
+            if not 0 <= phs[i] < self.local_hop:
+                raise ValueError("%s: utterance %d: local_phase must lie in [0, local_hop = %d), got %d" % (what, i, self.local_hop, phs[i]))
+            cols = fold.check_columns(plans[i], Wd, phs[i], self.local_hop, self.local_interp, self.local_upsample,
+                                      int(f.shape[1]), what if single else "%s: utterance %d" % (what, i))
+            for g, (first, count, ph) in zip(plans[i].segments, cols):
+                part = f[:, first:first + count]
+                seg_of.append(i)
+                lengths.append(g.e - g.s)
+                us.append(u_rows[i][g.s:g.e])
+                wins.append(prompts[which[i]] if g.s == 0 else silence)
+                feats.append(part.contiguous() if isinstance(part, torch.Tensor) else np.ascontiguousarray(part))
+                phases.append(ph)
+        want = bool(return_chosen) or bool(return_segments)
+        rep = lambda xs: [xs[i] for i in seg_of]
+        # ---- device work from here on: every segment of every utterance in ONE ragged call ------------------------------------
+        got = self.generate_batch(lengths, us, initial_tokens=np.stack(wins), temperature=rep(temps), top_k=rep(top_ks),
+                                  top_p=rep(top_ps), condition=None if cids is None else rep(cids), local=feats,
+                                  local_phase=phases, return_chosen=want, tile=tile)
+        rows, chosen = got if want else (got, None)
+        table = data.pcm_table(Q)
+        pcm, own_ch, segs, at = [], [], [], 0
+        for i in range(N):
+            S = len(plans[i].segments)
+            mine, mine_ch = rows[at:at + S], (chosen[at:at + S] if want else None)
+            at += S
+            pcm.append(self._unfold(mine, plans[i], table))
+            if return_chosen:
+                own_idx = self._fold_indices(plans[i])[0]
+                own_ch.append(torch.cat(list(mine_ch))[torch.as_tensor(own_idx).to(self.device)])
+            segs.append((plans[i], list(mine), list(mine_ch) if want else None))
+        res = (pcm[0] if single else pcm,)
+        if return_chosen:
+            res += (own_ch[0] if single else own_ch,)
+        if return_segments:
+            res += (segs[0] if single else segs,)
+        return res if len(res) > 1 else res[0]
+
+    @staticmethod
+    def _fold_indices(plan):
+        """Indices into the concatenation of a plan's segment rows: (owner index of every position; the positions inside seams,
+        their tail-side and head-side indices, their seam index i) -- int64 numpy arrays."""
+        starts = np.cumsum([0] + [g.e - g.s for g in plan.segments])
+        own = np.concatenate([np.arange(g.a - g.s, g.b - g.s, dtype=np.int64) + starts[u] for u, g in enumerate(plan.segments)])
+        O, S = plan.overlap, len(plan.segments)
+        i = np.arange(O, dtype=np.int64)
+        ends = [plan.segments[u].b for u in range(S - 1)] if O else []
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros((0,), np.int64)
+        pos = cat([b + i for b in ends])
+        tail = cat([starts[u] + b - plan.segments[u].s + i for u, b in enumerate(ends)])
+        head = cat([starts[u + 1] + b - plan.segments[u + 1].s + i for u, b in enumerate(ends)])
+        return own, pos, tail, head, cat([i for _ in ends])
+
+    def _unfold(self, rows, plan, table):
+        """``fold.unfold`` on the device, bit for bit: ``rows`` the plan's int32 token rows, ``table`` ``data.pcm_table``'s values.
+        The lookup is ``wn_mulaw_decode`` with the table's values as floats; the cross-fade is elementwise float32 torch
+        operations in ``fold.unfold``'s order -- d = h - t; m = w * d; y = t + m, each rounded on its own -- then round half to
+        even and clip."""
+        from . import data, fold
+        dev = self.device
+        own, pos, tail, head, seam_i = (torch.as_tensor(a).to(dev) for a in self._fold_indices(plan))
+        vals = data.pcm_lookup_device(torch.cat([r.to(torch.int32) for r in rows]).contiguous(), table)
+        out = vals[own]
+        if pos.numel():
+            w = torch.as_tensor(fold.seam_weights(plan.overlap)).to(dev)[seam_i]
+            t, h = vals[tail], vals[head]
+            d = h - t
+            m = w * d
+            y = t + m
+            out[pos] = y
+        return torch.round(out).clamp_(-32768.0, 32767.0).to(torch.int16)
+
     def open_stream(self, utterances=1, initial_tokens=None, condition=None, local=None, local_phase=0, temperature=1.0,
                     top_k=0, top_p=1.0, return_chosen: bool = False, ring_frames=None, max_pull=4096, tile=None):
         """Streaming synthesis: a ``DecodeStream`` over ``utterances`` utterances -- features go in by ``push``, samples come out

@@ -70,7 +70,7 @@ def first_free_column(window: int, span: int, hop: int) -> int:
     return -(-(int(window) + int(span) // 2) // int(hop))
 
 
-def copy_synthesis(net, tokens, feats, condition, uniforms, mel, pitch, forced=None, **controls):
+def copy_synthesis(net, tokens, feats, condition, uniforms, mel, pitch, forced=None, fold=None, **controls):
     """Copy synthesis as ``generate --keep`` frames it, for a list of files at once.  ``tokens[u]``: file u's M_u tokens as
     training reads them; ``feats[u]``: its (F, columns) features as the network takes them, written for the file, so that they fit
     at phase 0; ``condition``: None or a class id per file; ``uniforms[u]``: M_u - W uniforms; ``mel`` / ``pitch``: a
@@ -82,6 +82,15 @@ def copy_synthesis(net, tokens, feats, condition, uniforms, mel, pitch, forced=N
     the drawn samples: the file's length, the file's column grid (column k is centred on sample k * hop).  A column whose
     analysis span touches the window is left out -- it would be made of the file's own samples and flatter the result: the mel
     columns compared are k >= ceil((W + win / 2) / hop), the pitch columns k >= ceil((W + S / 2) / hop), S = win + tau_max.
+
+    ``fold`` = (body, overlap, warmup), the arguments of ``FasterWaveNet.generate_folded`` (an int or ``"auto"``; ints or None for
+    the method's defaults): the M_u - W samples are drawn folded instead -- every file cut into overlapping segments, all segments
+    of all files in ONE batched call, cross-faded -- with the same uniforms, keyed by position.  What comes back is a signal, not
+    tokens, so BOTH sides are then analysed as floats, ``pcm / 32768`` through one table (``data.pcm_table``): the file as
+    ``table[tokens]``, the resynthesis as ``table[window]`` followed by the folded signal.  The same three figures, on the same
+    columns: what a body, an overlap and a warm-up cost on a trained model.  ``nats_per_sample`` is that of the segments owning
+    the positions; ``emitted`` holds the int16 signal; a row gains ``fold``: {"segments", "body", "overlap", "warmup",
+    "identical_seams"}.  Not with ``forced``.
 
     Returns one dict per file: ``samples`` (M_u), ``emitted`` (the M_u - W tokens), ``nats_per_sample`` (of the emitted samples,
     from ``chosen``), ``log_mel_distance_db``, ``mel_columns``, ``pitch_columns``, and ``f0_metrics``'s entries."""
@@ -96,14 +105,35 @@ def copy_synthesis(net, tokens, feats, condition, uniforms, mel, pitch, forced=N
             raise ValueError("copy_synthesis: file %d holds %d samples; the window takes %d and the decoder runs two more at least"
                              % (u, t.size, W))
     lengths = [t.size - W for t in toks]
+    if fold is not None:
+        from . import data
+        from . import fold as _fold
+        if forced is not None:
+            raise ValueError("copy_synthesis: fold= does not go with forced=: given samples are not part of a folded run")
+        body, overlap, warmup = fold
+        pcm, chosen, segs = net.generate_folded(lengths, [np.asarray(r, dtype=np.float64).reshape(-1) for r in uniforms], body, overlap,
+                                                warmup, initial_tokens=np.stack([t[:W] for t in toks]), condition=condition,
+                                                local=list(feats), return_chosen=True, return_segments=True, **controls)
+        table = torch.as_tensor(data.pcm_table(Q).astype(np.float32)).to(pcm[0].device)
+        as_float = lambda t: table[torch.as_tensor(t).to(table.device).long()]
+        emitted = pcm
+        files = [as_float(t) / 32768.0 for t in toks]
+        whole = [torch.cat([as_float(t[:W]), e.to(torch.float32)]) / 32768.0 for t, e in zip(toks, emitted)]
+        mels, pits = mel.batch(files + whole), pitch.batch(files + whole)
+        folds = [{"segments": len(plan.segments), "body": plan.body, "overlap": plan.overlap, "warmup": plan.warmup,
+                  "identical_seams": _fold.identical_seams([r.cpu().numpy() for r in rows], plan)} for plan, rows, _ in segs]
+        return _copy_rows(toks, emitted, chosen, mels, pits, W, mel, pitch, folds)
     rows, chosen = net.generate_batch(lengths, [np.asarray(r, dtype=np.float64).reshape(-1) for r in uniforms],
                                       initial_tokens=np.stack([t[:W] for t in toks]), condition=condition, local=list(feats),
                                       return_chosen=True, forced=forced, **controls)
     emitted = [r.to(torch.int32) for r in rows]
     whole = [torch.cat([torch.as_tensor(t[:W]).to(e.device), e]) for t, e in zip(toks, emitted)]
-    mels = mel.batch(toks + whole, Q)
-    pits = pitch.batch(toks + whole, Q)
-    out = []
+    return _copy_rows(toks, emitted, chosen, mel.batch(toks + whole, Q), pitch.batch(toks + whole, Q), W, mel, pitch)
+
+
+def _copy_rows(toks, emitted, chosen, mels, pits, W, mel, pitch, folds=None):
+    """``copy_synthesis``'s rows from the analysed columns: ``mels`` / ``pits`` hold the N files' arrays, then the N resyntheses'."""
+    N, out = len(toks), []
     for u in range(N):
         km = first_free_column(W, mel.win, mel.hop)
         kp = first_free_column(W, pitch.span, pitch.hop)
@@ -113,6 +143,8 @@ def copy_synthesis(net, tokens, feats, condition, uniforms, mel, pitch, forced=N
         f0 = f0_metrics(pits[u][:, kp:], pits[N + u][:, kp:])
         row["pitch_columns"] = f0.pop("frames")
         row.update(f0)
+        if folds is not None:
+            row["fold"] = folds[u]
         out.append(row)
     return out
 

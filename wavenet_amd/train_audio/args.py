@@ -164,6 +164,20 @@ _TILE_FLAGS = (
                              "weights -- auto, 2, 4, 8 or 16 (models of any shape but the specialised 32/256-channel one, which "
                              "ignores it); the samples are the same, bit for bit"),
 )
+# folded decoding (FasterWaveNet.generate_folded, wavenet_amd/fold.py; train_audio/generate.py fold_job): off, attributes of the
+# namespace only when given, checked by generate before the model is built
+_FOLD_FLAGS = (
+    (("--fold",), str, None, "generate --fast, on a locally conditioned checkpoint (--local, --local-dir, --from-wav): decode every "
+                             "utterance as overlapping segments of this many SECONDS side by side in one batched run and cross-fade "
+                             "them where they meet; auto sizes the segments to fill one launch.  The uniforms are those of the "
+                             "command without the flag, keyed by position: with SECONDS at least the utterance's length the file "
+                             "is the same, byte for byte.  --report gains \"fold\" per file.  Excludes --chunk-frames, --keep, "
+                             "--best-of and --rank.  evaluate --copy-synthesis: resynthesise folded"),
+    (("--fold-overlap",), float, None, "generate / evaluate --fold: SECONDS of every seam, decoded by both neighbours and "
+                                       "cross-faded (default: one feature column; at most --fold's)"),
+    (("--fold-warmup",), float, None, "generate / evaluate --fold: SECONDS a segment decodes from a silent window ahead of its "
+                                      "body and throws away (default: input_width samples)"),
+)
 # regenerating stretches of a recording (FasterWaveNet.generate(..., forced=...); train_audio/generate.py keep_job / keep_mask): off,
 # attributes of the namespace only when given, checked by generate before the model is built
 _KEEP_HELP = ("generate --fast: keep this recording and draw only the --redraw stretches: the file's first input_width samples are "
@@ -202,6 +216,7 @@ class Args(argparse.Namespace):
     keep, redraw = None, None
     chunk_frames, ring_frames = None, None
     tile = None
+    fold, fold_overlap, fold_warmup = None, None, None
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -211,7 +226,7 @@ def build_parser() -> argparse.ArgumentParser:
             ap.add_argument(*flags, action="store_true", default=default, help=text)
         else:
             ap.add_argument(*flags, type=typ, default=default, help=text)
-    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _PITCH_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _GPUS_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS:
+    for flags, typ, default, text in _EMA_FLAGS + _SPEAKER_FLAGS + _LOCAL_FLAGS + _MEL_FLAGS + _PITCH_FLAGS + _STORAGE_FLAGS + _CORPUS_FLAGS + _RESAMPLE_FLAGS + _GPUS_FLAGS + _LIKELIHOOD_FLAGS + _RANK_FLAGS + _STREAM_FLAGS + _TILE_FLAGS + _FOLD_FLAGS:
         assert getattr(Args, flags[0].lstrip("-").replace("-", "_")) == default
         if typ is None:
             ap.add_argument(*flags, action="store_true", default=argparse.SUPPRESS, help=text)

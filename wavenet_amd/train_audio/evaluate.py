@@ -3,6 +3,7 @@ teacher-forced, in nats and bits per sample -- the held-out number that tells ov
 
     python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model [--ema] [--json scores.json]
     python -m wavenet_amd.train_audio.evaluate -w held_out_wav -m model --copy-synthesis [--seconds S] [--seed N] [--json FILE]
+                                               [--fold SECONDS|auto [--fold-overlap SECONDS] [--fold-warmup SECONDS]]
 
 Files are read as training reads them (mu-law tokens, silence trimmed) and scored by ``WaveNet.score``.  The command has
 its own parser: it shares ``-g / -w / -m`` with train and generate and takes none of their other flags."""
@@ -55,10 +56,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--temperature", type=float, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
     ap.add_argument("--top-k", type=int, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
     ap.add_argument("--top-p", type=float, default=argparse.SUPPRESS, help="--copy-synthesis: as for generate")
+    # folded resynthesis (FasterWaveNet.generate_folded; metrics.copy_synthesis(..., fold=)): present in the namespace only when given
+    ap.add_argument("--fold", type=str, default=argparse.SUPPRESS, metavar="SECONDS|auto",
+                    help="--copy-synthesis: resynthesise every file folded -- cut into overlapping segments of SECONDS (auto: sized to "
+                         "fill one launch), all decoded side by side and cross-faded, as generate --fold does -- and print the same "
+                         "figures: what folding costs on this checkpoint")
+    ap.add_argument("--fold-overlap", type=float, default=argparse.SUPPRESS, metavar="SECONDS", help="--fold: as for generate")
+    ap.add_argument("--fold-warmup", type=float, default=argparse.SUPPRESS, metavar="SECONDS", help="--fold: as for generate")
     return ap
 
 
-COPY_FLAGS = ("seconds", "seed", "temperature", "top_k", "top_p")
+COPY_FLAGS = ("seconds", "seed", "temperature", "top_k", "top_p", "fold", "fold_overlap", "fold_warmup")
 COPY_KEYS = ("log_mel_distance_db", "f0_rmse_cents", "f0_gross_error", "vuv_error", "voiced_frames", "nats_per_sample")
 
 
@@ -74,7 +82,16 @@ def copy_synthesis_job(args):
     if _local.load_mel(args.model_dir) is None:
         raise SystemExit("evaluate: --copy-synthesis compares mel columns and needs the mel parameters of a checkpoint trained with "
                          "train --local-mel ({} has no \"mel\")".format(os.path.join(args.model_dir, _local.FILE)))
-    kw = {f: getattr(args, f) for f in given}
+    kw = {f: getattr(args, f) for f in given if not f.startswith("fold")}
+    if any(f.startswith("fold") for f in given):
+        # generate's own checks and conversion to samples (a folded run is a --fast one)
+        from . import generate as _generate
+        probe = argparse.Namespace(fast=True, chunk_frames=None, keep=None, best_of=1, model_dir=args.model_dir,
+                                   **{f: getattr(args, f) for f in given if f.startswith("fold")})
+        try:
+            kw["fold"] = _generate.fold_job(probe)
+        except SystemExit as e:
+            raise SystemExit(str(e).replace("generate:", "evaluate:", 1))
     if "seconds" in kw and not kw["seconds"] > 0:
         raise SystemExit("evaluate: --seconds S needs S > 0, got {}".format(kw["seconds"]))
     from .. import sampling
@@ -86,7 +103,7 @@ def copy_synthesis_job(args):
 
 
 def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=None, resample=False, verbose: bool = True,
-                       forced: bool = False, **controls):
+                       forced: bool = False, fold=None, **controls):
     """Resynthesise every .wav file of ``wav_dir`` (sorted by name) from its own features and compare the result with the file:
     ``metrics.copy_synthesis`` over all files, one ``generate_batch`` run (``net``: a ``FasterWaveNet`` whose checkpoint has
     "mel" in local.json).  A file is read as training reads it (``resample``: at the model's rate) and cut to ``seconds``; its
@@ -95,7 +112,8 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
     temperature, top_k, top_p.  A checkpoint with "pitch" in local.json: the network's features are ``acoustic.MelPitch``'s (mel
     rows, then pitch channels), while the figures keep comparing pure ``LogMel`` columns (the mel count) and ``Pitch`` rows of file
     and resynthesis.  ``forced``: every sample behind the window is given instead of drawn (the resynthesis is then the file and every
-    distance 0: features and metrics sit on one grid).  Returns ``{"files": [{"file", "samples", "log_mel_distance_db", "f0_rmse_cents",
+    distance 0: features and metrics sit on one grid).  ``fold``: None, or (body, overlap, warmup) in samples -- the resynthesis is
+    ``generate_folded``'s (``metrics.copy_synthesis(..., fold=)``) and every row of the table gains "fold".  Returns ``{"files": [{"file", "samples", "log_mel_distance_db", "f0_rmse_cents",
     "f0_gross_error", "vuv_error", "voiced_frames", "nats_per_sample"}, ...], "total": {...}}`` -- the total weighted by what each
     figure was averaged over (``metrics.total``: compared columns, frames voiced in both, emitted samples) -- and prints one line
     per file and one for the total unless ``verbose`` is off."""
@@ -142,9 +160,12 @@ def copy_synthesis_dir(net, params, wav_dir, local_dir=None, seconds=None, seed=
             np.random.seed(seed)
         uniforms = [np.random.random_sample(t.size - W) for t in tokens]
         fkw = {"forced": [t[W:] for t in tokens]} if forced else {}
+        if fold is not None:
+            fkw["fold"] = fold
         got = metrics.copy_synthesis(net, tokens, feats, cids, uniforms, _local.mel_analyser(rates[0], mels, local[1], mel["win"]),
                                      pitch, **fkw, **controls)
-    table = {"files": [dict([("file", fn), ("samples", r["samples"])] + [(k, r[k]) for k in COPY_KEYS]) for fn, r in zip(files, got)]}
+    table = {"files": [dict([("file", fn), ("samples", r["samples"])] + [(k, r[k]) for k in COPY_KEYS] +
+                            ([("fold", r["fold"])] if "fold" in r else [])) for fn, r in zip(files, got)]}
     whole = metrics.total(got)
     table["total"] = dict([("samples", whole["samples"])] + [(k, whole[k]) for k in COPY_KEYS])
     if verbose:

@@ -20,7 +20,11 @@ columns at a time go to the decoder, which draws what they allow; ``generated.wa
 chunk is printed.
 On a checkpoint trained with ``train --local-mel --local-pitch`` the features carry three pitch channels behind the mel rows
 (``acoustic.MelPitch`` makes them from a ``--from-wav`` recording, streamed or not), and ``--f0-scale S`` multiplies the pitch of
-every voiced column by S before the network sees it (``pitch.scale_f0``)."""
+every voiced column by S before the network sees it (``pitch.scale_f0``).
+``--fast --fold SECONDS|auto [--fold-overlap SECONDS] [--fold-warmup SECONDS]`` (a locally conditioned checkpoint; with ``--local``,
+``--local-dir`` or ``--from-wav``) decodes every utterance folded: cut into overlapping segments that run side by side in the one
+batched call and are cross-faded where they meet (``FasterWaveNet.generate_folded``, ``wavenet_amd/fold.py``), from the uniforms the
+command draws without the flag."""
 from __future__ import annotations
 
 import json
@@ -208,7 +212,7 @@ def _keep_best(tokens, chosen, K):
     return [np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in kept], ranked
 
 
-def write_report(path, filenames, tokens, ranked, K, distances=None):
+def write_report(path, filenames, tokens, ranked, K, distances=None, folds=None):
     """``--report``: per written file {"file", "samples", "nats_per_sample", "bits_per_sample"} (the emitted samples only: no
     prompt, no window) and, with ``--best-of K`` > 1, "candidates" (every candidate's nats per sample) and "kept"; then the
     total weighted by samples, in the layout of ``evaluate --json``.  ``distances`` (``--rank mel``: the kept candidates'): every
@@ -221,6 +225,8 @@ def write_report(path, filenames, tokens, ranked, K, distances=None):
             row["candidates"], row["kept"] = list(cand), int(k)
         if distances is not None:
             row["log_mel_distance_db"] = distances[i]
+        if folds is not None:
+            row["fold"] = folds[i]
         rows.append(row)
         nats += cand[k] * len(t) if len(t) else 0.0
         samples += int(len(t))
@@ -233,13 +239,86 @@ def write_report(path, filenames, tokens, ranked, K, distances=None):
     return table
 
 
+def fold_job(args):
+    """``generate --fold SECONDS|auto [--fold-overlap SECONDS] [--fold-warmup SECONDS]``: every check, made before a model is built.
+    Returns None without ``--fold``, else (body, overlap, warmup) in samples as ``FasterWaveNet.generate_folded`` takes them: the
+    body an int or ``"auto"``, the other two None where the flag was not given (the method's defaults)."""
+    given = vars(args)
+    if "fold" not in given:
+        extra = [f for f, k in (("--fold-overlap", "fold_overlap"), ("--fold-warmup", "fold_warmup")) if k in given]
+        if extra:
+            raise SystemExit("generate: {} sizes the segments of a folded run: give --fold SECONDS|auto".format(" and ".join(extra)))
+        return None
+    if not args.fast:
+        raise SystemExit("generate: --fold decodes the segments of an utterance in one batched run on the device: give --fast")
+    bad = [f for f, on in (("--chunk-frames", args.chunk_frames is not None), ("--keep", args.keep),
+                           ("--best-of {}".format(args.best_of), int(args.best_of) > 1), ("--rank", "rank" in given)) if on]
+    if bad:
+        raise SystemExit("generate: --fold does not go with {}: streams, given samples and ranked candidates are not cut into "
+                         "segments".format(", ".join(bad)))
+    if _local.load_config(args.model_dir) is None:
+        raise SystemExit("generate: --fold needs a locally conditioned checkpoint -- the features are what makes the segments of "
+                         "one utterance agree -- and {} is missing".format(os.path.join(args.model_dir, _local.FILE)))
+    sr = float(_model.load_params(args.model_dir).sampling_rate)
+
+    def samples(flag, text, least):
+        try:
+            sec = float(text)
+        except (TypeError, ValueError):
+            sec = float("nan")
+        if not math.isfinite(sec) or int(round(sec * sr)) < least:
+            raise SystemExit("generate: {} takes seconds ({} sample{} at least{}), got {!r}".format(
+                flag, least, "" if least == 1 else "s", ", or auto" if flag == "--fold" else "", text))
+        return int(round(sec * sr))
+    body = "auto" if args.fold == "auto" else samples("--fold", args.fold, 1)
+    overlap = samples("--fold-overlap", args.fold_overlap, 0) if "fold_overlap" in given else None
+    warmup = samples("--fold-warmup", args.fold_warmup, 0) if "fold_warmup" in given else None
+    if body != "auto" and overlap is not None and overlap > body:
+        raise SystemExit("generate: --fold-overlap {:g} is {} samples, more than the {} of --fold {}: a seam lies inside one body".format(
+            args.fold_overlap, overlap, body, args.fold))
+    return body, overlap, warmup
+
+
+def generate_folded_files(net, params, names, lengths, uniforms, prompts, feats, cids, fold, output_dir="generated_audio",
+                          temperature=1.0, top_k=0, top_p=1.0, report=None):
+    """``generate --fold``: ONE ``FasterWaveNet.generate_folded`` call over the files of the run -- file u of ``lengths[u]`` samples
+    behind the window ``prompts[u]``, drawn with ``uniforms[u]`` (the row the command draws without the flag) under
+    ``feats[u]`` as speaker ``cids[u]`` -- and ``<output_dir>/<names[u]>.wav`` per file (``data.save_pcm_file``).  ``fold``: what
+    ``fold_job`` returned.  ``report``: ``write_report``'s file; a file's nats are those of the segments that own its positions,
+    and its row gains "fold": {"segments", "body", "overlap", "warmup", "identical_seams"}.  Returns (filenames, signals)."""
+    from .. import fold as _fold
+    body, overlap, warmup = fold
+    start_time = time.time()
+    got = net.generate_folded(list(lengths), list(uniforms), body, overlap, warmup, initial_tokens=np.stack(prompts), condition=cids,
+                              local=list(feats), temperature=temperature, top_k=top_k, top_p=top_p, return_chosen=bool(report),
+                              return_segments=bool(report))
+    pcm = [p.cpu().numpy() for p in (got[0] if report else got)]
+    print("\ndone in {:.3f} sec".format(time.time() - start_time))
+    os.makedirs(output_dir, exist_ok=True)
+    filenames = ["{}/{}.wav".format(output_dir, name) for name in names]
+    for filename, signal in zip(filenames, pcm):
+        data.save_pcm_file(filename, signal, params.sampling_rate)
+    if report:
+        ranked = [(0, [sampling.chosen_nll(c)]) for c in got[1]]
+        folds = [{"segments": len(plan.segments), "body": plan.body, "overlap": plan.overlap, "warmup": plan.warmup,
+                  "identical_seams": _fold.identical_seams([r.cpu().numpy() for r in rows], plan)} for plan, rows, _ in got[2]]
+        write_report(report, filenames, pcm, ranked, 1, folds=folds)
+    return filenames, pcm
+
+
 def generate_audio(net, params, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
-                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, best_of=1, report=None, rank=None):
-    """``rank``: None (the candidates of ``best_of`` are ranked on their likelihood) or a ``MelRank``."""
+                   temperature=1.0, top_k=0, top_p=1.0, condition=None, local=None, best_of=1, report=None, rank=None, fold=None):
+    """``rank``: None (the candidates of ``best_of`` are ranked on their likelihood) or a ``MelRank``; ``fold``: None or what
+    ``fold_job`` returned (``generate_folded_files`` with the uniforms drawn here without it)."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     n = int(sampling_rate * generate_sec) - 1                       # generate.py:24: time_step runs 1 .. n
     silence = silence_window(Q, input_width_of(params))
+    if fold is not None and n > 0:
+        (filename,), (signal,) = generate_folded_files(net, params, ["generated"], [n], [np.random.random_sample(n)], [silence], [local],
+                                                       None if condition is None else [condition], fold, output_dir, temperature,
+                                                       top_k, top_p, report)
+        return filename, signal
     start_time = time.time()
     ranked = dists = None
     if fast and (best_of > 1 or report or rank is not None):
@@ -508,12 +587,13 @@ def read_prompt(path, params, rkw={}):
 
 def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate_sec=1.0, fast=False, output_dir="generated_audio",
                         temperature=1.0, top_k=0, top_p=1.0, conditions=None, locals_=None, best_of=1, report=None, rkw={},
-                        rank=None):
+                        rank=None, fold=None):
     """``len(prompt_files)`` utterances, utterance u continuing ``prompt_files[u]`` (None: silence), written to
     ``generated_000.wav`` ...; with ``fast`` one ``generate_batch`` run, otherwise the host loop per utterance.
     ``best_of`` = K > 1 (``fast`` only): N * K candidates in that run, row ``u * K + c`` candidate c of utterance u, the
     most likely one of every utterance written under the utterance's name; ``report``: ``write_report``'s file; ``rank``: None or a
-    ``MelRank`` (the candidate closest to its recording's columns is written instead)."""
+    ``MelRank`` (the candidate closest to its recording's columns is written instead); ``fold``: None or what ``fold_job``
+    returned (``generate_folded_files`` with the uniforms drawn here without it)."""
     Q = params.quantization_steps
     sampling.check_controls(temperature, top_k, top_p)
     N = len(prompt_files)
@@ -521,6 +601,10 @@ def generate_utterances(net, params, prompt_files, sampling_rate=48000, generate
     silence = silence_window(Q, input_width_of(params))
     read = {f: read_prompt(f, params, rkw) for f in set(prompt_files) if f is not None}
     prompts = np.stack([silence if f is None else read[f] for f in prompt_files])
+    if fold is not None and n > 0:
+        return generate_folded_files(net, params, ["generated_{:03d}".format(i) for i in range(N)], [n] * N,
+                                     list(np.random.random_sample((N, n))), list(prompts), locals_, conditions, fold, output_dir,
+                                     temperature, top_k, top_p, report)
     start_time = time.time()
     ranked = dists = None
     if fast and (best_of > 1 or report or rank is not None):
@@ -591,7 +675,7 @@ def directory_job(args, seconds_given, f0=None):
 
 
 def generate_directory(net, params, names, feats, lengths, cids, seed=None, output_dir="generated_audio", temperature=1.0,
-                       top_k=0, top_p=1.0, best_of=1, report=None):
+                       top_k=0, top_p=1.0, best_of=1, report=None, fold=None):
     """One ragged ``generate_batch`` run over the whole directory, from silence; ``<output_dir>/NAME.wav`` per feature file,
     each at its own length.  With a seed every file draws what its own ``generate --fast --local NAME.npy`` run draws.
     ``best_of`` = K > 1: K candidates per file in that run (``random_sample((K, n_file))`` behind the file's seed), the most
@@ -604,6 +688,9 @@ def generate_directory(net, params, names, feats, lengths, cids, seed=None, outp
         if seed is not None:
             np.random.seed(seed)
         uniforms.append(np.random.random_sample(n) if best_of == 1 else np.random.random_sample((best_of, n)))
+    if fold is not None:                   # (``fold_job``'s answer: the same files and uniforms, every file cut into segments)
+        return generate_folded_files(net, params, names, lengths, uniforms, [silence] * len(names), feats, cids, fold, output_dir,
+                                     temperature, top_k, top_p, report)
     start_time = time.time()
     if best_of == 1 and not report:
         rows = net.generate_batch(list(lengths), uniforms, initial_tokens=silence, temperature=temperature, top_k=top_k, top_p=top_p,
@@ -728,6 +815,7 @@ def main(argv=None):
     best_of, report = likelihood_job(args)
     chunk_frames, ring_frames = stream_job(args)
     tile = tile_job(args)
+    fold = fold_job(args)
     rank_mel = rank_job(args)
     f0 = f0_scale_job(args)
     seconds_given = _seconds_given(argv)
@@ -738,7 +826,8 @@ def main(argv=None):
         if tile is not None:
             net.batch_tile = tile
         return generate_directory(net, params, names, feats, lengths, cids, seed=args.seed, output_dir=args.output_dir,
-                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, best_of=best_of, report=report)
+                                  temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, best_of=best_of, report=report,
+                                  fold=fold)
     n_utt, prompt_files = _args.utterance_prompts(args)
     if kept is not None:
         n_utt = len(kept[0])
@@ -810,10 +899,11 @@ def main(argv=None):
         return generate_utterances(net, params, prompt_files, sampling_rate=params.sampling_rate, generate_sec=args.seconds,
                                    fast=args.fast, output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k,
                                    top_p=args.top_p, conditions=cids if table else None, locals_=feats, best_of=best_of,
-                                   report=report, rkw=read_kw(args, params), rank=rank)
+                                   report=report, rkw=read_kw(args, params), rank=rank, fold=fold)
     return generate_audio(net, params, sampling_rate=params.sampling_rate, generate_sec=args.seconds, fast=args.fast,
                           output_dir=args.output_dir, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
-                          condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report, rank=rank)
+                          condition=cids[0], local=None if feats is None else feats[0], best_of=best_of, report=report, rank=rank,
+                          fold=fold)
 
 
 if __name__ == "__main__":
